@@ -20,16 +20,21 @@ Other configs (so that the driver can time them; each prints the same one-line c
       outer-product statistics on the device, pooling, the RCCL all-reduce of 2p + d^2 + 1 doubles, one W and V draw
   c5  SVD (square-root) filter, d = 13, 10 000 series
 
-The default run (no flags, one GPU) also times -- a few steps each, AFTER the headline's timed region -- the same workload with
-the steady-state shortcut off (`value_full_recursion`) and with 5 % of the observations missing (`value_missing_0.05`), and the
-other BASELINE configurations (`secondary`: c3 in both sampler forms (and with the shared factors off, and at one GPU's share of 8), c4 with and without the shortcut, c4g, c5, the literal-Q1
-smoother), each with its own roofline by SURVEY 8d's units, so that the driver's record carries them.  `--no-secondary` skips that.
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 (`metric`, `value`, `unit`, `ms_per_step`
+= milliseconds of one timed step, `higher_is_better`, `dtype`, the configuration).  `--dump-outputs DIR` then also writes what the
+last timed step returned (see dump_outputs).
 
-Prints ONE JSON line on rank 0 with the extra objects
+`--full` adds what the headline does not need, each measured after the timed region:
+  config.steady_fraction -- the share of steps that took the steady-state shortcut (one more call with DLM_OPT_COUNT_STEPS)
   roofline     -- the dominant kernel against its roof (HBM bytes or fp64 MFMA flops per SURVEY 8d), timed with HIP
                   events on the engine's stream inside the timed region; `peak_measured` is a device copy on this box
   cpu_baseline -- the oracle's C port of the Scala operation sequence on the host cores (N = 1 only; the Scala/Breeze
-                  reference cannot run: no JVM on the box)
+                  reference cannot run: no JVM on the box).  `--no-cpu-baseline` skips it.
+  secondary    -- default configuration (c2, one GPU) only: a few steps each of the same workload with the steady-state shortcut
+                  off (`value_full_recursion`) and with 5 % of the observations missing (`value_missing_0.05`), and of the other
+                  BASELINE configurations (c3 in both sampler forms (and with the shared factors off, and at one GPU's share of 8),
+                  c4 with and without the shortcut, c4g, c5, the literal-Q1 smoother), each with its own roofline by SURVEY 8d's
+                  units.  `--no-secondary` skips them.
 """
 import argparse
 import json
@@ -215,6 +220,37 @@ def cpu_baseline(config, mat, p, y_host, budget_s=12.0):
     return out
 
 
+DUMP_BYTES = 60 << 20        # (the data of --dump-outputs: under 64 MB with the .npy headers)
+DUMP_SEED = 0xD1A5EED2
+
+
+def dump_outputs(dirname, per_series, whole, N):
+    """--dump-outputs: writes every array as DIR/<name>.npy in float64.  `per_series` arrays have one row per series; when all of it
+    would pass DUMP_BYTES, they are cut to the same sample of series, drawn with a fixed seed from N alone (so that two builds
+    write the same rows), and the sample's indices go to DIR/series_index.npy."""
+    import torch
+
+    def host(a):
+        return (a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).astype(np.float64)
+
+    per_series = {k: v for k, v in per_series.items() if v is not None}
+    whole = {k: host(v) for k, v in whole.items() if v is not None}
+    row = sum(8 * (v[0].numel() if isinstance(v, torch.Tensor) else np.asarray(v)[0].size) for v in per_series.values())
+    fixed = sum(v.nbytes for v in whole.values())
+    idx = None
+    if fixed + N * row > DUMP_BYTES:
+        k = max(1, min(N, (DUMP_BYTES - fixed) // (row + 8)))
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(N, size=k, replace=False))
+        whole["series_index"] = idx.astype(np.float64)
+    for name, v in per_series.items():
+        if idx is not None:
+            v = v.index_select(0, torch.as_tensor(idx, device=v.device)) if isinstance(v, torch.Tensor) else np.asarray(v)[idx]
+        whole[name] = host(v)
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in whole.items():
+        np.save(os.path.join(dirname, name + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -230,8 +266,12 @@ def main():
     ap.add_argument("--semantics", choices=["textbook", "literal-q1"], default="textbook",
                     help="c2/c4 smoother covariance: textbook J X J^T (default) or the reference's literal J X J (Smoothing.scala:44)")
     ap.add_argument("--sampler", choices=["reference", "simsmooth"], default="reference", help="c3: Smoothing.step backward sampler or the simulation smoother")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="default run: skip the extra configurations timed beside the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="also the steady-state step counts, the roofline, the CPU baseline and (default configuration) the secondary configurations")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full, default configuration: skip the extra configurations timed beside the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float64; rank 0's series; a fixed sample of series when larger than 64 MB)")
     ap.add_argument("--flags", type=int, default=0, help="extra DLM_OPT_* bits (e.g. 8 = force generic kernels)")
     args = ap.parse_args()
 
@@ -264,7 +304,7 @@ def main():
     line = run_one(args, ctx)
     plain = (args.config == "c2" and world == 1 and args.flags == 0 and args.missing == 0.0 and args.records == "dense" and
              args.semantics == "textbook" and args.series is None and args.T == 1000)
-    if rank == 0 and plain and not args.no_secondary:
+    if rank == 0 and plain and args.full and not args.no_secondary:
         add_secondary(line, args, ctx)
     if rank == 0:
         print(json.dumps(line), flush=True)
@@ -276,6 +316,7 @@ def variant_of(args, **kw):
     import copy
     a = copy.copy(args)
     a.no_cpu_baseline = True
+    a.dump_outputs = None
     for k, v in kw.items():
         setattr(a, k, v)
     return a
@@ -382,8 +423,12 @@ def run_one(args, ctx):
         def step():
             eng.filter_smooth(mat, p, y, flags=flags, out=out)
     elif cfg == "c5":
+        last = {}
+
         def step():
-            status.copy_(eng.svd_filter(mat, p, y, flags=flags)["status"])
+            last.clear()             # (the previous step's records are released before the call, as when they were not kept)
+            last.update(eng.svd_filter(mat, p, y, flags=flags))
+            status.copy_(last["status"])
     else:
         # pooled-parameter Gibbs over all ranks: the communicator id goes through the torch.distributed store
         if backend == "nccl" and ctx.get("allreduce") is not None:
@@ -450,20 +495,62 @@ def run_one(args, ctx):
 
     status_bad = int((status != 0).sum().item())
     value = job_series * T * steps / elapsed
-    # how many steps took a short (steady-state) path: one more call with DLM_OPT_COUNT_STEPS, outside the timed region
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step (before anything below runs the path again)
+        if cfg in ("c2", "c4"):
+            dump_outputs(args.dump_outputs, {"filt": out["filt"], "smooth": out["smooth"], "status": out["status"]}, {}, N)
+        elif cfg == "c5":
+            dump_outputs(args.dump_outputs, {"svd": last["svd"], "status": last["status"]}, {}, N)
+        else:
+            st = last["state"]
+            dump_outputs(args.dump_outputs, {"stats": st.stats, "status": st.status}, {"V": st.p.v, "W": st.p.w}, N)
+    # --full: how many steps took a short (steady-state) path: one more call with DLM_OPT_COUNT_STEPS, outside the timed region
     steady_fraction = None
-    if cfg in ("c2", "c4"):
+    if args.full and cfg in ("c2", "c4"):
         eng.filter_smooth(mat, p, y, flags=flags | _lib.OPT_COUNT_STEPS, out=out)
-    elif cfg == "c5":
+    elif args.full and cfg == "c5":
         eng.svd_filter(mat, p, y, flags=flags | _lib.OPT_COUNT_STEPS)
-    if cfg in ("c2", "c4", "c5"):
+    if args.full and cfg in ("c2", "c4", "c5"):
         cnt = eng.last_counters()
         steady_fraction = {"forward": cnt[0] / (float(N) * T), "backward": cnt[1] / (float(N) * T)}
         if cnt[2] or cnt[3]:
             steady_fraction["shared_covariance_series"] = cnt[2]
             steady_fraction["own_recursion_series"] = cnt[3]
 
-    if rank == 0:
+    if rank != 0:
+        return None
+    workloads = {
+        "c2": f"C2: seasonal DLM polynomial(1)|+|seasonal(24,6), d=13, p=1, {job_series} series x T={T}, fused filter+smooth (dlm_filter_smooth_batch)",
+        "c3": f"C3: the C2 model inside pooled d-Inverse-Gamma Gibbs, {job_series} series x T={T}: FFBS + on-device statistics + dlm_stats_pool + RCCL all-reduce + conjugate draw per iteration",
+        "c4": f"C4: 20 x polynomial(2) under |*|, d=40, p=20, {job_series} series x T={T}, fused filter+smooth",
+        "c4g": f"C4 Gibbs: the C4 model inside pooled Inverse-Wishart Gibbs, {job_series} series x T={T}: FFBS + outer-product statistics + dlm_stats_pool + RCCL all-reduce + W, V draws per iteration",
+        "c5": f"C5: SVD (square-root) filter on the C2 model, d=13, {job_series} series x T={T} (dlm_svd_filter_batch)",
+    }
+    line = {
+        "metric": {"c2": "Kalman filter+smooth series*timesteps/sec", "c3": "Gibbs (FFBS + conjugate step) series*timesteps/sec",
+                   "c4": "Kalman filter+smooth series*timesteps/sec (d=40)", "c4g": "Gibbs (FFBS + Inverse-Wishart step) series*timesteps/sec (d=40)",
+                   "c5": "SVD filter series*timesteps/sec"}[cfg],
+        "value": value, "unit": "series*timesteps/s", "n_gpus": world, "steps": steps, "warmup": warmup,
+        "ms_per_step": elapsed / steps * 1e3, "step_ms": step_ms, "higher_is_better": True,
+        "scaling": "weak" if (world > 1 and args.scaling == "weak") else "strong",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": workloads[cfg], "series_total": job_series, "series_per_gpu": N, "T": T, "d": d, "p": q,
+                   "variant": variant, "records": args.records if cfg == "c2" else "dense",
+                   "semantics": ({"textbook": "textbook (S = C - J (R+ - S+) J^T)", "literal-q1": "literal-q1 (Smoothing.scala:44: J X J)"}[args.semantics]
+                                 if cfg in ("c2", "c4") else ("Smoothing.step backward sampler" if cfg in ("c3", "c4g") and args.sampler == "reference"
+                                                              else "simulation smoother" if cfg in ("c3", "c4g") else "sqrt(W) in the time update (Q2 off)")),
+                   "missing_fraction": args.missing,
+                   "steady_state_steps": "off (DLM_OPT_NO_STEADY)" if flags & _lib.OPT_NO_STEADY else "on where the covariance recursion has settled within 1e-12 (settle_test, DESIGN.md 4.5)",
+                   "steady_fraction": steady_fraction,
+                   "parallelism": f"series-sharded x{world}" + (", one RCCL all-reduce of %d doubles per iteration (comm world %d)" % (2 * q + (d if cfg == "c3" else d * d) + 1, comm_world)
+                                                                if cfg in ("c3", "c4g") else ", no collective")},
+        "status_nonzero_series": status_bad,
+    }
+    if cfg in ("c3", "c4g"):
+        st = last["state"]
+        line["config"]["pooled_V"] = float(np.diag(st.p.v)[0])
+        line["config"]["pooled_W_first"] = [float(x) for x in np.diag(st.p.w)[:3]]
+    if args.full:
         moved_note = None
         route_note = None
         f_ms, b_ms = float(np.mean(fwd_ms)), float(np.mean(bwd_ms))
@@ -531,37 +618,11 @@ def run_one(args, ctx):
         short = {"sparse16": "sp16", "mfma16": "mfma16", "wave-mfma": "w48", "tiled-mfma": "tiled", "sparse16-sampler": "sp16", "sparse16-rts": "rts16", "wave-sampler": "w48", "wave-simsmooth": "w48",
                  "sparse16-simsmooth": "sp16", "svd-jacobi": "", "sparse16-sampler-shared": "sp16", "wave-sampler-shared": "w48", "sparse16-rts-shared": "rts16"}.get(variant, variant)
         kname = (names[1] if dom_is_bwd else names[0]) + short
-        workloads = {
-            "c2": f"C2: seasonal DLM polynomial(1)|+|seasonal(24,6), d=13, p=1, {job_series} series x T={T}, fused filter+smooth (dlm_filter_smooth_batch)",
-            "c3": f"C3: the C2 model inside pooled d-Inverse-Gamma Gibbs, {job_series} series x T={T}: FFBS + on-device statistics + dlm_stats_pool + RCCL all-reduce + conjugate draw per iteration",
-            "c4": f"C4: 20 x polynomial(2) under |*|, d=40, p=20, {job_series} series x T={T}, fused filter+smooth",
-            "c4g": f"C4 Gibbs: the C4 model inside pooled Inverse-Wishart Gibbs, {job_series} series x T={T}: FFBS + outer-product statistics + dlm_stats_pool + RCCL all-reduce + W, V draws per iteration",
-            "c5": f"C5: SVD (square-root) filter on the C2 model, d=13, {job_series} series x T={T} (dlm_svd_filter_batch)",
-        }
-        line = {
-            "metric": {"c2": "Kalman filter+smooth series*timesteps/sec", "c3": "Gibbs (FFBS + conjugate step) series*timesteps/sec",
-                       "c4": "Kalman filter+smooth series*timesteps/sec (d=40)", "c4g": "Gibbs (FFBS + Inverse-Wishart step) series*timesteps/sec (d=40)",
-                       "c5": "SVD filter series*timesteps/sec"}[cfg],
-            "value": value, "unit": "series*timesteps/s", "n_gpus": world, "steps": steps, "warmup": warmup,
-            "ms_per_step": elapsed / steps * 1e3, "step_ms": step_ms, "higher_is_better": True,
-            "scaling": "weak" if (world > 1 and args.scaling == "weak") else "strong",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": workloads[cfg], "series_total": job_series, "series_per_gpu": N, "T": T, "d": d, "p": q,
-                       "variant": variant, "records": args.records if cfg == "c2" else "dense",
-                       "semantics": ({"textbook": "textbook (S = C - J (R+ - S+) J^T)", "literal-q1": "literal-q1 (Smoothing.scala:44: J X J)"}[args.semantics]
-                                     if cfg in ("c2", "c4") else ("Smoothing.step backward sampler" if cfg in ("c3", "c4g") and args.sampler == "reference"
-                                                                  else "simulation smoother" if cfg in ("c3", "c4g") else "sqrt(W) in the time update (Q2 off)")),
-                       "missing_fraction": args.missing,
-                       "steady_state_steps": "off (DLM_OPT_NO_STEADY)" if flags & _lib.OPT_NO_STEADY else "on where the covariance recursion has settled within 1e-12 (settle_test, DESIGN.md 4.5)",
-                       "steady_fraction": steady_fraction,
-                       "parallelism": f"series-sharded x{world}" + (", one RCCL all-reduce of %d doubles per iteration (comm world %d)" % (2 * q + (d if cfg == "c3" else d * d) + 1, comm_world)
-                                                                    if cfg in ("c3", "c4g") else ", no collective")},
-            "roofline": {"bound": bound, "kernel": kname, "achieved": achieved, "peak": peak, "unit": unit,
-                         "frac": achieved / peak, "traffic": None,
-                         "algorithmic_units_per_launch": dom_u * nt, "avg_launch_ms": dom_ms,
-                         "forward_ms": f_ms, "backward_ms": b_ms},
-            "status_nonzero_series": status_bad,
-        }
+        line["config"]["variant"] = variant      # (the kernels that ran: the step counts show whether the tables were made)
+        line["roofline"] = {"bound": bound, "kernel": kname, "achieved": achieved, "peak": peak, "unit": unit,
+                            "frac": achieved / peak, "traffic": None,
+                            "algorithmic_units_per_launch": dom_u * nt, "avg_launch_ms": dom_ms,
+                            "forward_ms": f_ms, "backward_ms": b_ms}
         if route_note:
             line["config"]["route_note"] = route_note
         if cfg == "c2" and variant == "sparse16-rts-shared" and dom_is_bwd:
@@ -603,14 +664,9 @@ def run_one(args, ctx):
                 line["roofline"]["peak_measured_note"] = ("peak_measured is a device copy (one read stream + one write stream); a kernel that mostly writes is not bound by it: "
                                                           "write-only kernels reach 5.6-6.2 TB/s on this pool (tools/micro, profiles/r04_notes.md section 9)")
             line["roofline"]["path_GBps"] = (fwd_u + bwd_u) * nt / ((f_ms + b_ms) * 1e-3) / 1e9
-        if cfg in ("c3", "c4g"):
-            st = last["state"]
-            line["config"]["pooled_V"] = float(np.diag(st.p.v)[0])
-            line["config"]["pooled_W_first"] = [float(x) for x in np.diag(st.p.w)[:3]]
         if not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(cfg, mat, p, y[: min(N, 4096)].cpu().numpy())
-        return line
-    return None
+    return line
 
 
 if __name__ == "__main__":

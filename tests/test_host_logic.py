@@ -340,3 +340,28 @@ def test_the_oracle_is_used_from_tests_smoke_and_the_cpu_baseline_only():
         tree, hits = oracle_imports(os.path.join(root, f))
         spans = [(n.lineno, n.end_lineno) for n in ast.walk(tree) if isinstance(n, ast.FunctionDef) and n.name in allowed]
         assert hits and all(any(a <= h <= b for a, b in spans) for h in hits), (f, hits, spans)
+
+
+def test_bench_dump_outputs_writes_a_fixed_sample_under_64_mb(tmp_path):
+    """bench.py --dump-outputs: arrays with one row per series are cut to the same seeded sample of series when the whole would pass
+    64 MB (rows as given, float64), the sample does not change from run to run, and small outputs are written whole."""
+    import torch
+    from bench import dump_outputs
+    N = 4000
+    rec = torch.arange(N, dtype=torch.float64)[:, None, None].expand(N, 101, 182)     # row n holds n; 590 MB if written whole
+    status = torch.arange(N, dtype=torch.int32)
+    for d in (tmp_path / "a", tmp_path / "b"):
+        dump_outputs(str(d), {"filt": rec, "smooth": 2 * rec, "status": status}, {"V": np.eye(1)}, N)
+    total = sum(f.stat().st_size for f in (tmp_path / "a").iterdir())
+    assert total <= 64 << 20
+    idx = np.load(tmp_path / "a" / "series_index.npy")
+    np.testing.assert_array_equal(idx, np.load(tmp_path / "b" / "series_index.npy"))
+    assert 1 < len(idx) < N and np.all(np.diff(idx) > 0)
+    filt = np.load(tmp_path / "a" / "filt.npy")
+    assert filt.dtype == np.float64 and filt.shape == (len(idx), 101, 182)
+    np.testing.assert_array_equal(filt[:, 0, 0], idx)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "smooth.npy")[:, 5, 7], 2 * idx)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "status.npy"), idx)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "V.npy"), np.eye(1))
+    dump_outputs(str(tmp_path / "c"), {"stats": torch.ones(50, 16), "status": None}, {"W": np.eye(13)}, 50)
+    assert sorted(f.name for f in (tmp_path / "c").iterdir()) == ["W.npy", "stats.npy"]

@@ -2,14 +2,14 @@
 # every bench configuration once (run on the GPU box): tools/bench_all.sh <outdir>
 out=${1:-gpurun_out/bench_all}; mkdir -p $out
 set -e
-python bench.py > $out/bench_c2.json 2> $out/bench_c2.err
-python bench.py --records packed --no-cpu-baseline > $out/bench_c2_packed.json 2> $out/bench_c2_packed.err
-python bench.py --missing 0.05 --no-cpu-baseline > $out/bench_c2_missing.json 2> $out/bench_c2_missing.err
-python bench.py --semantics literal-q1 --no-cpu-baseline --steps 3 --warmup 1 > $out/bench_c2_literal.json 2> $out/bench_c2_literal.err
-python bench.py --config c3 > $out/bench_c3.json 2> $out/bench_c3.err
-python bench.py --config c3 --sampler simsmooth --no-cpu-baseline > $out/bench_c3_sim.json 2> $out/bench_c3_sim.err
-python bench.py --config c4 > $out/bench_c4.json 2> $out/bench_c4.err
-python bench.py --config c5 > $out/bench_c5.json 2> $out/bench_c5.err
+python bench.py --full > $out/bench_c2.json 2> $out/bench_c2.err
+python bench.py --full --records packed --no-cpu-baseline > $out/bench_c2_packed.json 2> $out/bench_c2_packed.err
+python bench.py --full --missing 0.05 --no-cpu-baseline > $out/bench_c2_missing.json 2> $out/bench_c2_missing.err
+python bench.py --full --semantics literal-q1 --no-cpu-baseline --steps 3 --warmup 1 > $out/bench_c2_literal.json 2> $out/bench_c2_literal.err
+python bench.py --full --config c3 > $out/bench_c3.json 2> $out/bench_c3.err
+python bench.py --full --config c3 --sampler simsmooth --no-cpu-baseline > $out/bench_c3_sim.json 2> $out/bench_c3_sim.err
+python bench.py --full --config c4 > $out/bench_c4.json 2> $out/bench_c4.err
+python bench.py --full --config c5 > $out/bench_c5.json 2> $out/bench_c5.err
 for f in $out/bench_*.json; do python - "$f" <<'PY'
 import json, sys
 j = json.loads([l for l in open(sys.argv[1]).read().splitlines() if l.startswith("{")][-1]); r = j["roofline"]

@@ -3,7 +3,7 @@
 name=$1; shift
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$name; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $O/kt -o run --output-format csv -- python3 $R/bench.py --no-cpu-baseline "$@" > $O/bench.json 2> $O/kt.err
+rocprofv3 --kernel-trace --stats -d $O/kt -o run --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline "$@" > $O/bench.json 2> $O/kt.err
 cd $R
 f=$(find $O/kt -name "*kernel_stats.csv" | head -1)
 cp $f $O/kernel_stats.csv

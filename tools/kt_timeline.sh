@@ -4,7 +4,7 @@
 name=$1; shift
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$name; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace -d $O/kt -o run --output-format csv -- python3 $R/bench.py --no-cpu-baseline --no-secondary "$@" > $O/bench.json 2> $O/err.txt
+rocprofv3 --kernel-trace -d $O/kt -o run --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline --no-secondary "$@" > $O/bench.json 2> $O/err.txt
 cd $R
 python3 - "$O" <<'PY'
 import csv, glob, sys, json

@@ -3,11 +3,11 @@
 set -e
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_final; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $O/kt -o run --output-format csv -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/kt.err
-rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/pmc_fetch -o run --output-format csv -- python3 $R/bench.py --steps 2 --warmup 0 --no-cpu-baseline > $O/pmc_fetch.log 2>&1
-rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/pmc_write -o run --output-format csv -- python3 $R/bench.py --steps 2 --warmup 0 --no-cpu-baseline > $O/pmc_write.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/kt -o run --output-format csv -- python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/kt.err
+rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/pmc_fetch -o run --output-format csv -- python3 $R/bench.py --full --steps 2 --warmup 0 --no-cpu-baseline > $O/pmc_fetch.log 2>&1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/pmc_write -o run --output-format csv -- python3 $R/bench.py --full --steps 2 --warmup 0 --no-cpu-baseline > $O/pmc_write.log 2>&1
 cd $R
-python3 bench.py --steps 10 --warmup 3 > $O/bench_plain.json 2> $O/bench_plain.err
+python3 bench.py --full --steps 10 --warmup 3 > $O/bench_plain.json 2> $O/bench_plain.err
 python3 - <<PY
 import csv, glob, json, collections
 O = "$O"

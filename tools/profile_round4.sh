@@ -13,9 +13,9 @@ for c in "${CONFIGS[@]}"; do
   if ! echo "$tag" | grep -Eq "$FILTER"; then continue; fi
   echo "== $c" >&2
   ST="--steps 3 --warmup 1"; if [ "$tag" = "c2" ]; then ST="--steps 10 --warmup 3"; fi   # (the headline: the protocol of the driver-visible line)
-  rocprofv3 --kernel-trace --stats -d $O/kt_$tag -o run --output-format csv -- python3 $R/bench.py --config $c $ST --no-cpu-baseline --no-secondary > $O/bench_${tag}_under_rocprof.json 2> $O/kt_$tag.err
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/fetch_$tag -o run --output-format csv -- python3 $R/bench.py --config $c --steps 2 --warmup 0 --no-cpu-baseline --no-secondary > $O/fetch_$tag.log 2>&1
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/write_$tag -o run --output-format csv -- python3 $R/bench.py --config $c --steps 2 --warmup 0 --no-cpu-baseline --no-secondary > $O/write_$tag.log 2>&1
+  rocprofv3 --kernel-trace --stats -d $O/kt_$tag -o run --output-format csv -- python3 $R/bench.py --full --config $c $ST --no-cpu-baseline --no-secondary > $O/bench_${tag}_under_rocprof.json 2> $O/kt_$tag.err
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/fetch_$tag -o run --output-format csv -- python3 $R/bench.py --full --config $c --steps 2 --warmup 0 --no-cpu-baseline --no-secondary > $O/fetch_$tag.log 2>&1
+  rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/write_$tag -o run --output-format csv -- python3 $R/bench.py --full --config $c --steps 2 --warmup 0 --no-cpu-baseline --no-secondary > $O/write_$tag.log 2>&1
 done
 cd $R
 python3 - "$O" <<'PY'
@@ -43,7 +43,7 @@ for d in glob.glob(O + "/kt_*"):
         rows = list(csv.reader(open(st[0])))
         keep = [rows[0]] + [r for r in rows[1:] if r and "dlm" in r[0]]
         csv.writer(open(O + "/r04_kernel_stats_" + d.split("kt_")[-1] + ".csv", "w")).writerows(keep)
-out = {"note": ("rocprofv3 --pmc, FETCH_SIZE and WRITE_SIZE in separate passes of `python3 bench.py --config <c> --steps 2 --warmup 0 --no-cpu-baseline --no-secondary` "
+out = {"note": ("rocprofv3 --pmc, FETCH_SIZE and WRITE_SIZE in separate passes of `python3 bench.py --full --config <c> --steps 2 --warmup 0 --no-cpu-baseline --no-secondary` "
                 "(tools/profile_round4.sh); per-launch averages per (kernel, grid size).  FETCH_SIZE / WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE reports 1/2 of the "
                 "bytes of a coalesced streaming read (MI355X_MICROARCH.md, HBM): read bytes = 2 * FETCH_SIZE * 1024.  source_sha16: sha256[:16] of the .hip file that "
                 "defines the kernel when the counters were taken -- bench.py drops a figure whose source has changed since."),

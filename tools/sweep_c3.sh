@@ -3,7 +3,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$1; mkdir -p $O
 for n in 320 640 1250 2500 5000 10000; do
   for f in 2097152 67108864; do
-    python3 $R/bench.py --config c3 --series $n --steps 5 --warmup 2 --no-secondary --no-cpu-baseline --flags $f > $O/c3_${n}_$f.json 2>> $O/err.txt
+    python3 $R/bench.py --full --config c3 --series $n --steps 5 --warmup 2 --no-secondary --no-cpu-baseline --flags $f > $O/c3_${n}_$f.json 2>> $O/err.txt
     python3 - $O/c3_${n}_$f.json $n $f <<'PY'
 import json, sys
 j = json.load(open(sys.argv[1]))

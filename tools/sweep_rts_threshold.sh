@@ -4,7 +4,7 @@
 O=gpurun_out/r04/thr; mkdir -p $O
 for n in 1250 2500 5000 6500 7500 8192 10000 20000; do
   for f in 2097152 268435456; do
-    python bench.py --series $n --flags $f --steps 10 --warmup 3 --no-cpu-baseline --no-secondary > $O/n${n}_f$f.json 2>/dev/null
+    python bench.py --full --series $n --flags $f --steps 10 --warmup 3 --no-cpu-baseline --no-secondary > $O/n${n}_f$f.json 2>/dev/null
   done
 done
 python - <<'PY'

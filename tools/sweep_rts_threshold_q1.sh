@@ -4,7 +4,7 @@
 O=gpurun_out/r04/thrq1; mkdir -p $O
 for n in 64 256 512 1024 2048 4096; do
   for f in 2097152 268435456; do
-    python bench.py --semantics literal-q1 --series $n --flags $f --steps 10 --warmup 3 --no-cpu-baseline --no-secondary > $O/n${n}_f$f.json 2>/dev/null
+    python bench.py --full --semantics literal-q1 --series $n --flags $f --steps 10 --warmup 3 --no-cpu-baseline --no-secondary > $O/n${n}_f$f.json 2>/dev/null
   done
 done
 python - <<'PY'

@@ -8,7 +8,7 @@ res = {}
 for n in (10000, 5000, 2500, 2048, 1250, 1025, 1024, 512):
     best = None
     for rep in range(2):
-        out = subprocess.run([sys.executable, "bench.py", "--series", str(n), "--steps", "20", "--warmup", "3", "--no-cpu-baseline"], capture_output=True, text=True).stdout
+        out = subprocess.run([sys.executable, "bench.py", "--full", "--series", str(n), "--steps", "20", "--warmup", "3", "--no-cpu-baseline"], capture_output=True, text=True).stdout
         d = json.loads(out.strip().splitlines()[-1])
         if best is None or d["ms_per_step"] < best["ms_per_step"]:
             best = d
@@ -16,7 +16,7 @@ for n in (10000, 5000, 2500, 2048, 1250, 1025, 1024, 512):
                    "series_steps_per_s": best["value"]}
     print(n, res[str(n)], flush=True)
 t1 = res["10000"]["ms_per_call"]
-out = {"note": "python bench.py --series N --steps 20 --warmup 3 --no-cpu-baseline on ONE MI355X, best of 2 (tools/sweep_small4.sh): the share of one GPU of the 10 000-series strong-scaling job at 1 / 2 / 4 / 8 GPUs; projected speed-up = t(10 000) / t(10 000 / G).  No 8-GPU node was available to the build.  1024 / 1025 / 2048 / 512: one wave per series on 1024 SIMDs.",
+out = {"note": "python bench.py --full --series N --steps 20 --warmup 3 --no-cpu-baseline on ONE MI355X, best of 2 (tools/sweep_small4.sh): the share of one GPU of the 10 000-series strong-scaling job at 1 / 2 / 4 / 8 GPUs; projected speed-up = t(10 000) / t(10 000 / G).  No 8-GPU node was available to the build.  1024 / 1025 / 2048 / 512: one wave per series on 1024 SIMDs.",
        "runs": res,
        "projected_speedup": {"2": t1 / res["5000"]["ms_per_call"], "4": t1 / res["2500"]["ms_per_call"], "8": t1 / res["1250"]["ms_per_call"]}}
 json.dump(out, open("gpurun_out/r04_small_batch.json", "w"), indent=1)
