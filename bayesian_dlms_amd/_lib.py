@@ -20,6 +20,7 @@ OPT_MODEL_UNCHANGED = 1 << 8
 OPT_COUNT_STEPS = 1 << 9
 OPT_TRUST_MODEL_UNCHANGED = 1 << 10
 OPT_LOGLIK_LITERAL_Q7 = 1 << 11
+OPT_STUDENTT_LITERAL = 1 << 12
 OPT_NO_LANE = 1 << 16
 OPT_NO_SAMPLER16 = 1 << 17
 OPT_NO_WAVE = 1 << 18
@@ -56,6 +57,11 @@ class ParamsDesc(ctypes.Structure):
                 ("v_tstride", ctypes.c_int64), ("w_tstride", ctypes.c_int64)]
 
 
+class StudentTPrior(ctypes.Structure):
+    _fields_ = [("prior_nu_rate", ctypes.c_double), ("prop_nu_size", ctypes.c_double),
+                ("prior_w_shape", ctypes.c_double), ("prior_w_scale", ctypes.c_double)]
+
+
 class Options(ctypes.Structure):
     _fields_ = [("flags", ctypes.c_uint32), ("mem", ctypes.c_int32),
                 ("seed", ctypes.c_uint64), ("series_offset", ctypes.c_uint64)]
@@ -87,6 +93,8 @@ SYMBOLS = [
     ("dlm_simulate_batch", ctypes.c_int, [_V, _MP, _PP, _OP, _V, _V, _V]),
     ("dlm_dinvgamma_step_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _V, ctypes.c_double,
                                                 ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_uint64, _OP, _V, _V]),
+    ("dlm_studentt_step_batch", ctypes.c_int, [_V, _MP, _V, _V, _V, ctypes.POINTER(StudentTPrior), _V, _V, ctypes.c_uint64, _OP,
+                                               _V, _V, _V, _V, _V, _V, _V]),
     ("dlm_ou_ffbs_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, ctypes.c_int64, _V, ctypes.c_int64,
                                          _V, _OP, _V, _V, _V]),
     ("dlm_ar1_ffbs_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, ctypes.c_int64, _V, ctypes.c_int64,

@@ -156,6 +156,8 @@ class Stager {
   void out(T** field, T* p, size_t count) { add((void**)field, (void*)p, count * sizeof(T), false, true); }
   template <class T>
   void zeroed_out(T** field, T* p, size_t count) { add((void**)field, (void*)p, count * sizeof(T), false, true, true); }
+  template <class T>
+  void inout(T** field, T* p, size_t count) { add((void**)field, (void*)p, count * sizeof(T), true, true); }
 
   int commit() {
     if (host_) {
@@ -1008,6 +1010,56 @@ int dlm_dinvgamma_step_batch(dlm_engine* e, int32_t d, int32_t p, int32_t N, con
   e->variant = "dinvgamma-step";
   HIP_TRY(e, dlm::launch_dinvgamma_step(d, p, N, k.stats, alpha_v, beta_v, alpha_w, beta_w, opts->seed, opts->series_offset,
                                         iteration, k.V, k.W, e->stream));
+  return st.finish(opts->flags & DLM_OPT_ASYNC);
+}
+
+int dlm_studentt_step_batch(dlm_engine* e, const dlm_model_desc* model, const double* y, const double* theta,
+                            const double* stats, const dlm_studentt_prior* prior, const double* scale_in,
+                            const int32_t* nu_in, uint64_t iteration, const dlm_options* opts, double* v_out,
+                            double* scale_out, int32_t* nu_out, double* W_out, int32_t* accepted,
+                            double* loglik, int32_t* status) {
+  if (!e) return DLM_ERR_ARG;
+  if (!model || !opts || !prior) return fail(e, DLM_ERR_ARG, "null descriptor");
+  if (opts->mem != DLM_MEM_DEVICE && opts->mem != DLM_MEM_HOST) return fail(e, DLM_ERR_ARG, "opts->mem");
+  const int d = model->d, T = model->T, N = model->N;
+  if (d < 1 || T < 1 || N < 1 || model->p < 1) return fail(e, DLM_ERR_ARG, "d, p, T, N must be >= 1");
+  if (model->p != 1) return fail(e, DLM_ERR_UNSUPPORTED, "the Student-t step is univariate (StudentTGibbs.scala reads y(0) and v(0,0)): p must be 1");
+  if (d > 64) return fail(e, DLM_ERR_UNSUPPORTED, "d is limited to 64 in this build");
+  if (T > 0x1FFFFC) return fail(e, DLM_ERR_UNSUPPORTED, "T must stay below 2^21 - 4 (the Philox counter's slot field)");
+  if (!model->F || (model->f_stride != 0 && model->f_stride != (int64_t)d)) return fail(e, DLM_ERR_ARG, "F required; f_stride must be 0 or d");
+  const bool literal = (opts->flags & DLM_OPT_STUDENTT_LITERAL) != 0;
+  if (literal && model->f_stride)
+    return fail(e, DLM_ERR_UNSUPPORTED, "DLM_OPT_STUDENTT_LITERAL pairs y_t with theta_{t-1} and F at ITS time (SURVEY Q11): t0 - 1 is not in a time-varying F table");
+  if (!y || !theta || !stats || !scale_in || !nu_in || !v_out || !scale_out || !nu_out || !W_out || !accepted)
+    return fail(e, DLM_ERR_ARG, "y, theta, stats, scale_in, nu_in, v_out, scale_out, nu_out, W_out and accepted are required");
+  if (!(prior->prior_nu_rate > 0.0 && prior->prop_nu_size > 0.0 && prior->prior_w_shape > 0.0 && prior->prior_w_scale > 0.0))
+    return fail(e, DLM_ERR_ARG, "the Poisson rate, the proposal size and the InverseGamma prior of W must be positive");
+  HIP_TRY(e, hipSetDevice(e->device));
+  dlm::StudentTArgs k{};
+  const size_t n = N, t = T, dd = d;
+  Stager st(e, opts->mem == DLM_MEM_HOST);
+  st.in(&k.F, model->F, (model->f_stride ? t : 1) * dd);
+  st.in(&k.y, y, n * t);
+  st.in(&k.theta, theta, n * (t + 1) * dd);
+  st.in(&k.stats, stats, n * (dd + 3));
+  st.in(&k.scale_in, scale_in, n);
+  st.in(&k.nu_in, (const int*)nu_in, n);
+  st.out(&k.v_out, v_out, n * t);
+  st.out(&k.scale_out, scale_out, n);
+  st.out(&k.nu_out, (int*)nu_out, n);
+  st.out(&k.W_out, W_out, n * dd * dd);
+  st.inout(&k.accepted, (int*)accepted, n);
+  st.out(&k.loglik, loglik, loglik ? n : 0);
+  st.zeroed_out(&k.status, (int*)status, status ? n : 0);
+  int rc;
+  if ((rc = st.commit())) return rc;
+  k.d = d; k.T = T; k.N = N; k.f_stride = model->f_stride;
+  k.prior_nu_rate = prior->prior_nu_rate; k.prop_nu_size = prior->prop_nu_size;
+  k.prior_w_shape = prior->prior_w_shape; k.prior_w_scale = prior->prior_w_scale;
+  k.literal = literal ? 1 : 0;
+  k.seed = opts->seed; k.series_offset = opts->series_offset; k.iteration = iteration;
+  e->variant = "studentt-step";
+  HIP_TRY(e, dlm::launch_studentt_step(k, e->stream));
   return st.finish(opts->flags & DLM_OPT_ASYNC);
 }
 

@@ -9,42 +9,12 @@
 // 1 / scale).draw (InverseGamma.scala:14) = scale / Gamma(shape, 1).draw; the unit-scale Gamma is Marsaglia-Tsang (2000)
 // on Philox normals and uniforms keyed by (seed, global series, iteration, component, attempt): reproducible and
 // independent of the sharding.  The reference's generator cannot be seeded: only the distribution is
-// comparable with it; oracle/dlm_oracle.c restates this very construction.
+// comparable with it; oracle/dlm_oracle.c restates this very construction.  gibbs_rand and gamma_unit live in dlm_internal.h
+// (the Student-t step of dlm_studentt.hip draws W on this very stream and its own variates on a stream of its own).
 #include "dlm_internal.h"
 #include "../../include/dlm_engine.h"
 
 namespace dlm {
-
-__device__ __forceinline__ void gibbs_rand(unsigned long long seed, unsigned long long series, unsigned long long iteration,
-                                           unsigned comp, unsigned attempt, unsigned which, double& u1, double& u2) {
-  unsigned c[4] = {(unsigned)series, (unsigned)(series >> 32), (unsigned)iteration, comp * 2048u + attempt * 2u + which};
-  philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32) ^ 0x47494242u);
-  u1 = ((double)c[0] * 4294967296.0 + (double)c[1] + 1.0) * (1.0 / 18446744073709551616.0);   // (0, 1]
-  u2 = ((double)c[2] * 4294967296.0 + (double)c[3]) * (1.0 / 18446744073709551616.0);         // [0, 1)
-}
-
-// Gamma(a, 1): Marsaglia & Tsang, "A simple method for generating gamma variables" (2000); a < 1 by the u^(1/a) boost
-__device__ double gamma_unit(double a, unsigned long long seed, unsigned long long series, unsigned long long iteration, unsigned comp) {
-  double boost = 1.0;
-  if (a < 1.0) {
-    double u1, u2;
-    gibbs_rand(seed, series, iteration, comp, 1023u, 0u, u1, u2);
-    boost = pow(u1, 1.0 / a);
-    a += 1.0;
-  }
-  const double dd = a - 1.0 / 3.0, cc = 1.0 / sqrt(9.0 * dd);
-  for (unsigned k = 0; k < 1023u; ++k) {
-    double u1, u2, w1, w2;
-    gibbs_rand(seed, series, iteration, comp, k, 0u, u1, u2);
-    const double x = sqrt(-2.0 * log(u1)) * cos(6.283185307179586476925286766559 * u2);
-    double v = 1.0 + cc * x;
-    if (v <= 0.0) continue;
-    v = v * v * v;
-    gibbs_rand(seed, series, iteration, comp, k, 1u, w1, w2);
-    if (log(w1) < 0.5 * x * x + dd - dd * v + dd * log(v)) return dd * v * boost;
-  }
-  return dd * boost;   // unreachable in practice (acceptance > 95 % per attempt)
-}
 
 __global__ __launch_bounds__(256) void k_dinvgamma_step(int d, int p, int N, const double* __restrict__ stats, double av, double bv,
                                                         double aw, double bw, unsigned long long seed,

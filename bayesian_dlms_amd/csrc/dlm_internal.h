@@ -253,6 +253,22 @@ hipError_t launch_dinvgamma_step(int d, int p, int N, const double* stats, doubl
                                  unsigned long long seed, unsigned long long series_offset, unsigned long long iteration,
                                  double* Vout, double* Wout, hipStream_t s);
 
+// ---- Student-t observation DLM: one Gibbs step after the FFBS call (StudentTGibbs.scala:182-212), dlm_studentt.hip -------------
+struct StudentTArgs {
+  int d, T, N;
+  const double* F; long long f_stride;   // F_t = F + t * f_stride (d doubles, p = 1)
+  const double* y;        // [N][T]
+  const double* theta;    // [N][T+1][d]
+  const double* stats;    // [N][d + 3] = [ssy | n | ss (d) | T] of the FFBS call
+  const double* scale_in; const int* nu_in;
+  double prior_nu_rate, prop_nu_size, prior_w_shape, prior_w_scale;
+  int literal;            // DLM_OPT_STUDENTT_LITERAL
+  unsigned long long seed, series_offset, iteration;
+  double* v_out; double* scale_out; int* nu_out; double* W_out; int* accepted;
+  double* loglik; int* status;   // nullable
+};
+hipError_t launch_studentt_step(const StudentTArgs& a, hipStream_t s);
+
 // ---- KalmanFilter.likelihood literally (transition density of the filtered means), dlm_loglik.hip ------
 size_t loglik_q7_ws_bytes(const KArgs& a);
 hipError_t launch_loglik_q7(const KArgs& a, const double* records, void* ws, hipStream_t s);   // a.loglik [N] <- records [N][T+1][d+dd]
@@ -341,6 +357,47 @@ __device__ __forceinline__ void philox_normal2(unsigned long long seed, unsigned
   double r = sqrt(-2.0 * log(u1));
   double ang = 6.283185307179586476925286766559 * u2;
   z_even = r * cos(ang); z_odd = r * sin(ang);
+}
+
+// ---- Gamma variates on Philox uniforms (dlm_gibbs.hip, dlm_studentt.hip; oracle/dlm_oracle.c restates the GIBB stream) ----------
+// Counter (series lo, series hi, iteration, comp * 2048 + attempt * 2 + which) under the key (seed lo, seed hi ^ key): one stream per
+// key, each disjoint from the FFBS / simulation normals (key (seed lo, seed hi)) and from the others.
+//   DLM_KEY_GIBBS     dlm_dinvgamma_step_batch: comp = component of [V diagonal (p) | W diagonal (d)]; the Student-t step draws W here too
+//   DLM_KEY_STUDENTT  dlm_studentt_step_batch: comp = t for the variance v_t, DLM_ST_SLOT_* for its scalar draws (dlm_studentt.hip)
+constexpr unsigned DLM_KEY_GIBBS = 0x47494242u;      // "GIBB"
+constexpr unsigned DLM_KEY_STUDENTT = 0x53545544u;   // "STUD"
+
+__device__ __forceinline__ void gibbs_rand(unsigned long long seed, unsigned long long series, unsigned long long iteration,
+                                           unsigned comp, unsigned attempt, unsigned which, double& u1, double& u2,
+                                           unsigned key = DLM_KEY_GIBBS) {
+  unsigned c[4] = {(unsigned)series, (unsigned)(series >> 32), (unsigned)iteration, comp * 2048u + attempt * 2u + which};
+  philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32) ^ key);
+  u1 = ((double)c[0] * 4294967296.0 + (double)c[1] + 1.0) * (1.0 / 18446744073709551616.0);   // (0, 1]
+  u2 = ((double)c[2] * 4294967296.0 + (double)c[3]) * (1.0 / 18446744073709551616.0);         // [0, 1)
+}
+
+// Gamma(a, 1): Marsaglia & Tsang, "A simple method for generating gamma variables" (2000); a < 1 by the u^(1/a) boost
+__device__ inline double gamma_unit(double a, unsigned long long seed, unsigned long long series, unsigned long long iteration, unsigned comp,
+                                    unsigned key = DLM_KEY_GIBBS) {
+  double boost = 1.0;
+  if (a < 1.0) {
+    double u1, u2;
+    gibbs_rand(seed, series, iteration, comp, 1023u, 0u, u1, u2, key);
+    boost = pow(u1, 1.0 / a);
+    a += 1.0;
+  }
+  const double dd = a - 1.0 / 3.0, cc = 1.0 / sqrt(9.0 * dd);
+  for (unsigned k = 0; k < 1023u; ++k) {
+    double u1, u2, w1, w2;
+    gibbs_rand(seed, series, iteration, comp, k, 0u, u1, u2, key);
+    const double x = sqrt(-2.0 * log(u1)) * cos(6.283185307179586476925286766559 * u2);
+    double v = 1.0 + cc * x;
+    if (v <= 0.0) continue;
+    v = v * v * v;
+    gibbs_rand(seed, series, iteration, comp, k, 1u, w1, w2, key);
+    if (log(w1) < 0.5 * x * x + dd - dd * v + dd * log(v)) return dd * v * boost;
+  }
+  return dd * boost;   // unreachable in practice (acceptance > 95 % per attempt)
 }
 
 }  // namespace dlm

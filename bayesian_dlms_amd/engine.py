@@ -182,7 +182,8 @@ class Engine:
         packed = pack_params(params, N) if not isinstance(params, tuple) else params
         V, vs, W, ws, m0, m0s, C0, c0s = packed[:8]
         vts, wts = (packed[8], packed[9]) if len(packed) > 8 else (0, 0)
-        if vts and np.size(V) // max(1, (N if vs else 1)) != mat.T * vts or wts and np.size(W) // max(1, (N if ws else 1)) != mat.T * wts:
+        size = lambda a: a.numel() if hasattr(a, "numel") else np.size(a)     # (torch tensors: V_t / W_t streams kept on the device)
+        if vts and size(V) // max(1, (N if vs else 1)) != mat.T * vts or wts and size(W) // max(1, (N if ws else 1)) != mat.T * wts:
             raise ValueError("time-varying V / W need one matrix per observation")
         items = dict(F=(mat.F, np.float64), G=(mat.G, np.float64), gi=(mat.g_index, np.int32), dt=(mat.dt, np.float64),
                      V=(V, np.float64), W=(W, np.float64), m0=(m0, np.float64), C0=(C0, np.float64))
@@ -305,6 +306,42 @@ class Engine:
         self._check(self.lib.dlm_dinvgamma_step_batch(self.h, d, p, N, be.ptr(sb), float(av), float(bv), float(aw), float(bw),
                                                       int(iteration), op, be.ptr(V), be.ptr(W)))
         return V, W
+
+    def studentt_step(self, mat, y, theta, stats, prior, scale, nu, *, iteration, accepted=None, seed=0, series_offset=0,
+                      literal=False, want_loglik=True, flags=0, out=None):
+        """One StudentT.step after its FFBS call (dlm_studentt_step_batch; StudentTGibbs.scala:182-212) for N chains.
+        y [N][T] (or [N][T][1]; NaN = missing), theta [N][T+1][d] and stats [N][d + 3] of that FFBS call, scale [N] (s), nu [N]
+        (int32); prior = (prior_nu_rate, prop_nu_size, prior_w_shape, prior_w_scale).  accepted [N] int32 is incremented in
+        place (None: a fresh zero array).  Returns {"v" [N][T], "scale", "nu", "W" [N][d*d], "accepted", "loglik", "status"}: v is
+        the next FFBS call's V stream (v_stride = T, v_tstride = 1).  literal=True: the reference's arithmetic (Q11-Q15).
+        out: dict of existing buffers to write into ("v", "scale", "nu", "W"; scale / nu may be the inputs)."""
+        be = self._backend(y)
+        N, T, d = int(y.shape[0]), mat.T, mat.d
+        if mat.p != 1:
+            raise EngineError("the Student-t step is univariate: p must be 1")
+        yb = be.put(y).reshape(N, T)
+        tb, sb = be.put(theta), be.put(stats)
+        scb, nub = be.put(scale), be.put(nu, np.int32)
+        Fb = be.put(mat.F)
+        out = out or {}
+        v = out["v"] if "v" in out else be.empty((N, T))
+        sc_out = out["scale"] if "scale" in out else be.empty((N,))
+        nu_out = out["nu"] if "nu" in out else be.empty((N,), np.int32)
+        W = out["W"] if "W" in out else be.empty((N, d * d))
+        acc = be.put(accepted, np.int32) if accepted is not None else None
+        if acc is None:
+            acc = be.empty((N,), np.int32)
+            acc[...] = 0
+        ll = be.empty((N,)) if want_loglik else None
+        status = be.empty((N,), np.int32)
+        md = _lib.ModelDesc(d, mat.p, T, N, be.ptr(Fb).value, mat.f_stride, None, mat.n_g, None, None)
+        pr = _lib.StudentTPrior(*(float(x) for x in prior))
+        op = _lib.Options(flags | (_lib.OPT_STUDENTT_LITERAL if literal else 0), be.mem, seed, series_offset)
+        self._hold(flags, yb, tb, sb, scb, nub, Fb)
+        self._check(self.lib.dlm_studentt_step_batch(self.h, md, be.ptr(yb), be.ptr(tb), be.ptr(sb), pr, be.ptr(scb),
+                                                     be.ptr(nub), int(iteration), op, be.ptr(v), be.ptr(sc_out), be.ptr(nu_out),
+                                                     be.ptr(W), be.ptr(acc), be.ptr(ll), be.ptr(status)))
+        return {"v": v, "scale": sc_out, "nu": nu_out, "W": W, "accepted": acc, "loglik": ll, "status": status}
 
     def simulate(self, mat, params, N, *, seed=0, series_offset=0, device=False, want_x=True):
         """Dlm.simulateRegular over the model's time grid for N series (dlm_simulate_batch): (x [N][T+1][d], y [N][T][p])."""

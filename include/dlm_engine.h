@@ -66,6 +66,9 @@ enum {
                                          * and compare them on the host, as bayesian_dlms_amd/engine.py does)                     */
   DLM_OPT_LOGLIK_LITERAL_Q7 = 1u << 11, /* dlm_loglik_batch: KalmanFilter.likelihood as written (KalmanFilter.scala:299-306, what
                                          * MetropolisHastings.dlm evaluates): the transition density of the filtered means        */
+  DLM_OPT_STUDENTT_LITERAL = 1u << 12,  /* dlm_studentt_step_batch: StudentT.step's arithmetic as written: v_t drawn
+                                         * with the previous nu and theta_{t-1}, nu moved last, the proposal density at `to`, a
+                                         * missing y_t drawn with shape (nu + 1) / 2, 0.5 log(pi nu sqrt(s)) in the log-likelihood */
   /* Kernel-selection overrides: measurements and tests only, results do not depend on them.           */
   DLM_OPT_NO_LANE = 1u << 16,           /* no lane-per-series kernels (d <= 5, p = 1)                                  */
   DLM_OPT_NO_SAMPLER16 = 1u << 17,      /* no register-tile backward sampler: the generic kernel                       */
@@ -224,6 +227,34 @@ int dlm_simulate_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_par
 int dlm_dinvgamma_step_batch(dlm_engine* e, int32_t d, int32_t p, int32_t N, const double* stats, double alpha_v,
                              double beta_v, double alpha_w, double beta_w, uint64_t iteration, const dlm_options* opts,
                              double* V_out, double* W_out);
+
+/* One step of the Student-t observation DLM's Gibbs sampler (StudentT.step, StudentTGibbs.scala:182-212) for N independent
+ * chains, after the FFBS call of its state draw (dlm_ffbs_batch with the V_t stream v_t of the previous step and per-series W).
+ * p = 1 (the reference's model is univariate; DLM_ERR_UNSUPPORTED otherwise).  model: F (time-varying allowed in the default
+ * mode), d, T, N; G and the time grid are not read.  Inputs:
+ *   y [N][T] (NaN = missing), theta [N][T+1][d] as dlm_ffbs_batch writes it, stats [N][dlm_stats_len(d, 1, 0)] of that call,
+ *   scale_in [N] (s, the square of the Student-t scale), nu_in [N] (degrees of freedom, int32).
+ * Default (corrected) order: W | theta, then nu | (theta, s) by Metropolis-Hastings with v_t marginalised, then v_t | (theta, nu, s),
+ * then s | (v, nu):
+ *   W_ii ~ InverseGamma(prior_w_shape + T / 2, prior_w_scale + ss_i / 2)       (dlm_dinvgamma_step_batch's stream: W_out is that call's)
+ *   nu'  = Poisson(Gamma(r, nu / r)) + 1 (r = prop_nu_size), accepted against Poisson(prior_nu_rate) and the Student-t likelihood
+ *   v_t  ~ InverseGamma((nu + 1) / 2, nu s / 2 + e_t^2 / 2),  e_t = y_t - F_t^T theta_t;  missing y_t: InverseGamma(nu / 2, nu s / 2)
+ *   s    ~ Gamma(T nu / 2 + 1, 1 / (nu / 2 sum_t 1 / v_t))
+ * DLM_OPT_STUDENTT_LITERAL: the reference's arithmetic; the caller passes the INITIAL (s, W) every step (Q10).
+ * A literal call with a time-varying F is DLM_ERR_UNSUPPORTED (Q11 needs F at t0 - 1).
+ * Outputs: v_out [N][T] (the next FFBS call's V stream: v_stride = T, v_tstride = 1), scale_out [N], nu_out [N], W_out [N][d*d]
+ * (dense diagonal), accepted [N] (in / out: incremented on acceptance), loglik [N] (nullable: the Student-t log-likelihood at
+ * nu_out and scale_in), status [N] (nullable).  scale_out may be scale_in and nu_out may be nu_in.  A series with nu_in < 1, s not
+ * finite and positive, or a non-finite F^T theta_t gets DLM_ST_NONFINITE, NaN in its double outputs and nu_out = nu_in.
+ * Draws: W on the dlm_dinvgamma_step_batch stream (components 1 + i), everything else on a Philox stream of its own keyed by
+ * (opts->seed, opts->series_offset + n, iteration, slot): reproducible and independent of the sharding.  T < 2^21 - 4.
+ * The call reads F only: it does not count as the "previous model-taking call" of DLM_OPT_MODEL_UNCHANGED. */
+typedef struct { double prior_nu_rate, prop_nu_size, prior_w_shape, prior_w_scale; } dlm_studentt_prior;
+int dlm_studentt_step_batch(dlm_engine* e, const dlm_model_desc* model, const double* y, const double* theta,
+                            const double* stats, const dlm_studentt_prior* prior, const double* scale_in,
+                            const int32_t* nu_in, uint64_t iteration, const dlm_options* opts, double* v_out,
+                            double* scale_out, int32_t* nu_out, double* W_out, int32_t* accepted,
+                            double* loglik, int32_t* status);
 
 /* Scalar AR(1) state-space FFBS, one GPU lane per series: FilterAr.filterUnivariate / univariateSample / ffbs
  * (FilterAr.scala:15-82), the filter of the stochastic-volatility samplers (StochasticVolatility.scala:142-162,

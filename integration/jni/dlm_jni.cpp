@@ -234,6 +234,27 @@ JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_dinvgammaStep(JNI
   throw_if(env, eng(h), dlm_dinvgamma_step_batch(eng(h), d, p, n, ptr<const double>(stats), alphaV, betaV, alphaW, betaW, static_cast<uint64_t>(iteration), &o,
                                                  ptr<double>(vOut), ptr<double>(wOut)));
 }
+// ---- StudentT.step on the device (StudentTGibbs.scala:182-212), after the FFBS call of its state draw --------------------------------
+// The prior crosses as four doubles (dlm_studentt_prior's field order); model = the usual long[10] (F, d, T, N are read).
+JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_studenttStep(JNIEnv* env, jobject, jlong h, jlongArray model, jlong y, jlong theta, jlong stats,
+                                                                            jdouble priorNuRate, jdouble propNuSize, jdouble priorWShape, jdouble priorWScale,
+                                                                            jlong scaleIn, jlong nuIn, jlong iteration, jlongArray opts, jlong vOut,
+                                                                            jlong scaleOut, jlong nuOut, jlong wOut, jlong accepted, jlong loglik, jlong status) {
+  if (!model || env->GetArrayLength(model) != 10) { throw_arg(env, "model must be long[10] = {d, p, T, N, F, fStride, G, nG, gIndex, dt}"); return; }
+  jlong m[10];
+  env->GetLongArrayRegion(model, 0, 10, m);
+  dlm_model_desc md{};
+  md.d = static_cast<int32_t>(m[0]); md.p = static_cast<int32_t>(m[1]); md.T = static_cast<int32_t>(m[2]); md.N = static_cast<int32_t>(m[3]);
+  md.F = ptr<const double>(m[4]); md.f_stride = m[5]; md.G = ptr<const double>(m[6]); md.n_g = static_cast<int32_t>(m[7]);
+  md.g_index = ptr<const int32_t>(m[8]); md.dt = ptr<const double>(m[9]);
+  dlm_options o{};
+  if (!read_opts(env, opts, o)) return;
+  const dlm_studentt_prior pr{priorNuRate, propNuSize, priorWShape, priorWScale};
+  throw_if(env, eng(h), dlm_studentt_step_batch(eng(h), &md, ptr<const double>(y), ptr<const double>(theta), ptr<const double>(stats), &pr,
+                                                ptr<const double>(scaleIn), ptr<const int32_t>(nuIn), static_cast<uint64_t>(iteration), &o,
+                                                ptr<double>(vOut), ptr<double>(scaleOut), ptr<int32_t>(nuOut), ptr<double>(wOut),
+                                                ptr<int32_t>(accepted), ptr<double>(loglik), ptr<int32_t>(status)));
+}
 // ---- scalar AR(1) / OU FFBS: FilterAr (FilterAr.scala:15-82), FilterOu (FilterOu.scala:7-79) ------------------------------------------
 JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_ar1Ffbs(JNIEnv* env, jobject, jlong h, jint n, jint t, jlong y, jlong v, jlong vStride, jlong sv, jlong svStride,
                                                                        jlong z, jlongArray opts, jlong filt, jlong theta, jlong status) {

@@ -65,6 +65,8 @@ final class Native private[gpu] () {
   @native def svdFilter(h: Long, model: Array[Long], params: Array[Long], opts: Array[Long], y: Long, svdRec: Long, status: Long): Unit
   @native def svdFfbs(h: Long, model: Array[Long], params: Array[Long], opts: Array[Long], y: Long, z: Long, svdWs: Long, theta: Long, stats: Long, status: Long): Unit
   @native def dinvgammaStep(h: Long, d: Int, p: Int, n: Int, stats: Long, alphaV: Double, betaV: Double, alphaW: Double, betaW: Double, iteration: Long, opts: Array[Long], vOut: Long, wOut: Long): Unit
+  /** StudentT.step after its FFBS call (StudentTGibbs.scala:182-212): W, nu, v_t, s for N chains; the prior as four doubles */
+  @native def studenttStep(h: Long, model: Array[Long], y: Long, theta: Long, stats: Long, priorNuRate: Double, propNuSize: Double, priorWShape: Double, priorWScale: Double, scaleIn: Long, nuIn: Long, iteration: Long, opts: Array[Long], vOut: Long, scaleOut: Long, nuOut: Long, wOut: Long, accepted: Long, loglik: Long, status: Long): Unit
   @native def ar1Ffbs(h: Long, n: Int, t: Int, y: Long, v: Long, vStride: Long, sv: Long, svStride: Long, z: Long, opts: Array[Long], filt: Long, theta: Long, status: Long): Unit
   @native def ouFfbs(h: Long, n: Int, t: Int, times: Long, y: Long, v: Long, vStride: Long, sv: Long, svStride: Long, z: Long, opts: Array[Long], filt: Long, theta: Long, status: Long): Unit
   @native def statsPool(h: Long, stats: Long, n: Int, l: Int, pooled: Long, opts: Array[Long]): Unit
@@ -88,6 +90,7 @@ object Native {
   val ModelUnchanged = 1 << 8     // a PROMISE: F, G and the time grid are those of this engine's previous call (its structure analysis is reused); the engine verifies it with a device checksum and fails the call if it does not hold
   val CountSteps = 1 << 9         // count the steps that took a short path (Native.lastCounters)
   val LoglikLiteralQ7 = 1 << 11   // logLikelihood: KalmanFilter.likelihood as written (the transition density of the filtered means, KalmanFilter.scala:299-306)
+  val StudenttLiteral = 1 << 12   // studenttStep: StudentT.step's arithmetic as written (DESIGN.md 2, Q11-Q15); the caller passes the INITIAL (s, W) every step (Q10)
   val TrustModelUnchanged = 1 << 10 // with ModelUnchanged: skip the device checksum (only for callers that compared the tables themselves)
   val SvdPerSeries = 1 << 25      // SVD filter: every series its own decompositions (default: once per call where V, W, C0 are shared; the same bits)
   val SamplerPerSeries = 1 << 26  // ffbs: every series its own J_t, H_t, chol(H_t) (default: once per call where V, W, C0 are shared -- the pooled Gibbs samplers; the same draws, bit for bit)
