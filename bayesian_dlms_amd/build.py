@@ -22,6 +22,19 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def _compile_all(todo, verbose):
+    """Runs the compile commands side by side: the translation units are independent (the largest takes about two minutes)."""
+    if not todo:
+        return
+    from concurrent.futures import ThreadPoolExecutor
+    def run(cmd):
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    with ThreadPoolExecutor(max_workers=min(len(todo), max(1, (os.cpu_count() or 2) // 2))) as pool:
+        list(pool.map(run, todo))
+
+
 def build_variant(name, defines):
     """Experimental build with extra -D flags -> bayesian_dlms_amd/libdlm_engine_<name>.so."""
     out = os.path.join(HERE, f"libdlm_engine_{name}.so")
@@ -35,16 +48,49 @@ def build_variant(name, defines):
     return out
 
 
-def build_tu_variant(name, src, defines):
-    """Experimental build in which only ONE translation unit gets extra -D flags (the other objects come from the regular
-    build) -> bayesian_dlms_amd/libdlm_engine_<name>.so.  Select it with DLM_ENGINE_LIB."""
+def build_tu_variant(name, srcs, defines):
+    """Experimental build in which only the named translation unit(s) get extra -D flags (the other objects come from the regular
+    build) -> bayesian_dlms_amd/libdlm_engine_<name>.so.  `srcs`: one source file name or a list of them.  Select it with DLM_ENGINE_LIB."""
     build()
+    srcs = [srcs] if isinstance(srcs, str) else list(srcs)
     out = os.path.join(HERE, f"libdlm_engine_{name}.so")
-    o = os.path.join(HERE, "build", f"{name}_{src.replace('.hip', '.o')}")
-    subprocess.check_call([HIPCC] + FILE_FLAGS.get(src, FLAGS) + [f"-D{d}" for d in defines] + ["-c", os.path.join(CSRC, src), "-o", o])
-    objs = [o if s == src else os.path.join(HERE, "build", s.replace(".hip", ".o")) for s in SOURCES]
+    own = {src: os.path.join(HERE, "build", f"{name}_{src.replace('.hip', '.o')}") for src in srcs}
+    for src, o in own.items():
+        subprocess.check_call([HIPCC] + FILE_FLAGS.get(src, FLAGS) + [f"-D{d}" for d in defines] + ["-c", os.path.join(CSRC, src), "-o", o])
+    objs = [own.get(s, os.path.join(HERE, "build", s.replace(".hip", ".o"))) for s in SOURCES]
     subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs + ["-L/opt/rocm/lib", "-lrccl"])
     return out
+
+
+# The translation units whose LDS-DMA prefetches are waited for by hand count (vm_wait in csrc/dlm_internal.h)
+DRAIN_SOURCES = ["dlm_sparse16.hip", "dlm_sampler16.hip", "dlm_svd.hip"]
+DRAIN_LIB = os.path.join(HERE, "libdlm_engine_drain.so")
+
+
+def drain_object(src):
+    return os.path.join(HERE, "build", "drain", src.replace(".hip", ".o"))
+
+
+def build_drain_variant(force=False, verbose=False):
+    """The engine with every hand-counted wait drained (-DDLM_DRAIN_WAITS=1: vmcnt(0)) -> bayesian_dlms_amd/libdlm_engine_drain.so.
+    Only the DRAIN_SOURCES are compiled again; the other objects are the regular build's.  Rebuilt only when a source or header
+    is newer, as build() does.  tests/test_counted_waits_gpu.py compares it with the default build bit for bit."""
+    build(verbose=verbose)
+    hdrs = [os.path.join(CSRC, "dlm_internal.h"), os.path.join(HERE, "..", "include", "dlm_engine.h")]
+    os.makedirs(os.path.join(HERE, "build", "drain"), exist_ok=True)
+    todo = []
+    for src in DRAIN_SOURCES:
+        s, o = os.path.join(CSRC, src), drain_object(src)
+        if force or _stale(o, [s] + hdrs):
+            todo.append([HIPCC] + FILE_FLAGS.get(src, FLAGS) + ["-DDLM_DRAIN_WAITS=1", "-c", s, "-o", o])
+    _compile_all(todo, verbose)
+    objs = [drain_object(s) if s in DRAIN_SOURCES else os.path.join(HERE, "build", s.replace(".hip", ".o")) for s in SOURCES]
+    if force or _stale(DRAIN_LIB, objs):
+        cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", DRAIN_LIB] + objs + ["-L/opt/rocm/lib", "-lrccl"]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    return DRAIN_LIB
 
 
 def build(force=False, verbose=False):
@@ -58,14 +104,7 @@ def build(force=False, verbose=False):
         objs.append(o)
         if force or _stale(o, [s] + hdrs):
             todo.append([HIPCC] + FILE_FLAGS.get(src, FLAGS) + ["-c", s, "-o", o])
-    if todo:   # the translation units are independent: compile them side by side (the largest takes about two minutes)
-        from concurrent.futures import ThreadPoolExecutor
-        def run(cmd):
-            if verbose:
-                print(" ".join(cmd))
-            subprocess.check_call(cmd)
-        with ThreadPoolExecutor(max_workers=min(len(todo), max(1, (os.cpu_count() or 2) // 2))) as pool:
-            list(pool.map(run, todo))
+    _compile_all(todo, verbose)
     if force or _stale(LIB, objs):
         cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + ["-L/opt/rocm/lib", "-lrccl"]
         if verbose:
@@ -76,3 +115,5 @@ def build(force=False, verbose=False):
 
 if __name__ == "__main__":
     build(force="--force" in sys.argv, verbose=True)
+    if "--drain" in sys.argv:
+        build_drain_variant(force="--force" in sys.argv, verbose=True)

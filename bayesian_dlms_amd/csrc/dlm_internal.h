@@ -69,6 +69,20 @@ __host__ __device__ inline int stats_len(int d, int p, unsigned flags) {
   return 2 * p + ((flags & (1u << 4)) ? d * d : d) + 1;  // DLM_OPT_STATS_OUTER
 }
 
+// The one hand-counted vector-memory wait of the LDS-DMA prefetches (dlm_sparse16.hip, dlm_sampler16.hip, dlm_svd.hip): at most
+// N vector-memory operations of this wave still in flight.  N counts the loads, stores and LDS DMAs the wave issued after the
+// one waited for.  -DDLM_DRAIN_WAITS=1 turns every such wait into vmcnt(0) and changes nothing else
+// (build.build_drain_variant): tests/test_counted_waits_gpu.py compares the two builds bit for bit.  Every counted wait
+// goes through here (tests/test_counted_waits_host.py checks the sources and the code objects).
+#ifndef DLM_DRAIN_WAITS
+#define DLM_DRAIN_WAITS 0
+#endif
+template <int N>
+__device__ __forceinline__ void vm_wait() {
+  static_assert(N >= 0 && N <= 63, "vmcnt holds 0..63");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DLM_DRAIN_WAITS ? 0 : N) : "memory");
+}
+
 // ---- generic wave-per-series kernels (any d <= 64, p <= 64), dlm_generic.hip ----------
 size_t generic_filter_lds_bytes(int d, int p);
 size_t generic_smoother_lds_bytes(int d, int p);

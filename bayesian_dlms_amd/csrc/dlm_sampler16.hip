@@ -556,8 +556,6 @@ __device__ __forceinline__ i4 rsrc_words(const void* p, unsigned bytes) {
           __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000};
   return r;
 }
-template <int N>
-__device__ __forceinline__ void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ unsigned lds_addr_of(const void* p) { return (unsigned)(size_t)(__attribute__((address_space(3))) const char*)p; }
 template <int OFF>
 __device__ __forceinline__ double lds_read64(unsigned addr) {

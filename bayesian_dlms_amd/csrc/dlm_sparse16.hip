@@ -180,10 +180,6 @@ __device__ __forceinline__ void dma_record(const i4& rs, unsigned lds_addr, int 
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen offset:1024 lds"
                  ::"s"(lds_addr), "v"(voff), "s"(rs), "s"(soff) : "memory");
 }
-template <int N>
-__device__ __forceinline__ void vm_wait() {   // at most N vector-memory operations of this wave still in flight
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // Diagnostic build only (-DDLM_STAMP): s_memtime stamps around the phases of the backward step;
 // the sums of series 0 are written into status[1..] (never in the shipped build).

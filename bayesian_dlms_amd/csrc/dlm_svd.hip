@@ -732,7 +732,7 @@ __global__ __launch_bounds__(256) void k_svd_mean_filter(KArgs a, const double* 
   double ychunk = (lane < T) ? y[lane] : 0.0;
   asm volatile("" ::"v"(ychunk));
   ssync();
-  asm volatile("s_waitcnt vmcnt(1)" ::: "memory");   // row 0
+  vm_wait<1>();   // row 0
   {   // record 0: [m0 | dc0 | uc0]
     const double* row = (const double*)ring;
     double v[5];
@@ -760,7 +760,7 @@ __global__ __launch_bounds__(256) void k_svd_mean_filter(KArgs a, const double* 
       return;
     }
     // operations issued after the request for row t + 1: the 5 stores of record t - 1, the request for row t + 2 (>= 1), the 5 stores of record t
-    if (t == 0) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
+    if (t == 0) vm_wait<6>(); else vm_wait<11>();
     const double* row = (const double*)(ring + ((t + 1) & 1) * (rowb + 16));
     // a = G m
     double ai = 0.0;
@@ -932,7 +932,7 @@ __global__ __launch_bounds__(64, 3) void k_svd_mean_filter4(KArgs a, const doubl
     for (int q = 0; q < 4; ++q) deadmask |= (__builtin_amdgcn_readlane((int)dead, 16 * q) & 1) << q;
     if ((deadmask & 15u) == 15u) break;
     // operations issued after the request for row t + 1: the NS stores of record t - 1, the request for row t + 2 (>= 1), the NS stores of record t
-    if (t == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NS + 1) : "memory"); else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NS + 1) : "memory");
+    if (t == 0) vm_wait<NS + 1>(); else vm_wait<2 * NS + 1>();
     const unsigned slot = ring_lds + ((t + 1) & 1) * (rowb + 16);
     const double* row = (const double*)(ring + ((t + 1) & 1) * (rowb + 16));
     // a = G m
