@@ -34,7 +34,9 @@ OPT_SVD_PER_SERIES = 1 << 25
 OPT_SAMPLER_PER_SERIES = 1 << 26
 OPT_DRAW_EIG = 1 << 27
 OPT_SMOOTHER_PER_SERIES = 1 << 28
+OPT_NO_TABLE_REUSE = 1 << 29
 OPT_TEST_FAIL_AFTER_TABLES = 1 << 30
+TABLES_NONE, TABLES_BUILT, TABLES_REUSED, TABLES_SKIPPED = 0, 1, 2, 3   # dlm_last_table_reuse
 ST_NONFINITE, ST_NOT_PD, ST_NOCONV = 1, 2, 4
 COMM_ID_BYTES = 128
 
@@ -103,6 +105,7 @@ SYMBOLS = [
     ("dlm_filter_smooth_batch", ctypes.c_int, [_V, _MP, _PP, _V, _OP, _V, _V, _V]),
     ("dlm_last_timing", ctypes.c_int, [_V, ctypes.POINTER(ctypes.c_double * 2)]),
     ("dlm_last_counters", ctypes.c_int, [_V, ctypes.POINTER(ctypes.c_uint64 * 4)]),
+    ("dlm_last_table_reuse", ctypes.c_int, [_V, ctypes.POINTER(ctypes.c_int32)]),
     ("dlm_ffbs_batch", ctypes.c_int, [_V, _MP, _PP, _V, _V, _OP, _V, _V, _V, _V, _V]),
     ("dlm_stats_len", ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32]),
     ("dlm_backward_sample_batch", ctypes.c_int, [_V, _MP, _PP, _V, _V, _V, _OP, _V, _V, _V, _V]),

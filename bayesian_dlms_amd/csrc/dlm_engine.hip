@@ -66,6 +66,9 @@ struct dlm_engine {
   size_t sampws_bytes = 0;
   double* zws = nullptr;        // ... and the call's normals in the draw kernel's layout, made on a third stream while the batch is filtered
   size_t zws_bytes = 0;
+  void* rtsws = nullptr;        // shared factors of the RTS smoother: control words, key and tables of the last call that made them -- kept
+  size_t rtsws_bytes = 0;       //   across calls (nobody else carves it), reused where k_rts_key_check finds the call's key equal to theirs
+  bool rts_last = false;        // the last dlm_filter_smooth_batch call went through them (dlm_last_table_reuse)
   hipStream_t rng_stream = nullptr;
   hipEvent_t rng_ev = nullptr;
   hipStream_t cov_stream = nullptr;
@@ -569,14 +572,17 @@ int start_sampler_normals(dlm_engine* e, const KArgs& k, dlm::SampTabs& tb, bool
   }
   return DLM_OK;
 }
-// Shared factors of the RTS smoother (literal Q1; dlm_sampler16.hip): the tables are made on the second stream -- a filter and a smoother
-// run of ONE wave on a series of zeros -- while the batch is filtered on the first.  The workspace is the backward sampler's (e->sampws).
+// Shared factors of the RTS smoother (dlm_sampler16.hip): the tables are made on the second stream -- a filter and a smoother run of ONE wave
+// on a series of zeros -- while the batch is filtered on the first.  They live in a workspace of their own (e->rtsws) and stay there: a call
+// whose key equals theirs (k_rts_key_check, on the device: the host does not know hit from miss and queues the same launches either way) finds
+// the two one-wave kernels returning at once.  A re-size frees the old tables with the workspace; the new one starts invalid.
 int start_rts_tables(dlm_engine* e, const KArgs& k, dlm::RtsTabs& tb) {
   const size_t need = dlm::rts_shared_ws_bytes(k);
-  if (need > e->sampws_bytes) {
-    if (e->sampws) { { const int rcd = drain_all(e); if (rcd) return rcd; } HIP_TRY(e, hipFree(e->sampws)); e->sampws = nullptr; e->sampws_bytes = 0; }
-    HIP_TRY(e, hipMalloc(&e->sampws, need));
-    e->sampws_bytes = need;
+  if (need > e->rtsws_bytes) {
+    if (e->rtsws) { { const int rcd = drain_all(e); if (rcd) return rcd; } HIP_TRY(e, hipFree(e->rtsws)); e->rtsws = nullptr; e->rtsws_bytes = 0; }
+    HIP_TRY(e, hipMalloc(&e->rtsws, need));
+    e->rtsws_bytes = need;
+    HIP_TRY(e, hipMemsetAsync(e->rtsws, 0, 64, e->stream));   // the control words: no valid tables
   }
   const size_t cneed = sizeof(double) * dlm::covtabs_doubles(k.d, k.T);   // the forward covariance table of the shared-covariance kernels
   if (cneed > e->covws_bytes) {
@@ -586,18 +592,26 @@ int start_rts_tables(dlm_engine* e, const KArgs& k, dlm::RtsTabs& tb) {
   }
   int rc = ensure_route(e, (size_t)k.N);
   if (rc || (rc = ensure_cov_stream(e))) return rc;
-  dlm::rts_shared_carve(e->sampws, k, tb);
+  dlm::RtsKeep keep{};
+  dlm::rts_shared_carve(e->rtsws, k, tb, keep);
   dlm::CovTabs ctb{};
   dlm::covtabs_carve(e->covws, k.d, k.T, ctb);
+  const bool no_reuse = (k.flags & DLM_OPT_NO_TABLE_REUSE) != 0;
+  const int* gate = keep.ctl + dlm::RTS_CTL_GATE;
+  e->rts_last = true;
   HIP_TRY(e, dlm::launch_rts_shared_mark(k, e->route, tb, e->stream));                     // the series with a gap; where they are the majority, no tables (tb.skip)
-  HIP_TRY(e, dlm::launch_rts_shared_cov(k, e->sparse_k, e->sp_dev, tb, ctb, e->stream));   // the forward covariances: in front of the batch's forward pass
+  HIP_TRY(e, dlm::launch_rts_key_check(k, e->sparse_k, e->sp_dev, keep, no_reuse, e->stream));   // hit or miss; a miss marks the kept tables invalid before the kernels below overwrite them
+  HIP_TRY(e, dlm::launch_rts_shared_cov(k, e->sparse_k, e->sp_dev, tb, ctb, gate, e->stream));   // the forward covariances: in front of the batch's forward pass
   HIP_TRY(e, hipEventRecord(e->cov_ev[0], e->stream));
   e->cov_busy = true;                                                 // (from here on every exit path joins the stream: AuxScope)
   HIP_TRY(e, hipStreamWaitEvent(e->cov_stream, e->cov_ev[0], 0));
-  HIP_TRY(e, dlm::launch_rts_shared_tables(k, e->sparse_k, e->sp_dev, tb, e->cov_stream));   // J_t, S_t: beside it
+  HIP_TRY(e, dlm::launch_rts_shared_tables(k, e->sparse_k, e->sp_dev, tb, gate, e->cov_stream));   // J_t, S_t: beside it
   // The table run keeps a whole CU to itself (whole_cu_lds): it has to be resident before the forward pass fills every CU with its
   // workgroups, or it waits for that kernel's last wave.  The caller launches the gap count of the forward pass (mark_plain: a 30 us kernel)
   // in between on the engine's stream.
+  // Behind a table run that ran: its key and "valid".  An error exit from here on leaves a complete set (every exit path joins the stream),
+  // one before it leaves the set invalid.
+  HIP_TRY(e, dlm::launch_rts_key_commit(k, e->sparse_k, e->sp_dev, keep, no_reuse, e->cov_stream));
   HIP_TRY(e, hipEventRecord(e->cov_ev[1], e->cov_stream));
   return DLM_OK;
 }
@@ -773,6 +787,7 @@ void dlm_engine_destroy(dlm_engine* e) {
   if (e->route) (void)hipFree(e->route);
   if (e->plainbuf) (void)hipFree(e->plainbuf);
   if (e->sampws) (void)hipFree(e->sampws);
+  if (e->rtsws) (void)hipFree(e->rtsws);
   if (e->zws) (void)hipFree(e->zws);
   if (e->rng_ev) (void)hipEventDestroy(e->rng_ev);
   if (e->rng_stream) (void)hipStreamDestroy(e->rng_stream);
@@ -822,6 +837,18 @@ int dlm_last_counters(dlm_engine* e, uint64_t out[4]) {
   HIP_TRY(e, hipMemcpyAsync(h, e->counters, sizeof(h), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(e, hipStreamSynchronize(e->stream));
   for (int i = 0; i < 4; ++i) out[i] = h[i];
+  return DLM_OK;
+}
+
+int dlm_last_table_reuse(dlm_engine* e, int32_t* out) {
+  if (!e || !out) return DLM_ERR_ARG;
+  *out = DLM_TABLES_NONE;
+  if (!e->rts_last || !e->rtsws) return DLM_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  int h = 0;
+  HIP_TRY(e, hipMemcpyAsync(&h, (const int*)e->rtsws + dlm::RTS_CTL_LAST, sizeof(h), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  *out = h;
   return DLM_OK;
 }
 
@@ -1175,6 +1202,7 @@ int dlm_filter_smooth_batch(dlm_engine* e, const dlm_model_desc* model,
   int rc = check_common(e, model, params, opts);
   if (rc) return rc;
   if (!y || !smooth) return fail(e, DLM_ERR_ARG, "y and smooth are required");
+  e->rts_last = false;
   AuxScope aux(e);   // (the shared-covariance path runs its backward covariance table on the second stream)
   const size_t d = model->d, p = model->p, T = model->T, N = model->N, rec = d + d * d;
   KArgs k{};

@@ -186,12 +186,49 @@ struct RtsTabs {
   int* gaps;             // the number of series with a missing observation (launch_rts_shared_mark)
   int* skip;             // 1: more than half of the series have one -- the tables are not made, every series is routed to the per-series kernel
 };
+// The tables are a function of the model and of V, W, C0 alone: the engine keeps those of the last call that made them, in a workspace of
+// their own, and the next call uses them when everything they were computed from is byte for byte the same.  The key is a
+// copy of every byte the two one-wave kernels (k_cov_filter_sp16, k_smoother_rts16<.., true>) read; k_rts_key_check compares it with the
+// call's on the engine's stream -- the words themselves, no checksum -- and k_rts_key_commit writes it behind a table run.
+// What becomes of every field of KArgs in those two kernels (tests/test_rts_table_reuse_host.py holds this list against the struct, the
+// key, sampler_shared_model_ok and the launchers):
+//   RTS-KEY keyed:    d T flags F V W C0 G
+//                     (flags: the bits of RTS_KEY_FLAGS, what the two kernels test; G: as the tables of its rows and columns, SparseT [2],
+//                      and their K -- the kernels read G nowhere else)
+//   RTS-KEY fixed:    p g_index dt f_stride v_stride w_stride v_tstride w_tstride c0_stride packed
+//                     (one value only: sampler_shared_model_ok refuses the call otherwise)
+//   RTS-KEY replaced: N y m0_stride filt_in filt smooth status stats loglik prior fq route counters theta z series_offset plain settle_step
+//                     (set by launch_rts_shared_cov / cov_args / launch_cf / launch_rts_shared_tables to the table run's own)
+//   RTS-KEY unread:   n_g m0 cond spb spb_k spf spf_k seed route_take keep_cov ktab leave_step stretches
+//                     (n_g: without g_index only G_0 is used; m0: the covariance-only run starts from a mean of zeros; seed: simulation smoother
+//                      only; route_take: behind route; the others belong to other kernels)
+constexpr unsigned RTS_KEY_FLAGS = (1u << 0) | (1u << 22);   // DLM_OPT_SMOOTHER_COMPAT_Q1 (S_t), DLM_OPT_NO_STEADY (the covariance-only filter)
+struct RtsKeySrc {         // the call's side of the comparison: device pointers of the call
+  int d, T, K;             // K: the sparsity class, the template argument of both kernels
+  unsigned flags;          // KArgs::flags & RTS_KEY_FLAGS
+  const double *F, *V, *W, *C0;
+  const SparseT* sp;       // [2] rows, columns of G
+};
+// control words of the kept tables, at the head of their workspace: [0] the zero series' status (what RtsTabs::status points at: kept with the
+// tables), [8] gaps, [9] skip (RtsTabs), then
+enum { RTS_CTL_HIT = 10,     // this call found its key: the kept tables serve it
+       RTS_CTL_GATE = 11,    // skip | hit: what the two table kernels take for RtsTabs::skip -- they return at once
+       RTS_CTL_VALID = 12,   // the workspace holds a complete set of tables and their key
+       RTS_CTL_LAST = 13 };  // DLM_TABLES_* of the call (dlm_last_table_reuse)
+struct RtsKeep { int* ctl; unsigned* key; };
+constexpr int RTS_KEY_WORDS = 8 + 2 * (15 + 1 + 2 * 15 * 15) + 2 * (int)(sizeof(SparseT) / 4);   // at d = 15
 bool rts_shared_eligible(const KArgs& a, bool textbook);   // textbook: the call asks for S = C - J (R+ - S+) J^T (the default): a larger batch is needed to pay for the tables
 size_t rts_shared_ws_bytes(const KArgs& a);
-void rts_shared_carve(void* ws, const KArgs& a, RtsTabs& tb);
-// the tables: the covariance-only filter into ctb.ftab (launch_sparse16_cov_filter), then the smoother with its export on (both one wave)
-hipError_t launch_rts_shared_cov(const KArgs& a, int K, const SparseT* tabs_dev, RtsTabs& tb, const CovTabs& ctb, hipStream_t s);
-hipError_t launch_rts_shared_tables(const KArgs& a, int K, const SparseT* tabs_dev, const RtsTabs& tb, hipStream_t s);
+void rts_shared_carve(void* ws, const KArgs& a, RtsTabs& tb, RtsKeep& keep);   // (control words and key first: where they are does not depend on T)
+// behind launch_rts_shared_mark on the engine's stream: hit, gate; a miss marks the kept tables invalid before anything overwrites them.
+// no_reuse (DLM_OPT_NO_TABLE_REUSE): always a miss, and nothing is kept
+hipError_t launch_rts_key_check(const KArgs& a, int K, const SparseT* tabs_dev, const RtsKeep& keep, bool no_reuse, hipStream_t s);
+// behind launch_rts_shared_tables on its stream: after a table run that ran, the key and "valid"
+hipError_t launch_rts_key_commit(const KArgs& a, int K, const SparseT* tabs_dev, const RtsKeep& keep, bool no_reuse, hipStream_t s);
+// the tables: the covariance-only filter into ctb.ftab (launch_sparse16_cov_filter), then the smoother with its export on (both one wave).
+// gate: the device word for which the two kernels return at once (RTS_CTL_GATE)
+hipError_t launch_rts_shared_cov(const KArgs& a, int K, const SparseT* tabs_dev, RtsTabs& tb, const CovTabs& ctb, const int* gate, hipStream_t s);
+hipError_t launch_rts_shared_tables(const KArgs& a, int K, const SparseT* tabs_dev, const RtsTabs& tb, const int* gate, hipStream_t s);
 hipError_t launch_rts_shared_mark(const KArgs& a, unsigned char* route, const RtsTabs& tb, hipStream_t s);   // KArgs::route of the call from its observations; tb.gaps, tb.skip
 hipError_t launch_rts_shared_means(const KArgs& a, int K, const SparseT* tabs_dev, const RtsTabs& tb, bool own_rts, hipStream_t s);
 

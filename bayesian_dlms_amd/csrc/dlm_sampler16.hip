@@ -813,6 +813,52 @@ __global__ __launch_bounds__(256) void k_rts_decide(unsigned char* __restrict__ 
   if (sk && n < N) route[n] = 1;
 }
 
+// The kept tables (dlm_internal.h: RtsKeySrc, RTS_CTL_*).  Word i of a call's key: [d, T, K, flags, 0 x 4 | F (d) | V | W (d d) | C0 (d d) |
+// the row and column tables of G], doubles as two words each.
+__device__ __forceinline__ int rts_key_words(int d) { return 8 + 2 * (d + 1 + 2 * d * d) + 2 * (int)(sizeof(SparseT) / 4); }
+__device__ __forceinline__ unsigned rts_key_word(const RtsKeySrc& s, int i) {
+  if (i < 8) return i == 0 ? (unsigned)s.d : i == 1 ? (unsigned)s.T : i == 2 ? (unsigned)s.K : i == 3 ? s.flags : 0u;
+  i -= 8;
+  const int nf = 2 * s.d, nw = 2 * s.d * s.d;
+  const void* p = s.sp;
+  if (i < nf) p = s.F;
+  else if ((i -= nf) < 2) p = s.V;
+  else if ((i -= 2) < nw) p = s.W;
+  else if ((i -= nw) < nw) p = s.C0;
+  else i -= nw;
+  return ((const unsigned*)p)[i];
+}
+// One block, behind k_rts_decide.  A hit: the key of the kept tables is the call's, word for word.  A miss marks them invalid HERE, before the
+// table kernels of this call overwrite them; a call that makes no tables (skip: most of its series have a gap) leaves them as they are.
+__global__ __launch_bounds__(256) void k_rts_key_check(RtsKeySrc s, const unsigned* __restrict__ kept, int* __restrict__ ctl, int no_reuse) {
+  __shared__ int differs;
+  if (threadIdx.x == 0) differs = 0;
+  __syncthreads();
+  const int skip = ctl[9];
+  const bool compare = !no_reuse && !skip && ctl[RTS_CTL_VALID] != 0;
+  if (compare) {
+    bool df = false;
+    for (int i = threadIdx.x, n = rts_key_words(s.d); i < n; i += 256) df |= kept[i] != rts_key_word(s, i);
+    if (df) differs = 1;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int hit = (compare && !differs) ? 1 : 0;
+    ctl[RTS_CTL_HIT] = hit;
+    ctl[RTS_CTL_GATE] = (skip || hit) ? 1 : 0;
+    if (no_reuse || (!skip && !hit)) { ctl[RTS_CTL_VALID] = 0; ctl[0] = 0; }   // ([0]: the zero series' status, which the table run ORs into)
+    ctl[RTS_CTL_LAST] = skip ? DLM_TABLES_SKIPPED : hit ? DLM_TABLES_REUSED : DLM_TABLES_BUILT;
+  }
+}
+// One block, behind the table run on its stream: the tables are complete -- their key, then "valid"
+__global__ __launch_bounds__(256) void k_rts_key_commit(RtsKeySrc s, unsigned* __restrict__ kept, int* __restrict__ ctl, int no_reuse) {
+  if (no_reuse || ctl[RTS_CTL_GATE]) return;   // (no table run in this call)
+  for (int i = threadIdx.x, n = rts_key_words(s.d); i < n; i += 256) kept[i] = rts_key_word(s, i);
+  __threadfence();
+  __syncthreads();
+  if (threadIdx.x == 0) ctl[RTS_CTL_VALID] = 1;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // The reference's RTS smoother on the same register tiles: Smoothing.smoothStep / backwardsSmoother (Smoothing.scala:31-64),
 // from filter records alone (no innovations from a forward pass needed: serves dlm_smooth_batch and the literal mode).
@@ -1394,29 +1440,48 @@ bool rts_shared_eligible(const KArgs& a, bool textbook) {
   return sampler_shared_model_ok(a) && a.y && !(a.flags & (DLM_OPT_FORCE_GENERIC | DLM_OPT_SMOOTHER_PER_SERIES | DLM_OPT_NO_STEADY)) &&
          (a.N >= (textbook ? DLM_RTS_SHARED_MIN_TEXTBOOK : DLM_RTS_SHARED_MIN) || (a.flags & DLM_OPT_NO_SMALL_BATCH));
 }
+static size_t rts_key_bytes() { return up64((size_t)RTS_KEY_WORDS * 4); }
 size_t rts_shared_ws_bytes(const KArgs& a) {
   const size_t n1 = (size_t)a.T + 1, rec = (size_t)a.d + (size_t)a.d * a.d;
-  return up64(n1 * s16::RJ_ROW * 8) + up64(n1 * rec * 8) + up64(n1) + 64;   // (64: status block of 16 ints)
+  return 64 + rts_key_bytes() + up64(n1 * s16::RJ_ROW * 8) + up64(n1 * rec * 8) + up64(n1);   // (64: control block of 16 ints)
 }
-void rts_shared_carve(void* ws, const KArgs& a, RtsTabs& tb) {
+void rts_shared_carve(void* ws, const KArgs& a, RtsTabs& tb, RtsKeep& keep) {
   const size_t n1 = (size_t)a.T + 1, rec = (size_t)a.d + (size_t)a.d * a.d;
   char* p = (char*)ws;
+  keep.ctl = (int*)p; p += 64;
+  keep.key = (unsigned*)p; p += rts_key_bytes();
   tb.jrows = (double*)p; p += up64(n1 * s16::RJ_ROW * 8);
   tb.srec = (double*)p;  p += up64(n1 * rec * 8);
-  tb.need = (unsigned char*)p; p += up64(n1);
-  tb.status = (int*)p; tb.gaps = tb.status + 8; tb.skip = tb.status + 9;
+  tb.need = (unsigned char*)p;
+  tb.status = keep.ctl; tb.gaps = tb.status + 8; tb.skip = tb.status + 9;
   tb.crec = nullptr; tb.crec_stride = 0;
+}
+static RtsKeySrc rts_key_of(const KArgs& a, int K, const SparseT* tabs_dev) {
+  RtsKeySrc s;
+  s.d = a.d; s.T = a.T; s.K = K; s.flags = a.flags & RTS_KEY_FLAGS;
+  s.F = a.F; s.V = a.V; s.W = a.W; s.C0 = a.C0; s.sp = tabs_dev;
+  return s;
+}
+hipError_t launch_rts_key_check(const KArgs& a, int K, const SparseT* tabs_dev, const RtsKeep& keep, bool no_reuse, hipStream_t s) {
+  if (a.d < 1 || a.d > 15) return hipErrorInvalidValue;   // (the key's room: RTS_KEY_WORDS)
+  hipLaunchKernelGGL(s16::k_rts_key_check, dim3(1), dim3(256), 0, s, rts_key_of(a, K, tabs_dev), (const unsigned*)keep.key, keep.ctl, no_reuse ? 1 : 0);
+  return hipGetLastError();
+}
+hipError_t launch_rts_key_commit(const KArgs& a, int K, const SparseT* tabs_dev, const RtsKeep& keep, bool no_reuse, hipStream_t s) {
+  if (a.d < 1 || a.d > 15) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(s16::k_rts_key_commit, dim3(1), dim3(256), 0, s, rts_key_of(a, K, tabs_dev), keep.key, keep.ctl, no_reuse ? 1 : 0);
+  return hipGetLastError();
 }
 // the tables: the covariance-only filter (one wave; it stops where the recursion settles and a copy kernel fills the rows above) -- IN FRONT of
 // the batch's forward pass: beside it, with the memory system saturated by the batch's record stores, the one wave's dependent round trips
 // take ten times as long (0.22 -> 2.3 ms measured) -- then, beside the forward pass, the smoother with its export on, reading that table's rows
 // as its filter records
-hipError_t launch_rts_shared_cov(const KArgs& a, int K, const SparseT* tabs_dev, RtsTabs& tb, const CovTabs& ctb, hipStream_t s) {
+hipError_t launch_rts_shared_cov(const KArgs& a, int K, const SparseT* tabs_dev, RtsTabs& tb, const CovTabs& ctb, const int* gate, hipStream_t s) {
   KArgs kc = a;
   kc.smooth = nullptr; kc.filt = nullptr; kc.stats = nullptr; kc.theta = nullptr; kc.z = nullptr;
   tb.crec = ctb.ftab; tb.crec_stride = ctb.frow;
   CovTabs cs = ctb;
-  cs.skip = tb.skip;
+  cs.skip = gate;
   return launch_sparse16_cov_filter(kc, K, tabs_dev, cs, s);
 }
 // Dynamic LDS that, with the kernel's static LDS, fills a CU's 160 KB: no other workgroup that uses LDS -- every batch kernel of this library --
@@ -1437,7 +1502,9 @@ static size_t whole_cu_lds(F kernel) {
   static const size_t dyn = ask();
   return dyn;
 }
-hipError_t launch_rts_shared_tables(const KArgs& a, int K, const SparseT* tabs_dev, const RtsTabs& tb, hipStream_t s) {
+hipError_t launch_rts_shared_tables(const KArgs& a, int K, const SparseT* tabs_dev, const RtsTabs& tb0, const int* gate, hipStream_t s) {
+  RtsTabs tb = tb0;
+  tb.skip = const_cast<int*>(gate);   // (the kernel only reads it)
   KArgs kp = a;   // the covariances of every series without a missing observation, bit for bit
   kp.N = 1; kp.y = nullptr; kp.m0_stride = 0; kp.filt_in = nullptr; kp.filt = nullptr; kp.smooth = tb.srec; kp.status = tb.status; kp.stats = nullptr; kp.loglik = nullptr;
   kp.prior = nullptr; kp.fq = nullptr; kp.route = nullptr; kp.counters = nullptr; kp.theta = nullptr; kp.z = nullptr; kp.series_offset = 0; kp.plain = nullptr;
@@ -1464,7 +1531,7 @@ static hipError_t launch_mean_rts(const KArgs& a, const SparseT* sp, const RtsTa
 // route [N]: the series with a missing observation -- or, where more than half of them have one, every series (tb.skip: no tables)
 hipError_t launch_rts_shared_mark(const KArgs& a, unsigned char* route, const RtsTabs& tb, hipStream_t s) {
   if (!route || !a.y) return hipErrorInvalidValue;
-  hipError_t err = hipMemsetAsync(tb.status, 0, 16 * sizeof(int), s);   // the zero series' status, the gap count, the decision
+  hipError_t err = hipMemsetAsync(tb.gaps, 0, 2 * sizeof(int), s);   // the gap count, the decision (the zero series' status stays with the kept tables: k_rts_key_check)
   if (err != hipSuccess) return err;
   hipLaunchKernelGGL(s16::k_mark_gaps, dim3((a.N + 3) / 4), dim3(256), 0, s, a.y, a.N, a.T, route, tb.gaps);
   if ((err = hipGetLastError()) != hipSuccess) return err;

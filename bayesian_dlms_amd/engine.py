@@ -404,6 +404,13 @@ class Engine:
         self._check(self.lib.dlm_last_counters(self.h, ctypes.byref(c)))
         return tuple(int(v) for v in c)
 
+    def last_table_reuse(self):
+        """What the last filter_smooth call did about the shared RTS tables: _lib.TABLES_NONE / TABLES_BUILT / TABLES_REUSED /
+        TABLES_SKIPPED (dlm_last_table_reuse)."""
+        v = ctypes.c_int32(0)
+        self._check(self.lib.dlm_last_table_reuse(self.h, ctypes.byref(v)))
+        return int(v.value)
+
     def ffbs(self, mat, params, y, *, z=None, seed=0, series_offset=0, flags=0, want_theta=True,
              want_cond=False, want_stats=True, filt=None, want_filt=True):
         """FFBS (filt=None) or backward sampling from existing filter records (filt given).  want_filt=False: the forward

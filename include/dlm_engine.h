@@ -90,6 +90,9 @@ enum {
   DLM_OPT_SMOOTHER_PER_SERIES = 1u << 28, /* dlm_filter_smooth_batch with DLM_OPT_SMOOTHER_COMPAT_Q1, structured d <= 15, p = 1: every series computes its own J_t and
                                            S_t, also when the batch shares V, W, C0 on a regular grid (by default they are computed once per call and every series
                                            without a missing observation runs only its mean recursion: the same records, bit for bit) */
+  DLM_OPT_NO_TABLE_REUSE = 1u << 29,    /* dlm_filter_smooth_batch through the shared RTS tables: by default the engine keeps the tables of the last call that made
+                                           them and a later call whose d, T, F, G, V, W, C0 and semantics are byte for byte the same (compared on the device) uses them instead of
+                                           making them again: the same records, bit for bit.  With this flag a call makes its tables afresh and keeps none (dlm_last_table_reuse) */
   DLM_OPT_TEST_FAIL_AFTER_TABLES = 1u << 30, /* TEST HOOK (tests/test_shared_sampler_gpu.py, test_shared_rts_gpu.py): dlm_ffbs_batch / dlm_filter_smooth_batch return DLM_ERR_UNSUPPORTED right after they have started the
                                            shared-factor tables and normals on the engine's auxiliary streams -- the error path that must leave the engine usable */
   DLM_OPT_SHARED_COV = 1u << 24         /* d <= 15, p = 1, regular grid, V, W, C0 shared by the batch: ONE wave runs the covariance recursions, every series
@@ -317,6 +320,15 @@ int dlm_last_timing(dlm_engine *e, double ms[2]);
  *   out[3]  series of the same call that ran their own covariance recursion (a missing observation)
  * `bench.py` reports out[0..1] / (N T) as `steady_fraction`. */
 int dlm_last_counters(dlm_engine *e, uint64_t out[4]);
+
+/* What the LAST dlm_filter_smooth_batch call did about the shared RTS tables (synchronises the engine's stream): */
+enum {
+  DLM_TABLES_NONE = 0,     /* the call did not go through the shared tables (last variant other than "sparse16-rts-shared") */
+  DLM_TABLES_BUILT = 1,    /* it made them (and, without DLM_OPT_NO_TABLE_REUSE, kept them for the next call)              */
+  DLM_TABLES_REUSED = 2,   /* it found the kept tables' key equal to its own, byte for byte, and made none                  */
+  DLM_TABLES_SKIPPED = 3   /* most of its series had a missing observation: no tables, the kept ones untouched              */
+};
+int dlm_last_table_reuse(dlm_engine *e, int32_t *out);
 
 /* ---- FFBS + Gibbs sufficient statistics --------------------------------------------
  * Replaces Smoothing.ffbsDlm (Smoothing.scala:173-180) and, when `stats` is given, the

@@ -114,6 +114,13 @@ JNIEXPORT jlongArray JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_lastCounter
   return out;
 }
 
+// DLM_TABLES_* of the last filterSmooth call: 0 not through the shared RTS tables, 1 built, 2 reused, 3 skipped
+JNIEXPORT jint JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_lastTableReuse(JNIEnv* env, jobject, jlong h) {
+  int32_t v = 0;
+  if (throw_if(env, eng(h), dlm_last_table_reuse(eng(h), &v))) return 0;
+  return static_cast<jint>(v);
+}
+
 // ---- engine-owned device buffers ----------------------------------------------------------------------------------
 // address of a direct java.nio buffer (host mode, and the host side of upload / download)
 JNIEXPORT jlong JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_address(JNIEnv* env, jobject, jobject directBuffer) {

@@ -44,6 +44,7 @@ final class Native private[gpu] () {
   @native def streamWaitEngine(h: Long, stream: Long): Unit
   @native def lastTiming(h: Long): Array[Double]
   @native def lastCounters(h: Long): Array[Long]
+  @native def lastTableReuse(h: Long): Int
   @native def address(directBuffer: java.nio.Buffer): Long
   @native def bufferAlloc(h: Long, bytes: Long): Long
   @native def bufferFree(h: Long, dev: Long): Unit
@@ -96,6 +97,7 @@ object Native {
   val SamplerPerSeries = 1 << 26  // ffbs: every series its own J_t, H_t, chol(H_t) (default: once per call where V, W, C0 are shared -- the pooled Gibbs samplers; the same draws, bit for bit)
   val DrawEig = 1 << 27           // ffbs: draw with the reference's own factor, theta = h + E sqrt(Lambda) z from eigSym(H) (MultivariateGaussianSvd.scala:13-22), instead of the Cholesky factor
   val SmootherPerSeries = 1 << 28 // filterSmooth with SmootherCompatQ1: every series its own J_t, S_t (default: once per call where V, W, C0 are shared; the same records, bit for bit)
+  val NoTableReuse = 1 << 29      // filterSmooth through the shared RTS tables: make them afresh and keep none (default: a call whose model, V, W, C0 equal the last one's byte for byte reuses its tables; Native.lastTableReuse: 0 none, 1 built, 2 reused, 3 skipped)
   val NoSteady = 1 << 22          // every step recomputes the covariance recursion, also once it has settled (the reference's arithmetic, step for step)
   /** every reference quirk switched on: results are the reference's arithmetic, not the textbook's (SURVEY Q1 / Q2 / Q9) */
   val LiteralReference = SmootherCompatQ1 | SvdRawWQ2 | SvdSamplerQ9
