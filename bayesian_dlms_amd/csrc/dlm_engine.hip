@@ -14,30 +14,55 @@
 
 using dlm::KArgs;
 
+// A grow-only piece of device memory of the engine.  ensure() (below) is the one place that re-sizes one, dlm_engine_destroy the one
+// that frees them: every Ws member joins the engine's list when it is constructed.
+struct Workspace {
+  void* p = nullptr;
+  size_t bytes = 0;
+  Workspace* next;
+  explicit Workspace(Workspace*& list) : next(list) { list = this; }
+};
+template <class T>
+struct Ws : Workspace {
+  using Workspace::Workspace;
+  operator T*() const { return (T*)p; }
+};
+
 struct dlm_engine {
   int device = 0;
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
   std::string err;
   const char* variant = "none";
-  void* arena = nullptr;      // device staging arena for DLM_MEM_HOST calls
-  size_t arena_bytes = 0;
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // around the forward and backward kernels
   bool timed = false;
-  dlm::SparseT* sp_dev = nullptr;  // [2 n_g]: row table, column table of every G (structured fast path)
-  dlm::SparseBig* spb_dev = nullptr;   // the same for the tiled path (d up to 48)
-  dlm::SparseF* spf_dev = nullptr;     // tables of a structured F (tiled path)
-  size_t spb_count = 0;
-  size_t sp_count = 0;
+  // The workspaces, who lives in them during ONE call, and the streams that touch them (E: the engine's, C: cov_stream, R: rng_stream).
+  // Carves depend on the call's own d, T, N alone; only rtsws means anything to the call after.
+  //   arena     E C R  the staged buffers of a DLM_MEM_HOST call (Stager), 256-byte slots
+  //   sp_dev    E C    [2 n_g] row table, column table of every G (structured d <= 15 path)
+  //   spb_dev   E C    the same for the per-wave / tiled path (d up to 48)
+  //   fws       E      filtered records nobody asked for (packed on the structured path) | behind them the workspace of the Q7 log-likelihood
+  //   side      E      (e / Q, 1 / Q) per record, forward -> backward pass [N][T+1][2] | behind them CovTabs::eq [N][T+1]; the AR(1) records
+  //   xplus     E      x+ of the simulation smoother [N][T+1][d] | the compact means CovTabs::mc of the mean-only kernels
+  //   ystar     E      y - y+ of the simulation smoother, innovations of the tiled pass [N][T][p] | behind them the steady-step marks [N][T+1]
+  //   covws     E C    one of: the shared-covariance tables (4.9) | the forward covariance table of the shared RTS route | the SVD shared factors (4.10)
+  //   route     E C    one byte per series (which kernel serves it) | behind them, 64-byte aligned, KArgs::leave_step [N] (leave_of)
+  //   plainbuf  E      KArgs::plain of the call (k_count_gaps): one byte per series
+  //   sampws    E C    shared factors of the backward sampler (4.11): table, the zero series' records, flags
+  //   zws       E R    the call's normals in the draw kernel's layout
+  //   rtsws     E C    shared factors of the RTS smoother (4.13): control words, key and tables of the last call that made them -- kept
+  //                    across calls, so nobody else lives here; reused where k_rts_key_check finds the call's key equal to theirs
+  Workspace* workspaces = nullptr;   // (in front of the Ws members: they link themselves in)
+  Ws<void> arena{workspaces};
+  Ws<dlm::SparseT> sp_dev{workspaces};
+  Ws<dlm::SparseBig> spb_dev{workspaces};
+  Ws<double> fws{workspaces}, side{workspaces}, xplus{workspaces}, ystar{workspaces}, covws{workspaces};
+  Ws<unsigned char> route{workspaces}, plainbuf{workspaces};
+  Ws<void> sampws{workspaces};
+  Ws<double> zws{workspaces};
+  Ws<void> rtsws{workspaces};
+  dlm::SparseF* spf_dev = nullptr;     // tables of a structured F (tiled path), allocated once
   int sparse_k = 0;           // 0: some G is not structured (dense MFMA path, regular grids only)
-  double* fws = nullptr;      // filtered records of a fused call that does not want them (packed on the structured path)
-  size_t fws_bytes = 0;
-  double* side = nullptr;     // forward->backward innovations buffer of the fused fast path
-  size_t side_bytes = 0;
-  double* xplus = nullptr;    // simulated states x+ of the simulation smoother [N][T+1][d]
-  size_t xplus_bytes = 0;
-  double* ystar = nullptr;    // y - y+ of the simulation smoother (multivariate path) [N][T][p]
-  size_t ystar_bytes = 0;
   ncclComm_t comm = nullptr;
   bool has_comm = false;
   std::set<void*> buffers;     // dlm_buffer_alloc allocations still owned by the caller (released at destroy)
@@ -54,29 +79,18 @@ struct dlm_engine {
     std::vector<double> g_host, f_host;         // host-mode calls: the tables analysed
   } an;
   bool an_touched = true;
-  // shared-covariance path: the tables of the covariance-only run, one byte per series (route), and a second
-  // stream + events so that the backward covariance run overlaps the forward mean kernel
-  double* covws = nullptr;
-  size_t covws_bytes = 0;
-  unsigned char* route = nullptr;
-  size_t route_bytes = 0;
-  unsigned char* plainbuf = nullptr;   // KArgs::plain of the call (k_count_gaps): one byte per series
-  size_t plainbuf_bytes = 0;
-  void* sampws = nullptr;       // shared factors of the backward sampler: table, the zero series' records, flags
-  size_t sampws_bytes = 0;
-  double* zws = nullptr;        // ... and the call's normals in the draw kernel's layout, made on a third stream while the batch is filtered
-  size_t zws_bytes = 0;
-  void* rtsws = nullptr;        // shared factors of the RTS smoother: control words, key and tables of the last call that made them -- kept
-  size_t rtsws_bytes = 0;       //   across calls (nobody else carves it), reused where k_rts_key_check finds the call's key equal to theirs
-  bool rts_last = false;        // the last dlm_filter_smooth_batch call went through them (dlm_last_table_reuse)
+  bool rts_last = false;        // the last dlm_filter_smooth_batch call went through the tables of rtsws (dlm_last_table_reuse)
+  // the auxiliary streams: the one-wave table runs of the shared-covariance / shared-factor paths overlap the
+  // batch's forward kernel on cov_stream, the call's normals are made on rng_stream.  cov_ev[0] / the gate of aux_fork: a point of the engine's
+  // stream; cov_ev[1] / rng_ev: the stream's tail at its join
   hipStream_t rng_stream = nullptr;
   hipEvent_t rng_ev = nullptr;
   hipStream_t cov_stream = nullptr;
   hipEvent_t cov_ev[2] = {nullptr, nullptr};
   hipEvent_t rng_gate = nullptr;  // 16 <= d <= 48, records-free shared-factor FFBS: the end of the batch's forward pass, behind which the normals start
   hipEvent_t cov_ev2 = nullptr;   // behind the zero series' filter of a shared-factor table (its steady gain and settle step)
-  // work of the CURRENT call is (or may be) in flight on the auxiliary streams and e->stream does not depend on it yet: set when the
-  // first operation goes to the stream, cleared by aux_join / drain_all (the rules are written at aux_join)
+  // work of the CURRENT call is (or may be) in flight on the auxiliary streams and e->stream does not depend on it yet: set by aux_fork,
+  // cleared by join_cov / join_rng / drain_all (the rules are written at aux_fork)
   bool cov_busy = false, rng_busy = false;
   // DLM_OPT_COUNT_STEPS: [4] device counters the kernels add to (KArgs::counters), read by dlm_last_counters
   unsigned long long* counters = nullptr;
@@ -112,26 +126,35 @@ int promise_broken(dlm_engine* e) {
 // ---- the auxiliary streams (cov_stream: tables of the shared-covariance / shared-factor paths, raised priority; rng_stream: the
 // normals of a shared-factor call) -- who waits for whom.  Two rules, kept by every entry point:
 //   A. when an entry point returns -- success, error or "not eligible after all" -- e->stream depends on everything the call put on
-//      the auxiliary streams (aux_join; AuxScope does it on every exit path).  A caller that synchronises e->stream (every call
-//      without DLM_OPT_ASYNC does, dlm_engine_sync does) has therefore waited for the auxiliary work too, and the next call's work,
-//      whose auxiliary launches wait for an event recorded on e->stream, is ordered behind it.
-//   B. before a workspace any of the three streams may touch is freed or resized, before the engine moves to another stream and
-//      before it is destroyed, all three streams are drained on the host (drain_all).
+//      the auxiliary streams (join_cov / join_rng where the call wants the result; AuxScope on every other exit path).  A caller that
+//      synchronises e->stream (every call without DLM_OPT_ASYNC does, dlm_engine_sync does) has therefore waited for the auxiliary work
+//      too, and the next call's work, whose auxiliary launches wait for an event recorded on e->stream, is ordered behind it.
+//   B. before a workspace any of the three streams may touch is freed or resized (ensure), before the engine moves to another stream
+//      and before it is destroyed, all three streams are drained on the host (drain_all).
 // (Round 3 kept neither on its error paths: a return between start_sampler_tables and the hipStreamWaitEvent of the draw left kernels
 // on cov_stream / rng_stream reading the staging arena and e->sampws with nothing ordered behind them, the workspace re-size paths
 // synchronised e->stream alone, and dlm_engine_destroy freed buffers and destroyed streams with auxiliary work possibly in flight.)
-int aux_join(dlm_engine* e) {
-  if (e->cov_busy) {
-    e->cov_busy = false;   // (cleared first: a failing HIP call must not make every later exit path fail again)
-    HIP_TRY(e, hipEventRecord(e->cov_ev[1], e->cov_stream));            // everything queued on the stream so far
-    HIP_TRY(e, hipStreamWaitEvent(e->stream, e->cov_ev[1], 0));
-  }
-  if (e->rng_busy) {
-    e->rng_busy = false;
-    HIP_TRY(e, hipEventRecord(e->rng_ev, e->rng_stream));
-    HIP_TRY(e, hipStreamWaitEvent(e->stream, e->rng_ev, 0));
-  }
+// Fork: what e->stream holds up to `at` is visible to the auxiliary stream, which is busy from here on (every exit path joins it).
+// record = false: the caller recorded `at` on e->stream already (the gates of start_sampler_normals).
+int aux_fork(dlm_engine* e, hipStream_t aux, bool& busy, hipEvent_t at, bool record = true) {
+  if (record) HIP_TRY(e, hipEventRecord(at, e->stream));
+  busy = true;
+  HIP_TRY(e, hipStreamWaitEvent(aux, at, 0));
   return DLM_OK;
+}
+// Join: e->stream waits for everything queued on the auxiliary stream so far.  Nothing to do when the call put nothing there.
+int aux_join_one(dlm_engine* e, hipStream_t aux, bool& busy, hipEvent_t tail) {
+  if (!busy) return DLM_OK;
+  busy = false;   // (cleared first: a failing HIP call must not make every later exit path fail again)
+  HIP_TRY(e, hipEventRecord(tail, aux));
+  HIP_TRY(e, hipStreamWaitEvent(e->stream, tail, 0));
+  return DLM_OK;
+}
+int join_cov(dlm_engine* e) { return aux_join_one(e, e->cov_stream, e->cov_busy, e->cov_ev[1]); }
+int join_rng(dlm_engine* e) { return aux_join_one(e, e->rng_stream, e->rng_busy, e->rng_ev); }
+int aux_join(dlm_engine* e) {
+  const int rc = join_cov(e);
+  return rc ? rc : join_rng(e);
 }
 int drain_all(dlm_engine* e) {
   e->cov_busy = e->rng_busy = false;
@@ -145,6 +168,23 @@ struct AuxScope {   // rule A on every exit path of an entry point that may use 
   explicit AuxScope(dlm_engine* e_) : e(e_) {}
   ~AuxScope() { if (e && (e->cov_busy || e->rng_busy)) (void)aux_join(e); }
 };
+// Rule B in one place: `w` holds at least `need` bytes afterwards.  Grow-only; growing drains the three streams, frees, allocates anew
+// (the contents are gone: *fresh tells a caller that cares); a first allocation drains nothing; a failed hipMalloc leaves `w` empty.
+int ensure(dlm_engine* e, Workspace& w, size_t need, bool* fresh = nullptr) {
+  if (fresh) *fresh = false;
+  if (need <= w.bytes) return DLM_OK;
+  if (w.p) {
+    const int rc = drain_all(e);
+    if (rc) return rc;
+    HIP_TRY(e, hipFree(w.p));
+    w.p = nullptr;
+    w.bytes = 0;
+  }
+  HIP_TRY(e, hipMalloc(&w.p, need));
+  w.bytes = need;
+  if (fresh) *fresh = true;
+  return DLM_OK;
+}
 
 // Collects the buffers of one call.  Device mode: pointers pass through.  Host mode: every
 // buffer gets a slot in the engine's arena; inputs are copied up before the launch, outputs
@@ -166,15 +206,12 @@ class Stager {
     if (host_) {
       size_t need = 0;
       for (auto& b : bufs_) if (b.user) { b.offset = need; need += (b.bytes + 255) & ~(size_t)255; }
-      if (need > e_->arena_bytes) {
-        if (e_->arena) { { const int rcd = drain_all(e_); if (rcd) return rcd; } HIP_TRY(e_, hipFree(e_->arena)); e_->arena = nullptr; e_->arena_bytes = 0; }
-        HIP_TRY(e_, hipMalloc(&e_->arena, need));
-        e_->arena_bytes = need;
-      }
+      const int rc = ensure(e_, e_->arena, need);
+      if (rc) return rc;
     }
     for (auto& b : bufs_) {
       if (!b.user) { *b.field = nullptr; continue; }
-      void* dev = host_ ? (void*)((char*)e_->arena + b.offset) : b.user;
+      void* dev = host_ ? (void*)((char*)e_->arena.p + b.offset) : b.user;
       b.dev = dev;
       *b.field = dev;
       if (host_ && b.is_in) HIP_TRY(e_, hipMemcpyAsync(dev, b.user, b.bytes, hipMemcpyHostToDevice, e_->stream));
@@ -278,11 +315,7 @@ int analyse_g_tiled(dlm_engine* e, KArgs& k, const double* G_user, bool host_mod
   int K = 1;
   for (auto& t : tabs) K = t.K > K ? t.K : K;
   for (auto& t : tabs) t.K = K;
-  if (tabs.size() > e->spb_count) {
-    if (e->spb_dev) { { const int rcd = drain_all(e); if (rcd) return rcd; } HIP_TRY(e, hipFree(e->spb_dev)); e->spb_dev = nullptr; }
-    HIP_TRY(e, hipMalloc((void**)&e->spb_dev, tabs.size() * sizeof(dlm::SparseBig)));
-    e->spb_count = tabs.size();
-  }
+  { const int rc = ensure(e, e->spb_dev, tabs.size() * sizeof(dlm::SparseBig)); if (rc) return rc; }
   HIP_TRY(e, hipMemcpyAsync(e->spb_dev, tabs.data(), tabs.size() * sizeof(dlm::SparseBig), hipMemcpyHostToDevice, e->stream));
   HIP_TRY(e, hipStreamSynchronize(e->stream));  // tabs lives on this stack frame
   k.spb = e->spb_dev;
@@ -405,11 +438,7 @@ int analyse_g_fresh(dlm_engine* e, KArgs& k, const double* G_user, bool host_mod
     if (kq > 4) return DLM_OK;
     K = kq > K ? kq : K;
   }
-  if (tabs.size() > e->sp_count) {
-    if (e->sp_dev) { { const int rcd = drain_all(e); if (rcd) return rcd; } HIP_TRY(e, hipFree(e->sp_dev)); e->sp_dev = nullptr; }
-    HIP_TRY(e, hipMalloc((void**)&e->sp_dev, tabs.size() * sizeof(dlm::SparseT)));
-    e->sp_count = tabs.size();
-  }
+  { const int rc = ensure(e, e->sp_dev, tabs.size() * sizeof(dlm::SparseT)); if (rc) return rc; }
   HIP_TRY(e, hipMemcpyAsync(e->sp_dev, tabs.data(), tabs.size() * sizeof(dlm::SparseT), hipMemcpyHostToDevice, e->stream));
   HIP_TRY(e, hipStreamSynchronize(e->stream));  // tabs lives on this stack frame
   e->sparse_k = K;
@@ -423,45 +452,14 @@ int mark(dlm_engine* e, int i) {
   return DLM_OK;
 }
 
-int ensure_fws(dlm_engine* e, size_t need) {
-  if (need > e->fws_bytes) {
-    if (e->fws) { { const int rcd = drain_all(e); if (rcd) return rcd; } HIP_TRY(e, hipFree(e->fws)); e->fws = nullptr; e->fws_bytes = 0; }
-    HIP_TRY(e, hipMalloc((void**)&e->fws, need));
-    e->fws_bytes = need;
-  }
-  return DLM_OK;
-}
+// (e / Q, 1 / Q) per record for the per-series kernels, and behind them one double per record (e / Q) for the shared-covariance kernels
+int ensure_side(dlm_engine* e, size_t N, size_t T) { return ensure(e, e->side, sizeof(double) * 3 * N * (T + 1)); }
 
-int ensure_side(dlm_engine* e, const KArgs& k) {
-  // (e / Q, 1 / Q) per record for the per-series kernels, and behind them one double per record (e / Q) for the shared-covariance kernels
-  const size_t need = sizeof(double) * 3 * (size_t)k.N * ((size_t)k.T + 1);
-  if (need > e->side_bytes) {
-    if (e->side) { { const int rcd = drain_all(e); if (rcd) return rcd; } HIP_TRY(e, hipFree(e->side)); e->side = nullptr; e->side_bytes = 0; }
-    HIP_TRY(e, hipMalloc((void**)&e->side, need));
-    e->side_bytes = need;
-  }
-  return DLM_OK;
-}
-
-int ensure_xplus(dlm_engine* e, const KArgs& k) {
-  const size_t need = sizeof(double) * (size_t)k.N * ((size_t)k.T + 1) * (size_t)k.d;
-  if (need > e->xplus_bytes) {
-    if (e->xplus) { { const int rcd = drain_all(e); if (rcd) return rcd; } HIP_TRY(e, hipFree(e->xplus)); e->xplus = nullptr; e->xplus_bytes = 0; }
-    HIP_TRY(e, hipMalloc((void**)&e->xplus, need));
-    e->xplus_bytes = need;
-  }
-  return DLM_OK;
-}
+int ensure_xplus(dlm_engine* e, const KArgs& k) { return ensure(e, e->xplus, sizeof(double) * (size_t)k.N * ((size_t)k.T + 1) * (size_t)k.d); }
 
 int ensure_ystar(dlm_engine* e, const KArgs& k) {
   // innovations [N][T][p], then one byte per record [N][T+1]: the marks "C_t is C_{t-1}" of the per-wave forward kernel's steady steps
-  const size_t need = sizeof(double) * (size_t)k.N * (size_t)k.T * (size_t)k.p + (((size_t)k.N * (size_t)(k.T + 1) + 15) & ~(size_t)15);
-  if (need > e->ystar_bytes) {
-    if (e->ystar) { { const int rcd = drain_all(e); if (rcd) return rcd; } HIP_TRY(e, hipFree(e->ystar)); e->ystar = nullptr; e->ystar_bytes = 0; }
-    HIP_TRY(e, hipMalloc((void**)&e->ystar, need));
-    e->ystar_bytes = need;
-  }
-  return DLM_OK;
+  return ensure(e, e->ystar, sizeof(double) * (size_t)k.N * (size_t)k.T * (size_t)k.p + (((size_t)k.N * (size_t)(k.T + 1) + 15) & ~(size_t)15));
 }
 
 // DLM_OPT_PACKED_SYM is served by the structured d <= 15, p = 1 kernels (the lane kernels step aside for it)
@@ -480,23 +478,8 @@ bool use_shared_cov(const dlm_engine* e, const KArgs& k) {
 }
 // route: one byte per series; behind it (64-byte aligned) one int per series, the step a series left the per-wave filter at (KArgs::leave_step)
 size_t route_pad(size_t N) { return (N + 63) & ~(size_t)63; }
-int ensure_route(dlm_engine* e, size_t N) {
-  if (N > e->route_bytes) {
-    if (e->route) { { const int rcd = drain_all(e); if (rcd) return rcd; } HIP_TRY(e, hipFree(e->route)); e->route = nullptr; e->route_bytes = 0; }
-    HIP_TRY(e, hipMalloc((void**)&e->route, route_pad(N) + N * sizeof(int)));
-    e->route_bytes = N;
-  }
-  return DLM_OK;
-}
-int* leave_of(dlm_engine* e) { return (int*)(e->route + route_pad(e->route_bytes)); }
-int ensure_xplus_bytes(dlm_engine* e, size_t need) {
-  if (need > e->xplus_bytes) {
-    if (e->xplus) { { const int rcd = drain_all(e); if (rcd) return rcd; } HIP_TRY(e, hipFree(e->xplus)); e->xplus = nullptr; e->xplus_bytes = 0; }
-    HIP_TRY(e, hipMalloc((void**)&e->xplus, need));
-    e->xplus_bytes = need;
-  }
-  return DLM_OK;
-}
+int ensure_route(dlm_engine* e, size_t N) { return ensure(e, e->route, route_pad(N) + N * sizeof(int)); }
+int* leave_of(dlm_engine* e, size_t N) { return (int*)(e->route + route_pad(N)); }   // (N: the call's, as in its ensure_route)
 // Structured d <= 15 path on a regular grid: the series that miss more than T / 256 of their observations are marked (from the data
 // alone: the choice does not depend on the batch) and take every step in full -- the forward kernel without its convergence test, the
 // backward kernel in the instantiation without the shortcut's machinery.  With gaps nothing settles, and the machinery only costs.
@@ -504,11 +487,7 @@ int mark_plain(dlm_engine* e, KArgs& k) {
   k.plain = nullptr;
   if (!(fast_shape_ok(k) && e->sparse_k > 0) || use_lane(k) || !k.y || k.g_index || k.dt || k.f_stride || k.v_tstride || k.w_tstride ||
       (k.flags & DLM_OPT_NO_STEADY)) return DLM_OK;
-  if ((size_t)k.N > e->plainbuf_bytes) {
-    if (e->plainbuf) { { const int rcd = drain_all(e); if (rcd) return rcd; } HIP_TRY(e, hipFree(e->plainbuf)); e->plainbuf = nullptr; e->plainbuf_bytes = 0; }
-    HIP_TRY(e, hipMalloc((void**)&e->plainbuf, (size_t)k.N));
-    e->plainbuf_bytes = (size_t)k.N;
-  }
+  { const int rc = ensure(e, e->plainbuf, (size_t)k.N); if (rc) return rc; }
   HIP_TRY(e, dlm::launch_sparse16_count_gaps(k, e->plainbuf, e->stream));
   k.plain = e->plainbuf;
   return DLM_OK;
@@ -527,23 +506,14 @@ int ensure_cov_stream(dlm_engine* e) {
 // stream -- a filter and a sampler run of ONE wave on a series of zeros -- while the batch is filtered on the first.
 int start_sampler_normals(dlm_engine* e, const KArgs& k, dlm::SampTabs& tb, bool big, hipEvent_t gate);
 int start_sampler_tables(dlm_engine* e, const KArgs& k, dlm::SampTabs& tb, bool big, const double* crec = nullptr, int crec_stride = 0, bool defer_normals = false) {
-  const size_t need = big ? dlm::wave48_sampler_shared_ws_bytes(k) : dlm::sampler_shared_ws_bytes(k);
-  if (need > e->sampws_bytes) {
-    if (e->sampws) { { const int rcd = drain_all(e); if (rcd) return rcd; } HIP_TRY(e, hipFree(e->sampws)); e->sampws = nullptr; e->sampws_bytes = 0; }
-    HIP_TRY(e, hipMalloc(&e->sampws, need));
-    e->sampws_bytes = need;
-  }
-  int rc = ensure_route(e, (size_t)k.N);
-  if (rc || (rc = ensure_cov_stream(e))) return rc;
+  int rc = ensure(e, e->sampws, big ? dlm::wave48_sampler_shared_ws_bytes(k) : dlm::sampler_shared_ws_bytes(k));
+  if (rc || (rc = ensure_route(e, (size_t)k.N)) || (rc = ensure_cov_stream(e))) return rc;
   if (big) dlm::wave48_sampler_shared_carve(e->sampws, k, tb); else dlm::sampler_shared_carve(e->sampws, k, tb);
-  HIP_TRY(e, hipEventRecord(e->cov_ev[0], e->stream));               // the model and the tables of G are staged
-  e->cov_busy = true;                                                 // (from here on every exit path joins the stream: AuxScope)
-  HIP_TRY(e, hipStreamWaitEvent(e->cov_stream, e->cov_ev[0], 0));
+  if ((rc = aux_fork(e, e->cov_stream, e->cov_busy, e->cov_ev[0]))) return rc;   // the model and the tables of G are staged
   tb.zstride = 0; tb.mc4 = nullptr; tb.marked = 0;
   if (big) HIP_TRY(e, dlm::launch_wave48_sampler_shared_tables(k, tb, e->cov_stream, e->cov_ev2));
   else if (crec) HIP_TRY(e, dlm::launch_sampler_shared_tables_from(k, e->sparse_k, e->sp_dev, tb, crec, crec_stride, e->cov_stream));   // the covariances exist already
   else HIP_TRY(e, dlm::launch_sampler_shared_tables(k, e->sparse_k, e->sp_dev, tb, e->cov_stream));
-  HIP_TRY(e, hipEventRecord(e->cov_ev[1], e->cov_stream));
   tb.z4 = nullptr;
   if (defer_normals) return DLM_OK;   // (start_sampler_normals, behind the forward pass's launch)
   return start_sampler_normals(e, k, tb, big, e->cov_ev[0]);
@@ -553,21 +523,15 @@ int start_sampler_tables(dlm_engine* e, const KArgs& k, dlm::SampTabs& tb, bool 
 // kernel of forty million threads it started 0.4 ms late (the normals are wanted last, by the draw kernel; they now run beside k_steady_filter_w48).
 int start_sampler_normals(dlm_engine* e, const KArgs& k, dlm::SampTabs& tb, bool big, hipEvent_t gate) {
   if (!k.z) {
-    const size_t zb = big ? dlm::wave48_sampler_shared_normals_bytes(k) : dlm::sampler_shared_normals_bytes(k);
-    if (zb > e->zws_bytes) {
-      if (e->zws) { { const int rcd = drain_all(e); if (rcd) return rcd; } HIP_TRY(e, hipFree(e->zws)); e->zws = nullptr; e->zws_bytes = 0; }
-      HIP_TRY(e, hipMalloc((void**)&e->zws, zb));
-      e->zws_bytes = zb;
-    }
+    int rc = ensure(e, e->zws, big ? dlm::wave48_sampler_shared_normals_bytes(k) : dlm::sampler_shared_normals_bytes(k));
+    if (rc) return rc;
     if (!e->rng_stream) {
       HIP_TRY(e, hipStreamCreateWithFlags(&e->rng_stream, hipStreamNonBlocking));
       HIP_TRY(e, hipEventCreateWithFlags(&e->rng_ev, hipEventDisableTiming));
     }
-    e->rng_busy = true;
-    HIP_TRY(e, hipStreamWaitEvent(e->rng_stream, gate, 0));
+    if ((rc = aux_fork(e, e->rng_stream, e->rng_busy, gate, false))) return rc;
     if (big) HIP_TRY(e, dlm::launch_wave48_sampler_shared_normals(k, e->zws, e->rng_stream));
     else HIP_TRY(e, dlm::launch_sampler_shared_normals(k, e->zws, e->rng_stream));
-    HIP_TRY(e, hipEventRecord(e->rng_ev, e->rng_stream));
     tb.z4 = e->zws;
   }
   return DLM_OK;
@@ -577,21 +541,12 @@ int start_sampler_normals(dlm_engine* e, const KArgs& k, dlm::SampTabs& tb, bool
 // whose key equals theirs (k_rts_key_check, on the device: the host does not know hit from miss and queues the same launches either way) finds
 // the two one-wave kernels returning at once.  A re-size frees the old tables with the workspace; the new one starts invalid.
 int start_rts_tables(dlm_engine* e, const KArgs& k, dlm::RtsTabs& tb) {
-  const size_t need = dlm::rts_shared_ws_bytes(k);
-  if (need > e->rtsws_bytes) {
-    if (e->rtsws) { { const int rcd = drain_all(e); if (rcd) return rcd; } HIP_TRY(e, hipFree(e->rtsws)); e->rtsws = nullptr; e->rtsws_bytes = 0; }
-    HIP_TRY(e, hipMalloc(&e->rtsws, need));
-    e->rtsws_bytes = need;
-    HIP_TRY(e, hipMemsetAsync(e->rtsws, 0, 64, e->stream));   // the control words: no valid tables
-  }
-  const size_t cneed = sizeof(double) * dlm::covtabs_doubles(k.d, k.T);   // the forward covariance table of the shared-covariance kernels
-  if (cneed > e->covws_bytes) {
-    if (e->covws) { { const int rcd = drain_all(e); if (rcd) return rcd; } HIP_TRY(e, hipFree(e->covws)); e->covws = nullptr; e->covws_bytes = 0; }
-    HIP_TRY(e, hipMalloc((void**)&e->covws, cneed));
-    e->covws_bytes = cneed;
-  }
-  int rc = ensure_route(e, (size_t)k.N);
-  if (rc || (rc = ensure_cov_stream(e))) return rc;
+  bool fresh = false;
+  int rc = ensure(e, e->rtsws, dlm::rts_shared_ws_bytes(k), &fresh);
+  if (rc) return rc;
+  if (fresh) HIP_TRY(e, hipMemsetAsync(e->rtsws, 0, 64, e->stream));   // the control words: no valid tables
+  if ((rc = ensure(e, e->covws, sizeof(double) * dlm::covtabs_doubles(k.d, k.T)))) return rc;   // the forward covariance table of the shared-covariance kernels
+  if ((rc = ensure_route(e, (size_t)k.N)) || (rc = ensure_cov_stream(e))) return rc;
   dlm::RtsKeep keep{};
   dlm::rts_shared_carve(e->rtsws, k, tb, keep);
   dlm::CovTabs ctb{};
@@ -602,9 +557,7 @@ int start_rts_tables(dlm_engine* e, const KArgs& k, dlm::RtsTabs& tb) {
   HIP_TRY(e, dlm::launch_rts_shared_mark(k, e->route, tb, e->stream));                     // the series with a gap; where they are the majority, no tables (tb.skip)
   HIP_TRY(e, dlm::launch_rts_key_check(k, e->sparse_k, e->sp_dev, keep, no_reuse, e->stream));   // hit or miss; a miss marks the kept tables invalid before the kernels below overwrite them
   HIP_TRY(e, dlm::launch_rts_shared_cov(k, e->sparse_k, e->sp_dev, tb, ctb, gate, e->stream));   // the forward covariances: in front of the batch's forward pass
-  HIP_TRY(e, hipEventRecord(e->cov_ev[0], e->stream));
-  e->cov_busy = true;                                                 // (from here on every exit path joins the stream: AuxScope)
-  HIP_TRY(e, hipStreamWaitEvent(e->cov_stream, e->cov_ev[0], 0));
+  if ((rc = aux_fork(e, e->cov_stream, e->cov_busy, e->cov_ev[0]))) return rc;
   HIP_TRY(e, dlm::launch_rts_shared_tables(k, e->sparse_k, e->sp_dev, tb, gate, e->cov_stream));   // J_t, S_t: beside it
   // The table run keeps a whole CU to itself (whole_cu_lds): it has to be resident before the forward pass fills every CU with its
   // workgroups, or it waits for that kernel's last wave.  The caller launches the gap count of the forward pass (mark_plain: a 30 us kernel)
@@ -612,28 +565,17 @@ int start_rts_tables(dlm_engine* e, const KArgs& k, dlm::RtsTabs& tb) {
   // Behind a table run that ran: its key and "valid".  An error exit from here on leaves a complete set (every exit path joins the stream),
   // one before it leaves the set invalid.
   HIP_TRY(e, dlm::launch_rts_key_commit(k, e->sparse_k, e->sp_dev, keep, no_reuse, e->cov_stream));
-  HIP_TRY(e, hipEventRecord(e->cov_ev[1], e->cov_stream));
   return DLM_OK;
 }
 int ensure_shared(dlm_engine* e, const KArgs& k, dlm::CovTabs& tb, bool with_backward) {
-  const size_t need = sizeof(double) * dlm::covtabs_doubles(k.d, k.T);
-  if (need > e->covws_bytes) {
-    if (e->covws) { { const int rcd = drain_all(e); if (rcd) return rcd; } HIP_TRY(e, hipFree(e->covws)); e->covws = nullptr; e->covws_bytes = 0; }
-    HIP_TRY(e, hipMalloc((void**)&e->covws, need));
-    e->covws_bytes = need;
-  }
-  int rc = ensure_route(e, (size_t)k.N);
-  if (rc) return rc;
-  rc = ensure_side(e, k);
-  if (rc) return rc;
-  if ((rc = ensure_cov_stream(e))) return rc;
+  int rc = ensure(e, e->covws, sizeof(double) * dlm::covtabs_doubles(k.d, k.T));
+  if (rc || (rc = ensure_route(e, (size_t)k.N)) || (rc = ensure_side(e, k.N, k.T)) || (rc = ensure_cov_stream(e))) return rc;
   dlm::covtabs_carve(e->covws, k.d, k.T, tb);
   tb.eq = e->side + 2 * (size_t)k.N * ((size_t)k.T + 1);
   tb.mc = tb.sc = nullptr;
   if (with_backward) {   // compact means of the mean-only kernels: 512 bytes per step and group of four series, filtered then smoothed
     const size_t one = 64 * (size_t)((k.N + 3) / 4) * ((size_t)k.T + 1);
-    int rc2 = ensure_xplus_bytes(e, sizeof(double) * one);
-    if (rc2) return rc2;
+    if ((rc = ensure(e, e->xplus, sizeof(double) * one))) return rc;
     tb.mc = e->xplus;
   }
   return DLM_OK;
@@ -648,11 +590,8 @@ int run_shared_filter(dlm_engine* e, KArgs& k, dlm::CovTabs& tb, bool with_backw
   e->variant = "sparse16";   // (the same kernel family; dlm_last_counters[2] tells the series served by the shared-covariance kernels)
   HIP_TRY(e, dlm::launch_sparse16_cov_filter(k, e->sparse_k, e->sp_dev, tb, e->stream));
   if (with_backward) {
-    HIP_TRY(e, hipEventRecord(e->cov_ev[0], e->stream));
-    e->cov_busy = true;
-    HIP_TRY(e, hipStreamWaitEvent(e->cov_stream, e->cov_ev[0], 0));
+    if ((rc = aux_fork(e, e->cov_stream, e->cov_busy, e->cov_ev[0]))) return rc;
     HIP_TRY(e, dlm::launch_sparse16_cov_smoother(k, e->sparse_k, e->sp_dev, tb, e->cov_stream));
-    HIP_TRY(e, hipEventRecord(e->cov_ev[1], e->cov_stream));
   }
   HIP_TRY(e, dlm::launch_sparse16_mean_filter(k, e->sparse_k, e->sp_dev, tb, e->stream));
   KArgs kg = k;
@@ -661,8 +600,7 @@ int run_shared_filter(dlm_engine* e, KArgs& k, dlm::CovTabs& tb, bool with_backw
   return DLM_OK;
 }
 int run_shared_smoother(dlm_engine* e, KArgs& k, const dlm::CovTabs& tb) {
-  HIP_TRY(e, hipStreamWaitEvent(e->stream, e->cov_ev[1], 0));   // the S_t table
-  e->cov_busy = false;                                          // (cov_ev[1] was recorded behind the stream's last operation of this call)
+  { const int rc = join_cov(e); if (rc) return rc; }   // the S_t table
   HIP_TRY(e, dlm::launch_sparse16_mean_smoother(k, e->sparse_k, e->sp_dev, tb, e->stream));
   KArgs kg = k;
   kg.route_take = 1;
@@ -676,7 +614,7 @@ int run_filter(dlm_engine* e, const KArgs& k, bool want_side) {
     e->variant = "lane";
     HIP_TRY(e, dlm::launch_lane_filter(k, e->stream));
   } else if (use_fast(e, k) && (!k.prior || e->sparse_k)) {   // the dense-G MFMA kernel does not write (a, R) records
-    if (want_side) { int rc = ensure_side(e, k); if (rc) return rc; }
+    if (want_side) { int rc = ensure_side(e, k.N, k.T); if (rc) return rc; }
     double* side = want_side ? e->side : nullptr;
     if (e->sparse_k) {
       e->variant = "sparse16";
@@ -775,20 +713,8 @@ void dlm_engine_destroy(dlm_engine* e) {
   (void)hipSetDevice(e->device);
   (void)drain_all(e);   // rule B: nothing of a DLM_OPT_ASYNC call (or of a call that failed half-way) is in flight on any of the three streams
   if (e->has_comm) ncclCommDestroy(e->comm);
-  if (e->arena) (void)hipFree(e->arena);
-  if (e->side) (void)hipFree(e->side);
-  if (e->xplus) (void)hipFree(e->xplus);
-  if (e->ystar) (void)hipFree(e->ystar);
-  if (e->sp_dev) (void)hipFree(e->sp_dev);
-  if (e->fws) (void)hipFree(e->fws);
-  if (e->spb_dev) (void)hipFree(e->spb_dev);
+  for (Workspace* w = e->workspaces; w; w = w->next) if (w->p) (void)hipFree(w->p);
   if (e->spf_dev) (void)hipFree(e->spf_dev);
-  if (e->covws) (void)hipFree(e->covws);
-  if (e->route) (void)hipFree(e->route);
-  if (e->plainbuf) (void)hipFree(e->plainbuf);
-  if (e->sampws) (void)hipFree(e->sampws);
-  if (e->rtsws) (void)hipFree(e->rtsws);
-  if (e->zws) (void)hipFree(e->zws);
   if (e->rng_ev) (void)hipEventDestroy(e->rng_ev);
   if (e->rng_stream) (void)hipStreamDestroy(e->rng_stream);
   for (auto& ev : e->cov_ev) if (ev) (void)hipEventDestroy(ev);
@@ -846,7 +772,7 @@ int dlm_last_table_reuse(dlm_engine* e, int32_t* out) {
   if (!e->rts_last || !e->rtsws) return DLM_OK;
   HIP_TRY(e, hipSetDevice(e->device));
   int h = 0;
-  HIP_TRY(e, hipMemcpyAsync(&h, (const int*)e->rtsws + dlm::RTS_CTL_LAST, sizeof(h), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(&h, (const int*)e->rtsws.p + dlm::RTS_CTL_LAST, sizeof(h), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(e, hipStreamSynchronize(e->stream));
   *out = h;
   return DLM_OK;
@@ -1132,8 +1058,7 @@ static int ar1_common(dlm_engine* e, int32_t N, int32_t T, const double* times, 
   if ((rc = st.commit())) return rc;
   double* fws = k.filt;
   if (!fws) {   // the backward sampler reads the filter records: engine scratch when the caller does not want them
-    KArgs ks{}; ks.N = N; ks.T = T;
-    if ((rc = ensure_side(e, ks))) return rc;
+    if ((rc = ensure_side(e, n, t))) return rc;
     fws = e->side;
   }
   e->variant = ou ? "ou-lane" : "ar1-lane";
@@ -1162,12 +1087,12 @@ int dlm_loglik_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_param
     if (params->w_tstride) return fail(e, DLM_ERR_UNSUPPORTED, "DLM_OPT_LOGLIK_LITERAL_Q7 takes a time-invariant W (KalmanFilter.likelihood is given p.w)");
     const size_t d = model->d, rec = d + d * d;
     const size_t recs = N * (T + 1) * rec * sizeof(double), wsb = dlm::loglik_q7_ws_bytes(k);
-    if ((rc = ensure_fws(e, recs + wsb))) return rc;
+    if ((rc = ensure(e, e->fws, recs + wsb))) return rc;
     double* ll_out = k.loglik;
     k.filt = e->fws; k.loglik = nullptr;
     if ((rc = run_filter(e, k, false))) return rc;
     k.loglik = ll_out;
-    HIP_TRY(e, dlm::launch_loglik_q7(k, e->fws, (char*)e->fws + recs, e->stream));
+    HIP_TRY(e, dlm::launch_loglik_q7(k, e->fws, (char*)e->fws.p + recs, e->stream));
     return st.finish(opts->flags & DLM_OPT_ASYNC);
   }
   if ((rc = run_filter(e, k, false))) return rc;   // k.filt == nullptr: the forward kernels store nothing
@@ -1229,7 +1154,7 @@ int dlm_filter_smooth_batch(dlm_engine* e, const dlm_model_desc* model,
   //  them -- the RTS kernel per series is five times slower; literal Q1 has only that kernel)
   if (!filt) {   // smoothed moments only: the filtered records stay in an engine workspace, packed on the structured path
     k.packed |= (fast_smoother_ok(e, k) && e->sparse_k > 0 && !use_lane(k) && !rts_shared) ? 1 : 0;
-    if ((rc = ensure_fws(e, (k.packed & 1) ? N * (T + 1) * (size_t)dlm::packed_rec_bytes((int)d) : N * (T + 1) * rec * sizeof(double)))) return rc;
+    if ((rc = ensure(e, e->fws, (k.packed & 1) ? N * (T + 1) * (size_t)dlm::packed_rec_bytes((int)d) : N * (T + 1) * rec * sizeof(double)))) return rc;
     k.filt = e->fws;
   }
   if ((rc = mark(e, 0))) return rc;
@@ -1248,10 +1173,7 @@ int dlm_filter_smooth_batch(dlm_engine* e, const dlm_model_desc* model,
     return st.finish(opts->flags & DLM_OPT_ASYNC);
   }
   if ((rc = run_filter(e, k, fused_fast))) return rc;
-  if (rts_shared) {
-    HIP_TRY(e, hipStreamWaitEvent(e->stream, e->cov_ev[1], 0));   // the tables (in front of the timing mark: the backward time is the mean kernel's)
-    e->cov_busy = false;
-  }
+  if (rts_shared && (rc = join_cov(e))) return rc;   // the tables (in front of the timing mark: the backward time is the mean kernel's)
   if ((rc = mark(e, 1))) return rc;
   k.filt_in = k.filt;
   if (rts_shared) {
@@ -1266,6 +1188,89 @@ int dlm_filter_smooth_batch(dlm_engine* e, const dlm_model_desc* model,
   } else if ((rc = run_smoother(e, k, fused_fast))) return rc;
   if ((rc = mark(e, 2))) return rc;
   return st.finish(opts->flags & DLM_OPT_ASYNC);
+}
+
+// ---- the forward halves of dlm_ffbs_batch, one route each (sampler_common chooses).  The three simulation smoothers (Durbin-Koopman) are
+// the whole call: forward and backward pass, both timing marks.
+static int simsmooth_lane(dlm_engine* e, KArgs& k) {
+  int rc = ensure_xplus(e, k);
+  if (rc) return rc;
+  e->variant = "lane-simsmooth";
+  HIP_TRY(e, dlm::launch_lane_simsmooth(k, e->xplus, e->stream));
+  return (rc = mark(e, 1)) ? rc : mark(e, 2);
+}
+static int simsmooth_sparse16(dlm_engine* e, KArgs& k) {   // the structured d <= 15 path
+  int rc;
+  if ((rc = ensure_side(e, k.N, k.T)) || (rc = ensure_xplus(e, k))) return rc;
+  e->variant = "sparse16-simsmooth";
+  HIP_TRY(e, dlm::launch_sparse16_filter(k, e->sparse_k, e->sp_dev, e->side, e->xplus, e->stream));
+  if ((rc = mark(e, 1))) return rc;
+  k.filt_in = k.filt;
+  HIP_TRY(e, dlm::launch_sparse16_simsmooth(k, e->sparse_k, e->sp_dev, e->side, e->xplus, e->stream));
+  return mark(e, 2);
+}
+static int simsmooth_tiled(dlm_engine* e, KArgs& k) {      // per-wave / tiled kernels
+  int rc;
+  if (k.w_tstride) {   // a W_t stream (DlmFsvSystem.ffbs): the per-wave kernels, whose simulation prologue factors W_t at every step -- at any batch size
+    k.flags |= DLM_OPT_FORCE_WAVE;
+    if (!dlm::wave48_simsmooth_supported(k))
+      return fail(e, DLM_ERR_UNSUPPORTED, "a W_t stream with DLM_OPT_FFBS_SIMSMOOTH needs a structured G (at most four nonzeros per row and column); the reference-form sampler takes any model");
+  }
+  if ((rc = ensure_xplus(e, k)) || (rc = ensure_ystar(e, k))) return rc;
+  e->variant = dlm::wave48_simsmooth_supported(k) ? "wave-simsmooth" : "tiled-simsmooth";
+  HIP_TRY(e, dlm::launch_tiled_simsmooth(k, e->xplus, e->ystar, e->stream));
+  return (rc = mark(e, 1)) ? rc : mark(e, 2);
+}
+// No records AND shared factors (d <= 15): nothing of the filtered covariances is needed per series -- the draw kernel reads the
+// means, the table is made from the covariance recursion alone.  So the forward pass is section 4.9's: one wave's covariance
+// recursion into a table, a mean-only kernel per series (compact means, 128 instead of 1456 bytes per series-step at d = 13);
+// the table of factors is made from that covariance table while the mean kernel runs; a series with a missing observation is
+// marked by the mean kernel and runs its own filter and sampler on the workspace.
+static int forward_shared_means(dlm_engine* e, KArgs& k, dlm::SampTabs& stb) {
+  int rc;
+  dlm::CovTabs ctb;
+  if ((rc = ensure_shared(e, k, ctb, true))) return rc;
+  k.route = e->route; k.route_take = 0; k.filt = nullptr;
+  HIP_TRY(e, dlm::launch_sparse16_cov_filter(k, e->sparse_k, e->sp_dev, ctb, e->stream));
+  if ((rc = start_sampler_tables(e, k, stb, false, ctb.ftab, ctb.frow))) return rc;
+  if (k.flags & DLM_OPT_TEST_FAIL_AFTER_TABLES) return fail(e, DLM_ERR_UNSUPPORTED, "DLM_OPT_TEST_FAIL_AFTER_TABLES");
+  HIP_TRY(e, dlm::launch_sparse16_mean_filter(k, e->sparse_k, e->sp_dev, ctb, e->stream));
+  stb.mc4 = ctb.mc;
+  KArgs kg = k;
+  kg.route_take = 1; kg.filt = e->fws;
+  HIP_TRY(e, dlm::launch_sparse16_filter(kg, e->sparse_k, e->sp_dev, nullptr, nullptr, e->stream));
+  k.filt_in = e->fws;
+  return DLM_OK;
+}
+// Every other call: run_filter, with the tables (and normals) of a shared-factor draw started in front of it.  norec_big: 16 <= d <= 48,
+// shared factors and no records wanted.
+static int forward_records(dlm_engine* e, KArgs& k, dlm::SampTabs& stb, bool shared_factors, bool shared_big, bool norec_big) {
+  int rc;
+  // (norec_big: the normals start behind the forward pass: 8.64 -> 8.26 ms per C4 Gibbs iteration on one box)
+  if ((shared_factors || shared_big) && (rc = start_sampler_tables(e, k, stb, shared_big, nullptr, 0, norec_big))) return rc;
+  if ((shared_factors || shared_big) && (k.flags & DLM_OPT_TEST_FAIL_AFTER_TABLES))   // test hook: an error exit with the auxiliary streams busy
+    return fail(e, DLM_ERR_UNSUPPORTED, "DLM_OPT_TEST_FAIL_AFTER_TABLES");
+  if (norec_big) {
+    // the draw kernel reads only the means of the series without a gap, so those series' steady steps store the mean alone
+    // (KArgs::keep_cov; the first, full steps still write what the convergence test re-reads)
+    HIP_TRY(e, dlm::launch_wave48_mark_gaps(k, e->route, e->stream));
+    k.keep_cov = e->route;
+    k.ktab = stb.ktab;     // ... and they leave the filter where the recursion settles: k_steady_filter_w48 carries their means on
+    k.leave_step = leave_of(e, (size_t)k.N);
+    HIP_TRY(e, hipMemsetD32Async((hipDeviceptr_t)k.leave_step, k.T, (size_t)k.N, e->stream));   // T: the series ran the whole filter
+    stb.marked = 1;
+  }
+  if ((rc = run_filter(e, k, false))) return rc;
+  if (norec_big) {
+    if (!e->rng_gate) HIP_TRY(e, hipEventCreateWithFlags(&e->rng_gate, hipEventDisableTiming));
+    HIP_TRY(e, hipEventRecord(e->rng_gate, e->stream));
+    if ((rc = start_sampler_normals(e, k, stb, true, e->rng_gate))) return rc;
+    HIP_TRY(e, hipStreamWaitEvent(e->stream, e->cov_ev2, 0));   // the zero series' filter: the steady gain and the step it settled at
+    HIP_TRY(e, dlm::launch_wave48_steady_filter(k, stb.ktab, stb.settle, e->stream));
+  }
+  k.keep_cov = nullptr; k.ktab = nullptr; k.leave_step = nullptr;
+  k.filt_in = k.filt;
+  return DLM_OK;
 }
 
 static int sampler_common(dlm_engine* e, const dlm_model_desc* model, const dlm_params_desc* params,
@@ -1306,93 +1311,26 @@ static int sampler_common(dlm_engine* e, const dlm_model_desc* model, const dlm_
   // whether or not this call uses one -- a series' draws do not depend on the route it takes
   k.stretches = (dlm::sampler_shared_model_ok(k) || dlm::wave48_sampler_shared_model_ok(k)) ? 1 : 0;
   if (norec) {   // the records of the forward pass are nobody's output: an engine workspace
-    if ((rc = ensure_fws(e, N * (T + 1) * rec * sizeof(double)))) return rc;
+    if ((rc = ensure(e, e->fws, N * (T + 1) * rec * sizeof(double)))) return rc;
     k.filt = e->fws;
   }
   if (forward) {
     if ((rc = analyse_g(e, k, model->G, opts->mem == DLM_MEM_HOST))) return rc;
     if ((rc = mark(e, 0))) return rc;
-    if (simflag && use_lane(k) && !k.v_tstride && !k.w_tstride) {
-      if ((rc = ensure_xplus(e, k))) return rc;
-      e->variant = "lane-simsmooth";
-      HIP_TRY(e, dlm::launch_lane_simsmooth(k, e->xplus, e->stream));
-      if ((rc = mark(e, 1)) || (rc = mark(e, 2))) return rc;
-      return st.finish(opts->flags & DLM_OPT_ASYNC);
+    if (simflag) {
+      int (*sim)(dlm_engine*, KArgs&) = nullptr;
+      if (use_lane(k) && !k.v_tstride && !k.w_tstride) sim = simsmooth_lane;
+      else if (e->sparse_k) sim = simsmooth_sparse16;
+      else if (k.v_tstride || (k.w_tstride && !use_tiled(k)))
+        return fail(e, DLM_ERR_UNSUPPORTED, "a V_t / W_t stream with DLM_OPT_FFBS_SIMSMOOTH needs a structured G (this one is dense); V_t also p = 1");
+      else if (use_tiled(k)) sim = simsmooth_tiled;
+      else if (z) return fail(e, DLM_ERR_UNSUPPORTED, "injected normals with DLM_OPT_FFBS_SIMSMOOTH need a fast path (structured d <= 15 or 16 <= d <= 48)");
+      if (sim) return (rc = sim(e, k)) ? rc : st.finish(opts->flags & DLM_OPT_ASYNC);   // (otherwise: the reference-form sampler below)
     }
-    if (simflag && e->sparse_k) {
-      // Durbin-Koopman simulation smoother on the structured fast path
-      if ((rc = ensure_side(e, k)) || (rc = ensure_xplus(e, k))) return rc;
-      e->variant = "sparse16-simsmooth";
-      HIP_TRY(e, dlm::launch_sparse16_filter(k, e->sparse_k, e->sp_dev, e->side, e->xplus, e->stream));
-      if ((rc = mark(e, 1))) return rc;
-      k.filt_in = k.filt;
-      HIP_TRY(e, dlm::launch_sparse16_simsmooth(k, e->sparse_k, e->sp_dev, e->side, e->xplus, e->stream));
-      if ((rc = mark(e, 2))) return rc;
-      return st.finish(opts->flags & DLM_OPT_ASYNC);
-    }
-    if (simflag && (k.v_tstride || (k.w_tstride && !use_tiled(k))))
-      return fail(e, DLM_ERR_UNSUPPORTED, "a V_t / W_t stream with DLM_OPT_FFBS_SIMSMOOTH needs a structured G (this one is dense); V_t also p = 1");
-    if (simflag && use_tiled(k)) {
-      if (k.w_tstride) {   // a W_t stream (DlmFsvSystem.ffbs): the per-wave kernels, whose simulation prologue factors W_t at every step -- at any batch size
-        k.flags |= DLM_OPT_FORCE_WAVE;
-        if (!dlm::wave48_simsmooth_supported(k))
-          return fail(e, DLM_ERR_UNSUPPORTED, "a W_t stream with DLM_OPT_FFBS_SIMSMOOTH needs a structured G (at most four nonzeros per row and column); the reference-form sampler takes any model");
-      }
-      if ((rc = ensure_xplus(e, k)) || (rc = ensure_ystar(e, k))) return rc;
-      e->variant = dlm::wave48_simsmooth_supported(k) ? "wave-simsmooth" : "tiled-simsmooth";
-      HIP_TRY(e, dlm::launch_tiled_simsmooth(k, e->xplus, e->ystar, e->stream));
-      if ((rc = mark(e, 1)) || (rc = mark(e, 2))) return rc;
-      return st.finish(opts->flags & DLM_OPT_ASYNC);
-    }
-    if (simflag && z) return fail(e, DLM_ERR_UNSUPPORTED, "injected normals with DLM_OPT_FFBS_SIMSMOOTH need a fast path (structured d <= 15 or 16 <= d <= 48)");
     shared_factors = !simflag && !eig && !use_lane(k) && fast_shape_ok(k) && e->sparse_k > 0 && dlm::sampler_shared_eligible(k);
     shared_big = !simflag && !eig && !shared_factors && use_tiled(k) && dlm::wave48_sampler_shared_eligible(k);   // 16 <= d <= 48 on the per-wave kernels
-    if (norec && shared_factors) {
-      // No records AND shared factors (d <= 15): nothing of the filtered covariances is needed per series -- the draw kernel reads the
-      // means, the table is made from the covariance recursion alone.  So the forward pass is section 4.9's: one wave's covariance
-      // recursion into a table, a mean-only kernel per series (compact means, 128 instead of 1456 bytes per series-step at d = 13);
-      // the table of factors is made from that covariance table while the mean kernel runs; a series with a missing observation is
-      // marked by the mean kernel and runs its own filter and sampler on the workspace.
-      dlm::CovTabs ctb;
-      if ((rc = ensure_shared(e, k, ctb, true))) return rc;
-      k.route = e->route; k.route_take = 0; k.filt = nullptr;
-      HIP_TRY(e, dlm::launch_sparse16_cov_filter(k, e->sparse_k, e->sp_dev, ctb, e->stream));
-      if ((rc = start_sampler_tables(e, k, stb, false, ctb.ftab, ctb.frow))) return rc;
-      if (k.flags & DLM_OPT_TEST_FAIL_AFTER_TABLES) return fail(e, DLM_ERR_UNSUPPORTED, "DLM_OPT_TEST_FAIL_AFTER_TABLES");
-      HIP_TRY(e, dlm::launch_sparse16_mean_filter(k, e->sparse_k, e->sp_dev, ctb, e->stream));
-      stb.mc4 = ctb.mc;
-      KArgs kg = k;
-      kg.route_take = 1; kg.filt = e->fws;
-      HIP_TRY(e, dlm::launch_sparse16_filter(kg, e->sparse_k, e->sp_dev, nullptr, nullptr, e->stream));
-      k.filt_in = e->fws;
-    } else {
-      const bool defer_z = norec && shared_big;   // (the normals start behind the forward pass: 8.64 -> 8.26 ms per C4 Gibbs iteration on one box)
-      if ((shared_factors || shared_big) && (rc = start_sampler_tables(e, k, stb, shared_big, nullptr, 0, defer_z))) return rc;
-      if ((shared_factors || shared_big) && (k.flags & DLM_OPT_TEST_FAIL_AFTER_TABLES))   // test hook: an error exit with the auxiliary streams busy
-        return fail(e, DLM_ERR_UNSUPPORTED, "DLM_OPT_TEST_FAIL_AFTER_TABLES");
-      if (norec && shared_big) {
-        // 16 <= d <= 48, no records wanted: the draw kernel reads only the means of the series without a gap, so those series'
-        // steady steps store the mean alone (KArgs::keep_cov; the first, full steps still write what the convergence test re-reads)
-        HIP_TRY(e, dlm::launch_wave48_mark_gaps(k, e->route, e->stream));
-        k.keep_cov = e->route;
-        k.ktab = stb.ktab;     // ... and they leave the filter where the recursion settles: k_steady_filter_w48 carries their means on
-        k.leave_step = leave_of(e);
-        HIP_TRY(e, hipMemsetD32Async((hipDeviceptr_t)k.leave_step, k.T, (size_t)k.N, e->stream));   // T: the series ran the whole filter
-        stb.marked = 1;
-      }
-      if ((rc = run_filter(e, k, false))) return rc;
-      if (norec && shared_big) {
-        if (defer_z) {
-          if (!e->rng_gate) HIP_TRY(e, hipEventCreateWithFlags(&e->rng_gate, hipEventDisableTiming));
-          HIP_TRY(e, hipEventRecord(e->rng_gate, e->stream));
-          if ((rc = start_sampler_normals(e, k, stb, true, e->rng_gate))) return rc;
-        }
-        HIP_TRY(e, hipStreamWaitEvent(e->stream, e->cov_ev2, 0));   // the zero series' filter: the steady gain and the step it settled at
-        HIP_TRY(e, dlm::launch_wave48_steady_filter(k, stb.ktab, stb.settle, e->stream));
-      }
-      k.keep_cov = nullptr; k.ktab = nullptr; k.leave_step = nullptr;
-      k.filt_in = k.filt;
-    }
+    rc = norec && shared_factors ? forward_shared_means(e, k, stb) : forward_records(e, k, stb, shared_factors, shared_big, norec && shared_big);
+    if (rc) return rc;
   }
   if (!forward && ((rc = analyse_g(e, k, model->G, opts->mem == DLM_MEM_HOST)) || (rc = mark(e, 0)))) return rc;   // the structure tables of G
   if ((rc = mark(e, 1))) return rc;
@@ -1413,9 +1351,7 @@ static int sampler_common(dlm_engine* e, const dlm_model_desc* model, const dlm_
     // V, W, C0 shared by the batch on a regular grid: J_t, H_t and the factors once per call (the table of the second stream), the
     // series draw against it; a series with a missing observation computes its own as always
     e->variant = "sparse16-sampler-shared";
-    HIP_TRY(e, hipStreamWaitEvent(e->stream, e->cov_ev[1], 0));
-    e->cov_busy = false;
-    if (stb.z4) { HIP_TRY(e, hipStreamWaitEvent(e->stream, e->rng_ev, 0)); e->rng_busy = false; }
+    if ((rc = aux_join(e))) return rc;   // the tables, and the normals where the call makes them
     k.route = e->route;
     HIP_TRY(e, dlm::launch_sampler_shared_draw(k, e->sparse_k, e->sp_dev, stb, e->stream));
     return done();
@@ -1432,9 +1368,7 @@ static int sampler_common(dlm_engine* e, const dlm_model_desc* model, const dlm_
   }
   if (shared_big) {
     e->variant = "wave-sampler-shared";
-    HIP_TRY(e, hipStreamWaitEvent(e->stream, e->cov_ev[1], 0));
-    e->cov_busy = false;
-    if (stb.z4) { HIP_TRY(e, hipStreamWaitEvent(e->stream, e->rng_ev, 0)); e->rng_busy = false; }
+    if ((rc = aux_join(e))) return rc;   // the tables, and the normals where the call makes them
     k.route = e->route;
     HIP_TRY(e, dlm::launch_wave48_sampler_shared_draw(k, stb, e->stream));
     return done();
@@ -1487,12 +1421,7 @@ int dlm_svd_filter_batch(dlm_engine* e, const dlm_model_desc* model,
     // parameters shared by the batch: the decompositions once per call (one wave), a mean-only kernel per series; a series with a
     // missing observation runs k_svd_filter as always
     if ((rc = ensure_route(e, (size_t)k.N))) return rc;
-    const size_t need = sizeof(double) * dlm::svd_shared_ws_doubles(k);
-    if (need > e->covws_bytes) {
-      if (e->covws) { { const int rcd = drain_all(e); if (rcd) return rcd; } HIP_TRY(e, hipFree(e->covws)); e->covws = nullptr; e->covws_bytes = 0; }
-      HIP_TRY(e, hipMalloc((void**)&e->covws, need));
-      e->covws_bytes = need;
-    }
+    if ((rc = ensure(e, e->covws, sizeof(double) * dlm::svd_shared_ws_doubles(k)))) return rc;
     HIP_TRY(e, dlm::launch_svd_filter_shared(k, rec_dev, e->covws, e->route, e->stream));
   } else HIP_TRY(e, dlm::launch_svd_filter(k, rec_dev, e->stream));
   if ((rc = mark(e, 1)) || (rc = mark(e, 2))) return rc;
