@@ -167,11 +167,9 @@ __global__ __launch_bounds__(64) void k_ar1_ffbs(int N, int T, const double* __r
 hipError_t launch_ar1_ffbs(int N, int T, const double* times, const double* y, const double* v, long long v_stride,
                            const double* sv, long long sv_stride, const double* z, unsigned long long seed,
                            unsigned long long series_offset, double* filt, double* theta, int* status, hipStream_t s) {
-  if (times) hipLaunchKernelGGL(k_ar1_ffbs<true>, dim3((N + 63) / 64), dim3(64), 0, s, N, T, times, y, v, v_stride, sv,
-                                sv_stride, z, seed, series_offset, filt, theta, status);
-  else hipLaunchKernelGGL(k_ar1_ffbs<false>, dim3((N + 63) / 64), dim3(64), 0, s, N, T, times, y, v, v_stride, sv,
-                          sv_stride, z, seed, series_offset, filt, theta, status);
-  return hipGetLastError();
+  return pick_bool(times != nullptr, [&](auto OU) {   // the Ornstein-Uhlenbeck variant on a time grid
+    return launch(k_ar1_ffbs<OU()>, dim3((N + 63) / 64), dim3(64), 0, s, N, T, times, y, v, v_stride, sv, sv_stride, z, seed, series_offset, filt, theta, status);
+  });
 }
 
 }  // namespace dlm

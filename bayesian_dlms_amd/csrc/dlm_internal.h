@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace dlm {
 
@@ -81,6 +82,26 @@ template <int N>
 __device__ __forceinline__ void vm_wait() {
   static_assert(N >= 0 && N <= 63, "vmcnt holds 0..63");
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DLM_DRAIN_WAITS ? 0 : N) : "memory");
+}
+
+// ---- launchers: from run-time values to template arguments (host only) -------------------------------------------------
+// A kernel's template arguments are chosen by selection rules: pick / pick_bool hand the rule's value to a generic lambda as a
+// type (std::integral_constant: V() or decltype(V)::value is a constant expression there), and only the listed values are
+// instantiated.  Each rule is ONE function (with_* / pick in the kernel files); a table run that must use the per-series
+// launch's very instantiation goes through the same function (below the table of variants).
+template <int... Vs, class F>
+inline hipError_t pick(int v, F&& f) {   // f(integral_constant<int, V>) for the listed V equal to v; no such V: hipErrorInvalidValue
+  // (a LEFT fold: the compiler instantiates f for the listed values in their order, and the kernels stand in the code object in that order)
+  hipError_t err = hipErrorInvalidValue;
+  (void)(... || (v == Vs && ((err = f(std::integral_constant<int, Vs>{})), true)));
+  return err;
+}
+template <class F>
+inline hipError_t pick_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <class Kernel, class... Args>
+inline hipError_t launch(Kernel kernel, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, const Args&... args) {
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, s, args...);
+  return hipGetLastError();
 }
 
 // ---- generic wave-per-series kernels (any d <= 64, p <= 64), dlm_generic.hip ----------

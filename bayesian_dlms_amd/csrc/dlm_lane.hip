@@ -1018,46 +1018,26 @@ bool lane_supported(const KArgs& a) {
   return a.d >= 1 && a.d <= LANE_MAX_D && a.p == 1 && a.N >= LANE_MIN_N;
 }
 
-hipError_t launch_lane_filter(const KArgs& a, hipStream_t s) {
-  const dim3 grid((a.N + 63) / 64), block(64);
+// D = a.d (1..LANE_MAX_D): f(D)
+template <class F>
+static hipError_t with_lane_d(const KArgs& a, F f) { return pick<1, 2, 3, 4, 5>(a.d, f); }
+// ... and IRR (irregular grid, or F / V / W by time step): f(D, IRR)
+template <class F>
+static hipError_t with_lane_d_irr(const KArgs& a, F f) {
   const bool irr = a.g_index || a.dt || a.f_stride || a.v_tstride || a.w_tstride;
-  switch (a.d) {
-    case 1: if (irr) hipLaunchKernelGGL((lane::k_filter_lane<1, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((lane::k_filter_lane<1, false>), grid, block, 0, s, a); break;
-    case 2: if (irr) hipLaunchKernelGGL((lane::k_filter_lane<2, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((lane::k_filter_lane<2, false>), grid, block, 0, s, a); break;
-    case 3: if (irr) hipLaunchKernelGGL((lane::k_filter_lane<3, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((lane::k_filter_lane<3, false>), grid, block, 0, s, a); break;
-    case 4: if (irr) hipLaunchKernelGGL((lane::k_filter_lane<4, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((lane::k_filter_lane<4, false>), grid, block, 0, s, a); break;
-    case 5: if (irr) hipLaunchKernelGGL((lane::k_filter_lane<5, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((lane::k_filter_lane<5, false>), grid, block, 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_lane_d(a, [&](auto D) { return pick_bool(irr, [&](auto IRR) { return f(D, IRR); }); });
+}
+
+hipError_t launch_lane_filter(const KArgs& a, hipStream_t s) {
+  return with_lane_d_irr(a, [&](auto D, auto IRR) { return launch(lane::k_filter_lane<D(), IRR()>, dim3((a.N + 63) / 64), dim3(64), 0, s, a); });
 }
 
 hipError_t launch_lane_smoother(const KArgs& a, hipStream_t s) {
-  const dim3 grid((a.N + 63) / 64), block(64);
-  const bool irr = a.g_index || a.dt || a.f_stride || a.v_tstride || a.w_tstride;
-  switch (a.d) {
-    case 1: if (irr) hipLaunchKernelGGL((lane::k_smoother_lane<1, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((lane::k_smoother_lane<1, false>), grid, block, 0, s, a); break;
-    case 2: if (irr) hipLaunchKernelGGL((lane::k_smoother_lane<2, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((lane::k_smoother_lane<2, false>), grid, block, 0, s, a); break;
-    case 3: if (irr) hipLaunchKernelGGL((lane::k_smoother_lane<3, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((lane::k_smoother_lane<3, false>), grid, block, 0, s, a); break;
-    case 4: if (irr) hipLaunchKernelGGL((lane::k_smoother_lane<4, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((lane::k_smoother_lane<4, false>), grid, block, 0, s, a); break;
-    case 5: if (irr) hipLaunchKernelGGL((lane::k_smoother_lane<5, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((lane::k_smoother_lane<5, false>), grid, block, 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_lane_d_irr(a, [&](auto D, auto IRR) { return launch(lane::k_smoother_lane<D(), IRR()>, dim3((a.N + 63) / 64), dim3(64), 0, s, a); });
 }
 
-
 hipError_t launch_lane_sampler(const KArgs& a, hipStream_t s) {
-  const dim3 grid((a.N + 63) / 64), block(64);
-  switch (a.d) {
-    case 1: hipLaunchKernelGGL(lane::k_sampler_lane<1>, grid, block, 0, s, a); break;
-    case 2: hipLaunchKernelGGL(lane::k_sampler_lane<2>, grid, block, 0, s, a); break;
-    case 3: hipLaunchKernelGGL(lane::k_sampler_lane<3>, grid, block, 0, s, a); break;
-    case 4: hipLaunchKernelGGL(lane::k_sampler_lane<4>, grid, block, 0, s, a); break;
-    case 5: hipLaunchKernelGGL(lane::k_sampler_lane<5>, grid, block, 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_lane_d(a, [&](auto D) { return launch(lane::k_sampler_lane<D()>, dim3((a.N + 63) / 64), dim3(64), 0, s, a); });
 }
 
 // forward SIM pass (filt records + x+) followed by the mean-only backward pass; xplus [N][T+1][d] is engine workspace
@@ -1065,15 +1045,10 @@ hipError_t launch_lane_simsmooth(const KArgs& a, double* xplus, hipStream_t s) {
   const dim3 grid((a.N + 63) / 64), block(64);
   KArgs b = a;
   b.filt_in = a.filt;
-  switch (a.d) {
-    case 1: hipLaunchKernelGGL(lane::k_simfilter_lane<1>, grid, block, 0, s, a, xplus); hipLaunchKernelGGL(lane::k_simsmooth_lane<1>, grid, block, 0, s, b, (const double*)xplus); break;
-    case 2: hipLaunchKernelGGL(lane::k_simfilter_lane<2>, grid, block, 0, s, a, xplus); hipLaunchKernelGGL(lane::k_simsmooth_lane<2>, grid, block, 0, s, b, (const double*)xplus); break;
-    case 3: hipLaunchKernelGGL(lane::k_simfilter_lane<3>, grid, block, 0, s, a, xplus); hipLaunchKernelGGL(lane::k_simsmooth_lane<3>, grid, block, 0, s, b, (const double*)xplus); break;
-    case 4: hipLaunchKernelGGL(lane::k_simfilter_lane<4>, grid, block, 0, s, a, xplus); hipLaunchKernelGGL(lane::k_simsmooth_lane<4>, grid, block, 0, s, b, (const double*)xplus); break;
-    case 5: hipLaunchKernelGGL(lane::k_simfilter_lane<5>, grid, block, 0, s, a, xplus); hipLaunchKernelGGL(lane::k_simsmooth_lane<5>, grid, block, 0, s, b, (const double*)xplus); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_lane_d(a, [&](auto D) {
+    const hipError_t err = launch(lane::k_simfilter_lane<D()>, grid, block, 0, s, a, xplus);
+    return err != hipSuccess ? err : launch(lane::k_simsmooth_lane<D()>, grid, block, 0, s, b, (const double*)xplus);
+  });
 }
 
 }  // namespace dlm

@@ -1270,27 +1270,13 @@ __global__ __launch_bounds__(64, 3) void k_mean_rts16(KArgs a, const SparseT* __
 
 template <class Tab>
 static hipError_t launch_sampler_t(const KArgs& a, int K, const Tab* tabs_dev, hipStream_t s) {
-  switch (K) {
-    case 1: hipLaunchKernelGGL((s16::k_sampler_sp16<1, Tab>), dim3(a.N), dim3(64), 0, s, a, tabs_dev, SampTabs{}); break;
-    case 2: hipLaunchKernelGGL((s16::k_sampler_sp16<2, Tab>), dim3(a.N), dim3(64), 0, s, a, tabs_dev, SampTabs{}); break;
-    case 3: hipLaunchKernelGGL((s16::k_sampler_sp16<3, Tab>), dim3(a.N), dim3(64), 0, s, a, tabs_dev, SampTabs{}); break;
-    case 4: hipLaunchKernelGGL((s16::k_sampler_sp16<4, Tab>), dim3(a.N), dim3(64), 0, s, a, tabs_dev, SampTabs{}); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return pick<1, 2, 3, 4>(K, [&](auto k) { return launch(s16::k_sampler_sp16<k(), Tab>, dim3(a.N), dim3(64), 0, s, a, tabs_dev, SampTabs{}); });
 }
 hipError_t launch_sparse16_sampler(const KArgs& a, int K, const SparseT* tabs_dev, hipStream_t s) { return launch_sampler_t(a, K, tabs_dev, s); }
 
 template <class Tab>
 static hipError_t launch_rts_t(const KArgs& a, int K, const Tab* tabs_dev, hipStream_t s) {
-  switch (K) {
-    case 1: hipLaunchKernelGGL((s16::k_smoother_rts16<1, Tab>), dim3(a.N), dim3(64), 0, s, a, tabs_dev, RtsTabs{}); break;
-    case 2: hipLaunchKernelGGL((s16::k_smoother_rts16<2, Tab>), dim3(a.N), dim3(64), 0, s, a, tabs_dev, RtsTabs{}); break;
-    case 3: hipLaunchKernelGGL((s16::k_smoother_rts16<3, Tab>), dim3(a.N), dim3(64), 0, s, a, tabs_dev, RtsTabs{}); break;
-    case 4: hipLaunchKernelGGL((s16::k_smoother_rts16<4, Tab>), dim3(a.N), dim3(64), 0, s, a, tabs_dev, RtsTabs{}); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return pick<1, 2, 3, 4>(K, [&](auto k) { return launch(s16::k_smoother_rts16<k(), Tab>, dim3(a.N), dim3(64), 0, s, a, tabs_dev, RtsTabs{}); });
 }
 // ---- shared factors ------------------------------------------------------------------------------------------------------------
 #ifndef DLM_SAMPLER_SHARED_MIN
@@ -1320,6 +1306,11 @@ void sampler_shared_carve(void* ws, const KArgs& a, SampTabs& tb) {
   tb.need = (unsigned char*)p; p += up64(n1);
   tb.status = (int*)p; tb.settle = tb.status + 1;
 }
+// the table run of both launch_sampler_shared_tables*: the sampler with its export on, on the records of the series of zeros kp
+static hipError_t launch_sampler_table_run(const KArgs& kp, int K, const SparseT* tabs_dev, const SampTabs& tb, hipStream_t s) {
+  const dim3 grid(s16::sf_stretches(kp.T));   // one wave per stretch
+  return pick<1, 2, 3, 4>(K, [&](auto k) { return launch(s16::k_sampler_sp16<k(), SparseT, true>, grid, dim3(64), 0, s, kp, tabs_dev, tb); });
+}
 hipError_t launch_sampler_shared_tables(const KArgs& a, int K, const SparseT* tabs_dev, const SampTabs& tb, hipStream_t s) {
   hipError_t err = hipMemsetAsync(tb.zeros, 0, (size_t)(a.T > 16 ? a.T : 16) * 8, s);
   if (err != hipSuccess) return err;
@@ -1330,27 +1321,17 @@ hipError_t launch_sampler_shared_tables(const KArgs& a, int K, const SparseT* ta
   if ((err = launch_sparse16_filter(kf, K, tabs_dev, nullptr, nullptr, s)) != hipSuccess) return err;
   KArgs kp = kf;
   kp.y = nullptr; kp.filt_in = tb.zrec;
-  const dim3 grid(s16::sf_stretches(a.T));   // one wave per stretch
-  switch (K) {
-    case 1: hipLaunchKernelGGL((s16::k_sampler_sp16<1, SparseT, true>), grid, dim3(64), 0, s, kp, tabs_dev, tb); break;
-    case 2: hipLaunchKernelGGL((s16::k_sampler_sp16<2, SparseT, true>), grid, dim3(64), 0, s, kp, tabs_dev, tb); break;
-    case 3: hipLaunchKernelGGL((s16::k_sampler_sp16<3, SparseT, true>), grid, dim3(64), 0, s, kp, tabs_dev, tb); break;
-    case 4: hipLaunchKernelGGL((s16::k_sampler_sp16<4, SparseT, true>), grid, dim3(64), 0, s, kp, tabs_dev, tb); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return launch_sampler_table_run(kp, K, tabs_dev, tb, s);
 }
-template <int K, bool ZD>
+// k_mean_sampler_sp16<K, NR, ZD>.  NR: DMA instructions per table row, min(4, ceil(17 d / 64)); ZD: the normals come from SampTabs::z4 (none injected)
+template <int K>
 static hipError_t launch_mean_sampler(const KArgs& a, const SparseT* sp, const SampTabs& tb, hipStream_t s) {
-  const dim3 grid((a.N + 3) / 4), blk(64);
   const int nr = (17 * a.d + 63) / 64;
-  switch (nr) {
-    case 1: hipLaunchKernelGGL((s16::k_mean_sampler_sp16<K, 1, ZD>), grid, blk, 0, s, a, sp, tb); break;
-    case 2: hipLaunchKernelGGL((s16::k_mean_sampler_sp16<K, 2, ZD>), grid, blk, 0, s, a, sp, tb); break;
-    case 3: hipLaunchKernelGGL((s16::k_mean_sampler_sp16<K, 3, ZD>), grid, blk, 0, s, a, sp, tb); break;
-    default: hipLaunchKernelGGL((s16::k_mean_sampler_sp16<K, 4, ZD>), grid, blk, 0, s, a, sp, tb); break;
-  }
-  return hipGetLastError();
+  return pick_bool(a.z != nullptr, [&](auto INJECTED) {
+    return pick<1, 2, 3, 4>(nr < 4 ? nr : 4, [&](auto NR) {
+      return launch(s16::k_mean_sampler_sp16<K, NR(), !decltype(INJECTED)::value>, dim3((a.N + 3) / 4), dim3(64), 0, s, a, sp, tb);
+    });
+  });
 }
 // The normals of the whole call in the draw kernel's layout, made while the batch is filtered: they are a third of the draw
 // kernel's instructions otherwise, in its dependent chain.  One wave per group of four series and 16 steps; lane 16 j + c makes the
@@ -1378,8 +1359,7 @@ __global__ __launch_bounds__(256) void k_normals4(KArgs a, double* __restrict__ 
 size_t sampler_shared_normals_bytes(const KArgs& a) { return (size_t)((a.N + 3) / 4) * ((size_t)a.T + 1) * 512; }
 hipError_t launch_sampler_shared_normals(const KArgs& a, double* z4, hipStream_t s) {
   const long long waves = (long long)((a.N + 3) / 4) * ((a.T + 16) / 16);
-  hipLaunchKernelGGL(k_normals4, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, a, z4);
-  return hipGetLastError();
+  return launch(k_normals4, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, a, z4);
 }
 hipError_t launch_sampler_shared_tables_from(const KArgs& a, int K, const SparseT* tabs_dev, SampTabs tb, const double* crec, int stride, hipStream_t s) {
   hipError_t err = hipMemsetAsync(tb.status, 0, sizeof(int), s);
@@ -1388,35 +1368,18 @@ hipError_t launch_sampler_shared_tables_from(const KArgs& a, int K, const Sparse
   kp.N = 1; kp.y = nullptr; kp.filt_in = crec; kp.filt = nullptr; kp.status = tb.status; kp.stats = nullptr; kp.loglik = nullptr; kp.prior = nullptr; kp.fq = nullptr;
   kp.route = nullptr; kp.counters = nullptr; kp.theta = nullptr; kp.z = nullptr; kp.series_offset = 0; kp.m0_stride = 0;
   tb.zstride = stride;
-  const dim3 grid(s16::sf_stretches(a.T));
-  switch (K) {
-    case 1: hipLaunchKernelGGL((s16::k_sampler_sp16<1, SparseT, true>), grid, dim3(64), 0, s, kp, tabs_dev, tb); break;
-    case 2: hipLaunchKernelGGL((s16::k_sampler_sp16<2, SparseT, true>), grid, dim3(64), 0, s, kp, tabs_dev, tb); break;
-    case 3: hipLaunchKernelGGL((s16::k_sampler_sp16<3, SparseT, true>), grid, dim3(64), 0, s, kp, tabs_dev, tb); break;
-    case 4: hipLaunchKernelGGL((s16::k_sampler_sp16<4, SparseT, true>), grid, dim3(64), 0, s, kp, tabs_dev, tb); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return launch_sampler_table_run(kp, K, tabs_dev, tb, s);
 }
 hipError_t launch_sampler_shared_draw(const KArgs& a, int K, const SparseT* tabs_dev, const SampTabs& tb, hipStream_t s) {
   if (!a.route) return hipErrorInvalidValue;
   hipError_t err;
   if (tb.mc4) { /* the mean-only forward kernel has marked the series it left */ }
-  else if (a.y) hipLaunchKernelGGL(s16::k_mark_gaps, dim3((a.N + 3) / 4), dim3(256), 0, s, a.y, a.N, a.T, a.route, (int*)nullptr);
-  else if ((err = hipMemsetAsync(a.route, 0, (size_t)a.N, s)) != hipSuccess) return err;
-  if ((err = hipGetLastError()) != hipSuccess) return err;
+  else if ((err = a.y ? launch(s16::k_mark_gaps, dim3((a.N + 3) / 4), dim3(256), 0, s, a.y, a.N, a.T, a.route, (int*)nullptr)
+                      : hipMemsetAsync(a.route, 0, (size_t)a.N, s)) != hipSuccess) return err;
   KArgs km = a;
   km.route_take = 0;
   if (!a.z && !tb.z4) return hipErrorInvalidValue;   // the normals: injected, or made by launch_sampler_shared_normals
-#define DLM_MS(KK) err = a.z ? launch_mean_sampler<KK, false>(km, tabs_dev, tb, s) : launch_mean_sampler<KK, true>(km, tabs_dev, tb, s)
-  switch (K) {
-    case 1: DLM_MS(1); break;
-    case 2: DLM_MS(2); break;
-    case 3: DLM_MS(3); break;
-    case 4: DLM_MS(4); break;
-    default: return hipErrorInvalidValue;
-  }
-#undef DLM_MS
+  err = pick<1, 2, 3, 4>(K, [&](auto k) { return launch_mean_sampler<k()>(km, tabs_dev, tb, s); });
   if (err != hipSuccess) return err;
   KArgs kg = a;   // the series with a missing observation: their own factors
   kg.route_take = 1;
@@ -1464,13 +1427,11 @@ static RtsKeySrc rts_key_of(const KArgs& a, int K, const SparseT* tabs_dev) {
 }
 hipError_t launch_rts_key_check(const KArgs& a, int K, const SparseT* tabs_dev, const RtsKeep& keep, bool no_reuse, hipStream_t s) {
   if (a.d < 1 || a.d > 15) return hipErrorInvalidValue;   // (the key's room: RTS_KEY_WORDS)
-  hipLaunchKernelGGL(s16::k_rts_key_check, dim3(1), dim3(256), 0, s, rts_key_of(a, K, tabs_dev), (const unsigned*)keep.key, keep.ctl, no_reuse ? 1 : 0);
-  return hipGetLastError();
+  return launch(s16::k_rts_key_check, dim3(1), dim3(256), 0, s, rts_key_of(a, K, tabs_dev), (const unsigned*)keep.key, keep.ctl, no_reuse ? 1 : 0);
 }
 hipError_t launch_rts_key_commit(const KArgs& a, int K, const SparseT* tabs_dev, const RtsKeep& keep, bool no_reuse, hipStream_t s) {
   if (a.d < 1 || a.d > 15) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(s16::k_rts_key_commit, dim3(1), dim3(256), 0, s, rts_key_of(a, K, tabs_dev), keep.key, keep.ctl, no_reuse ? 1 : 0);
-  return hipGetLastError();
+  return launch(s16::k_rts_key_commit, dim3(1), dim3(256), 0, s, rts_key_of(a, K, tabs_dev), keep.key, keep.ctl, no_reuse ? 1 : 0);
 }
 // the tables: the covariance-only filter (one wave; it stops where the recursion settles and a copy kernel fills the rows above) -- IN FRONT of
 // the batch's forward pass: beside it, with the memory system saturated by the batch's record stores, the one wave's dependent round trips
@@ -1508,35 +1469,28 @@ hipError_t launch_rts_shared_tables(const KArgs& a, int K, const SparseT* tabs_d
   KArgs kp = a;   // the covariances of every series without a missing observation, bit for bit
   kp.N = 1; kp.y = nullptr; kp.m0_stride = 0; kp.filt_in = nullptr; kp.filt = nullptr; kp.smooth = tb.srec; kp.status = tb.status; kp.stats = nullptr; kp.loglik = nullptr;
   kp.prior = nullptr; kp.fq = nullptr; kp.route = nullptr; kp.counters = nullptr; kp.theta = nullptr; kp.z = nullptr; kp.series_offset = 0; kp.plain = nullptr;
-  switch (K) {
-    case 1: hipLaunchKernelGGL((s16::k_smoother_rts16<1, SparseT, true>), dim3(1), dim3(64), whole_cu_lds<1>(s16::k_smoother_rts16<1, SparseT, true>), s, kp, tabs_dev, tb); break;
-    case 2: hipLaunchKernelGGL((s16::k_smoother_rts16<2, SparseT, true>), dim3(1), dim3(64), whole_cu_lds<2>(s16::k_smoother_rts16<2, SparseT, true>), s, kp, tabs_dev, tb); break;
-    case 3: hipLaunchKernelGGL((s16::k_smoother_rts16<3, SparseT, true>), dim3(1), dim3(64), whole_cu_lds<3>(s16::k_smoother_rts16<3, SparseT, true>), s, kp, tabs_dev, tb); break;
-    case 4: hipLaunchKernelGGL((s16::k_smoother_rts16<4, SparseT, true>), dim3(1), dim3(64), whole_cu_lds<4>(s16::k_smoother_rts16<4, SparseT, true>), s, kp, tabs_dev, tb); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return pick<1, 2, 3, 4>(K, [&](auto k) {
+    const auto kernel = s16::k_smoother_rts16<k(), SparseT, true>;
+    return launch(kernel, dim3(1), dim3(64), whole_cu_lds<k()>(kernel), s, kp, tabs_dev, tb);
+  });
 }
 template <int K>
 static hipError_t launch_mean_rts(const KArgs& a, const SparseT* sp, const RtsTabs& tb, hipStream_t s) {
   const dim3 grid((a.N + 3) / 4), blk(64);
-  const int d = a.d;   // store / DMA instructions per step: see k_mean_rts16
-  if (d <= 7) hipLaunchKernelGGL((s16::k_mean_rts16<K, 2, 1, 1>), grid, blk, 0, s, a, sp, tb);
-  else if (d <= 10) hipLaunchKernelGGL((s16::k_mean_rts16<K, 4, 1, 2>), grid, blk, 0, s, a, sp, tb);
-  else if (d <= 13) hipLaunchKernelGGL((s16::k_mean_rts16<K, 6, 2, 2>), grid, blk, 0, s, a, sp, tb);
-  else if (d == 14) hipLaunchKernelGGL((s16::k_mean_rts16<K, 8, 2, 2>), grid, blk, 0, s, a, sp, tb);
-  else hipLaunchKernelGGL((s16::k_mean_rts16<K, 8, 2, 3>), grid, blk, 0, s, a, sp, tb);
-  return hipGetLastError();
+  // (NP, NRS, NRJ) -- store / DMA instructions per step: see k_mean_rts16 -- for d <= 7, <= 10, <= 13, 14, 15
+  constexpr int shape[5][3] = {{2, 1, 1}, {4, 1, 2}, {6, 2, 2}, {8, 2, 2}, {8, 2, 3}};
+  const int d = a.d;
+  return pick<0, 1, 2, 3, 4>(d <= 7 ? 0 : d <= 10 ? 1 : d <= 13 ? 2 : d == 14 ? 3 : 4, [&](auto c) {
+    return launch(s16::k_mean_rts16<K, shape[c()][0], shape[c()][1], shape[c()][2]>, grid, blk, 0, s, a, sp, tb);
+  });
 }
 // route [N]: the series with a missing observation -- or, where more than half of them have one, every series (tb.skip: no tables)
 hipError_t launch_rts_shared_mark(const KArgs& a, unsigned char* route, const RtsTabs& tb, hipStream_t s) {
   if (!route || !a.y) return hipErrorInvalidValue;
   hipError_t err = hipMemsetAsync(tb.gaps, 0, 2 * sizeof(int), s);   // the gap count, the decision (the zero series' status stays with the kept tables: k_rts_key_check)
   if (err != hipSuccess) return err;
-  hipLaunchKernelGGL(s16::k_mark_gaps, dim3((a.N + 3) / 4), dim3(256), 0, s, a.y, a.N, a.T, route, tb.gaps);
-  if ((err = hipGetLastError()) != hipSuccess) return err;
-  hipLaunchKernelGGL(s16::k_rts_decide, dim3((a.N + 255) / 256), dim3(256), 0, s, route, a.N, (const int*)tb.gaps, tb.skip);
-  return hipGetLastError();
+  if ((err = launch(s16::k_mark_gaps, dim3((a.N + 3) / 4), dim3(256), 0, s, a.y, a.N, a.T, route, tb.gaps)) != hipSuccess) return err;
+  return launch(s16::k_rts_decide, dim3((a.N + 255) / 256), dim3(256), 0, s, route, a.N, (const int*)tb.gaps, tb.skip);
 }
 // a.route [N] as launch_rts_shared_mark left it; the mean-only kernel smooths the series without a gap, k_smoother_rts16 the others
 // (own_rts; otherwise the caller launches its per-series kernel for them)
@@ -1545,13 +1499,7 @@ hipError_t launch_rts_shared_means(const KArgs& a, int K, const SparseT* tabs_de
   hipError_t err;
   KArgs km = a;
   km.route_take = 0;
-  switch (K) {
-    case 1: err = launch_mean_rts<1>(km, tabs_dev, tb, s); break;
-    case 2: err = launch_mean_rts<2>(km, tabs_dev, tb, s); break;
-    case 3: err = launch_mean_rts<3>(km, tabs_dev, tb, s); break;
-    case 4: err = launch_mean_rts<4>(km, tabs_dev, tb, s); break;
-    default: return hipErrorInvalidValue;
-  }
+  err = pick<1, 2, 3, 4>(K, [&](auto k) { return launch_mean_rts<k()>(km, tabs_dev, tb, s); });
   if (err != hipSuccess || !own_rts) return err;
   KArgs kg = a;   // the series with a missing observation: their own J_t, S_t
   kg.route_take = 1;

@@ -1753,63 +1753,58 @@ int sparse16_analyse(const double* G /* d x d column-major, host */, int d, Spar
 // over all CUs one by one instead of four at a time (at 1250 series: 5 waves on almost every CU instead of 8 on 57 of them).
 static int waves_per_block(const KArgs& a) { return (a.N < 2048 && !(a.flags & DLM_OPT_NO_SMALL_BATCH)) ? 1 : 4; }
 
+// k_filter_sp16<K, SIM, IRR, LL>: f(SIM, IRR, LL).  SIM: the simulation smoother's forward pass (x+ wanted); LL: the log-likelihood,
+// only without SIM -- six of the eight combinations
+template <class F>
+static hipError_t with_filter_variant(const KArgs& a, bool sim, F f) {
+  const bool irr = a.g_index || a.dt || a.f_stride || a.v_tstride || a.w_tstride;
+  if (a.loglik && !sim) return pick_bool(irr, [&](auto IRR) { return f(std::false_type{}, IRR, std::true_type{}); });
+  return pick_bool(sim, [&](auto SIM) { return pick_bool(irr, [&](auto IRR) { return f(SIM, IRR, std::false_type{}); }); });
+}
 template <int K>
 static hipError_t launch_f(const KArgs& a, const SparseT* sp, double* side, double* xplus, hipStream_t s) {
-  const bool irr = a.g_index || a.dt || a.f_stride || a.v_tstride || a.w_tstride;
   const int wpb = waves_per_block(a);
   const dim3 grid((a.N + wpb - 1) / wpb), blk(64 * wpb);
-  if (a.loglik && !xplus) {
-    if (irr) hipLaunchKernelGGL((k_filter_sp16<K, false, true, true>), grid, blk, 0, s, a, sp, side, xplus);
-    else hipLaunchKernelGGL((k_filter_sp16<K, false, false, true>), grid, blk, 0, s, a, sp, side, xplus);
-  } else if (xplus && irr) hipLaunchKernelGGL((k_filter_sp16<K, true, true>), grid, blk, 0, s, a, sp, side, xplus);
-  else if (xplus) hipLaunchKernelGGL((k_filter_sp16<K, true, false>), grid, blk, 0, s, a, sp, side, xplus);
-  else if (irr) hipLaunchKernelGGL((k_filter_sp16<K, false, true>), grid, blk, 0, s, a, sp, side, xplus);
-  else hipLaunchKernelGGL((k_filter_sp16<K, false, false>), grid, blk, 0, s, a, sp, side, xplus);
-  return hipGetLastError();
+  return with_filter_variant(a, xplus != nullptr, [&](auto SIM, auto IRR, auto LL) {
+    return launch(k_filter_sp16<K, SIM(), IRR(), LL()>, grid, blk, 0, s, a, sp, side, xplus);
+  });
 }
 template <int K>
 static hipError_t launch_ss(const KArgs& a, const SparseT* sp, const double* side, const double* xplus, hipStream_t s) {
   const int wpb = waves_per_block(a);
   const dim3 grid((a.N + wpb - 1) / wpb), blk(64 * wpb);
-  if (a.g_index || a.dt || a.f_stride || a.v_tstride) hipLaunchKernelGGL((k_simsmooth_sp16<K, true>), grid, blk, 0, s, a, sp, side, xplus);
-  else hipLaunchKernelGGL((k_simsmooth_sp16<K, false>), grid, blk, 0, s, a, sp, side, xplus);
-  return hipGetLastError();
+  return pick_bool(a.g_index || a.dt || a.f_stride || a.v_tstride, [&](auto IRR) { return launch(k_simsmooth_sp16<K, IRR()>, grid, blk, 0, s, a, sp, side, xplus); });
+}
+#ifndef DLM_PIPE_MAX
+#define DLM_PIPE_MAX 3072   // up to three waves per SIMD (measured: 1.86 -> 1.78 ms at 2500 series, 3.00 -> 3.17 at 5000)
+#endif
+// k_smoother_sp16<K, IRR, PIPE, PLAIN>: f(IRR, PIPE, PLAIN), four of the eight combinations
+template <class F>
+static hipError_t with_smoother_variant(const KArgs& a, F f) {
+  const std::true_type yes; const std::false_type no;
+  if (a.g_index || a.dt || a.f_stride || a.v_tstride || a.w_tstride) return f(yes, no, no);
+  if ((a.flags & DLM_OPT_NO_STEADY) && a.N > DLM_PIPE_MAX) return f(no, no, yes);   // every step a full step: the kernel without the machinery
+  if (a.N <= DLM_PIPE_MAX && !(a.flags & DLM_OPT_NO_PIPE)) return f(no, yes, no);
+  return f(no, no, no);
 }
 template <int K>
 static hipError_t launch_s(const KArgs& a, const SparseT* sp, const double* side, hipStream_t s) {
   const int wpb = waves_per_block(a);
   const size_t ring = (size_t)wpb * 2 * (((a.packed & 1) ? packed_rec_bytes(a.d) : (a.d + a.d * a.d) * 8) + 16);   // dynamic LDS: DMA ring, 2 slots per wave
   const dim3 grid((a.N + wpb - 1) / wpb), blk(64 * wpb);
-  if (a.g_index || a.dt || a.f_stride || a.v_tstride || a.w_tstride) hipLaunchKernelGGL((k_smoother_sp16<K, true>), grid, blk, ring, s, a, sp, side);
-#ifndef DLM_PIPE_MAX
-#define DLM_PIPE_MAX 3072   // up to three waves per SIMD (measured: 1.86 -> 1.78 ms at 2500 series, 3.00 -> 3.17 at 5000)
-#endif
-  else if ((a.flags & DLM_OPT_NO_STEADY) && a.N > DLM_PIPE_MAX) hipLaunchKernelGGL((k_smoother_sp16<K, false, false, true>), grid, blk, ring, s, a, sp, side);   // every step a full step: the kernel without the machinery
-  else if (a.N <= DLM_PIPE_MAX && !(a.flags & DLM_OPT_NO_PIPE)) hipLaunchKernelGGL((k_smoother_sp16<K, false, true>), grid, blk, ring, s, a, sp, side);
-  else hipLaunchKernelGGL((k_smoother_sp16<K, false>), grid, blk, ring, s, a, sp, side);
-  return hipGetLastError();
+  return with_smoother_variant(a, [&](auto IRR, auto PIPE, auto PLAIN) {
+    return launch(k_smoother_sp16<K, IRR(), PIPE(), PLAIN()>, grid, blk, ring, s, a, sp, side);
+  });
 }
 
 hipError_t launch_sparse16_filter(const KArgs& a, int K, const SparseT* rows_dev, double* side, double* xplus,
                                   hipStream_t s) {
-  switch (K) {
-    case 1: return launch_f<1>(a, rows_dev, side, xplus, s);
-    case 2: return launch_f<2>(a, rows_dev, side, xplus, s);
-    case 3: return launch_f<3>(a, rows_dev, side, xplus, s);
-    case 4: return launch_f<4>(a, rows_dev, side, xplus, s);
-  }
-  return hipErrorInvalidValue;
+  return pick<1, 2, 3, 4>(K, [&](auto k) { return launch_f<k()>(a, rows_dev, side, xplus, s); });
 }
 
 hipError_t launch_sparse16_simsmooth(const KArgs& a, int K, const SparseT* tabs_dev, const double* side,
                                      const double* xplus, hipStream_t s) {
-  switch (K) {
-    case 1: return launch_ss<1>(a, tabs_dev, side, xplus, s);
-    case 2: return launch_ss<2>(a, tabs_dev, side, xplus, s);
-    case 3: return launch_ss<3>(a, tabs_dev, side, xplus, s);
-    case 4: return launch_ss<4>(a, tabs_dev, side, xplus, s);
-  }
-  return hipErrorInvalidValue;
+  return pick<1, 2, 3, 4>(K, [&](auto k) { return launch_ss<k()>(a, tabs_dev, side, xplus, s); });
 }
 
 // ---- shared-covariance launches: the covariance-only runs take `a` with N = 1 and the tables as their record buffers ----------
@@ -1826,60 +1821,53 @@ static hipError_t launch_cf(const KArgs& a, const SparseT* sp, const CovTabs& tb
   if (err != hipSuccess) return err;
   KArgs k = cov_args(a, tb);
   k.settle_step = (a.flags & DLM_OPT_NO_STEADY) ? nullptr : settle;
-  hipLaunchKernelGGL((k_cov_filter_sp16<K>), dim3(1), dim3(64), 0, s, k, sp, tb.cside, tb.ftab + (a.d + a.d * a.d), tb.skip);
-  if ((err = hipGetLastError()) != hipSuccess) return err;
-  hipLaunchKernelGGL(k_cov_fill_sp16, dim3(a.T + 1), dim3(64), 0, s, tb.ftab, tb.frow / 8, tb.cside, (const int*)settle, a.T);
-  return hipGetLastError();
+  if ((err = launch(k_cov_filter_sp16<K>, dim3(1), dim3(64), 0, s, k, sp, tb.cside, tb.ftab + (a.d + a.d * a.d), tb.skip)) != hipSuccess) return err;
+  return launch(k_cov_fill_sp16, dim3(a.T + 1), dim3(64), 0, s, tb.ftab, tb.frow / 8, tb.cside, (const int*)settle, a.T);
 }
 template <int K>
 static hipError_t launch_cs(const KArgs& a, const SparseT* sp, const CovTabs& tb, hipStream_t s) {
   const size_t ring = 2 * ((size_t)(a.d + a.d * a.d) * 8 + 16);
-  hipLaunchKernelGGL((k_cov_smoother_sp16<K>), dim3(1), dim3(64), ring, s, cov_args(a, tb), sp, (const double*)tb.cside, tb.btab);
-  return hipGetLastError();
+  return launch(k_cov_smoother_sp16<K>, dim3(1), dim3(64), ring, s, cov_args(a, tb), sp, (const double*)tb.cside, tb.btab);
 }
+// NP of the mean-only kernels (k_mean_filter_sp16, k_mean_smoother_sp16): f(NP)
+template <class F>
+static hipError_t with_mean_np(int d, F f) { return pick<4, 6, 8>(d <= 10 ? 4 : d <= 13 ? 6 : 8, f); }
 template <int K>
 static hipError_t launch_mf(const KArgs& a, const SparseT* sp, const CovTabs& tb, hipStream_t s) {
   const int wpb = a.N < 8192 ? 1 : 4, nw = (a.N + 3) / 4;   // four series per wave
   const dim3 grid((nw + wpb - 1) / wpb), blk(64 * wpb);
   const size_t ring = (size_t)wpb * 2 * tb.frow;
-#define DLM_MF(MODE) { if (a.d <= 10) hipLaunchKernelGGL((k_mean_filter_sp16<K, 4, MODE>), grid, blk, ring, s, a, sp, tb); \
-                      else if (a.d <= 13) hipLaunchKernelGGL((k_mean_filter_sp16<K, 6, MODE>), grid, blk, ring, s, a, sp, tb); \
-                      else hipLaunchKernelGGL((k_mean_filter_sp16<K, 8, MODE>), grid, blk, ring, s, a, sp, tb); }
-  if (tb.mc && !a.filt) DLM_MF(0)        // dlm_ffbs_batch that keeps no records: the compact means alone (for the shared-factor draw kernel)
-  else if (tb.mc) DLM_MF(2)              // fused call: records, and compact means for the backward kernel
-  else DLM_MF(1)                         // dlm_filter_batch: records only
-#undef DLM_MF
-  return hipGetLastError();
+  // MODE 0: dlm_ffbs_batch that keeps no records: the compact means alone (for the shared-factor draw kernel); 2: fused call: records, and
+  // compact means for the backward kernel; 1: dlm_filter_batch: records only
+  return pick<0, 2, 1>(tb.mc ? (a.filt ? 2 : 0) : 1, [&](auto MODE) {
+    return with_mean_np(a.d, [&](auto NP) { return launch(k_mean_filter_sp16<K, NP(), decltype(MODE)::value>, grid, blk, ring, s, a, sp, tb); });
+  });
 }
 template <int K>
 static hipError_t launch_ms(const KArgs& a, const SparseT* sp, const CovTabs& tb, hipStream_t s) {
   const int wpb = a.N < 8192 ? 1 : 4, nw = (a.N + 3) / 4;
   const dim3 grid((nw + wpb - 1) / wpb), blk(64 * wpb);
   const size_t ring = (size_t)wpb * (2 * ((size_t)tb.brow + 16) + MEAN_AHEAD * 512);
-  if (a.d <= 10) hipLaunchKernelGGL((k_mean_smoother_sp16<K, 4, true>), grid, blk, ring, s, a, sp, tb);
-  else if (a.d <= 13) hipLaunchKernelGGL((k_mean_smoother_sp16<K, 6, true>), grid, blk, ring, s, a, sp, tb);
-  else hipLaunchKernelGGL((k_mean_smoother_sp16<K, 8, true>), grid, blk, ring, s, a, sp, tb);
-  return hipGetLastError();
+  return with_mean_np(a.d, [&](auto NP) { return launch(k_mean_smoother_sp16<K, NP(), true>, grid, blk, ring, s, a, sp, tb); });
 }
-#define DLM_K_SWITCH(fn, ...) switch (K) { case 1: return fn<1>(__VA_ARGS__); case 2: return fn<2>(__VA_ARGS__); case 3: return fn<3>(__VA_ARGS__); case 4: return fn<4>(__VA_ARGS__); } return hipErrorInvalidValue;
-hipError_t launch_sparse16_cov_filter(const KArgs& a, int K, const SparseT* rows_dev, const CovTabs& tabs, hipStream_t s) { DLM_K_SWITCH(launch_cf, a, rows_dev, tabs, s) }
-hipError_t launch_sparse16_cov_smoother(const KArgs& a, int K, const SparseT* cols_dev, const CovTabs& tabs, hipStream_t s) { DLM_K_SWITCH(launch_cs, a, cols_dev, tabs, s) }
-hipError_t launch_sparse16_mean_filter(const KArgs& a, int K, const SparseT* rows_dev, const CovTabs& tabs, hipStream_t s) { DLM_K_SWITCH(launch_mf, a, rows_dev, tabs, s) }
-hipError_t launch_sparse16_mean_smoother(const KArgs& a, int K, const SparseT* cols_dev, const CovTabs& tabs, hipStream_t s) { DLM_K_SWITCH(launch_ms, a, cols_dev, tabs, s) }
-#undef DLM_K_SWITCH
+hipError_t launch_sparse16_cov_filter(const KArgs& a, int K, const SparseT* rows_dev, const CovTabs& tabs, hipStream_t s) {
+  return pick<1, 2, 3, 4>(K, [&](auto k) { return launch_cf<k()>(a, rows_dev, tabs, s); });
+}
+hipError_t launch_sparse16_cov_smoother(const KArgs& a, int K, const SparseT* cols_dev, const CovTabs& tabs, hipStream_t s) {
+  return pick<1, 2, 3, 4>(K, [&](auto k) { return launch_cs<k()>(a, cols_dev, tabs, s); });
+}
+hipError_t launch_sparse16_mean_filter(const KArgs& a, int K, const SparseT* rows_dev, const CovTabs& tabs, hipStream_t s) {
+  return pick<1, 2, 3, 4>(K, [&](auto k) { return launch_mf<k()>(a, rows_dev, tabs, s); });
+}
+hipError_t launch_sparse16_mean_smoother(const KArgs& a, int K, const SparseT* cols_dev, const CovTabs& tabs, hipStream_t s) {
+  return pick<1, 2, 3, 4>(K, [&](auto k) { return launch_ms<k()>(a, cols_dev, tabs, s); });
+}
 
 hipError_t launch_sparse16_count_gaps(const KArgs& a, unsigned char* plain, hipStream_t s) {
-  hipLaunchKernelGGL(k_count_gaps, dim3((a.N + 3) / 4), dim3(256), 0, s, a.y, a.N, a.T, plain);
-  return hipGetLastError();
+  return launch(k_count_gaps, dim3((a.N + 3) / 4), dim3(256), 0, s, a.y, a.N, a.T, plain);
 }
 hipError_t launch_sparse16_smoother(const KArgs& a, int K, const SparseT* cols_dev, const double* side, hipStream_t s) {
-  switch (K) {
-    case 1: return launch_s<1>(a, cols_dev, side, s);
-    case 2: return launch_s<2>(a, cols_dev, side, s);
-    case 3: return launch_s<3>(a, cols_dev, side, s);
-    case 4: return launch_s<4>(a, cols_dev, side, s);
-  }
-  return hipErrorInvalidValue;
+  return pick<1, 2, 3, 4>(K, [&](auto k) { return launch_s<k()>(a, cols_dev, side, s); });
 }
 
 }  // namespace dlm

@@ -1005,20 +1005,20 @@ hipError_t launch_svd_filter_shared(const KArgs& a, double* svd_rec, double* ws,
   km.route = route; km.route_take = 0;
 #ifdef DLM_SVD_MEAN_ONE_PER_WAVE
   const int wpb = 4;
-  hipLaunchKernelGGL(k_svd_mean_filter, dim3((a.N + wpb - 1) / wpb), dim3(64 * wpb), (size_t)wpb * 2 * (tstride * 8 + 16), s, km, (const double*)tab, tstride,
-                     (const double*)aux, (const int*)cst, svd_rec);
+  err = launch(k_svd_mean_filter, dim3((a.N + wpb - 1) / wpb), dim3(64 * wpb), (size_t)wpb * 2 * (tstride * 8 + 16), s, km, (const double*)tab, tstride,
+               (const double*)aux, (const int*)cst, svd_rec);
 #else
   {
     const dim3 grid((a.N + 3) / 4), blk(64);
     const size_t ring = 2 * ((size_t)tstride * 8 + 16);
+    // NS: the store instructions per step, ceil(4 srec / 64), rounded up to one of the four sizes that are compiled (see k_svd_mean_filter4)
     const int ns = (4 * srec + 63) / 64;
-    if (ns <= 4) hipLaunchKernelGGL(k_svd_mean_filter4<4>, grid, blk, ring, s, km, (const double*)tab, tstride, (const double*)aux, (const int*)cst, svd_rec);
-    else if (ns <= 8) hipLaunchKernelGGL(k_svd_mean_filter4<8>, grid, blk, ring, s, km, (const double*)tab, tstride, (const double*)aux, (const int*)cst, svd_rec);
-    else if (ns <= 13) hipLaunchKernelGGL(k_svd_mean_filter4<13>, grid, blk, ring, s, km, (const double*)tab, tstride, (const double*)aux, (const int*)cst, svd_rec);
-    else hipLaunchKernelGGL(k_svd_mean_filter4<18>, grid, blk, ring, s, km, (const double*)tab, tstride, (const double*)aux, (const int*)cst, svd_rec);
+    err = pick<4, 8, 13, 18>(ns <= 4 ? 4 : ns <= 8 ? 8 : ns <= 13 ? 13 : 18, [&](auto NS) {
+      return launch(k_svd_mean_filter4<NS()>, grid, blk, ring, s, km, (const double*)tab, tstride, (const double*)aux, (const int*)cst, svd_rec);
+    });
   }
 #endif
-  if ((err = hipGetLastError()) != hipSuccess) return err;
+  if (err != hipSuccess) return err;
   KArgs kg = a;
   kg.route = route; kg.route_take = 1;
   hipLaunchKernelGGL(k_svd_filter<16>, dim3(a.N), dim3(64), svd_filter_lds_bytes(a.d, a.p), s, kg, svd_rec, 0, (double*)nullptr);
@@ -1215,26 +1215,20 @@ static hipError_t svd_big_lds_once() {
   }();
   return done;
 }
-hipError_t launch_svd_filter(const KArgs& a, double* svd_rec, hipStream_t s) {
+// NM = svd_nm(d, p): the 16- or the 48-wide LDS matrices: f(NM)
+template <class F>
+static hipError_t with_svd_nm(const KArgs& a, F f) {
   if (!svd_supported(a)) return hipErrorNotSupported;
-  if (svd_nm(a.d, a.p) == 16) hipLaunchKernelGGL(k_svd_filter<16>, dim3(a.N), dim3(64), svd_filter_lds_bytes(a.d, a.p), s, a, svd_rec, 0, (double*)nullptr);
-  else {
-    const hipError_t e = svd_big_lds_once();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_svd_filter<48>, dim3(a.N), dim3(64), svd_filter_lds_bytes(a.d, a.p), s, a, svd_rec, 0, (double*)nullptr);
-  }
-  return hipGetLastError();
+  if (svd_nm(a.d, a.p) == 16) return f(std::integral_constant<int, 16>{});
+  const hipError_t e = svd_big_lds_once();
+  return e != hipSuccess ? e : f(std::integral_constant<int, 48>{});
+}
+hipError_t launch_svd_filter(const KArgs& a, double* svd_rec, hipStream_t s) {
+  return with_svd_nm(a, [&](auto NM) { return launch(k_svd_filter<NM()>, dim3(a.N), dim3(64), svd_filter_lds_bytes(a.d, a.p), s, a, svd_rec, 0, (double*)nullptr); });
 }
 
 hipError_t launch_svd_sampler(const KArgs& a, const double* svd_rec, hipStream_t s) {
-  if (!svd_supported(a)) return hipErrorNotSupported;
-  if (svd_nm(a.d, a.p) == 16) hipLaunchKernelGGL(k_svd_sampler<16>, dim3(a.N), dim3(64), svd_sampler_lds_bytes(a.d, a.p), s, a, svd_rec);
-  else {
-    const hipError_t e = svd_big_lds_once();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_svd_sampler<48>, dim3(a.N), dim3(64), svd_sampler_lds_bytes(a.d, a.p), s, a, svd_rec);
-  }
-  return hipGetLastError();
+  return with_svd_nm(a, [&](auto NM) { return launch(k_svd_sampler<NM()>, dim3(a.N), dim3(64), svd_sampler_lds_bytes(a.d, a.p), s, a, svd_rec); });
 }
 
 }  // namespace dlm

@@ -2751,56 +2751,40 @@ bool wave48_filter_supported(const KArgs& a) {
   return shape_ok(a) && a.spb && wave48_wanted(a);
 }
 
-template <int DT, int PT>
-static hipError_t launch_w48_filter_k(const KArgs& a, int K, double* innov, int zero_m0, hipStream_t s) {
-  const size_t lds = sizeof(double) * w48::lds_doubles(DT, PT);
-  const int kf = (a.spf && !(a.flags & DLM_OPT_NO_SPARSE_F)) ? a.spf_k : 0;   // 0: dense (or time-varying) F
-  if (K <= 2) {
-    if (kf == 1) hipLaunchKernelGGL((w48::k_filter_w48<DT, PT, 2, 1>), dim3(a.N), dim3(64), lds, s, a, innov, zero_m0);
-    else if (kf > 1) hipLaunchKernelGGL((w48::k_filter_w48<DT, PT, 2, 4>), dim3(a.N), dim3(64), lds, s, a, innov, zero_m0);
-    else hipLaunchKernelGGL((w48::k_filter_w48<DT, PT, 2, 0>), dim3(a.N), dim3(64), lds, s, a, innov, zero_m0);
-  } else {
-    if (kf >= 1) hipLaunchKernelGGL((w48::k_filter_w48<DT, PT, 4, 4>), dim3(a.N), dim3(64), lds, s, a, innov, zero_m0);
-    else hipLaunchKernelGGL((w48::k_filter_w48<DT, PT, 4, 0>), dim3(a.N), dim3(64), lds, s, a, innov, zero_m0);
-  }
-  return hipGetLastError();
+// ---- the launchers' selection rules, each written once ---------------------------------------------------------------------------
+// (DT, PT): 16-wide tiles of the state (d <= 16 / 32 / 48) and of the observation (p <= 16 / 32) -- six cases
+static int tiles_d(const KArgs& a) { return a.d <= 16 ? 1 : (a.d <= 32 ? 2 : 3); }
+static int tiles_p(const KArgs& a) { return a.p <= 16 ? 1 : 2; }
+// kf: the nonzeros per column of a structured F (1..4); 0: dense F.  sparse_f: the forward kernels; sparse_f_fixed: the backward kernels and
+// the simulation's prologue, which take a time-varying F for a dense one
+static int sparse_f(const KArgs& a) { return (a.spf && !(a.flags & DLM_OPT_NO_SPARSE_F)) ? a.spf_k : 0; }
+static int sparse_f_fixed(const KArgs& a) { return a.f_stride ? 0 : sparse_f(a); }
+// (K, KF) the kernels are compiled for, from the sparsity class K of G and kf: (2, 1), (2, 4), (2, 0), (4, 4), (4, 0)
+template <class F>
+static hipError_t with_sparsity(int K, int kf, F f) {
+  if (K <= 2) return pick<1, 4, 0>(kf == 1 ? 1 : (kf > 1 ? 4 : 0), [&](auto KF) { return f(std::integral_constant<int, 2>{}, KF); });
+  return pick<4, 0>(kf >= 1 ? 4 : 0, [&](auto KF) { return f(std::integral_constant<int, 4>{}, KF); });
+}
+// both: f(DT, PT, K, KF), the template arguments of the filter, smoother, simulation-smoother and steady-filter kernels
+template <class F>
+static hipError_t with_tiles_and_sparsity(const KArgs& a, int K, int kf, F f) {
+  return pick<1, 2, 3>(tiles_d(a), [&](auto DT) {
+    return pick<1, 2>(tiles_p(a), [&](auto PT) { return with_sparsity(K, kf, [&](auto KG, auto KF) { return f(DT, PT, KG, KF); }); });
+  });
 }
 
 bool wave48_smoother_supported(const KArgs& a) { return shape_ok(a) && a.spb && wave48_wanted(a); }
 
-template <int DT, int PT>
-static hipError_t launch_w48_smoother_k(const KArgs& a, int K, const double* innov, hipStream_t s) {
-  const size_t lds = sizeof(double) * w48::lds_doubles(DT, PT);
-  const int kf = (a.spf && !a.f_stride && !(a.flags & DLM_OPT_NO_SPARSE_F)) ? a.spf_k : 0;   // 0: dense (or time-varying) F
-  if (K <= 2) {
-    if (kf == 1) hipLaunchKernelGGL((w48::k_smoother_w48<DT, PT, 2, 1>), dim3(a.N), dim3(64), lds, s, a, innov);
-    else if (kf > 1) hipLaunchKernelGGL((w48::k_smoother_w48<DT, PT, 2, 4>), dim3(a.N), dim3(64), lds, s, a, innov);
-    else hipLaunchKernelGGL((w48::k_smoother_w48<DT, PT, 2, 0>), dim3(a.N), dim3(64), lds, s, a, innov);
-  } else {
-    if (kf >= 1) hipLaunchKernelGGL((w48::k_smoother_w48<DT, PT, 4, 4>), dim3(a.N), dim3(64), lds, s, a, innov);
-    else hipLaunchKernelGGL((w48::k_smoother_w48<DT, PT, 4, 0>), dim3(a.N), dim3(64), lds, s, a, innov);
-  }
-  return hipGetLastError();
-}
-
 hipError_t launch_wave48_smoother(const KArgs& a, int K, const double* innov, hipStream_t s) {
-  const bool d2 = a.d <= 32, p1 = a.p <= 16;
-  if (a.d <= 16 && p1) return launch_w48_smoother_k<1, 1>(a, K, innov, s);
-  if (a.d <= 16) return launch_w48_smoother_k<1, 2>(a, K, innov, s);
-  if (d2 && p1) return launch_w48_smoother_k<2, 1>(a, K, innov, s);
-  if (d2) return launch_w48_smoother_k<2, 2>(a, K, innov, s);
-  if (p1) return launch_w48_smoother_k<3, 1>(a, K, innov, s);
-  return launch_w48_smoother_k<3, 2>(a, K, innov, s);
+  return with_tiles_and_sparsity(a, K, sparse_f_fixed(a), [&](auto DT, auto PT, auto KG, auto KF) {
+    return launch(w48::k_smoother_w48<DT(), PT(), KG(), KF()>, dim3(a.N), dim3(64), sizeof(double) * w48::lds_doubles(DT(), PT()), s, a, innov);
+  });
 }
 
 static hipError_t launch_wave48_filter_z(const KArgs& a, int K, double* innov, int zero_m0, hipStream_t s) {
-  const bool d2 = a.d <= 32, p1 = a.p <= 16;
-  if (a.d <= 16 && p1) return launch_w48_filter_k<1, 1>(a, K, innov, zero_m0, s);
-  if (a.d <= 16) return launch_w48_filter_k<1, 2>(a, K, innov, zero_m0, s);
-  if (d2 && p1) return launch_w48_filter_k<2, 1>(a, K, innov, zero_m0, s);
-  if (d2) return launch_w48_filter_k<2, 2>(a, K, innov, zero_m0, s);
-  if (p1) return launch_w48_filter_k<3, 1>(a, K, innov, zero_m0, s);
-  return launch_w48_filter_k<3, 2>(a, K, innov, zero_m0, s);
+  return with_tiles_and_sparsity(a, K, sparse_f(a), [&](auto DT, auto PT, auto KG, auto KF) {
+    return launch(w48::k_filter_w48<DT(), PT(), KG(), KF()>, dim3(a.N), dim3(64), sizeof(double) * w48::lds_doubles(DT(), PT()), s, a, innov, zero_m0);
+  });
 }
 hipError_t launch_wave48_filter(const KArgs& a, int K, double* innov, hipStream_t s) { return launch_wave48_filter_z(a, K, innov, 0, s); }
 
@@ -2811,35 +2795,10 @@ bool wave48_simsmooth_supported(const KArgs& a) {
   return shape_ok(a) && a.spb && !a.v_tstride && !a.cond && wave48_wanted(a);   // (a W_t stream only enters the simulation: k_sim_prologue_w48 factors it per step; V_t would enter the backward gain)
 }
 
-template <int DT, int PT>
-static hipError_t launch_w48_sims_k(const KArgs& a, int K, const double* xplus, const double* innov, hipStream_t s) {
-  const size_t lds = sizeof(double) * w48::lds_doubles(DT, PT);
-  const int kf = (a.spf && !a.f_stride && !(a.flags & DLM_OPT_NO_SPARSE_F)) ? a.spf_k : 0;   // 0: dense (or time-varying) F
-  if (K <= 2) {
-    if (kf == 1) hipLaunchKernelGGL((w48::k_simsmooth_w48<DT, PT, 2, 1>), dim3(a.N), dim3(64), lds, s, a, xplus, innov);
-    else if (kf > 1) hipLaunchKernelGGL((w48::k_simsmooth_w48<DT, PT, 2, 4>), dim3(a.N), dim3(64), lds, s, a, xplus, innov);
-    else hipLaunchKernelGGL((w48::k_simsmooth_w48<DT, PT, 2, 0>), dim3(a.N), dim3(64), lds, s, a, xplus, innov);
-  } else {
-    if (kf >= 1) hipLaunchKernelGGL((w48::k_simsmooth_w48<DT, PT, 4, 4>), dim3(a.N), dim3(64), lds, s, a, xplus, innov);
-    else hipLaunchKernelGGL((w48::k_simsmooth_w48<DT, PT, 4, 0>), dim3(a.N), dim3(64), lds, s, a, xplus, innov);
-  }
-  return hipGetLastError();
-}
-
 hipError_t launch_wave48_simsmooth(const KArgs& a, int K, double* xplus, double* ystar, hipStream_t s) {
-  {
-    const int kf = (a.spf && !a.f_stride && !(a.flags & DLM_OPT_NO_SPARSE_F)) ? a.spf_k : 0;
-    const size_t lds = sizeof(double) * (48 * 49 + 32 * 33 + (kf ? 0 : w48::FIMG) + 48 + 48 + 96);
-    if (K <= 2) {
-      if (kf == 1) hipLaunchKernelGGL((w48::k_sim_prologue_w48<2, 1>), dim3(a.N), dim3(64), lds, s, a, xplus, ystar);
-      else if (kf > 1) hipLaunchKernelGGL((w48::k_sim_prologue_w48<2, 4>), dim3(a.N), dim3(64), lds, s, a, xplus, ystar);
-      else hipLaunchKernelGGL((w48::k_sim_prologue_w48<2, 0>), dim3(a.N), dim3(64), lds, s, a, xplus, ystar);
-    } else {
-      if (kf >= 1) hipLaunchKernelGGL((w48::k_sim_prologue_w48<4, 4>), dim3(a.N), dim3(64), lds, s, a, xplus, ystar);
-      else hipLaunchKernelGGL((w48::k_sim_prologue_w48<4, 0>), dim3(a.N), dim3(64), lds, s, a, xplus, ystar);
-    }
-  }
-  hipError_t e = hipGetLastError();
+  const int kf = sparse_f_fixed(a);
+  const size_t lds = sizeof(double) * (48 * 49 + 32 * 33 + (kf ? 0 : w48::FIMG) + 48 + 48 + 96);
+  hipError_t e = with_sparsity(K, kf, [&](auto KG, auto KF) { return launch(w48::k_sim_prologue_w48<KG(), KF()>, dim3(a.N), dim3(64), lds, s, a, xplus, ystar); });
   if (e != hipSuccess) return e;
   KArgs f = a;
   f.y = ystar; f.z = nullptr; f.theta = nullptr; f.stats = nullptr; f.fq = nullptr; f.prior = nullptr; f.loglik = nullptr;
@@ -2847,35 +2806,33 @@ hipError_t launch_wave48_simsmooth(const KArgs& a, int K, double* xplus, double*
   if (e != hipSuccess) return e;
   KArgs b = a;
   b.filt_in = a.filt;
-  const bool d2 = a.d <= 32, p1 = a.p <= 16;
-  if (a.d <= 16 && p1) return launch_w48_sims_k<1, 1>(b, K, xplus, ystar, s);
-  if (a.d <= 16) return launch_w48_sims_k<1, 2>(b, K, xplus, ystar, s);
-  if (d2 && p1) return launch_w48_sims_k<2, 1>(b, K, xplus, ystar, s);
-  if (d2) return launch_w48_sims_k<2, 2>(b, K, xplus, ystar, s);
-  if (p1) return launch_w48_sims_k<3, 1>(b, K, xplus, ystar, s);
-  return launch_w48_sims_k<3, 2>(b, K, xplus, ystar, s);
+  return with_tiles_and_sparsity(b, K, kf, [&](auto DT, auto PT, auto KG, auto KF) {
+    return launch(w48::k_simsmooth_w48<DT(), PT(), KG(), KF()>, dim3(b.N), dim3(64), sizeof(double) * w48::lds_doubles(DT(), PT()), s, b, (const double*)xplus, (const double*)ystar);
+  });
 }
 
 // reference-form backward sampler on register tiles, 16 <= d <= 48 with a structured G (a.filt_in -> theta / cond / stats)
 bool wave48_sampler_supported(const KArgs& a) { return tiled_supported(a) && a.spb && wave48_wanted(a); }
 
-template <int DT>
-static hipError_t launch_w48_sampler_k(const KArgs& a, int K, hipStream_t s) {
-  const size_t lds = sizeof(double) * (size_t)(2 * 16 * DT * (16 * DT + 1) + 6 * 16 * DT);
-  const bool outer = (a.flags & DLM_OPT_STATS_OUTER) != 0 && a.stats;
-  if (K <= 2) {
-    if (outer) hipLaunchKernelGGL((w48::k_sampler_w48<DT, 2, true>), dim3(a.N), dim3(64), lds, s, a, SampTabs{});
-    else hipLaunchKernelGGL((w48::k_sampler_w48<DT, 2, false>), dim3(a.N), dim3(64), lds, s, a, SampTabs{});
-  } else {
-    if (outer) hipLaunchKernelGGL((w48::k_sampler_w48<DT, 4, true>), dim3(a.N), dim3(64), lds, s, a, SampTabs{});
-    else hipLaunchKernelGGL((w48::k_sampler_w48<DT, 4, false>), dim3(a.N), dim3(64), lds, s, a, SampTabs{});
-  }
-  return hipGetLastError();
+// k_sampler_w48 / k_mean_sampler_w48 <DT, K, OUTER>: f(DT, K, OUTER).  DT 2 or 3 (d = 16 takes two tiles here); OUTER: the call's statistics
+// hold the outer product (stats_outer of the CALL: a table run's own arguments carry no statistics)
+static int sampler_dt(const KArgs& a) { return a.d <= 32 ? 2 : 3; }
+static bool stats_outer(const KArgs& a) { return (a.flags & DLM_OPT_STATS_OUTER) != 0 && a.stats; }
+template <class F>
+static hipError_t with_sampler_variant(const KArgs& a, bool outer, F f) {
+  return pick<2, 3>(sampler_dt(a), [&](auto DT) {
+    return pick<2, 4>(a.spb_k <= 2 ? 2 : 4, [&](auto K) { return pick_bool(outer, [&](auto OUTER) { return f(DT, K, OUTER); }); });
+  });
 }
-hipError_t launch_wave48_sampler(const KArgs& a, hipStream_t s) {
-  if (a.d <= 32) return launch_w48_sampler_k<2>(a, a.spb_k, s);
-  return launch_w48_sampler_k<3>(a, a.spb_k, s);
+// the series of a call (grid a.N, no tables) and the table run of its shared factors (one wave per stretch, tb): one selection, so that the
+// table holds what the per-series kernel of the same call computes, bit for bit
+static hipError_t launch_w48_sampler_k(const KArgs& a, bool outer, dim3 grid, const SampTabs& tb, hipStream_t s) {
+  return with_sampler_variant(a, outer, [&](auto DT, auto K, auto OUTER) {
+    const size_t lds = sizeof(double) * (size_t)(2 * 16 * DT() * (16 * DT() + 1) + 6 * 16 * DT());
+    return launch(w48::k_sampler_w48<DT(), K(), OUTER()>, grid, dim3(64), lds, s, a, tb);
+  });
 }
+hipError_t launch_wave48_sampler(const KArgs& a, hipStream_t s) { return launch_w48_sampler_k(a, stats_outer(a), dim3(a.N), SampTabs{}, s); }
 
 // ---- shared factors: regular grid, time-invariant F / V / W, V, W, C0 shared by the batch -------------------------
 bool wave48_sampler_shared_model_ok(const KArgs& a) {
@@ -2888,33 +2845,19 @@ bool wave48_sampler_shared_eligible(const KArgs& a) {
          !(a.flags & (DLM_OPT_FORCE_GENERIC | DLM_OPT_NO_SAMPLER16 | DLM_OPT_SAMPLER_PER_SERIES));
 }
 static size_t up64w(size_t x) { return (x + 63) & ~(size_t)63; }
-static int ws_dt(const KArgs& a) { return a.d <= 32 ? 2 : 3; }
 size_t wave48_sampler_shared_ws_bytes(const KArgs& a) {
   const size_t n1 = (size_t)a.T + 1, rec = (size_t)a.d + (size_t)a.d * a.d, zn = (size_t)a.T * a.p > 64 ? (size_t)a.T * a.p : 64;
-  return up64w(n1 * w48::ws_row_doubles(ws_dt(a)) * 8) + up64w(n1 * rec * 8) + up64w(zn * 8) + up64w(n1) + 64 + up64w(wave48_ktab_doubles(a) * 8);
+  return up64w(n1 * w48::ws_row_doubles(sampler_dt(a)) * 8) + up64w(n1 * rec * 8) + up64w(zn * 8) + up64w(n1) + 64 + up64w(wave48_ktab_doubles(a) * 8);
 }
 void wave48_sampler_shared_carve(void* ws, const KArgs& a, SampTabs& tb) {
   const size_t n1 = (size_t)a.T + 1, rec = (size_t)a.d + (size_t)a.d * a.d, zn = (size_t)a.T * a.p > 64 ? (size_t)a.T * a.p : 64;
   char* p = (char*)ws;
-  tb.rows = (double*)p;  p += up64w(n1 * w48::ws_row_doubles(ws_dt(a)) * 8);
+  tb.rows = (double*)p;  p += up64w(n1 * w48::ws_row_doubles(sampler_dt(a)) * 8);
   tb.zrec = (double*)p;  p += up64w(n1 * rec * 8);
   tb.zeros = (double*)p; p += up64w(zn * 8);
   tb.need = (unsigned char*)p; p += up64w(n1);
   tb.status = (int*)p; tb.settle = tb.status + 1; p += 64;
   tb.ktab = (double*)p;
-}
-template <int DT>
-static void launch_w48_tables_k(const KArgs& kp, const SampTabs& tb, bool outer, hipStream_t s) {
-  const size_t lds = sizeof(double) * (size_t)(2 * 16 * DT * (16 * DT + 1) + 6 * 16 * DT);
-  const dim3 grid(w48::ws_stretches(kp.T));   // one wave per stretch
-  // (the instantiation launch_w48_sampler_k picks for the series of this call that compute their own factors)
-  if (kp.spb_k <= 2) {
-    if (outer) hipLaunchKernelGGL((w48::k_sampler_w48<DT, 2, true>), grid, dim3(64), lds, s, kp, tb);
-    else hipLaunchKernelGGL((w48::k_sampler_w48<DT, 2, false>), grid, dim3(64), lds, s, kp, tb);
-  } else {
-    if (outer) hipLaunchKernelGGL((w48::k_sampler_w48<DT, 4, true>), grid, dim3(64), lds, s, kp, tb);
-    else hipLaunchKernelGGL((w48::k_sampler_w48<DT, 4, false>), grid, dim3(64), lds, s, kp, tb);
-  }
 }
 hipError_t launch_wave48_sampler_shared_tables(const KArgs& a, const SampTabs& tb, hipStream_t s, hipEvent_t after_filter) {
   const size_t zn = (size_t)a.T * a.p > 64 ? (size_t)a.T * a.p : 64;
@@ -2932,70 +2875,38 @@ hipError_t launch_wave48_sampler_shared_tables(const KArgs& a, const SampTabs& t
   if (after_filter && (err = hipEventRecord(after_filter, s)) != hipSuccess) return err;
   KArgs kp = kf;
   kp.y = nullptr; kp.filt_in = tb.zrec; kp.settle_step = nullptr; kp.ktab = nullptr;
-  const bool outer = (a.flags & DLM_OPT_STATS_OUTER) != 0 && a.stats;
-  if (a.d <= 32) launch_w48_tables_k<2>(kp, tb, outer, s); else launch_w48_tables_k<3>(kp, tb, outer, s);
-  return hipGetLastError();
-}
-template <int DT>
-static void launch_w48_mean_k(const KArgs& a, const SampTabs& tb, hipStream_t s) {
-  const size_t lds = sizeof(double) * (size_t)(6 * 16 * DT + (16 * DT * (16 * DT + 1)) / 2 + a.p * (a.d + 1));
-  const bool outer = (a.flags & DLM_OPT_STATS_OUTER) != 0 && a.stats;
-  if (a.spb_k <= 2) {
-    if (outer) hipLaunchKernelGGL((w48::k_mean_sampler_w48<DT, 2, true>), dim3(a.N), dim3(64), lds, s, a, tb);
-    else hipLaunchKernelGGL((w48::k_mean_sampler_w48<DT, 2, false>), dim3(a.N), dim3(64), lds, s, a, tb);
-  } else {
-    if (outer) hipLaunchKernelGGL((w48::k_mean_sampler_w48<DT, 4, true>), dim3(a.N), dim3(64), lds, s, a, tb);
-    else hipLaunchKernelGGL((w48::k_mean_sampler_w48<DT, 4, false>), dim3(a.N), dim3(64), lds, s, a, tb);
-  }
+  return launch_w48_sampler_k(kp, stats_outer(a), dim3(w48::ws_stretches(kp.T)), tb, s);   // one wave per stretch
 }
 size_t wave48_sampler_shared_normals_bytes(const KArgs& a) { return (size_t)a.N * ((size_t)a.T + 1) * a.d * 8; }
 hipError_t launch_wave48_sampler_shared_normals(const KArgs& a, double* z, hipStream_t s) {
   const long long total = (long long)a.N * (a.T + 1) * ((a.d + 1) / 2);
   const long long blocks = (total + 255) / 256;
-  hipLaunchKernelGGL(w48::k_normals_rows, dim3((unsigned)(blocks < 65536 * 4 ? blocks : 65536 * 4)), dim3(256), 0, s, a, z);
-  return hipGetLastError();
+  return launch(w48::k_normals_rows, dim3((unsigned)(blocks < 65536 * 4 ? blocks : 65536 * 4)), dim3(256), 0, s, a, z);
 }
-size_t wave48_ktab_doubles(const KArgs& a) { const int PT = a.p <= 16 ? 1 : 2, DT = a.d <= 16 ? 1 : (a.d <= 32 ? 2 : 3); return (size_t)16 * PT * w48::il_of(DT, PT); }
-template <int DT, int PT>
-static void launch_w48_steady_k(const KArgs& a, const double* ktab, const int* settle, hipStream_t s) {
-  const int kf = (a.spf && !(a.flags & DLM_OPT_NO_SPARSE_F)) ? a.spf_k : 0;
-  const size_t lds = sizeof(double) * (size_t)(16 * PT * w48::il_of(DT, PT) + (kf ? 0 : w48::fimg_of(DT, PT)) + 3 * w48::vl_of(DT, PT));
-  const int K = a.spb_k;
-  if (K <= 2) {
-    if (kf == 1) hipLaunchKernelGGL((w48::k_steady_filter_w48<DT, PT, 2, 1>), dim3(a.N), dim3(64), lds, s, a, ktab, settle);
-    else if (kf > 1) hipLaunchKernelGGL((w48::k_steady_filter_w48<DT, PT, 2, 4>), dim3(a.N), dim3(64), lds, s, a, ktab, settle);
-    else hipLaunchKernelGGL((w48::k_steady_filter_w48<DT, PT, 2, 0>), dim3(a.N), dim3(64), lds, s, a, ktab, settle);
-  } else {
-    if (kf >= 1) hipLaunchKernelGGL((w48::k_steady_filter_w48<DT, PT, 4, 4>), dim3(a.N), dim3(64), lds, s, a, ktab, settle);
-    else hipLaunchKernelGGL((w48::k_steady_filter_w48<DT, PT, 4, 0>), dim3(a.N), dim3(64), lds, s, a, ktab, settle);
-  }
-}
+size_t wave48_ktab_doubles(const KArgs& a) { const int PT = tiles_p(a), DT = tiles_d(a); return (size_t)16 * PT * w48::il_of(DT, PT); }
 hipError_t launch_wave48_steady_filter(const KArgs& a, const double* ktab, const int* settle, hipStream_t s) {
-  const bool d2 = a.d <= 32, p1 = a.p <= 16;
-  if (a.d <= 16 && p1) launch_w48_steady_k<1, 1>(a, ktab, settle, s);
-  else if (a.d <= 16) launch_w48_steady_k<1, 2>(a, ktab, settle, s);
-  else if (d2 && p1) launch_w48_steady_k<2, 1>(a, ktab, settle, s);
-  else if (d2) launch_w48_steady_k<2, 2>(a, ktab, settle, s);
-  else if (p1) launch_w48_steady_k<3, 1>(a, ktab, settle, s);
-  else launch_w48_steady_k<3, 2>(a, ktab, settle, s);
-  return hipGetLastError();
+  const int kf = sparse_f(a);
+  return with_tiles_and_sparsity(a, a.spb_k, kf, [&](auto DT, auto PT, auto KG, auto KF) {
+    const size_t lds = sizeof(double) * (size_t)(16 * PT() * w48::il_of(DT(), PT()) + (kf ? 0 : w48::fimg_of(DT(), PT())) + 3 * w48::vl_of(DT(), PT()));
+    return launch(w48::k_steady_filter_w48<DT(), PT(), KG(), KF()>, dim3(a.N), dim3(64), lds, s, a, ktab, settle);
+  });
 }
 hipError_t launch_wave48_mark_gaps(const KArgs& a, unsigned char* route, hipStream_t s) {
-  hipLaunchKernelGGL(w48::k_mark_gaps_w48, dim3(a.N), dim3(256), 0, s, a.y, a.N, a.T * a.p, route);
-  return hipGetLastError();
+  return launch(w48::k_mark_gaps_w48, dim3(a.N), dim3(256), 0, s, a.y, a.N, a.T * a.p, route);
 }
 hipError_t launch_wave48_sampler_shared_draw(const KArgs& a, const SampTabs& tb, hipStream_t s) {
   if (!a.route) return hipErrorInvalidValue;
   hipError_t err;
   if (tb.marked) { /* the engine marked the gaps before the forward pass */ }
-  else if (a.y) hipLaunchKernelGGL(w48::k_mark_gaps_w48, dim3(a.N), dim3(256), 0, s, a.y, a.N, a.T * a.p, a.route);
-  else if ((err = hipMemsetAsync(a.route, 0, (size_t)a.N, s)) != hipSuccess) return err;
-  if ((err = hipGetLastError()) != hipSuccess) return err;
+  else if ((err = a.y ? launch_wave48_mark_gaps(a, a.route, s) : hipMemsetAsync(a.route, 0, (size_t)a.N, s)) != hipSuccess) return err;
   KArgs km = a;
   km.route_take = 0;
   if (!km.z) km.z = tb.z4;          // the call's normals made beside the filter (k_normals_rows); nullptr: the draw kernel makes them itself
-  if (a.d <= 32) launch_w48_mean_k<2>(km, tb, s); else launch_w48_mean_k<3>(km, tb, s);
-  if ((err = hipGetLastError()) != hipSuccess) return err;
+  err = with_sampler_variant(km, stats_outer(km), [&](auto DT, auto K, auto OUTER) {
+    const size_t lds = sizeof(double) * (size_t)(6 * 16 * DT() + (16 * DT() * (16 * DT() + 1)) / 2 + km.p * (km.d + 1));
+    return launch(w48::k_mean_sampler_w48<DT(), K(), OUTER()>, dim3(km.N), dim3(64), lds, s, km, tb);
+  });
+  if (err != hipSuccess) return err;
   KArgs kg = a;   // the series with a missing observation: their own factors
   kg.route_take = 1;
   return launch_wave48_sampler(kg, s);

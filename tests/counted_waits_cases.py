@@ -24,7 +24,7 @@ if ROOT not in sys.path:
 from bayesian_dlms_amd import _lib  # noqa: E402
 from bayesian_dlms_amd.dlm import Dlm, DlmParameters, materialise  # noqa: E402
 
-PIPE_MAX = 3072          # DLM_PIPE_MAX (dlm_sparse16.hip, launch_s)
+PIPE_MAX = 3072          # DLM_PIPE_MAX (dlm_sparse16.hip, with_smoother_variant)
 W_C2 = np.array([0.01, 0.2, 0.4, 0.5, 0.2, 0.1, 0.4, 0.2, 0.4, 0.5, 0.2, 0.1, 0.4])
 CNT = _lib.OPT_COUNT_STEPS
 EDGES = [(1, 5), (2, 3), (3, 1), (63, 4), (64, 6), (65, 7), (1000, 37)]   # (T, N): prologue / epilogue, the 64-step branch, long T
@@ -36,7 +36,7 @@ def rts_inst(d, K):            # launch_mean_rts (dlm_sampler16.hip)
     return f"k_mean_rts16<{K}, {np_}, {nrs}, {nrj}>"
 
 
-def mean_np(d):                # launch_mf / launch_ms (dlm_sparse16.hip)
+def mean_np(d):                # with_mean_np (dlm_sparse16.hip)
     return 4 if d <= 10 else 6 if d <= 13 else 8
 
 
@@ -49,7 +49,7 @@ def svd_ns(d):                 # launch_svd_filter_shared: ceil(4 srec / 64), sr
     return 4 if ns <= 4 else 8 if ns <= 8 else 13 if ns <= 13 else 18
 
 
-def smoother_inst(K, irregular, N, flags):   # launch_s (dlm_sparse16.hip)
+def smoother_inst(K, irregular, N, flags):   # with_smoother_variant (dlm_sparse16.hip)
     b = lambda v: "true" if v else "false"
     if irregular:
         irr, pipe, plain = True, False, False
