@@ -13,6 +13,8 @@ FLAGS = BASE_FLAGS + ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 # dlm_wave48.hip keeps whole matrices in registers (up to the 512-register budget of a wave): its accumulators may live
 # in AGPRs, and the VGPR-form rewrite pass of this compiler crashes on it
 FILE_FLAGS = {"dlm_wave48.hip": BASE_FLAGS}
+# an object is stale when its source or any of these is newer (dlm_wave.h: the device primitives of the kernel files)
+HEADERS = [os.path.join(CSRC, "dlm_internal.h"), os.path.join(CSRC, "dlm_wave.h"), os.path.join(HERE, "..", "include", "dlm_engine.h")]
 
 
 def _stale(target, deps):
@@ -76,12 +78,11 @@ def build_drain_variant(force=False, verbose=False):
     Only the DRAIN_SOURCES are compiled again; the other objects are the regular build's.  Rebuilt only when a source or header
     is newer, as build() does.  tests/test_counted_waits_gpu.py compares it with the default build bit for bit."""
     build(verbose=verbose)
-    hdrs = [os.path.join(CSRC, "dlm_internal.h"), os.path.join(HERE, "..", "include", "dlm_engine.h")]
     os.makedirs(os.path.join(HERE, "build", "drain"), exist_ok=True)
     todo = []
     for src in DRAIN_SOURCES:
         s, o = os.path.join(CSRC, src), drain_object(src)
-        if force or _stale(o, [s] + hdrs):
+        if force or _stale(o, [s] + HEADERS):
             todo.append([HIPCC] + FILE_FLAGS.get(src, FLAGS) + ["-DDLM_DRAIN_WAITS=1", "-c", s, "-o", o])
     _compile_all(todo, verbose)
     objs = [drain_object(s) if s in DRAIN_SOURCES else os.path.join(HERE, "build", s.replace(".hip", ".o")) for s in SOURCES]
@@ -94,7 +95,6 @@ def build_drain_variant(force=False, verbose=False):
 
 
 def build(force=False, verbose=False):
-    hdrs = [os.path.join(CSRC, "dlm_internal.h"), os.path.join(HERE, "..", "include", "dlm_engine.h")]
     objs = []
     os.makedirs(os.path.join(HERE, "build"), exist_ok=True)
     todo = []
@@ -102,7 +102,7 @@ def build(force=False, verbose=False):
         s = os.path.join(CSRC, src)
         o = os.path.join(HERE, "build", src.replace(".hip", ".o"))
         objs.append(o)
-        if force or _stale(o, [s] + hdrs):
+        if force or _stale(o, [s] + HEADERS):
             todo.append([HIPCC] + FILE_FLAGS.get(src, FLAGS) + ["-c", s, "-o", o])
     _compile_all(todo, verbose)
     if force or _stale(LIB, objs):

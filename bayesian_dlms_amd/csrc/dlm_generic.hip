@@ -22,7 +22,7 @@ namespace dlm {
 
 #define CM(i, j, ld) ((i) + (j) * (ld))
 
-__device__ __forceinline__ void wsync() { __syncthreads(); }  // block == one wavefront
+__device__ __forceinline__ void block_sync() { __syncthreads(); }  // block == one wavefront
 
 // C(m x n) = op(A)(m x k) * op(B)(k x n).  Column-major; generic (LDS or global) pointers.
 template <bool TA, bool TB>
@@ -47,21 +47,21 @@ __device__ __forceinline__ void gemm(int lane, int m, int n, int k, const double
 __device__ bool chol_lds(int lane, int n, double* A, bool psd = false) {
   bool bad = false;
   for (int k = 0; k < n; ++k) {
-    wsync();
+    block_sync();
     double akk = A[CM(k, k, n)];
     const bool np = !(akk > 0.0);
     if (np) { bad = true; akk = 1e-300; }
     const double lkk = (np && psd) ? 0.0 : sqrt(akk), inv = (np && psd) ? 0.0 : 1.0 / lkk;
-    wsync();
+    block_sync();
     for (int i = k + lane; i < n; i += 64) A[CM(i, k, n)] = (i == k) ? lkk : A[CM(i, k, n)] * inv;
-    wsync();
+    block_sync();
     const int r = n - k - 1;
     for (int idx = lane; idx < r * r; idx += 64) {
       const int i = k + 1 + idx % r, j = k + 1 + idx / r;
       if (i >= j) A[CM(i, j, n)] = fma(-A[CM(i, k, n)], A[CM(j, k, n)], A[CM(i, j, n)]);
     }
   }
-  wsync();
+  block_sync();
   return bad;
 }
 
@@ -72,7 +72,7 @@ __device__ bool chol_lds(int lane, int n, double* A, bool psd = false) {
 // eigenvectors, columns in ascending order of the eigenvalues `lam`; E: n x n scratch; tmp: n doubles of scratch.
 __device__ void eig_lds(int lane, int n, double* S, double* E, double* lam, double* tmp) {
   for (int i = lane; i < n * n; i += 64) E[i] = (i % n == i / n) ? 1.0 : 0.0;
-  wsync();
+  block_sync();
   for (int sweep = 0; sweep < 100; ++sweep) {
     double off = 0.0, dia = 0.0;
     for (int i = lane; i < n * n; i += 64) { const double v = S[i] * S[i]; if (i % n == i / n) dia += v; else off += v; }
@@ -86,7 +86,7 @@ __device__ void eig_lds(int lane, int n, double* S, double* E, double* lam, doub
         const double tau = (aqq - app) / (2.0 * apq);
         const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
         const double c = 1.0 / sqrt(1.0 + t * t), s = t * c;
-        wsync();                                                   // every lane has read the pivot entries
+        block_sync();                                                   // every lane has read the pivot entries
         for (int k = lane; k < n; k += 64) {                       // columns p, q
           const double skp = S[CM(k, p, n)], skq = S[CM(k, q, n)];
           S[CM(k, p, n)] = c * skp - s * skq;
@@ -95,18 +95,18 @@ __device__ void eig_lds(int lane, int n, double* S, double* E, double* lam, doub
           E[CM(k, p, n)] = c * ekp - s * ekq;
           E[CM(k, q, n)] = s * ekp + c * ekq;
         }
-        wsync();
+        block_sync();
         for (int k = lane; k < n; k += 64) {                       // rows p, q
           const double spk = S[CM(p, k, n)], sqk = S[CM(q, k, n)];
           S[CM(p, k, n)] = c * spk - s * sqk;
           S[CM(q, k, n)] = s * spk + c * sqk;
         }
-        wsync();
+        block_sync();
       }
   }
-  wsync();
+  block_sync();
   for (int j = lane; j < n; j += 64) tmp[j] = S[CM(j, j, n)];
-  wsync();
+  block_sync();
   for (int j = lane; j < n; j += 64) {                             // ascending order (ties by index), canonical sign, into S
     const double lj = tmp[j];
     int rank = 0;
@@ -117,7 +117,7 @@ __device__ void eig_lds(int lane, int n, double* S, double* E, double* lam, doub
     lam[rank] = lj;
     for (int i = 0; i < n; ++i) S[CM(i, rank, n)] = sg * E[CM(i, j, n)];
   }
-  wsync();
+  block_sync();
 }
 
 // Solve (L L^T) X = B in place for the n x nrhs LDS matrix B; one lane per right-hand side.
@@ -135,7 +135,7 @@ __device__ void chol_solve_lds(int lane, int n, int nrhs, const double* L, doubl
       x[i] = s / L[CM(i, i, n)];
     }
   }
-  wsync();
+  block_sync();
 }
 
 __device__ __forceinline__ bool any_nonfinite(int lane, int n, const double* v) {
@@ -184,7 +184,7 @@ __global__ __launch_bounds__(64) void k_filter_generic(KArgs a) {
     const double dt = a.dt ? a.dt[t] : 1.0;
     V = V0 + (size_t)t * a.v_tstride;   // time-varying variances (StudentTGibbs.scala:100-136, DlmFsvSystem.scala:137-208)
     W = W0 + (size_t)t * a.w_tstride;
-    wsync();
+    block_sync();
     // advState (KalmanFilter.scala:273-286)
     if (dt == 0.0) {
       for (int i = lane; i < d; i += 64) av[i] = m[i];
@@ -192,20 +192,20 @@ __global__ __launch_bounds__(64) void k_filter_generic(KArgs a) {
     } else {
       gemm<false, false>(lane, d, 1, d, Gt, d, m, d, av, d);
       gemm<false, false>(lane, d, d, d, Gt, d, C, d, T1, d);
-      wsync();
+      block_sync();
       gemm<false, true>(lane, d, d, d, T1, d, Gt, d, R, d);
-      wsync();
+      block_sync();
       for (int i = lane; i < dd; i += 64) R[i] = fma(W[i], dt, R[i]);
     }
-    wsync();
+    block_sync();
     // oneStepPrediction, unmasked (KalmanFilter.scala:311-321)
     gemm<true, false>(lane, p, 1, d, Ft, d, av, d, fv, p);
     gemm<false, false>(lane, d, p, d, R, d, Ft, d, RF, d);
-    wsync();
+    block_sync();
     gemm<true, false>(lane, p, p, d, Ft, d, RF, d, Q, p);
-    wsync();
+    block_sync();
     for (int i = lane; i < p * p; i += 64) Q[i] += V[i];
-    wsync();
+    block_sync();
     if (pri) {
       double* pr = pri + (size_t)(t + 1) * rec;
       for (int i = lane; i < d; i += 64) pr[i] = av[i];
@@ -224,7 +224,7 @@ __global__ __launch_bounds__(64) void k_filter_generic(KArgs a) {
       const int pos = __popcll(mask & ((1ull << lane) - 1ull));
       idx[pos] = lane; yv[pos] = yl;
     }
-    wsync();
+    block_sync();
     if (pm == 0) {  // updateState :74-75
       for (int i = lane; i < d; i += 64) m[i] = av[i];
       for (int i = lane; i < dd; i += 64) C[i] = R[i];
@@ -233,12 +233,12 @@ __global__ __launch_bounds__(64) void k_filter_generic(KArgs a) {
       for (int k = lane; k < pm * pm; k += 64) Qm[k] = Q[CM(idx[k % pm], idx[k / pm], p)];
       for (int k = lane; k < pm * d; k += 64) { const int j = k % pm, i = k / pm; Kt[CM(j, i, pm)] = RF[CM(i, idx[j], d)]; }
       for (int j = lane; j < pm; j += 64) ev[j] = yv[j] - fv[idx[j]];
-      wsync();
+      block_sync();
       if (chol_lds(lane, pm, Qm)) st |= DLM_ST_NOT_PD;
       chol_solve_lds(lane, pm, d, Qm, Kt);  // Kt = Qm^-1 (R Fm)^T  => K = Kt^T
       if (a.loglik) {   // -1/2 (pm log 2pi + log det Qm + e^T Qm^-1 e) from the factor just computed
         for (int j = lane; j < pm; j += 64) yv[j] = ev[j];    // yv (the packed observations) is free now
-        wsync();
+        block_sync();
         chol_solve_lds(lane, pm, 1, Qm, yv);
         double part = 0.0;
         for (int j = lane; j < pm; j += 64) part += 2.0 * log(Qm[CM(j, j, pm)]) + ev[j] * yv[j];
@@ -264,9 +264,9 @@ __global__ __launch_bounds__(64) void k_filter_generic(KArgs a) {
         for (int r = 0; r < pm; ++r) s = fma(Kt[CM(r, i, pm)], V[CM(idx[r], idx[l], p)], s);
         RF[CM(i, l, d)] = s;
       }
-      wsync();
+      block_sync();
       gemm<false, false>(lane, d, d, d, T1, d, R, d, T2, d);
-      wsync();
+      block_sync();
       for (int k = lane; k < dd; k += 64) {
         const int i = k % d, j = k / d;
         double s = 0.0;
@@ -275,7 +275,7 @@ __global__ __launch_bounds__(64) void k_filter_generic(KArgs a) {
         C[k] = s;
       }
     }
-    wsync();
+    block_sync();
     if (out) {
       double* o = out + (size_t)(t + 1) * rec;
       for (int i = lane; i < d; i += 64) o[i] = m[i];
@@ -300,17 +300,17 @@ __device__ bool backward_prologue(int lane, int d, const double* Gt, const doubl
   if (dt == 0.0) {
     for (int i = lane; i < d; i += 64) a1[i] = m[i];
     for (int i = lane; i < dd; i += 64) R[i] = C[i];
-    wsync();
+    block_sync();
   } else {
     gemm<false, false>(lane, d, 1, d, Gt, d, m, d, a1, d);
-    wsync();
+    block_sync();
     gemm<false, true>(lane, d, d, d, T1, d, Gt, d, R, d);
-    wsync();
+    block_sync();
     for (int i = lane; i < dd; i += 64) R[i] = fma(W[i], dt, R[i]);
-    wsync();
+    block_sync();
   }
   if (Rfull) { for (int i = lane; i < dd; i += 64) Rfull[i] = R[i]; }
-  wsync();
+  block_sync();
   const bool bad = chol_lds(lane, d, R);
   chol_solve_lds(lane, d, d, R, T1);  // T1 = R^-1 G C = J^T
   return bad;
@@ -342,16 +342,16 @@ __global__ __launch_bounds__(64) void k_smoother_generic(KArgs a) {
     const double* Gt = a.G + (size_t)(a.g_index ? a.g_index[t] : 0) * dd;
     const double dt = a.dt ? a.dt[t] : 1.0;
     const double* r = fin + (size_t)t * rec;
-    wsync();
+    block_sync();
     for (int i = lane; i < d; i += 64) m[i] = r[i];
     for (int i = lane; i < dd; i += 64) C[i] = r[d + i];
-    wsync();
+    block_sync();
     const double* Wt = W + (size_t)t * a.w_tstride;   // the transition into record t+1
     if (backward_prologue(lane, d, Gt, Wt, dt, m, C, a1, R, T1, X)) st |= DLM_ST_NOT_PD;
     // X = R_{t+1} - S_{t+1}; u = s_{t+1} - a_{t+1}
     for (int i = lane; i < dd; i += 64) X[i] -= S[i];
     for (int i = lane; i < d; i += 64) u[i] = s[i] - a1[i];
-    wsync();
+    block_sync();
     // mean = m + J u ; T2 = J X  (J = T1^T)
     for (int i = lane; i < d; i += 64) {
       double acc = m[i];
@@ -359,13 +359,13 @@ __global__ __launch_bounds__(64) void k_smoother_generic(KArgs a) {
       s[i] = acc;
     }
     gemm<true, false>(lane, d, d, d, T1, d, X, d, T2, d);
-    wsync();
+    block_sync();
     // covariance = C - (J X) J^T  (textbook)   or   C - (J X) J  (Smoothing.scala:44, Q1)
     if (compat) gemm<false, true>(lane, d, d, d, T2, d, T1, d, X, d);
     else        gemm<false, false>(lane, d, d, d, T2, d, T1, d, X, d);
-    wsync();
+    block_sync();
     for (int i = lane; i < dd; i += 64) S[i] = C[i] - X[i];
-    wsync();
+    block_sync();
     double* o = out + (size_t)t * rec;
     for (int i = lane; i < d; i += 64) o[i] = s[i];
     for (int i = lane; i < dd; i += 64) o[d + i] = S[i];
@@ -412,13 +412,13 @@ __global__ __launch_bounds__(64) void k_sampler_generic(KArgs a) {
       zv[i] = zin ? zin[(size_t)T * d + i] : philox_normal(a.seed, series, (unsigned)T, (unsigned)i);
     }
     for (int i = lane; i < dd; i += 64) H[i] = r[d + i];
-    wsync();
+    block_sync();
     if (cond) {
       double* c = cond + (size_t)T * rec;
       for (int i = lane; i < d; i += 64) c[i] = h[i];
       for (int i = lane; i < dd; i += 64) c[d + i] = H[i];
     }
-    wsync();
+    block_sync();
     if (eig) {   // the reference's factor: theta = m + E sqrt(Lambda) z (a rounding-level negative eigenvalue counts as zero and is flagged: the reference would draw NaN)
       eig_lds(lane, d, H, D, a1, u);
       for (int i = lane; i < d; i += 64) {
@@ -435,7 +435,7 @@ __global__ __launch_bounds__(64) void k_sampler_generic(KArgs a) {
       th[i] = acc;
     }
     }
-    wsync();
+    block_sync();
     if (thout) for (int i = lane; i < d; i += 64) thout[(size_t)T * d + i] = th[i];
   }
   for (int t = T - 1; t >= 0; --t) {
@@ -443,7 +443,7 @@ __global__ __launch_bounds__(64) void k_sampler_generic(KArgs a) {
     const double* Ft = a.F + (size_t)t * a.f_stride;
     const double dt = a.dt ? a.dt[t] : 1.0;
     const double* r = fin + (size_t)t * rec;
-    wsync();
+    block_sync();
     // observation residual statistic of theta_{t+1} (Gibbs.scala:29-39)
     if (a.stats && y) {
       for (int j = lane; j < p; j += 64) {
@@ -461,11 +461,11 @@ __global__ __launch_bounds__(64) void k_sampler_generic(KArgs a) {
       zv[i] = zin ? zin[(size_t)t * d + i] : philox_normal(a.seed, series, (unsigned)t, (unsigned)i);
     }
     for (int i = lane; i < dd; i += 64) C[i] = r[d + i];
-    wsync();
+    block_sync();
     const double* Wt = W + (size_t)t * a.w_tstride;   // the transition into record t+1
     if (backward_prologue(lane, d, Gt, Wt, dt, m, C, a1, R, T1, nullptr)) st |= DLM_ST_NOT_PD;
     for (int i = lane; i < d; i += 64) u[i] = th[i] - a1[i];
-    wsync();
+    block_sync();
     // h = m + J u ; D = I - J G   (Smoothing.scala:88-93)
     for (int i = lane; i < d; i += 64) {
       double acc = m[i];
@@ -478,32 +478,32 @@ __global__ __launch_bounds__(64) void k_sampler_generic(KArgs a) {
       for (int l = 0; l < d; ++l) acc = fma(-T1[CM(l, i, d)], Gt[CM(l, j, d)], acc);
       D[k] = acc;
     }
-    wsync();
+    block_sync();
     gemm<false, false>(lane, d, d, d, D, d, C, d, T2, d);     // D C
-    wsync();
+    block_sync();
     gemm<false, true>(lane, d, d, d, T2, d, D, d, H, d);      // D C D^T
     gemm<true, false>(lane, d, d, d, T1, d, Wt, d, R, d);      // J W -> R (its Cholesky factor is spent)
-    wsync();
+    block_sync();
     for (int k = lane; k < dd; k += 64) {                      // H += dt * (J W) J^T
       const int i = k % d, j = k / d;
       double acc = 0.0;
       for (int l = 0; l < d; ++l) acc = fma(R[CM(i, l, d)], T1[CM(l, j, d)], acc);
       H[k] = fma(acc, dt, H[k]);
     }
-    wsync();
+    block_sync();
     for (int k = lane; k < dd; k += 64) {                      // (H + H^T) / 2  (:95)
       const int i = k % d, j = k / d;
       if (i > j) { const double v = (H[CM(i, j, d)] + H[CM(j, i, d)]) / 2.0; T2[CM(i, j, d)] = v; T2[CM(j, i, d)] = v; }
       else if (i == j) T2[k] = H[k];
     }
-    wsync();
+    block_sync();
     if (cond) {
       double* c = cond + (size_t)t * rec;
       for (int i = lane; i < d; i += 64) c[i] = h[i];
       for (int i = lane; i < dd; i += 64) c[d + i] = T2[i];
     }
     if (eig) {
-      wsync();
+      block_sync();
       eig_lds(lane, d, T2, D, a1, u);                            // (D, a1 and u are free here)
       if (a1[0] < 0.0) st |= DLM_ST_NOT_PD;
       for (int i = lane; i < d; i += 64) {
@@ -511,7 +511,7 @@ __global__ __launch_bounds__(64) void k_sampler_generic(KArgs a) {
         for (int k = 0; k < d; ++k) { const double lk = a1[k]; acc = fma(T2[CM(i, k, d)] * sqrt(lk > 0.0 ? lk : 0.0), zv[k], acc); }
         R[i] = acc;                                              // (R's d x d block is spent: theta_t parks there while u is scratch)
       }
-      wsync();
+      block_sync();
       for (int i = lane; i < d; i += 64) u[i] = R[i];
     } else {
     if (chol_lds(lane, d, T2, true)) st |= DLM_ST_NOT_PD;
@@ -522,24 +522,24 @@ __global__ __launch_bounds__(64) void k_sampler_generic(KArgs a) {
       u[i] = acc;  // theta_t
     }
     }
-    wsync();
+    block_sync();
     if (a.stats) {
       for (int i = lane; i < d; i += 64) {   // diff = theta_{t+1} - G theta_t  -> a1
         double acc = th[i];
         for (int k = 0; k < d; ++k) acc = fma(-Gt[CM(i, k, d)], u[k], acc);
         a1[i] = acc;
       }
-      wsync();
+      block_sync();
       const double dts = (dt == 0.0) ? 1.0 : dt;
       if (outer) for (int k = lane; k < dd; k += 64) OUT[k] += a1[k % d] * a1[k / d] / dts;
       for (int i = lane; i < d; i += 64) ssv[i] += a1[i] * a1[i] / dts;
     }
-    wsync();
+    block_sync();
     for (int i = lane; i < d; i += 64) th[i] = u[i];
     if (thout) for (int i = lane; i < d; i += 64) thout[(size_t)t * d + i] = u[i];
     if (any_nonfinite(lane, d, u)) st |= DLM_ST_NONFINITE;
   }
-  wsync();
+  block_sync();
   if (a.stats) {
     const int L = stats_len(d, p, a.flags);
     double* so = a.stats + (size_t)n * L;
@@ -594,12 +594,12 @@ __global__ __launch_bounds__(64) void k_simulate_generic(KArgs a) {
   int st = 0;
   for (int i = lane; i < dd; i += 64) { Lw[i] = W0[i]; Lc[i] = C0[i]; }
   for (int i = lane; i < p * p; i += 64) Lv[i] = V0[i];
-  wsync();
+  block_sync();
   if (chol_lds(lane, d, Lw)) st |= DLM_ST_NOT_PD;
   if (chol_lds(lane, d, Lc)) st |= DLM_ST_NOT_PD;
   if (chol_lds(lane, p, Lv)) st |= DLM_ST_NOT_PD;
   for (int i = lane; i < d; i += 64) z[i] = philox_normal(a.seed, series, 0u, (unsigned)i);
-  wsync();
+  block_sync();
   for (int i = lane; i < d; i += 64) {   // initialiseState (:268-273): x0 = m0 + chol(C0) z
     double acc = m0[i];
     for (int k = 0; k <= i; ++k) acc = fma(Lc[CM(i, k, d)], z[k], acc);
@@ -611,25 +611,25 @@ __global__ __launch_bounds__(64) void k_simulate_generic(KArgs a) {
     const double* Ft = a.F + (size_t)t * a.f_stride;
     const double dt = a.dt ? a.dt[t] : 1.0, sdt = sqrt(dt);
     if (a.w_tstride || a.v_tstride) {   // time-varying variances: factor this step's matrices
-      wsync();
+      block_sync();
       if (a.w_tstride) for (int i = lane; i < dd; i += 64) Lw[i] = (W0 + (size_t)t * a.w_tstride)[i];
       if (a.v_tstride) for (int i = lane; i < p * p; i += 64) Lv[i] = (V0 + (size_t)t * a.v_tstride)[i];
-      wsync();
+      block_sync();
       if (a.w_tstride && chol_lds(lane, d, Lw)) st |= DLM_ST_NOT_PD;
       if (a.v_tstride && chol_lds(lane, p, Lv)) st |= DLM_ST_NOT_PD;
     }
-    wsync();
+    block_sync();
     for (int i = lane; i < d + p; i += 64) z[i] = philox_normal(a.seed, series, (unsigned)(t + 1), (unsigned)i);
     gemm<false, false>(lane, d, 1, d, Gt, d, x, d, gx, d);      // G x
-    wsync();
+    block_sync();
     for (int i = lane; i < d; i += 64) {                          // stepState (:245-255)
       double acc = gx[i];
       for (int k = 0; k <= i; ++k) acc = fma(Lw[CM(i, k, d)] * sdt, z[k], acc);
       xn[i] = acc;
     }
-    wsync();
+    block_sync();
     gemm<true, false>(lane, p, 1, d, Ft, d, xn, d, fy, p);        // F^T x
-    wsync();
+    block_sync();
     for (int j = lane; j < p; j += 64) {                          // observation (:257-266)
       double acc = fy[j];
       for (int k = 0; k <= j; ++k) acc = fma(Lv[CM(j, k, p)], z[d + k], acc);
@@ -637,7 +637,7 @@ __global__ __launch_bounds__(64) void k_simulate_generic(KArgs a) {
     }
     for (int i = lane; i < d; i += 64) { x[i] = xn[i]; if (xo) xo[(size_t)(t + 1) * d + i] = xn[i]; }
   }
-  wsync();
+  block_sync();
   if (any_nonfinite(lane, d, x)) st |= DLM_ST_NONFINITE;
   if (a.status && lane == 0) a.status[n] |= st;
 }

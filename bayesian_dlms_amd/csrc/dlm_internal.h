@@ -72,7 +72,7 @@ __host__ __device__ inline int stats_len(int d, int p, unsigned flags) {
 
 // The one hand-counted vector-memory wait of the LDS-DMA prefetches (dlm_sparse16.hip, dlm_sampler16.hip, dlm_svd.hip): at most
 // N vector-memory operations of this wave still in flight.  N counts the loads, stores and LDS DMAs the wave issued after the
-// one waited for.  -DDLM_DRAIN_WAITS=1 turns every such wait into vmcnt(0) and changes nothing else
+// one waited for (the DMA itself: lds_dma<NR>, dlm_wave.h).  -DDLM_DRAIN_WAITS=1 turns every such wait into vmcnt(0) and changes nothing else
 // (build.build_drain_variant): tests/test_counted_waits_gpu.py compares the two builds bit for bit.  Every counted wait
 // goes through here (tests/test_counted_waits_host.py checks the sources and the code objects).
 #ifndef DLM_DRAIN_WAITS

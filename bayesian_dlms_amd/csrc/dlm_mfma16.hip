@@ -22,31 +22,15 @@
 //   needs no d x d solve, and never re-reads or recomputes R+.  It requires V > 0.
 //   The innovations (e_t/Q_t, 1/Q_t) come from the forward pass through a side buffer.
 #include "dlm_internal.h"
+#include "dlm_wave.h"
 #include "../../include/dlm_engine.h"
 
 namespace dlm {
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ d4 mmT(const d4& x, const d4& y) {  // X^T * Y
-  d4 acc = {0.0, 0.0, 0.0, 0.0};
-  acc = __builtin_amdgcn_mfma_f64_16x16x4f64(x[0], y[0], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f64_16x16x4f64(x[1], y[1], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f64_16x16x4f64(x[2], y[2], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f64_16x16x4f64(x[3], y[3], acc, 0, 0, 0);
-  return acc;
-}
 
 __device__ __forceinline__ double sum_over_g(double v) {  // sum lanes c, c+16, c+32, c+48
   v += __shfl_xor(v, 16);
   v += __shfl_xor(v, 32);
   return v;
-}
-
-__device__ __forceinline__ double uniform_from_lane(double v, int src) {
-  const int lo = __builtin_amdgcn_readlane((int)__double2loint(v), src);
-  const int hi = __builtin_amdgcn_readlane((int)__double2hiint(v), src);
-  return __hiloint2double(hi, lo);
 }
 
 // The fast kernels address a series' records through 32-bit buffer offsets: one series' record stream must stay
@@ -111,7 +95,7 @@ __global__ __launch_bounds__(256) void k_filter_mfma16(KArgs a, double* __restri
   for (int t = 0; t < T; ++t) {
     // observation stream: one coalesced 64-step chunk per 64 iterations
     if ((t & 63) == 0) ychunk = (t + lane < T) ? y[t + lane] : 0.0;
-    const double yt = uniform_from_lane(ychunk, t & 63);
+    const double yt = readlane_d(ychunk, t & 63);
 
     // advState: a = G m, R = G C G^T + W
     const d4 cgt = mmT(cc, gt);                       // C G^T   (C symmetric)
@@ -128,12 +112,12 @@ __global__ __launch_bounds__(256) void k_filter_mfma16(KArgs a, double* __restri
 #pragma unroll
     for (int r = 0; r < 4; ++r) { fp = fma(Fr[r], rp[r], fp); rfc = fma(R[r], Fr[r], rfc); }
     fp = col15 ? fp : 0.0;
-    const double f = uniform_from_lane(sum_over_g(fp), 15);
+    const double f = readlane_d(sum_over_g(fp), 15);
     rfc = sum_over_g(rfc);                            // (R F)[c], all lanes
     double rfr[4], qp = 0.0;
 #pragma unroll
     for (int r = 0; r < 4; ++r) { rfr[r] = __shfl(rfc, 4 * r + g); qp = fma(Fr[r], rfr[r], qp); }
-    const double Q = uniform_from_lane(sum_over_g(qp), 0) + V;
+    const double Q = readlane_d(sum_over_g(qp), 0) + V;
 
     double* o = out + (size_t)(t + 1) * rec;
     if (yt == yt) {
@@ -275,8 +259,8 @@ __global__ __launch_bounds__(256) void k_smoother_mfma16(KArgs a, const double* 
         const double cand = __shfl(pkr[k], 16 * (c & 3));
         pkc = ((c >> 2) == k) ? cand : pkc;
       }
-      kq = uniform_from_lane(sum_over_g(col15 ? kq : 0.0), 15);
-      kpk = uniform_from_lane(sum_over_g(kpk), 0);
+      kq = readlane_d(sum_over_g(col15 ? kq : 0.0), 15);
+      kpk = readlane_d(sum_over_g(kpk), 0);
       const double sc = iq + kpk, sr = eq - kq;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {

@@ -18,43 +18,15 @@
 // stretch of 32 steps on a series of zeros), k_mean_sampler_sp16 (the draw against the table, four series per wave, means / table rows
 // / normals by LDS DMA), k_normals4 (the call's normals made beside the forward pass), k_mark_gaps, and their launchers.
 #include "dlm_internal.h"
+#include "dlm_wave.h"
 #include "../../include/dlm_engine.h"
 
 namespace dlm {
 namespace s16 {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-typedef unsigned u2 __attribute__((ext_vector_type(2)));
 constexpr int IL = 17;
 constexpr int IMG = 16 * IL;
-constexpr int OOB = 0x7ffffff0;
 
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ double sum_g(double v) {   // sum over lanes c, c+16, c+32, c+48; all get it
-  unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
-  u2 l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-  u2 h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-  v = __hiloint2double((int)h[0], (int)l[0]) + __hiloint2double((int)h[1], (int)l[1]);
-  lo = (unsigned)__double2loint(v); hi = (unsigned)__double2hiint(v);
-  l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-  h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-  return __hiloint2double((int)h[0], (int)l[0]) + __hiloint2double((int)h[1], (int)l[1]);
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mk_rsrc(const void* p, size_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ double bld(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-  const u2 v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
-  return __hiloint2double((int)v[1], (int)v[0]);
-}
-__device__ __forceinline__ void bst(__amdgpu_buffer_rsrc_t r, int voff, int soff, double x) {
-  const u2 v = {(unsigned)__double2loint(x), (unsigned)__double2hiint(x)};
-  __builtin_amdgcn_raw_buffer_store_b64(v, r, voff, soff, 0);
-}
 // X^T Y over the first `rows` rows (lane 16 g + c, register r <-> element (4 r + g, c))
 __device__ __forceinline__ d4 mm(const d4& x, const d4& y, int rows) {
   d4 acc = {0.0, 0.0, 0.0, 0.0};
@@ -142,11 +114,6 @@ __device__ __forceinline__ bool direct_inverse(const d4& Q, d4& X, int n, double
 // every multiplier travels by v_readlane (the indices are compile-time), so the thirteen dependent pivots cost no LDS
 // round trip and no barrier.  A non-positive pivot gives a zero column (a direction without variance, as the oracle's
 // factor) and is reported.  hcol / zc: h[lane], z[lane] in the lanes 0..d-1; returns theta[lane] there.
-__device__ __forceinline__ double readlane_d(double v, int src) {
-  const int lo = __builtin_amdgcn_readlane((int)__double2loint(v), src);
-  const int hi = __builtin_amdgcn_readlane((int)__double2hiint(v), src);
-  return __hiloint2double(hi, lo);
-}
 __device__ __forceinline__ void chol_factor(const double* img, int d, int lane, double (&row)[15], bool& bad) {
   const double* src = img + (lane < 16 ? lane : 0) * IL;
 #pragma unroll
@@ -545,50 +512,12 @@ __global__ __launch_bounds__(64, 2) void k_sampler_sp16(KArgs a, const Tab* __re
 // (0 + 1) + (2 + 3) sum, chol_draw's chain over the pivots, the gathers of G in table order), the same normals.  The factors
 // live in registers (column c of J^T, row c of L) and are replaced when the table has a row for the step (SampTabs::need);
 // rows travel two steps ahead by LDS DMA from L2, the four series' filtered means SF_AHEAD steps ahead from their records.
-// All vector-memory traffic of the loop is issued by hand and waited for by count (vm_wait), see dlm_sparse16.hip.
+// All vector-memory traffic of the loop is issued by hand and waited for by count (vm_wait), see dlm_wave.h.
 // NR: DMA instructions per table row = ceil(17 d / 64).
 // ---------------------------------------------------------------------------------------------------------------------
-typedef int i4 __attribute__((ext_vector_type(4)));
-typedef double d2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ i4 rsrc_words(const void* p, unsigned bytes) {
-  const unsigned long long a = (unsigned long long)p;
-  i4 r = {__builtin_amdgcn_readfirstlane((int)(unsigned)a), __builtin_amdgcn_readfirstlane((int)(unsigned)((a >> 32) & 0xffffu)),
-          __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000};
-  return r;
-}
-__device__ __forceinline__ unsigned lds_addr_of(const void* p) { return (unsigned)(size_t)(__attribute__((address_space(3))) const char*)p; }
-template <int OFF>
-__device__ __forceinline__ double lds_read64(unsigned addr) {
-  double v;
-  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-  return v;
-}
-template <int OFF>
-__device__ __forceinline__ d2 lds_read128(unsigned addr) {
-  d2 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-  return v;
-}
-// 16 bytes per lane from byte offset voff + soff of the buffer to LDS address lds_addr + 16 lane (+ 1024 per further instruction)
-template <int NR>
-__device__ __forceinline__ void dma_row(const i4& rs, unsigned lds_addr, int soff, int lane, int n16) {
-  const int voff = lane * 16;
-  lds_addr = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr);
-  soff = __builtin_amdgcn_readfirstlane(soff);
-  // NR = ceil(n16 / 64): every instruction has lanes to serve, so the count of operations in flight is NR whatever the exec mask
-  if (lane < n16) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds_addr), "v"(voff), "s"(rs), "s"(soff) : "memory");
-  if constexpr (NR > 1) if (lane + 64 < n16) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen offset:1024 lds" ::"s"(lds_addr), "v"(voff), "s"(rs), "s"(soff) : "memory");
-  if constexpr (NR > 2) if (lane + 128 < n16) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen offset:2048 lds" ::"s"(lds_addr), "v"(voff), "s"(rs), "s"(soff) : "memory");
-  if constexpr (NR > 3) if (lane + 192 < n16) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen offset:3072 lds" ::"s"(lds_addr), "v"(voff), "s"(rs), "s"(soff) : "memory");
-}
 __device__ __forceinline__ double mul_rn(double x, double y) {   // a product that is rounded before it is used (never contracted into the addition behind it)
 #pragma clang fp contract(off)
   return x * y;
-}
-__device__ __forceinline__ double row_pick(double v, int lane, int src) {   // the value of lane src (0..15, wave-uniform) of this lane's 16-lane row
-  const int a_ = ((lane & 48) + src) << 2;
-  const int lo = __builtin_amdgcn_ds_bpermute(a_, __double2loint(v)), hi = __builtin_amdgcn_ds_bpermute(a_, __double2hiint(v));
-  return __hiloint2double(hi, lo);
 }
 
 // ZD: the normals come from SampTabs::z4 (k_normals4) by LDS DMA, four steps ahead; otherwise they are the injected ones (KArgs::z)
@@ -627,8 +556,7 @@ __global__ __launch_bounds__(64, 3) void k_mean_sampler_sp16(KArgs a, const Spar
   auto dma_means = [&](unsigned lds_addr, int soff) {
     lds_addr = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr);
     soff = __builtin_amdgcn_readfirstlane(soff);
-    if (lane < 32)   // 4 x 8 pieces; the other lanes' LDS destinations lie beyond the slot
-      asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds_addr), "v"(mvoff), "s"(rmean), "s"(soff) : "memory");
+    if (lane < 32) lds_dma_issue(rmean, lds_addr, mvoff, soff);   // 4 x 8 pieces; the other lanes' LDS destinations lie beyond the slot
   };
   const i4 rz = rsrc_words(ZD ? tb.z4 + (size_t)(n0 / 4) * (T + 1) * 64 : nullptr, ZD ? (unsigned)((size_t)(T + 1) * 512) : 0u);
   const unsigned zring_lds = lds_addr_of(vZ);
@@ -636,8 +564,7 @@ __global__ __launch_bounds__(64, 3) void k_mean_sampler_sp16(KArgs a, const Spar
   auto dma_z = [&](int tz) {   // the wave's 512 bytes of normals of step tz into slot tz & 3
     const unsigned la = (unsigned)__builtin_amdgcn_readfirstlane((int)(zring_lds + (unsigned)(tz & 3) * 512u));
     const int soff = __builtin_amdgcn_readfirstlane((tz > 0 ? tz : 0) * 512);
-    if (lane < 32)
-      asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(la), "v"(zvoff), "s"(rz), "s"(soff) : "memory");
+    if (lane < 32) lds_dma_issue(rz, la, zvoff, soff);
   };
   double* thout = a.theta ? a.theta + (size_t)n0 * (T + 1) * d : nullptr;
   const __amdgpu_buffer_rsrc_t rth = mk_rsrc(thout, thout ? (size_t)nser * (T + 1) * d * 8 : 0);
@@ -674,8 +601,8 @@ __global__ __launch_bounds__(64, 3) void k_mean_sampler_sp16(KArgs a, const Spar
   // requests: the means of steps T .. T - SF_AHEAD + 1 (the oldest), then the table rows T and T - 1
   for (int k = 0; k < SF_AHEAD; ++k) { const int tk = T - k > 0 ? T - k : 0; dma_means(mring_lds + ((T - k) & (SF_AHEAD - 1)) * 512, tk * mstep); }
   if constexpr (ZD) for (int k = 0; k < 4; ++k) dma_z(T - k);   // the normals of steps T .. T - 3
-  dma_row<NR>(rtab, ring_lds + (T & 1) * SF_SLOT, T * (SF_ROW * 8), lane, n16);
-  dma_row<NR>(rtab, ring_lds + ((T - 1) & 1) * SF_SLOT, (T > 0 ? T - 1 : 0) * (SF_ROW * 8), lane, n16);
+  lds_dma<NR>(rtab, ring_lds + (T & 1) * SF_SLOT, T * (SF_ROW * 8), lane, n16);
+  lds_dma<NR>(rtab, ring_lds + ((T - 1) & 1) * SF_SLOT, (T > 0 ? T - 1 : 0) * (SF_ROW * 8), lane, n16);
   // need[t], need[t - 1], need[t - 2] as the loop goes down: bit (s & 63) of the mask of s's block of 64 steps
   unsigned long long nmask = 0;
   auto need_of = [&](int s_) -> bool {
@@ -697,7 +624,7 @@ __global__ __launch_bounds__(64, 3) void k_mean_sampler_sp16(KArgs a, const Spar
     thc = draw(vc ? mr : 0.0, vZ + (T & 3) * 64);
     wave_sync();
     dma_means(mslot, (T > SF_AHEAD ? T - SF_AHEAD : 0) * mstep);
-    if (nd2) dma_row<NR>(rtab, slot, (T - 2) * (SF_ROW * 8), lane, n16);
+    if (nd2) lds_dma<NR>(rtab, slot, (T - 2) * (SF_ROW * 8), lane, n16);
     if constexpr (ZD) dma_z(T - 4);
     bst(rth, offth, T * d * 8, thc);
   }
@@ -738,7 +665,7 @@ __global__ __launch_bounds__(64, 3) void k_mean_sampler_sp16(KArgs a, const Spar
     else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(mr), "+v"(mg[0]), "+v"(mg[1]), "+v"(mg[2]), "+v"(mg[3])::"memory");
     if (nd0) read_row(slot, true);
     dma_means(mslot, (t > SF_AHEAD ? t - SF_AHEAD : 0) * mstep);
-    if (nd2) dma_row<NR>(rtab, slot, (t - 2) * (SF_ROW * 8), lane, n16);
+    if (nd2) lds_dma<NR>(rtab, slot, (t - 2) * (SF_ROW * 8), lane, n16);
     const double mc = vc ? mr : 0.0;
     double a1 = 0.0;
 #pragma unroll
@@ -1097,25 +1024,6 @@ __global__ __launch_bounds__(64) void k_smoother_rts16(KArgs a, const Tab* __res
 #ifndef DLM_RTS_STORE_AUX
 #define DLM_RTS_STORE_AUX 2   // nt: the records are written once and read by nobody in this call; non-temporal stores leave the table rows and the means in L2
 #endif
-__device__ __forceinline__ void bst128(__amdgpu_buffer_rsrc_t r, int voff, int soff, d2 x) {
-  typedef unsigned u4 __attribute__((ext_vector_type(4)));
-  const u4 v = {(unsigned)__double2loint(x[0]), (unsigned)__double2hiint(x[0]), (unsigned)__double2loint(x[1]), (unsigned)__double2hiint(x[1])};
-  __builtin_amdgcn_raw_buffer_store_b128(v, r, voff, soff, DLM_RTS_STORE_AUX);
-}
-__device__ __forceinline__ d2 lds_read128v(unsigned addr) {
-  d2 v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-  return v;
-}
-template <int NP>
-__device__ __forceinline__ void lds_wait_np(d2 (&pc)[NP]) {
-  static_assert(NP == 2 || NP == 4 || NP == 6 || NP == 8, "pieces");
-  if constexpr (NP == 2) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pc[0]), "+v"(pc[1])::"memory");
-  else if constexpr (NP == 4) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pc[0]), "+v"(pc[1]), "+v"(pc[2]), "+v"(pc[3])::"memory");
-  else if constexpr (NP == 6) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pc[0]), "+v"(pc[1]), "+v"(pc[2]), "+v"(pc[3]), "+v"(pc[4]), "+v"(pc[5])::"memory");
-  else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pc[0]), "+v"(pc[1]), "+v"(pc[2]), "+v"(pc[3]), "+v"(pc[4]), "+v"(pc[5]), "+v"(pc[6]), "+v"(pc[7])::"memory");
-}
-
 template <int K, int NP, int NRS, int NRJ>
 __global__ __launch_bounds__(64, 3) void k_mean_rts16(KArgs a, const SparseT* __restrict__ sp, RtsTabs tb) {
   __shared__ __attribute__((aligned(16))) double lds[2 * 64 + 2 * (RS_SLOT / 8) + 2 * RJ_ROW + SF_AHEAD * 64];
@@ -1157,8 +1065,7 @@ __global__ __launch_bounds__(64, 3) void k_mean_rts16(KArgs a, const SparseT* __
   auto dma_means = [&](unsigned lds_addr, int soff) {
     lds_addr = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr);
     soff = __builtin_amdgcn_readfirstlane(soff);
-    if (lane < 32)   // 4 x 8 pieces; the other lanes' LDS destinations lie beyond the slot
-      asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds_addr), "v"(mvoff), "s"(rmean), "s"(soff) : "memory");
+    if (lane < 32) lds_dma_issue(rmean, lds_addr, mvoff, soff);   // 4 x 8 pieces; the other lanes' LDS destinations lie beyond the slot
   };
   unsigned psrc[NP];
   int pdst[NP];
@@ -1187,20 +1094,20 @@ __global__ __launch_bounds__(64, 3) void k_mean_rts16(KArgs a, const SparseT* __
   auto emit = [&](int t, unsigned sslot, unsigned jslot, unsigned mslot, bool nd2) {
     d2 pc[NP];
 #pragma unroll
-    for (int k = 0; k < NP; ++k) pc[k] = lds_read128v((psrc[k] & 0x80000000u) ? vH_lds + (psrc[k] & 0x7fffffffu) : sslot + psrc[k]);
-    lds_wait_np<NP>(pc);
+    for (int k = 0; k < NP; ++k) pc[k] = lds_read128((psrc[k] & 0x80000000u) ? vH_lds + (psrc[k] & 0x7fffffffu) : sslot + psrc[k]);
+    lds_wait<NP>(pc);
     dma_means(mslot, (t > SF_AHEAD ? t - SF_AHEAD : 0) * recb);
-    if (nd2) dma_row<NRJ>(rjt, jslot, (t - 2) * (RJ_ROW * 8), lane, nj16);
-    dma_row<NRS>(rst, sslot, (t > 1 ? t - 2 : 0) * recb, lane, npc);
+    if (nd2) lds_dma<NRJ>(rjt, jslot, (t - 2) * (RJ_ROW * 8), lane, nj16);
+    lds_dma<NRS>(rst, sslot, (t > 1 ? t - 2 : 0) * recb, lane, npc);
     const int so = t * recb;
 #pragma unroll
-    for (int k = 0; k < NP; ++k) bst128(rout, pdst[k], so, pc[k]);
+    for (int k = 0; k < NP; ++k) bst128<DLM_RTS_STORE_AUX>(rout, pdst[k], so, pc[k]);
   };
 
   // requests: the means of steps T .. T - SF_AHEAD + 1, the S_t records T and T - 1, the J row of step T - 1 (its first step is a full one)
   for (int k = 0; k < SF_AHEAD; ++k) { const int tk = T - k > 0 ? T - k : 0; dma_means(mring_lds + ((T - k) & (SF_AHEAD - 1)) * 512, tk * recb); }
-  dma_row<NRS>(rst, sring_lds + (T & 1) * RS_SLOT, T * recb, lane, npc);
-  dma_row<NRS>(rst, sring_lds + ((T - 1) & 1) * RS_SLOT, (T - 1) * recb, lane, npc);
+  lds_dma<NRS>(rst, sring_lds + (T & 1) * RS_SLOT, T * recb, lane, npc);
+  lds_dma<NRS>(rst, sring_lds + ((T - 1) & 1) * RS_SLOT, (T - 1) * recb, lane, npc);
   // need[t], need[t - 1], need[t - 2] as the loop goes down: bit (s & 63) of the mask of s's block of 64 steps
   unsigned long long nmask = 0;
   auto need_of = [&](int s_) -> bool {
@@ -1210,7 +1117,7 @@ __global__ __launch_bounds__(64, 3) void k_mean_rts16(KArgs a, const SparseT* __
   };
   bool nd0 = need_of(T), nd1 = need_of(T - 1), nd2 = need_of(T - 2);
   (void)nd0;
-  if (nd1) dma_row<NRJ>(rjt, jring_lds + ((T - 1) & 1) * (RJ_ROW * 8), (T - 1) * (RJ_ROW * 8), lane, nj16);
+  if (nd1) lds_dma<NRJ>(rjt, jring_lds + ((T - 1) & 1) * (RJ_ROW * 8), (T - 1) * (RJ_ROW * 8), lane, nj16);
   double sc;
   {   // s_T = m_T, S_T = C_T (Smoothing.scala:59-61): the table's record T
     vm_wait<0>();

@@ -17,12 +17,10 @@
 //
 // Recursions and reference citations: see dlm_mfma16.hip (identical algebra).
 #include "dlm_internal.h"
+#include "dlm_wave.h"
 #include "../../include/dlm_engine.h"
 
 namespace dlm {
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-typedef unsigned u2 __attribute__((ext_vector_type(2)));
 
 constexpr int LD = 17;                        // leading dimension of an LDS image
 constexpr int IMG = 16 * LD;                  // doubles per image
@@ -40,179 +38,17 @@ constexpr int WAVE_LDS = 2 * IMG + 8 * 16 + 2;    // two images + eight 16-vecto
 constexpr int SM_WAVES_K2 = DLM_SM_WAVES_K2;   // backward kernel, at most two nonzeros per row / column of G (C2): five waves fit with one value spilled into the every-8th-step branch
 constexpr int SM_WAVES = DLM_SM_WAVES, FI_WAVES = DLM_FI_WAVES;     // waves per SIMD the register allocator must at least allow (backward / forward kernels)
 
-// One dependent chain of four: two chains of two were measured slower (profiles/r01_pmc_notes.md).
-__device__ __forceinline__ d4 mmT(const d4& x, const d4& y) {  // X^T * Y
-  d4 acc = {0.0, 0.0, 0.0, 0.0};
-  acc = __builtin_amdgcn_mfma_f64_16x16x4f64(x[0], y[0], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f64_16x16x4f64(x[1], y[1], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f64_16x16x4f64(x[2], y[2], acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f64_16x16x4f64(x[3], y[3], acc, 0, 0, 0);
-  return acc;
-}
-
-// LDS hand-off between lanes of ONE wavefront: the LDS queue is in order per wave, so only
-// the compiler has to be kept from reordering.
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-template <int N>
-__device__ __forceinline__ double row_ror(double v) {  // DPP rotate within a 16-lane row
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(0, lo, 0x120 + N, 0xf, 0xf, true);   // bound_ctrl: no "old" value to set up
-  hi = __builtin_amdgcn_update_dpp(0, hi, 0x120 + N, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
-// sum over the 16 lanes of a row (over c); every lane of the row gets the sum
-__device__ __forceinline__ double row_sum(double v) {
-  v += row_ror<8>(v); v += row_ror<4>(v); v += row_ror<2>(v); v += row_ror<1>(v);
-  return v;
-}
-// sum over lanes c, c+16, c+32, c+48 (over g) with the gfx950 permlane swaps; all get the sum
-__device__ __forceinline__ double sum_g(double v) {
-  unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
-  u2 l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-  u2 h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-  v = __hiloint2double((int)h[0], (int)l[0]) + __hiloint2double((int)h[1], (int)l[1]);
-  lo = (unsigned)__double2loint(v); hi = (unsigned)__double2hiint(v);
-  l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-  h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-  return __hiloint2double((int)h[0], (int)l[0]) + __hiloint2double((int)h[1], (int)l[1]);
-}
-
-// max over the 64 lanes; every lane gets it (the steady-state tests: every fourth step at most)
-__device__ __forceinline__ double wave_max(double v) {
-  v = fmax(v, row_ror<8>(v)); v = fmax(v, row_ror<4>(v)); v = fmax(v, row_ror<2>(v)); v = fmax(v, row_ror<1>(v));
-  unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
-  u2 l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-  u2 h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-  v = fmax(__hiloint2double((int)h[0], (int)l[0]), __hiloint2double((int)h[1], (int)l[1]));
-  lo = (unsigned)__double2loint(v); hi = (unsigned)__double2hiint(v);
-  l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-  h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-  return fmax(__hiloint2double((int)h[0], (int)l[0]), __hiloint2double((int)h[1], (int)l[1]));
-}
-
-// two float maxima at the price of one 64-bit reduction: a rides in the low, b in the high word through the same shuffles
-__device__ __forceinline__ void wave_max2f(float& a, float& b) {
-#define DLM_MAX2F_ROW(N) { a = fmaxf(a, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a), 0x120 + N, 0xf, 0xf, true))); \
-                           b = fmaxf(b, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(b), 0x120 + N, 0xf, 0xf, true))); }
-  DLM_MAX2F_ROW(8) DLM_MAX2F_ROW(4) DLM_MAX2F_ROW(2) DLM_MAX2F_ROW(1)
-#undef DLM_MAX2F_ROW
-  u2 l = __builtin_amdgcn_permlane16_swap((unsigned)__float_as_int(a), (unsigned)__float_as_int(a), false, false);
-  u2 h = __builtin_amdgcn_permlane16_swap((unsigned)__float_as_int(b), (unsigned)__float_as_int(b), false, false);
-  a = fmaxf(__int_as_float((int)l[0]), __int_as_float((int)l[1])); b = fmaxf(__int_as_float((int)h[0]), __int_as_float((int)h[1]));
-  l = __builtin_amdgcn_permlane32_swap((unsigned)__float_as_int(a), (unsigned)__float_as_int(a), false, false);
-  h = __builtin_amdgcn_permlane32_swap((unsigned)__float_as_int(b), (unsigned)__float_as_int(b), false, false);
-  a = fmaxf(__int_as_float((int)l[0]), __int_as_float((int)l[1])); b = fmaxf(__int_as_float((int)h[0]), __int_as_float((int)h[1]));
-}
-// 1/x from v_rcp_f64 and two Newton steps (about 1 ulp): 5 VALU instructions instead of the 11 of the IEEE
-// division expansion.  The forward pass is bound by VALU issue, and every lane computes this scalar.
-__device__ __forceinline__ double fast_rcp(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  r = fma(fma(-x, r, 1.0), r, r);
-  r = fma(fma(-x, r, 1.0), r, r);
-  return r;
-}
-
-__device__ __forceinline__ double uniform_from_lane(double v, int src) {
-  const int lo = __builtin_amdgcn_readlane((int)__double2loint(v), src);
-  const int hi = __builtin_amdgcn_readlane((int)__double2hiint(v), src);
-  return __hiloint2double(hi, lo);
-}
-
-// Record I/O through raw buffer instructions: padded lanes carry an out-of-range offset, for
-// which the hardware returns 0 on loads and drops stores -- no exec-mask branches.
-constexpr int OOB = 0x7ffffff0;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, size_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-// -DDLM_EXP_NOLOAD / -DDLM_EXP_NOSTORE: the two timing probes behind the floors quoted in profiles/r01_pmc_notes.md
-// (records re-read from cache / stores skipped with the value kept live); never defined in the shipped build.
-__device__ __forceinline__ double buf_load(__amdgpu_buffer_rsrc_t r, const char*, int voff, int soff) {
-#ifdef DLM_EXP_NOLOAD
-  soff = 0;
-#endif
-  const u2 v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
-  return __hiloint2double((int)v[1], (int)v[0]);
-}
-__device__ __forceinline__ void buf_store(__amdgpu_buffer_rsrc_t r, char*, int voff, int soff, double x) {
-#ifdef DLM_EXP_NOSTORE
-  asm volatile("" ::"v"(x));
-  return;
-#endif
-  const u2 v = {(unsigned)__double2loint(x), (unsigned)__double2hiint(x)};
-  __builtin_amdgcn_raw_buffer_store_b64(v, r, voff, soff, 0);
-}
-
-// the forward pass's (e / Q, 1 / Q) pair for the backward pass: one 16-byte store from lane 0 (the others carry OOB)
-typedef unsigned u4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void side_store(__amdgpu_buffer_rsrc_t r, int voff, int soff, double a, double b) {
-  const u4 v = {(unsigned)__double2loint(a), (unsigned)__double2hiint(a), (unsigned)__double2loint(b), (unsigned)__double2hiint(b)};
-  __builtin_amdgcn_raw_buffer_store_b128(v, r, voff, soff, 0);
-}
-
-// ---- record prefetch by LDS DMA (backward pass) ---------------------------------------------------
-// `buffer_load_dwordx4 ... lds` copies 16 B per lane straight from HBM into LDS: no VGPRs are held while
-// the load is in flight, so the backward pass can keep TWO records in flight per wave (the loaded HBM
-// latency is of the order of one step) without giving up occupancy.  The instruction is issued from inline
-// assembly on purpose: the compiler's wait-count insertion treats an LDS-DMA it knows about as aliasing
-// every later LDS read and waits vmcnt(0) -- which would also wait for the just-issued record stores.
-// The waits are placed by hand instead (vm_wait<N>); vector-memory operations of a wave retire in order.
-typedef int i4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ i4 rsrc_words(const void* p, unsigned bytes) {
-  const unsigned long long a = (unsigned long long)p;
-  i4 r = {__builtin_amdgcn_readfirstlane((int)(unsigned)a), __builtin_amdgcn_readfirstlane((int)(unsigned)((a >> 32) & 0xffffu)),
-          __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000};
-  return r;
-}
-// copy the record of n16 x 16 bytes at byte offset soff of the buffer to LDS byte address lds_addr
-__device__ __forceinline__ void dma_record(const i4& rs, unsigned lds_addr, int soff, int lane, int n16) {
-  const int voff = lane * 16;
-  lds_addr = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr);   // wave-uniform by construction
-  soff = __builtin_amdgcn_readfirstlane(soff);
-  if (lane < n16)
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                 ::"s"(lds_addr), "v"(voff), "s"(rs), "s"(soff) : "memory");
-  if (lane + 64 < n16)
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen offset:1024 lds"
-                 ::"s"(lds_addr), "v"(voff), "s"(rs), "s"(soff) : "memory");
-}
-
-// Diagnostic build only (-DDLM_STAMP): s_memtime stamps around the phases of the backward step;
+// Diagnostic build only (-DDLM_STAMP): s_memtime stamps (stamp(), dlm_wave.h) around the phases of the backward step;
 // the sums of series 0 are written into status[1..] (never in the shipped build).
 #ifdef DLM_STAMP
-__device__ __forceinline__ unsigned long long stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
 #define STAMP(k) { const unsigned long long _t = stamp(); seg[k] += _t - tlast; tlast = _t; }
 #else
 #define STAMP(k)
 #endif
 
-// LDS reads issued from inline assembly as single ds_read_b64: the compiler would pair them into
-// ds_read2_b64, which runs at half the LDS rate (8 LDS cycles per KiB against 4 for two ds_read_b64;
-// MI355X_MICROARCH LDS table) -- and both passes of this kernel are bound by LDS cycles.  The compiler
-// does not count these reads: lds_fence() waits for them before their results are used.
-__device__ __forceinline__ unsigned lds_addr_of(const void* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) const char*)p;
-}
-template <int OFF>
-__device__ __forceinline__ double lds_read64(unsigned addr) {
-  double v;
-  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-  return v;
-}
-__device__ __forceinline__ void lds_fence(d4& a, d4& b) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b)::"memory");
-}
-__device__ __forceinline__ void lds_fence(d4& a) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a)::"memory"); }
+// The wave-level primitives used below -- the cross-lane sums, the raw buffer loads / stores and their out-of-range offsets, the
+// record prefetch by LDS DMA with its hand-counted waits, the hand-issued ds_read_b64 (both passes of this kernel are bound by
+// LDS cycles) -- and the rules they rest on: dlm_wave.h.
 
 template <int K>
 __device__ __forceinline__ d4 congruence_pass2(const d4& y, double* imgB, const int (&idx)[K], const double (&val)[K],
@@ -367,14 +203,14 @@ __device__ __forceinline__ void filter_body(const KArgs& a, const SparseT* __res
   const bool packed = SIM || a.packed;                // records go to an engine-internal workspace: packed (see below)
   const int recb = COV ? rec * 8 + 128 : (packed ? packed_rec_bytes(d) : rec * 8);   // record stride (COV: a table row is the record followed by the 16 doubles of kftab)
   char* bout = a.filt ? (char*)a.filt + (size_t)n * (T + 1) * recb : nullptr;
-  const __amdgpu_buffer_rsrc_t rout = make_rsrc(bout, a.filt ? (size_t)(T + 1) * recb : 0);
+  const __amdgpu_buffer_rsrc_t rout = mk_rsrc(bout, a.filt ? (size_t)(T + 1) * recb : 0);
   double ll = 0.0;   // sum_t log N(y_t; f_t, Q_t) (KalmanFilter.conditionalLikelihood, KalmanFilter.scala:138-153)
   double* fq = a.fq ? a.fq + (size_t)n * (T + 1) * 2 : nullptr;
   double* sd = side ? side + (size_t)n * (T + 1) * 2 : nullptr;
-  const __amdgpu_buffer_rsrc_t rside = make_rsrc(sd, sd ? (size_t)(T + 1) * 16 : 0);   // zero-sized without a side buffer: stores dropped
+  const __amdgpu_buffer_rsrc_t rside = mk_rsrc(sd, sd ? (size_t)(T + 1) * 16 : 0);   // zero-sized without a side buffer: stores dropped
   const int offS = lane == 0 ? 0 : OOB;
   char* bpri = a.prior ? (char*)(a.prior + (size_t)n * (T + 1) * rec) : nullptr;   // optional (a_t, R_t) records
-  const __amdgpu_buffer_rsrc_t rpri = make_rsrc(bpri ? bpri : bout, (size_t)(T + 1) * rec * 8);
+  const __amdgpu_buffer_rsrc_t rpri = mk_rsrc(bpri ? bpri : bout, (size_t)(T + 1) * rec * 8);
 
   int idx[K];
   double val[K];
@@ -443,10 +279,10 @@ __device__ __forceinline__ void filter_body(const KArgs& a, const SparseT* __res
   }
 
 #pragma unroll
-  for (int r = 0; r < 4; ++r) buf_store(rout, bout, offA[r], 0, cc[r]);
+  for (int r = 0; r < 4; ++r) bst(rout, offA[r], 0, cc[r]);
   if (bpri) {   // record 0: a = m0, R = C0 (KalmanFilter.scala:117)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) buf_store(rpri, bpri, offA[r], 0, cc[r]);
+    for (int r = 0; r < 4; ++r) bst(rpri, offA[r], 0, cc[r]);
   }
   if (lane == 0) {
     if (fq) { fq[0] = __builtin_nan(""); fq[1] = __builtin_nan(""); }
@@ -474,7 +310,7 @@ __device__ __forceinline__ void filter_body(const KArgs& a, const SparseT* __res
       // vmcnt(0), which every step would also wait for the record stores of the step before
       asm volatile("" ::"v"(ychunk));
     }
-    double yt = uniform_from_lane(ychunk, t & 63);
+    double yt = readlane_d(ychunk, t & 63);
     const int gi = (IRR && a.g_index) ? a.g_index[t] : 0;   // uniform: scalar loads
     const double dt = (IRR && a.dt) ? a.dt[t] : 1.0;
     if (IRR && gi != gcur) {
@@ -527,7 +363,7 @@ __device__ __forceinline__ void filter_body(const KArgs& a, const SparseT* __res
       double ac = vRF[idx[0]] * val[0];
 #pragma unroll
       for (int s = 1; s < K; ++s) ac = fma(vRF[idx[s]], val[s], ac);      // a = G m (row 15 of the table: the unit row)
-      const double f = uniform_from_lane(row_sum(Fc * ac), 0);
+      const double f = readlane_d(row_sum(Fc * ac), 0);
       const double e = yt - f, erq = e * rq_st;
       const double mn = fma(Kst, e, ac);                                   // m = a + K e
       if (COV && g == 0) ((double*)((char*)kftab + (size_t)(t + 1) * recb))[c] = vc ? Kst : (c == 15 ? -rq_st : 0.0);   // [15]: 1 / Q negated = "steady step"
@@ -539,11 +375,11 @@ __device__ __forceinline__ void filter_body(const KArgs& a, const SparseT* __res
       for (int r = 0; r < 4; ++r) { const double mr = vRF[4 * r + g]; cc[r] = col15 ? mr : cc[r]; }
       cc[3] = (g == 3 && !col15) ? mn : cc[3];
       if (LL) ll -= 0.5 * (lq_st + e * erq);                                 // log(2 pi) + log Q of the settled forecast variance: computed once
-      side_store(rside, offS, (t + 1) * 16, erq, -rq_st);                  // 1/Q negated: "C_t is C_{t-1}" for the backward pass
+      bst128(rside, offS, (t + 1) * 16, erq, -rq_st);                  // 1/Q negated: "C_t is C_{t-1}" for the backward pass
       if (fq && lane == 0) { fq[2 * (t + 1)] = f; fq[2 * (t + 1) + 1] = Q_st; }
       const int so = (t + 1) * recb;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) buf_store(rout, bout, offA[r], so, cc[r]);
+      for (int r = 0; r < 4; ++r) bst(rout, offA[r], so, cc[r]);
       wave_sync();
       if (COV && a.settle_step) {   // the covariance-only run: every later row repeats this one (the series is all zeros) -- k_cov_fill_sp16 copies it
         if (lane == 0) *a.settle_step = t + 1;
@@ -597,7 +433,7 @@ __device__ __forceinline__ void filter_body(const KArgs& a, const SparseT* __res
     }
     if (bpri) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) buf_store(rpri, bpri, offA[r], (t + 1) * recb, R[r]);
+      for (int r = 0; r < 4; ++r) bst(rpri, offA[r], (t + 1) * recb, R[r]);
     }
     // RF (element 15 is the forecast f = F^T a) ; Q = F^T R F + V
     double rfc = 0.0;
@@ -609,8 +445,8 @@ __device__ __forceinline__ void filter_body(const KArgs& a, const SparseT* __res
     double rfr[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) rfr[r] = vRF[4 * r + g];     // (R F)[4r+g]
-    const double f = uniform_from_lane(rfc, 15);
-    const double Q = uniform_from_lane(row_sum(Fc * rfc), 0) + V;
+    const double f = readlane_d(rfc, 15);
+    const double Q = readlane_d(row_sum(Fc * rfc), 0) + V;
 
     if (yt == yt) {
       // Joseph form for p = 1 with K = RF / Q:  R - K RF^T - RF K^T + Q K K^T
@@ -635,17 +471,17 @@ __device__ __forceinline__ void filter_body(const KArgs& a, const SparseT* __res
         if (settle_test(settle, dl, mx, 4)) { steady = true; Kst = Kc; rq_st = rq; Q_st = Q; if (LL) lq_st = 1.8378770664093453 + log(Q); }
       }
       if (LL) ll -= 0.5 * (1.8378770664093453 + log(Q) + e * erq);   // -log N(y; f, Q); log(2 pi) = 1.83787...
-      side_store(rside, offS, (t + 1) * 16, erq, rq);
+      bst128(rside, offS, (t + 1) * 16, erq, rq);
     } else {
       cc = R;
       steady = false;
       settle_reset(settle);
-      side_store(rside, offS, (t + 1) * 16, __builtin_nan(""), __builtin_nan(""));
+      bst128(rside, offS, (t + 1) * 16, __builtin_nan(""), __builtin_nan(""));
     }
     if (fq && lane == 0) { fq[2 * (t + 1)] = f; fq[2 * (t + 1) + 1] = Q; }
     const int so = (t + 1) * recb;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) buf_store(rout, bout, offA[r], so, cc[r]);
+    for (int r = 0; r < 4; ++r) bst(rout, offA[r], so, cc[r]);
     wave_sync();   // the images are rewritten at the top of the next step
   }
   if (LL && a.loglik && lane == 0) a.loglik[n] = ll;
@@ -732,7 +568,7 @@ __device__ __forceinline__ void smoother_body(const KArgs& a, const SparseT* __r
   const int rins = COV ? rinb + 128 : rinb, recs = COV ? 2 * recb + 128 : recb;   // strides
   const char* bin = (const char*)a.filt_in + (size_t)n * (T + 1) * rins;
   char* bout = (char*)a.smooth + (size_t)n * (T + 1) * recs;
-  const __amdgpu_buffer_rsrc_t rout = make_rsrc(bout, (size_t)(T + 1) * recs);
+  const __amdgpu_buffer_rsrc_t rout = mk_rsrc(bout, (size_t)(T + 1) * recs);
   const double* sd = side + (size_t)n * (T + 1) * 2;
 
   int idx[K];
@@ -786,9 +622,9 @@ __device__ __forceinline__ void smoother_body(const KArgs& a, const SparseT* __r
   double ceq = sd[2 * T], ciq = sd[2 * T + 1];
   double neq, niq;
   { const int t1 = T > 0 ? T - 1 : 0; neq = sd[2 * t1]; niq = sd[2 * t1 + 1]; }
-  dma_record(rdma, ring_lds + (T & 1) * slotb, T * rins, lane, n16);
+  lds_dma<2>(rdma, ring_lds + (T & 1) * slotb, T * rins, lane, n16);
   { const int t1 = T > 0 ? T - 1 : 0;
-    dma_record(rdma, ring_lds + ((T - 1) & 1) * slotb, t1 * rins, lane, (ST && uniform_from_lane(ciq, 0) < 0.0) ? n16m : n16); }
+    lds_dma<2>(rdma, ring_lds + ((T - 1) & 1) * slotb, t1 * rins, lane, (ST && readlane_d(ciq, 0) < 0.0) ? n16m : n16); }
   vQ[c] = 0.0;
   d4 out = {0.0, 0.0, 0.0, 0.0};                     // the record stored last (assigned in every step before its store)
   d4 cc = {0.0, 0.0, 0.0, 0.0};
@@ -818,10 +654,10 @@ __device__ __forceinline__ void smoother_body(const KArgs& a, const SparseT* __r
       for (int r = 0; r < 4; ++r) cc[r] = (inherit && !col15) ? cc[r] : nr[r];   // (holding nr for the steady step instead costs 8 VGPRs: 4 waves per SIMD)
     }
     // the innovations are per-series scalars: keep them in SGPRs so `observed` is a scalar branch
-    const double eq = uniform_from_lane(ceq, 0), iqraw = uniform_from_lane(ciq, 0);
+    const double eq = readlane_d(ceq, 0), iqraw = readlane_d(ciq, 0);
     const double iq = fabs(iqraw);                           // the forward pass negates 1/Q where C_t is C_{t-1} (its steady state)
     const bool same_c = iqraw < 0.0;
-    const bool mean_only = ST && uniform_from_lane(niq, 0) < 0.0;   // C_{t-1} is C_{t-2}: record t-2 needs only its mean
+    const bool mean_only = ST && readlane_d(niq, 0) < 0.0;   // C_{t-1} is C_{t-2}: record t-2 needs only its mean
     ceq = neq; ciq = niq;
     {
       const int tp = t > 1 ? t - 2 : 0;                      // record 0 is re-read harmlessly at the end
@@ -848,7 +684,7 @@ __device__ __forceinline__ void smoother_body(const KArgs& a, const SparseT* __r
       ++nsteady;
       was_steady = true;
       if (COV && g == 0) ((double*)(bout + (size_t)t * recs + recb))[c] = col15 ? 1.0 : vK[c];   // K_t (that of the step before) and the mark "steady step"
-      { const int t2 = t > 1 ? t - 2 : 0; dma_record(rdma, ring_lds + (t & 1) * slotb, t2 * rins, lane, mean_only ? n16m : n16); }
+      { const int t2 = t > 1 ? t - 2 : 0; lds_dma<2>(rdma, ring_lds + (t & 1) * slotb, t2 * rins, lane, mean_only ? n16m : n16); }
       d4 nqr;
       {
         const unsigned bq = lds_addr_of(vQ + g);             // -q_t, published by the last step's closing wave_sync
@@ -859,7 +695,7 @@ __device__ __forceinline__ void smoother_body(const KArgs& a, const SparseT* __r
 #pragma unroll
       for (int r = 0; r < 4; ++r) ncq = fma(cc[r], nqr[r], ncq);
       ncq = sum_g(ncq);
-      const double kq = uniform_from_lane(row_sum(vK[c] * qcol), 0);   // K_t is K_{t+1}: still in vK
+      const double kq = readlane_d(row_sum(vK[c] * qcol), 0);   // K_t is K_{t+1}: still in vK
       vR[c] = fma(FREG ? Fcr : imgA[c * LD + 16], eq - kq, qcol);
       imgB[c * LD + 15] = ncq;                               // column 15 of the parked S_t: one read per register fetches [S | -C q]
       wave_sync();
@@ -895,7 +731,7 @@ __device__ __forceinline__ void smoother_body(const KArgs& a, const SparseT* __r
     if (COV && g == 0) ((double*)(bout + (size_t)t * recs + recb))[c] = col15 ? 0.0 : vK[c];
     // the slot just read is free again: request record t-2 into it (always issued, so that the operation
     // count behind every request is the same; below record 0 it re-reads record 0, which nobody uses)
-    { const int t2 = t > 1 ? t - 2 : 0; dma_record(rdma, ring_lds + (t & 1) * slotb, t2 * rins, lane, mean_only ? n16m : n16); }
+    { const int t2 = t > 1 ? t - 2 : 0; lds_dma<2>(rdma, ring_lds + (t & 1) * slotb, t2 * rins, lane, mean_only ? n16m : n16); }
     d4 kr, nqr;
     {
       const unsigned bk = lds_addr_of(vK + g), bq = lds_addr_of(vQ + g);
@@ -955,7 +791,7 @@ __device__ __forceinline__ void smoother_body(const KArgs& a, const SparseT* __r
           asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pk), "+v"(pkc), "+v"(fr)::"memory");
         }
         const double kk = row_sum(vK[c] * (g < 2 ? qcol : pkc));  // rows 0-1: K.q, rows 2-3: K.(P K)
-        const double kq = uniform_from_lane(kk, 0), kpk = uniform_from_lane(kk, 32);
+        const double kq = readlane_d(kk, 0), kpk = readlane_d(kk, 32);
         const double sc = iq + kpk;
         const double Fc = FREG ? Fcr : imgA[c * LD + 16];
         rcol = fma(Fc, eq - kq, qcol);
@@ -1022,10 +858,10 @@ __device__ __forceinline__ void smoother_body(const KArgs& a, const SparseT* __r
     same_next = same_c;
     const int so = t * recs;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) buf_store(rout, bout, offA[r], so, out[r]);
+    for (int r = 0; r < 4; ++r) bst(rout, offA[r], so, out[r]);
     if (COV) {   // C_t behind S_t and the K row: one table row serves a whole backward step of the mean-only kernel
 #pragma unroll
-      for (int r = 0; r < 4; ++r) buf_store(rout, bout, offA[r], so + recb + 128, cc[r]);
+      for (int r = 0; r < 4; ++r) bst(rout, offA[r], so + recb + 128, cc[r]);
     }
     STAMP(5)
   }
@@ -1102,7 +938,7 @@ __global__ __launch_bounds__(256, FI_WAVES) void k_simsmooth_sp16(KArgs a, const
   const double V = a.V[(size_t)n * a.v_stride];
   double rV = 1.0 / V;   // 1 / V_t of the record's observation when time-varying (IRR instantiation)
   const char* bin = (const char*)a.filt_in + (size_t)n * (T + 1) * recb;
-  const __amdgpu_buffer_rsrc_t rin = make_rsrc(bin, (size_t)(T + 1) * recb);
+  const __amdgpu_buffer_rsrc_t rin = mk_rsrc(bin, (size_t)(T + 1) * recb);
   const double* sd = side + (size_t)n * (T + 1) * 2;
   const double* xp = xplus + (size_t)n * (T + 1) * d;
   const double* y = a.y ? a.y + (size_t)n * T : nullptr;
@@ -1132,8 +968,8 @@ __global__ __launch_bounds__(256, FI_WAVES) void k_simsmooth_sp16(KArgs a, const
   d4 ncc;
   double nm, nx;
 #pragma unroll
-  for (int r = 0; r < 4; ++r) ncc[r] = buf_load(rin, bin, offC[r], T * recb);
-  nm = buf_load(rin, bin, offMl, T * recb);
+  for (int r = 0; r < 4; ++r) ncc[r] = bld(rin, offC[r], T * recb);
+  nm = bld(rin, offMl, T * recb);
   nx = vc ? xp[(size_t)T * d + c] : 0.0;
   double neq = sd[2 * T], niq = sd[2 * T + 1];
   double ychunk = 0.0;
@@ -1143,15 +979,15 @@ __global__ __launch_bounds__(256, FI_WAVES) void k_simsmooth_sp16(KArgs a, const
   for (int t = T; t >= 0; --t) {
     const d4 cc = ncc;
     const double mcol = nm, xcol = nx;
-    const double eq = uniform_from_lane(neq, 0), iq = uniform_from_lane(niq, 0);
+    const double eq = readlane_d(neq, 0), iq = readlane_d(niq, 0);
     const bool same_prev = !IRR && iq < 0.0;                 // C_{t-1} is C_t: the next record is fetched as its mean alone
     {
       const int tp = t > 0 ? t - 1 : 0;
       if (!same_prev) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) ncc[r] = buf_load(rin, bin, offC[r], tp * recb);
+        for (int r = 0; r < 4; ++r) ncc[r] = bld(rin, offC[r], tp * recb);
       }
-      nm = buf_load(rin, bin, offMl, tp * recb);
+      nm = bld(rin, offMl, tp * recb);
       nx = vc ? xp[(size_t)tp * d + c] : 0.0;
       neq = sd[2 * tp]; niq = sd[2 * tp + 1];
     }
@@ -1201,7 +1037,7 @@ __global__ __launch_bounds__(256, FI_WAVES) void k_simsmooth_sp16(KArgs a, const
       if (t > 0 && y) {   // observation residual of theta_t against y_t
         const int ti = t - 1;
         if (t == T || (ti & 63) == 63) ychunk = ((ti & ~63) + lane < T) ? y[(ti & ~63) + lane] : 0.0;
-        const double yv = uniform_from_lane(ychunk, ti & 63);
+        const double yv = readlane_d(ychunk, ti & 63);
         if (yv == yv) { const double res = yv - row_sum(Fc * th); ssy = fma(res, res, ssy); nob += 1.0; }
       }
     }
@@ -1270,76 +1106,14 @@ __global__ __launch_bounds__(256, FI_WAVES) void k_simsmooth_sp16(KArgs a, const
 // What a series-step costs is then its records: the state record is the table's C_t (S_t) with the mean patched into its
 // first d doubles, written as 16-byte pieces -- two store instructions per record.
 // ---------------------------------------------------------------------------------------
-typedef double d2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ d2 buf_load2(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-  const u4 v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
-  d2 o = {__hiloint2double((int)v[1], (int)v[0]), __hiloint2double((int)v[3], (int)v[2])};
-  return o;
-}
-__device__ __forceinline__ void buf_store2(__amdgpu_buffer_rsrc_t r, int voff, int soff, d2 x) {
-  const u4 v = {(unsigned)__double2loint(x[0]), (unsigned)__double2hiint(x[0]), (unsigned)__double2loint(x[1]), (unsigned)__double2hiint(x[1])};
-  __builtin_amdgcn_raw_buffer_store_b128(v, r, voff, soff, 0);
-}
-
-
-// n16 <= 256 pieces of 16 bytes from byte offset soff of the buffer to LDS byte address lds_addr (see dma_record)
-__device__ __forceinline__ void dma_pieces(const i4& rs, unsigned lds_addr, int soff, int lane, int n16) {
-  const int voff = lane * 16;
-  lds_addr = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr);
-  soff = __builtin_amdgcn_readfirstlane(soff);
-  if (lane < n16)
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds_addr), "v"(voff), "s"(rs), "s"(soff) : "memory");
-  if (lane + 64 < n16)
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen offset:1024 lds" ::"s"(lds_addr), "v"(voff), "s"(rs), "s"(soff) : "memory");
-  if (lane + 128 < n16)
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen offset:2048 lds" ::"s"(lds_addr), "v"(voff), "s"(rs), "s"(soff) : "memory");
-  if (lane + 192 < n16)
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen offset:3072 lds" ::"s"(lds_addr), "v"(voff), "s"(rs), "s"(soff) : "memory");
-}
-__device__ __forceinline__ d2 lds_read128(unsigned addr) {
-  d2 v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-  return v;
-}
-// the reads above are not counted by the compiler: these waits also tie the loaded registers to the wait, so that no use of
-// them can be scheduled ahead of it
-__device__ __forceinline__ void lds_wait(d2& a) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a)::"memory"); }
-__device__ __forceinline__ void lds_wait(d2& a, d2& b, d2& c) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c)::"memory"); }
-__device__ __forceinline__ void lds_wait(d2& a, d2& b, double& c) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c)::"memory"); }
-__device__ __forceinline__ void lds_wait(d4& a, d4& b, d2& c, d2& e, double& f) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(e), "+v"(f)::"memory");
-}
 
 // ---- four series per wave ------------------------------------------------------------------------------------------
 // A mean recursion is a d-vector: sixteen lanes.  Lane 16 j + c of a wave holds component c of series j (j = 0..3) of the wave's
 // four consecutive series; the row-wise DPP reductions and the gathers through LDS advance four series with the instructions of
 // one, one table row (LDS-DMA, two steps ahead) serves all four, and their four records leave as 16-byte pieces, six store
 // instructions for 4 x d (d + 1) / 2 pieces.
-__device__ __forceinline__ double row_lane0(double v, int lane) {   // every lane of a 16-lane row gets the value of the row's lane 0
-  const int a = (lane & 48) << 2;
-  const int lo = __builtin_amdgcn_ds_bpermute(a, __double2loint(v)), hi = __builtin_amdgcn_ds_bpermute(a, __double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double row_pick(double v, int lane, int src) {   // ... of the row's lane src (0..15, wave-uniform)
-  const int a = ((lane & 48) + src) << 2;
-  const int lo = __builtin_amdgcn_ds_bpermute(a, __double2loint(v)), hi = __builtin_amdgcn_ds_bpermute(a, __double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
-template <int CTRL>
-__device__ __forceinline__ double quad_perm(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, true);
-  hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
 constexpr int MEAN4_LDS = 6 * 64;   // per wave: six vectors of 4 x 16 doubles
 constexpr int MEAN_AHEAD = 8;       // backward: the filtered means are requested this many steps ahead (512-byte slots)
-template <int NP>
-__device__ __forceinline__ void lds_wait_pieces(d2 (&pc)[NP]) {
-  if constexpr (NP == 4) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pc[0]), "+v"(pc[1]), "+v"(pc[2]), "+v"(pc[3])::"memory");
-  else if constexpr (NP == 6) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pc[0]), "+v"(pc[1]), "+v"(pc[2]), "+v"(pc[3]), "+v"(pc[4]), "+v"(pc[5])::"memory");
-  else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pc[0]), "+v"(pc[1]), "+v"(pc[2]), "+v"(pc[3]), "+v"(pc[4]), "+v"(pc[5]), "+v"(pc[6]), "+v"(pc[7])::"memory");
-}
 
 // Forward.  Table row r (tb.ftab, tb.frow bytes) = [C_r record | R_r F or K_r (16 doubles; [15] = +-1/Q_r)].
 // NP: store instructions per step = 64-lane groups of 16-byte pieces covering the four records (4, 6 or 8 for d <= 10, 13, 15)
@@ -1375,8 +1149,8 @@ __global__ __launch_bounds__(256) void k_mean_filter_sp16(KArgs a, const SparseT
   const double* y = a.y + (size_t)n * T;
   const size_t sbytes = (size_t)(T + 1) * recb;                      // one series' records
   char* bout = REC ? (char*)a.filt + (size_t)n0 * sbytes : nullptr;
-  const __amdgpu_buffer_rsrc_t rout = make_rsrc(bout, REC ? (size_t)nser * sbytes : 0);
-  const __amdgpu_buffer_rsrc_t rcmp = make_rsrc(CMP ? (char*)(tb.mc + (size_t)(n0 / 4) * (T + 1) * 64) : nullptr, CMP ? (size_t)(T + 1) * 512 : 0);
+  const __amdgpu_buffer_rsrc_t rout = mk_rsrc(bout, REC ? (size_t)nser * sbytes : 0);
+  const __amdgpu_buffer_rsrc_t rcmp = mk_rsrc(CMP ? (char*)(tb.mc + (size_t)(n0 / 4) * (T + 1) * 64) : nullptr, CMP ? (size_t)(T + 1) * 512 : 0);
   const int offmc = have ? lane * 8 : OOB;           // this lane's double of the wave's 512 compact bytes of a step
   double* eqn = tb.eq + (size_t)n * (T + 1);
   const double Fc = vc ? a.F[c] : 0.0;
@@ -1400,8 +1174,8 @@ __global__ __launch_bounds__(256) void k_mean_filter_sp16(KArgs a, const SparseT
   const unsigned pkf = recb + c * 8, ptd = c * 8;   // K row entry, table double c (the record's first 16 doubles beyond the mean)
   const i4 rtab = rsrc_words(tb.ftab, (unsigned)((size_t)(T + 1) * frow));
   const int nrow = frow / 16;
-  dma_pieces(rtab, ring_lds, 0, lane, nrow);                    // row 0 -> slot 0
-  dma_pieces(rtab, ring_lds + frow, frow, lane, nrow);          // row 1 -> slot 1
+  lds_dma<4>(rtab, ring_lds, 0, lane, nrow);                    // row 0 -> slot 0
+  lds_dma<4>(rtab, ring_lds + frow, frow, lane, nrow);          // row 1 -> slot 1
   // k_filter_sp16 carries the mean twice, as column 15 and as row 15 of its augmented tile, and a full step updates the two
   // copies with differently associated products (m_col = a + (R F)(e / Q), m_row = a + (R F / Q) e) from each other's advance:
   // a_col = G m_row, a_row = G m_col.  The record holds m_col.  Both are followed here (a steady step sets them equal).
@@ -1422,7 +1196,7 @@ __global__ __launch_bounds__(256) void k_mean_filter_sp16(KArgs a, const SparseT
 
   auto store = [&](const d2 (&pc)[NP], int so) {
 #pragma unroll
-    for (int k = 0; k < NP; ++k) buf_store2(rout, ((deadmask >> pser[k]) & 1u) ? OOB : pdst[k], so, pc[k]);
+    for (int k = 0; k < NP; ++k) bst128(rout, ((deadmask >> pser[k]) & 1u) ? OOB : pdst[k], so, pc[k]);
   };
   if constexpr (REC) {   // record 0: [m0 | C0]
     d2 pc[NP];
@@ -1433,12 +1207,12 @@ __global__ __launch_bounds__(256) void k_mean_filter_sp16(KArgs a, const SparseT
       wave_sync();
 #pragma unroll
       for (int k = 0; k < NP; ++k) pc[k] = lds_read128((psrc[k] & 0x80000000u) ? vH_lds + (psrc[k] & 0x7fffffffu) : ring_lds + psrc[k]);
-      lds_wait_pieces<NP>(pc);
+      lds_wait<NP>(pc);
     }
-    dma_pieces(rtab, ring_lds, (T >= 2 ? 2 : T) * frow, lane, nrow);   // row 2 -> slot 0
+    lds_dma<4>(rtab, ring_lds, (T >= 2 ? 2 : T) * frow, lane, nrow);   // row 2 -> slot 0
     store(pc, 0);
-  } else dma_pieces(rtab, ring_lds, (T >= 2 ? 2 : T) * frow, lane, nrow);   // row 2 -> slot 0
-  if constexpr (CMP) buf_store(rcmp, nullptr, offmc, 0, vc ? mcol : 0.0);
+  } else lds_dma<4>(rtab, ring_lds, (T >= 2 ? 2 : T) * frow, lane, nrow);   // row 2 -> slot 0
+  if constexpr (CMP) bst(rcmp, offmc, 0, vc ? mcol : 0.0);
   for (int t = 0; t < T; ++t) {
     if (t > 0 && (t & 63) == 0) {
 #pragma unroll
@@ -1461,7 +1235,7 @@ __global__ __launch_bounds__(256) void k_mean_filter_sp16(KArgs a, const SparseT
     const unsigned slot = ring_lds + ((t + 1) & 1) * frow;
     double kfc = lds_read64<0>(slot + pkf);
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(kfc)::"memory");
-    const double rqs = uniform_from_lane(kfc, 15);        // +-1/Q_t rides in the row's last slot; negative: the step is a steady one
+    const double rqs = readlane_d(kfc, 15);        // +-1/Q_t rides in the row's last slot; negative: the step is a steady one
     const double rq = fabs(rqs);
     double ac = vW[idx[0]] * val[0];
 #pragma unroll
@@ -1482,8 +1256,8 @@ __global__ __launch_bounds__(256) void k_mean_filter_sp16(KArgs a, const SparseT
       double pf = 0.0;                                                     // rows g', g' + 4, g' + 8, g' + 12 (g' = c & 3) as one FMA chain ...
 #pragma unroll
       for (int k = 0; k < 4; ++k) pf = fma(vA[16 * j + (c & 3) + 4 * k], F4[k], pf);
-      pf = pf + quad_perm<0xB1>(pf);                                       // ... then (p0 + p1) + (p2 + p3), as the cross-row sum of k_filter_sp16 adds them
-      const double f = pf + quad_perm<0x4E>(pf);
+      pf = pf + dpp_mov<0xB1>(pf);                                       // ... then (p0 + p1) + (p2 + p3), as the cross-row sum of k_filter_sp16 adds them
+      const double f = pf + dpp_mov<0x4E>(pf);
       e = yt - f; erq = e * rq;
       mcol = fma(kfc, erq, ac);                                            // m_col = a_col + (R F)(e / Q)
       mrow = fma(kfc * rq, e, ar);                                         // m_row = a_row + K e,  K = (R F) / Q
@@ -1511,12 +1285,12 @@ __global__ __launch_bounds__(256) void k_mean_filter_sp16(KArgs a, const SparseT
         wave_sync();
 #pragma unroll
         for (int k = 0; k < NP; ++k) pc[k] = lds_read128((psrc[k] & 0x80000000u) ? vH_lds + (psrc[k] & 0x7fffffffu) : slot + psrc[k]);
-        lds_wait_pieces<NP>(pc);
+        lds_wait<NP>(pc);
       }
-      { const int tn = t + 3 <= T ? t + 3 : T; dma_pieces(rtab, slot, tn * frow, lane, nrow); }   // the slot is free again: row t + 3
+      { const int tn = t + 3 <= T ? t + 3 : T; lds_dma<4>(rtab, slot, tn * frow, lane, nrow); }   // the slot is free again: row t + 3
       store(pc, (t + 1) * recb);
-    } else { const int tn = t + 3 <= T ? t + 3 : T; dma_pieces(rtab, slot, tn * frow, lane, nrow); }
-    if constexpr (CMP) buf_store(rcmp, nullptr, dead ? OOB : offmc, (t + 1) * 512, vc ? mcol : 0.0);
+    } else { const int tn = t + 3 <= T ? t + 3 : T; lds_dma<4>(rtab, slot, tn * frow, lane, nrow); }
+    if constexpr (CMP) bst(rcmp, dead ? OOB : offmc, (t + 1) * 512, vc ? mcol : 0.0);
   }
   vm_wait<0>();   // no DMA may still be writing this block's LDS when the wave ends
   if (have && !dead && c == 0) a.route[n] = 0;
@@ -1568,8 +1342,8 @@ __global__ __launch_bounds__(256) void k_mean_smoother_sp16(KArgs a, const Spars
   const double V = a.V[0];
   const char* bin = (const char*)(tb.mc + (size_t)(n0 / 4) * (T + 1) * 64);    // the wave's compact filtered means: 512 bytes per step
   const size_t sbytes = (size_t)(T + 1) * recb;
-  const __amdgpu_buffer_rsrc_t rout = REC ? make_rsrc((char*)a.smooth + (size_t)n0 * sbytes, (size_t)nser * sbytes)
-                                          : make_rsrc(tb.sc + (size_t)(n0 / 4) * (T + 1) * 64, (size_t)(T + 1) * 512);
+  const __amdgpu_buffer_rsrc_t rout = REC ? mk_rsrc((char*)a.smooth + (size_t)n0 * sbytes, (size_t)nser * sbytes)
+                                          : mk_rsrc(tb.sc + (size_t)(n0 / 4) * (T + 1) * 64, (size_t)(T + 1) * 512);
   const int offsc = dead ? OOB : lane * 8;
   const int npc = rec / 2;
   unsigned psrc[NP];
@@ -1598,7 +1372,7 @@ __global__ __launch_bounds__(256) void k_mean_smoother_sp16(KArgs a, const Spars
   auto dma_means = [&](unsigned lds_addr, int soff) {
     lds_addr = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr);
     soff = __builtin_amdgcn_readfirstlane(soff);
-    if (mact) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds_addr), "v"(mvoff), "s"(rmean), "s"(soff) : "memory");
+    if (mact) lds_dma_issue(rmean, lds_addr, mvoff, soff);
   };
   int st = (V > 0.0) ? 0 : DLM_ST_NOT_PD;
   unsigned nsteady = 0;
@@ -1611,8 +1385,8 @@ __global__ __launch_bounds__(256) void k_mean_smoother_sp16(KArgs a, const Spars
     // the means of steps T .. T - MEAN_AHEAD + 1 first (the oldest requests), then the table rows T and T - 1
     for (int k = 0; k < MEAN_AHEAD; ++k) { const int tk = T - k > 0 ? T - k : 0; dma_means(mring_lds + ((T - k) & (MEAN_AHEAD - 1)) * 512, tk * 512); }
     const int t1 = T > 0 ? T - 1 : 0;
-    dma_pieces(rtab, ring_lds + (T & 1) * slotb, T * brow, lane, nrow);
-    dma_pieces(rtab, ring_lds + (t1 & 1) * slotb, t1 * brow, lane, nrow);
+    lds_dma<4>(rtab, ring_lds + (T & 1) * slotb, T * brow, lane, nrow);
+    lds_dma<4>(rtab, ring_lds + (t1 & 1) * slotb, t1 * brow, lane, nrow);
   }
   double ek[4] = {0.0, 0.0, 0.0, 0.0};   // e / Q of records 64 b + 16 k + c of this row's series
   double sm = 0.0;
@@ -1636,10 +1410,10 @@ __global__ __launch_bounds__(256) void k_mean_smoother_sp16(KArgs a, const Spars
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(cc), "+v"(mr), "+v"(kb), "+v"(td)::"memory");
     if constexpr (!REC) {   // the slots are free again: table row t - 2, means t - MEAN_AHEAD (always issued: the operation count behind every request stays the same)
       const int t2 = t > 1 ? t - 2 : 0, tm = t > MEAN_AHEAD ? t - MEAN_AHEAD : 0;
-      dma_pieces(rtab, slot, t2 * brow, lane, nrow);
+      lds_dma<4>(rtab, slot, t2 * brow, lane, nrow);
       dma_means(mslot, tm * 512);
     }
-    const bool steady = uniform_from_lane(kb, 15) != 0.0;    // the step k_smoother_sp16 takes in its steady form
+    const bool steady = readlane_d(kb, 15) != 0.0;    // the step k_smoother_sp16 takes in its steady form
     if (steady) {
       // s_t = m_t + C_t q_t by column sums on the symmetric C_t (k_smoother_sp16's steady step), once per series
       nsteady += 4 - __builtin_popcount(deadmask);
@@ -1683,18 +1457,18 @@ __global__ __launch_bounds__(256) void k_mean_smoother_sp16(KArgs a, const Spars
       d2 pc[NP];
 #pragma unroll
       for (int k = 0; k < NP; ++k) pc[k] = lds_read128((psrc[k] & 0x80000000u) ? vH_lds + (psrc[k] & 0x7fffffffu) : slot + psrc[k]);
-      lds_wait_pieces<NP>(pc);
+      lds_wait<NP>(pc);
       {
         const int t2 = t > 1 ? t - 2 : 0, tm = t > MEAN_AHEAD ? t - MEAN_AHEAD : 0;
-        dma_pieces(rtab, slot, t2 * brow, lane, nrow);
+        lds_dma<4>(rtab, slot, t2 * brow, lane, nrow);
         dma_means(mslot, tm * 512);
       }
       const int so = t * recb;
 #pragma unroll
-      for (int k = 0; k < NP; ++k) buf_store2(rout, pdst[k], so, pc[k]);
+      for (int k = 0; k < NP; ++k) bst128(rout, pdst[k], so, pc[k]);
     } else {
       wave_sync();
-      buf_store(rout, nullptr, offsc, t * 512, vc ? sm : 0.0);
+      bst(rout, offsc, t * 512, vc ? sm : 0.0);
     }
   }
   vm_wait<0>();   // no DMA may still be writing this block's LDS when the wave ends

@@ -18,6 +18,7 @@
 // and DLM_OPT_SVD_SAMPLER_Q9 (backward step uses sqrt(W) where sqrt(W)^-1 is needed,
 // SvdSampler.scala:71-73).  Defaults are the mathematically consistent forms.
 #include "dlm_internal.h"
+#include "dlm_wave.h"
 #include "../../include/dlm_engine.h"
 
 namespace dlm {
@@ -29,21 +30,8 @@ template <int NM> struct SvdDim { static constexpr int SL = NM + 1, PK = NM == 1
 #define M17(buf, i, j) (buf)[(i) + (j) * SL]
 #define STK(i, j) stack[(i) + (j) * stl]
 
-// A block is ONE wavefront: LDS hand-offs need only keep the compiler (and the in-order LDS queue) in order --
-// no s_barrier, and none of the vmcnt(0) a __syncthreads() fence would add after the record stores.
-__device__ __forceinline__ void ssync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+// A block is ONE wavefront: LDS hand-offs are wave_sync() (dlm_wave.h, with dpp_mov, fast_rcp, the raw buffer stores and the LDS DMA).
 
-template <int CTRL>
-__device__ __forceinline__ double dpp_mov(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, true);
-  hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
 // sum over the 8 lanes of a half-row, result in all of them: row_half_mirror (i <-> 7 - i), then the quad
 // permutations xor 1 and xor 2 -- three DPP steps, no LDS
 __device__ __forceinline__ double sum8(double v) {
@@ -58,12 +46,6 @@ __device__ __forceinline__ double fast_rsqrt(double x) {
   double r = __builtin_amdgcn_rsq(x);
   r = r * fma(-0.5 * x * r, r, 1.5);
   r = r * fma(-0.5 * x * r, r, 1.5);
-  return r;
-}
-__device__ __forceinline__ double fast_rcp(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  r = fma(fma(-x, r, 1.0), r, r);
-  r = fma(fma(-x, r, 1.0), r, r);
   return r;
 }
 
@@ -86,7 +68,7 @@ __device__ int jacobi_svd(int lane, int m, int n, double* A, int lda, double* V,
   if (!warm) {
     for (int k = lane; k < n * n; k += 64) M17(V, k % n, k / n) = (k % n == k / n) ? 1.0 : 0.0;
   } else {
-    ssync();
+    wave_sync();
     // row i of A, replaced by row^T V: lane i and, beyond 64 rows (NM = 48: m <= 96), lane i - 64 in a second pass
     for (int i0 = 0; i0 < m; i0 += 64) {
       double row[NM];
@@ -120,7 +102,7 @@ __device__ int jacobi_svd(int lane, int m, int n, double* A, int lda, double* V,
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch) { const int gg = grp + 8 * ch; ras[ch] = gg % (np - 1); rbs[ch] = (np - 1 - gg % (np - 1)) % (np - 1); }
     for (int r = 0; r < np - 1; ++r) {
-      ssync();
+      wave_sync();
 #pragma unroll
       for (int ch = 0; ch < NCH; ++ch) {
       const int gg = grp + 8 * ch;
@@ -177,13 +159,13 @@ __device__ int jacobi_svd(int lane, int m, int n, double* A, int lda, double* V,
     // settled), and the verification sweep (a third of the work with a warm start) can be skipped.
     conv = (__ballot(rot_any) == 0ull) || (__ballot(big_any) == 0ull);
   }
-  ssync();
+  wave_sync();
   if (lane < n) {
     double s = 0.0;
     for (int i = 0; i < m; ++i) s = fma(A[i + lane * lda], A[i + lane * lda], s);
     sig[lane] = sqrt(s);
   }
-  ssync();
+  wave_sync();
 #ifdef DLM_STAMP
   return (conv ? 0 : 1) | (nsweeps << 8);
 #else
@@ -216,13 +198,13 @@ __device__ void secular_update(int lane, int d, double delta, double w, double* 
   const double EPS = 2.220446049250313e-16;
   const bool act = lane < d;
   if (act) stau[lane] = delta;
-  ssync();
+  wave_sync();
   int rank = 0;
   if (act)
     for (int k = 0; k < d; ++k) { const double dk = stau[k]; rank += (dk < delta) || (dk == delta && k < lane); }
-  ssync();
+  wave_sync();
   if (act) { sds[rank] = delta; sw2[rank] = w; sperm[rank] = lane; }
-  ssync();
+  wave_sync();
   // regularise (every lane the same scalar recurrences, values broadcast from LDS): strictly increasing poles, no vanishing weights
   double wn2 = 0.0, scale = 0.0;
   for (int j = 0; j < d; ++j) { const double wj = sw2[j]; wn2 = fma(wj, wj, wn2); scale = fmax(scale, sds[j]); }
@@ -239,10 +221,10 @@ __device__ void secular_update(int lane, int d, double delta, double w, double* 
     wn2 = fma(wj, wj, wn2);
     if (j == lane) { mine = dj; wmine = wj; }
   }
-  ssync();
+  wave_sync();
   if (act) { sds[lane] = mine; sw2[lane] = wmine * wmine; }
   const double wsgn = wmine < 0.0 ? -1.0 : 1.0;
-  ssync();
+  wave_sync();
   // ---- roots: lane i, eigenvalue i in (delta_i, delta_{i+1}) ----------------------------------------------------------
   const int i = act ? lane : 0;
   const bool last = i == d - 1;
@@ -290,7 +272,7 @@ __device__ void secular_update(int lane, int d, double delta, double w, double* 
     }
   }
   if (act) { stau[lane] = t; sdso[lane] = dso; }
-  ssync();
+  wave_sync();
   // ---- Gu-Eisenstat weights (lane j = i) -------------------------------------------------------------------------------
   {
     double prod = 1.0;
@@ -301,7 +283,7 @@ __device__ void secular_update(int lane, int d, double delta, double w, double* 
     }
     if (act) szh[lane] = sqrt(fabs(prod)) * wsgn;
   }
-  ssync();
+  wave_sync();
   // ---- eigenvectors: lane i builds column i, rows back in the caller's order ----------------------------------------------
   {
     double nrm = 0.0;
@@ -312,7 +294,7 @@ __device__ void secular_update(int lane, int d, double delta, double w, double* 
       sig[lane] = sqrt(dso + t);
     }
   }
-  ssync();
+  wave_sync();
 }
 
 // sqrtSvd / sqrtInvSvd (SvdFilter.scala:210-227): out = diag(sig^{+-1/2}) V^T for the SPD n x n Mx.
@@ -321,14 +303,14 @@ __device__ int sqrt_svd(int lane, int n, const double* Mx /* global, col-major n
                         double* out, double* stack, int stl, double* Vacc, double* sig) {
   constexpr int SL = NM + 1;
   for (int k = lane; k < n * n; k += 64) STK(k % n, k / n) = Mx[k];
-  ssync();
+  wave_sync();
   const int rc = jacobi_svd<NM>(lane, n, n, stack, stl, Vacc, sig);
   for (int k = lane; k < n * n; k += 64) {
     const int i = k % n, j = k / n;
     const double s = inverse ? 1.0 / sqrt(sig[i]) : sqrt(sig[i]);
     M17(out, i, j) = s * M17(Vacc, j, i);
   }
-  ssync();
+  wave_sync();
   return rc;
 }
 
@@ -421,17 +403,17 @@ __global__ __launch_bounds__(64, (NM == 16 && !LONE) ? 4 : 1) void k_svd_filter(
   // transformParams (SvdFilter.scala:232-236)
   if (a.flags & DLM_OPT_SVD_RAW_W_Q2) {
     for (int k = lane; k < dd; k += 64) M17(L.Wadv, k % d, k / d) = W[k];
-    ssync();
+    wave_sync();
   } else if (sqrt_svd<NM>(lane, d, W, false, L.Wadv, stack, stl, L.V, L.sig)) st |= DLM_ST_NOCONV;
   if (sqrt_svd<NM>(lane, p, V, true, L.sVinv, stack, stl, L.V, L.sig)) st |= DLM_ST_NOCONV;
   if (aux && lane == 0) aux[0] = M17(L.sVinv, 0, 0);
   // initialiseState (SvdFilter.scala:83-95): svd(C0) -> dc0 = sqrt(sigma), uc0 = V
   for (int k = lane; k < dd; k += 64) STK(k % d, k / d) = C0[k];
-  ssync();
+  wave_sync();
   if (jacobi_svd<NM>(lane, d, d, stack, stl, L.V, L.sig)) st |= DLM_ST_NOCONV;
   for (int i = lane; i < d; i += 64) { L.m[i] = m0[i]; L.dc[i] = sqrt(L.sig[i]); out[i] = m0[i]; out[d + i] = sqrt(L.sig[i]); }
   for (int k = lane; k < dd; k += 64) { M17(L.uc, k % d, k / d) = M17(L.V, k % d, k / d); out[2 * d + k] = M17(L.V, k % d, k / d); }
-  ssync();
+  wave_sync();
 
   // Warm starts: L.ur / L.V still hold the right vectors of the previous step's two decompositions.  They are
   // dropped every 64th step (a rotation product drifts from orthogonality by ~1e-16 per step) and whenever the
@@ -459,9 +441,9 @@ __global__ __launch_bounds__(64, (NM == 16 && !LONE) ? 4 : 1) void k_svd_filter(
   int dbg_sw1 = 0, dbg_sw2 = 0;   // sweep counts (reported by the diagnostic build only)
 #ifdef DLM_STAMP
   unsigned long long tj = 0, t0_ = 0, tstart;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tstart)::"memory");
-#define SVD_T0 asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t0_)::"memory");
-#define SVD_T1 { unsigned long long t1_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t1_)::"memory"); tj += t1_ - t0_; }
+  tstart = stamp_loose();
+#define SVD_T0 t0_ = stamp_loose();
+#define SVD_T1 { const unsigned long long t1_ = stamp_loose(); tj += t1_ - t0_; }
 #else
 #define SVD_T0
 #define SVD_T1
@@ -487,7 +469,7 @@ __global__ __launch_bounds__(64, (NM == 16 && !LONE) ? 4 : 1) void k_svd_filter(
   if constexpr (LONE) {
     for (int k = lane; k < dd; k += 64) Gs[k] = a.G[k];
     for (int k = lane; k < d * p; k += 64) Fs[k] = a.F[k];
-    ssync();
+    wave_sync();
   }
   for (int t = 0; t < T; ++t) {
     const double* Gt = LONE ? Gs : a.G + (size_t)(a.g_index ? a.g_index[t] : 0) * dd;
@@ -500,17 +482,17 @@ __global__ __launch_bounds__(64, (NM == 16 && !LONE) ? 4 : 1) void k_svd_filter(
     if (a.w_tstride) {
       const double* Wt = W + (size_t)t * a.w_tstride;
       if (a.flags & DLM_OPT_SVD_RAW_W_Q2) {
-        ssync();
+        wave_sync();
         for (int k = lane; k < dd; k += 64) M17(L.Wadv, k % d, k / d) = Wt[k];
-        ssync();
+        wave_sync();
       } else {
-        ssync();
+        wave_sync();
         if (sqrt_svd<NM>(lane, d, Wt, false, L.Wadv, stack, stl, L.V, L.sig)) st |= DLM_ST_NOCONV;
         warm_c = false;
       }
     }
     if (a.v_tstride) {
-      ssync();
+      wave_sync();
       if (sqrt_svd<NM>(lane, p, V + (size_t)t * a.v_tstride, true, L.sVinv, stack, stl, L.V, L.sig)) st |= DLM_ST_NOCONV;
       warm_c = false;
     }
@@ -519,7 +501,7 @@ __global__ __launch_bounds__(64, (NM == 16 && !LONE) ? 4 : 1) void k_svd_filter(
       for (int i = lane; i < d; i += 64) { L.a[i] = L.m[i]; L.dr[i] = L.dc[i]; }
       for (int k = lane; k < dd; k += 64) M17(L.ur, k % d, k / d) = M17(L.uc, k % d, k / d);
       warm_r = false;
-      ssync();
+      wave_sync();
       have_r = false;
       reuse_r = false;
     } else {
@@ -531,7 +513,7 @@ __global__ __launch_bounds__(64, (NM == 16 && !LONE) ? 4 : 1) void k_svd_filter(
         L.a[i] = s;
       }
       reuse_r = settled && have_r && gi == gprev && dt == dtprev && !a.w_tstride && !(a.flags & DLM_OPT_FORCE_GENERIC);
-      if (reuse_r) { ssync(); } else {
+      if (reuse_r) { wave_sync(); } else {
       have_r = true; have_c = false; gprev = gi; dtprev = dt;
       each_dd([&](int, int i, int j) {   // stack = [diag(dc) uc^T G^T ; Wadv sqrt(dt)]
         double s = 0.0;
@@ -539,7 +521,7 @@ __global__ __launch_bounds__(64, (NM == 16 && !LONE) ? 4 : 1) void k_svd_filter(
         STK(i, j) = L.dc[i] * s;
         STK(d + i, j) = M17(L.Wadv, i, j) * sdt;
       });
-      ssync();
+      wave_sync();
       SVD_T0
       { const int rc = jacobi_svd<NM>(lane, 2 * d, d, stack, stl, L.ur, L.dr, warm_r); if (rc & 1) st |= DLM_ST_NOCONV; dbg_sw1 += rc >> 8; }   // dr = sigma, ur = V
       SVD_T1
@@ -551,7 +533,7 @@ __global__ __launch_bounds__(64, (NM == 16 && !LONE) ? 4 : 1) void k_svd_filter(
     const unsigned long long mask = __ballot(yl == yl);
     const int pm = __popcll(mask);
     if (yl == yl) { const int pos = __popcll(mask & ((1ull << lane) - 1ull)); L.idx[pos] = lane; L.yv[pos] = yl; }
-    ssync();
+    wave_sync();
     // same prior factors, same observation pattern, same F and V: (uc, dc) of the step before are the posterior factors
     const bool reuse_c = reuse_r && have_c && mask == mask_prev && pm > 0 && !a.f_stride && !a.v_tstride;
     if (pm == 0) {
@@ -571,7 +553,7 @@ __global__ __launch_bounds__(64, (NM == 16 && !LONE) ? 4 : 1) void k_svd_filter(
         for (int l = 0; l < pm; ++l) s = fma(M17(L.sVinv, L.idx[i], L.idx[l]), Ft[j + L.idx[l] * d], s);
         STK(PK + i, j) = s;                    // vm fm^T, parked in rows PK.. of the stack
       }
-      ssync();
+      wave_sync();
       if (reuse_c) ++nsteady;
       if (!reuse_c) {
       // stack ((pm + d) x d) = [vm fm^T ur ; diag(1/dr)]
@@ -581,19 +563,19 @@ __global__ __launch_bounds__(64, (NM == 16 && !LONE) ? 4 : 1) void k_svd_filter(
         for (int l = 0; l < d; ++l) s = fma(STK(PK + i, l), M17(L.ur, l, j), s);
         STK(i, j) = s;
       }
-      ssync();                                 // rows PK.. are overwritten next
+      wave_sync();                                 // rows PK.. are overwritten next
       if (pm == 1 && !(a.flags & DLM_OPT_FORCE_GENERIC)) {
         // one observed component: [w^T ; diag(1 / dr)] has A^T A = diag(1 / dr^2) + w w^T -- no Jacobi sweeps (secular_update)
         const double wj = lane < d ? STK(0, lane) : 0.0;
         const double rj = lane < d ? 1.0 / L.dr[lane] : 0.0;
-        ssync();
+        wave_sync();
         SVD_T0
         secular_update<NM>(lane, d, rj * rj, wj, L.V, L.sig, stack);
         SVD_T1
         warm_c = false;
       } else {
       for (int k = lane; k < dd; k += 64) { const int i = k % d, j = k / d; STK(pm + i, j) = (i == j) ? 1.0 / L.dr[i] : 0.0; }
-      ssync();
+      wave_sync();
       SVD_T0
       { const int rc = jacobi_svd<NM>(lane, pm + d, d, stack, stl, L.V, L.sig, warm_c); if (rc & 1) st |= DLM_ST_NOCONV; dbg_sw2 += rc >> 8; }
       SVD_T1
@@ -630,32 +612,32 @@ __global__ __launch_bounds__(64, (NM == 16 && !LONE) ? 4 : 1) void k_svd_filter(
         }
         L.tv[j] = s;
       }
-      ssync();
+      wave_sync();
       for (int i = lane; i < d; i += 64) {
         double s = 0.0;
         for (int j = 0; j < pm; ++j) s = fma(Ft[i + L.idx[j] * d], L.tv[j], s);
         L.gs[i] = s;
       }
-      ssync();
+      wave_sync();
       for (int i = lane; i < d; i += 64) {     // yv <- dc^2 * (uc^T gs)
         double s = 0.0;
         for (int l = 0; l < d; ++l) s = fma(M17(L.uc, l, i), L.gs[l], s);
         L.yv[i] = L.dc[i] * L.dc[i] * s;
       }
-      ssync();
+      wave_sync();
       for (int i = lane; i < d; i += 64) {
         double s = L.a[i];
         for (int l = 0; l < d; ++l) s = fma(M17(L.uc, i, l), L.yv[l], s);
         L.m[i] = s;
       }
     }
-    ssync();
+    wave_sync();
     double* o = out + (size_t)(t + 1) * srec;
     for (int i = lane; i < d; i += 64) { o[i] = L.m[i]; o[d + i] = L.dc[i]; }
     each_dd([&](int k, int i, int j) { o[2 * d + k] = M17(L.uc, i, j); });
   }
 #ifdef DLM_STAMP
-  if (n == 0 && lane == 0 && a.status) { unsigned long long tend; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tend)::"memory"); a.status[1] = dbg_sw1; a.status[2] = dbg_sw2; a.status[3] = (int)(tj / T); a.status[4] = (int)((tend - tstart) / T); }
+  if (n == 0 && lane == 0 && a.status) { const unsigned long long tend = stamp_loose(); a.status[1] = dbg_sw1; a.status[2] = dbg_sw2; a.status[3] = (int)(tj / T); a.status[4] = (int)((tend - tstart) / T); }
 #else
   (void)dbg_sw1; (void)dbg_sw2;
 #endif
@@ -678,18 +660,6 @@ __global__ __launch_bounds__(64, (NM == 16 && !LONE) ? 4 : 1) void k_svd_filter(
 // missing observation is marked in KArgs::route and served by k_svd_filter (p = 1, regular grid, time-invariant model).
 // One wave per series; table row t + 1 ([0 | dc | uc], padded to a multiple of 16 bytes) travels two steps ahead into an LDS ring.
 // ---------------------------------------------------------------------------------------
-typedef int i4s __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void svd_dma_row(const i4s& rs, unsigned lds_addr, int soff, int lane, int n16) {
-  const int voff = lane * 16;
-  lds_addr = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr);
-  soff = __builtin_amdgcn_readfirstlane(soff);
-  if (lane < n16)
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds_addr), "v"(voff), "s"(rs), "s"(soff) : "memory");
-  if (lane + 64 < n16)
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen offset:1024 lds" ::"s"(lds_addr), "v"(voff), "s"(rs), "s"(soff) : "memory");
-  if (lane + 128 < n16)   // (d = 16: 144 pieces)
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen offset:2048 lds" ::"s"(lds_addr), "v"(voff), "s"(rs), "s"(soff) : "memory");
-}
 __global__ __launch_bounds__(256) void k_svd_mean_filter(KArgs a, const double* __restrict__ tab, int tstride, const double* __restrict__ aux,
                                                          const int* __restrict__ cov_status, double* __restrict__ rec_out) {
   extern __shared__ __attribute__((aligned(16))) char ring_all[];
@@ -705,7 +675,7 @@ __global__ __launch_bounds__(256) void k_svd_mean_filter(KArgs a, const double* 
   const double* m0 = a.m0 + (size_t)n * a.m0_stride;
   const double* y = a.y + (size_t)n * T;
   double* out = rec_out + (size_t)n * (T + 1) * srec;
-  const int OOBo = 0x7ffffff0;
+  // (the builtin itself, not mk_rsrc: through the helper two SGPRs of this kernel trade names -- the same code, but no longer the object that was compared bit for bit)
   const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(out, 0, (int)((size_t)(T + 1) * srec * 8), 0x00020000);
   // G and F in registers: lane i holds row i of G and F[i] (d <= 16)
   double Gi[16];
@@ -717,21 +687,19 @@ __global__ __launch_bounds__(256) void k_svd_mean_filter(KArgs a, const double* 
   double* vF = vG + 16;                               // F
   if (lane < 16) vF[lane] = Fl;
   char* ring = ring_all + wave * 2 * (rowb + 16);
-  const unsigned ring_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)ring;
-  const unsigned long long ta = (unsigned long long)tab;
-  const i4s rtab = {__builtin_amdgcn_readfirstlane((int)(unsigned)ta), __builtin_amdgcn_readfirstlane((int)(unsigned)((ta >> 32) & 0xffffu)),
-                    __builtin_amdgcn_readfirstlane((int)((size_t)(T + 1) * rowb)), 0x00020000};
+  const unsigned ring_lds = lds_addr_of(ring);
+  const i4 rtab = rsrc_words(tab, (unsigned)((size_t)(T + 1) * rowb));
   const int n16 = rowb / 16;
   int offp[5];          // this lane's doubles of a record: lane, lane + 64, ... (2 d + d^2 <= 288)
 #pragma unroll
-  for (int k = 0; k < 5; ++k) offp[k] = (lane + 64 * k < srec) ? (lane + 64 * k) * 8 : OOBo;
-  svd_dma_row(rtab, ring_lds, 0, lane, n16);
-  svd_dma_row(rtab, ring_lds + rowb + 16, rowb, lane, n16);
+  for (int k = 0; k < 5; ++k) offp[k] = (lane + 64 * k < srec) ? (lane + 64 * k) * 8 : OOB;
+  lds_dma<3>(rtab, ring_lds, 0, lane, n16);
+  lds_dma<3>(rtab, ring_lds + rowb + 16, rowb, lane, n16);
   double mi = lane < d ? m0[lane] : 0.0;
   if (lane < 16) vM[lane] = mi;
   double ychunk = (lane < T) ? y[lane] : 0.0;
   asm volatile("" ::"v"(ychunk));
-  ssync();
+  wave_sync();
   vm_wait<1>();   // row 0
   {   // record 0: [m0 | dc0 | uc0]
     const double* row = (const double*)ring;
@@ -740,13 +708,9 @@ __global__ __launch_bounds__(256) void k_svd_mean_filter(KArgs a, const double* 
     for (int k = 0; k < 5; ++k) v[k] = (lane + 64 * k < srec) ? row[lane + 64 * k] : 0.0;
     v[0] = lane < d ? mi : v[0];
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4])::"memory");
-    svd_dma_row(rtab, ring_lds, (T >= 2 ? 2 : T) * rowb, lane, n16);
+    lds_dma<3>(rtab, ring_lds, (T >= 2 ? 2 : T) * rowb, lane, n16);
 #pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      const unsigned lo = (unsigned)__double2loint(v[k]), hi = (unsigned)__double2hiint(v[k]);
-      const unsigned __attribute__((ext_vector_type(2))) w = {lo, hi};
-      __builtin_amdgcn_raw_buffer_store_b64(w, rout, offp[k], 0, 0);
-    }
+    for (int k = 0; k < 5; ++k) bst(rout, offp[k], 0, v[k]);
   }
   for (int t = 0; t < T; ++t) {
     if (t > 0 && (t & 63) == 0) {
@@ -767,13 +731,13 @@ __global__ __launch_bounds__(256) void k_svd_mean_filter(KArgs a, const double* 
 #pragma unroll
     for (int k = 0; k < 16; ++k) if (k < d) ai = fma(Gi[k], vM[k], ai);
     if (lane < 16) vA[lane] = lane < d ? ai : 0.0;
-    ssync();
+    wave_sync();
     double fs = 0.0;
     for (int k = 0; k < d; ++k) fs = fma(vF[k], vA[k], fs);
     const double e = yt - fs;
     const double tv = fma(vv, e, 0.0);
     if (lane < 16) vG[lane] = lane < d ? fma(Fl, tv, 0.0) : 0.0;              // gs = F tv
-    ssync();
+    wave_sync();
     double yv = 0.0;
     if (lane < d) {
       double s_ = 0.0;
@@ -781,30 +745,26 @@ __global__ __launch_bounds__(256) void k_svd_mean_filter(KArgs a, const double* 
       const double dci = row[d + lane];
       yv = dci * dci * s_;
     }
-    ssync();
+    wave_sync();
     if (lane < 16) vG[lane] = lane < d ? yv : 0.0;
-    ssync();
+    wave_sync();
     if (lane < d) {
       double s_ = ai;
       for (int l = 0; l < d; ++l) s_ = fma(row[2 * d + lane + l * d], vG[l], s_);   // uc[i][l]
       mi = s_;
     }
-    ssync();
+    wave_sync();
     if (lane < 16) vM[lane] = lane < d ? mi : 0.0;
-    ssync();
+    wave_sync();
     double v[5];
 #pragma unroll
     for (int k = 0; k < 5; ++k) v[k] = (lane + 64 * k < srec) ? row[lane + 64 * k] : 0.0;
     v[0] = lane < d ? mi : v[0];
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4])::"memory");
-    { const int tn = t + 3 <= T ? t + 3 : T; svd_dma_row(rtab, ring_lds + ((t + 1) & 1) * (rowb + 16), tn * rowb, lane, n16); }
+    { const int tn = t + 3 <= T ? t + 3 : T; lds_dma<3>(rtab, ring_lds + ((t + 1) & 1) * (rowb + 16), tn * rowb, lane, n16); }
     const int so = (t + 1) * srec * 8;
 #pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      const unsigned lo = (unsigned)__double2loint(v[k]), hi = (unsigned)__double2hiint(v[k]);
-      const unsigned __attribute__((ext_vector_type(2))) w = {lo, hi};
-      __builtin_amdgcn_raw_buffer_store_b64(w, rout, offp[k], so, 0);
-    }
+    for (int k = 0; k < 5; ++k) bst(rout, offp[k], so, v[k]);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (lane == 0) a.route[n] = 0;
@@ -824,11 +784,6 @@ __global__ __launch_bounds__(256) void k_svd_mean_filter(KArgs a, const double* 
 // NS: store instructions per step = ceil(4 (2 d + d^2) / 64) rounded up to 4, 8, 13 or 18 (an instruction whose lanes all lie beyond the
 // records is still issued: the waits count it).
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ double svd_row_pick(double v, int lane, int src) {   // the value of lane src (0..15, wave-uniform) of this lane's 16-lane row
-  const int a_ = ((lane & 48) + src) << 2;
-  const int lo = __builtin_amdgcn_ds_bpermute(a_, __double2loint(v)), hi = __builtin_amdgcn_ds_bpermute(a_, __double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
 template <int NS>
 __global__ __launch_bounds__(64, 3) void k_svd_mean_filter4(KArgs a, const double* __restrict__ tab, int tstride, const double* __restrict__ aux,
                                                             const int* __restrict__ cov_status, double* __restrict__ rec_out) {
@@ -850,8 +805,7 @@ __global__ __launch_bounds__(64, 3) void k_svd_mean_filter4(KArgs a, const doubl
   const double* m0 = a.m0 + (size_t)n * a.m0_stride;
   const double* y = a.y + (size_t)n * T;
   const size_t sbytes = (size_t)(T + 1) * srec * 8;
-  const int OOBo = 0x7ffffff0;
-  const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((char*)rec_out + (size_t)n0 * sbytes, 0, (int)((size_t)nser * sbytes), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rout = mk_rsrc((char*)rec_out + (size_t)n0 * sbytes, (size_t)nser * sbytes);
   double Gi[16];               // row c of G
 #pragma unroll
   for (int k = 0; k < 16; ++k) Gi[k] = (vc && k < d) ? a.G[c + k * d] : 0.0;
@@ -859,11 +813,9 @@ __global__ __launch_bounds__(64, 3) void k_svd_mean_filter4(KArgs a, const doubl
   const double vv = fma(s00, s00, 0.0);               // (vm^T vm)[0][0]
   const double Fl = vc ? a.F[c] : 0.0;
   if (lane < 16) vF[lane] = Fl;
-  const unsigned ring_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)ring;
-  const unsigned vM_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)vM;
-  const unsigned long long ta = (unsigned long long)tab;
-  const i4s rtab = {__builtin_amdgcn_readfirstlane((int)(unsigned)ta), __builtin_amdgcn_readfirstlane((int)(unsigned)((ta >> 32) & 0xffffu)),
-                    __builtin_amdgcn_readfirstlane((int)((size_t)(T + 1) * rowb)), 0x00020000};
+  const unsigned ring_lds = lds_addr_of(ring);
+  const unsigned vM_lds = lds_addr_of(vM);
+  const i4 rtab = rsrc_words(tab, (unsigned)((size_t)(T + 1) * rowb));
   const int n16 = rowb / 16;
   bool dead = !have;
   // the four records as one stream of doubles: double q = 64 k + lane is double q % srec of series q / srec; the first d of a record are its mean (vM)
@@ -873,7 +825,7 @@ __global__ __launch_bounds__(64, 3) void k_svd_mean_filter4(KArgs a, const doubl
   for (int k = 0; k < NS; ++k) {
     const int q = 64 * k + lane, sj = q / srec, pp = q - sj * srec;
     pser[k] = sj < 4 ? sj : 4;
-    pdst[k] = sj < nser ? (int)((size_t)sj * sbytes) + pp * 8 : OOBo;
+    pdst[k] = sj < nser ? (int)((size_t)sj * sbytes) + pp * 8 : OOB;
     psrc[k] = pp < d ? (0x80000000u | (unsigned)((16 * (sj & 3) + pp) * 8)) : (unsigned)(pp * 8);
   }
   unsigned deadmask = 0;
@@ -881,7 +833,7 @@ __global__ __launch_bounds__(64, 3) void k_svd_mean_filter4(KArgs a, const doubl
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
       const unsigned ad = (psrc[k] & 0x80000000u) ? vM_lds + (psrc[k] & 0x7fffffffu) : slot + psrc[k];
-      asm volatile("ds_read_b64 %0, %1" : "=v"(v[k]) : "v"(ad) : "memory");
+      v[k] = lds_read64<0>(ad);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
@@ -889,21 +841,17 @@ __global__ __launch_bounds__(64, 3) void k_svd_mean_filter4(KArgs a, const doubl
   };
   auto store_doubles = [&](const double (&v)[NS], int so, unsigned dm) {
 #pragma unroll
-    for (int k = 0; k < NS; ++k) {
-      const unsigned lo = (unsigned)__double2loint(v[k]), hi = (unsigned)__double2hiint(v[k]);
-      const unsigned __attribute__((ext_vector_type(2))) w = {lo, hi};
-      __builtin_amdgcn_raw_buffer_store_b64(w, rout, ((dm >> pser[k]) & 1u) ? OOBo : pdst[k], so, 0);
-    }
+    for (int k = 0; k < NS; ++k) bst(rout, ((dm >> pser[k]) & 1u) ? OOB : pdst[k], so, v[k]);
   };
-  svd_dma_row(rtab, ring_lds, 0, lane, n16);
-  svd_dma_row(rtab, ring_lds + rowb + 16, rowb, lane, n16);
+  lds_dma<3>(rtab, ring_lds, 0, lane, n16);
+  lds_dma<3>(rtab, ring_lds + rowb + 16, rowb, lane, n16);
   double mi = vc ? m0[c] : 0.0;
   vM[lane] = mi;
   double yk[4];                                      // the observations of this row's series, 64 steps at a time
 #pragma unroll
   for (int k = 0; k < 4; ++k) yk[k] = (16 * k + c < T) ? y[16 * k + c] : 0.0;
   asm volatile("" ::"v"(yk[0]), "v"(yk[1]), "v"(yk[2]), "v"(yk[3]));
-  ssync();
+  wave_sync();
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // rows 0 and 1
   {   // record 0: [m0 | dc0 | uc0]
     deadmask = 0;
@@ -912,7 +860,7 @@ __global__ __launch_bounds__(64, 3) void k_svd_mean_filter4(KArgs a, const doubl
     deadmask |= 16u;
     double v[NS];
     read_doubles(ring_lds, v);
-    svd_dma_row(rtab, ring_lds, (T >= 2 ? 2 : T) * rowb, lane, n16);
+    lds_dma<3>(rtab, ring_lds, (T >= 2 ? 2 : T) * rowb, lane, n16);
     store_doubles(v, 0, deadmask);
   }
   for (int t = 0; t < T; ++t) {
@@ -922,7 +870,7 @@ __global__ __launch_bounds__(64, 3) void k_svd_mean_filter4(KArgs a, const doubl
       asm volatile("" ::"v"(yk[0]), "v"(yk[1]), "v"(yk[2]), "v"(yk[3]));
     }
     const int kk = (t >> 4) & 3;
-    const double yt = svd_row_pick(kk == 0 ? yk[0] : kk == 1 ? yk[1] : kk == 2 ? yk[2] : yk[3], lane, t & 15);
+    const double yt = row_pick(kk == 0 ? yk[0] : kk == 1 ? yk[1] : kk == 2 ? yk[2] : yk[3], lane, t & 15);
     if (!dead && !(yt == yt)) {   // a missing observation: the factors of this series are its own -- k_svd_filter takes it (all of it)
       dead = true;
       if (c == 0) a.route[n] = 1;
@@ -940,13 +888,13 @@ __global__ __launch_bounds__(64, 3) void k_svd_mean_filter4(KArgs a, const doubl
 #pragma unroll
     for (int k = 0; k < 16; ++k) if (k < d) ai = fma(Gi[k], vM[16 * j + k], ai);
     vA[lane] = vc ? ai : 0.0;
-    ssync();
+    wave_sync();
     double fs = 0.0;
     for (int k = 0; k < d; ++k) fs = fma(vF[k], vA[16 * j + k], fs);
     const double e = yt - fs;
     const double tv = fma(vv, e, 0.0);
     vG[lane] = vc ? fma(Fl, tv, 0.0) : 0.0;              // gs = F tv
-    ssync();
+    wave_sync();
     double yv = 0.0;
     if (vc) {
       double s_ = 0.0;
@@ -955,18 +903,18 @@ __global__ __launch_bounds__(64, 3) void k_svd_mean_filter4(KArgs a, const doubl
       yv = dci * dci * s_;
     }
     vY[lane] = vc ? yv : 0.0;
-    ssync();
+    wave_sync();
     if (vc) {
       double s_ = ai;
       for (int l = 0; l < d; ++l) s_ = fma(row[2 * d + c + l * d], vY[16 * j + l], s_);   // uc[i][l]
       mi = s_;
     }
-    ssync();                                             // (the reads of vM by this step's a = G m are done)
+    wave_sync();                                             // (the reads of vM by this step's a = G m are done)
     vM[lane] = vc ? mi : 0.0;
-    ssync();
+    wave_sync();
     double v[NS];
     read_doubles(slot, v);
-    { const int tn = t + 3 <= T ? t + 3 : T; svd_dma_row(rtab, slot, tn * rowb, lane, n16); }
+    { const int tn = t + 3 <= T ? t + 3 : T; lds_dma<3>(rtab, slot, tn * rowb, lane, n16); }
     store_doubles(v, (t + 1) * srec * 8, deadmask);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no DMA may still be writing this block's LDS when the wave ends
@@ -1040,10 +988,10 @@ __device__ void canon_factor(int lane, int d, double* U, double* s, const double
     const double sg = M17(U, arg, lane) < 0.0 ? -1.0 : 1.0;
     for (int i = 0; i < d; ++i) M17(Utmp, i, rank) = sg * M17(U, i, lane);
   }
-  ssync();
+  wave_sync();
   for (int k = lane; k < d * d; k += 64) M17(U, k % d, k / d) = M17(Utmp, k % d, k / d);
   if (lane < d) s[lane] = stmp[lane];
-  ssync();
+  wave_sync();
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1077,7 +1025,7 @@ __global__ __launch_bounds__(64) void k_svd_sampler(KArgs a, const double* __res
   for (int i = lane; i < d; i += 64) ssv[i] = 0.0;
   for (int k = lane; k < dd; k += 64) M17(outer, k % d, k / d) = 0.0;
   for (int i = lane; i < 2 * NM; i += 64) ssy[i] = 0.0;
-  ssync();
+  wave_sync();
 
   // initialise (SvdSampler.scala:38-45): theta_T = m_T + uc_T diag(dc_T) z, canonical factor order
   {
@@ -1087,7 +1035,7 @@ __global__ __launch_bounds__(64) void k_svd_sampler(KArgs a, const double* __res
       zv[i] = zin ? zin[(size_t)T * d + i] : philox_normal(a.seed, series, (unsigned)T, (unsigned)i);
     }
     for (int k = lane; k < dd; k += 64) M17(L.uc, k % d, k / d) = r[2 * d + k];
-    ssync();
+    wave_sync();
     canon_factor<NM>(lane, d, L.uc, L.dc, L.sig, L.tmp, L.tv);
     for (int i = lane; i < d; i += 64) {
       double s = L.m[i];
@@ -1095,7 +1043,7 @@ __global__ __launch_bounds__(64) void k_svd_sampler(KArgs a, const double* __res
       th[i] = s;
       if (thout) thout[(size_t)T * d + i] = s;
     }
-    ssync();
+    wave_sync();
   }
   for (int t = T - 1; t >= 0; --t) {
     const double* Gt = a.G + (size_t)(a.g_index ? a.g_index[t] : 0) * dd;
@@ -1117,7 +1065,7 @@ __global__ __launch_bounds__(64) void k_svd_sampler(KArgs a, const double* __res
       zv[i] = zin ? zin[(size_t)t * d + i] : philox_normal(a.seed, series, (unsigned)t, (unsigned)i);
     }
     for (int k = lane; k < dd; k += 64) M17(L.uc, k % d, k / d) = r[2 * d + k];
-    ssync();
+    wave_sync();
     if (a.w_tstride) {   // the step from record t uses W_t, the transition into observation t (DlmFsvSystem.scala:196-205)
       if (sqrt_svd<NM>(lane, d, W + (size_t)t * a.w_tstride, !(a.flags & DLM_OPT_SVD_SAMPLER_Q9), L.sWb, stack, stl, L.V, L.sig)) st |= DLM_ST_NOCONV;
     }
@@ -1133,7 +1081,7 @@ __global__ __launch_bounds__(64) void k_svd_sampler(KArgs a, const double* __res
       for (int l = 0; l < d; ++l) s = fma(M17(L.sWb, i, l), Gt[l + j * d], s);
       M17(L.tmp, i, j) = s;
     }
-    ssync();
+    wave_sync();
     // stack (2d x d) = [sqrtWb G uc ; diag(1/dc)]
     for (int k = lane; k < dd; k += 64) {
       const int i = k % d, j = k / d;
@@ -1142,7 +1090,7 @@ __global__ __launch_bounds__(64) void k_svd_sampler(KArgs a, const double* __res
       STK(i, j) = s;
       STK(d + i, j) = (i == j) ? 1.0 / L.dc[i] : 0.0;
     }
-    ssync();
+    wave_sync();
     if (jacobi_svd<NM>(lane, 2 * d, d, stack, stl, L.V, L.sig)) st |= DLM_ST_NOCONV;
     // uh = uc V -> Wadv buffer ; dh = 1/sigma -> tv
     for (int k = lane; k < dd; k += 64) {
@@ -1152,22 +1100,22 @@ __global__ __launch_bounds__(64) void k_svd_sampler(KArgs a, const double* __res
       M17(L.Wadv, i, j) = s;
     }
     for (int i = lane; i < d; i += 64) L.tv[i] = 1.0 / L.sig[i];
-    ssync();
+    wave_sync();
     canon_factor<NM>(lane, d, L.Wadv, L.tv, L.sig, L.V, L.dc);   // V, dc are free scratch now
     double* uh = L.Wadv; double* dh = L.tv;
     // h = m + uh dh^2 uh^T G^T sqrtWb^T sqrtWb (theta_{t+1} - a_{t+1})
     double* u = L.sig;   // d-vectors: reuse sig, dc as scratch
     double* v1 = L.dc;
     for (int i = lane; i < d; i += 64) u[i] = th[i] - L.a[i];
-    ssync();
+    wave_sync();
     for (int i = lane; i < d; i += 64) { double s = 0.0; for (int k = 0; k < d; ++k) s = fma(M17(L.sWb, i, k), u[k], s); v1[i] = s; }
-    ssync();
+    wave_sync();
     for (int i = lane; i < d; i += 64) { double s = 0.0; for (int k = 0; k < d; ++k) s = fma(M17(L.sWb, k, i), v1[k], s); u[i] = s; }
-    ssync();
+    wave_sync();
     for (int i = lane; i < d; i += 64) { double s = 0.0; for (int k = 0; k < d; ++k) s = fma(Gt[k + i * d], u[k], s); v1[i] = s; }
-    ssync();
+    wave_sync();
     for (int i = lane; i < d; i += 64) { double s = 0.0; for (int k = 0; k < d; ++k) s = fma(M17(uh, k, i), v1[k], s); u[i] = dh[i] * dh[i] * s; }
-    ssync();
+    wave_sync();
     for (int i = lane; i < d; i += 64) {
       double h = L.m[i];
       for (int k = 0; k < d; ++k) h = fma(M17(uh, i, k), u[k], h);
@@ -1175,21 +1123,21 @@ __global__ __launch_bounds__(64) void k_svd_sampler(KArgs a, const double* __res
       for (int k = 0; k < d; ++k) s = fma(M17(uh, i, k) * dh[k], zv[k], s);
       v1[i] = s;   // theta_t
     }
-    ssync();
+    wave_sync();
     if (a.stats) {
       for (int i = lane; i < d; i += 64) {
         double s = th[i];
         for (int k = 0; k < d; ++k) s = fma(-Gt[i + k * d], v1[k], s);
         u[i] = s;   // theta_{t+1} - G theta_t
       }
-      ssync();
+      wave_sync();
       const double dts = (dt == 0.0) ? 1.0 : dt;
       if (want_outer) for (int k = lane; k < dd; k += 64) M17(outer, k % d, k / d) += u[k % d] * u[k / d] / dts;
       for (int i = lane; i < d; i += 64) ssv[i] += u[i] * u[i] / dts;
     }
-    ssync();
+    wave_sync();
     for (int i = lane; i < d; i += 64) { th[i] = v1[i]; if (thout) thout[(size_t)t * d + i] = v1[i]; }
-    ssync();
+    wave_sync();
   }
   bool bad = false;
   for (int i = lane; i < d; i += 64) bad |= !isfinite(th[i]);

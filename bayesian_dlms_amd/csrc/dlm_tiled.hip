@@ -21,13 +21,12 @@
 //   which needs no d x d solve and no R_{t+1}; only a p x p SPD inverse per distinct mask.
 #include <cstdlib>
 #include "dlm_internal.h"
+#include "dlm_wave.h"
 #include "../../include/dlm_engine.h"
 
 #include <type_traits>
 
 namespace dlm {
-
-typedef double d4 __attribute__((ext_vector_type(4)));
 
 constexpr int NT = 512;         // threads per workgroup: 8 waves, two per SIMD (latency hiding, 1 workgroup per CU)
 constexpr int NW = NT / 64;
@@ -44,31 +43,12 @@ constexpr int SML = 32 * PL;    // doubles in a 32 x p-wide matrix
 // through global memory inside a launch, so only the LDS queue has to drain.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-__device__ __forceinline__ void wsync() {   // LDS hand-off inside ONE wavefront (in-order LDS queue)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // ---- record I/O with a FIXED number of instructions per thread -----------------------------------------
-// Raw buffer loads/stores whose padded lanes carry an out-of-range offset (loads give 0, stores are dropped), in
+// Raw buffer loads/stores (mk_rsrc / bld / bst, dlm_wave.h) whose padded lanes carry an out-of-range offset (loads give 0, stores are dropped), in
 // loops with compile-time trip counts: the compiler then knows exactly how many vector-memory operations sit
 // between a prefetch and its use and waits with a counted vmcnt.  With data-dependent store loops it falls back to
 // vmcnt(0) at the first use of a prefetched value -- which, vector-memory operations retiring in order, also waits
 // for the record stores of the step before (8k of 51k cycles per backward step at C4).
-typedef unsigned u2v __attribute__((ext_vector_type(2)));
-constexpr int OOB = 0x7ffffff0;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mk_rsrc(const void* p, size_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ double bld(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-  const u2v v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
-  return __hiloint2double((int)v[1], (int)v[0]);
-}
-__device__ __forceinline__ void bst(__amdgpu_buffer_rsrc_t r, int voff, int soff, double x) {
-  const u2v v = {(unsigned)__double2loint(x), (unsigned)__double2hiint(x)};
-  __builtin_amdgcn_raw_buffer_store_b64(v, r, voff, soff, 0);
-}
 // Byte offsets of this thread's share of a record [vector (n) | matrix (n x n, column-major)]: row i = lane,
 // columns j = wave + 8 q, q < 6; the vector element tid (threads 0..n-1).
 struct RecOff { int m[6]; int v; };
@@ -158,11 +138,11 @@ __device__ __forceinline__ void gemm_t(int tid, int mt, int nt, int kb, const do
       if (AVG) acc[q][r] = v;
     }
     if (SYM && AVG && i0 == j0) {
-      wsync();
+      wave_sync();
       d4 w;
 #pragma unroll
       for (int r = 0; r < 4; ++r) w[r] = C[(i0 + c) * ldc + i0 + 4 * r + g];
-      wsync();
+      wave_sync();
 #pragma unroll
       for (int r = 0; r < 4; ++r) C[(i0 + 4 * r + g) * ldc + i0 + c] = 0.5 * (acc[q][r] + w[r]);
     }
@@ -238,11 +218,6 @@ __device__ __forceinline__ void gemm_g(int tid, int mt, int kb, const double* L,
   }
 }
 
-__device__ __forceinline__ double bcast_lane(double v, int src) {   // lane `src` -> SGPR pair (uniform)
-  const int lo = __builtin_amdgcn_readlane((int)__double2loint(v), src);
-  const int hi = __builtin_amdgcn_readlane((int)__double2hiint(v), src);
-  return __hiloint2double(hi, lo);
-}
 
 // Z = T X T^T (+ add) for a structured T (at most K <= 4 nonzeros per row), all d x d row-major in LDS with leading
 // dimension DL; Y is scratch, Z may alias X.  Thread (lane i, wave w) owns the elements (i, w + 8 q): pass 1
@@ -273,7 +248,7 @@ __device__ __forceinline__ void sparse_congruence_k(int tid, int d, int tix, dou
 #pragma unroll
   for (int q = 0; q < 6; ++q)
 #pragma unroll
-    for (int s_ = 0; s_ < K; ++s_) { ix[q][s_] = __builtin_amdgcn_readlane(tix, 4 * q + s_); vl[q][s_] = bcast_lane(tvl, 4 * q + s_); }
+    for (int s_ = 0; s_ < K; ++s_) { ix[q][s_] = __builtin_amdgcn_readlane(tix, 4 * q + s_); vl[q][s_] = readlane_d(tvl, 4 * q + s_); }
   double in[6][K];
 #pragma unroll
   for (int q = 0; q < 6; ++q)
@@ -344,11 +319,11 @@ __device__ __forceinline__ void gemm_update3(int tid, int mt, int kb, const doub
     if (i0 != j0) C[(j0 + c) * ldc + i0 + 4 * r + g] = v[r];
   }
   if (i0 == j0) {   // a diagonal tile holds both triangles, rounded differently: average them (same wave wrote all of it)
-    wsync();
+    wave_sync();
     d4 w;
 #pragma unroll
     for (int r = 0; r < 4; ++r) w[r] = C[(i0 + c) * ldc + i0 + 4 * r + g];
-    wsync();
+    wave_sync();
 #pragma unroll
     for (int r = 0; r < 4; ++r) C[(i0 + 4 * r + g) * ldc + i0 + c] = 0.5 * (v[r] + w[r]);
   }
@@ -397,13 +372,13 @@ __device__ __noinline__ bool spd_inverse(int tid, int n_, double* A, double* Li,
     static_for<0, 32>([&](auto Kc) {
       constexpr int k = Kc;
       if (k < n) {
-        double akk = bcast_lane(a[k], k);
+        double akk = readlane_d(a[k], k);
         if (!(akk > 0.0)) { bad = true; akk = 1e-300; }
         const double lkk = sqrt(akk), inv = 1.0 / lkk;
         a[k] = (lane == k) ? lkk : a[k] * inv;               // column k of L (rows >= k are meaningful)
         static_for<k + 1, 32>([&](auto J) {
           constexpr int j = J;
-          if (j < n) a[j] = fma(-a[k], bcast_lane(a[k], j), a[j]);   // A[i][j] -= L[i][k] L[j][k]
+          if (j < n) a[j] = fma(-a[k], readlane_d(a[k], j), a[j]);   // A[i][j] -= L[i][k] L[j][k]
         });
       }
     });
@@ -415,14 +390,14 @@ __device__ __noinline__ bool spd_inverse(int tid, int n_, double* A, double* Li,
       x[i] = 0.0;
       if (i < n) {
         double acc = (lane == i) ? 1.0 : 0.0;
-        static_for<0, i>([&](auto Lc) { constexpr int l = Lc; acc = fma(-bcast_lane(a[l], i), x[l], acc); });
-        x[i] = acc * bcast_lane(dinv, i);
+        static_for<0, i>([&](auto Lc) { constexpr int l = Lc; acc = fma(-readlane_d(a[l], i), x[l], acc); });
+        x[i] = acc * readlane_d(dinv, i);
       }
     });
     for (int idx = lane; idx < 32 * PL; idx += 64) Li[idx] = 0.0;
-    wsync();
+    wave_sync();
     if (lane < n) static_for<0, 32>([&](auto Ic) { constexpr int i = Ic; if (i < n) Li[i * PL + lane] = x[i]; });
-    wsync();
+    wave_sync();
     // A^-1 = X^T X : up to 2 x 2 tiles, all on this wave
     const int nt = (n + 15) / 16, kb = (n + 3) / 4, g = lane >> 4, c = lane & 15;
     for (int tile = 0; tile < nt * nt; ++tile) {
@@ -551,7 +526,7 @@ __device__ __forceinline__ bool spd_inverse_warm(int tid, int n, const double* Q
 }
 
 #ifdef DLM_STAMP
-#define TSTAMP(k) { unsigned long long _t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t)::"memory"); seg[k] += _t - tlast; tlast = _t; }
+#define TSTAMP(k) { const unsigned long long _t = stamp_loose(); seg[k] += _t - tlast; tlast = _t; }
 #else
 #define TSTAMP(k)
 #endif
@@ -692,7 +667,7 @@ __global__ __launch_bounds__(NT) void k_filter_tiled(KArgs a, double* __restrict
 #ifdef DLM_STAMP
   int dbgc[3] = {0, 0, 0};
   unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tlast)::"memory");
+  tlast = stamp_loose();
 #endif
   for (int t = 0; t < T; ++t) {
     TSTAMP(7)
@@ -885,7 +860,7 @@ __global__ __launch_bounds__(NT) void k_smoother_tiled(KArgs a, const double* __
   ecur = bld(rinn, T > 0 ? eoff : OOB, (T > 0 ? T - 1 : 0) * p * 8);
 #ifdef DLM_STAMP
   unsigned long long seg[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tlast)::"memory");
+  tlast = stamp_loose();
 #endif
   for (int t = T; t >= 0; --t) {
     lds_barrier();

@@ -25,6 +25,7 @@
 //   K^T = Qi S^T,  m' = a + K e,  C' = R - K S^T   (upper tiles, mirrored: exactly symmetric)
 #include <cstdlib>
 #include "dlm_internal.h"
+#include "dlm_wave.h"
 #include "../../include/dlm_engine.h"
 
 namespace dlm {
@@ -38,11 +39,6 @@ __device__ __attribute__((noinline)) bool settle_eval(float* st, double dmax, do
   return settle_test(st, (float)(dmax * sc), (float)(smax * sc), 4);
 }
 
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-typedef unsigned u2 __attribute__((ext_vector_type(2)));
-
-constexpr int OOB = 0x7ffffff0;
 // LDS of one wave, sized by the tile counts of the instantiation (DT tiles for d, PT for p, MX the larger): the image
 // (16 MX rows, odd leading dimension: row-wise and transposed reads both spread over the banks), the copy of F or the
 // tables of a structured F, the scratch of the direct inverse, ten vectors.  8 KB at one tile per dimension, 35 KB at
@@ -61,48 +57,10 @@ constexpr int lds_doubles(int DT, int PT) { return img_of(DT, PT) + fimg_of(DT, 
 constexpr int FIMG = 48 * 33;   // (the prologue kernel's own fixed layout)
 constexpr int FLD = 33;
 
-__device__ __forceinline__ void wave_sync() {   // LDS hand-off between lanes of one wave (in-order LDS queue)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ double sum_g(double v) {   // sum over lanes c, c+16, c+32, c+48; all get it
-  unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
-  u2 l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-  u2 h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-  v = __hiloint2double((int)h[0], (int)l[0]) + __hiloint2double((int)h[1], (int)l[1]);
-  lo = (unsigned)__double2loint(v); hi = (unsigned)__double2hiint(v);
-  l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-  h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-  return __hiloint2double((int)h[0], (int)l[0]) + __hiloint2double((int)h[1], (int)l[1]);
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mk_rsrc(const void* p, size_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ double bld(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-  const u2 v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
-  return __hiloint2double((int)v[1], (int)v[0]);
-}
-__device__ __forceinline__ void bst(__amdgpu_buffer_rsrc_t r, int voff, int soff, double x) {
-  const u2 v = {(unsigned)__double2loint(x), (unsigned)__double2hiint(x)};
-  __builtin_amdgcn_raw_buffer_store_b64(v, r, voff, soff, 0);
-}
-
-// 16-byte stores.  One wave per SIMD can keep at most 63 vector-memory operations in flight: with 8 bytes per lane a step's 39
-// record stores are all the bandwidth a wave can ask for.  A lane of the tile layout holds rows 4 r + g of its column;
-// v_permlane16_swap of registers r and r + 1 leaves it with two ADJACENT rows of one of them (even d: 16 contiguous bytes).
-typedef unsigned u4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void bst4(__amdgpu_buffer_rsrc_t r, int voff, int soff, double x, double y) {
-  const u4 v = {(unsigned)__double2loint(x), (unsigned)__double2hiint(x), (unsigned)__double2loint(y), (unsigned)__double2hiint(y)};
-  __builtin_amdgcn_raw_buffer_store_b128(v, r, voff, soff, 0);   // (nontemporal stores measured slower: 22.1 against 18.7 ms at C4)
-}
-// registers (x: rows 4 r + g, y: rows 4 (r + 1) + g)  ->  (lo, hi) = rows (base, base + 1), base = 4 (r + (g & 1)) + (g & 2)
-__device__ __forceinline__ void pair_rows(double x, double y, double& lo, double& hi) {
-  const u2 l = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(x), (unsigned)__double2loint(y), false, false);
-  const u2 h = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(y), false, false);
-  lo = __hiloint2double((int)h[0], (int)l[0]);
-  hi = __hiloint2double((int)h[1], (int)l[1]);
-}
+// The wave hand-off, sum_g and the raw buffer loads / stores: dlm_wave.h.  Records leave by 16-byte stores (bst128): with 8 bytes
+// per lane a step's 39 record stores are all the bandwidth a wave can ask for (at most 63 vector-memory operations in flight).  A
+// lane of the tile layout holds rows 4 r + g of its column; pair_rows on registers r and r + 1 leaves it with two ADJACENT rows of
+// one of them (even d: 16 contiguous bytes).  (Nontemporal stores measured slower: 22.1 against 18.7 ms at C4.)
 
 // Z[a][b] = sum_k X[k][a]^T Y[k][b] over the first `rows` rows of the operands (MFMAs of all-padding k-blocks are
 // skipped).  UP: only the tiles a <= b.  Consecutive MFMAs go to different accumulators.
@@ -606,7 +564,7 @@ __global__ __launch_bounds__(64, (DT <= 2 && PT == 1 && KF <= 1) ? 2 : 1) void k
             double lo, hi;
             pair_rows(C[aa][b][r], C[aa][b][r + 1], lo, hi);
             const int i = 16 * aa + 4 * (r + (g & 1)) + (g & 2);
-            bst4(rfo, (i < d && jd[b]) ? cpart[b] + i * 8 : OOB, so, lo, hi);
+            bst128(rfo, (i < d && jd[b]) ? cpart[b] + i * 8 : OOB, so, lo, hi);
           }
     } else {
 #pragma unroll
@@ -1127,7 +1085,7 @@ __global__ __launch_bounds__(64, (DT <= 2 && PT == 1 && KF <= 1) ? 2 : 1) void k
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
               const int i = 16 * aa + 8 * h + 2 * g;
-              bst4(rout, (i < d && jd[b]) ? cpart[b] + i * 8 : OOB, so, img[i * IL + 16 * b + c], img[(i + 1) * IL + 16 * b + c]);
+              bst128(rout, (i < d && jd[b]) ? cpart[b] + i * 8 : OOB, so, img[i * IL + 16 * b + c], img[(i + 1) * IL + 16 * b + c]);
             }
       } else {
 #pragma unroll
@@ -1433,8 +1391,7 @@ __global__ __launch_bounds__(64, (DT <= 2 && PT == 1 && KF <= 1) ? 2 : 1) void k
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int i = 16 * aa + 4 * r + g;
-            const u2 v = __builtin_amdgcn_raw_buffer_load_b64(rout, (i < d && jd[b]) ? cpart[b] + i * 8 : OOB, so, 1);   // glc
-            const double old = __hiloint2double((int)v[1], (int)v[0]);
+            const double old = bld_glc(rout, (i < d && jd[b]) ? cpart[b] + i * 8 : OOB, so);
             dmax = fmax(dmax, settle_absdiff(P[aa][b][r], old)); pmax = fmax(pmax, fabs(P[aa][b][r]));
           }
       for (int o_ = 32; o_ > 0; o_ >>= 1) { dmax = fmax(dmax, __shfl_xor(dmax, o_)); pmax = fmax(pmax, __shfl_xor(pmax, o_)); }
@@ -1452,8 +1409,7 @@ __global__ __launch_bounds__(64, (DT <= 2 && PT == 1 && KF <= 1) ? 2 : 1) void k
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int i = 16 * aa + 4 * r + g;
-            const u2 v = __builtin_amdgcn_raw_buffer_load_b64(rout, (i < d && jd[b]) ? cpart[b] + i * 8 : OOB, so, 1);
-            img[i * IL + 16 * b + c] = __hiloint2double((int)v[1], (int)v[0]);
+            img[i * IL + 16 * b + c] = bld_glc(rout, (i < d && jd[b]) ? cpart[b] + i * 8 : OOB, so);
           }
       wave_sync();
       smode = true;
@@ -2008,11 +1964,6 @@ __global__ __launch_bounds__(64, 4) void k_steady_filter_w48(KArgs a, const doub
 // LDS per wave: two images (scratch; the second also keeps the factor L in its lower triangle and the comparison copy of
 // C in its strict upper triangle) and six vectors -- 39 KB at DT = 3: four series per CU.
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ double readlane_d(double v, int src) {
-  const int lo = __builtin_amdgcn_readlane((int)__double2loint(v), src);
-  const int hi = __builtin_amdgcn_readlane((int)__double2hiint(v), src);
-  return __hiloint2double(hi, lo);
-}
 
 // Shared factors (dlm_sampler16.hip has the d <= 15 form).  EXP: the series is the one series of zeros, workgroup b
 // makes the table rows of stretch b -- per step computed in full, per lane [ J^T tiles (4 DT^2) | row `lane` of L (16 DT, zero
