@@ -8,11 +8,72 @@
 
 #include <cstdio>
 #include <cstring>
+#include <map>
+#include <mutex>
 #include <set>
 #include <string>
 #include <vector>
 
 using dlm::KArgs;
+
+// ---- who asks for LDS (dlm_internal.h: launch).  One book for the process, guarded: an engine is single-threaded, a process may hold several.
+namespace dlm {
+namespace {
+struct LdsEntry {
+  size_t granted = 0;     // hipFuncAttributeMaxDynamicSharedMemorySize of this (function, device) so far
+  long long whole = -1;   // whole_cu_lds of it (-1: not asked yet)
+};
+std::mutex lds_mutex;
+std::map<std::pair<const void*, int>, LdsEntry> lds_book;   // (kernel, device); (nullptr, device): `granted` holds the device's limit
+size_t limit_locked(int dev) {
+  LdsEntry& lim = lds_book[{nullptr, dev}];
+  if (!lim.granted) {
+    int v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) { (void)hipGetLastError(); v = 0; }
+    lim.granted = v > 0 ? (size_t)v : 0;
+  }
+  return lim.granted;
+}
+hipError_t opt_in_locked(const void* fn, int dev, size_t bytes) {
+  if (bytes > limit_locked(dev)) return hipErrorInvalidValue;
+  LdsEntry& en = lds_book[{fn, dev}];
+  if (bytes <= en.granted) return hipSuccess;
+  const hipError_t err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (err == hipSuccess) en.granted = bytes;
+  return err;
+}
+}  // namespace
+size_t lds_limit() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
+  std::lock_guard<std::mutex> lock(lds_mutex);
+  return limit_locked(dev);
+}
+hipError_t lds_opt_in(const void* fn, size_t bytes) {
+  int dev = 0;
+  const hipError_t err = hipGetDevice(&dev);
+  if (err != hipSuccess) return err;
+  std::lock_guard<std::mutex> lock(lds_mutex);
+  return opt_in_locked(fn, dev, bytes);
+}
+size_t whole_cu_lds(const void* fn) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
+  std::lock_guard<std::mutex> lock(lds_mutex);
+  LdsEntry& en = lds_book[{fn, dev}];
+  if (en.whole < 0) {
+    en.whole = 0;
+    hipFuncAttributes at;
+    const size_t whole = limit_locked(dev);
+    if (hipFuncGetAttributes(&at, fn) != hipSuccess) (void)hipGetLastError();
+    else if (at.sharedSizeBytes < whole) {
+      if (opt_in_locked(fn, dev, whole - at.sharedSizeBytes) == hipSuccess) en.whole = (long long)(whole - at.sharedSizeBytes);
+      else (void)hipGetLastError();
+    }
+  }
+  return (size_t)en.whole;
+}
+}  // namespace dlm
 
 // A grow-only piece of device memory of the engine.  ensure() (below) is the one place that re-sizes one, dlm_engine_destroy the one
 // that frees them: every Ws member joins the engine's list when it is constructed.
@@ -374,9 +435,8 @@ int model_checksum(dlm_engine* e, const KArgs& k, bool store) {
     HIP_TRY(e, hipHostGetDevicePointer((void**)&e->model_bad_dev, e->model_bad, 0));
   }
   const long long nF = (long long)(k.f_stride ? k.T : 1) * k.d * k.p, nG = (long long)k.n_g * k.d * k.d;
-  hipLaunchKernelGGL(k_model_checksum, dim3(1), dim3(256), 0, e->stream, k.F, nF, k.G, nG, k.g_index, k.dt, (long long)k.T,
-                     e->model_sum, store ? 1 : 0, e->model_bad_dev);
-  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, dlm::launch(k_model_checksum, dim3(1), dim3(256), 0, e->stream, k.F, nF, k.G, nG, k.g_index, k.dt, (long long)k.T,
+                         e->model_sum, store ? 1 : 0, e->model_bad_dev));
   return DLM_OK;
 }
 
@@ -629,7 +689,7 @@ int run_filter(dlm_engine* e, const KArgs& k, bool want_side) {
     HIP_TRY(e, dlm::launch_tiled_filter(k, want_side ? e->ystar : nullptr, e->stream));
   } else {
     e->variant = "generic";
-    if (dlm::generic_filter_lds_bytes(k.d, k.p) > 160 * 1024)   // 3 d + 4 d^2 + 2 d p + 2 p^2 + 3 p doubles of one CU's 160 KB of LDS
+    if (dlm::generic_filter_lds_bytes(k.d, k.p) > dlm::lds_limit())   // 3 d + 4 d^2 + 2 d p + 2 p^2 + 3 p doubles of one CU's 160 KB of LDS
       return fail(e, DLM_ERR_UNSUPPORTED, "the general filter kernel keeps a series' matrices in the LDS of one CU: this d, p needs more than its 160 KB (d = 64 fits with p <= 12, p = 64 with d <= 26)");
     HIP_TRY(e, dlm::launch_generic_filter(k, e->stream));
   }
@@ -663,7 +723,7 @@ int run_smoother(dlm_engine* e, const KArgs& k, bool have_side) {
     HIP_TRY(e, dlm::launch_small_mv_rts(k, e->stream));
   } else {
     e->variant = "generic";
-    if (dlm::generic_smoother_lds_bytes(k.d, k.p) > 160 * 1024)
+    if (dlm::generic_smoother_lds_bytes(k.d, k.p) > dlm::lds_limit())
       return fail(e, DLM_ERR_UNSUPPORTED, "the general RTS smoother kernel keeps six d x d matrices in the LDS of one CU: d <= 58 (structured models with d <= 48 take the per-wave kernels)");
     HIP_TRY(e, dlm::launch_generic_smoother(k, e->stream));
   }
@@ -888,8 +948,7 @@ int dlm_unpack_records(dlm_engine* e, int32_t d, int64_t count, const double* pa
   int rc = st.commit();
   if (rc) return rc;
   const long long total = (long long)count * (long long)rec;
-  hipLaunchKernelGGL(k_unpack_records, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, e->stream, (int)d, (long long)count, (int)prec, src, dst);
-  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, dlm::launch(k_unpack_records, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, e->stream, (int)d, (long long)count, (int)prec, src, dst));
   return st.finish(opts->flags & DLM_OPT_ASYNC);
 }
 
@@ -1336,7 +1395,7 @@ static int sampler_common(dlm_engine* e, const dlm_model_desc* model, const dlm_
   if ((rc = mark(e, 1))) return rc;
   auto done = [&]() { const int r = mark(e, 2); return r ? r : st.finish(opts->flags & DLM_OPT_ASYNC); };
   if (eig) {
-    if (dlm::generic_sampler_lds_bytes(k.d, k.p) > 160 * 1024)
+    if (dlm::generic_sampler_lds_bytes(k.d, k.p) > dlm::lds_limit())
       return fail(e, DLM_ERR_UNSUPPORTED, "DLM_OPT_DRAW_EIG runs on the general backward sampler kernel: d <= 53");
     e->variant = "generic-eig";
     HIP_TRY(e, dlm::launch_generic_sampler(k, e->stream));
@@ -1379,7 +1438,7 @@ static int sampler_common(dlm_engine* e, const dlm_model_desc* model, const dlm_
     return done();
   }
   e->variant = "generic";
-  if (dlm::generic_sampler_lds_bytes(k.d, k.p) > 160 * 1024)
+  if (dlm::generic_sampler_lds_bytes(k.d, k.p) > dlm::lds_limit())
     return fail(e, DLM_ERR_UNSUPPORTED, "the general backward sampler kernel keeps seven d x d matrices in the LDS of one CU: d <= 53 (structured models with d <= 48 take the per-wave kernels)");
   HIP_TRY(e, dlm::launch_generic_sampler(k, e->stream));
   return done();

@@ -645,47 +645,25 @@ __global__ __launch_bounds__(64) void k_simulate_generic(KArgs a) {
 // ---------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------
-static hipError_t check_lds(const void* fn, size_t bytes) {
-  if (bytes > 160 * 1024) return hipErrorInvalidValue;
-  if (bytes > 64 * 1024) return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  return hipSuccess;
-}
-
+// (a d, p whose matrices do not fit a CU's LDS: hipErrorInvalidValue from launch)
 hipError_t launch_generic_filter(const KArgs& a, hipStream_t s) {
-  const size_t lds = generic_filter_lds_bytes(a.d, a.p);
-  hipError_t e = check_lds((const void*)k_filter_generic, lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_filter_generic, dim3(a.N), dim3(64), lds, s, a);
-  return hipGetLastError();
+  return launch(k_filter_generic, dim3(a.N), dim3(64), generic_filter_lds_bytes(a.d, a.p), s, a);
 }
 
 hipError_t launch_generic_smoother(const KArgs& a, hipStream_t s) {
-  const size_t lds = generic_smoother_lds_bytes(a.d, a.p);
-  hipError_t e = check_lds((const void*)k_smoother_generic, lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_smoother_generic, dim3(a.N), dim3(64), lds, s, a);
-  return hipGetLastError();
+  return launch(k_smoother_generic, dim3(a.N), dim3(64), generic_smoother_lds_bytes(a.d, a.p), s, a);
 }
 
 hipError_t launch_generic_sampler(const KArgs& a, hipStream_t s) {
-  const size_t lds = generic_sampler_lds_bytes(a.d, a.p);
-  hipError_t e = check_lds((const void*)k_sampler_generic, lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_sampler_generic, dim3(a.N), dim3(64), lds, s, a);
-  return hipGetLastError();
+  return launch(k_sampler_generic, dim3(a.N), dim3(64), generic_sampler_lds_bytes(a.d, a.p), s, a);
 }
 
 hipError_t launch_generic_simulate(const KArgs& a, hipStream_t s) {
-  const size_t lds = generic_simulate_lds_bytes(a.d, a.p);
-  hipError_t e = check_lds((const void*)k_simulate_generic, lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_simulate_generic, dim3(a.N), dim3(64), lds, s, a);
-  return hipGetLastError();
+  return launch(k_simulate_generic, dim3(a.N), dim3(64), generic_simulate_lds_bytes(a.d, a.p), s, a);
 }
 
 hipError_t launch_stats_pool(const double* stats, int N, int L, double* pooled, hipStream_t s) {
-  hipLaunchKernelGGL(k_stats_pool, dim3(L), dim3(256), 0, s, stats, N, L, pooled);
-  return hipGetLastError();
+  return launch(k_stats_pool, dim3(L), dim3(256), 0, s, stats, N, L, pooled);
 }
 
 }  // namespace dlm

@@ -45,9 +45,8 @@ hipError_t launch_dinvgamma_step(int d, int p, int N, const double* stats, doubl
                                  unsigned long long seed, unsigned long long series_offset, unsigned long long iteration,
                                  double* Vout, double* Wout, hipStream_t s) {
   const long long total = (long long)N * (p + d);
-  hipLaunchKernelGGL(k_dinvgamma_step, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d, p, N, stats, av, bv, aw, bw,
-                     seed, series_offset, iteration, Vout, Wout);
-  return hipGetLastError();
+  return launch(k_dinvgamma_step, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d, p, N, stats, av, bv, aw, bw,
+                seed, series_offset, iteration, Vout, Wout);
 }
 
 }  // namespace dlm

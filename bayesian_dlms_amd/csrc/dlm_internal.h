@@ -62,6 +62,26 @@ struct KArgs {
                                   // recursion has settled and leaves here the last record it wrote -- every later record would repeat that covariance
 };
 
+// The arguments of a TABLE RUN: one wave that runs a per-series kernel on a series of zeros (the shared-covariance, shared-factor and
+// shared RTS routes, the SVD filter's shared factors).  table_run_args is where every one of them starts: N = 1, what describes the model
+// and the parameters the batch shares, and NOTHING that belongs to the call's own series -- every pointer null, every count 0.  The site
+// then assigns what its run reads or writes (its zeros, its record buffers, status, ...).  Every field of KArgs stands in one of the two
+// lists, so that a new field cannot be added without deciding which it is (tests/test_launch_layer_host.py holds the lists against the
+// struct and against the function; site by field: profiles/r09_notes.md):
+//   TABLE-RUN carried:  d p T F f_stride G n_g g_index dt V v_stride W w_stride v_tstride w_tstride C0 c0_stride spb spb_k spf spf_k flags stretches
+//   TABLE-RUN per call: N m0 m0_stride y z filt_in filt prior fq smooth theta cond stats loglik status packed seed series_offset route route_take counters plain keep_cov ktab leave_step settle_step
+inline KArgs table_run_args(const KArgs& a) {
+  KArgs k{};
+  k.N = 1;
+  k.d = a.d; k.p = a.p; k.T = a.T;
+  k.F = a.F; k.f_stride = a.f_stride; k.G = a.G; k.n_g = a.n_g; k.g_index = a.g_index; k.dt = a.dt;
+  k.V = a.V; k.v_stride = a.v_stride; k.W = a.W; k.w_stride = a.w_stride; k.v_tstride = a.v_tstride; k.w_tstride = a.w_tstride;
+  k.C0 = a.C0; k.c0_stride = a.c0_stride;
+  k.spb = a.spb; k.spb_k = a.spb_k; k.spf = a.spf; k.spf_k = a.spf_k;
+  k.flags = a.flags; k.stretches = a.stretches;
+  return k;
+}
+
 // Packed record of the structured fast path's internal workspaces: [m (d) | lower triangle of C by rows], padded to a
 // multiple of 16 B (the backward pass fetches records by 16-byte LDS-DMA pieces).
 __host__ __device__ inline int packed_rec_bytes(int d) { return ((d + d * (d + 1) / 2) * 8 + 15) & ~15; }
@@ -98,8 +118,23 @@ inline hipError_t pick(int v, F&& f) {   // f(integral_constant<int, V>) for the
 }
 template <class F>
 inline hipError_t pick_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+// Dynamic LDS above the 64 KB a kernel gets without asking is asked for in ONE place (dlm_engine.hip; DESIGN.md 4, below the table of
+// variants): lds_opt_in grants `bytes` to `fn` on the CURRENT device -- HIP keeps the attribute per device, and a process may hold engines
+// on several -- once per (function, device) and amount; more than the device has: hipErrorInvalidValue.  launch calls it, nobody else.
+hipError_t lds_opt_in(const void* fn, size_t bytes);
+size_t lds_limit();   // LDS of one workgroup on the current device (hipDeviceAttributeMaxSharedMemoryPerBlock); 0: the runtime does not say
+// Dynamic LDS that, with the kernel's static LDS, fills a CU: no other workgroup that uses LDS -- every batch kernel of this library --
+// becomes resident beside it.  A table run is ONE wave whose dependent chain is what the call waits for; on a CU it shares with eight waves
+// per SIMD of the batch's forward pass it queues behind their MFMAs (64 cycles of the pipe each) and LDS traffic at every link of the chain
+// (measured: 1.8 ms alone, 4.5 ms beside k_filter_sp16).  One CU of 256 is what the isolation costs the batch.  0: the runtime refused
+// (the run then shares its CU; nothing records that).
+size_t whole_cu_lds(const void* fn);
 template <class Kernel, class... Args>
 inline hipError_t launch(Kernel kernel, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, const Args&... args) {
+  if (lds_bytes > 64 * 1024) {
+    const hipError_t err = lds_opt_in((const void*)kernel, lds_bytes);
+    if (err != hipSuccess) return err;
+  }
   hipLaunchKernelGGL(kernel, grid, block, lds_bytes, s, args...);
   return hipGetLastError();
 }
@@ -219,7 +254,8 @@ struct RtsTabs {
 //   RTS-KEY fixed:    p g_index dt f_stride v_stride w_stride v_tstride w_tstride c0_stride packed
 //                     (one value only: sampler_shared_model_ok refuses the call otherwise)
 //   RTS-KEY replaced: N y m0_stride filt_in filt smooth status stats loglik prior fq route counters theta z series_offset plain settle_step
-//                     (set by launch_rts_shared_cov / cov_args / launch_cf / launch_rts_shared_tables to the table run's own)
+//                     (per call: table_run_args carries none of them; launch_rts_shared_tables / cov_args / launch_cf set the table run's own
+//                      where it has one)
 //   RTS-KEY unread:   n_g m0 cond spb spb_k spf spf_k seed route_take keep_cov ktab leave_step stretches
 //                     (n_g: without g_index only G_0 is used; m0: the covariance-only run starts from a mean of zeros; seed: simulation smoother
 //                      only; route_take: behind route; the others belong to other kernels)

@@ -298,13 +298,11 @@ __global__ __launch_bounds__(256) void k_smoother_mfma16(KArgs a, const double* 
 }
 
 hipError_t launch_mfma16_filter(const KArgs& a, double* side, hipStream_t s) {
-  hipLaunchKernelGGL(k_filter_mfma16, dim3((a.N + 3) / 4), dim3(256), 0, s, a, side);
-  return hipGetLastError();
+  return launch(k_filter_mfma16, dim3((a.N + 3) / 4), dim3(256), 0, s, a, side);
 }
 
 hipError_t launch_mfma16_smoother(const KArgs& a, const double* side, hipStream_t s) {
-  hipLaunchKernelGGL(k_smoother_mfma16, dim3((a.N + 3) / 4), dim3(256), 0, s, a, side);
-  return hipGetLastError();
+  return launch(k_smoother_mfma16, dim3((a.N + 3) / 4), dim3(256), 0, s, a, side);
 }
 
 }  // namespace dlm

@@ -1222,9 +1222,8 @@ hipError_t launch_sampler_shared_tables(const KArgs& a, int K, const SparseT* ta
   hipError_t err = hipMemsetAsync(tb.zeros, 0, (size_t)(a.T > 16 ? a.T : 16) * 8, s);
   if (err != hipSuccess) return err;
   if ((err = hipMemsetAsync(tb.status, 0, sizeof(int), s)) != hipSuccess) return err;
-  KArgs kf = a;   // the filter on a series of zeros: the covariances of every series without a missing observation, bit for bit
-  kf.N = 1; kf.y = tb.zeros; kf.m0 = tb.zeros; kf.m0_stride = 0; kf.filt = tb.zrec; kf.status = tb.status; kf.stats = nullptr; kf.loglik = nullptr;
-  kf.prior = nullptr; kf.fq = nullptr; kf.route = nullptr; kf.counters = nullptr; kf.theta = nullptr; kf.z = nullptr; kf.series_offset = 0;
+  KArgs kf = table_run_args(a);   // the filter on a series of zeros: the covariances of every series without a missing observation, bit for bit
+  kf.y = tb.zeros; kf.m0 = tb.zeros; kf.filt = tb.zrec; kf.status = tb.status;
   if ((err = launch_sparse16_filter(kf, K, tabs_dev, nullptr, nullptr, s)) != hipSuccess) return err;
   KArgs kp = kf;
   kp.y = nullptr; kp.filt_in = tb.zrec;
@@ -1271,9 +1270,8 @@ hipError_t launch_sampler_shared_normals(const KArgs& a, double* z4, hipStream_t
 hipError_t launch_sampler_shared_tables_from(const KArgs& a, int K, const SparseT* tabs_dev, SampTabs tb, const double* crec, int stride, hipStream_t s) {
   hipError_t err = hipMemsetAsync(tb.status, 0, sizeof(int), s);
   if (err != hipSuccess) return err;
-  KArgs kp = a;
-  kp.N = 1; kp.y = nullptr; kp.filt_in = crec; kp.filt = nullptr; kp.status = tb.status; kp.stats = nullptr; kp.loglik = nullptr; kp.prior = nullptr; kp.fq = nullptr;
-  kp.route = nullptr; kp.counters = nullptr; kp.theta = nullptr; kp.z = nullptr; kp.series_offset = 0; kp.m0_stride = 0;
+  KArgs kp = table_run_args(a);
+  kp.filt_in = crec; kp.status = tb.status;
   tb.zstride = stride;
   return launch_sampler_table_run(kp, K, tabs_dev, tb, s);
 }
@@ -1345,40 +1343,19 @@ hipError_t launch_rts_key_commit(const KArgs& a, int K, const SparseT* tabs_dev,
 // take ten times as long (0.22 -> 2.3 ms measured) -- then, beside the forward pass, the smoother with its export on, reading that table's rows
 // as its filter records
 hipError_t launch_rts_shared_cov(const KArgs& a, int K, const SparseT* tabs_dev, RtsTabs& tb, const CovTabs& ctb, const int* gate, hipStream_t s) {
-  KArgs kc = a;
-  kc.smooth = nullptr; kc.filt = nullptr; kc.stats = nullptr; kc.theta = nullptr; kc.z = nullptr;
   tb.crec = ctb.ftab; tb.crec_stride = ctb.frow;
   CovTabs cs = ctb;
   cs.skip = gate;
-  return launch_sparse16_cov_filter(kc, K, tabs_dev, cs, s);
-}
-// Dynamic LDS that, with the kernel's static LDS, fills a CU's 160 KB: no other workgroup that uses LDS -- every batch kernel of this library --
-// becomes resident beside it.  A table run is ONE wave whose dependent chain is what the call waits for; on a CU it shares with eight waves
-// per SIMD of the batch's forward pass it queues behind their MFMAs (64 cycles of the pipe each) and LDS traffic at every link of the chain
-// (measured: 1.8 ms alone, 4.5 ms beside k_filter_sp16).  One CU of 256 is what the isolation costs the batch.
-template <int TAG, class F>   // TAG: one static per kernel (instantiations of one template share their function type)
-static size_t whole_cu_lds(F kernel) {
-  auto ask = [&]() -> size_t {
-    hipFuncAttributes at;
-    if (hipFuncGetAttributes(&at, (const void*)kernel) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    const size_t whole = 160 * 1024;
-    if (at.sharedSizeBytes >= whole) return 0;
-    const size_t dyn = whole - at.sharedSizeBytes;
-    if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    return dyn;
-  };
-  static const size_t dyn = ask();
-  return dyn;
+  return launch_sparse16_cov_filter(a, K, tabs_dev, cs, s);   // (cov_args: the covariance-only run takes nothing of the call's own series)
 }
 hipError_t launch_rts_shared_tables(const KArgs& a, int K, const SparseT* tabs_dev, const RtsTabs& tb0, const int* gate, hipStream_t s) {
   RtsTabs tb = tb0;
   tb.skip = const_cast<int*>(gate);   // (the kernel only reads it)
-  KArgs kp = a;   // the covariances of every series without a missing observation, bit for bit
-  kp.N = 1; kp.y = nullptr; kp.m0_stride = 0; kp.filt_in = nullptr; kp.filt = nullptr; kp.smooth = tb.srec; kp.status = tb.status; kp.stats = nullptr; kp.loglik = nullptr;
-  kp.prior = nullptr; kp.fq = nullptr; kp.route = nullptr; kp.counters = nullptr; kp.theta = nullptr; kp.z = nullptr; kp.series_offset = 0; kp.plain = nullptr;
+  KArgs kp = table_run_args(a);   // the covariances of every series without a missing observation, bit for bit (the records: tb.crec)
+  kp.smooth = tb.srec; kp.status = tb.status;
   return pick<1, 2, 3, 4>(K, [&](auto k) {
-    const auto kernel = s16::k_smoother_rts16<k(), SparseT, true>;
-    return launch(kernel, dim3(1), dim3(64), whole_cu_lds<k()>(kernel), s, kp, tabs_dev, tb);
+    const auto kernel = s16::k_smoother_rts16<k(), SparseT, true>;   // (alone on its CU: whole_cu_lds)
+    return launch(kernel, dim3(1), dim3(64), whole_cu_lds((const void*)kernel), s, kp, tabs_dev, tb);
   });
 }
 template <int K>

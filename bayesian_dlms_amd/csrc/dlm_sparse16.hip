@@ -1583,9 +1583,8 @@ hipError_t launch_sparse16_simsmooth(const KArgs& a, int K, const SparseT* tabs_
 
 // ---- shared-covariance launches: the covariance-only runs take `a` with N = 1 and the tables as their record buffers ----------
 static KArgs cov_args(const KArgs& a, const CovTabs& tb) {
-  KArgs k = a;
-  k.N = 1; k.y = nullptr; k.status = nullptr; k.route = nullptr; k.counters = nullptr; k.loglik = nullptr; k.prior = nullptr; k.fq = nullptr;
-  k.filt = tb.ftab; k.filt_in = tb.ftab; k.smooth = tb.btab; k.packed = 0; k.m0_stride = 0; k.plain = nullptr;
+  KArgs k = table_run_args(a);   // (packed = 0: the tables' rows are dense records; no status: what the recursion meets, every series meets)
+  k.filt = tb.ftab; k.filt_in = tb.ftab; k.smooth = tb.btab;
   return k;
 }
 template <int K>

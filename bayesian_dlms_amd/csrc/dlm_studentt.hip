@@ -230,8 +230,7 @@ __global__ __launch_bounds__(256) __attribute__((flatten)) void k_studentt_step(
 }
 
 hipError_t launch_studentt_step(const StudentTArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(k_studentt_step, dim3((unsigned)((a.N + 3) / 4)), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch(k_studentt_step, dim3((unsigned)((a.N + 3) / 4)), dim3(256), 0, s, a);
 }
 
 }  // namespace dlm

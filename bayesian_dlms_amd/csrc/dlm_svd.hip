@@ -945,10 +945,9 @@ hipError_t launch_svd_filter_shared(const KArgs& a, double* svd_rec, double* ws,
   int* cst = (int*)(aux + 8);
   hipError_t err = hipMemsetAsync(zeros, 0, sizeof(double) * ((size_t)a.T + 16), s);
   if (err != hipSuccess) return err;
-  KArgs kc = a;
-  kc.N = 1; kc.y = zeros; kc.m0 = zeros; kc.m0_stride = 0; kc.status = cst; kc.counters = nullptr; kc.route = nullptr;
-  hipLaunchKernelGGL((k_svd_filter<16, true>), dim3(1), dim3(64), svd_filter_lone_lds_bytes(a.d, a.p), s, kc, tab, tstride, aux);
-  if ((err = hipGetLastError()) != hipSuccess) return err;
+  KArgs kc = table_run_args(a);
+  kc.y = zeros; kc.m0 = zeros; kc.status = cst;
+  if ((err = launch(k_svd_filter<16, true>, dim3(1), dim3(64), svd_filter_lone_lds_bytes(a.d, a.p), s, kc, tab, tstride, aux)) != hipSuccess) return err;
   KArgs km = a;
   km.route = route; km.route_take = 0;
 #ifdef DLM_SVD_MEAN_ONE_PER_WAVE
@@ -969,8 +968,7 @@ hipError_t launch_svd_filter_shared(const KArgs& a, double* svd_rec, double* ws,
   if (err != hipSuccess) return err;
   KArgs kg = a;
   kg.route = route; kg.route_take = 1;
-  hipLaunchKernelGGL(k_svd_filter<16>, dim3(a.N), dim3(64), svd_filter_lds_bytes(a.d, a.p), s, kg, svd_rec, 0, (double*)nullptr);
-  return hipGetLastError();
+  return launch(k_svd_filter<16>, dim3(a.N), dim3(64), svd_filter_lds_bytes(a.d, a.p), s, kg, svd_rec, 0, (double*)nullptr);
 }
 
 // canonical factor: columns of U (d x d, LDS ld SL) and entries of s reordered so that the
@@ -1154,22 +1152,11 @@ __global__ __launch_bounds__(64) void k_svd_sampler(KArgs a, const double* __res
 }
 
 bool svd_supported(const KArgs& a) { return a.d >= 1 && a.d <= 48 && a.p >= 1 && a.p <= 32; }
-// the NM = 48 instantiations take up to 151 KB of the CU's 160 KB of LDS: above the 64 KB a kernel gets without asking
-static hipError_t svd_big_lds_once() {
-  static hipError_t done = []() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_svd_filter<48>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_svd_sampler<48>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }();
-  return done;
-}
-// NM = svd_nm(d, p): the 16- or the 48-wide LDS matrices: f(NM)
+// NM = svd_nm(d, p): the 16- or the 48-wide LDS matrices: f(NM)  (the NM = 48 instantiations take up to 151 KB of the CU's 160 KB of LDS)
 template <class F>
 static hipError_t with_svd_nm(const KArgs& a, F f) {
   if (!svd_supported(a)) return hipErrorNotSupported;
-  if (svd_nm(a.d, a.p) == 16) return f(std::integral_constant<int, 16>{});
-  const hipError_t e = svd_big_lds_once();
-  return e != hipSuccess ? e : f(std::integral_constant<int, 48>{});
+  return pick<48, 16>(svd_nm(a.d, a.p), f);   // (48 first: where the wide instantiations have always stood in the code object)
 }
 hipError_t launch_svd_filter(const KArgs& a, double* svd_rec, hipStream_t s) {
   return with_svd_nm(a, [&](auto NM) { return launch(k_svd_filter<NM()>, dim3(a.N), dim3(64), svd_filter_lds_bytes(a.d, a.p), s, a, svd_rec, 0, (double*)nullptr); });

@@ -1156,43 +1156,23 @@ __global__ __launch_bounds__(NT) void k_simsmooth_tiled(KArgs a, const double* _
   if (a.status && tid == 0 && st) atomicOr(&a.status[n], st);
 }
 
-static hipError_t set_lds(const void* fn, size_t bytes) {
-  return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
 hipError_t launch_tiled_filter(const KArgs& a, double* innov, hipStream_t s) {
   if (wave48_filter_supported(a)) return launch_wave48_filter(a, a.spb_k, innov, s);
-  const size_t lds = tiled_filter_lds_bytes();
-  hipError_t e = set_lds((const void*)k_filter_tiled<false>, lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_filter_tiled<false>, dim3(a.N), dim3(NT), lds, s, a, (double*)nullptr, innov);
-  return hipGetLastError();
+  return launch(k_filter_tiled<false>, dim3(a.N), dim3(NT), tiled_filter_lds_bytes(), s, a, (double*)nullptr, innov);
 }
 
 hipError_t launch_tiled_simsmooth(const KArgs& a, double* xplus, double* ystar, hipStream_t s) {
   if (wave48_simsmooth_supported(a)) return launch_wave48_simsmooth(a, a.spb_k, xplus, ystar, s);
-  size_t lds = sizeof(double) * FILT_SIM_DOUBLES + 16;
-  hipError_t e = set_lds((const void*)k_filter_tiled<true>, lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_filter_tiled<true>, dim3(a.N), dim3(NT), lds, s, a, xplus, ystar);
-  e = hipGetLastError();
+  const hipError_t e = launch(k_filter_tiled<true>, dim3(a.N), dim3(NT), sizeof(double) * FILT_SIM_DOUBLES + 16, s, a, xplus, ystar);
   if (e != hipSuccess) return e;
   KArgs b = a;
   b.filt_in = a.filt;
-  lds = sizeof(double) * SIMS_DOUBLES + 16;
-  e = set_lds((const void*)k_simsmooth_tiled, lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_simsmooth_tiled, dim3(a.N), dim3(NT), lds, s, b, (const double*)xplus, (const double*)ystar);
-  return hipGetLastError();
+  return launch(k_simsmooth_tiled, dim3(a.N), dim3(NT), sizeof(double) * SIMS_DOUBLES + 16, s, b, (const double*)xplus, (const double*)ystar);
 }
 
 hipError_t launch_tiled_smoother(const KArgs& a, const double* innov, hipStream_t s) {
   if (wave48_smoother_supported(a)) return launch_wave48_smoother(a, a.spb_k, innov, s);
-  const size_t lds = tiled_smoother_lds_bytes();
-  hipError_t e = set_lds((const void*)k_smoother_tiled, lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_smoother_tiled, dim3(a.N), dim3(NT), lds, s, a, innov);
-  return hipGetLastError();
+  return launch(k_smoother_tiled, dim3(a.N), dim3(NT), tiled_smoother_lds_bytes(), s, a, innov);
 }
 
 }  // namespace dlm

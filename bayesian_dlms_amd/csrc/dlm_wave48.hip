@@ -2815,9 +2815,8 @@ hipError_t launch_wave48_sampler_shared_tables(const KArgs& a, const SampTabs& t
   hipError_t err = hipMemsetAsync(tb.zeros, 0, zn * 8, s);
   if (err != hipSuccess) return err;
   if ((err = hipMemsetAsync(tb.status, 0, sizeof(int), s)) != hipSuccess) return err;
-  KArgs kf = a;   // the filter on a series of zeros: the covariances of every series without a missing observation, bit for bit
-  kf.N = 1; kf.y = tb.zeros; kf.m0 = tb.zeros; kf.m0_stride = 0; kf.filt = tb.zrec; kf.status = tb.status; kf.stats = nullptr; kf.loglik = nullptr;
-  kf.prior = nullptr; kf.fq = nullptr; kf.route = nullptr; kf.counters = nullptr; kf.theta = nullptr; kf.z = nullptr; kf.series_offset = 0; kf.keep_cov = nullptr;
+  KArgs kf = table_run_args(a);   // the filter on a series of zeros: the covariances of every series without a missing observation, bit for bit
+  kf.y = tb.zeros; kf.m0 = tb.zeros; kf.filt = tb.zrec; kf.status = tb.status;
   kf.flags |= DLM_OPT_FORCE_WAVE;   // the kernel family that filters the batch, whatever the batch size
   if ((err = hipMemsetD32Async((hipDeviceptr_t)tb.settle, a.T, 1, s)) != hipSuccess) return err;
   kf.settle_step = tb.settle;       // (stops where its covariance recursion has settled: within 30 steps for the C4 model)

@@ -5,30 +5,10 @@ the launchers, so that a field added to KArgs, or one the launchers start to pas
 import ctypes
 import os
 import re
+import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "bayesian_dlms_amd", "csrc")
-
-
-def _read(*parts):
-    return open(os.path.join(ROOT, *parts)).read()
-
-
-def _strip(src):
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return re.sub(r"//[^\n]*", "", src)
-
-
-def _body(src, head):
-    """The brace-balanced body that follows the first occurrence of `head`."""
-    i = src.index(head)
-    i = src.index("{", i)
-    depth, j = 0, i
-    while True:
-        depth += {"{": 1, "}": -1}.get(src[j], 0)
-        if depth == 0:
-            return src[i:j + 1]
-        j += 1
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from source_lint import body as _body, builder_copies, kargs_fields as _kargs_fields, read as _read, strip as _strip  # noqa: E402
 
 
 def test_flag_and_indicator_agree_between_header_python_jni_and_scala():
@@ -53,21 +33,6 @@ def test_flag_and_indicator_agree_between_header_python_jni_and_scala():
 def test_the_library_exports_the_indicator():
     from bayesian_dlms_amd import _lib
     assert hasattr(_lib.load(), "dlm_last_table_reuse")
-
-
-def _kargs_fields():
-    hdr = _strip(_read("bayesian_dlms_amd", "csrc", "dlm_internal.h"))
-    body = _body(hdr, "struct KArgs")
-    fields = []
-    for decl in body.strip("{}").split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        for part in decl.split(","):
-            name = re.search(r"(\w+)\s*$", part.strip())
-            assert name, decl
-            fields.append(name.group(1))
-    return fields
 
 
 def _key_lists():
@@ -120,11 +85,23 @@ def test_keyed_fields_are_compared_fixed_ones_refused_replaced_ones_set_by_the_l
     for f in lists["fixed"]:
         assert re.search(r"\ba\.%s\b" % f, ok), f
     assert re.search(r"return\s+sampler_shared_model_ok\(a\)\s*&&", _body(s16, "bool rts_shared_eligible"))
-    # replaced: assigned by one of the launchers on the way to the two kernels
+    # the arguments of both table runs start from table_run_args: whatever it carries over from the call is keyed, fixed or unread ...
+    for fn, var in (("hipError_t launch_rts_shared_tables", "kp"), ("static KArgs cov_args", "k")):
+        assert re.search(r"KArgs %s = table_run_args\(a\);" % var, _body(s16 if "rts" in fn else sp16, fn)), fn
+    assert re.search(r"KArgs k = cov_args\(a, tb\);", _body(sp16, "static hipError_t launch_cf"))
+    assert re.search(r"launch\(k_cov_filter_sp16<K>, [^;]*, s, k, sp,", _body(sp16, "static hipError_t launch_cf"))
+    assert re.search(r"launch\(kernel, [^;]*, s, kp, tabs_dev, tb\)", _body(s16, "hipError_t launch_rts_shared_tables"))
+    copies, others = builder_copies()
+    assert others == ["N"] and copies, (copies, others)
+    for f in copies:
+        assert f in lists["keyed"] + lists["fixed"] + lists["unread"], f
+    # ... replaced: not carried over, or assigned by one of the launchers on the way to the two kernels
     launch = (_body(s16, "hipError_t launch_rts_shared_cov") + _body(s16, "hipError_t launch_rts_shared_tables") +
               _body(sp16, "static KArgs cov_args") + _body(sp16, "static hipError_t launch_cf"))
     for f in lists["replaced"]:
-        assert re.search(r"\bk[cp]?\.%s\s*=" % f, launch), f
+        assert f not in copies or re.search(r"\bk[cp]?\.%s\s*=" % f, launch), f
+    # ... and nothing but `a` reaches the covariance-only filter on the RTS route (no copy with fields of its own in between)
+    assert re.search(r"return launch_sparse16_cov_filter\(a, K, tabs_dev, cs, s\);", _body(s16, "hipError_t launch_rts_shared_cov"))
     # ... and the two kernels take the gate for RtsTabs::skip / CovTabs::skip
     assert re.search(r"cs\.skip\s*=\s*gate\s*;", _body(s16, "hipError_t launch_rts_shared_cov"))
     assert re.search(r"tb\.skip\s*=\s*const_cast<int\*>\(gate\)\s*;", _body(s16, "hipError_t launch_rts_shared_tables"))
