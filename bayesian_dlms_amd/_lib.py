@@ -64,6 +64,15 @@ class StudentTPrior(ctypes.Structure):
                 ("prior_w_shape", ctypes.c_double), ("prior_w_scale", ctypes.c_double)]
 
 
+class SvPrior(ctypes.Structure):
+    """dlm_sv_prior: phi_update 0 = Gaussian(phi_a = mean, phi_b = sd) conjugate, 1 = Beta(phi_a, phi_b) prior with the Beta proposal."""
+    _fields_ = [("phi_update", ctypes.c_int32), ("literal", ctypes.c_int32),
+                ("phi_a", ctypes.c_double), ("phi_b", ctypes.c_double),
+                ("mu_mean", ctypes.c_double), ("mu_sd", ctypes.c_double),
+                ("sigma_shape", ctypes.c_double), ("sigma_scale", ctypes.c_double),
+                ("prop_lambda", ctypes.c_double), ("prop_tau", ctypes.c_double)]
+
+
 class Options(ctypes.Structure):
     _fields_ = [("flags", ctypes.c_uint32), ("mem", ctypes.c_int32),
                 ("seed", ctypes.c_uint64), ("series_offset", ctypes.c_uint64)]
@@ -97,6 +106,9 @@ SYMBOLS = [
                                                 ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_uint64, _OP, _V, _V]),
     ("dlm_studentt_step_batch", ctypes.c_int, [_V, _MP, _V, _V, _V, ctypes.POINTER(StudentTPrior), _V, _V, ctypes.c_uint64, _OP,
                                                _V, _V, _V, _V, _V, _V, _V]),
+    ("dlm_sv_mixture_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, ctypes.c_uint64, _OP, _V, _V, _V, _V]),
+    ("dlm_sv_params_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, ctypes.POINTER(SvPrior), ctypes.c_uint64, _OP,
+                                           _V, _V, _V]),
     ("dlm_ou_ffbs_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, ctypes.c_int64, _V, ctypes.c_int64,
                                          _V, _OP, _V, _V, _V]),
     ("dlm_ar1_ffbs_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, ctypes.c_int64, _V, ctypes.c_int64,

@@ -1075,6 +1075,77 @@ int dlm_studentt_step_batch(dlm_engine* e, const dlm_model_desc* model, const do
   return st.finish(opts->flags & DLM_OPT_ASYNC);
 }
 
+int dlm_sv_mixture_batch(dlm_engine* e, int32_t N, int32_t T, const double* y, const double* alpha, uint64_t iteration,
+                         const dlm_options* opts, double* ystar, double* v, int8_t* k, int32_t* status) {
+  if (!e) return DLM_ERR_ARG;
+  if (!opts || (opts->mem != DLM_MEM_DEVICE && opts->mem != DLM_MEM_HOST)) return fail(e, DLM_ERR_ARG, "opts");
+  if (N < 1 || T < 2) return fail(e, DLM_ERR_ARG, "N >= 1 and T >= 2 (the reference's parameter draws throw on a single observation, StochasticVolatility.scala:220-222)");
+  if (T >= 0x1FFFF8) return fail(e, DLM_ERR_ARG, "T must stay below 2^21 - 8 (the Philox counter's slot field)");
+  if ((long long)N * T >= (1ll << 39)) return fail(e, DLM_ERR_ARG, "N T must stay below 2^39 (one thread per element)");
+  if (!y || !ystar || !v) return fail(e, DLM_ERR_ARG, "y, ystar and v are required");
+  HIP_TRY(e, hipSetDevice(e->device));
+  dlm::SvMixArgs a{};
+  const size_t n = N, t = T;
+  Stager st(e, opts->mem == DLM_MEM_HOST);
+  st.in(&a.y, y, n * t);
+  st.in(&a.alpha, alpha, alpha ? n * (t + 1) : 0);
+  st.out(&a.ystar, ystar, n * t);
+  st.out(&a.v, v, n * t);
+  st.out(&a.k, (signed char*)k, k ? n * t : 0);
+  st.zeroed_out(&a.status, (int*)status, status ? n : 0);
+  int rc;
+  if ((rc = st.commit())) return rc;
+  a.N = N; a.T = T;
+  a.seed = opts->seed; a.series_offset = opts->series_offset; a.iteration = iteration;
+  e->variant = "sv-mixture";
+  HIP_TRY(e, dlm::launch_sv_mixture(a, e->stream));
+  return st.finish(opts->flags & DLM_OPT_ASYNC);
+}
+
+int dlm_sv_params_batch(dlm_engine* e, int32_t N, int32_t T, const double* alpha, const double* sv_in, const dlm_sv_prior* prior,
+                        uint64_t iteration, const dlm_options* opts, double* sv_out, int32_t* accepted, int32_t* status) {
+  if (!e) return DLM_ERR_ARG;
+  if (!opts || !prior) return fail(e, DLM_ERR_ARG, "null descriptor");
+  if (opts->mem != DLM_MEM_DEVICE && opts->mem != DLM_MEM_HOST) return fail(e, DLM_ERR_ARG, "opts->mem");
+  if (N < 1 || T < 2) return fail(e, DLM_ERR_ARG, "N >= 1 and T >= 2 (the reference's sums throw on a single observation, StochasticVolatility.scala:220-222)");
+  if (T >= 0x1FFFF8) return fail(e, DLM_ERR_ARG, "T must stay below 2^21 - 8 (the Philox counter's slot field)");
+  if (prior->phi_update != 0 && prior->phi_update != 1) return fail(e, DLM_ERR_ARG, "phi_update: 0 (Gaussian conjugate) or 1 (Beta-proposal Metropolis-Hastings)");
+  if (prior->literal != 0 && prior->literal != 1) return fail(e, DLM_ERR_ARG, "literal: 0 or 1");
+  const bool beta = prior->phi_update == 1;
+  if (!alpha || !sv_in || !sv_out || (beta && !accepted)) return fail(e, DLM_ERR_ARG, "alpha, sv_in and sv_out are required (and accepted with the Beta proposal)");
+  const auto fin = [](double x) { return x - x == 0.0; };
+  if (!(prior->mu_sd > 0.0 && fin(prior->mu_sd) && fin(prior->mu_mean))) return fail(e, DLM_ERR_ARG, "the Gaussian prior of mu needs a finite mean and a positive standard deviation");
+  if (!(prior->sigma_shape > 0.0 && prior->sigma_scale > 0.0 && fin(prior->sigma_shape) && fin(prior->sigma_scale)))
+    return fail(e, DLM_ERR_ARG, "the InverseGamma prior of sigma^2 needs a positive shape and scale");
+  if (beta) {
+    if (!(prior->phi_a > 0.0 && prior->phi_b > 0.0 && fin(prior->phi_a) && fin(prior->phi_b))) return fail(e, DLM_ERR_ARG, "the Beta prior of phi needs positive a and b");
+    if (!(prior->prop_lambda > 0.0 && prior->prop_tau > 0.0 && fin(prior->prop_lambda) && fin(prior->prop_tau)))
+      return fail(e, DLM_ERR_ARG, "the Beta proposal needs positive lambda and tau");
+  } else if (!(prior->phi_b > 0.0 && fin(prior->phi_b) && fin(prior->phi_a))) {
+    return fail(e, DLM_ERR_ARG, "the Gaussian prior of phi needs a finite mean and a positive standard deviation");
+  }
+  HIP_TRY(e, hipSetDevice(e->device));
+  dlm::SvParamsArgs a{};
+  const size_t n = N, t = T;
+  Stager st(e, opts->mem == DLM_MEM_HOST);
+  st.in(&a.alpha, alpha, n * (t + 1));
+  st.in(&a.sv_in, sv_in, n * 3);
+  st.out(&a.sv_out, sv_out, n * 3);
+  st.inout(&a.accepted, (int*)accepted, accepted ? n : 0);
+  st.zeroed_out(&a.status, (int*)status, status ? n : 0);
+  int rc;
+  if ((rc = st.commit())) return rc;
+  a.N = N; a.T = T;
+  a.phi_update = prior->phi_update; a.literal = prior->literal;
+  a.phi_a = prior->phi_a; a.phi_b = prior->phi_b; a.mu_mean = prior->mu_mean; a.mu_sd = prior->mu_sd;
+  a.sigma_shape = prior->sigma_shape; a.sigma_scale = prior->sigma_scale;
+  a.prop_lambda = prior->prop_lambda; a.prop_tau = prior->prop_tau;
+  a.seed = opts->seed; a.series_offset = opts->series_offset; a.iteration = iteration;
+  e->variant = "sv-params";
+  HIP_TRY(e, dlm::launch_sv_params(a, e->stream));
+  return st.finish(opts->flags & DLM_OPT_ASYNC);
+}
+
 static int ar1_common(dlm_engine* e, int32_t N, int32_t T, const double* times, bool ou, const double* y, const double* v,
                       int64_t v_stride, const double* sv, int64_t sv_stride, const double* z, const dlm_options* opts,
                       double* filt, double* theta, int32_t* status);

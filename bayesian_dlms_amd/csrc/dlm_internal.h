@@ -377,6 +377,30 @@ struct StudentTArgs {
 };
 hipError_t launch_studentt_step(const StudentTArgs& a, hipStream_t s);
 
+// ---- AR(1) stochastic volatility: the mixture indicators before the AR(1) FFBS call and the parameter draws after it
+// (StochasticVolatility.scala:112-157, :170-252, StochVolKnots.scala:25-43), dlm_sv.hip -------------
+struct SvMixArgs {
+  int N, T;
+  const double* y;        // [N][T]
+  const double* alpha;    // [N][T+1], or nullptr: the initial transform (no draw)
+  unsigned long long seed, series_offset, iteration;
+  double* ystar; double* v;   // [N][T]
+  signed char* k;         // [N][T], nullable
+  int* status;            // [N], nullable (zeroed by the caller)
+};
+struct SvParamsArgs {
+  int N, T;
+  const double* alpha;    // [N][T+1]
+  const double* sv_in;    // [N][3] = (phi, mu, sigma_eta)
+  int phi_update, literal;
+  double phi_a, phi_b, mu_mean, mu_sd, sigma_shape, sigma_scale, prop_lambda, prop_tau;
+  unsigned long long seed, series_offset, iteration;
+  double* sv_out;         // [N][3], may be sv_in
+  int* accepted; int* status;   // nullable
+};
+hipError_t launch_sv_mixture(const SvMixArgs& a, hipStream_t s);
+hipError_t launch_sv_params(const SvParamsArgs& a, hipStream_t s);
+
 // ---- KalmanFilter.likelihood literally (transition density of the filtered means), dlm_loglik.hip ------
 size_t loglik_q7_ws_bytes(const KArgs& a);
 hipError_t launch_loglik_q7(const KArgs& a, const double* records, void* ws, hipStream_t s);   // a.loglik [N] <- records [N][T+1][d+dd]
@@ -472,8 +496,10 @@ __device__ __forceinline__ void philox_normal2(unsigned long long seed, unsigned
 // key, each disjoint from the FFBS / simulation normals (key (seed lo, seed hi)) and from the others.
 //   DLM_KEY_GIBBS     dlm_dinvgamma_step_batch: comp = component of [V diagonal (p) | W diagonal (d)]; the Student-t step draws W here too
 //   DLM_KEY_STUDENTT  dlm_studentt_step_batch: comp = t for the variance v_t, DLM_ST_SLOT_* for its scalar draws (dlm_studentt.hip)
+//   DLM_KEY_SV        dlm_sv_mixture_batch: comp = t for the mixture indicator k_t; dlm_sv_params_batch: DLM_SV_SLOT_* (dlm_sv.hip)
 constexpr unsigned DLM_KEY_GIBBS = 0x47494242u;      // "GIBB"
 constexpr unsigned DLM_KEY_STUDENTT = 0x53545544u;   // "STUD"
+constexpr unsigned DLM_KEY_SV = 0x5354564Fu;         // "STVO"
 
 __device__ __forceinline__ void gibbs_rand(unsigned long long seed, unsigned long long series, unsigned long long iteration,
                                            unsigned comp, unsigned attempt, unsigned which, double& u1, double& u2,

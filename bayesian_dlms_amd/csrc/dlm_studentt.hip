@@ -25,6 +25,7 @@
 // (series, iteration, slot): slot t for v_t, DLM_ST_SLOT_* for the four scalar draws.  gamma_unit is Marsaglia-Tsang
 // (dlm_internal.h); Poisson is inversion below lambda = 10 and Hormann's PTRS (1993) above.
 #include "dlm_internal.h"
+#include "dlm_wave.h"
 #include "../../include/dlm_engine.h"
 
 namespace dlm {
@@ -76,17 +77,6 @@ __device__ double poisson_draw(double lam, unsigned long long seed, unsigned lon
     if (log(V) + log(invalpha) - log(a / (us * us) + b) <= -lam + k * loglam - ptrs_loggam(k + 1.0)) return k;
   }
   return floor(lam);   // unreachable in practice (acceptance > 85 % per attempt)
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
-  return v;
-}
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
 }
 
 __global__ __launch_bounds__(256) __attribute__((flatten)) void k_studentt_step(StudentTArgs a) {

@@ -62,6 +62,18 @@ __device__ __forceinline__ double wave_max(double v) {
   h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
   return fmax(__hiloint2double((int)h[0], (int)l[0]), __hiloint2double((int)h[1], (int)l[1]));
 }
+// sum over the 64 lanes by the xor butterfly (partner 32, 16, ..., 1): a fixed order, every lane gets the sum.  The reductions of the
+// one-wave-per-series Gibbs steps (dlm_studentt.hip, dlm_sv.hip), whose NumPy restatements follow this order
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
+  return v;
+}
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
 // two float maxima at the price of one 64-bit reduction: a rides in the low, b in the high word through the same shuffles
 __device__ __forceinline__ void wave_max2f(float& a, float& b) {
 #define DLM_MAX2F_ROW(N) { a = fmaxf(a, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a), 0x120 + N, 0xf, 0xf, true))); \

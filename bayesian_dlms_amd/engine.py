@@ -83,7 +83,7 @@ class _Device:
 
     def empty(self, shape, dtype=np.float64):
         t = self.torch
-        return t.empty(shape, dtype=t.float64 if dtype == np.float64 else t.int32, device=self.device)
+        return t.empty(shape, dtype=t.float64 if dtype == np.float64 else t.int8 if dtype == np.int8 else t.int32, device=self.device)
 
     @staticmethod
     def ptr(a):
@@ -342,6 +342,60 @@ class Engine:
                                                      be.ptr(nub), int(iteration), op, be.ptr(v), be.ptr(sc_out), be.ptr(nu_out),
                                                      be.ptr(W), be.ptr(acc), be.ptr(ll), be.ptr(status)))
         return {"v": v, "scale": sc_out, "nu": nu_out, "W": W, "accepted": acc, "loglik": ll, "status": status}
+
+    def sv_mixture(self, y, alpha, *, iteration, seed=0, series_offset=0, want_k=False, flags=0, out=None):
+        """The mixture indicators of the stochastic-volatility sampler (dlm_sv_mixture_batch; StochasticVolatility.sampleKt,
+        StochasticVolatility.scala:112-157) for N chains: y [N][T] (NaN = missing), alpha [N][T+1] as ar1_ffbs writes its theta.
+        Returns {"ystar" [N][T], "v" [N][T], "k" [N][T] int8 or None, "status"}: ystar and v are the next ar1_ffbs call's y and v.
+        alpha=None: the initial transform (ystar = log y^2 + 1.27, v = pi^2 / 2; no draw, no k).
+        out: dict of existing buffers to write into ("ystar", "v", "k")."""
+        be = self._backend(y)
+        N, T = int(y.shape[0]), int(y.shape[1])
+        yb = be.put(y).reshape(N, T)
+        ab = be.put(alpha)
+        if ab is not None and tuple(ab.shape) != (N, T + 1):
+            raise EngineError(f"alpha must be [N][T+1] = {(N, T + 1)}, got {tuple(ab.shape)}")
+        out = out or {}
+        ystar = out["ystar"] if "ystar" in out else be.empty((N, T))
+        v = out["v"] if "v" in out else be.empty((N, T))
+        k = None
+        if want_k and ab is not None:
+            k = out["k"] if "k" in out else be.empty((N, T), np.int8)
+        status = be.empty((N,), np.int32)
+        op = _lib.Options(flags, be.mem, seed, series_offset)
+        self._hold(flags, yb, ab)
+        self._check(self.lib.dlm_sv_mixture_batch(self.h, N, T, be.ptr(yb), be.ptr(ab), int(iteration), op, be.ptr(ystar), be.ptr(v),
+                                                  be.ptr(k), be.ptr(status)))
+        return {"ystar": ystar, "v": v, "k": k, "status": status}
+
+    def sv_params(self, alpha, sv, prior, *, iteration, accepted=None, seed=0, series_offset=0, flags=0, out=None):
+        """phi, mu, sigma of the stochastic-volatility sampler given the state draw (dlm_sv_params_batch; samplePhiConjugate or
+        samplePhi, sampleMu, sampleSigma) for N chains: alpha [N][T+1], sv [N][3] = (phi, mu, sigma).  prior: a _lib.SvPrior, or its ten
+        fields in order (phi_update, literal, phi_a, phi_b, mu_mean, mu_sd, sigma_shape, sigma_scale, prop_lambda, prop_tau).
+        accepted [N] int32 is incremented in place (None: a fresh zero array).  Returns {"sv" [N][3], "accepted", "status"}.
+        out: dict with an existing "sv" buffer to write into (it may be the input)."""
+        be = self._backend(alpha)
+        N, T = int(alpha.shape[0]), int(alpha.shape[1]) - 1
+        ab, sb = be.put(alpha), be.put(sv)
+        if tuple(sb.shape) != (N, 3):
+            raise EngineError(f"sv must be [N][3] = {(N, 3)}, got {tuple(sb.shape)}")
+        if isinstance(prior, _lib.SvPrior):
+            pr = prior
+        else:
+            f = tuple(prior)
+            pr = _lib.SvPrior(int(f[0]), int(f[1]), *(float(x) for x in f[2:]))
+        out = out or {}
+        sv_out = out["sv"] if "sv" in out else be.empty((N, 3))
+        acc = be.put(accepted, np.int32) if accepted is not None else None
+        if acc is None:
+            acc = be.empty((N,), np.int32)
+            acc[...] = 0
+        status = be.empty((N,), np.int32)
+        op = _lib.Options(flags, be.mem, seed, series_offset)
+        self._hold(flags, ab, sb)
+        self._check(self.lib.dlm_sv_params_batch(self.h, N, T, be.ptr(ab), be.ptr(sb), pr, int(iteration), op, be.ptr(sv_out),
+                                                 be.ptr(acc), be.ptr(status)))
+        return {"sv": sv_out, "accepted": acc, "status": status}
 
     def simulate(self, mat, params, N, *, seed=0, series_offset=0, device=False, want_x=True):
         """Dlm.simulateRegular over the model's time grid for N series (dlm_simulate_batch): (x [N][T+1][d], y [N][T][p])."""

@@ -1,0 +1,217 @@
+"""Gibbs sampler of the stochastic-volatility model with AR(1) latent log-volatility on the device
+(StochasticVolatility.sampleUni / sampleBeta, StochasticVolatility.scala:269-341).
+
+  y_t = eps_t exp(alpha_t / 2),   alpha_t = mu + phi (alpha_{t-1} - mu) + eta_t,   eta_t ~ N(0, sigma_eta^2)
+
+log y_t^2 = alpha_t + log eps_t^2 with log eps^2 approximated by the seven-component normal mixture of Kim, Shephard & Chib.  Every
+series runs its own chain -- the reference's semantics for one series, N at once -- and one iteration is three engine calls:
+
+  dlm_sv_mixture_batch  k_t | (y_t, alpha_t);  ystar_t = log y_t^2 - m_{k_t},  v_t = v_{k_t}
+  dlm_ar1_ffbs_batch    alpha | (ystar, v, phi, mu, sigma)
+  dlm_sv_params_batch   phi (Gaussian conjugate, or Beta-proposal Metropolis-Hastings), mu | phi, sigma | (phi, mu)
+
+y, alpha, ystar, v and the parameters stay on the device across iterations whatever the input type; per iteration only the [N][3]
+parameters, `accepted` and `status` cross to the host, plus alpha when asked for.  The chain starts as initialStateAr does
+(StochVolKnots.scala:345-352): ystar = log y^2 + 1.27, v = pi^2 / 2 at every step, one FFBS.
+
+The default is the corrected sampler; literal=True runs the reference's arithmetic (Q16-Q19).  The priors
+are the families the device evaluates: `Gaussian` for mu and for the conjugate phi, `Beta` for the Metropolis-Hastings phi,
+`InverseGamma` for sigma_eta^2; the reference's arbitrary ContinuousDistr of sampleBeta is not offered.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Callable, Iterator, Optional
+
+import numpy as np
+
+from . import _lib
+from .gibbs import InverseGamma
+
+MASK64 = (1 << 64) - 1
+
+
+@dataclass(frozen=True)
+class SvParameters:
+    """SvParameters(phi, mu, sigmaEta) (StochasticVolatility.scala:12-25)."""
+    phi: float
+    mu: float
+    sigma_eta: float
+
+
+@dataclass(frozen=True)
+class Gaussian:
+    """Gaussian(mean, sd) as Breeze takes it: the second argument is the standard deviation."""
+    mean: float
+    sd: float
+
+    def draw(self, rng: np.random.Generator):
+        return self.mean + self.sd * rng.standard_normal()
+
+
+@dataclass(frozen=True)
+class Beta:
+    a: float
+    b: float
+
+    def draw(self, rng: np.random.Generator):
+        return rng.beta(self.a, self.b)
+
+
+def _is_torch(a):
+    return hasattr(a, "data_ptr")
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if _is_torch(a) else np.asarray(a)
+
+
+def initial_parameters(prior_phi, prior_mu: Gaussian, prior_sigma: InverseGamma, n_series: int, *, seed: int = 0,
+                       series_offset: int = 0) -> np.ndarray:
+    """(phi, mu, sigma_eta) [N][3] drawn from the priors on the host (sampleUni / sampleBeta, StochasticVolatility.scala:308-340) by a
+    generator keyed by (seed, global series index) -- a sharded run starts where the single-GPU run does.  phi is redrawn until
+    |phi| < 1 (inside (0, 1) for a Beta prior): the FFBS needs a stationary state."""
+    beta = isinstance(prior_phi, Beta)
+    out = np.empty((n_series, 3))
+    for k in range(n_series):
+        rng = np.random.default_rng([int(seed), int(series_offset) + k, 0x5356])
+        phi = float(prior_phi.draw(rng))
+        while not ((0.0 < phi < 1.0) if beta else (abs(phi) < 1.0)):
+            phi = float(prior_phi.draw(rng))
+        mu = float(prior_mu.draw(rng))
+        out[k] = (phi, mu, np.sqrt(float(prior_sigma.draw(rng))))
+    return out
+
+
+class StochasticVolatility:
+    @dataclass
+    class State:
+        """StochVolState (StochasticVolatility.scala), batched: params [N][3] = (phi, mu, sigma_eta) on the host, alpha [N][T+1] a host
+        copy when asked for (keep_alpha) else None, accepted [N] (the Beta proposal's acceptances so far; zeros for sample_uni),
+        status [N]: the three calls' flags or'ed."""
+        params: np.ndarray
+        alpha: Optional[np.ndarray]
+        accepted: np.ndarray
+        status: np.ndarray
+
+    @staticmethod
+    def simulate(p: SvParameters, T: int, N: int, seed: int = 0):
+        """StochasticVolatility.simulate (:66-72) for N series with NumPy: (y [N][T], alpha [N][T+1]), alpha[:, 0] the stationary
+        initial state.  For tests and benchmarks."""
+        rng = np.random.default_rng(seed)
+        alpha = np.empty((N, T + 1))
+        alpha[:, 0] = p.mu + p.sigma_eta / np.sqrt(1.0 - p.phi * p.phi) * rng.standard_normal(N)
+        eta = rng.standard_normal((N, T)) * p.sigma_eta
+        for t in range(T):
+            alpha[:, t + 1] = p.mu + p.phi * (alpha[:, t] - p.mu) + eta[:, t]
+        y = rng.standard_normal((N, T)) * np.exp(0.5 * alpha[:, 1:])
+        return y, alpha
+
+    @staticmethod
+    def _seed_ffbs(seed, k):
+        # the FFBS normals are keyed by (seed, series, t) alone: a seed per FFBS call, k = 0 the initial state's
+        return (int(seed) * 1000003 + k) & MASK64
+
+    @staticmethod
+    def initial_state_ar(y, sv, engine, *, seed: int = 0, series_offset: int = 0, ffbs: Optional[Callable] = None,
+                         mixture: Optional[Callable] = None, out=None):
+        """initialStateAr (StochVolKnots.scala:345-352): one FFBS on ystar = log y^2 + 1.27 with v = pi^2 / 2 at every step.
+        Returns {"alpha" [N][T+1], "ystar", "v", "status"}."""
+        run_mix = mixture if mixture is not None else engine.sv_mixture
+        run_ffbs = ffbs if ffbs is not None else engine.ar1_ffbs
+        mix = run_mix(y, None, iteration=0, seed=seed, series_offset=series_offset, out=out)
+        f = run_ffbs(mix["ystar"], mix["v"], sv, seed=StochasticVolatility._seed_ffbs(seed, 0), series_offset=series_offset,
+                     want_filt=False, want_theta=True)
+        return {"alpha": f["theta"], "ystar": mix["ystar"], "v": mix["v"], "status": _or_status(mix.get("status"), f.get("status"))}
+
+    @staticmethod
+    def sample_state_ar(y, alpha, sv, engine, *, iteration: int, seed: int = 0, series_offset: int = 0,
+                        ffbs: Optional[Callable] = None, mixture: Optional[Callable] = None, out=None):
+        """sampleStateAr (StochasticVolatility.scala:142-162): the mixture indicators given alpha, then the FFBS draw of alpha.
+        Returns {"alpha" [N][T+1], "ystar", "v", "status"}; out: the "ystar" / "v" buffers to reuse."""
+        run_mix = mixture if mixture is not None else engine.sv_mixture
+        run_ffbs = ffbs if ffbs is not None else engine.ar1_ffbs
+        mix = run_mix(y, alpha, iteration=iteration, seed=seed, series_offset=series_offset, out=out)
+        f = run_ffbs(mix["ystar"], mix["v"], sv, seed=StochasticVolatility._seed_ffbs(seed, iteration + 1), series_offset=series_offset,
+                     want_filt=False, want_theta=True)
+        return {"alpha": f["theta"], "ystar": mix["ystar"], "v": mix["v"], "status": _or_status(mix.get("status"), f.get("status"))}
+
+    @staticmethod
+    def _sample(ys, prior, beta, prior_phi, prior_mu, prior_sigma, engine, *, n_iter, seed, params0, series_offset, keep_alpha,
+                ffbs, mixture, params):
+        N, T = int(ys.shape[0]), int(ys.shape[1])
+        if T < 2:
+            raise ValueError("the stochastic-volatility sampler needs T >= 2 (the reference's sums throw on a single observation)")
+        run_params = params if params is not None else engine.sv_params
+        torch = None
+        dev = None
+        if _is_torch(ys) or engine is not None:
+            import torch
+            dev = ys.device if _is_torch(ys) else torch.device("cuda", engine.device)
+        def put(a, dtype=np.float64):
+            a = np.ascontiguousarray(a, dtype=dtype)
+            return torch.as_tensor(a, device=dev) if torch is not None else a
+        y = ys.reshape(N, T).to(dtype=torch.float64).contiguous() if _is_torch(ys) else put(np.asarray(ys, dtype=np.float64).reshape(N, T))
+        if params0 is None:
+            sv_h = initial_parameters(prior_phi, prior_mu, prior_sigma, N, seed=seed, series_offset=series_offset)
+        else:
+            p0 = (params0.phi, params0.mu, params0.sigma_eta) if isinstance(params0, SvParameters) else params0
+            sv_h = np.broadcast_to(np.asarray(p0, dtype=np.float64), (N, 3)).copy()
+            bad = ~((sv_h[:, 0] > 0.0) & (sv_h[:, 0] < 1.0)) if beta else ~(np.abs(sv_h[:, 0]) < 1.0)
+            if bad.any() or not (sv_h[:, 2] > 0.0).all():
+                raise ValueError("initial parameters need a stationary phi (inside (0, 1) for the Beta proposal) and sigma_eta > 0")
+        sv = put(sv_h)
+        acc = put(np.zeros(N, dtype=np.int32), np.int32)
+        st = StochasticVolatility.initial_state_ar(y, sv, engine, seed=seed, series_offset=series_offset, ffbs=ffbs, mixture=mixture)
+        alpha, bufs, status0 = st["alpha"], {"ystar": st["ystar"], "v": st["v"]}, st["status"]
+        for it in range(n_iter):
+            st = StochasticVolatility.sample_state_ar(y, alpha, sv, engine, iteration=it, seed=seed, series_offset=series_offset,
+                                                      ffbs=ffbs, mixture=mixture, out=bufs)
+            alpha, bufs = st["alpha"], {"ystar": st["ystar"], "v": st["v"]}
+            res = run_params(alpha, sv, prior, iteration=it, accepted=acc, seed=seed, series_offset=series_offset, out={"sv": sv})
+            sv, acc = res["sv"], res["accepted"]
+            status = _or_status(st["status"], res.get("status"))
+            if it == 0:
+                status = _or_status(status, status0)
+            yield StochasticVolatility.State(_host(sv).copy(), _host(alpha).copy() if keep_alpha else None,
+                                             _host(acc).astype(np.int32), status)
+
+    @staticmethod
+    def sample_uni(ys, prior_phi: Gaussian, prior_mu: Gaussian, prior_sigma: InverseGamma, engine, *, n_iter: int, seed: int = 0,
+                   params0=None, literal: bool = False, series_offset: int = 0, keep_alpha: bool = False,
+                   ffbs: Optional[Callable] = None, mixture: Optional[Callable] = None,
+                   params: Optional[Callable] = None) -> Iterator["StochasticVolatility.State"]:
+        """StochasticVolatility.sampleUni (:323-341) for N independent series: ys [N][T] (NaN = missing; numpy or a torch device
+        tensor).  phi is drawn from its Gaussian conjugate conditional, restricted to (-1, 1) unless literal.  Yields one State per
+        iteration.  params0: the initial (phi, mu, sigma_eta) -- an SvParameters, a triple or an [N][3] array; None draws them from
+        the priors (initial_parameters).  ffbs= / mixture= / params= replace engine.ar1_ffbs / sv_mixture / sv_params, for tests."""
+        if not isinstance(prior_phi, Gaussian) or not isinstance(prior_mu, Gaussian) or not isinstance(prior_sigma, InverseGamma):
+            raise TypeError("the device evaluates a Gaussian prior of phi and of mu and an InverseGamma prior of sigma_eta^2 only")
+        prior = _lib.SvPrior(0, 1 if literal else 0, prior_phi.mean, prior_phi.sd, prior_mu.mean, prior_mu.sd, prior_sigma.shape,
+                             prior_sigma.scale, 100.0, 0.05)
+        return StochasticVolatility._sample(ys, prior, False, prior_phi, prior_mu, prior_sigma, engine, n_iter=n_iter, seed=seed,
+                                            params0=params0, series_offset=series_offset, keep_alpha=keep_alpha, ffbs=ffbs,
+                                            mixture=mixture, params=params)
+
+    @staticmethod
+    def sample_beta(ys, prior_phi: Beta, prior_mu: Gaussian, prior_sigma: InverseGamma, engine, *, n_iter: int, seed: int = 0,
+                    params0=None, literal: bool = False, series_offset: int = 0, keep_alpha: bool = False,
+                    prop_lambda: float = 100.0, prop_tau: float = 0.05, ffbs: Optional[Callable] = None,
+                    mixture: Optional[Callable] = None, params: Optional[Callable] = None) -> Iterator["StochasticVolatility.State"]:
+        """StochasticVolatility.sampleBeta (:303-321): as sample_uni with phi in (0, 1) moved by Metropolis-Hastings, proposal
+        Beta(lambda phi + tau, lambda (1 - phi) + tau) (the reference passes 100, 0.05), prior Beta(a, b)."""
+        if not isinstance(prior_phi, Beta) or not isinstance(prior_mu, Gaussian) or not isinstance(prior_sigma, InverseGamma):
+            raise TypeError("the device evaluates a Beta prior of phi, a Gaussian prior of mu and an InverseGamma prior of sigma_eta^2 only")
+        prior = _lib.SvPrior(1, 1 if literal else 0, prior_phi.a, prior_phi.b, prior_mu.mean, prior_mu.sd, prior_sigma.shape,
+                             prior_sigma.scale, float(prop_lambda), float(prop_tau))
+        return StochasticVolatility._sample(ys, prior, True, prior_phi, prior_mu, prior_sigma, engine, n_iter=n_iter, seed=seed,
+                                            params0=params0, series_offset=series_offset, keep_alpha=keep_alpha, ffbs=ffbs,
+                                            mixture=mixture, params=params)
+
+
+def _or_status(a, b):
+    if a is None and b is None:
+        return None
+    a = 0 if a is None else _host(a).astype(np.int32)
+    b = 0 if b is None else _host(b).astype(np.int32)
+    return np.asarray(a | b, dtype=np.int32)

@@ -280,6 +280,63 @@ int dlm_ou_ffbs_batch(dlm_engine* e, int32_t N, int32_t T, const double* times, 
                       int64_t v_stride, const double* sv, int64_t sv_stride, const double* z, const dlm_options* opts,
                       double* filt, double* theta, int32_t* status);
 
+/* Gibbs sampler of the stochastic-volatility model with AR(1) latent log-volatility (StochasticVolatility.sampleUni / sampleBeta,
+ * StochasticVolatility.scala:269-341) for N independent chains: the two calls around dlm_ar1_ffbs_batch.
+ *   y_t = eps_t exp(alpha_t / 2),  alpha_t = mu + phi (alpha_{t-1} - mu) + eta_t,  eta_t ~ N(0, sigma^2);
+ *   log y_t^2 = alpha_t + log eps_t^2, log eps^2 approximated by the seven-component normal mixture (pi_j, m_j, v_j) of
+ *   Kim, Shephard & Chib (StochasticVolatility.scala:42-44).
+ * Chain state per series: alpha [T+1] (alpha[0] the state before the first observation, alpha[t+1] the state of y[t]: the theta of
+ * dlm_ar1_ffbs_batch) and sv = (phi, mu, sigma) in SvParameters order.  One iteration:
+ *   dlm_sv_mixture_batch   k_t | (y_t, alpha_t), ystar_t = log y_t^2 - m_{k_t}, v_t = v_{k_t}        (sampleKt, :112-140; :151-157)
+ *   dlm_ar1_ffbs_batch     alpha | (ystar, v, sv)   with v_stride = T, sv_stride = 3                  (FilterAr, :160-161)
+ *   dlm_sv_params_batch    phi, then mu given the new phi, then sigma given both                      (:276-283 / :294-299)
+ *
+ * dlm_sv_mixture_batch.  y [N][T] (NaN = missing), alpha [N][T+1] or NULL, ystar [N][T], v [N][T], k [N][T] int8 (nullable: the
+ * indicators 0..6), status [N] (nullable).  Per element, with x = alpha[n][t+1]:
+ *   lw_j = log pi_j + log N(log y_t^2 - m_j; x, v_j)  (a missing y_t: lw_j = log pi_j),  w_j = exp(lw_j - max lw),
+ *   p_j = w_0 + ... + w_j in index order,  k = #{ j in 0..5 : u p_6 >= p_j },  u the [0, 1) uniform of the element.
+ * A missing y_t keeps ystar_t = NaN and takes v_t = v_k of its prior draw.  alpha == NULL is the initial transform of
+ * initialStateAr (StochVolKnots.scala:345-352): ystar = log y^2 + 1.27, v = pi^2 / 2, no draw, k not written.
+ * Q20: an observed y_t whose log y_t^2 is not finite (y_t = 0, y_t^2 underflowing) would make every weight -inf and the draw NaN in the
+ * reference; it is treated as missing and the series gets DLM_ST_NONFINITE (so does a series with a non-finite alpha).
+ *
+ * dlm_sv_params_batch.  alpha [N][T+1], sv_in [N][3], sv_out [N][3] (may be sv_in), accepted [N] (in / out: incremented when the
+ * Beta proposal is accepted; nullable with phi_update = 0), status [N] (nullable).  prior->phi_update selects samplePhiConjugate
+ * (StochVolKnots.scala:25-43; phi_a, phi_b = mean and STANDARD DEVIATION of the Gaussian prior, as Breeze takes them) or the
+ * Beta-proposal Metropolis-Hastings samplePhi (:189-202; phi_a, phi_b = the Beta prior's a, b; prop_lambda, prop_tau: the reference
+ * passes 100, 0.05).  Default arithmetic, over all T pairs (alpha_{t-1}, alpha_t), psi the prior's standard deviation:
+ *   phi ~ N(mean, 1 / prec) restricted to (-1, 1),  prec = 1 / psi^2 + sum (alpha_{t-1} - mu)^2 / sigma^2,
+ *         mean = (m / psi^2 + sum (alpha_{t-1} - mu)(alpha_t - mu) / sigma^2) / prec; by rejection, at most 1023 attempts -- after
+ *         that phi stays and the series gets DLM_ST_NOT_PD;
+ *   or  phi' ~ Beta(lambda phi + tau, lambda (1 - phi) + tau), accepted with the full Hastings ratio against
+ *         Beta(a, b)(phi) N(alpha_0; mu, sigma^2 / (1 - phi^2)) prod_t N(alpha_t; mu + phi (alpha_{t-1} - mu), sigma^2);
+ *   mu ~ N(mean, 1 / prec),  prec = 1 / psi^2 + T (1 - phi)^2 / sigma^2,  mean = (m / psi^2 + (1 - phi) / sigma^2 sum (alpha_t - phi alpha_{t-1})) / prec;
+ *   sigma^2 ~ InverseGamma(shape + T / 2, scale + 1/2 sum (alpha_t - mu - phi (alpha_{t-1} - mu))^2),  sigma = sqrt.
+ * The conjugate mode leaves the stationary density of alpha_0 out of its three conditionals (it is not conjugate); the Beta mode's
+ * target has it.  prior->literal = 1 is the reference's arithmetic: `1 / sigma * sigma` (= 1) where 1 / sigma^2
+ * belongs; the T - 1 pairs t = 2..T in every transition sum, but sum_{t=1..T} (alpha_t - mu)^2 in phi's precision; shape + (T + 1) / 2;
+ * an unrestricted Gaussian phi (|phi| >= 1 makes the next dlm_ar1_ffbs_batch report DLM_ST_NOT_PD).
+ * A series whose sv_in is not finite, whose sigma <= 0, whose phi lies outside (0, 1) in the Beta mode, or whose sums are not finite
+ * gets DLM_ST_NONFINITE and NaN in sv_out.
+ *
+ * Draws: a Philox stream of their own keyed by (opts->seed, opts->series_offset + n, iteration, slot): slot t for k_t, six slots
+ * at the top of the field for the scalar draws (Marsaglia-Tsang Gammas, Box-Muller normals): reproducible and independent of
+ * the sharding.  Limits: N >= 1, 2 <= T < 2^21 - 8 (the reference throws on T = 1; the slot field), N T < 2^39; non-positive
+ * standard deviations, shape, scale, Beta or proposal parameters and unknown modes are DLM_ERR_ARG.  opts: mem, seed,
+ * series_offset, DLM_OPT_ASYNC. */
+typedef struct {
+  int32_t phi_update;            /* 0: Gaussian conjugate (sampleUni), 1: Beta-proposal MH (sampleBeta) */
+  int32_t literal;               /* 1: the reference's arithmetic, Q16-Q19 */
+  double phi_a, phi_b;           /* Gaussian(mean, sd) as Breeze takes it, or Beta(a, b) */
+  double mu_mean, mu_sd;
+  double sigma_shape, sigma_scale;
+  double prop_lambda, prop_tau;  /* the reference passes 100, 0.05 */
+} dlm_sv_prior;
+int dlm_sv_mixture_batch(dlm_engine* e, int32_t N, int32_t T, const double* y, const double* alpha, uint64_t iteration,
+                         const dlm_options* opts, double* ystar, double* v, int8_t* k, int32_t* status);
+int dlm_sv_params_batch(dlm_engine* e, int32_t N, int32_t T, const double* alpha, const double* sv_in, const dlm_sv_prior* prior,
+                        uint64_t iteration, const dlm_options* opts, double* sv_out, int32_t* accepted, int32_t* status);
+
 /* Per-series log-likelihood by the prediction-error decomposition,
  *   loglik[n] = sum_t log N(y_t^obs ; f_t^obs, Q_t^obs),
  * i.e. KalmanFilter.conditionalLikelihood (KalmanFilter.scala:138-153) summed over the series (steps with no observed

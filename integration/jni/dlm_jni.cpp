@@ -277,6 +277,25 @@ JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_ouFfbs(JNIEnv* en
   throw_if(env, eng(h), dlm_ou_ffbs_batch(eng(h), n, t, ptr<const double>(times), ptr<const double>(y), ptr<const double>(v), vStride, ptr<const double>(sv), svStride,
                                           ptr<const double>(z), &o, ptr<double>(filt), ptr<double>(theta), ptr<int32_t>(status)));
 }
+// ---- the AR(1) stochastic-volatility sampler around ar1Ffbs (StochasticVolatility.scala:112-157, :189-252; StochVolKnots.scala:25-43) ----
+// alpha = 0: the initial transform of initialStateAr.  The prior crosses as scalars in dlm_sv_prior's field order.
+JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_svMixture(JNIEnv* env, jobject, jlong h, jint n, jint t, jlong y, jlong alpha, jlong iteration, jlongArray opts,
+                                                                         jlong ystar, jlong v, jlong k, jlong status) {
+  dlm_options o{};
+  if (!read_opts(env, opts, o)) return;
+  throw_if(env, eng(h), dlm_sv_mixture_batch(eng(h), n, t, ptr<const double>(y), ptr<const double>(alpha), static_cast<uint64_t>(iteration), &o, ptr<double>(ystar),
+                                             ptr<double>(v), ptr<int8_t>(k), ptr<int32_t>(status)));
+}
+JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_svParams(JNIEnv* env, jobject, jlong h, jint n, jint t, jlong alpha, jlong svIn, jint phiUpdate, jint literal,
+                                                                        jdouble phiA, jdouble phiB, jdouble muMean, jdouble muSd, jdouble sigmaShape, jdouble sigmaScale,
+                                                                        jdouble propLambda, jdouble propTau, jlong iteration, jlongArray opts, jlong svOut, jlong accepted,
+                                                                        jlong status) {
+  dlm_options o{};
+  if (!read_opts(env, opts, o)) return;
+  const dlm_sv_prior pr{phiUpdate, literal, phiA, phiB, muMean, muSd, sigmaShape, sigmaScale, propLambda, propTau};
+  throw_if(env, eng(h), dlm_sv_params_batch(eng(h), n, t, ptr<const double>(alpha), ptr<const double>(svIn), &pr, static_cast<uint64_t>(iteration), &o, ptr<double>(svOut),
+                                            ptr<int32_t>(accepted), ptr<int32_t>(status)));
+}
 // ---- pooled-parameter Gibbs: reduce over series, then over GPUs (RCCL) ---------------------------------------------------------------
 JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_statsPool(JNIEnv* env, jobject, jlong h, jlong stats, jint n, jint l, jlong pooled, jlongArray opts) {
   dlm_options o{};

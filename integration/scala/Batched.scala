@@ -70,6 +70,9 @@ final class Native private[gpu] () {
   @native def studenttStep(h: Long, model: Array[Long], y: Long, theta: Long, stats: Long, priorNuRate: Double, propNuSize: Double, priorWShape: Double, priorWScale: Double, scaleIn: Long, nuIn: Long, iteration: Long, opts: Array[Long], vOut: Long, scaleOut: Long, nuOut: Long, wOut: Long, accepted: Long, loglik: Long, status: Long): Unit
   @native def ar1Ffbs(h: Long, n: Int, t: Int, y: Long, v: Long, vStride: Long, sv: Long, svStride: Long, z: Long, opts: Array[Long], filt: Long, theta: Long, status: Long): Unit
   @native def ouFfbs(h: Long, n: Int, t: Int, times: Long, y: Long, v: Long, vStride: Long, sv: Long, svStride: Long, z: Long, opts: Array[Long], filt: Long, theta: Long, status: Long): Unit
+  /** the AR(1) stochastic-volatility sampler around ar1Ffbs: the mixture indicators (sampleKt; alpha = 0: initialStateAr's transform), then phi, mu, sigma; the prior as scalars in dlm_sv_prior's order */
+  @native def svMixture(h: Long, n: Int, t: Int, y: Long, alpha: Long, iteration: Long, opts: Array[Long], ystar: Long, v: Long, k: Long, status: Long): Unit
+  @native def svParams(h: Long, n: Int, t: Int, alpha: Long, svIn: Long, phiUpdate: Int, literal: Int, phiA: Double, phiB: Double, muMean: Double, muSd: Double, sigmaShape: Double, sigmaScale: Double, propLambda: Double, propTau: Double, iteration: Long, opts: Array[Long], svOut: Long, accepted: Long, status: Long): Unit
   @native def statsPool(h: Long, stats: Long, n: Int, l: Int, pooled: Long, opts: Array[Long]): Unit
   @native def commUniqueId(): Array[Byte]
   @native def commInitRank(h: Long, nranks: Int, rank: Int, id: Array[Byte]): Unit
