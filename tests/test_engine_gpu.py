@@ -3,6 +3,7 @@ reference's golden vectors.  Tolerances are fp64 and stated per test."""
 import csv
 import json
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -11,6 +12,9 @@ import oracle
 from bayesian_dlms_amd import _lib
 from bayesian_dlms_amd.dlm import Dlm, DlmParameters, materialise
 from bayesian_dlms_amd.engine import EngineError
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from joint_posterior import dk_reference_draw, dk_reference_draw_mv  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -622,26 +626,6 @@ def test_svd_ffbs_draws_and_stats(eng, literal):
 # ------------------------------------------------------------------------------------------
 # FFBS by the Durbin-Koopman simulation smoother (DLM_OPT_FFBS_SIMSMOOTH)
 # ------------------------------------------------------------------------------------------
-def dk_reference_draw(mat, p, y, z):
-    """theta = E[x | y - y+] + x+ with (x+, y+) simulated from z [T+1][d+1]; smoothing by the oracle.  p.w / p.v may be [T] streams
-    (W_t drives the transition into record t, V_t observation t)."""
-    d, T = mat.d, mat.T
-    G = oracle.from_cm(mat.G[: d * d], d, d); F = mat.F[:d]
-    Lc = np.linalg.cholesky(p.c0)
-    Lws = [np.linalg.cholesky(w) for w in p.w] if p.w.ndim == 3 else [np.linalg.cholesky(p.w)] * T
-    svs = [np.sqrt(v[0, 0]) for v in p.v] if p.v.ndim == 3 else [np.sqrt(p.v[0, 0])] * T
-    x = p.m0 + Lc @ z[0, :d]
-    xs, yp = [x], np.empty((T, 1))
-    for t in range(1, T + 1):
-        x = G @ x + Lws[t - 1] @ z[t, :d]
-        xs.append(x)
-        yp[t - 1, 0] = F @ x + svs[t - 1] * z[t, d]
-    om = omodel(mat)
-    f = oracle.kf_filter(om, p.v, p.w, np.zeros(d), p.c0, y - yp)      # zero prior mean
-    s = oracle.smoother(om, f, compat_q1=False)
-    return s["s"] + np.array(xs)
-
-
 @pytest.mark.parametrize("dense_w", [False, True])
 def test_ffbs_simulation_smoother_matches_reference_construction(eng, dense_w):
     mod, mat, p = seasonal_model(T=90)
@@ -980,24 +964,6 @@ def test_status_flags_nonfinite_and_not_pd(eng):
     assert out["status"][0] & _lib.ST_NOT_PD
     ok = eng.filter_smooth(mat, bad, y[:1], flags=_lib.OPT_FORCE_GENERIC)   # the generic RTS path handles V = 0
     assert ok["status"][0] == 0 and np.all(np.isfinite(ok["smooth"]))
-
-
-def dk_reference_draw_mv(mat, p, y, z):
-    """Multivariate version of dk_reference_draw: z [T+1][d+p] (state noise, then observation noise)."""
-    d, q, T = mat.d, mat.p, mat.T
-    G = oracle.from_cm(mat.G[: d * d], d, d); F = oracle.from_cm(mat.F[: d * q], d, q)
-    Lc, Lv = np.linalg.cholesky(p.c0), np.linalg.cholesky(p.v)
-    Lws = [np.linalg.cholesky(w) for w in p.w] if p.w.ndim == 3 else [np.linalg.cholesky(p.w)] * T     # (a W_t stream: W_t drives the transition into record t)
-    x = p.m0 + Lc @ z[0, :d]
-    xs, yp = [x], np.empty((T, q))
-    for t in range(1, T + 1):
-        x = G @ x + Lws[t - 1] @ z[t, :d]
-        xs.append(x)
-        yp[t - 1] = F.T @ x + Lv @ z[t, d:]
-    om = omodel(mat)
-    f = oracle.kf_filter(om, p.v, p.w, np.zeros(d), p.c0, y - yp)
-    s = oracle.smoother(om, f, compat_q1=False)
-    return s["s"] + np.array(xs)
 
 
 def test_ffbs_simulation_smoother_multivariate(eng):

@@ -494,3 +494,64 @@ def test_driver_recovers_simulated_parameters_printed_only(eng):
         print(f"sample_{kind}: posterior means over {N} series: phi {post[:, 0].mean():.3f} (sd over series {post[:, 0].std():.3f}), "
               f"mu {post[:, 1].mean():.3f} ({post[:, 1].std():.3f}), sigma {post[:, 2].mean():.3f} ({post[:, 2].std():.3f}); simulated at 0.8, 1.0, 0.3")
         assert np.isfinite(draws).all()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the pairing of the mixture draw with the state draw: y[t] belongs to alpha[t + 1] across dlm_sv_mixture_batch -> dlm_ar1_ffbs_batch
+INV_SV = (0.8, 1.0, 0.3)
+
+
+def _invariance_data(N=16384, T=17, seed=2024):
+    """(y [N][T], alpha [N][T+1]) from the model the mixture sampler targets, on the host: alpha the stationary AR(1) path,
+    k_t ~ pi (the weights as the kernel normalises them), log y_t^2 = alpha_{t+1} + m_k + sqrt(v_k) eps, y_t = +- exp(log y_t^2 / 2)."""
+    phi, mu, sigma = INV_SV
+    rng = np.random.default_rng(seed)
+    alpha = np.empty((N, T + 1))
+    alpha[:, 0] = mu + sigma / math.sqrt(1.0 - phi * phi) * rng.standard_normal(N)
+    for t in range(T):
+        alpha[:, t + 1] = mu + phi * (alpha[:, t] - mu) + sigma * rng.standard_normal(N)
+    k = rng.choice(7, size=(N, T), p=PIS / PIS.sum())
+    ly = alpha[:, 1:] + MEANS[k] + np.sqrt(VARS[k]) * rng.standard_normal((N, T))
+    return rng.choice([-1.0, 1.0], (N, T)) * np.exp(0.5 * ly), alpha
+
+
+def _invariance_checks(y, alpha_new):
+    """The assertions of test_mixture_then_state_draw_leaves_the_joint_law_invariant on a new state draw (tools and rehearsals call it too)."""
+    from scipy import special, stats as ss
+    phi, mu, sigma = INV_SV
+    N, T = y.shape
+    e = np.empty_like(alpha_new)                  # whitened: iid N(0, 1) under the stationary AR(1) law
+    e[:, 0] = (alpha_new[:, 0] - mu) * math.sqrt(1.0 - phi * phi) / sigma
+    e[:, 1:] = (alpha_new[:, 1:] - mu - phi * (alpha_new[:, :-1] - mu)) / sigma
+    mean, var, lag = e.mean(axis=0), e.var(axis=0), (e[:, 1:] * e[:, :-1]).mean(axis=0)
+    se = 1.0 / math.sqrt(N)
+    print(f"whitened residuals, in standard errors: largest |mean| {np.abs(mean).max() / se:.2f}, largest |var - 1| "
+          f"{np.abs(var - 1.0).max() / (math.sqrt(2.0) * se):.2f}, largest |lag-one product| {np.abs(lag).max() / se:.2f}")
+    assert (np.abs(mean) <= 5.0 * se).all(), mean
+    assert (np.abs(var - 1.0) <= 5.0 * math.sqrt(2.0) * se).all(), var
+    assert (np.abs(lag) <= 5.0 * se).all(), lag
+    # not a no-op, and paired the right way round: log y_t^2 - alpha_new[t + 1] is the seven-component mixture, - alpha_new[t] is not
+    w = PIS / PIS.sum()
+    cdf = lambda x: (w * special.ndtr((np.asarray(x)[..., None] - MEANS) / np.sqrt(VARS))).sum(axis=-1)
+    ly = np.log(y * y)
+    right = ss.kstest((ly - alpha_new[:, 1:]).reshape(-1), cdf)
+    wrong = ss.kstest((ly - alpha_new[:, :-1]).reshape(-1), cdf)
+    print(f"KS against the mixture: log y_t^2 - alpha[t+1]: D {right.statistic:.5f} p {right.pvalue:.3g};  - alpha[t]: D {wrong.statistic:.5f} p {wrong.pvalue:.3g}")
+    assert right.pvalue > 1e-3
+    assert wrong.pvalue < 1e-3
+
+
+@pytest.mark.gpu
+def test_mixture_then_state_draw_leaves_the_joint_law_invariant(eng):
+    """sv_mixture then ar1_ffbs is a Gibbs block on (k, alpha) given y: it leaves p(alpha | y) invariant, so with (alpha, y) drawn from
+    the model the new alpha is again a stationary AR(1) path -- exactly, in one sweep, with N independent replicates -- and
+    (alpha_new, y) has the joint law of (alpha, y).  A shift of the pairing y[t] <-> alpha[t + 1] in either kernel breaks both.
+    Whitened residuals within five standard errors; the observation residual by Kolmogorov-Smirnov.  Rehearsed on the CPU with
+    this file's restatement of the mixture kernel and the oracle's AR(1) FFBS (profiles/r10_notes.md)."""
+    y, alpha = _invariance_data()
+    N, T = y.shape
+    mix = eng.sv_mixture(y, alpha, iteration=0, seed=41)
+    out = eng.ar1_ffbs(mix["ystar"], mix["v"], np.asarray(INV_SV), seed=43)
+    assert eng.last_variant == "ar1-lane" and (mix["status"] == 0).all() and (out["status"] == 0).all()
+    assert np.abs(out["theta"] - alpha).mean() > 0.05        # a new draw, not the old path
+    _invariance_checks(y, out["theta"])
