@@ -73,6 +73,17 @@ class SvPrior(ctypes.Structure):
                 ("prop_lambda", ctypes.c_double), ("prop_tau", ctypes.c_double)]
 
 
+class SvOuPrior(ctypes.Structure):
+    """dlm_sv_ou_prior: Beta(phi_a, phi_b) prior of the rate, Gaussian(mean, sd) of mu, InverseGamma(shape, scale) of sigma_eta ITSELF,
+    the Beta proposal's (lambda, tau) and the two random walks' standard deviations."""
+    _fields_ = [("literal", ctypes.c_int32),
+                ("phi_a", ctypes.c_double), ("phi_b", ctypes.c_double),
+                ("mu_mean", ctypes.c_double), ("mu_sd", ctypes.c_double),
+                ("sigma_shape", ctypes.c_double), ("sigma_scale", ctypes.c_double),
+                ("prop_lambda", ctypes.c_double), ("prop_tau", ctypes.c_double),
+                ("delta_sigma", ctypes.c_double), ("delta_mu", ctypes.c_double)]
+
+
 class Options(ctypes.Structure):
     _fields_ = [("flags", ctypes.c_uint32), ("mem", ctypes.c_int32),
                 ("seed", ctypes.c_uint64), ("series_offset", ctypes.c_uint64)]
@@ -109,6 +120,8 @@ SYMBOLS = [
     ("dlm_sv_mixture_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, ctypes.c_uint64, _OP, _V, _V, _V, _V]),
     ("dlm_sv_params_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, ctypes.POINTER(SvPrior), ctypes.c_uint64, _OP,
                                            _V, _V, _V]),
+    ("dlm_sv_ou_params_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, ctypes.POINTER(SvOuPrior), ctypes.c_uint64,
+                                              _OP, _V, _V, _V]),
     ("dlm_ou_ffbs_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, ctypes.c_int64, _V, ctypes.c_int64,
                                          _V, _OP, _V, _V, _V]),
     ("dlm_ar1_ffbs_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, ctypes.c_int64, _V, ctypes.c_int64,

@@ -1146,6 +1146,47 @@ int dlm_sv_params_batch(dlm_engine* e, int32_t N, int32_t T, const double* alpha
   return st.finish(opts->flags & DLM_OPT_ASYNC);
 }
 
+int dlm_sv_ou_params_batch(dlm_engine* e, int32_t N, int32_t T, const double* times, const double* alpha, const double* sv_in,
+                           const dlm_sv_ou_prior* prior, uint64_t iteration, const dlm_options* opts, double* sv_out,
+                           int32_t* accepted, int32_t* status) {
+  if (!e) return DLM_ERR_ARG;
+  if (!opts || !prior) return fail(e, DLM_ERR_ARG, "null descriptor");
+  if (opts->mem != DLM_MEM_DEVICE && opts->mem != DLM_MEM_HOST) return fail(e, DLM_ERR_ARG, "opts->mem");
+  if (N < 1 || T < 2) return fail(e, DLM_ERR_ARG, "N >= 1 and T >= 2 (one informative pair of states at least)");
+  if (T >= 0x1FFFF8) return fail(e, DLM_ERR_ARG, "T must stay below 2^21 - 8 (the Philox counter's slot field)");
+  if (prior->literal != 0 && prior->literal != 1) return fail(e, DLM_ERR_ARG, "literal: 0 or 1");
+  if (!times || !alpha || !sv_in || !sv_out || !accepted) return fail(e, DLM_ERR_ARG, "times, alpha, sv_in, sv_out and accepted are required");
+  const auto fin = [](double x) { return x - x == 0.0; };
+  const auto pos = [&](double x) { return x > 0.0 && fin(x); };
+  if (!(pos(prior->phi_a) && pos(prior->phi_b))) return fail(e, DLM_ERR_ARG, "the Beta prior of phi needs positive a and b");
+  if (!(pos(prior->mu_sd) && fin(prior->mu_mean))) return fail(e, DLM_ERR_ARG, "the Gaussian prior of mu needs a finite mean and a positive standard deviation");
+  if (!(pos(prior->sigma_shape) && pos(prior->sigma_scale))) return fail(e, DLM_ERR_ARG, "the InverseGamma prior of sigma needs a positive shape and scale");
+  if (!(pos(prior->prop_lambda) && pos(prior->prop_tau))) return fail(e, DLM_ERR_ARG, "the Beta proposal needs positive lambda and tau");
+  if (!(pos(prior->delta_sigma) && pos(prior->delta_mu))) return fail(e, DLM_ERR_ARG, "the random walks of sigma and mu need positive standard deviations");
+  HIP_TRY(e, hipSetDevice(e->device));
+  dlm::SvOuParamsArgs a{};
+  const size_t n = N, t = T;
+  Stager st(e, opts->mem == DLM_MEM_HOST);
+  st.in(&a.times, times, t);
+  st.in(&a.alpha, alpha, n * (t + 1));
+  st.in(&a.sv_in, sv_in, n * 3);
+  st.out(&a.sv_out, sv_out, n * 3);
+  st.inout(&a.accepted, (int*)accepted, n * 3);
+  st.zeroed_out(&a.status, (int*)status, status ? n : 0);
+  int rc;
+  if ((rc = st.commit())) return rc;
+  a.N = N; a.T = T;
+  a.literal = prior->literal;
+  a.phi_a = prior->phi_a; a.phi_b = prior->phi_b; a.mu_mean = prior->mu_mean; a.mu_sd = prior->mu_sd;
+  a.sigma_shape = prior->sigma_shape; a.sigma_scale = prior->sigma_scale;
+  a.prop_lambda = prior->prop_lambda; a.prop_tau = prior->prop_tau;
+  a.delta_sigma = prior->delta_sigma; a.delta_mu = prior->delta_mu;
+  a.seed = opts->seed; a.series_offset = opts->series_offset; a.iteration = iteration;
+  e->variant = "sv-ou-params";
+  HIP_TRY(e, dlm::launch_sv_ou_params(a, e->stream));
+  return st.finish(opts->flags & DLM_OPT_ASYNC);
+}
+
 static int ar1_common(dlm_engine* e, int32_t N, int32_t T, const double* times, bool ou, const double* y, const double* v,
                       int64_t v_stride, const double* sv, int64_t sv_stride, const double* z, const dlm_options* opts,
                       double* filt, double* theta, int32_t* status);

@@ -401,6 +401,22 @@ struct SvParamsArgs {
 hipError_t launch_sv_mixture(const SvMixArgs& a, hipStream_t s);
 hipError_t launch_sv_params(const SvParamsArgs& a, hipStream_t s);
 
+// ---- stochastic volatility with Ornstein-Uhlenbeck log-volatility on an irregular grid: the three Metropolis moves after the OU
+// FFBS call (StochasticVolatility.scala:350-431, :459-478), dlm_sv_ou.hip -------------
+struct SvOuParamsArgs {
+  int N, T;
+  const double* times;    // [T], shared by the batch
+  const double* alpha;    // [N][T+1] as dlm_ou_ffbs_batch writes its theta
+  const double* sv_in;    // [N][3] = (phi, mu, sigma_eta), phi the mean-reversion rate
+  int literal;
+  double phi_a, phi_b, mu_mean, mu_sd, sigma_shape, sigma_scale, prop_lambda, prop_tau, delta_sigma, delta_mu;
+  unsigned long long seed, series_offset, iteration;
+  double* sv_out;         // [N][3], may be sv_in
+  int* accepted;          // [N][3]: phi, sigma, mu
+  int* status;            // nullable
+};
+hipError_t launch_sv_ou_params(const SvOuParamsArgs& a, hipStream_t s);
+
 // ---- KalmanFilter.likelihood literally (transition density of the filtered means), dlm_loglik.hip ------
 size_t loglik_q7_ws_bytes(const KArgs& a);
 hipError_t launch_loglik_q7(const KArgs& a, const double* records, void* ws, hipStream_t s);   // a.loglik [N] <- records [N][T+1][d+dd]
@@ -497,9 +513,11 @@ __device__ __forceinline__ void philox_normal2(unsigned long long seed, unsigned
 //   DLM_KEY_GIBBS     dlm_dinvgamma_step_batch: comp = component of [V diagonal (p) | W diagonal (d)]; the Student-t step draws W here too
 //   DLM_KEY_STUDENTT  dlm_studentt_step_batch: comp = t for the variance v_t, DLM_ST_SLOT_* for its scalar draws (dlm_studentt.hip)
 //   DLM_KEY_SV        dlm_sv_mixture_batch: comp = t for the mixture indicator k_t; dlm_sv_params_batch: DLM_SV_SLOT_* (dlm_sv.hip)
+//   DLM_KEY_SVOU      dlm_sv_ou_params_batch: DLM_SVOU_SLOT_* (dlm_sv_ou.hip); the OU chain's mixture call draws under DLM_KEY_SV
 constexpr unsigned DLM_KEY_GIBBS = 0x47494242u;      // "GIBB"
 constexpr unsigned DLM_KEY_STUDENTT = 0x53545544u;   // "STUD"
 constexpr unsigned DLM_KEY_SV = 0x5354564Fu;         // "STVO"
+constexpr unsigned DLM_KEY_SVOU = 0x53564F55u;       // "SVOU"
 
 __device__ __forceinline__ void gibbs_rand(unsigned long long seed, unsigned long long series, unsigned long long iteration,
                                            unsigned comp, unsigned attempt, unsigned which, double& u1, double& u2,

@@ -287,7 +287,7 @@ class Engine:
             self._check(self.lib.dlm_ar1_ffbs_batch(self.h, N, T, be.ptr(yb), be.ptr(vb), v_stride, be.ptr(sb), sv_stride,
                                                     be.ptr(zb), op, be.ptr(filt), be.ptr(theta), be.ptr(status)))
         else:
-            tb = be.put(np.asarray(times, dtype=np.float64))
+            tb = be.put(times)   # (a device tensor stays where it is)
             self._check(self.lib.dlm_ou_ffbs_batch(self.h, N, T, be.ptr(tb), be.ptr(yb), be.ptr(vb), v_stride, be.ptr(sb),
                                                    sv_stride, be.ptr(zb), op, be.ptr(filt), be.ptr(theta), be.ptr(status)))
         return {"filt": filt, "theta": theta, "status": status}
@@ -395,6 +395,42 @@ class Engine:
         self._hold(flags, ab, sb)
         self._check(self.lib.dlm_sv_params_batch(self.h, N, T, be.ptr(ab), be.ptr(sb), pr, int(iteration), op, be.ptr(sv_out),
                                                  be.ptr(acc), be.ptr(status)))
+        return {"sv": sv_out, "accepted": acc, "status": status}
+
+    def sv_ou_params(self, times, alpha, sv, prior, *, iteration, accepted=None, seed=0, series_offset=0, flags=0, out=None):
+        """phi, sigma, mu of the stochastic-volatility sampler with Ornstein-Uhlenbeck log-volatility given the state draw
+        (dlm_sv_ou_params_batch; samplePhiOu, sampleSigmaMetropOu, sampleMuOu in stepOu's order) for N chains: times [T] shared by the
+        batch, alpha [N][T+1] as ar1_ffbs(times=...) writes its theta, sv [N][3] = (phi, mu, sigma) with phi the mean-reversion rate.
+        prior: a _lib.SvOuPrior, or its eleven fields in order (literal, phi_a, phi_b, mu_mean, mu_sd, sigma_shape, sigma_scale,
+        prop_lambda, prop_tau, delta_sigma, delta_mu).  accepted [N][3] int32 (phi, sigma, mu) is incremented in place (None: a fresh
+        zero array).  Returns {"sv" [N][3], "accepted", "status"}.  out: dict with an existing "sv" buffer to write into (it may be
+        the input)."""
+        be = self._backend(alpha)
+        N, T = int(alpha.shape[0]), int(alpha.shape[1]) - 1
+        ab, sb = be.put(alpha), be.put(sv)
+        tb = be.put(times)
+        if tuple(tb.shape) != (T,):
+            raise EngineError(f"times must be [T] = {(T,)}, got {tuple(tb.shape)}")
+        if tuple(sb.shape) != (N, 3):
+            raise EngineError(f"sv must be [N][3] = {(N, 3)}, got {tuple(sb.shape)}")
+        if isinstance(prior, _lib.SvOuPrior):
+            pr = prior
+        else:
+            f = tuple(prior)
+            pr = _lib.SvOuPrior(int(f[0]), *(float(x) for x in f[1:]))
+        out = out or {}
+        sv_out = out["sv"] if "sv" in out else be.empty((N, 3))
+        acc = be.put(accepted, np.int32) if accepted is not None else None
+        if acc is None:
+            acc = be.empty((N, 3), np.int32)
+            acc[...] = 0
+        elif tuple(acc.shape) != (N, 3):
+            raise EngineError(f"accepted must be [N][3] = {(N, 3)}, got {tuple(acc.shape)}")
+        status = be.empty((N,), np.int32)
+        op = _lib.Options(flags, be.mem, seed, series_offset)
+        self._hold(flags, tb, ab, sb)
+        self._check(self.lib.dlm_sv_ou_params_batch(self.h, N, T, be.ptr(tb), be.ptr(ab), be.ptr(sb), pr, int(iteration), op,
+                                                    be.ptr(sv_out), be.ptr(acc), be.ptr(status)))
         return {"sv": sv_out, "accepted": acc, "status": status}
 
     def simulate(self, mat, params, N, *, seed=0, series_offset=0, device=False, want_x=True):

@@ -17,6 +17,12 @@ parameters, `accepted` and `status` cross to the host, plus alpha when asked for
 The default is the corrected sampler; literal=True runs the reference's arithmetic (Q16-Q19).  The priors
 are the families the device evaluates: `Gaussian` for mu and for the conjugate phi, `Beta` for the Metropolis-Hastings phi,
 `InverseGamma` for sigma_eta^2; the reference's arbitrary ContinuousDistr of sampleBeta is not offered.
+
+sample_ou is the same chain with an Ornstein-Uhlenbeck log-volatility observed at arbitrary times (StochasticVolatility.sampleOu,
+:343-500):  alpha(t + dt) | alpha(t) ~ N(mu + e^(-phi dt) (alpha(t) - mu), sigma_eta^2 (1 - e^(-2 phi dt)) / (2 phi)),  phi the
+mean-reversion rate.  Its three calls are dlm_sv_mixture_batch, dlm_ou_ffbs_batch and dlm_sv_ou_params_batch (Metropolis moves of phi,
+sigma_eta, mu).  Its `InverseGamma` prior is on sigma_eta ITSELF, as the reference evaluates it -- the one
+difference between the two samplers' priors.
 """
 from __future__ import annotations
 
@@ -67,10 +73,11 @@ def _host(a):
 
 
 def initial_parameters(prior_phi, prior_mu: Gaussian, prior_sigma: InverseGamma, n_series: int, *, seed: int = 0,
-                       series_offset: int = 0) -> np.ndarray:
+                       series_offset: int = 0, sigma_squared: bool = True) -> np.ndarray:
     """(phi, mu, sigma_eta) [N][3] drawn from the priors on the host (sampleUni / sampleBeta, StochasticVolatility.scala:308-340) by a
     generator keyed by (seed, global series index) -- a sharded run starts where the single-GPU run does.  phi is redrawn until
-    |phi| < 1 (inside (0, 1) for a Beta prior): the FFBS needs a stationary state."""
+    |phi| < 1 (inside (0, 1) for a Beta prior): the FFBS needs a stationary state.  sigma_squared=False: the InverseGamma is the
+    prior of sigma_eta itself (sample_ou), not of its square."""
     beta = isinstance(prior_phi, Beta)
     out = np.empty((n_series, 3))
     for k in range(n_series):
@@ -79,7 +86,8 @@ def initial_parameters(prior_phi, prior_mu: Gaussian, prior_sigma: InverseGamma,
         while not ((0.0 < phi < 1.0) if beta else (abs(phi) < 1.0)):
             phi = float(prior_phi.draw(rng))
         mu = float(prior_mu.draw(rng))
-        out[k] = (phi, mu, np.sqrt(float(prior_sigma.draw(rng))))
+        sig = float(prior_sigma.draw(rng))
+        out[k] = (phi, mu, np.sqrt(sig) if sigma_squared else sig)
     return out
 
 
@@ -87,8 +95,8 @@ class StochasticVolatility:
     @dataclass
     class State:
         """StochVolState (StochasticVolatility.scala), batched: params [N][3] = (phi, mu, sigma_eta) on the host, alpha [N][T+1] a host
-        copy when asked for (keep_alpha) else None, accepted [N] (the Beta proposal's acceptances so far; zeros for sample_uni),
-        status [N]: the three calls' flags or'ed."""
+        copy when asked for (keep_alpha) else None, accepted [N] (the Beta proposal's acceptances so far; zeros for sample_uni;
+        [N][3] for sample_ou: the acceptances of phi, sigma_eta, mu), status [N]: the three calls' flags or'ed."""
         params: np.ndarray
         alpha: Optional[np.ndarray]
         accepted: np.ndarray
@@ -108,41 +116,70 @@ class StochasticVolatility:
         return y, alpha
 
     @staticmethod
+    def simulate_ou(p: SvParameters, times, N: int, seed: int = 0):
+        """StochasticVolatility.simOu for N series with NumPy on the grid times [T]: (y [N][T], alpha [N][T+1]) in the layout of
+        dlm_ou_ffbs_batch's theta -- alpha[:, 0] ~ N(mu, sigma_eta^2) and alpha[:, 1] = alpha[:, 0] both sit at times[0], alpha[:, t]
+        at times[t-1].  For tests and benchmarks."""
+        times = np.asarray(times, dtype=np.float64)
+        T = times.size
+        rng = np.random.default_rng(seed)
+        alpha = np.empty((N, T + 1))
+        alpha[:, 0] = p.mu + p.sigma_eta * rng.standard_normal(N)
+        alpha[:, 1] = alpha[:, 0]
+        z = rng.standard_normal((N, T))
+        for t in range(2, T + 1):
+            dt = times[t - 1] - times[t - 2]
+            if dt == 0.0:          # a repeated time: the state stays, bit for bit
+                alpha[:, t] = alpha[:, t - 1]
+                continue
+            sd = p.sigma_eta * np.sqrt(-np.expm1(-2.0 * p.phi * dt) / (2.0 * p.phi))
+            alpha[:, t] = p.mu + np.exp(-p.phi * dt) * (alpha[:, t - 1] - p.mu) + sd * z[:, t - 1]
+        y = rng.standard_normal((N, T)) * np.exp(0.5 * alpha[:, 1:])
+        return y, alpha
+
+    @staticmethod
     def _seed_ffbs(seed, k):
         # the FFBS normals are keyed by (seed, series, t) alone: a seed per FFBS call, k = 0 the initial state's
         return (int(seed) * 1000003 + k) & MASK64
 
     @staticmethod
     def initial_state_ar(y, sv, engine, *, seed: int = 0, series_offset: int = 0, ffbs: Optional[Callable] = None,
-                         mixture: Optional[Callable] = None, out=None):
+                         mixture: Optional[Callable] = None, out=None, times=None):
         """initialStateAr (StochVolKnots.scala:345-352): one FFBS on ystar = log y^2 + 1.27 with v = pi^2 / 2 at every step.
-        Returns {"alpha" [N][T+1], "ystar", "v", "status"}."""
+        Returns {"alpha" [N][T+1], "ystar", "v", "status"}.  times [T]: initialStateOu (StochasticVolatility.scala:480-487), the
+        Ornstein-Uhlenbeck FFBS on that grid."""
+        grid = {} if times is None else {"times": times}
         run_mix = mixture if mixture is not None else engine.sv_mixture
         run_ffbs = ffbs if ffbs is not None else engine.ar1_ffbs
         mix = run_mix(y, None, iteration=0, seed=seed, series_offset=series_offset, out=out)
         f = run_ffbs(mix["ystar"], mix["v"], sv, seed=StochasticVolatility._seed_ffbs(seed, 0), series_offset=series_offset,
-                     want_filt=False, want_theta=True)
+                     want_filt=False, want_theta=True, **grid)
         return {"alpha": f["theta"], "ystar": mix["ystar"], "v": mix["v"], "status": _or_status(mix.get("status"), f.get("status"))}
 
     @staticmethod
     def sample_state_ar(y, alpha, sv, engine, *, iteration: int, seed: int = 0, series_offset: int = 0,
-                        ffbs: Optional[Callable] = None, mixture: Optional[Callable] = None, out=None):
+                        ffbs: Optional[Callable] = None, mixture: Optional[Callable] = None, out=None, times=None):
         """sampleStateAr (StochasticVolatility.scala:142-162): the mixture indicators given alpha, then the FFBS draw of alpha.
-        Returns {"alpha" [N][T+1], "ystar", "v", "status"}; out: the "ystar" / "v" buffers to reuse."""
+        Returns {"alpha" [N][T+1], "ystar", "v", "status"}; out: the "ystar" / "v" buffers to reuse.  times [T]: sampleStateOu
+        (:433-452), the Ornstein-Uhlenbeck FFBS on that grid."""
+        grid = {} if times is None else {"times": times}
         run_mix = mixture if mixture is not None else engine.sv_mixture
         run_ffbs = ffbs if ffbs is not None else engine.ar1_ffbs
         mix = run_mix(y, alpha, iteration=iteration, seed=seed, series_offset=series_offset, out=out)
         f = run_ffbs(mix["ystar"], mix["v"], sv, seed=StochasticVolatility._seed_ffbs(seed, iteration + 1), series_offset=series_offset,
-                     want_filt=False, want_theta=True)
+                     want_filt=False, want_theta=True, **grid)
         return {"alpha": f["theta"], "ystar": mix["ystar"], "v": mix["v"], "status": _or_status(mix.get("status"), f.get("status"))}
 
     @staticmethod
     def _sample(ys, prior, beta, prior_phi, prior_mu, prior_sigma, engine, *, n_iter, seed, params0, series_offset, keep_alpha,
-                ffbs, mixture, params):
+                ffbs, mixture, params, times=None):
+        # times [T]: the Ornstein-Uhlenbeck chain on that grid (sample_ou) -- the FFBS calls take the grid, the parameter call is
+        # sv_ou_params with the grid in front and `accepted` is [N][3]; everything else is the AR(1) chain's plumbing
+        ou = times is not None
         N, T = int(ys.shape[0]), int(ys.shape[1])
         if T < 2:
             raise ValueError("the stochastic-volatility sampler needs T >= 2 (the reference's sums throw on a single observation)")
-        run_params = params if params is not None else engine.sv_params
+        run_params = params if params is not None else (engine.sv_ou_params if ou else engine.sv_params)
         torch = None
         dev = None
         if _is_torch(ys) or engine is not None:
@@ -153,7 +190,7 @@ class StochasticVolatility:
             return torch.as_tensor(a, device=dev) if torch is not None else a
         y = ys.reshape(N, T).to(dtype=torch.float64).contiguous() if _is_torch(ys) else put(np.asarray(ys, dtype=np.float64).reshape(N, T))
         if params0 is None:
-            sv_h = initial_parameters(prior_phi, prior_mu, prior_sigma, N, seed=seed, series_offset=series_offset)
+            sv_h = initial_parameters(prior_phi, prior_mu, prior_sigma, N, seed=seed, series_offset=series_offset, sigma_squared=not ou)
         else:
             p0 = (params0.phi, params0.mu, params0.sigma_eta) if isinstance(params0, SvParameters) else params0
             sv_h = np.broadcast_to(np.asarray(p0, dtype=np.float64), (N, 3)).copy()
@@ -161,14 +198,23 @@ class StochasticVolatility:
             if bad.any() or not (sv_h[:, 2] > 0.0).all():
                 raise ValueError("initial parameters need a stationary phi (inside (0, 1) for the Beta proposal) and sigma_eta > 0")
         sv = put(sv_h)
-        acc = put(np.zeros(N, dtype=np.int32), np.int32)
-        st = StochasticVolatility.initial_state_ar(y, sv, engine, seed=seed, series_offset=series_offset, ffbs=ffbs, mixture=mixture)
+        acc = put(np.zeros((N, 3) if ou else N, dtype=np.int32), np.int32)
+        grid, lead = {}, ()
+        if ou:
+            tgrid = _host(times).astype(np.float64)
+            if tgrid.shape != (T,):
+                raise ValueError(f"times must be [T] = {(T,)}, got {tgrid.shape}")
+            tgrid = put(tgrid)
+            grid, lead = {"times": tgrid}, (tgrid,)
+        st = StochasticVolatility.initial_state_ar(y, sv, engine, seed=seed, series_offset=series_offset, ffbs=ffbs, mixture=mixture,
+                                                   **grid)
         alpha, bufs, status0 = st["alpha"], {"ystar": st["ystar"], "v": st["v"]}, st["status"]
         for it in range(n_iter):
             st = StochasticVolatility.sample_state_ar(y, alpha, sv, engine, iteration=it, seed=seed, series_offset=series_offset,
-                                                      ffbs=ffbs, mixture=mixture, out=bufs)
+                                                      ffbs=ffbs, mixture=mixture, out=bufs, **grid)
             alpha, bufs = st["alpha"], {"ystar": st["ystar"], "v": st["v"]}
-            res = run_params(alpha, sv, prior, iteration=it, accepted=acc, seed=seed, series_offset=series_offset, out={"sv": sv})
+            res = run_params(*lead, alpha, sv, prior, iteration=it, accepted=acc, seed=seed, series_offset=series_offset,
+                             out={"sv": sv})
             sv, acc = res["sv"], res["accepted"]
             status = _or_status(st["status"], res.get("status"))
             if it == 0:
@@ -207,6 +253,28 @@ class StochasticVolatility:
         return StochasticVolatility._sample(ys, prior, True, prior_phi, prior_mu, prior_sigma, engine, n_iter=n_iter, seed=seed,
                                             params0=params0, series_offset=series_offset, keep_alpha=keep_alpha, ffbs=ffbs,
                                             mixture=mixture, params=params)
+
+    @staticmethod
+    def sample_ou(times, ys, prior_phi: Beta, prior_mu: Gaussian, prior_sigma: InverseGamma, engine, *, n_iter: int, seed: int = 0,
+                  params0=None, literal: bool = False, series_offset: int = 0, keep_alpha: bool = False, prop_lambda: float = 10.0,
+                  prop_tau: float = 0.05, delta_sigma: float = 0.05, delta_mu: float = 0.05, ffbs: Optional[Callable] = None,
+                  mixture: Optional[Callable] = None, params: Optional[Callable] = None) -> Iterator["StochasticVolatility.State"]:
+        """StochasticVolatility.sampleOu (:489-500) for N independent series observed at the shared times [T]: ys [N][T] (NaN = missing),
+        the log-volatility an Ornstein-Uhlenbeck process with rate phi in (0, 1), mean mu and volatility sigma_eta.  Per iteration
+        sv_mixture, ar1_ffbs(times=...), sv_ou_params: Metropolis moves of phi (Beta(lambda phi + tau, lambda (1 - phi) + tau) proposal,
+        Beta prior), sigma_eta (log-normal walk of sd delta_sigma; the InverseGamma prior is on sigma_eta ITSELF, where
+        sample_uni / sample_beta take it on sigma_eta^2) and mu (Gaussian walk of sd delta_mu), State.accepted [N][3] in that order.
+        The proposal arguments default to the reference signatures' own (10, 0.05, 0.05, 0.05).  literal=True runs the reference's
+        arithmetic and passes lambda = 0.05, as stepOu does by handing 0.05 to the `lambda` parameter (Q22).
+        Everything else as sample_uni; ffbs= / mixture= / params= replace engine.ar1_ffbs / sv_mixture / sv_ou_params, for tests."""
+        if not isinstance(prior_phi, Beta) or not isinstance(prior_mu, Gaussian) or not isinstance(prior_sigma, InverseGamma):
+            raise TypeError("the device evaluates a Beta prior of phi, a Gaussian prior of mu and an InverseGamma prior of sigma_eta only")
+        prior = _lib.SvOuPrior(1 if literal else 0, prior_phi.a, prior_phi.b, prior_mu.mean, prior_mu.sd, prior_sigma.shape,
+                               prior_sigma.scale, 0.05 if literal else float(prop_lambda), float(prop_tau), float(delta_sigma),
+                               float(delta_mu))
+        return StochasticVolatility._sample(ys, prior, True, prior_phi, prior_mu, prior_sigma, engine, n_iter=n_iter, seed=seed,
+                                            params0=params0, series_offset=series_offset, keep_alpha=keep_alpha, ffbs=ffbs,
+                                            mixture=mixture, params=params, times=times)
 
 
 def _or_status(a, b):

@@ -337,6 +337,56 @@ int dlm_sv_mixture_batch(dlm_engine* e, int32_t N, int32_t T, const double* y, c
 int dlm_sv_params_batch(dlm_engine* e, int32_t N, int32_t T, const double* alpha, const double* sv_in, const dlm_sv_prior* prior,
                         uint64_t iteration, const dlm_options* opts, double* sv_out, int32_t* accepted, int32_t* status);
 
+/* The parameter step of the stochastic-volatility sampler whose log-volatility is an Ornstein-Uhlenbeck process observed at
+ * arbitrary times (StochasticVolatility.sampleOu / stepOu, StochasticVolatility.scala:343-500) for N independent chains:
+ *   y_i = eps_i exp(alpha_i / 2),  alpha(t + dt) | alpha(t) ~ N(mu + e^(-phi dt) (alpha(t) - mu), sigma^2 (1 - e^(-2 phi dt)) / (2 phi)),
+ * phi > 0 the mean-reversion rate.  One iteration:
+ *   dlm_sv_mixture_batch     as for the AR(1) sampler (it works per element and never sees the time grid)
+ *   dlm_ou_ffbs_batch        alpha | (ystar, v, sv) on the grid `times`, v_stride = T, sv_stride = 3             (sampleStateOu, :433-452)
+ *   dlm_sv_ou_params_batch   three Metropolis moves: phi, then sigma at the new phi, then mu at the new phi and sigma  (:459-478)
+ *
+ * times [T] shared by the batch; alpha [N][T+1] as dlm_ou_ffbs_batch writes its theta: alpha[0] and alpha[1] both sit at times[0]
+ * (the reference's first dt is 0) and alpha[t] belongs to times[t-1], so the informative pairs are (alpha[t-1], alpha[t]), t = 2..T,
+ * with dt_t = times[t-1] - times[t-2].  A pair with dt = 0 contributes nothing (ouLikelihood, :360-361); n counts the pairs with
+ * dt > 0.  sv_in [N][3], sv_out [N][3] (may be sv_in), accepted [N][3] (in / out, REQUIRED: the acceptances of phi, sigma, mu are
+ * added), status [N] (nullable).  With e_t = exp(-phi dt_t), g_t = -expm1(-2 phi dt_t), d_t = alpha[t] - mu0 (mu0 the incoming mu):
+ *   log p(alpha | phi, mu, sigma) = -n/2 log 2 pi - n log sigma + n/2 log(2 phi) - L(phi) / 2 - phi Q(phi, mu) / sigma^2,
+ *   L = sum log g_t,  A = sum (d_t - e_t d_{t-1})^2 / g_t,  B = sum (d_t - e_t d_{t-1})(1 - e_t) / g_t,  C = sum (1 - e_t)^2 / g_t,
+ *   Q(phi, mu0 + delta) = A - 2 delta B + delta^2 C.
+ * The row is read once: (L, A, B, C) at phi and at the proposed phi' are all the three moves need.  Each move accepts when
+ * log u < Delta.  Default arithmetic:
+ *   phi'   ~ Beta(lambda phi + tau, lambda (1 - phi) + tau) (rejected when it rounds to 0 or 1), prior Beta(phi_a, phi_b), target
+ *            (a - 1) log phi + (b - 1) log(1 - phi) + n/2 log(2 phi) - L(phi) / 2 - phi A(phi) / sigma^2, with the full Hastings ratio;
+ *   sigma' = sigma exp(delta_sigma z), prior InverseGamma(sigma_shape, sigma_scale) ON SIGMA ITSELF (priorSigma.logPdf(newSigma), :407;
+ *            dlm_sv_params_batch's prior is on sigma^2), target -(shape + 1) log sigma - scale / sigma - n log sigma - phi A / sigma^2
+ *            - log sigma - (alpha_0 - mu)^2 / (2 sigma^2), plus log(sigma' / sigma) for the log-normal walk;
+ *   mu'    = mu + delta_mu z, prior Gaussian(mu_mean, mu_sd) (the STANDARD DEVIATION, as Breeze takes it), target
+ *            -(mu - m)^2 / (2 s^2) - phi Q(phi, mu) / sigma^2 - (alpha_0 - mu)^2 / (2 sigma^2).
+ * The terms in alpha_0 are log N(alpha_0; mu, sigma^2), the initial state as dlm_ou_ffbs_batch draws it (c0 = sigma^2).
+ * prior->literal = 1 is the reference's arithmetic: plain Metropolis ratios for the two asymmetric proposals
+ * and no term for the initial state.  Q22: the reference's stepOu passes lambda = 0.05 (it meant tau); lambda, tau, delta_sigma and
+ * delta_mu are fields here, the signatures' defaults being 10, 0.05, 0.05, 0.05.  Q25: sigma and mu start from the incoming values
+ * and see the new phi (and sigma), as stepOu has it.
+ * A negative or non-finite step of `times` gives EVERY series DLM_ST_NONFINITE and NaN in sv_out.  A series whose sv_in is not
+ * finite, whose phi lies outside (0, 1), whose sigma <= 0 or whose sums at its phi are not finite gets DLM_ST_NONFINITE and NaN in
+ * sv_out; its counters stay.
+ *
+ * Draws: a Philox stream of its own (another key than dlm_sv_mixture_batch's), counter (opts->seed, opts->series_offset + n,
+ * iteration, slot), seven slots at the top of the field (two Marsaglia-Tsang Gammas, two Box-Muller normals, three uniforms):
+ * reproducible and independent of the sharding.  Limits: N >= 1, 2 <= T < 2^21 - 8; non-positive standard deviation, shape, scale,
+ * Beta or proposal parameters and literal outside {0, 1} are DLM_ERR_ARG.  opts: mem, seed, series_offset, DLM_OPT_ASYNC. */
+typedef struct {
+  int32_t literal;                 /* 1: the reference's arithmetic, Q23-Q24 */
+  double phi_a, phi_b;             /* Beta(a, b) prior of phi */
+  double mu_mean, mu_sd;           /* Gaussian(mean, sd) as Breeze takes it */
+  double sigma_shape, sigma_scale; /* InverseGamma prior of sigma (not sigma^2) */
+  double prop_lambda, prop_tau;    /* the Beta proposal; the signature's defaults are 10, 0.05, stepOu passes 0.05, 0.05 (Q22) */
+  double delta_sigma, delta_mu;    /* the random walks' standard deviations; the reference passes 0.05, 0.05 */
+} dlm_sv_ou_prior;
+int dlm_sv_ou_params_batch(dlm_engine* e, int32_t N, int32_t T, const double* times, const double* alpha, const double* sv_in,
+                           const dlm_sv_ou_prior* prior, uint64_t iteration, const dlm_options* opts, double* sv_out,
+                           int32_t* accepted, int32_t* status);
+
 /* Per-series log-likelihood by the prediction-error decomposition,
  *   loglik[n] = sum_t log N(y_t^obs ; f_t^obs, Q_t^obs),
  * i.e. KalmanFilter.conditionalLikelihood (KalmanFilter.scala:138-153) summed over the series (steps with no observed

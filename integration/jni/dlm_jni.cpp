@@ -296,6 +296,18 @@ JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_svParams(JNIEnv* 
   throw_if(env, eng(h), dlm_sv_params_batch(eng(h), n, t, ptr<const double>(alpha), ptr<const double>(svIn), &pr, static_cast<uint64_t>(iteration), &o, ptr<double>(svOut),
                                             ptr<int32_t>(accepted), ptr<int32_t>(status)));
 }
+// ---- the OU stochastic-volatility sampler's parameter step after ouFfbs (StochasticVolatility.scala:350-431, :459-478): the prior, the
+// proposal's (lambda, tau) and the walks' standard deviations cross as scalars in dlm_sv_ou_prior's field order; accepted is [N][3]
+JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_svOuParams(JNIEnv* env, jobject, jlong h, jint n, jint t, jlong times, jlong alpha, jlong svIn, jint literal,
+                                                                          jdouble phiA, jdouble phiB, jdouble muMean, jdouble muSd, jdouble sigmaShape, jdouble sigmaScale,
+                                                                          jdouble propLambda, jdouble propTau, jdouble deltaSigma, jdouble deltaMu, jlong iteration,
+                                                                          jlongArray opts, jlong svOut, jlong accepted, jlong status) {
+  dlm_options o{};
+  if (!read_opts(env, opts, o)) return;
+  const dlm_sv_ou_prior pr{literal, phiA, phiB, muMean, muSd, sigmaShape, sigmaScale, propLambda, propTau, deltaSigma, deltaMu};
+  throw_if(env, eng(h), dlm_sv_ou_params_batch(eng(h), n, t, ptr<const double>(times), ptr<const double>(alpha), ptr<const double>(svIn), &pr, static_cast<uint64_t>(iteration),
+                                               &o, ptr<double>(svOut), ptr<int32_t>(accepted), ptr<int32_t>(status)));
+}
 // ---- pooled-parameter Gibbs: reduce over series, then over GPUs (RCCL) ---------------------------------------------------------------
 JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_statsPool(JNIEnv* env, jobject, jlong h, jlong stats, jint n, jint l, jlong pooled, jlongArray opts) {
   dlm_options o{};

@@ -73,6 +73,8 @@ final class Native private[gpu] () {
   /** the AR(1) stochastic-volatility sampler around ar1Ffbs: the mixture indicators (sampleKt; alpha = 0: initialStateAr's transform), then phi, mu, sigma; the prior as scalars in dlm_sv_prior's order */
   @native def svMixture(h: Long, n: Int, t: Int, y: Long, alpha: Long, iteration: Long, opts: Array[Long], ystar: Long, v: Long, k: Long, status: Long): Unit
   @native def svParams(h: Long, n: Int, t: Int, alpha: Long, svIn: Long, phiUpdate: Int, literal: Int, phiA: Double, phiB: Double, muMean: Double, muSd: Double, sigmaShape: Double, sigmaScale: Double, propLambda: Double, propTau: Double, iteration: Long, opts: Array[Long], svOut: Long, accepted: Long, status: Long): Unit
+  /** the OU stochastic-volatility sampler's parameter step after ouFfbs (stepOu): Metropolis moves of phi, sigma, mu; the prior, the Beta proposal's (lambda, tau) and the walks' standard deviations as scalars in dlm_sv_ou_prior's order; accepted is [N][3] */
+  @native def svOuParams(h: Long, n: Int, t: Int, times: Long, alpha: Long, svIn: Long, literal: Int, phiA: Double, phiB: Double, muMean: Double, muSd: Double, sigmaShape: Double, sigmaScale: Double, propLambda: Double, propTau: Double, deltaSigma: Double, deltaMu: Double, iteration: Long, opts: Array[Long], svOut: Long, accepted: Long, status: Long): Unit
   @native def statsPool(h: Long, stats: Long, n: Int, l: Int, pooled: Long, opts: Array[Long]): Unit
   @native def commUniqueId(): Array[Byte]
   @native def commInitRank(h: Long, nranks: Int, rank: Int, id: Array[Byte]): Unit
