@@ -150,6 +150,7 @@ struct dlm_engine {
   hipEvent_t cov_ev[2] = {nullptr, nullptr};
   hipEvent_t rng_gate = nullptr;  // 16 <= d <= 48, records-free shared-factor FFBS: the end of the batch's forward pass, behind which the normals start
   hipEvent_t cov_ev2 = nullptr;   // behind the zero series' filter of a shared-factor table (its steady gain and settle step)
+  hipEvent_t rts_ev = nullptr;    // behind the shared RTS tables (start_rts_tables): what the backward kernels wait for; the broadcast of S_t runs on behind it
   // work of the CURRENT call is (or may be) in flight on the auxiliary streams and e->stream does not depend on it yet: set by aux_fork,
   // cleared by join_cov / join_rng / drain_all (the rules are written at aux_fork)
   bool cov_busy = false, rng_busy = false;
@@ -559,6 +560,7 @@ int ensure_cov_stream(dlm_engine* e) {
     HIP_TRY(e, hipStreamCreateWithPriority(&e->cov_stream, hipStreamNonBlocking, hi));
     for (auto& ev : e->cov_ev) HIP_TRY(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     HIP_TRY(e, hipEventCreateWithFlags(&e->cov_ev2, hipEventDisableTiming));
+    HIP_TRY(e, hipEventCreateWithFlags(&e->rts_ev, hipEventDisableTiming));
   }
   return DLM_OK;
 }
@@ -625,6 +627,11 @@ int start_rts_tables(dlm_engine* e, const KArgs& k, dlm::RtsTabs& tb) {
   // Behind a table run that ran: its key and "valid".  An error exit from here on leaves a complete set (every exit path joins the stream),
   // one before it leaves the set invalid.
   HIP_TRY(e, dlm::launch_rts_key_commit(k, e->sparse_k, e->sp_dev, keep, no_reuse, e->cov_stream));
+  // The tables stand: the backward kernels of the call wait for this point, not for the end of the stream.  Behind it S_t goes into the smoothed
+  // records of the series the tables serve (k_rts_broadcast) -- on a hit the two one-wave kernels above return at once and it runs beside the
+  // forward pass, on a miss beside the backward kernels.  The call joins the stream behind those (every other exit path: AuxScope).
+  HIP_TRY(e, hipEventRecord(e->rts_ev, e->cov_stream));
+  HIP_TRY(e, dlm::launch_rts_broadcast(k, e->route, tb, e->cov_stream));
   return DLM_OK;
 }
 int ensure_shared(dlm_engine* e, const KArgs& k, dlm::CovTabs& tb, bool with_backward) {
@@ -779,6 +786,7 @@ void dlm_engine_destroy(dlm_engine* e) {
   if (e->rng_stream) (void)hipStreamDestroy(e->rng_stream);
   for (auto& ev : e->cov_ev) if (ev) (void)hipEventDestroy(ev);
   if (e->cov_ev2) (void)hipEventDestroy(e->cov_ev2);
+  if (e->rts_ev) (void)hipEventDestroy(e->rts_ev);
   if (e->rng_gate) (void)hipEventDestroy(e->rng_gate);
   if (e->cov_stream) (void)hipStreamDestroy(e->cov_stream);
   if (e->counters) (void)hipFree(e->counters);
@@ -1320,7 +1328,8 @@ int dlm_filter_smooth_batch(dlm_engine* e, const dlm_model_desc* model,
   // that does not take the filtered records gets them written to the engine's workspace, dense: the mean kernel reads their first 128 bytes).
   const bool q1 = (k.flags & DLM_OPT_SMOOTHER_COMPAT_Q1) != 0;
   const bool rts_shared = fast_shape_ok(k) && e->sparse_k > 0 && !use_lane(k) && !k.packed && !(k.flags & DLM_OPT_SHARED_COV) &&
-                          (q1 ? !fused_fast : fast_smoother_ok(e, k)) && dlm::rts_shared_eligible(k, !q1);
+                          (q1 ? !fused_fast : fast_smoother_ok(e, k)) && dlm::rts_shared_eligible(k, !q1) &&
+                          ((uintptr_t)k.smooth & 15) == 0;   // (the two writers of a smoothed record split it by 16-byte pieces and 128-byte lines)
   // (textbook: the series with a missing observation keep the information-form kernel, k_smoother_sp16, and the forward pass its side records for
   //  them -- the RTS kernel per series is five times slower; literal Q1 has only that kernel)
   if (!filt) {   // smoothed moments only: the filtered records stay in an engine workspace, packed on the structured path
@@ -1344,7 +1353,7 @@ int dlm_filter_smooth_batch(dlm_engine* e, const dlm_model_desc* model,
     return st.finish(opts->flags & DLM_OPT_ASYNC);
   }
   if ((rc = run_filter(e, k, fused_fast))) return rc;
-  if (rts_shared && (rc = join_cov(e))) return rc;   // the tables (in front of the timing mark: the backward time is the mean kernel's)
+  if (rts_shared) HIP_TRY(e, hipStreamWaitEvent(e->stream, e->rts_ev, 0));   // the tables (in front of the timing mark: the backward time is the mean kernel's and what the broadcast of S_t has left)
   if ((rc = mark(e, 1))) return rc;
   k.filt_in = k.filt;
   if (rts_shared) {
@@ -1357,6 +1366,7 @@ int dlm_filter_smooth_batch(dlm_engine* e, const dlm_model_desc* model,
       HIP_TRY(e, dlm::launch_sparse16_smoother(kg, e->sparse_k, e->sp_dev, e->side, e->stream));
     }
   } else if ((rc = run_smoother(e, k, fused_fast))) return rc;
+  if (rts_shared && (rc = join_cov(e))) return rc;   // the broadcast of S_t
   if ((rc = mark(e, 2))) return rc;
   return st.finish(opts->flags & DLM_OPT_ASYNC);
 }

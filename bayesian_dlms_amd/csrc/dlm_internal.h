@@ -288,6 +288,9 @@ hipError_t launch_rts_shared_cov(const KArgs& a, int K, const SparseT* tabs_dev,
 hipError_t launch_rts_shared_tables(const KArgs& a, int K, const SparseT* tabs_dev, const RtsTabs& tb, const int* gate, hipStream_t s);
 hipError_t launch_rts_shared_mark(const KArgs& a, unsigned char* route, const RtsTabs& tb, hipStream_t s);   // KArgs::route of the call from its observations; tb.gaps, tb.skip
 hipError_t launch_rts_shared_means(const KArgs& a, int K, const SparseT* tabs_dev, const RtsTabs& tb, bool own_rts, hipStream_t s);
+// behind launch_rts_key_commit on its stream: S_t of the tables into a.smooth for every series that route leaves to them (k_rts_broadcast); the mean
+// kernel of launch_rts_shared_means writes the lines that hold s_t
+hipError_t launch_rts_broadcast(const KArgs& a, const unsigned char* route, const RtsTabs& tb, hipStream_t s);
 
 // the same for 16 <= d <= 48 (dlm_wave48.hip): rows of 64 x (4 DT^2 + 16 DT) doubles, per lane [ J^T tiles | row `lane` of L ]
 bool wave48_sampler_shared_model_ok(const KArgs& a);

@@ -157,7 +157,7 @@ constexpr int SF_AHEAD = 8;                // the filtered means are requested t
 // shared factors of the RTS smoother (k_smoother_rts16<EXP>, k_mean_rts16): a row of RtsTabs::jrows
 constexpr int RJ_ENT = 18;                 // 144 bytes per component: sixteen lanes' 16-byte LDS reads fall into distinct banks
 constexpr int RJ_ROW = 16 * RJ_ENT;
-constexpr int RS_SLOT = 1936;              // LDS bytes of a record slot: a record of d = 15 is 1920 bytes, + 16
+constexpr int RT_SLOT = 384;               // LDS bytes of a table slot of k_mean_rts16: the first 256 bytes of row t, then the last 128 of row t - 1
 // Stretches: steps t at the top of one start from scratch (k_sampler_sp16, every series).  32 steps long -- and 16 below step SF_SHORT_END, where
 // the filtered covariance of a typical model is still moving and every step of a stretch is computed in full: the longest stretch is what the
 // draw kernel of a shared-factor call waits for (C3: the table 1.24 -> 0.7 ms, no longer behind the forward mean kernel).
@@ -1015,18 +1015,37 @@ __global__ __launch_bounds__(64) void k_smoother_rts16(KArgs a, const Tab* __res
 // in the operations of k_smoother_rts16, one for one (the gather of G in table order, matTvec's four chains and their (0 + 1) +
 // (2 + 3) sum): the records are bit for bit those of the per-series kernel.  Column c of J^T lives in registers and is replaced
 // where the table has a row for the step (RtsTabs::need: a full step of the table run; the others reuse J as the per-series kernel
-// does); J rows and S_t records travel two steps ahead by LDS DMA from L2, the four series' filtered means SF_AHEAD steps ahead
-// from the heads of their filter records; a record leaves as 16-byte pieces: the table's S_t with s_t patched into the first d doubles.
+// does); J rows travel two steps ahead by LDS DMA from L2, the four series' filtered means SF_AHEAD steps ahead from the heads of
+// their filter records.
 //   row t of RtsTabs::jrows (RJ_ROW doubles): per component c < d  [ J_t^T[0..15][c] | 2 pad ]
-// NP: store instructions per step (64-lane groups of 16-byte pieces covering four records, rounded up to 2, 4, 6, 8);
-// NRS / NRJ: DMA instructions per S_t record / per J row -- exact, the waits below count them.
+// S_t is 93 % of a smoothed record and does not depend on the data: k_rts_broadcast below writes it from registers, beside the
+// forward pass, and this kernel writes only what holds s_t.  Who writes which 16-byte piece of a served series' records
+// (rts_head_piece; measured by tools/micro/rts_broadcast.hip, profiles/r12_notes.md: a line that two kernels each write in part
+// costs the writer half its rate, a line written whole by either costs nothing):
+//   records of 256 bytes and more (d >= 6): this kernel writes, per step, the one or two 128-byte lines that the first 128 bytes
+//     of record t lie in -- the tail of S_{t-1}, s_t, the start of S_t -- clipped to the series' own records; the broadcast every
+//     other line.  The lines of two steps cannot meet: their heads are 128 bytes and more apart.
+//   shorter records: this kernel the first 128 bytes of a record, the broadcast the rest.
+// One store instruction per step: lane 16 j + c piece c of series j's lines.  The table travels two steps ahead as one DMA of 24
+// pieces: the first 256 bytes of row t (doubles d .. 15 of them complete the head) and the last 128 of row t - 1.
+// NRJ: DMA instructions per J row -- exact, the waits below count them.  NP, NRS (the stores and DMAs per S_t record of the kernel
+// that assembled whole records) no longer enter the code: they name the d band of the instantiation, as the case matrix of
+// tests/counted_waits_cases.py lists them.
 // ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool rts_split_lines(int recb) { return recb >= 256; }
+// the piece at byte o of a record whose first byte has address = ph mod 128: is it k_mean_rts16's?  (last: record T, no head follows)
+__device__ __forceinline__ bool rts_head_piece(int o, int ph, int recb, bool lines, bool last) {
+  if (!lines) return o < 128;
+  const int ls = o - ((ph + o) & 127);               // where the piece's line starts, relative to the record
+  return ls < 128 || (!last && ls + 128 > recb);     // the line meets this record's head, or the next one's
+}
 #ifndef DLM_RTS_STORE_AUX
 #define DLM_RTS_STORE_AUX 2   // nt: the records are written once and read by nobody in this call; non-temporal stores leave the table rows and the means in L2
 #endif
 template <int K, int NP, int NRS, int NRJ>
 __global__ __launch_bounds__(64, 3) void k_mean_rts16(KArgs a, const SparseT* __restrict__ sp, RtsTabs tb) {
-  __shared__ __attribute__((aligned(16))) double lds[2 * 64 + 2 * (RS_SLOT / 8) + 2 * RJ_ROW + SF_AHEAD * 64];
+  static_assert(NP >= 2 && NRS >= 1, "the d band (launch_mean_rts)");
+  __shared__ __attribute__((aligned(16))) double lds[2 * 64 + 2 * (RT_SLOT / 8) + 2 * RJ_ROW + SF_AHEAD * 64];
   const int lane = threadIdx.x, j = lane >> 4, c = lane & 15;
   const int n0 = 4 * blockIdx.x;
   if (n0 >= a.N) return;
@@ -1045,7 +1064,7 @@ __global__ __launch_bounds__(64, 3) void k_mean_rts16(KArgs a, const SparseT* __
   if (deadmask == 0xfu) return;
   double* vU = lds;            // s_{t+1} - a+   [4][16]
   double* vH = vU + 64;        // the first 16 doubles of each series' smoothed record
-  char* ring = (char*)(vH + 64);                    // two S_t slots, two J slots, then the slots of the means
+  char* ring = (char*)(vH + 64);                    // two table slots, two J slots, then the slots of the means
   const int d = a.d, T = a.T, rec = d + d * d, recb = rec * 8;
   const bool vc = c < d;
   int idx[K];
@@ -1058,23 +1077,27 @@ __global__ __launch_bounds__(64, 3) void k_mean_rts16(KArgs a, const SparseT* __
   const i4 rst = rsrc_words(tb.srec, (unsigned)sbytes);
   const __amdgpu_buffer_rsrc_t rout = mk_rsrc((char*)a.smooth + (size_t)n0 * sbytes, (size_t)nser * sbytes);
   const int mvoff = (lane < 32 && (lane >> 3) < nser) ? (int)((size_t)(lane >> 3) * sbytes) + (lane & 7) * 16 : OOB;   // 16 doubles from the head of each record
-  const unsigned sring_lds = lds_addr_of(ring), jring_lds = sring_lds + 2 * RS_SLOT, mring_lds = jring_lds + 2 * (RJ_ROW * 8);
+  const unsigned sring_lds = lds_addr_of(ring), jring_lds = sring_lds + 2 * RT_SLOT, mring_lds = jring_lds + 2 * (RJ_ROW * 8);
   const unsigned vH_lds = lds_addr_of(vH);
-  const int npc = rec / 2;                           // 16-byte pieces of a record
   const int nj16 = d * (RJ_ENT / 2);                 // ... of a J row that travel
   auto dma_means = [&](unsigned lds_addr, int soff) {
     lds_addr = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr);
     soff = __builtin_amdgcn_readfirstlane(soff);
     if (lane < 32) lds_dma_issue(rmean, lds_addr, mvoff, soff);   // 4 x 8 pieces; the other lanes' LDS destinations lie beyond the slot
   };
-  unsigned psrc[NP];
-  int pdst[NP];
-#pragma unroll
-  for (int k = 0; k < NP; ++k) {
-    const int q = 64 * k + lane, sj = q / npc, pp = q - sj * npc;
-    pdst[k] = (sj < nser && !((deadmask >> (sj & 3)) & 1u)) ? (int)((size_t)sj * sbytes) + pp * 16 : OOB;
-    psrc[k] = pp < 8 ? (0x80000000u | (unsigned)((16 * (sj & 3) + 2 * pp) * 8)) : (unsigned)(pp * 16);
-  }
+  // the table's part of a step: relative to row t - 1, so that one descriptor offset serves both rows (t = 0 has no row in front)
+  const int tvoff = lane < 16 ? (lane * 16 < recb ? recb + lane * 16 : OOB) : (lane < 24 && recb >= 128 ? recb - 128 + (lane - 16) * 16 : OOB);
+  const int tvoff0 = (lane < 16 && lane * 16 < recb) ? lane * 16 : OOB;
+  auto dma_row = [&](unsigned lds_addr, int t) {
+    lds_addr = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr);
+    const int soff = __builtin_amdgcn_readfirstlane((t > 0 ? t - 1 : 0) * recb);
+    const int vo = t > 0 ? tvoff : tvoff0;
+    if (lane < 24) lds_dma_issue(rst, lds_addr, vo, soff);
+  };
+  // the store: piece c of the lines of series j (rts_head_piece's rule from the side of the head: the lines that meet [0, 128) of record t)
+  const bool lines = rts_split_lines(recb);
+  const int q16 = 16 * c, jbase = (int)((size_t)j * sbytes), phstep = lines ? (recb & 127) : 0;
+  int ph = lines ? (int)(((unsigned long long)a.smooth + (unsigned long long)(n0 + j) * sbytes + (unsigned long long)T * recb) & 127ull) : 0;   // of record t, from T down
   const unsigned ptd = (unsigned)(c * 8);            // double c of the S_t record: what the head of a record holds beyond the mean
   const unsigned char* need = tb.need;
 
@@ -1090,24 +1113,24 @@ __global__ __launch_bounds__(64, 3) void k_mean_rts16(KArgs a, const SparseT* __
 #pragma unroll
     for (int k = 0; k < 8; ++k) { Jc[2 * k] = q[k][0]; Jc[2 * k + 1] = q[k][1]; }   // (a lane beyond d holds component 0's: finite, and what it computes is never used)
   };
-  // the record of step t: the head from vH, the rest from the S_t slot; then the slots of step t are free for step t - 2
+  // the lines of step t: the head from vH, the bytes around it from the table slot; then the slots of step t are free for step t - 2
   auto emit = [&](int t, unsigned sslot, unsigned jslot, unsigned mslot, bool nd2) {
-    d2 pc[NP];
-#pragma unroll
-    for (int k = 0; k < NP; ++k) pc[k] = lds_read128((psrc[k] & 0x80000000u) ? vH_lds + (psrc[k] & 0x7fffffffu) : sslot + psrc[k]);
-    lds_wait<NP>(pc);
+    const int off = q16 - ph;                       // of the piece inside record t: < 0 the tail of S_{t-1}, < 128 the head, else S_t
+    d2 pc = lds_read128(off < 0 ? sslot + RT_SLOT + off : (off < 128 ? vH_lds + 128 * j + off : sslot + off));
+    lds_wait(pc);
     dma_means(mslot, (t > SF_AHEAD ? t - SF_AHEAD : 0) * recb);
     if (nd2) lds_dma<NRJ>(rjt, jslot, (t - 2) * (RJ_ROW * 8), lane, nj16);
-    lds_dma<NRS>(rst, sslot, (t > 1 ? t - 2 : 0) * recb, lane, npc);
-    const int so = t * recb;
-#pragma unroll
-    for (int k = 0; k < NP; ++k) bst128<DLM_RTS_STORE_AUX>(rout, pdst[k], so, pc[k]);
+    dma_row(sslot, t > 1 ? t - 2 : 0);
+    const int x = t * recb + off;                   // ... from the series' first record: in front of it, the lines are not this series'
+    const bool on = !dead && x >= 0 && q16 < (lines ? (ph ? 256 : 128) : (recb < 128 ? recb : 128));
+    bst128<DLM_RTS_STORE_AUX>(rout, on ? jbase + x : OOB, 0, pc);
+    ph = (ph - phstep) & 127;
   };
 
-  // requests: the means of steps T .. T - SF_AHEAD + 1, the S_t records T and T - 1, the J row of step T - 1 (its first step is a full one)
+  // requests: the means of steps T .. T - SF_AHEAD + 1, the table's part of steps T and T - 1, the J row of step T - 1 (its first step is a full one)
   for (int k = 0; k < SF_AHEAD; ++k) { const int tk = T - k > 0 ? T - k : 0; dma_means(mring_lds + ((T - k) & (SF_AHEAD - 1)) * 512, tk * recb); }
-  lds_dma<NRS>(rst, sring_lds + (T & 1) * RS_SLOT, T * recb, lane, npc);
-  lds_dma<NRS>(rst, sring_lds + ((T - 1) & 1) * RS_SLOT, (T - 1) * recb, lane, npc);
+  dma_row(sring_lds + (T & 1) * RT_SLOT, T);
+  dma_row(sring_lds + ((T - 1) & 1) * RT_SLOT, T - 1);
   // need[t], need[t - 1], need[t - 2] as the loop goes down: bit (s & 63) of the mask of s's block of 64 steps
   unsigned long long nmask = 0;
   auto need_of = [&](int s_) -> bool {
@@ -1122,7 +1145,7 @@ __global__ __launch_bounds__(64, 3) void k_mean_rts16(KArgs a, const SparseT* __
   {   // s_T = m_T, S_T = C_T (Smoothing.scala:59-61): the table's record T
     vm_wait<0>();
     wave_sync();
-    const unsigned sslot = sring_lds + (T & 1) * RS_SLOT, mslot = mring_lds + (T & (SF_AHEAD - 1)) * 512;
+    const unsigned sslot = sring_lds + (T & 1) * RT_SLOT, mslot = mring_lds + (T & (SF_AHEAD - 1)) * 512;
     double mr = lds_read64<0>(mslot + lane * 8), td = lds_read64<0>(sslot + ptd);
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(mr), "+v"(td)::"memory");
     sc = vc ? mr : 0.0;
@@ -1133,11 +1156,11 @@ __global__ __launch_bounds__(64, 3) void k_mean_rts16(KArgs a, const SparseT* __
   for (int t = T - 1; t >= 0; --t) {
     nd0 = nd1; nd1 = nd2; nd2 = need_of(t - 2);
     // A step issues, in this order: the request for the means (SF_AHEAD steps ahead), for a J row (two steps ahead, when it exists), for
-    // an S_t record (two steps ahead), its NP stores.  Operations younger than the request for record t (issued by step t + 2): that step's
-    // stores, then step t + 1: means, J row t - 1 (when it exists), record t - 1, stores.  The J row of step t is older than its record, the
-    // means older still.  (Step T - 1: everything it reads was waited for before step T.)
-    if (nd1) vm_wait<2 * NP + 1 + NRS + NRJ>(); else vm_wait<2 * NP + 1 + NRS>();
-    const unsigned sslot = sring_lds + (t & 1) * RS_SLOT, jslot = jring_lds + (t & 1) * (RJ_ROW * 8), mslot = mring_lds + (t & (SF_AHEAD - 1)) * 512;
+    // the table's part (two steps ahead), its one store.  Operations younger than the request for the table's part of step t (issued by step
+    // t + 2): that step's store, then step t + 1: means, J row t - 1 (when it exists), the table's part of t - 1, store.  The J row of step t is
+    // older than its table part, the means older still.  (Step T - 1: everything it reads was waited for before step T.)
+    if (nd1) vm_wait<4 + NRJ>(); else vm_wait<4>();
+    const unsigned sslot = sring_lds + (t & 1) * RT_SLOT, jslot = jring_lds + (t & 1) * (RJ_ROW * 8), mslot = mring_lds + (t & (SF_AHEAD - 1)) * 512;
     double mr = lds_read64<0>(mslot + lane * 8), td = lds_read64<0>(sslot + ptd);
     double mg[K];
 #pragma unroll
@@ -1170,6 +1193,41 @@ __global__ __launch_bounds__(64, 3) void k_mean_rts16(KArgs a, const SparseT* __
   if (!dead && c == 0) {
     const int sj = stz | (((badl >> (16 * j)) & 0xffffull) ? DLM_ST_NONFINITE : 0);
     if (a.status && sj) atomicOr(&a.status[n], sj);
+  }
+}
+
+// The other pieces (rts_head_piece): S_t of the table into the records of every series the tables serve.  Wave w: row t = w mod (T + 1)
+// -- the four waves of a block write adjacent records of the same series -- and the series [nb, ne) of chunk w / (T + 1).  The row's
+// pieces behind byte 128 sit in registers (at most 112: d = 15); the loop over the series loads only the routes, 64 series at a time,
+// and waits for nothing else.  Stores with the default policy: measured faster than nt for whole lines (profiles/r12_notes.md).
+// skip: RtsTabs::skip, no tables in this call.
+__global__ __launch_bounds__(256) void k_rts_broadcast(const double* __restrict__ srec, double* smooth, const unsigned char* __restrict__ route,
+                                                       const int* __restrict__ skip, int N, int T, int d, int nch) {
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+  if (w >= (T + 1) * nch || *skip != 0) return;
+  const int t = w % (T + 1), ch = w / (T + 1);
+  const int per = (N + nch - 1) / nch, nb = ch * per, ne = nb + per < N ? nb + per : N;
+  const int recb = (d + d * d) * 8;
+  const bool lines = rts_split_lines(recb), last = t == T;
+  const size_t sbytes = (size_t)(T + 1) * recb;
+  d2 pc[2];
+  int po[2];
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int o = 128 + 16 * (64 * k + lane);
+    po[k] = o < recb ? o : -1;
+    pc[k] = d2{0.0, 0.0};
+    if (o < recb) pc[k] = *(const d2*)((const char*)srec + (size_t)t * recb + o);
+  }
+  unsigned long long routed = 0;
+  for (int n = nb; n < ne; ++n) {
+    const int i = (n - nb) & 63;
+    if (i == 0) routed = __ballot(n + lane < ne && route[n + lane] != 0);
+    if ((routed >> i) & 1ull) continue;             // a series with a gap: its per-series smoother writes its whole records
+    const __amdgpu_buffer_rsrc_t r = mk_rsrc((char*)smooth + (size_t)n * sbytes, sbytes);
+    const int ph = (int)(((unsigned long long)smooth + (unsigned long long)n * sbytes + (unsigned long long)t * recb) & 127ull);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) bst128(r, (po[k] >= 0 && !rts_head_piece(po[k], ph, recb, lines, last)) ? po[k] : OOB, t * recb, pc[k]);
   }
 }
 
@@ -1361,12 +1419,22 @@ hipError_t launch_rts_shared_tables(const KArgs& a, int K, const SparseT* tabs_d
 template <int K>
 static hipError_t launch_mean_rts(const KArgs& a, const SparseT* sp, const RtsTabs& tb, hipStream_t s) {
   const dim3 grid((a.N + 3) / 4), blk(64);
-  // (NP, NRS, NRJ) -- store / DMA instructions per step: see k_mean_rts16 -- for d <= 7, <= 10, <= 13, 14, 15
+  // (NP, NRS, NRJ) -- the d band and the DMA instructions per J row: see k_mean_rts16 -- for d <= 7, <= 10, <= 13, 14, 15
   constexpr int shape[5][3] = {{2, 1, 1}, {4, 1, 2}, {6, 2, 2}, {8, 2, 2}, {8, 2, 3}};
   const int d = a.d;
   return pick<0, 1, 2, 3, 4>(d <= 7 ? 0 : d <= 10 ? 1 : d <= 13 ? 2 : d == 14 ? 3 : 4, [&](auto c) {
     return launch(s16::k_mean_rts16<K, shape[c()][0], shape[c()][1], shape[c()][2]>, grid, blk, 0, s, a, sp, tb);
   });
+}
+// S_t into the smoothed records of the series that the tables serve (a.smooth, route as launch_rts_shared_mark left it): behind the table run
+// on its stream, beside the forward pass.  Two waves per SIMD of a 256-CU device is where the writer reaches its rate; more change nothing.
+hipError_t launch_rts_broadcast(const KArgs& a, const unsigned char* route, const RtsTabs& tb, hipStream_t s) {
+  if (!route || !a.smooth || a.d < 1 || a.d > 15) return hipErrorInvalidValue;
+  const long long rows = (long long)a.T + 1;
+  long long nch = (2048 + rows - 1) / rows;
+  if (nch > a.N) nch = a.N;
+  if (nch < 1) nch = 1;
+  return launch(s16::k_rts_broadcast, dim3((unsigned)((rows * nch + 3) / 4)), dim3(256), 0, s, (const double*)tb.srec, a.smooth, route, (const int*)tb.skip, a.N, a.T, a.d, (int)nch);
 }
 // route [N]: the series with a missing observation -- or, where more than half of them have one, every series (tb.skip: no tables)
 hipError_t launch_rts_shared_mark(const KArgs& a, unsigned char* route, const RtsTabs& tb, hipStream_t s) {
