@@ -1067,6 +1067,11 @@ __global__ __launch_bounds__(64) void k_svd_sampler(KArgs a, const double* __res
     if (a.w_tstride) {   // the step from record t uses W_t, the transition into observation t (DlmFsvSystem.scala:196-205)
       if (sqrt_svd<NM>(lane, d, W + (size_t)t * a.w_tstride, !(a.flags & DLM_OPT_SVD_SAMPLER_Q9), L.sWb, stack, stl, L.V, L.sig)) st |= DLM_ST_NOCONV;
     }
+    // The transition into record t + 1 has covariance W dt_t (as the filter's time update has it), so the consistent form takes
+    // sqrtInv(W) / sqrt(dt_t).  SvdSampler.step uses ps.w unscaled (SvdSampler.scala:19-26): the literal mode keeps that, and dt = 0
+    // (no advance) stays as it was.  On a regular grid both factors are exactly 1.
+    const bool scale_dt = !(a.flags & DLM_OPT_SVD_SAMPLER_Q9) && dt != 0.0;
+    const double isdt = scale_dt ? 1.0 / sqrt(dt) : 1.0, idt = scale_dt ? 1.0 / dt : 1.0;
     // a_{t+1} = G m_t ; tmp = sqrtWb G
     for (int i = lane; i < d; i += 64) {
       double s = 0.0;
@@ -1077,7 +1082,7 @@ __global__ __launch_bounds__(64) void k_svd_sampler(KArgs a, const double* __res
       const int i = k % d, j = k / d;
       double s = 0.0;
       for (int l = 0; l < d; ++l) s = fma(M17(L.sWb, i, l), Gt[l + j * d], s);
-      M17(L.tmp, i, j) = s;
+      M17(L.tmp, i, j) = s * isdt;
     }
     wave_sync();
     // stack (2d x d) = [sqrtWb G uc ; diag(1/dc)]
@@ -1108,7 +1113,7 @@ __global__ __launch_bounds__(64) void k_svd_sampler(KArgs a, const double* __res
     wave_sync();
     for (int i = lane; i < d; i += 64) { double s = 0.0; for (int k = 0; k < d; ++k) s = fma(M17(L.sWb, i, k), u[k], s); v1[i] = s; }
     wave_sync();
-    for (int i = lane; i < d; i += 64) { double s = 0.0; for (int k = 0; k < d; ++k) s = fma(M17(L.sWb, k, i), v1[k], s); u[i] = s; }
+    for (int i = lane; i < d; i += 64) { double s = 0.0; for (int k = 0; k < d; ++k) s = fma(M17(L.sWb, k, i), v1[k], s); u[i] = s * idt; }
     wave_sync();
     for (int i = lane; i < d; i += 64) { double s = 0.0; for (int k = 0; k < d; ++k) s = fma(Gt[k + i * d], u[k], s); v1[i] = s; }
     wave_sync();

@@ -474,7 +474,8 @@ int dlm_backward_sample_batch(dlm_engine *e, const dlm_model_desc *model,
 /* ---- SVD (square-root) filter / sampler -------------------------------------------
  * Replaces SvdFilter.filterDlm (SvdFilter.scala:158-161) and SvdSampler.ffbsDlm
  * (SvdSampler.scala:79-82).  svd_rec [N][T+1][d + d + d*d] = (m_t, dc_t, uc_t) with
- * C_t = uc diag(dc^2) uc^T.  d <= 48, p <= 32 (DLM_ERR_UNSUPPORTED beyond): one wavefront per series, the
+ * C_t = uc diag(dc^2) uc^T.  The sampler's backward step uses sqrt(W)^-1 / sqrt(dt_t) (the reference's step leaves dt out: DESIGN.md 2,
+ * Q26; DLM_OPT_SVD_SAMPLER_Q9 keeps the literal factor).  d <= 48, p <= 32 (DLM_ERR_UNSUPPORTED beyond): one wavefront per series, the
  * decompositions in LDS; models with d, p <= 16 keep fourteen series per CU, larger ones one. */
 int dlm_svd_filter_batch(dlm_engine *e, const dlm_model_desc *model,
                          const dlm_params_desc *params, const double *y,

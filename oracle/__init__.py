@@ -36,8 +36,9 @@ _ip = ctypes.POINTER(ctypes.c_int)
 def lib():
     global _lib
     if _lib is None:
-        if not os.path.exists(_LIB_PATH):
-            build()
+        if not os.environ.get("DLM_ORACLE_LIB"):
+            build()      # no-op unless the default library is missing or older than dlm_oracle.c (a stale one would miss entry points).
+                         # With DLM_ORACLE_LIB set nothing is built: a missing file then fails in CDLL below, loudly
         _lib = ctypes.CDLL(_LIB_PATH)
         _lib.oracle_normal.restype = ctypes.c_double
         _lib.oracle_normal.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32]
@@ -225,13 +226,14 @@ def svd_filter(M, V, W, m0, C0, y, raw_w_q2=False):
 
 
 def svd_backward_sample(M, W, sf, z, literal_q9=True):
-    """SvdSampler (SvdSampler.scala:15-60).  W may be a [T] stream (the step from record t uses W_t)."""
+    """SvdSampler (SvdSampler.scala:15-60).  W may be a [T] stream (the step from record t uses W_t).  literal_q9=False is the
+    consistent form: sqrtInv(W) / sqrt(dt_t) on the model's grid; the literal form uses sqrt(W) unscaled, as the reference does."""
     d, T = M.d, M.T
     z = np.ascontiguousarray(z, dtype=np.float64).reshape(T + 1, d)
     theta = np.empty((T + 1, d)); h = np.empty((T + 1, d))
     dh = np.empty((T + 1, d)); uh = np.empty((T + 1, d * d))
     Wf, wts = _tv(W, d)
-    lib().oracle_svd_backward_sample_tv(d, T, _p(M.G), _pi(M.g_index), _p(Wf), ctypes.c_long(wts), _p(sf["m"]), _p(sf["dc"]),
+    lib().oracle_svd_backward_sample_dt(d, T, _p(M.G), _pi(M.g_index), _p(M.dt), _p(Wf), ctypes.c_long(wts), _p(sf["m"]), _p(sf["dc"]),
                                         _p(sf["uc"]), _p(sf["a"]), _p(z), int(bool(literal_q9)), _p(theta), _p(h), _p(dh), _p(uh))
     return {"theta": theta, "h": h, "dh": dh, "uh": uh}
 

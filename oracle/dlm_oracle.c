@@ -870,7 +870,10 @@ void oracle_svd_filter(int d, int p, int T, const double *F, long f_stride, cons
 /* ------------------------------------------------------------------ */
 /* w_tstride != 0: the backward step from record t uses W + t w_tstride (the transition into observation t),
  * as DlmFsvSystem.ffbsSvd zips ps with filtered.init (DlmFsvSystem.scala:196-205). */
-void oracle_svd_backward_sample_tv(int d, int T, const double *G, const int *g_index,
+/* dt (NULL: all 1): the transition into record t + 1 has covariance W dt_t, so the consistent form (literal_q9 == 0) takes
+ * sqrtInvSvd(W) / sqrt(dt_t); the reference's step uses ps.w unscaled (SvdSampler.scala:19-26), which the literal form keeps.
+ * dt_t = 0 (no advance) is left as it was. */
+void oracle_svd_backward_sample_dt(int d, int T, const double *G, const int *g_index, const double *dt,
                                    const double *W, long w_tstride, const double *m, const double *dc,
                                    const double *uc, const double *a, const double *z,
                                    int literal_q9, double *theta, double *h_out, double *dh_out,
@@ -904,7 +907,10 @@ void oracle_svd_backward_sample_tv(int d, int T, const double *G, const int *g_i
     const double *a1 = a + (size_t)(t + 1) * d, *thn = theta + (size_t)(t + 1) * d;
     if (w_tstride) oracle_sqrt_svd(d, W + (size_t)t * w_tstride, literal_q9 ? 0 : 1, sqrtW);
     /* root = svd([sqrtW * g * uc ; diag(1/dc)]) : SvdSampler.scala:19-21 */
+    const double dtt = (dt && !literal_q9 && dt[t] != 0.0) ? dt[t] : 1.0;
+    const double isdt = 1.0 / sqrt(dtt);
     mm(d, d, d, sqrtW, d, 0, Gn, d, 0, t1, d);
+    for (int k = 0; k < dd; ++k) t1[k] *= isdt;
     mm(d, d, d, t1, d, 0, uct, d, 0, t2, d);
     for (int j = 0; j < d; ++j)
       for (int i = 0; i < d; ++i) {
@@ -919,6 +925,7 @@ void oracle_svd_backward_sample_tv(int d, int T, const double *G, const int *g_i
     for (int i = 0; i < d; ++i) u[i] = thn[i] - a1[i];
     mm(d, 1, d, sqrtW, d, 0, u, d, 0, v1, d);
     mm(d, 1, d, sqrtW, d, 1, v1, d, 0, v2, d);
+    for (int i = 0; i < d; ++i) v2[i] *= 1.0 / dtt;
     mm(d, 1, d, Gn, d, 1, v2, d, 0, v1, d);
     mm(d, 1, d, uh, d, 1, v1, d, 0, v2, d);
     for (int i = 0; i < d; ++i) v2[i] *= dh[i] * dh[i];
@@ -937,12 +944,21 @@ void oracle_svd_backward_sample_tv(int d, int T, const double *G, const int *g_i
   free(u); free(v1); free(v2);
 }
 
+/* The entry point without a time grid (every dt = 1), as it has always been. */
+void oracle_svd_backward_sample_tv(int d, int T, const double *G, const int *g_index,
+                                   const double *W, long w_tstride, const double *m, const double *dc,
+                                   const double *uc, const double *a, const double *z,
+                                   int literal_q9, double *theta, double *h_out, double *dh_out,
+                                   double *uh_out) {
+  oracle_svd_backward_sample_dt(d, T, G, g_index, NULL, W, w_tstride, m, dc, uc, a, z, literal_q9, theta, h_out, dh_out, uh_out);
+}
+
 void oracle_svd_backward_sample(int d, int T, const double *G, const int *g_index,
                                 const double *W, const double *m, const double *dc,
                                 const double *uc, const double *a, const double *z,
                                 int literal_q9, double *theta, double *h_out, double *dh_out,
                                 double *uh_out) {
-  oracle_svd_backward_sample_tv(d, T, G, g_index, W, 0, m, dc, uc, a, z, literal_q9, theta, h_out, dh_out, uh_out);
+  oracle_svd_backward_sample_dt(d, T, G, g_index, NULL, W, 0, m, dc, uc, a, z, literal_q9, theta, h_out, dh_out, uh_out);
 }
 
 /* ------------------------------------------------------------------ */

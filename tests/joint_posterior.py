@@ -412,6 +412,8 @@ def _build_cases():
     rng = np.random.default_rng(109)
     mat, p = c2(4)
     add("svd_c2_T4", "svd", "svd-jacobi", mat=mat, p=p, y=yc2)
+    mati, _ = c2(4, times=np.cumsum([1.0, 2.0, 0.5, 3.0]))     # an irregular grid: the backward step needs W dt_t (tests/test_gibbs_invariance_gpu.py found it missing)
+    add("svd_c2_T4_irregular", "svd", "svd-jacobi", mat=mati, p=p, y=yc2)
     mat, p = block_model(10, 3, 2, seed=12)
     y = _walk(rng, 3, 10); y[1, 4] = np.nan
     add("svd_d20_p10_T3_component_missing", "svd", "svd-jacobi", mat=mat,
