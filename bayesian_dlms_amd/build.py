@@ -13,8 +13,8 @@ FLAGS = BASE_FLAGS + ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 # dlm_wave48.hip keeps whole matrices in registers (up to the 512-register budget of a wave): its accumulators may live
 # in AGPRs, and the VGPR-form rewrite pass of this compiler crashes on it
 FILE_FLAGS = {"dlm_wave48.hip": BASE_FLAGS}
-# an object is stale when its source or any of these is newer (dlm_wave.h: the device primitives of the kernel files)
-HEADERS = [os.path.join(CSRC, "dlm_internal.h"), os.path.join(CSRC, "dlm_wave.h"), os.path.join(HERE, "..", "include", "dlm_engine.h")]
+# an object is stale when its source or any of these is newer (dlm_wave.h: the device primitives of the kernel files; dlm_draws.h: the draws of the Gibbs parameter steps)
+HEADERS = [os.path.join(CSRC, "dlm_internal.h"), os.path.join(CSRC, "dlm_wave.h"), os.path.join(CSRC, "dlm_draws.h"), os.path.join(HERE, "..", "include", "dlm_engine.h")]
 
 
 def _stale(target, deps):

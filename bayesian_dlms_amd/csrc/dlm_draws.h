@@ -1,0 +1,165 @@
+// The scalar draws of the Gibbs parameter steps (dlm_gibbs.hip, dlm_studentt.hip, dlm_sv.hip, dlm_sv_ou.hip), each defined here ONCE:
+// the Philox uniforms under a stream key, the Gamma, normal and log-uniform variates, the Beta proposal of the two stochastic-volatility
+// steps, the conjugate draw of a diagonal W, and the table of counter slots (dlm_engine.hip takes its limits on T from it).
+#pragma once
+#include "dlm_internal.h"
+
+namespace dlm {
+
+// ---- the streams ----------------------------------------------------------------------------------------------------------------
+// Counter (series lo, series hi, iteration, comp * 2048 + attempt * 2 + which) under the key (seed lo, seed hi ^ key): one stream per
+// key, each disjoint from the FFBS / simulation normals (key (seed lo, seed hi)) and from the others.  oracle/dlm_oracle.c restates the
+// GIBB stream.
+//   DLM_KEY_GIBBS     dlm_dinvgamma_step_batch: comp = component of [V diagonal (p) | W diagonal (d)]; the Student-t step draws W here too
+//   DLM_KEY_STUDENTT  dlm_studentt_step_batch: comp = t for the variance v_t, DLM_ST_SLOT_* for its scalar draws
+//   DLM_KEY_SV        dlm_sv_mixture_batch: comp = t for the mixture indicator k_t; dlm_sv_params_batch: DLM_SV_SLOT_*
+//   DLM_KEY_SVOU      dlm_sv_ou_params_batch: DLM_SVOU_SLOT_*; the OU chain's mixture call draws under DLM_KEY_SV
+constexpr unsigned DLM_KEY_GIBBS = 0x47494242u;      // "GIBB"
+constexpr unsigned DLM_KEY_STUDENTT = 0x53545544u;   // "STUD"
+constexpr unsigned DLM_KEY_SV = 0x5354564Fu;         // "STVO"
+constexpr unsigned DLM_KEY_SVOU = 0x53564F55u;       // "SVOU"
+
+// ---- the slots ------------------------------------------------------------------------------------------------------------------
+// comp is a 21-bit field (the counter word is comp * 2048 + attempt * 2 + which).  A sampler whose per-time draws take comp = t < T
+// gives its scalar draws the slots from DLM_SLOT_TOP downward, and T stays below the lowest of them: DLM_*_MAX_T is the largest T the
+// entry points admit (dlm_engine.hip).
+constexpr unsigned DLM_SLOT_TOP = 0x1FFFFFu;
+enum : unsigned {   // dlm_studentt_step_batch, DLM_KEY_STUDENTT
+  DLM_ST_SLOT_PROP_GAMMA = DLM_SLOT_TOP,        // lambda ~ Gamma(r, nu / r) of the proposal
+  DLM_ST_SLOT_POISSON = DLM_SLOT_TOP - 1,       // Poisson(lambda)
+  DLM_ST_SLOT_ACCEPT = DLM_SLOT_TOP - 2,        // the Metropolis-Hastings uniform
+  DLM_ST_SLOT_SCALE = DLM_SLOT_TOP - 3,         // s ~ Gamma
+};
+enum : unsigned {   // dlm_sv_params_batch, DLM_KEY_SV (dlm_sv_mixture_batch takes the slots t)
+  DLM_SV_SLOT_PHI = DLM_SLOT_TOP,               // phi ~ N (conjugate mode; attempt k of the rejection)
+  DLM_SV_SLOT_MU = DLM_SLOT_TOP - 1,            // mu ~ N
+  DLM_SV_SLOT_SIGMA = DLM_SLOT_TOP - 2,         // sigma^2: the Gamma of the InverseGamma
+  DLM_SV_SLOT_PROP_A = DLM_SLOT_TOP - 3,        // Beta proposal: Gamma(lambda phi + tau)
+  DLM_SV_SLOT_PROP_B = DLM_SLOT_TOP - 4,        //                Gamma(lambda (1 - phi) + tau)
+  DLM_SV_SLOT_ACCEPT = DLM_SLOT_TOP - 5,        // the Metropolis-Hastings uniform
+};
+enum : unsigned {   // dlm_sv_ou_params_batch, DLM_KEY_SVOU (no per-time draws of its own: the limit is the mixture call's)
+  DLM_SVOU_SLOT_PROP_A = DLM_SLOT_TOP,          // Beta proposal: Gamma(lambda phi + tau)
+  DLM_SVOU_SLOT_PROP_B = DLM_SLOT_TOP - 1,      //                Gamma(lambda (1 - phi) + tau)
+  DLM_SVOU_SLOT_ACC_PHI = DLM_SLOT_TOP - 2,     // phi's uniform
+  DLM_SVOU_SLOT_Z_SIGMA = DLM_SLOT_TOP - 3,     // sigma's walk
+  DLM_SVOU_SLOT_ACC_SIGMA = DLM_SLOT_TOP - 4,   // sigma's uniform
+  DLM_SVOU_SLOT_Z_MU = DLM_SLOT_TOP - 5,        // mu's walk
+  DLM_SVOU_SLOT_ACC_MU = DLM_SLOT_TOP - 6,      // mu's uniform
+};
+constexpr int DLM_ST_MAX_T = 0x1FFFFC;     // v_t takes slot t < T
+constexpr int DLM_SV_MAX_T = 0x1FFFF7;     // k_t takes slot t < T; 0x1FFFF8 and 0x1FFFF9 are kept free
+constexpr int DLM_SVOU_MAX_T = 0x1FFFF7;   // the chain's mixture call runs at the same T
+static_assert(DLM_ST_SLOT_SCALE > (unsigned)DLM_ST_MAX_T - 1, "the Student-t step's scalar slots lie above every time slot");
+static_assert(DLM_SV_SLOT_ACCEPT > (unsigned)DLM_SV_MAX_T, "the SV step's scalar slots lie above every time slot");
+static_assert(DLM_SVOU_SLOT_ACC_MU > (unsigned)DLM_SVOU_MAX_T, "the OU step's scalar slots lie above every time slot");
+
+// ---- uniforms, normals, Gammas ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void gibbs_rand(unsigned long long seed, unsigned long long series, unsigned long long iteration,
+                                           unsigned comp, unsigned attempt, unsigned which, double& u1, double& u2,
+                                           unsigned key = DLM_KEY_GIBBS) {
+  unsigned c[4] = {(unsigned)series, (unsigned)(series >> 32), (unsigned)iteration, comp * 2048u + attempt * 2u + which};
+  philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32) ^ key);
+  u1 = ((double)c[0] * 4294967296.0 + (double)c[1] + 1.0) * (1.0 / 18446744073709551616.0);   // (0, 1]
+  u2 = ((double)c[2] * 4294967296.0 + (double)c[3]) * (1.0 / 18446744073709551616.0);         // [0, 1)
+}
+
+// N(0, 1) of attempt `attempt` of a scalar slot: the Box-Muller cosine of the block's pair
+__device__ __forceinline__ double draw_normal(unsigned key, unsigned long long seed, unsigned long long series, unsigned long long it,
+                                              unsigned slot, unsigned attempt = 0u) {
+  double u1, u2;
+  gibbs_rand(seed, series, it, slot, attempt, 0u, u1, u2, key);
+  return sqrt(-2.0 * log(u1)) * cos(6.283185307179586476925286766559 * u2);
+}
+// log u, u the (0, 1] uniform of a scalar slot: what a Metropolis-Hastings move compares its log acceptance ratio with
+__device__ __forceinline__ double draw_log_uniform(unsigned key, unsigned long long seed, unsigned long long series, unsigned long long it,
+                                                   unsigned slot) {
+  double u1, u2;
+  gibbs_rand(seed, series, it, slot, 0u, 0u, u1, u2, key);
+  return log(u1);
+}
+
+// Gamma(a, 1): Marsaglia & Tsang, "A simple method for generating gamma variables" (2000); a < 1 by the u^(1/a) boost
+__device__ inline double gamma_unit(double a, unsigned long long seed, unsigned long long series, unsigned long long iteration, unsigned comp,
+                                    unsigned key = DLM_KEY_GIBBS) {
+  double boost = 1.0;
+  if (a < 1.0) {
+    double u1, u2;
+    gibbs_rand(seed, series, iteration, comp, 1023u, 0u, u1, u2, key);
+    boost = pow(u1, 1.0 / a);
+    a += 1.0;
+  }
+  const double dd = a - 1.0 / 3.0, cc = 1.0 / sqrt(9.0 * dd);
+  for (unsigned k = 0; k < 1023u; ++k) {
+    double u1, u2, w1, w2;
+    gibbs_rand(seed, series, iteration, comp, k, 0u, u1, u2, key);
+    const double x = sqrt(-2.0 * log(u1)) * cos(6.283185307179586476925286766559 * u2);
+    double v = 1.0 + cc * x;
+    if (v <= 0.0) continue;
+    v = v * v * v;
+    gibbs_rand(seed, series, iteration, comp, k, 1u, w1, w2, key);
+    if (log(w1) < 0.5 * x * x + dd - dd * v + dd * log(v)) return dd * v * boost;
+  }
+  return dd * boost;   // unreachable in practice (acceptance > 95 % per attempt)
+}
+
+// ---- the Beta proposal of phi (samplePhi, StochasticVolatility.scala:189-202; samplePhiOu of stepOu) ------------------------------
+// phi' ~ Beta(lambda phi + tau, lambda (1 - phi) + tau) as ga / (ga + gb).  Both functions are called by the WHOLE wave: the two Gammas
+// are drawn on lanes 0 and 1, the six lgamma values of the Hastings ratio are made side by side on lanes 0..5, and the shuffles leave
+// every lane with every member.  lq_fwd / lq_back are returned apart: the callers add them to their target in their own order.
+struct BetaProposal {
+  double phi0, phip;       // the current value and the proposal
+  double A0, B0, A1, B1;   // the proposal's parameters at phi0 and at phip
+  double G[6];             // lgamma of A0, B0, A0 + B0, A1, B1, A1 + B1
+  bool ok;                 // phip lies inside (0, 1) (one that rounds to 0 or 1 is rejected)
+
+  // `bad`: the series' input is unusable -- nothing is drawn, and the caller uses no member
+  __device__ __forceinline__ void draw(int lane, double phi, double lam, double tau, bool bad, unsigned key, unsigned long long seed,
+                                       unsigned long long series, unsigned long long it, unsigned slot_a, unsigned slot_b) {
+    phi0 = phi;
+    A0 = lam * phi0 + tau; B0 = lam * (1.0 - phi0) + tau;
+    double g = 1.0;
+    if (lane < 2 && !bad) g = gamma_unit(lane == 0 ? A0 : B0, seed, series, it, lane == 0 ? slot_a : slot_b, key);
+    const double ga = __shfl(g, 0, 64), gb = __shfl(g, 1, 64);
+    phip = ga / (ga + gb);
+    ok = phip > 0.0 && phip < 1.0;
+    A1 = lam * phip + tau; B1 = lam * (1.0 - phip) + tau;
+  }
+  __device__ __forceinline__ void lgammas(int lane) {
+    double garg = 1.0;
+    switch (lane) {
+      case 0: garg = A0; break;  case 1: garg = B0; break;  case 2: garg = A0 + B0; break;
+      case 3: garg = A1; break;  case 4: garg = B1; break;  case 5: garg = A1 + B1; break;
+      default: break;
+    }
+    const double lg = lgamma(garg);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) G[j] = __shfl(lg, j, 64);
+  }
+  __device__ __forceinline__ double lq_fwd() const {    // log q(phi' | phi)
+    return G[2] - G[0] - G[1] + (A0 - 1.0) * log(phip) + (B0 - 1.0) * log(1.0 - phip);
+  }
+  __device__ __forceinline__ double lq_back() const {   // log q(phi | phi')
+    return G[5] - G[3] - G[4] + (A1 - 1.0) * log(phi0) + (B1 - 1.0) * log(1.0 - phi0);
+  }
+};
+
+// ---- the conjugate InverseGamma draw of a diagonal variance (GibbsSampling.sampleSystemMatrix, Gibbs.scala:56-78) ----------------------
+// InverseGamma(shape, rate).draw = rate / Gamma(shape, 1).draw on DLM_KEY_GIBBS component comp.  The kernel draws the Gamma at its ONE
+// call of gamma_unit (k_dinvgamma_step draws V there too, k_studentt_step its proposal: the lanes of a second call site would run behind
+// the first's); the rest is here, so that dlm_studentt_step_batch's W_out is dlm_dinvgamma_step_batch's by construction.
+struct InvGammaDraw { double shape, rate; unsigned comp; };
+// W_ii of a series with the FFBS statistics st = [ssy (p) | n (p) | ss (d) | T]:  InverseGamma(aw + T / 2, bw + ss_i / 2) (the shape uses
+// T), component p + i
+__device__ __forceinline__ InvGammaDraw w_draw(const double* st, int d, int p, int i, double aw, double bw) {
+  const int L = 2 * p + d + 1;
+  return InvGammaDraw{aw + 0.5 * st[L - 1], bw + 0.5 * st[2 * p + i], (unsigned)(p + i)};
+}
+// column i of the dense diagonal n x n matrix M: the draw q, whose Gamma(q.shape, 1) variate is g, on the diagonal
+__device__ __forceinline__ void store_diag_draw(double* M, int n, int i, const InvGammaDraw& q, double g) {
+  const double val = q.rate / g;
+  double* col = M + (size_t)i * n;
+  for (int k = 0; k < n; ++k) col[k] = (k == i) ? val : 0.0;
+}
+
+}  // namespace dlm

@@ -3,6 +3,7 @@
 #include "../../include/dlm_engine.h"
 #include <cstdlib>
 #include "dlm_internal.h"
+#include "dlm_draws.h"
 
 #include <rccl/rccl.h>
 
@@ -170,6 +171,18 @@ int fail(dlm_engine* e, int code, const std::string& msg) {
   if (e) e->err = msg;
   return code;
 }
+
+// the options of a call: present, and opts->mem one of the two memory spaces
+int check_opts(dlm_engine* e, const dlm_options* o) {
+  if (!o) return fail(e, DLM_ERR_ARG, "null descriptor");
+  if (o->mem != DLM_MEM_DEVICE && o->mem != DLM_MEM_HOST) return fail(e, DLM_ERR_ARG, "opts->mem");
+  return DLM_OK;
+}
+// what the entry points ask of a prior's numbers (a NaN fails both)
+bool is_finite(double x) { return x - x == 0.0; }
+bool is_positive(double x) { return x > 0.0 && is_finite(x); }
+// where the draws of a Gibbs parameter step sit in the Philox counter space
+dlm::DrawStream draw_stream(const dlm_options* o, uint64_t iteration) { return dlm::DrawStream{o->seed, o->series_offset, iteration}; }
 
 // the device checksum of a DLM_OPT_MODEL_UNCHANGED call did not match the model the engine analysed: its results are invalid
 int promise_broken(dlm_engine* e) {
@@ -1015,7 +1028,8 @@ int dlm_dinvgamma_step_batch(dlm_engine* e, int32_t d, int32_t p, int32_t N, con
                              double beta_v, double alpha_w, double beta_w, uint64_t iteration, const dlm_options* opts,
                              double* V_out, double* W_out) {
   if (!e) return DLM_ERR_ARG;
-  if (!opts || (opts->mem != DLM_MEM_DEVICE && opts->mem != DLM_MEM_HOST)) return fail(e, DLM_ERR_ARG, "opts");
+  int rc;
+  if ((rc = check_opts(e, opts))) return rc;
   if (d < 1 || p < 1 || N < 1 || !stats || !V_out || !W_out) return fail(e, DLM_ERR_ARG, "d, p, N >= 1; stats, V_out, W_out required");
   if (!(alpha_v > 0.0 && beta_v > 0.0 && alpha_w > 0.0 && beta_w > 0.0)) return fail(e, DLM_ERR_ARG, "InverseGamma priors need positive shape and scale");
   HIP_TRY(e, hipSetDevice(e->device));
@@ -1025,11 +1039,9 @@ int dlm_dinvgamma_step_batch(dlm_engine* e, int32_t d, int32_t p, int32_t N, con
   st.in(&k.stats, stats, n * L);
   st.out(&k.V, V_out, n * p * p);
   st.out(&k.W, W_out, n * d * d);
-  int rc;
   if ((rc = st.commit())) return rc;
   e->variant = "dinvgamma-step";
-  HIP_TRY(e, dlm::launch_dinvgamma_step(d, p, N, k.stats, alpha_v, beta_v, alpha_w, beta_w, opts->seed, opts->series_offset,
-                                        iteration, k.V, k.W, e->stream));
+  HIP_TRY(e, dlm::launch_dinvgamma_step(d, p, N, k.stats, alpha_v, beta_v, alpha_w, beta_w, draw_stream(opts, iteration), k.V, k.W, e->stream));
   return st.finish(opts->flags & DLM_OPT_ASYNC);
 }
 
@@ -1039,13 +1051,14 @@ int dlm_studentt_step_batch(dlm_engine* e, const dlm_model_desc* model, const do
                             double* scale_out, int32_t* nu_out, double* W_out, int32_t* accepted,
                             double* loglik, int32_t* status) {
   if (!e) return DLM_ERR_ARG;
-  if (!model || !opts || !prior) return fail(e, DLM_ERR_ARG, "null descriptor");
-  if (opts->mem != DLM_MEM_DEVICE && opts->mem != DLM_MEM_HOST) return fail(e, DLM_ERR_ARG, "opts->mem");
+  if (!model || !prior) return fail(e, DLM_ERR_ARG, "null descriptor");
+  int rc;
+  if ((rc = check_opts(e, opts))) return rc;
   const int d = model->d, T = model->T, N = model->N;
   if (d < 1 || T < 1 || N < 1 || model->p < 1) return fail(e, DLM_ERR_ARG, "d, p, T, N must be >= 1");
   if (model->p != 1) return fail(e, DLM_ERR_UNSUPPORTED, "the Student-t step is univariate (StudentTGibbs.scala reads y(0) and v(0,0)): p must be 1");
   if (d > 64) return fail(e, DLM_ERR_UNSUPPORTED, "d is limited to 64 in this build");
-  if (T > 0x1FFFFC) return fail(e, DLM_ERR_UNSUPPORTED, "T must stay below 2^21 - 4 (the Philox counter's slot field)");
+  if (T > dlm::DLM_ST_MAX_T) return fail(e, DLM_ERR_UNSUPPORTED, "T must stay below 2^21 - 4 (the Philox counter's slot field)");
   if (!model->F || (model->f_stride != 0 && model->f_stride != (int64_t)d)) return fail(e, DLM_ERR_ARG, "F required; f_stride must be 0 or d");
   const bool literal = (opts->flags & DLM_OPT_STUDENTT_LITERAL) != 0;
   if (literal && model->f_stride)
@@ -1071,13 +1084,11 @@ int dlm_studentt_step_batch(dlm_engine* e, const dlm_model_desc* model, const do
   st.inout(&k.accepted, (int*)accepted, n);
   st.out(&k.loglik, loglik, loglik ? n : 0);
   st.zeroed_out(&k.status, (int*)status, status ? n : 0);
-  int rc;
   if ((rc = st.commit())) return rc;
   k.d = d; k.T = T; k.N = N; k.f_stride = model->f_stride;
-  k.prior_nu_rate = prior->prior_nu_rate; k.prop_nu_size = prior->prop_nu_size;
-  k.prior_w_shape = prior->prior_w_shape; k.prior_w_scale = prior->prior_w_scale;
+  k.prior = *prior;
   k.literal = literal ? 1 : 0;
-  k.seed = opts->seed; k.series_offset = opts->series_offset; k.iteration = iteration;
+  k.rs = draw_stream(opts, iteration);
   e->variant = "studentt-step";
   HIP_TRY(e, dlm::launch_studentt_step(k, e->stream));
   return st.finish(opts->flags & DLM_OPT_ASYNC);
@@ -1086,9 +1097,10 @@ int dlm_studentt_step_batch(dlm_engine* e, const dlm_model_desc* model, const do
 int dlm_sv_mixture_batch(dlm_engine* e, int32_t N, int32_t T, const double* y, const double* alpha, uint64_t iteration,
                          const dlm_options* opts, double* ystar, double* v, int8_t* k, int32_t* status) {
   if (!e) return DLM_ERR_ARG;
-  if (!opts || (opts->mem != DLM_MEM_DEVICE && opts->mem != DLM_MEM_HOST)) return fail(e, DLM_ERR_ARG, "opts");
+  int rc;
+  if ((rc = check_opts(e, opts))) return rc;
   if (N < 1 || T < 2) return fail(e, DLM_ERR_ARG, "N >= 1 and T >= 2 (the reference's parameter draws throw on a single observation, StochasticVolatility.scala:220-222)");
-  if (T >= 0x1FFFF8) return fail(e, DLM_ERR_ARG, "T must stay below 2^21 - 8 (the Philox counter's slot field)");
+  if (T > dlm::DLM_SV_MAX_T) return fail(e, DLM_ERR_ARG, "T must stay below 2^21 - 8 (the Philox counter's slot field)");
   if ((long long)N * T >= (1ll << 39)) return fail(e, DLM_ERR_ARG, "N T must stay below 2^39 (one thread per element)");
   if (!y || !ystar || !v) return fail(e, DLM_ERR_ARG, "y, ystar and v are required");
   HIP_TRY(e, hipSetDevice(e->device));
@@ -1101,10 +1113,9 @@ int dlm_sv_mixture_batch(dlm_engine* e, int32_t N, int32_t T, const double* y, c
   st.out(&a.v, v, n * t);
   st.out(&a.k, (signed char*)k, k ? n * t : 0);
   st.zeroed_out(&a.status, (int*)status, status ? n : 0);
-  int rc;
   if ((rc = st.commit())) return rc;
   a.N = N; a.T = T;
-  a.seed = opts->seed; a.series_offset = opts->series_offset; a.iteration = iteration;
+  a.rs = draw_stream(opts, iteration);
   e->variant = "sv-mixture";
   HIP_TRY(e, dlm::launch_sv_mixture(a, e->stream));
   return st.finish(opts->flags & DLM_OPT_ASYNC);
@@ -1113,23 +1124,21 @@ int dlm_sv_mixture_batch(dlm_engine* e, int32_t N, int32_t T, const double* y, c
 int dlm_sv_params_batch(dlm_engine* e, int32_t N, int32_t T, const double* alpha, const double* sv_in, const dlm_sv_prior* prior,
                         uint64_t iteration, const dlm_options* opts, double* sv_out, int32_t* accepted, int32_t* status) {
   if (!e) return DLM_ERR_ARG;
-  if (!opts || !prior) return fail(e, DLM_ERR_ARG, "null descriptor");
-  if (opts->mem != DLM_MEM_DEVICE && opts->mem != DLM_MEM_HOST) return fail(e, DLM_ERR_ARG, "opts->mem");
+  if (!prior) return fail(e, DLM_ERR_ARG, "null descriptor");
+  int rc;
+  if ((rc = check_opts(e, opts))) return rc;
   if (N < 1 || T < 2) return fail(e, DLM_ERR_ARG, "N >= 1 and T >= 2 (the reference's sums throw on a single observation, StochasticVolatility.scala:220-222)");
-  if (T >= 0x1FFFF8) return fail(e, DLM_ERR_ARG, "T must stay below 2^21 - 8 (the Philox counter's slot field)");
+  if (T > dlm::DLM_SV_MAX_T) return fail(e, DLM_ERR_ARG, "T must stay below 2^21 - 8 (the Philox counter's slot field)");
   if (prior->phi_update != 0 && prior->phi_update != 1) return fail(e, DLM_ERR_ARG, "phi_update: 0 (Gaussian conjugate) or 1 (Beta-proposal Metropolis-Hastings)");
   if (prior->literal != 0 && prior->literal != 1) return fail(e, DLM_ERR_ARG, "literal: 0 or 1");
   const bool beta = prior->phi_update == 1;
   if (!alpha || !sv_in || !sv_out || (beta && !accepted)) return fail(e, DLM_ERR_ARG, "alpha, sv_in and sv_out are required (and accepted with the Beta proposal)");
-  const auto fin = [](double x) { return x - x == 0.0; };
-  if (!(prior->mu_sd > 0.0 && fin(prior->mu_sd) && fin(prior->mu_mean))) return fail(e, DLM_ERR_ARG, "the Gaussian prior of mu needs a finite mean and a positive standard deviation");
-  if (!(prior->sigma_shape > 0.0 && prior->sigma_scale > 0.0 && fin(prior->sigma_shape) && fin(prior->sigma_scale)))
-    return fail(e, DLM_ERR_ARG, "the InverseGamma prior of sigma^2 needs a positive shape and scale");
+  if (!(is_positive(prior->mu_sd) && is_finite(prior->mu_mean))) return fail(e, DLM_ERR_ARG, "the Gaussian prior of mu needs a finite mean and a positive standard deviation");
+  if (!(is_positive(prior->sigma_shape) && is_positive(prior->sigma_scale))) return fail(e, DLM_ERR_ARG, "the InverseGamma prior of sigma^2 needs a positive shape and scale");
   if (beta) {
-    if (!(prior->phi_a > 0.0 && prior->phi_b > 0.0 && fin(prior->phi_a) && fin(prior->phi_b))) return fail(e, DLM_ERR_ARG, "the Beta prior of phi needs positive a and b");
-    if (!(prior->prop_lambda > 0.0 && prior->prop_tau > 0.0 && fin(prior->prop_lambda) && fin(prior->prop_tau)))
-      return fail(e, DLM_ERR_ARG, "the Beta proposal needs positive lambda and tau");
-  } else if (!(prior->phi_b > 0.0 && fin(prior->phi_b) && fin(prior->phi_a))) {
+    if (!(is_positive(prior->phi_a) && is_positive(prior->phi_b))) return fail(e, DLM_ERR_ARG, "the Beta prior of phi needs positive a and b");
+    if (!(is_positive(prior->prop_lambda) && is_positive(prior->prop_tau))) return fail(e, DLM_ERR_ARG, "the Beta proposal needs positive lambda and tau");
+  } else if (!(is_positive(prior->phi_b) && is_finite(prior->phi_a))) {
     return fail(e, DLM_ERR_ARG, "the Gaussian prior of phi needs a finite mean and a positive standard deviation");
   }
   HIP_TRY(e, hipSetDevice(e->device));
@@ -1141,14 +1150,10 @@ int dlm_sv_params_batch(dlm_engine* e, int32_t N, int32_t T, const double* alpha
   st.out(&a.sv_out, sv_out, n * 3);
   st.inout(&a.accepted, (int*)accepted, accepted ? n : 0);
   st.zeroed_out(&a.status, (int*)status, status ? n : 0);
-  int rc;
   if ((rc = st.commit())) return rc;
   a.N = N; a.T = T;
-  a.phi_update = prior->phi_update; a.literal = prior->literal;
-  a.phi_a = prior->phi_a; a.phi_b = prior->phi_b; a.mu_mean = prior->mu_mean; a.mu_sd = prior->mu_sd;
-  a.sigma_shape = prior->sigma_shape; a.sigma_scale = prior->sigma_scale;
-  a.prop_lambda = prior->prop_lambda; a.prop_tau = prior->prop_tau;
-  a.seed = opts->seed; a.series_offset = opts->series_offset; a.iteration = iteration;
+  a.prior = *prior;
+  a.rs = draw_stream(opts, iteration);
   e->variant = "sv-params";
   HIP_TRY(e, dlm::launch_sv_params(a, e->stream));
   return st.finish(opts->flags & DLM_OPT_ASYNC);
@@ -1158,19 +1163,18 @@ int dlm_sv_ou_params_batch(dlm_engine* e, int32_t N, int32_t T, const double* ti
                            const dlm_sv_ou_prior* prior, uint64_t iteration, const dlm_options* opts, double* sv_out,
                            int32_t* accepted, int32_t* status) {
   if (!e) return DLM_ERR_ARG;
-  if (!opts || !prior) return fail(e, DLM_ERR_ARG, "null descriptor");
-  if (opts->mem != DLM_MEM_DEVICE && opts->mem != DLM_MEM_HOST) return fail(e, DLM_ERR_ARG, "opts->mem");
+  if (!prior) return fail(e, DLM_ERR_ARG, "null descriptor");
+  int rc;
+  if ((rc = check_opts(e, opts))) return rc;
   if (N < 1 || T < 2) return fail(e, DLM_ERR_ARG, "N >= 1 and T >= 2 (one informative pair of states at least)");
-  if (T >= 0x1FFFF8) return fail(e, DLM_ERR_ARG, "T must stay below 2^21 - 8 (the Philox counter's slot field)");
+  if (T > dlm::DLM_SVOU_MAX_T) return fail(e, DLM_ERR_ARG, "T must stay below 2^21 - 8 (the Philox counter's slot field)");
   if (prior->literal != 0 && prior->literal != 1) return fail(e, DLM_ERR_ARG, "literal: 0 or 1");
   if (!times || !alpha || !sv_in || !sv_out || !accepted) return fail(e, DLM_ERR_ARG, "times, alpha, sv_in, sv_out and accepted are required");
-  const auto fin = [](double x) { return x - x == 0.0; };
-  const auto pos = [&](double x) { return x > 0.0 && fin(x); };
-  if (!(pos(prior->phi_a) && pos(prior->phi_b))) return fail(e, DLM_ERR_ARG, "the Beta prior of phi needs positive a and b");
-  if (!(pos(prior->mu_sd) && fin(prior->mu_mean))) return fail(e, DLM_ERR_ARG, "the Gaussian prior of mu needs a finite mean and a positive standard deviation");
-  if (!(pos(prior->sigma_shape) && pos(prior->sigma_scale))) return fail(e, DLM_ERR_ARG, "the InverseGamma prior of sigma needs a positive shape and scale");
-  if (!(pos(prior->prop_lambda) && pos(prior->prop_tau))) return fail(e, DLM_ERR_ARG, "the Beta proposal needs positive lambda and tau");
-  if (!(pos(prior->delta_sigma) && pos(prior->delta_mu))) return fail(e, DLM_ERR_ARG, "the random walks of sigma and mu need positive standard deviations");
+  if (!(is_positive(prior->phi_a) && is_positive(prior->phi_b))) return fail(e, DLM_ERR_ARG, "the Beta prior of phi needs positive a and b");
+  if (!(is_positive(prior->mu_sd) && is_finite(prior->mu_mean))) return fail(e, DLM_ERR_ARG, "the Gaussian prior of mu needs a finite mean and a positive standard deviation");
+  if (!(is_positive(prior->sigma_shape) && is_positive(prior->sigma_scale))) return fail(e, DLM_ERR_ARG, "the InverseGamma prior of sigma needs a positive shape and scale");
+  if (!(is_positive(prior->prop_lambda) && is_positive(prior->prop_tau))) return fail(e, DLM_ERR_ARG, "the Beta proposal needs positive lambda and tau");
+  if (!(is_positive(prior->delta_sigma) && is_positive(prior->delta_mu))) return fail(e, DLM_ERR_ARG, "the random walks of sigma and mu need positive standard deviations");
   HIP_TRY(e, hipSetDevice(e->device));
   dlm::SvOuParamsArgs a{};
   const size_t n = N, t = T;
@@ -1181,15 +1185,10 @@ int dlm_sv_ou_params_batch(dlm_engine* e, int32_t N, int32_t T, const double* ti
   st.out(&a.sv_out, sv_out, n * 3);
   st.inout(&a.accepted, (int*)accepted, n * 3);
   st.zeroed_out(&a.status, (int*)status, status ? n : 0);
-  int rc;
   if ((rc = st.commit())) return rc;
   a.N = N; a.T = T;
-  a.literal = prior->literal;
-  a.phi_a = prior->phi_a; a.phi_b = prior->phi_b; a.mu_mean = prior->mu_mean; a.mu_sd = prior->mu_sd;
-  a.sigma_shape = prior->sigma_shape; a.sigma_scale = prior->sigma_scale;
-  a.prop_lambda = prior->prop_lambda; a.prop_tau = prior->prop_tau;
-  a.delta_sigma = prior->delta_sigma; a.delta_mu = prior->delta_mu;
-  a.seed = opts->seed; a.series_offset = opts->series_offset; a.iteration = iteration;
+  a.prior = *prior;
+  a.rs = draw_stream(opts, iteration);
   e->variant = "sv-ou-params";
   HIP_TRY(e, dlm::launch_sv_ou_params(a, e->stream));
   return st.finish(opts->flags & DLM_OPT_ASYNC);
@@ -1216,7 +1215,8 @@ static int ar1_common(dlm_engine* e, int32_t N, int32_t T, const double* times, 
                       int64_t v_stride, const double* sv, int64_t sv_stride, const double* z, const dlm_options* opts,
                       double* filt, double* theta, int32_t* status) {
   if (!e) return DLM_ERR_ARG;
-  if (!opts || (opts->mem != DLM_MEM_DEVICE && opts->mem != DLM_MEM_HOST)) return fail(e, DLM_ERR_ARG, "opts");
+  int rc;
+  if ((rc = check_opts(e, opts))) return rc;
   if (N < 1 || T < 1) return fail(e, DLM_ERR_ARG, "N and T must be >= 1 (the reference throws on empty input, FilterAr.scala:40)");
   if (!y || !v || !sv) return fail(e, DLM_ERR_ARG, "y, v and sv are required");
   if (!filt && !theta) return fail(e, DLM_ERR_ARG, "nothing to compute: filt and theta are both NULL");
@@ -1233,7 +1233,6 @@ static int ar1_common(dlm_engine* e, int32_t N, int32_t T, const double* times, 
   st.out(&k.filt, filt, filt ? n * (t + 1) * 2 : 0);
   st.out(&k.theta, theta, theta ? n * (t + 1) : 0);
   st.zeroed_out(&k.status, (int*)status, status ? n : 0);
-  int rc;
   if ((rc = st.commit())) return rc;
   double* fws = k.filt;
   if (!fws) {   // the backward sampler reads the filter records: engine scratch when the caller does not want them

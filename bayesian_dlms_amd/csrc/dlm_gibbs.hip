@@ -9,44 +9,32 @@
 // 1 / scale).draw (InverseGamma.scala:14) = scale / Gamma(shape, 1).draw; the unit-scale Gamma is Marsaglia-Tsang (2000)
 // on Philox normals and uniforms keyed by (seed, global series, iteration, component, attempt): reproducible and
 // independent of the sharding.  The reference's generator cannot be seeded: only the distribution is
-// comparable with it; oracle/dlm_oracle.c restates this very construction.  gibbs_rand and gamma_unit live in dlm_internal.h
-// (the Student-t step of dlm_studentt.hip draws W on this very stream and its own variates on a stream of its own).
-#include "dlm_internal.h"
+// comparable with it; oracle/dlm_oracle.c restates this very construction.  gibbs_rand, gamma_unit and the W draw live in dlm_draws.h
+// (the Student-t step of dlm_studentt.hip draws W through the same functions and its own variates on a stream of its own).
+#include "dlm_draws.h"
 #include "../../include/dlm_engine.h"
 
 namespace dlm {
 
 __global__ __launch_bounds__(256) void k_dinvgamma_step(int d, int p, int N, const double* __restrict__ stats, double av, double bv,
-                                                        double aw, double bw, unsigned long long seed,
-                                                        unsigned long long series_offset, unsigned long long iteration,
-                                                        double* __restrict__ Vout, double* __restrict__ Wout) {
+                                                        double aw, double bw, DrawStream rs, double* __restrict__ Vout,
+                                                        double* __restrict__ Wout) {
   const int per = p + d;
   const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
   if (gid >= (long long)N * per) return;
   const int n = (int)(gid / per), comp = (int)(gid % per);
-  const int L = 2 * p + d + 1;
-  const double* s = stats + (size_t)n * L;
-  const unsigned long long series = series_offset + (unsigned long long)n;
-  double shape, rate;
-  if (comp < p) { shape = av + 0.5 * s[p + comp]; rate = bv + 0.5 * s[comp]; }
-  else { shape = aw + 0.5 * s[L - 1]; rate = bw + 0.5 * s[2 * p + (comp - p)]; }
-  const double val = rate / gamma_unit(shape, seed, series, iteration, (unsigned)comp);
-  if (comp < p) {   // column comp of the dense diagonal V
-    double* col = Vout + (size_t)n * p * p + (size_t)comp * p;
-    for (int i = 0; i < p; ++i) col[i] = (i == comp) ? val : 0.0;
-  } else {
-    const int i0 = comp - p;
-    double* col = Wout + (size_t)n * d * d + (size_t)i0 * d;
-    for (int i = 0; i < d; ++i) col[i] = (i == i0) ? val : 0.0;
-  }
+  const double* s = stats + (size_t)n * (2 * p + d + 1);
+  const bool v = comp < p;
+  const InvGammaDraw q = v ? InvGammaDraw{av + 0.5 * s[p + comp], bv + 0.5 * s[comp], (unsigned)comp} : w_draw(s, d, p, comp - p, aw, bw);
+  const double g = gamma_unit(q.shape, rs.seed, rs.series_offset + (unsigned long long)n, rs.iteration, q.comp);
+  if (v) store_diag_draw(Vout + (size_t)n * p * p, p, comp, q, g);
+  else store_diag_draw(Wout + (size_t)n * d * d, d, comp - p, q, g);
 }
 
 hipError_t launch_dinvgamma_step(int d, int p, int N, const double* stats, double av, double bv, double aw, double bw,
-                                 unsigned long long seed, unsigned long long series_offset, unsigned long long iteration,
-                                 double* Vout, double* Wout, hipStream_t s) {
+                                 const DrawStream& rs, double* Vout, double* Wout, hipStream_t s) {
   const long long total = (long long)N * (p + d);
-  return launch(k_dinvgamma_step, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d, p, N, stats, av, bv, aw, bw,
-                seed, series_offset, iteration, Vout, Wout);
+  return launch(k_dinvgamma_step, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d, p, N, stats, av, bv, aw, bw, rs, Vout, Wout);
 }
 
 }  // namespace dlm

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
+#include "../../include/dlm_engine.h"
 
 namespace dlm {
 
@@ -359,10 +360,12 @@ hipError_t launch_ar1_ffbs(int N, int T, const double* times, const double* y, c
                            const double* sv, long long sv_stride, const double* z, unsigned long long seed,
                            unsigned long long series_offset, double* filt, double* theta, int* status, hipStream_t s);
 
+// ---- the Gibbs parameter steps: where a call's draws sit in the Philox counter space (dlm_draws.h) ----
+struct DrawStream { unsigned long long seed, series_offset, iteration; };   // series n draws at (seed, series_offset + n, iteration)
+
 // ---- d-Inverse-Gamma conjugate draws on the device (Gibbs.scala:23-78), dlm_gibbs.hip --------------
 hipError_t launch_dinvgamma_step(int d, int p, int N, const double* stats, double av, double bv, double aw, double bw,
-                                 unsigned long long seed, unsigned long long series_offset, unsigned long long iteration,
-                                 double* Vout, double* Wout, hipStream_t s);
+                                 const DrawStream& rs, double* Vout, double* Wout, hipStream_t s);
 
 // ---- Student-t observation DLM: one Gibbs step after the FFBS call (StudentTGibbs.scala:182-212), dlm_studentt.hip -------------
 struct StudentTArgs {
@@ -372,9 +375,9 @@ struct StudentTArgs {
   const double* theta;    // [N][T+1][d]
   const double* stats;    // [N][d + 3] = [ssy | n | ss (d) | T] of the FFBS call
   const double* scale_in; const int* nu_in;
-  double prior_nu_rate, prop_nu_size, prior_w_shape, prior_w_scale;
+  dlm_studentt_prior prior;
   int literal;            // DLM_OPT_STUDENTT_LITERAL
-  unsigned long long seed, series_offset, iteration;
+  DrawStream rs;
   double* v_out; double* scale_out; int* nu_out; double* W_out; int* accepted;
   double* loglik; int* status;   // nullable
 };
@@ -386,7 +389,7 @@ struct SvMixArgs {
   int N, T;
   const double* y;        // [N][T]
   const double* alpha;    // [N][T+1], or nullptr: the initial transform (no draw)
-  unsigned long long seed, series_offset, iteration;
+  DrawStream rs;
   double* ystar; double* v;   // [N][T]
   signed char* k;         // [N][T], nullable
   int* status;            // [N], nullable (zeroed by the caller)
@@ -395,9 +398,8 @@ struct SvParamsArgs {
   int N, T;
   const double* alpha;    // [N][T+1]
   const double* sv_in;    // [N][3] = (phi, mu, sigma_eta)
-  int phi_update, literal;
-  double phi_a, phi_b, mu_mean, mu_sd, sigma_shape, sigma_scale, prop_lambda, prop_tau;
-  unsigned long long seed, series_offset, iteration;
+  dlm_sv_prior prior;
+  DrawStream rs;
   double* sv_out;         // [N][3], may be sv_in
   int* accepted; int* status;   // nullable
 };
@@ -411,9 +413,8 @@ struct SvOuParamsArgs {
   const double* times;    // [T], shared by the batch
   const double* alpha;    // [N][T+1] as dlm_ou_ffbs_batch writes its theta
   const double* sv_in;    // [N][3] = (phi, mu, sigma_eta), phi the mean-reversion rate
-  int literal;
-  double phi_a, phi_b, mu_mean, mu_sd, sigma_shape, sigma_scale, prop_lambda, prop_tau, delta_sigma, delta_mu;
-  unsigned long long seed, series_offset, iteration;
+  dlm_sv_ou_prior prior;
+  DrawStream rs;
   double* sv_out;         // [N][3], may be sv_in
   int* accepted;          // [N][3]: phi, sigma, mu
   int* status;            // nullable
@@ -508,51 +509,6 @@ __device__ __forceinline__ void philox_normal2(unsigned long long seed, unsigned
   double r = sqrt(-2.0 * log(u1));
   double ang = 6.283185307179586476925286766559 * u2;
   z_even = r * cos(ang); z_odd = r * sin(ang);
-}
-
-// ---- Gamma variates on Philox uniforms (dlm_gibbs.hip, dlm_studentt.hip; oracle/dlm_oracle.c restates the GIBB stream) ----------
-// Counter (series lo, series hi, iteration, comp * 2048 + attempt * 2 + which) under the key (seed lo, seed hi ^ key): one stream per
-// key, each disjoint from the FFBS / simulation normals (key (seed lo, seed hi)) and from the others.
-//   DLM_KEY_GIBBS     dlm_dinvgamma_step_batch: comp = component of [V diagonal (p) | W diagonal (d)]; the Student-t step draws W here too
-//   DLM_KEY_STUDENTT  dlm_studentt_step_batch: comp = t for the variance v_t, DLM_ST_SLOT_* for its scalar draws (dlm_studentt.hip)
-//   DLM_KEY_SV        dlm_sv_mixture_batch: comp = t for the mixture indicator k_t; dlm_sv_params_batch: DLM_SV_SLOT_* (dlm_sv.hip)
-//   DLM_KEY_SVOU      dlm_sv_ou_params_batch: DLM_SVOU_SLOT_* (dlm_sv_ou.hip); the OU chain's mixture call draws under DLM_KEY_SV
-constexpr unsigned DLM_KEY_GIBBS = 0x47494242u;      // "GIBB"
-constexpr unsigned DLM_KEY_STUDENTT = 0x53545544u;   // "STUD"
-constexpr unsigned DLM_KEY_SV = 0x5354564Fu;         // "STVO"
-constexpr unsigned DLM_KEY_SVOU = 0x53564F55u;       // "SVOU"
-
-__device__ __forceinline__ void gibbs_rand(unsigned long long seed, unsigned long long series, unsigned long long iteration,
-                                           unsigned comp, unsigned attempt, unsigned which, double& u1, double& u2,
-                                           unsigned key = DLM_KEY_GIBBS) {
-  unsigned c[4] = {(unsigned)series, (unsigned)(series >> 32), (unsigned)iteration, comp * 2048u + attempt * 2u + which};
-  philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32) ^ key);
-  u1 = ((double)c[0] * 4294967296.0 + (double)c[1] + 1.0) * (1.0 / 18446744073709551616.0);   // (0, 1]
-  u2 = ((double)c[2] * 4294967296.0 + (double)c[3]) * (1.0 / 18446744073709551616.0);         // [0, 1)
-}
-
-// Gamma(a, 1): Marsaglia & Tsang, "A simple method for generating gamma variables" (2000); a < 1 by the u^(1/a) boost
-__device__ inline double gamma_unit(double a, unsigned long long seed, unsigned long long series, unsigned long long iteration, unsigned comp,
-                                    unsigned key = DLM_KEY_GIBBS) {
-  double boost = 1.0;
-  if (a < 1.0) {
-    double u1, u2;
-    gibbs_rand(seed, series, iteration, comp, 1023u, 0u, u1, u2, key);
-    boost = pow(u1, 1.0 / a);
-    a += 1.0;
-  }
-  const double dd = a - 1.0 / 3.0, cc = 1.0 / sqrt(9.0 * dd);
-  for (unsigned k = 0; k < 1023u; ++k) {
-    double u1, u2, w1, w2;
-    gibbs_rand(seed, series, iteration, comp, k, 0u, u1, u2, key);
-    const double x = sqrt(-2.0 * log(u1)) * cos(6.283185307179586476925286766559 * u2);
-    double v = 1.0 + cc * x;
-    if (v <= 0.0) continue;
-    v = v * v * v;
-    gibbs_rand(seed, series, iteration, comp, k, 1u, w1, w2, key);
-    if (log(w1) < 0.5 * x * x + dd - dd * v + dd * log(v)) return dd * v * boost;
-  }
-  return dd * boost;   // unreachable in practice (acceptance > 95 % per attempt)
 }
 
 }  // namespace dlm

@@ -20,21 +20,14 @@
 // on N or on its neighbours.  The scalar draws are made on one lane each and broadcast.  The kernel is flattened: an out-of-line
 // gamma_unit costs a call frame in scratch.
 //
-// Random streams.  W: the dlm_dinvgamma_step_batch stream (key DLM_KEY_GIBBS, component 1 + i as with p = 1), so that W_out is
-// that call's W_out for the same statistics, seed, iteration and offset.  Everything else: key DLM_KEY_STUDENTT, counter
-// (series, iteration, slot): slot t for v_t, DLM_ST_SLOT_* for the four scalar draws.  gamma_unit is Marsaglia-Tsang
-// (dlm_internal.h); Poisson is inversion below lambda = 10 and Hormann's PTRS (1993) above.
-#include "dlm_internal.h"
+// Random streams.  W: dlm_dinvgamma_step_batch's draw (w_draw / store_diag_draw of dlm_draws.h with p = 1: key DLM_KEY_GIBBS, component
+// 1 + i), so that W_out is that call's W_out for the same statistics, seed, iteration and offset.  Everything else: key
+// DLM_KEY_STUDENTT, counter (series, iteration, slot): slot t for v_t, DLM_ST_SLOT_* for the four scalar draws (the slot table of
+// dlm_draws.h).  gamma_unit is Marsaglia-Tsang (dlm_draws.h); Poisson is inversion below lambda = 10 and Hormann's PTRS (1993) above.
+#include "dlm_draws.h"
 #include "dlm_wave.h"
-#include "../../include/dlm_engine.h"
 
 namespace dlm {
-
-constexpr unsigned DLM_ST_SLOT_PROP_GAMMA = 0x1FFFFFu;   // lambda ~ Gamma(r, nu / r) of the proposal
-constexpr unsigned DLM_ST_SLOT_POISSON = 0x1FFFFEu;      // Poisson(lambda)
-constexpr unsigned DLM_ST_SLOT_ACCEPT = 0x1FFFFDu;       // the Metropolis-Hastings uniform
-constexpr unsigned DLM_ST_SLOT_SCALE = 0x1FFFFCu;        // s ~ Gamma
-// (v_t takes slot t < T <= 0x1FFFFC: the counter word is slot * 2048 + attempt * 2 + which)
 
 // log Gamma(x) for the PTRS test: Stirling's series at x + n >= 7, recursion below (the loggam of NumPy's PTRS); lighter than lgamma
 __device__ __forceinline__ double ptrs_loggam(double x) {
@@ -85,32 +78,28 @@ __global__ __launch_bounds__(256) __attribute__((flatten)) void k_studentt_step(
   if (n >= a.N) return;   // (whole waves: the shuffles below see every lane of the wave)
   const int d = a.d, T = a.T;
   const bool lit = a.literal != 0;
-  const unsigned long long series = a.series_offset + (unsigned long long)n, seed = a.seed, it = a.iteration;
+  const unsigned long long series = a.rs.series_offset + (unsigned long long)n, seed = a.rs.seed, it = a.rs.iteration;
   const double s = a.scale_in[n];
   const int nu = a.nu_in[n];
   const double* th = a.theta + (size_t)n * (T + 1) * d;
   const double* yn = a.y + (size_t)n * T;
   double* vn = a.v_out + (size_t)n * T;
   bool bad = !(nu >= 1) || !(s > 0.0) || !(s < __builtin_inf());
-  const double r = a.prop_nu_size, dnu = (double)nu;
+  const double r = a.prior.prop_nu_size, dnu = (double)nu;
 
-  // the Gamma draws that need no data, one per lane: W_ii on dlm_dinvgamma_step_batch's stream and arithmetic (p = 1: stats =
-  // [ssy | n | ss (d) | T], component 1 + i) for j = i < d; for j = d the proposal's lambda ~ Gamma(r, q / (1 - q)),
-  // q = nu / (r + nu) (Breeze's NegativeBinomial(r, q) draws Poisson(lambda)), then nu' = Poisson(lambda) + 1
-  const int L = d + 3;
-  const double* st = a.stats + (size_t)n * L;
+  // the Gamma draws that need no data, one per lane: W_ii as dlm_dinvgamma_step_batch draws it (p = 1: stats = [ssy | n | ss (d) | T])
+  // for j = i < d; for j = d the proposal's lambda ~ Gamma(r, q / (1 - q)), q = nu / (r + nu) (Breeze's NegativeBinomial(r, q)
+  // draws Poisson(lambda)), then nu' = Poisson(lambda) + 1
+  const double* st = a.stats + (size_t)n * (d + 3);
   double* Wn = a.W_out + (size_t)n * d * d;
   double nup = 0.0;
   for (int j = lane; j <= d; j += 64) {
     const bool w = j < d;
     const double q = dnu / (r + dnu);
-    const double shape = w ? a.prior_w_shape + 0.5 * st[L - 1] : r, rate = w ? a.prior_w_scale + 0.5 * st[2 + j] : 0.0;
-    const double g = bad ? __builtin_nan("") : gamma_unit(shape, seed, series, it, w ? 1u + (unsigned)j : DLM_ST_SLOT_PROP_GAMMA,
-                                                             w ? DLM_KEY_GIBBS : DLM_KEY_STUDENTT);
+    const InvGammaDraw wq = w ? w_draw(st, d, 1, j, a.prior.prior_w_shape, a.prior.prior_w_scale) : InvGammaDraw{r, 0.0, DLM_ST_SLOT_PROP_GAMMA};
+    const double g = bad ? __builtin_nan("") : gamma_unit(wq.shape, seed, series, it, wq.comp, w ? DLM_KEY_GIBBS : DLM_KEY_STUDENTT);
     if (w) {
-      const double val = rate / g;
-      double* col = Wn + (size_t)j * d;
-      for (int i = 0; i < d; ++i) col[i] = (i == j) ? val : 0.0;
+      store_diag_draw(Wn, d, j, wq, g);
     } else if (!bad) {
       nup = poisson_draw(g * (q / (1.0 - q)), seed, series, it) + 1.0;
     }
@@ -172,7 +161,7 @@ __global__ __launch_bounds__(256) __attribute__((flatten)) void k_studentt_step(
   int acc = 0, nu_v = nu;
   double ll_out = 0.0;
   if (lane == 0 && !bad) {
-    const double lam = a.prior_nu_rate, nobsd = (double)nobs, PI = 3.141592653589793;
+    const double lam = a.prior.prior_nu_rate, nobsd = (double)nobs, PI = 3.141592653589793;
     const double c0 = lit ? sc : s;   // Q14: the reference's normaliser has the scale sqrt(s) where s belongs
     const double ll0 = nobsd * (G[0] - 0.5 * log(PI * dnu * c0) - G[1]) - (dnu + 1.0) * 0.5 * A0;
     ll_out = ll0;
@@ -183,9 +172,7 @@ __global__ __launch_bounds__(256) __attribute__((flatten)) void k_studentt_step(
       const double pp1 = G[6] - G[7] - G[8] + r * log(1.0 - q1) + k1 * log(q1);   // propP(nu', nu)
       const double pp2 = G[9] - G[10] - G[8] + r * log(1.0 - q2) + k2 * log(q2);  // propP(nu, nu')
       const double lacc = lm1 + pp1 - lm0 - pp2;
-      double u1, u2;
-      gibbs_rand(seed, series, it, DLM_ST_SLOT_ACCEPT, 0u, 0u, u1, u2, DLM_KEY_STUDENTT);
-      if (log(u1) < lacc) { acc = 1; ll_out = ll1; }
+      if (draw_log_uniform(DLM_KEY_STUDENTT, seed, series, it, DLM_ST_SLOT_ACCEPT) < lacc) { acc = 1; ll_out = ll1; }
     }
     nu_v = (acc && !lit) ? (int)nup : nu;   // the nu of the variance and scale draws: the new one (Q15), the old one when literal
   }

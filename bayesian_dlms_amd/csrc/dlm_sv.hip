@@ -39,20 +39,12 @@
 // unrestricted Gaussian phi (Q19).
 //
 // Random streams: key DLM_KEY_SV, counter (series, iteration, slot): slot t for k_t (the u2 uniform of attempt 0), DLM_SV_SLOT_* for
-// the scalar draws.  Normals are the Box-Muller cosine of the pair at attempt k; gamma_unit is Marsaglia-Tsang (dlm_internal.h).
-#include "dlm_internal.h"
+// the scalar draws (the slot table of dlm_draws.h).  Normals are the Box-Muller cosine of the pair at attempt k (draw_normal); gamma_unit
+// is Marsaglia-Tsang; the Beta proposal is BetaProposal (all dlm_draws.h).
+#include "dlm_draws.h"
 #include "dlm_wave.h"
-#include "../../include/dlm_engine.h"
 
 namespace dlm {
-
-constexpr unsigned DLM_SV_SLOT_PHI = 0x1FFFFFu;      // phi ~ N (conjugate mode; attempt k of the rejection)
-constexpr unsigned DLM_SV_SLOT_MU = 0x1FFFFEu;       // mu ~ N
-constexpr unsigned DLM_SV_SLOT_SIGMA = 0x1FFFFDu;    // sigma^2: the Gamma of the InverseGamma
-constexpr unsigned DLM_SV_SLOT_PROP_A = 0x1FFFFCu;   // Beta proposal: Gamma(lambda phi + tau)
-constexpr unsigned DLM_SV_SLOT_PROP_B = 0x1FFFFBu;   //                Gamma(lambda (1 - phi) + tau)
-constexpr unsigned DLM_SV_SLOT_ACCEPT = 0x1FFFFAu;   // the Metropolis-Hastings uniform
-// (0x1FFFF9 is kept free; k_t takes slot t < T <= 0x1FFFF7: the counter word is slot * 2048 + attempt * 2 + which)
 
 // The mixture of StochasticVolatility.scala:42-44 (pi_j, m_j, v_j), j = 0..6, and what the weights need of it:
 //   SV_C[j] = log pi_j - 1/2 log(2 pi v_j),  SV_H[j] = 1 / (2 v_j),  SV_LP[j] = log pi_j
@@ -97,7 +89,7 @@ __global__ __launch_bounds__(256) void k_sv_mixture(SvMixArgs a) {
 #pragma unroll
   for (int j = 0; j < 7; ++j) { c = c + exp(lw[j] - mx); p[j] = c; }
   double u1, u2;
-  gibbs_rand(a.seed, a.series_offset + (unsigned long long)n, a.iteration, (unsigned)t, 0u, 0u, u1, u2, DLM_KEY_SV);
+  gibbs_rand(a.rs.seed, a.rs.series_offset + (unsigned long long)n, a.rs.iteration, (unsigned)t, 0u, 0u, u1, u2, DLM_KEY_SV);
   const double us = u2 * p[6];
   int k = 0;
 #pragma unroll
@@ -110,20 +102,14 @@ __global__ __launch_bounds__(256) void k_sv_mixture(SvMixArgs a) {
   if (a.k) a.k[e] = (signed char)k;
 }
 
-// N(0, 1) of attempt k of a scalar slot: the Box-Muller cosine of the block's pair
-__device__ __forceinline__ double sv_normal(unsigned long long seed, unsigned long long series, unsigned long long it, unsigned slot, unsigned k) {
-  double u1, u2;
-  gibbs_rand(seed, series, it, slot, k, 0u, u1, u2, DLM_KEY_SV);
-  return sqrt(-2.0 * log(u1)) * cos(6.283185307179586476925286766559 * u2);
-}
-
 __global__ __launch_bounds__(256) __attribute__((flatten)) void k_sv_params(SvParamsArgs a) {
   const int lane = threadIdx.x & 63;
   const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (n >= a.N) return;   // (whole waves: the shuffles below see every lane of the wave)
   const int T = a.T;
-  const bool lit = a.literal != 0, beta = a.phi_update != 0;
-  const unsigned long long series = a.series_offset + (unsigned long long)n, seed = a.seed, it = a.iteration;
+  const dlm_sv_prior& pr = a.prior;
+  const bool lit = pr.literal != 0, beta = pr.phi_update != 0;
+  const unsigned long long series = a.rs.series_offset + (unsigned long long)n, seed = a.rs.seed, it = a.rs.iteration;
   const double INF = __builtin_inf();
   const double* al = a.alpha + (size_t)n * (T + 1);
   const double phi0 = a.sv_in[(size_t)n * 3], mu0 = a.sv_in[(size_t)n * 3 + 1], sig0 = a.sv_in[(size_t)n * 3 + 2];
@@ -146,18 +132,18 @@ __global__ __launch_bounds__(256) __attribute__((flatten)) void k_sv_params(SvPa
     const double d0 = a0 - mu0, d1 = a1 - mu0, dT = aT - mu0;
     S = wave_sum(S) + (lit ? dT * dT : d0 * d0);
     S2 = wave_sum(S2) + (lit ? 0.0 : d0 * d1);
-    const double psi2 = a.phi_b * a.phi_b;
+    const double psi2 = pr.phi_b * pr.phi_b;
     const double prec = lit ? 1.0 / psi2 + S : 1.0 / psi2 + S / s2;   // Q16
-    const double mean = lit ? (a.phi_a / psi2 + S2) / prec : (a.phi_a / psi2 + S2 / s2) / prec;
+    const double mean = lit ? (pr.phi_a / psi2 + S2) / prec : (pr.phi_a / psi2 + S2 / s2) / prec;
     if (!(prec > 0.0) || !(prec < INF) || !(fabs(mean) < INF)) bad = true;
     if (lane == 0 && !bad) {
       const double sd = sqrt(1.0 / prec);
       if (lit) {   // Q19: unrestricted
-        phi = mean + sd * sv_normal(seed, series, it, DLM_SV_SLOT_PHI, 0u);
+        phi = mean + sd * draw_normal(DLM_KEY_SV, seed, series, it, DLM_SV_SLOT_PHI);
       } else {
         bool ok = false;
         for (unsigned k = 0; k < 1023u && !ok; ++k) {
-          const double cand = mean + sd * sv_normal(seed, series, it, DLM_SV_SLOT_PHI, k);
+          const double cand = mean + sd * draw_normal(DLM_KEY_SV, seed, series, it, DLM_SV_SLOT_PHI, k);
           if (fabs(cand) < 1.0) { phi = cand; ok = true; }
         }
         if (!ok) st |= DLM_ST_NOT_PD;
@@ -165,13 +151,9 @@ __global__ __launch_bounds__(256) __attribute__((flatten)) void k_sv_params(SvPa
     }
   } else {
     // samplePhi: the proposal needs no data and is drawn first (lanes 0, 1), then both residual sums in one pass
-    const double lam = a.prop_lambda, tau = a.prop_tau;
-    const double A0 = lam * phi0 + tau, B0 = lam * (1.0 - phi0) + tau;
-    double g = 1.0;
-    if (lane < 2 && !bad) g = gamma_unit(lane == 0 ? A0 : B0, seed, series, it, lane == 0 ? DLM_SV_SLOT_PROP_A : DLM_SV_SLOT_PROP_B, DLM_KEY_SV);
-    const double ga = __shfl(g, 0, 64), gb = __shfl(g, 1, 64);
-    const double phip = ga / (ga + gb);
-    const bool prop_ok = phip > 0.0 && phip < 1.0;
+    BetaProposal q;
+    q.draw(lane, phi0, pr.prop_lambda, pr.prop_tau, bad, DLM_KEY_SV, seed, series, it, DLM_SV_SLOT_PROP_A, DLM_SV_SLOT_PROP_B);
+    const double phip = q.phip;
     double Q0 = 0.0, Q1 = 0.0;
     for (int t = 2 + lane; t <= T; t += 64) {
       const double p = al[t - 1] - mu0, c = al[t] - mu0;
@@ -183,29 +165,15 @@ __global__ __launch_bounds__(256) __attribute__((flatten)) void k_sv_params(SvPa
     const double f0 = d1 - phi0 * d0, f1 = d1 - phip * d0;
     Q0 = wave_sum(Q0) + (lit ? 0.0 : f0 * f0);
     Q1 = wave_sum(Q1) + (lit ? 0.0 : f1 * f1);
-    const double A1 = lam * phip + tau, B1 = lam * (1.0 - phip) + tau;
-    double garg = 1.0;
-    switch (lane) {
-      case 0: garg = A0; break;  case 1: garg = B0; break;  case 2: garg = A0 + B0; break;
-      case 3: garg = A1; break;  case 4: garg = B1; break;  case 5: garg = A1 + B1; break;
-      default: break;
-    }
-    const double lg = lgamma(garg);
-    double G[6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) G[j] = __shfl(lg, j, 64);
+    q.lgammas(lane);
     if (!(fabs(Q0) < INF)) bad = true;
-    if (lane == 0 && !bad && prop_ok) {
+    if (lane == 0 && !bad && q.ok) {
       // log target without the terms free of phi: Beta(a, b) prior, the stationary density of alpha_0, the transitions
       const double o0 = 1.0 - phi0 * phi0, o1 = 1.0 - phip * phip;
-      const double lt0 = (a.phi_a - 1.0) * log(phi0) + (a.phi_b - 1.0) * log(1.0 - phi0) + 0.5 * log(o0) - 0.5 * d0 * d0 * o0 / s2 - 0.5 * Q0 / s2;
-      const double lt1 = (a.phi_a - 1.0) * log(phip) + (a.phi_b - 1.0) * log(1.0 - phip) + 0.5 * log(o1) - 0.5 * d0 * d0 * o1 / s2 - 0.5 * Q1 / s2;
-      const double lq_fwd = G[2] - G[0] - G[1] + (A0 - 1.0) * log(phip) + (B0 - 1.0) * log(1.0 - phip);    // log q(phi' | phi)
-      const double lq_back = G[5] - G[3] - G[4] + (A1 - 1.0) * log(phi0) + (B1 - 1.0) * log(1.0 - phi0);   // log q(phi | phi')
-      const double lacc = lt1 - lt0 + lq_back - lq_fwd;
-      double u1, u2;
-      gibbs_rand(seed, series, it, DLM_SV_SLOT_ACCEPT, 0u, 0u, u1, u2, DLM_KEY_SV);
-      if (log(u1) < lacc) { acc = 1; phi = phip; }
+      const double lt0 = (pr.phi_a - 1.0) * log(phi0) + (pr.phi_b - 1.0) * log(1.0 - phi0) + 0.5 * log(o0) - 0.5 * d0 * d0 * o0 / s2 - 0.5 * Q0 / s2;
+      const double lt1 = (pr.phi_a - 1.0) * log(phip) + (pr.phi_b - 1.0) * log(1.0 - phip) + 0.5 * log(o1) - 0.5 * d0 * d0 * o1 / s2 - 0.5 * Q1 / s2;
+      const double lacc = lt1 - lt0 + q.lq_back() - q.lq_fwd();
+      if (draw_log_uniform(DLM_KEY_SV, seed, series, it, DLM_SV_SLOT_ACCEPT) < lacc) { acc = 1; phi = phip; }
     }
   }
   phi = __shfl(phi, 0, 64);
@@ -214,12 +182,12 @@ __global__ __launch_bounds__(256) __attribute__((flatten)) void k_sv_params(SvPa
   double M = 0.0;
   for (int t = 2 + lane; t <= T; t += 64) M = M + (al[t] - phi * al[t - 1]);
   M = wave_sum(M) + (lit ? 0.0 : a1 - phi * a0);
-  const double pm2 = a.mu_sd * a.mu_sd, omp = 1.0 - phi;
+  const double pm2 = pr.mu_sd * pr.mu_sd, omp = 1.0 - phi;
   const double mprec = lit ? 1.0 / pm2 + (Td - 1.0) * omp * omp : 1.0 / pm2 + Td * omp * omp / s2;   // Q16
-  const double mmean = lit ? (a.mu_mean / pm2 + omp * M) / mprec : (a.mu_mean / pm2 + omp / s2 * M) / mprec;
+  const double mmean = lit ? (pr.mu_mean / pm2 + omp * M) / mprec : (pr.mu_mean / pm2 + omp / s2 * M) / mprec;
   if (!(mprec > 0.0) || !(mprec < INF) || !(fabs(mmean) < INF)) bad = true;
   double mu = mu0;
-  if (lane == 0 && !bad) mu = mmean + sqrt(1.0 / mprec) * sv_normal(seed, series, it, DLM_SV_SLOT_MU, 0u);
+  if (lane == 0 && !bad) mu = mmean + sqrt(1.0 / mprec) * draw_normal(DLM_KEY_SV, seed, series, it, DLM_SV_SLOT_MU);
   mu = __shfl(mu, 0, 64);
 
   // sampleSigma at the new phi and mu
@@ -230,8 +198,8 @@ __global__ __launch_bounds__(256) __attribute__((flatten)) void k_sv_params(SvPa
   }
   const double fr = (a1 - mu) - phi * (a0 - mu);
   Q = wave_sum(Q) + (lit ? 0.0 : fr * fr);
-  const double shape = a.sigma_shape + (lit ? (Td + 1.0) * 0.5 : Td * 0.5);   // Q18
-  const double scale = a.sigma_scale + 0.5 * Q;
+  const double shape = pr.sigma_shape + (lit ? (Td + 1.0) * 0.5 : Td * 0.5);   // Q18
+  const double scale = pr.sigma_scale + 0.5 * Q;
   if (!(scale > 0.0) || !(scale < INF)) bad = true;
   if (lane == 0) {
     double sig = __builtin_nan("");

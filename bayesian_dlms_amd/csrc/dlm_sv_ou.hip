@@ -34,39 +34,21 @@
 //        see the new phi, sigma) is the order above.
 //
 // Random streams: key DLM_KEY_SVOU, counter (series, iteration, slot), the seven slots below.  Normals are the Box-Muller cosine of
-// attempt 0; gamma_unit is Marsaglia-Tsang (dlm_internal.h).  The kernel is flattened, as k_sv_params is.
-#include "dlm_internal.h"
+// attempt 0 (draw_normal), the uniforms come as their logs (draw_log_uniform), gamma_unit is Marsaglia-Tsang and the Beta proposal is
+// BetaProposal, k_sv_params' own (all dlm_draws.h, with the slot table).  The kernel is flattened, as k_sv_params is.
+#include "dlm_draws.h"
 #include "dlm_wave.h"
-#include "../../include/dlm_engine.h"
 
 namespace dlm {
-
-constexpr unsigned DLM_SVOU_SLOT_PROP_A = 0x1FFFFFu;      // Beta proposal: Gamma(lambda phi + tau)
-constexpr unsigned DLM_SVOU_SLOT_PROP_B = 0x1FFFFEu;      //                Gamma(lambda (1 - phi) + tau)
-constexpr unsigned DLM_SVOU_SLOT_ACC_PHI = 0x1FFFFDu;     // phi's uniform
-constexpr unsigned DLM_SVOU_SLOT_Z_SIGMA = 0x1FFFFCu;     // sigma's walk
-constexpr unsigned DLM_SVOU_SLOT_ACC_SIGMA = 0x1FFFFBu;   // sigma's uniform
-constexpr unsigned DLM_SVOU_SLOT_Z_MU = 0x1FFFFAu;        // mu's walk
-constexpr unsigned DLM_SVOU_SLOT_ACC_MU = 0x1FFFF9u;      // mu's uniform
-
-__device__ __forceinline__ double svou_normal(unsigned long long seed, unsigned long long series, unsigned long long it, unsigned slot) {
-  double u1, u2;
-  gibbs_rand(seed, series, it, slot, 0u, 0u, u1, u2, DLM_KEY_SVOU);
-  return sqrt(-2.0 * log(u1)) * cos(6.283185307179586476925286766559 * u2);
-}
-__device__ __forceinline__ double svou_log_uniform(unsigned long long seed, unsigned long long series, unsigned long long it, unsigned slot) {
-  double u1, u2;
-  gibbs_rand(seed, series, it, slot, 0u, 0u, u1, u2, DLM_KEY_SVOU);
-  return log(u1);
-}
 
 __global__ __launch_bounds__(256) __attribute__((flatten)) void k_sv_ou_params(SvOuParamsArgs a) {
   const int lane = threadIdx.x & 63;
   const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (n >= a.N) return;   // (whole waves: the shuffles below see every lane of the wave)
   const int T = a.T;
-  const bool lit = a.literal != 0;
-  const unsigned long long series = a.series_offset + (unsigned long long)n, seed = a.seed, it = a.iteration;
+  const dlm_sv_ou_prior& pr = a.prior;
+  const bool lit = pr.literal != 0;
+  const unsigned long long series = a.rs.series_offset + (unsigned long long)n, seed = a.rs.seed, it = a.rs.iteration;
   const double INF = __builtin_inf();
   const double* al = a.alpha + (size_t)n * (T + 1);
   const double* tm = a.times;
@@ -74,13 +56,9 @@ __global__ __launch_bounds__(256) __attribute__((flatten)) void k_sv_ou_params(S
   bool bad = !(phi0 > 0.0 && phi0 < 1.0) || !(fabs(mu0) < INF) || !(sig0 > 0.0) || !(sig0 < INF);
 
   // samplePhiOu's proposal (lanes 0, 1)
-  const double lam = a.prop_lambda, tau = a.prop_tau;
-  const double A0 = lam * phi0 + tau, B0 = lam * (1.0 - phi0) + tau;
-  double gm = 1.0;
-  if (lane < 2 && !bad) gm = gamma_unit(lane == 0 ? A0 : B0, seed, series, it, lane == 0 ? DLM_SVOU_SLOT_PROP_A : DLM_SVOU_SLOT_PROP_B, DLM_KEY_SVOU);
-  const double ga = __shfl(gm, 0, 64), gb = __shfl(gm, 1, 64);
-  const double phip = ga / (ga + gb);
-  const bool prop_ok = phip > 0.0 && phip < 1.0;
+  BetaProposal q;
+  q.draw(lane, phi0, pr.prop_lambda, pr.prop_tau, bad, DLM_KEY_SVOU, seed, series, it, DLM_SVOU_SLOT_PROP_A, DLM_SVOU_SLOT_PROP_B);
+  const double phip = q.phip;
 
   // the row, once: (L, A, B, C) at phi0 and at phi'
   double L0 = 0.0, SA0 = 0.0, SB0 = 0.0, SC0 = 0.0, L1 = 0.0, SA1 = 0.0, SB1 = 0.0, SC1 = 0.0;
@@ -111,17 +89,7 @@ __global__ __launch_bounds__(256) __attribute__((flatten)) void k_sv_ou_params(S
   if (!(fabs(L0) < INF) || !(fabs(SA0) < INF) || !(fabs(SB0) < INF) || !(fabs(SC0) < INF)) bad = true;
 
   // the Beta proposal's six lgamma values side by side, one per lane
-  const double A1 = lam * phip + tau, B1 = lam * (1.0 - phip) + tau;
-  double garg = 1.0;
-  switch (lane) {
-    case 0: garg = A0; break;  case 1: garg = B0; break;  case 2: garg = A0 + B0; break;
-    case 3: garg = A1; break;  case 4: garg = B1; break;  case 5: garg = A1 + B1; break;
-    default: break;
-  }
-  const double lg = lgamma(garg);
-  double G[6];
-#pragma unroll
-  for (int j = 0; j < 6; ++j) G[j] = __shfl(lg, j, 64);
+  q.lgammas(lane);
 
   if (lane != 0) return;
   double* o = a.sv_out + (size_t)n * 3;
@@ -134,41 +102,39 @@ __global__ __launch_bounds__(256) __attribute__((flatten)) void k_sv_ou_params(S
 
   // phi
   double phi = phi0, SA = SA0, SB = SB0, SC = SC0;
-  if (prop_ok) {
+  if (q.ok) {
     const double s2 = sig0 * sig0;
-    const double lt0 = (a.phi_a - 1.0) * log(phi0) + (a.phi_b - 1.0) * log(1.0 - phi0) + 0.5 * nd * log(2.0 * phi0) - 0.5 * L0 - phi0 * SA0 / s2;
-    const double lt1 = (a.phi_a - 1.0) * log(phip) + (a.phi_b - 1.0) * log(1.0 - phip) + 0.5 * nd * log(2.0 * phip) - 0.5 * L1 - phip * SA1 / s2;
-    const double lq_fwd = G[2] - G[0] - G[1] + (A0 - 1.0) * log(phip) + (B0 - 1.0) * log(1.0 - phip);    // log q(phi' | phi)
-    const double lq_back = G[5] - G[3] - G[4] + (A1 - 1.0) * log(phi0) + (B1 - 1.0) * log(1.0 - phi0);   // log q(phi | phi')
-    const double lacc = lit ? lt1 - lt0 : lt1 - lt0 + lq_back - lq_fwd;   // Q23
-    if (svou_log_uniform(seed, series, it, DLM_SVOU_SLOT_ACC_PHI) < lacc) { acc_phi = 1; phi = phip; SA = SA1; SB = SB1; SC = SC1; }
+    const double lt0 = (pr.phi_a - 1.0) * log(phi0) + (pr.phi_b - 1.0) * log(1.0 - phi0) + 0.5 * nd * log(2.0 * phi0) - 0.5 * L0 - phi0 * SA0 / s2;
+    const double lt1 = (pr.phi_a - 1.0) * log(phip) + (pr.phi_b - 1.0) * log(1.0 - phip) + 0.5 * nd * log(2.0 * phip) - 0.5 * L1 - phip * SA1 / s2;
+    const double lacc = lit ? lt1 - lt0 : lt1 - lt0 + q.lq_back() - q.lq_fwd();   // Q23
+    if (draw_log_uniform(DLM_KEY_SVOU, seed, series, it, DLM_SVOU_SLOT_ACC_PHI) < lacc) { acc_phi = 1; phi = phip; SA = SA1; SB = SB1; SC = SC1; }
   }
 
   // sigma at the new phi, from sig0 (Q25)
   const double d0 = al[0] - mu0;
   double sig = sig0;
   {
-    const double sigp = sig0 * exp(a.delta_sigma * svou_normal(seed, series, it, DLM_SVOU_SLOT_Z_SIGMA));
+    const double sigp = sig0 * exp(pr.delta_sigma * draw_normal(DLM_KEY_SVOU, seed, series, it, DLM_SVOU_SLOT_Z_SIGMA));
     if (sigp > 0.0 && sigp < INF) {
       const double ls0 = log(sig0), ls1 = log(sigp);
-      double lt0 = -(a.sigma_shape + 1.0) * ls0 - a.sigma_scale / sig0 - nd * ls0 - phi * SA / (sig0 * sig0);
-      double lt1 = -(a.sigma_shape + 1.0) * ls1 - a.sigma_scale / sigp - nd * ls1 - phi * SA / (sigp * sigp);
+      double lt0 = -(pr.sigma_shape + 1.0) * ls0 - pr.sigma_scale / sig0 - nd * ls0 - phi * SA / (sig0 * sig0);
+      double lt1 = -(pr.sigma_shape + 1.0) * ls1 - pr.sigma_scale / sigp - nd * ls1 - phi * SA / (sigp * sigp);
       if (!lit) {   // Q24, Q23
         lt0 = lt0 - ls0 - d0 * d0 / (2.0 * sig0 * sig0);
         lt1 = lt1 - ls1 - d0 * d0 / (2.0 * sigp * sigp);
       }
       const double lacc = lit ? lt1 - lt0 : lt1 - lt0 + log(sigp / sig0);
-      if (svou_log_uniform(seed, series, it, DLM_SVOU_SLOT_ACC_SIGMA) < lacc) { acc_sig = 1; sig = sigp; }
+      if (draw_log_uniform(DLM_KEY_SVOU, seed, series, it, DLM_SVOU_SLOT_ACC_SIGMA) < lacc) { acc_sig = 1; sig = sigp; }
     }
   }
 
   // mu at the new phi and sigma, from mu0 (Q25)
   double mu = mu0;
   {
-    const double mup = mu0 + a.delta_mu * svou_normal(seed, series, it, DLM_SVOU_SLOT_Z_MU);
-    const double dl = mup - mu0, s2 = sig * sig, ps2 = a.mu_sd * a.mu_sd;
+    const double mup = mu0 + pr.delta_mu * draw_normal(DLM_KEY_SVOU, seed, series, it, DLM_SVOU_SLOT_Z_MU);
+    const double dl = mup - mu0, s2 = sig * sig, ps2 = pr.mu_sd * pr.mu_sd;
     const double Q1 = SA - 2.0 * dl * SB + dl * dl * SC;
-    const double m0 = mu0 - a.mu_mean, m1 = mup - a.mu_mean;
+    const double m0 = mu0 - pr.mu_mean, m1 = mup - pr.mu_mean;
     double lt0 = -(m0 * m0) / (2.0 * ps2) - phi * SA / s2;
     double lt1 = -(m1 * m1) / (2.0 * ps2) - phi * Q1 / s2;
     if (!lit) {   // Q24
@@ -176,7 +142,7 @@ __global__ __launch_bounds__(256) __attribute__((flatten)) void k_sv_ou_params(S
       lt0 = lt0 - d0 * d0 / (2.0 * s2);
       lt1 = lt1 - d1 * d1 / (2.0 * s2);
     }
-    if (svou_log_uniform(seed, series, it, DLM_SVOU_SLOT_ACC_MU) < lt1 - lt0) { acc_mu = 1; mu = mup; }
+    if (draw_log_uniform(DLM_KEY_SVOU, seed, series, it, DLM_SVOU_SLOT_ACC_MU) < lt1 - lt0) { acc_mu = 1; mu = mup; }
   }
 
   o[0] = phi; o[1] = mu; o[2] = sig;

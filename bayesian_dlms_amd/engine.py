@@ -48,6 +48,26 @@ def pack_params(params: Union[DlmParameters, Sequence[DlmParameters]], N: int):
             C0.reshape(-1), C0.shape[1], vts, wts)
 
 
+def _out_or_empty(be, out, name, shape, dtype=np.float64):
+    """The caller's buffer out[name], or a fresh one."""
+    return out[name] if out and name in out else be.empty(shape, dtype)
+
+
+def _counter(be, accepted, shape):
+    """The caller's int32 acceptance counter (incremented in place), or a fresh one of zeros."""
+    acc = be.put(np.zeros(shape, np.int32) if accepted is None else accepted, np.int32)
+    if tuple(acc.shape) != tuple(shape):
+        raise EngineError(f"accepted must have the shape {tuple(shape)}, got {tuple(acc.shape)}")
+    return acc
+
+
+def _as_prior(cls, prior):
+    """A prior struct of _lib as it is, or made from its fields in order (integers where the struct has them)."""
+    if isinstance(prior, cls):
+        return prior
+    return cls(*((float if t is ctypes.c_double else int)(x) for (_, t), x in zip(cls._fields_, tuple(prior), strict=True)))
+
+
 class _Host:
     mem = _lib.DLM_MEM_HOST
 
@@ -323,19 +343,15 @@ class Engine:
         tb, sb = be.put(theta), be.put(stats)
         scb, nub = be.put(scale), be.put(nu, np.int32)
         Fb = be.put(mat.F)
-        out = out or {}
-        v = out["v"] if "v" in out else be.empty((N, T))
-        sc_out = out["scale"] if "scale" in out else be.empty((N,))
-        nu_out = out["nu"] if "nu" in out else be.empty((N,), np.int32)
-        W = out["W"] if "W" in out else be.empty((N, d * d))
-        acc = be.put(accepted, np.int32) if accepted is not None else None
-        if acc is None:
-            acc = be.empty((N,), np.int32)
-            acc[...] = 0
+        v = _out_or_empty(be, out, "v", (N, T))
+        sc_out = _out_or_empty(be, out, "scale", (N,))
+        nu_out = _out_or_empty(be, out, "nu", (N,), np.int32)
+        W = _out_or_empty(be, out, "W", (N, d * d))
+        acc = _counter(be, accepted, (N,))
         ll = be.empty((N,)) if want_loglik else None
         status = be.empty((N,), np.int32)
         md = _lib.ModelDesc(d, mat.p, T, N, be.ptr(Fb).value, mat.f_stride, None, mat.n_g, None, None)
-        pr = _lib.StudentTPrior(*(float(x) for x in prior))
+        pr = _as_prior(_lib.StudentTPrior, prior)
         op = _lib.Options(flags | (_lib.OPT_STUDENTT_LITERAL if literal else 0), be.mem, seed, series_offset)
         self._hold(flags, yb, tb, sb, scb, nub, Fb)
         self._check(self.lib.dlm_studentt_step_batch(self.h, md, be.ptr(yb), be.ptr(tb), be.ptr(sb), pr, be.ptr(scb),
@@ -355,12 +371,9 @@ class Engine:
         ab = be.put(alpha)
         if ab is not None and tuple(ab.shape) != (N, T + 1):
             raise EngineError(f"alpha must be [N][T+1] = {(N, T + 1)}, got {tuple(ab.shape)}")
-        out = out or {}
-        ystar = out["ystar"] if "ystar" in out else be.empty((N, T))
-        v = out["v"] if "v" in out else be.empty((N, T))
-        k = None
-        if want_k and ab is not None:
-            k = out["k"] if "k" in out else be.empty((N, T), np.int8)
+        ystar = _out_or_empty(be, out, "ystar", (N, T))
+        v = _out_or_empty(be, out, "v", (N, T))
+        k = _out_or_empty(be, out, "k", (N, T), np.int8) if want_k and ab is not None else None
         status = be.empty((N,), np.int32)
         op = _lib.Options(flags, be.mem, seed, series_offset)
         self._hold(flags, yb, ab)
@@ -374,28 +387,7 @@ class Engine:
         fields in order (phi_update, literal, phi_a, phi_b, mu_mean, mu_sd, sigma_shape, sigma_scale, prop_lambda, prop_tau).
         accepted [N] int32 is incremented in place (None: a fresh zero array).  Returns {"sv" [N][3], "accepted", "status"}.
         out: dict with an existing "sv" buffer to write into (it may be the input)."""
-        be = self._backend(alpha)
-        N, T = int(alpha.shape[0]), int(alpha.shape[1]) - 1
-        ab, sb = be.put(alpha), be.put(sv)
-        if tuple(sb.shape) != (N, 3):
-            raise EngineError(f"sv must be [N][3] = {(N, 3)}, got {tuple(sb.shape)}")
-        if isinstance(prior, _lib.SvPrior):
-            pr = prior
-        else:
-            f = tuple(prior)
-            pr = _lib.SvPrior(int(f[0]), int(f[1]), *(float(x) for x in f[2:]))
-        out = out or {}
-        sv_out = out["sv"] if "sv" in out else be.empty((N, 3))
-        acc = be.put(accepted, np.int32) if accepted is not None else None
-        if acc is None:
-            acc = be.empty((N,), np.int32)
-            acc[...] = 0
-        status = be.empty((N,), np.int32)
-        op = _lib.Options(flags, be.mem, seed, series_offset)
-        self._hold(flags, ab, sb)
-        self._check(self.lib.dlm_sv_params_batch(self.h, N, T, be.ptr(ab), be.ptr(sb), pr, int(iteration), op, be.ptr(sv_out),
-                                                 be.ptr(acc), be.ptr(status)))
-        return {"sv": sv_out, "accepted": acc, "status": status}
+        return self._sv_params(None, alpha, sv, prior, iteration, accepted, seed, series_offset, flags, out)
 
     def sv_ou_params(self, times, alpha, sv, prior, *, iteration, accepted=None, seed=0, series_offset=0, flags=0, out=None):
         """phi, sigma, mu of the stochastic-volatility sampler with Ornstein-Uhlenbeck log-volatility given the state draw
@@ -405,32 +397,26 @@ class Engine:
         prop_lambda, prop_tau, delta_sigma, delta_mu).  accepted [N][3] int32 (phi, sigma, mu) is incremented in place (None: a fresh
         zero array).  Returns {"sv" [N][3], "accepted", "status"}.  out: dict with an existing "sv" buffer to write into (it may be
         the input)."""
+        return self._sv_params(times, alpha, sv, prior, iteration, accepted, seed, series_offset, flags, out)
+
+    def _sv_params(self, times, alpha, sv, prior, iteration, accepted, seed, series_offset, flags, out):
+        """sv_params (times=None: one acceptance counter per series) and sv_ou_params (its grid; three counters per series)."""
+        ou = times is not None
         be = self._backend(alpha)
         N, T = int(alpha.shape[0]), int(alpha.shape[1]) - 1
-        ab, sb = be.put(alpha), be.put(sv)
-        tb = be.put(times)
-        if tuple(tb.shape) != (T,):
+        ab, sb, tb = be.put(alpha), be.put(sv), be.put(times)
+        if ou and tuple(tb.shape) != (T,):
             raise EngineError(f"times must be [T] = {(T,)}, got {tuple(tb.shape)}")
         if tuple(sb.shape) != (N, 3):
             raise EngineError(f"sv must be [N][3] = {(N, 3)}, got {tuple(sb.shape)}")
-        if isinstance(prior, _lib.SvOuPrior):
-            pr = prior
-        else:
-            f = tuple(prior)
-            pr = _lib.SvOuPrior(int(f[0]), *(float(x) for x in f[1:]))
-        out = out or {}
-        sv_out = out["sv"] if "sv" in out else be.empty((N, 3))
-        acc = be.put(accepted, np.int32) if accepted is not None else None
-        if acc is None:
-            acc = be.empty((N, 3), np.int32)
-            acc[...] = 0
-        elif tuple(acc.shape) != (N, 3):
-            raise EngineError(f"accepted must be [N][3] = {(N, 3)}, got {tuple(acc.shape)}")
+        pr = _as_prior(_lib.SvOuPrior if ou else _lib.SvPrior, prior)
+        sv_out = _out_or_empty(be, out, "sv", (N, 3))
+        acc = _counter(be, accepted, (N, 3) if ou else (N,))
         status = be.empty((N,), np.int32)
         op = _lib.Options(flags, be.mem, seed, series_offset)
         self._hold(flags, tb, ab, sb)
-        self._check(self.lib.dlm_sv_ou_params_batch(self.h, N, T, be.ptr(tb), be.ptr(ab), be.ptr(sb), pr, int(iteration), op,
-                                                    be.ptr(sv_out), be.ptr(acc), be.ptr(status)))
+        call, grid = (self.lib.dlm_sv_ou_params_batch, (be.ptr(tb),)) if ou else (self.lib.dlm_sv_params_batch, ())
+        self._check(call(self.h, N, T, *grid, be.ptr(ab), be.ptr(sb), pr, int(iteration), op, be.ptr(sv_out), be.ptr(acc), be.ptr(status)))
         return {"sv": sv_out, "accepted": acc, "status": status}
 
     def simulate(self, mat, params, N, *, seed=0, series_offset=0, device=False, want_x=True):

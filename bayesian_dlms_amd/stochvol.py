@@ -32,6 +32,7 @@ from typing import Callable, Iterator, Optional
 import numpy as np
 
 from . import _lib
+from ._chain import host, or_status, place
 from .gibbs import InverseGamma
 
 MASK64 = (1 << 64) - 1
@@ -62,14 +63,6 @@ class Beta:
 
     def draw(self, rng: np.random.Generator):
         return rng.beta(self.a, self.b)
-
-
-def _is_torch(a):
-    return hasattr(a, "data_ptr")
-
-
-def _host(a):
-    return a.detach().cpu().numpy() if _is_torch(a) else np.asarray(a)
 
 
 def initial_parameters(prior_phi, prior_mu: Gaussian, prior_sigma: InverseGamma, n_series: int, *, seed: int = 0,
@@ -154,7 +147,7 @@ class StochasticVolatility:
         mix = run_mix(y, None, iteration=0, seed=seed, series_offset=series_offset, out=out)
         f = run_ffbs(mix["ystar"], mix["v"], sv, seed=StochasticVolatility._seed_ffbs(seed, 0), series_offset=series_offset,
                      want_filt=False, want_theta=True, **grid)
-        return {"alpha": f["theta"], "ystar": mix["ystar"], "v": mix["v"], "status": _or_status(mix.get("status"), f.get("status"))}
+        return {"alpha": f["theta"], "ystar": mix["ystar"], "v": mix["v"], "status": or_status(mix.get("status"), f.get("status"))}
 
     @staticmethod
     def sample_state_ar(y, alpha, sv, engine, *, iteration: int, seed: int = 0, series_offset: int = 0,
@@ -168,7 +161,7 @@ class StochasticVolatility:
         mix = run_mix(y, alpha, iteration=iteration, seed=seed, series_offset=series_offset, out=out)
         f = run_ffbs(mix["ystar"], mix["v"], sv, seed=StochasticVolatility._seed_ffbs(seed, iteration + 1), series_offset=series_offset,
                      want_filt=False, want_theta=True, **grid)
-        return {"alpha": f["theta"], "ystar": mix["ystar"], "v": mix["v"], "status": _or_status(mix.get("status"), f.get("status"))}
+        return {"alpha": f["theta"], "ystar": mix["ystar"], "v": mix["v"], "status": or_status(mix.get("status"), f.get("status"))}
 
     @staticmethod
     def _sample(ys, prior, beta, prior_phi, prior_mu, prior_sigma, engine, *, n_iter, seed, params0, series_offset, keep_alpha,
@@ -180,15 +173,7 @@ class StochasticVolatility:
         if T < 2:
             raise ValueError("the stochastic-volatility sampler needs T >= 2 (the reference's sums throw on a single observation)")
         run_params = params if params is not None else (engine.sv_ou_params if ou else engine.sv_params)
-        torch = None
-        dev = None
-        if _is_torch(ys) or engine is not None:
-            import torch
-            dev = ys.device if _is_torch(ys) else torch.device("cuda", engine.device)
-        def put(a, dtype=np.float64):
-            a = np.ascontiguousarray(a, dtype=dtype)
-            return torch.as_tensor(a, device=dev) if torch is not None else a
-        y = ys.reshape(N, T).to(dtype=torch.float64).contiguous() if _is_torch(ys) else put(np.asarray(ys, dtype=np.float64).reshape(N, T))
+        put, y = place(ys, engine, N, T)
         if params0 is None:
             sv_h = initial_parameters(prior_phi, prior_mu, prior_sigma, N, seed=seed, series_offset=series_offset, sigma_squared=not ou)
         else:
@@ -201,7 +186,7 @@ class StochasticVolatility:
         acc = put(np.zeros((N, 3) if ou else N, dtype=np.int32), np.int32)
         grid, lead = {}, ()
         if ou:
-            tgrid = _host(times).astype(np.float64)
+            tgrid = host(times).astype(np.float64)
             if tgrid.shape != (T,):
                 raise ValueError(f"times must be [T] = {(T,)}, got {tgrid.shape}")
             tgrid = put(tgrid)
@@ -216,11 +201,11 @@ class StochasticVolatility:
             res = run_params(*lead, alpha, sv, prior, iteration=it, accepted=acc, seed=seed, series_offset=series_offset,
                              out={"sv": sv})
             sv, acc = res["sv"], res["accepted"]
-            status = _or_status(st["status"], res.get("status"))
+            status = or_status(st["status"], res.get("status"))
             if it == 0:
-                status = _or_status(status, status0)
-            yield StochasticVolatility.State(_host(sv).copy(), _host(alpha).copy() if keep_alpha else None,
-                                             _host(acc).astype(np.int32), status)
+                status = or_status(status, status0)
+            yield StochasticVolatility.State(host(sv).copy(), host(alpha).copy() if keep_alpha else None,
+                                             host(acc).astype(np.int32), status)
 
     @staticmethod
     def sample_uni(ys, prior_phi: Gaussian, prior_mu: Gaussian, prior_sigma: InverseGamma, engine, *, n_iter: int, seed: int = 0,
@@ -276,10 +261,3 @@ class StochasticVolatility:
                                             params0=params0, series_offset=series_offset, keep_alpha=keep_alpha, ffbs=ffbs,
                                             mixture=mixture, params=params, times=times)
 
-
-def _or_status(a, b):
-    if a is None and b is None:
-        return None
-    a = 0 if a is None else _host(a).astype(np.int32)
-    b = 0 if b is None else _host(b).astype(np.int32)
-    return np.asarray(a | b, dtype=np.int32)

@@ -27,6 +27,7 @@ from typing import Callable, Iterator, Optional
 import numpy as np
 
 from . import _lib
+from ._chain import host, or_status, place
 from .dlm import Dlm, DlmParameters, materialise
 from .gibbs import InverseGamma
 
@@ -52,14 +53,6 @@ class NegativeBinomialProposal:
     size: float
 
 
-def _is_torch(a):
-    return hasattr(a, "data_ptr")
-
-
-def _host(a):
-    return a.detach().cpu().numpy() if _is_torch(a) else np.asarray(a)
-
-
 def initial_nu(prior_nu: Poisson, n_series: int, *, seed: int = 0, series_offset: int = 0) -> np.ndarray:
     """nu_0 per series drawn from the prior on the host by a generator keyed by (seed, global series index) -- a sharded run
     starts where the single-GPU run does -- and redrawn while it is 0 (a chain at nu = 0 is NaN from its first step)."""
@@ -83,7 +76,7 @@ class StudentT:
         d: int
 
         def w_diag(self) -> np.ndarray:
-            w = _host(self.W).reshape(-1, self.d, self.d)
+            w = host(self.W).reshape(-1, self.d, self.d)
             return np.diagonal(w, axis1=1, axis2=2).copy()
 
     @dataclass
@@ -127,15 +120,7 @@ class StudentT:
         run_step = step if step is not None else engine.studentt_step
 
         # where the chain lives: a torch device (an engine, or a device tensor given), else host arrays (injected callables)
-        torch = None
-        dev = None
-        if _is_torch(ys) or engine is not None:
-            import torch
-            dev = ys.device if _is_torch(ys) else torch.device("cuda", engine.device)
-        def put(a, dtype=np.float64):
-            a = np.ascontiguousarray(a, dtype=dtype)
-            return torch.as_tensor(a, device=dev) if torch is not None else a
-        y = ys.reshape(N, T).to(dtype=torch.float64).contiguous() if _is_torch(ys) else put(np.asarray(ys, dtype=np.float64).reshape(N, T))
+        put, y = place(ys, engine, N, T)
 
         if nu0 is None:
             nu_h = initial_nu(prior_nu, N, seed=seed, series_offset=series_offset)
@@ -164,10 +149,8 @@ class StudentT:
             res = run_step(mat, y, theta, stats, prior, s_in, nu, iteration=it, accepted=acc, seed=seed,
                            series_offset=series_offset, literal=literal)
             vs, s, nu, W, acc = res["v"], res["scale"], res["nu"], res["W"], res["accepted"]
-            status = _host(res["status"]).astype(np.int32) if res.get("status") is not None else None
-            if fstatus is not None:
-                status = _host(fstatus).astype(np.int32) | (status if status is not None else 0)
-            yield StudentT.State(StudentT.Params(_host(s).copy(), W, d), _host(vs).copy() if keep_variances else None,
-                                 _host(nu).astype(np.int32), _host(theta).copy() if keep_theta else None,
-                                 _host(acc).astype(np.int32),
-                                 _host(res["loglik"]).copy() if res.get("loglik") is not None else None, status)
+            status = or_status(fstatus, res.get("status"))
+            yield StudentT.State(StudentT.Params(host(s).copy(), W, d), host(vs).copy() if keep_variances else None,
+                                 host(nu).astype(np.int32), host(theta).copy() if keep_theta else None,
+                                 host(acc).astype(np.int32),
+                                 host(res["loglik"]).copy() if res.get("loglik") is not None else None, status)

@@ -433,9 +433,9 @@ def st_checks(case, nu, W, v, theta, y, start=None):
 
 
 def st_sweep_host(case, state, it, mutant=None, seed=SEED, rng=None):
-    """One sweep on the CPU: theta | (v, W, y) by the oracle with the V_t stream v, then the NumPy `step` of tests/test_studentt_gpu.py
+    """One sweep on the CPU: theta | (v, W, y) by the oracle with the V_t stream v, then the NumPy `step` of tests/sampler_restatement.py
     (imported: the restatement the kernel is pinned to draw for draw) with scale_in = s; its scale_out is ignored.  The mutants wrap it."""
-    import test_studentt_gpu as st
+    import sampler_restatement as st
     rng = np.random.default_rng([seed, 5, it]) if rng is None else rng
     mat = case.mat
     d, T = mat.d, mat.T
@@ -472,12 +472,12 @@ def _nu_move_without_proposal(st, case, y, theta, nu0, seed, series, it):
     on the ratio of the targets alone."""
     from scipy import stats as ss
     lam, r = case.prior[0], case.prior[1]
-    g = st.gamma_unit(r, seed, series, it, st.SLOT_PROP_GAMMA, st.KEY_STUDENTT)[0]
+    g = st.gamma_unit(r, seed, series, it, st.ST_SLOT_PROP_GAMMA, st.KEY_STUDENTT)[0]
     nup = st.poisson(g * (nu0 / r), seed, series, it) + 1.0
     e = y - np.einsum("td,td->t", case.F[:, :, 0], theta[1:])
     e = e[~np.isnan(e)]
     target = lambda nu: ss.t.logpdf(e, nu, scale=math.sqrt(case.scale)).sum() + nu * math.log(lam) - math.lgamma(nu + 1.0)
-    u = st.gibbs_rand(seed, series, it, [st.SLOT_ACCEPT], 0, 0, st.KEY_STUDENTT)[0][0]
+    u = st.gibbs_rand(seed, series, it, [st.ST_SLOT_ACCEPT], 0, 0, st.KEY_STUDENTT)[0][0]
     return int(nup) if math.log(u) < target(nup) - target(float(nu0)) else nu0
 
 

@@ -886,7 +886,7 @@ def test_gibbs_dinvgamma_recovers_variances(eng):
 def test_gibbs_per_series_engine_matches_oracle_ffbs(eng):
     """Per-series Gibbs through the engine equals the same chain driven by the oracle's FFBS."""
     from bayesian_dlms_amd.gibbs import GibbsSampling, InverseGamma
-    from test_host_logic import oracle_ffbs
+    from oracle_gibbs import oracle_ffbs
     mod = Dlm.polynomial(2)
     times = np.arange(1, 41, dtype=np.float64)
     mat = materialise(mod, times)

@@ -7,7 +7,7 @@ import sys
 import numpy as np
 import pytest
 
-import oracle
+from oracle_gibbs import oracle_ffbs, toy
 from bayesian_dlms_amd.dlm import (Data, Dlm, DlmParameters, angle, block_diagonal, materialise,
                                    rotation_matrix, seasonal_g)
 from bayesian_dlms_amd.engine import pack_params
@@ -92,36 +92,9 @@ def test_shard_bounds_cover_everything():
 # ------------------------------------------------------------------------------------------
 # Gibbs host logic with the oracle standing in for the engine's FFBS (no GPU needed)
 # ------------------------------------------------------------------------------------------
-def oracle_ffbs(mat, params, y, *, seed=0, series_offset=0, flags=0, want_theta=True, want_stats=True, **kw):
-    om = oracle.Model(mat.d, mat.p, mat.T, mat.F, mat.G, mat.g_index, mat.dt, mat.f_stride)
-    plist = [params] * y.shape[0] if isinstance(params, DlmParameters) else list(params)
-    outer = bool(flags & 16)
-    thetas, stats = [], []
-    for n in range(y.shape[0]):
-        p = plist[n]
-        f = oracle.kf_filter(om, p.v, p.w, p.m0, p.c0, y[n])
-        z = oracle.normals(seed, series_offset + n, mat.T + 1, mat.d)
-        th = oracle.backward_sample(om, p.w, f, z, factor="chol")["theta"]
-        st = oracle.gibbs_stats(om, y[n], th, want_outer=outer)
-        body = st["outer"] if outer else st["ss"]
-        stats.append(np.concatenate([st["ssy"], st["n"], body, [mat.T]]))
-        thetas.append(th)
-    return {"theta": np.stack(thetas), "stats": np.stack(stats)}
-
-
-def _toy(N=6, T=40, seed=0):
-    mod = Dlm.polynomial(2)
-    times = np.arange(1, T + 1, dtype=np.float64)
-    rng = np.random.default_rng(seed)
-    y = rng.standard_normal((N, T, 1)).cumsum(axis=1)
-    y[rng.random(y.shape) < 0.1] = np.nan
-    p = DlmParameters([[2.0]], np.diag([0.5, 0.2]), [0.0, 0.0], np.eye(2) * 10)
-    return mod, times, y, p
-
-
 def test_gibbs_per_series_is_shard_invariant():
     """Per-series Gibbs: running a shard with its series_offset reproduces the full-batch chain."""
-    mod, times, y, p = _toy()
+    mod, times, y, p = toy()
     pv, pw = InverseGamma(5.0, 4.0), InverseGamma(17.0, 4.0)
     full = list(GibbsSampling.sample(mod, pv, pw, p, times, y, None, n_iter=3, seed=7, ffbs=oracle_ffbs))
     lo, hi = shard_bounds(6, 2, 1)
@@ -148,7 +121,7 @@ def test_gibbs_posterior_parameters():
 
 
 def test_gibbs_wishart_runs_and_is_spd():
-    mod, times, y, p = _toy(N=2, T=30)
+    mod, times, y, p = toy(N=2, T=30)
     out = list(GibbsWishart.sample(mod, InverseGamma(5.0, 4.0), InverseWishart(5.0, np.eye(2)), p, times, y, None,
                                    n_iter=2, seed=3, ffbs=oracle_ffbs))
     w = out[-1].p[0].w
@@ -165,10 +138,10 @@ import numpy as np
 import torch, torch.distributed as dist
 sys.path.insert(0, os.environ["DLM_ROOT"]); sys.path.insert(0, os.path.join(os.environ["DLM_ROOT"], "tests"))
 from bayesian_dlms_amd.gibbs import GibbsSampling, InverseGamma, shard_bounds
-from test_host_logic import oracle_ffbs, _toy
+from oracle_gibbs import oracle_ffbs, toy
 rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
 dist.init_process_group("gloo", rank=rank, world_size=world)
-mod, times, y, p = _toy()
+mod, times, y, p = toy()
 lo, hi = shard_bounds(y.shape[0], world, rank)
 def allreduce(a):
     t = torch.from_numpy(np.ascontiguousarray(a)); dist.all_reduce(t); return t.numpy()
@@ -191,7 +164,7 @@ def test_pooled_gibbs_two_ranks_gloo(tmp_path):
     r0, r1 = np.load(tmp_path / "rank0.npy"), np.load(tmp_path / "rank1.npy")
     np.testing.assert_array_equal(r0, r1)                     # every rank makes the same draw
     # ... and it is the chain a single process gets on the whole batch
-    mod, times, y, p = _toy()
+    mod, times, y, p = toy()
     one = list(GibbsSampling.sample(mod, InverseGamma(5.0, 4.0), InverseGamma(17.0, 4.0), p, times, y, None,
                                     n_iter=3, seed=11, pooled=True, ffbs=oracle_ffbs))
     ref = np.array([np.concatenate([np.diag(s.p.v), np.diag(s.p.w)]) for s in one])
@@ -286,31 +259,13 @@ def test_option_flags_agree_between_header_python_and_scala():
         assert by_camel.get(n.lower()) == sh, n
 
 
-def test_per_wave_kernels_keep_their_registers(tmp_path):
+def test_per_wave_kernels_keep_their_registers():
     """The 16 <= d <= 48 kernels live at the 512-register limit of a wave and the allocator's choices for a whole kernel turn on a
     few instructions: in round 4 ONE store added inside k_filter_w48's time loop took the C4 instantiation from 474 registers and no
     scratch to 395 spilled values (every-step C4 forward pass 24 -> 48 ms, 4 x the algorithmic HBM traffic by PMC) without failing
     a single parity test.  The code object of the built dlm_wave48.o is checked here (seconds: no compilation)."""
-    import re
-    import subprocess
-    from bayesian_dlms_amd import build as b
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    obj = os.path.join(root, "bayesian_dlms_amd", "build", "dlm_wave48.o")
-    if not os.path.exists(obj):
-        b.build()
-    llvm = "/opt/rocm/lib/llvm/bin"
-    fat, co = str(tmp_path / "fat.bin"), str(tmp_path / "w48.co")
-    subprocess.check_call([f"{llvm}/llvm-objcopy", "--dump-section", f".hip_fatbin={fat}", obj])
-    subprocess.check_call([f"{llvm}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"])
-    notes = subprocess.run([f"{llvm}/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
-    meta = {}
-    for blk in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:
-        get = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1))
-        meta[re.search(r"\.name:\s+(\S+)", blk).group(1)] = (get("private_segment_fixed_size"), get("vgpr_spill_count"))
-    def of(frag):
-        hit = [v for k, v in meta.items() if frag in k]
-        assert len(hit) == 1, (frag, [k for k in meta if frag.split("IL")[0] in k][:4])
-        return hit[0]
+    from code_object import kernel_resources
+    of = lambda frag: kernel_resources("dlm_wave48.o", frag)[:2]
     # <DT, PT, K, KF>: (3, 2, 2, 1) is C4 (d = 40, p = 20, structured F), (2, 1, 2, 1) d = 20 / p = 10
     assert of("k_filter_w48ILi3ELi2ELi2ELi1E") == (0, 0)
     assert of("k_filter_w48ILi2ELi1ELi2ELi1E") == (0, 0)

@@ -2,8 +2,8 @@
 sampleSigma) and the StochasticVolatility.sample_uni / sample_beta drivers.
 
 First a NumPy restatement of both kernels (bayesian_dlms_amd/csrc/dlm_sv.hip), operation for operation and in the same summation
-order: the Philox stream, gibbs_rand, gamma_unit and the lane-sequential sums with their xor butterfly come from
-tests/test_studentt_gpu.py.  The tests compare the kernels with it draw for draw, then check the distributions, the Beta chain's
+order: the mixture call's is here, the parameter call's (`params_step`) and the draws it is built on come from
+tests/sampler_restatement.py.  The tests compare the kernels with it draw for draw, then check the distributions, the Beta chain's
 target, the invariances and the drivers.
 
 On the shapes of the draw-for-draw parameter test: with T = 2 the default sums hold the two pairs (alpha_0, alpha_1), (alpha_1, alpha_2)
@@ -18,10 +18,9 @@ from bayesian_dlms_amd import _lib
 from bayesian_dlms_amd.engine import Engine, EngineError
 from bayesian_dlms_amd.gibbs import InverseGamma
 from bayesian_dlms_amd.stochvol import Beta, Gaussian, StochasticVolatility, SvParameters
-from test_studentt_gpu import gamma_unit, gibbs_rand, wave_sum
+from sampler_restatement import KEY_SV, gibbs_rand, params_step
+from sampler_restatement import sv_prior as prior, sv_prior_tuple as as_tuple
 
-KEY_SV = 0x5354564F
-SLOT_PHI, SLOT_MU, SLOT_SIGMA, SLOT_PROP_A, SLOT_PROP_B, SLOT_ACCEPT = 0x1FFFFF, 0x1FFFFE, 0x1FFFFD, 0x1FFFFC, 0x1FFFFB, 0x1FFFFA
 # the mixture of Kim, Shephard & Chib as StochasticVolatility.scala:42-44 has it
 PIS = np.array([0.0073, 0.1056, 0.00002, 0.044, 0.34, 0.2457, 0.2575])
 MEANS = np.array([-11.4, -5.24, -9.84, 1.51, -0.65, 0.53, -2.36])
@@ -64,93 +63,6 @@ def mixture(y, alpha, *, seed, series_offset, it):
     margin = np.abs(us[..., None] - p[..., :6]).min(axis=-1) / p[..., 6]
     ystar = np.where(obs, ly - MEANS[k], np.nan)
     return ystar, VARS[k], k, np.where(degenerate.any(axis=1), _lib.ST_NONFINITE, 0), margin
-
-
-def normal(seed, series, it, slot, k):
-    u1, u2 = gibbs_rand(seed, series, it, [slot], k, 0, KEY_SV)
-    return math.sqrt(-2.0 * math.log(u1[0])) * math.cos(6.283185307179586476925286766559 * u2[0])
-
-
-def params_step(al, sv, pr, *, seed, series, it):
-    """One series of k_sv_params.  al [T+1]; sv = (phi, mu, sigma); pr: the ten fields of dlm_sv_prior as a dict.
-    -> (phi, mu, sigma, accepted, status, attempts)."""
-    T = al.size - 1
-    lit, beta = bool(pr["literal"]), bool(pr["phi_update"])
-    phi0, mu0, sig0 = (float(x) for x in sv)
-    if not (math.isfinite(phi0) and math.isfinite(mu0) and sig0 > 0.0 and sig0 < math.inf) or (beta and not 0.0 < phi0 < 1.0):
-        return math.nan, math.nan, math.nan, 0, _lib.ST_NONFINITE, 0
-    s2 = sig0 * sig0
-    a0, a1, aT = al[0], al[1], al[T]
-    prev, cur = al[1:T], al[2:T + 1]             # the pairs t = 2..T
-    st, acc, attempts, phi = 0, 0, 0, phi0
-    if not beta:
-        p, c = prev - mu0, cur - mu0
-        d0, d1, dT = a0 - mu0, a1 - mu0, aT - mu0
-        S = wave_sum(p * p) + (dT * dT if lit else d0 * d0)
-        S2 = wave_sum(p * c) + (0.0 if lit else d0 * d1)
-        psi2 = pr["phi_b"] * pr["phi_b"]
-        prec = 1.0 / psi2 + S if lit else 1.0 / psi2 + S / s2
-        mean = (pr["phi_a"] / psi2 + S2) / prec if lit else (pr["phi_a"] / psi2 + S2 / s2) / prec
-        sd = math.sqrt(1.0 / prec)
-        if lit:
-            phi, attempts = mean + sd * normal(seed, series, it, SLOT_PHI, 0), 1
-        else:
-            ok = False
-            for k in range(1023):
-                cand = mean + sd * normal(seed, series, it, SLOT_PHI, k)
-                attempts += 1
-                if abs(cand) < 1.0:
-                    phi, ok = cand, True
-                    break
-            if not ok:
-                st |= _lib.ST_NOT_PD
-    else:
-        lam, tau = pr["prop_lambda"], pr["prop_tau"]
-        A0, B0 = lam * phi0 + tau, lam * (1.0 - phi0) + tau
-        ga = gamma_unit(A0, seed, series, it, SLOT_PROP_A, KEY_SV)[0]
-        gb = gamma_unit(B0, seed, series, it, SLOT_PROP_B, KEY_SV)[0]
-        phip = ga / (ga + gb)
-        p, c = prev - mu0, cur - mu0
-        r0, r1 = c - phi0 * p, c - phip * p
-        d0, d1 = a0 - mu0, a1 - mu0
-        f0, f1 = d1 - phi0 * d0, d1 - phip * d0
-        Q0 = wave_sum(r0 * r0) + (0.0 if lit else f0 * f0)
-        Q1 = wave_sum(r1 * r1) + (0.0 if lit else f1 * f1)
-        A1, B1 = lam * phip + tau, lam * (1.0 - phip) + tau
-        if 0.0 < phip < 1.0:
-            lg, log = math.lgamma, math.log
-            pa, pb = pr["phi_a"], pr["phi_b"]
-            o0, o1 = 1.0 - phi0 * phi0, 1.0 - phip * phip
-            lt0 = (pa - 1.0) * log(phi0) + (pb - 1.0) * log(1.0 - phi0) + 0.5 * log(o0) - 0.5 * d0 * d0 * o0 / s2 - 0.5 * Q0 / s2
-            lt1 = (pa - 1.0) * log(phip) + (pb - 1.0) * log(1.0 - phip) + 0.5 * log(o1) - 0.5 * d0 * d0 * o1 / s2 - 0.5 * Q1 / s2
-            lq_fwd = lg(A0 + B0) - lg(A0) - lg(B0) + (A0 - 1.0) * log(phip) + (B0 - 1.0) * log(1.0 - phip)
-            lq_back = lg(A1 + B1) - lg(A1) - lg(B1) + (A1 - 1.0) * log(phi0) + (B1 - 1.0) * log(1.0 - phi0)
-            lacc = lt1 - lt0 + lq_back - lq_fwd
-            u1, _ = gibbs_rand(seed, series, it, [SLOT_ACCEPT], 0, 0, KEY_SV)
-            if math.log(u1[0]) < lacc:
-                acc, phi = 1, phip
-    M = wave_sum(cur - phi * prev) + (0.0 if lit else a1 - phi * a0)
-    pm2, omp, Td = pr["mu_sd"] * pr["mu_sd"], 1.0 - phi, float(T)
-    mprec = 1.0 / pm2 + (Td - 1.0) * omp * omp if lit else 1.0 / pm2 + Td * omp * omp / s2
-    mmean = (pr["mu_mean"] / pm2 + omp * M) / mprec if lit else (pr["mu_mean"] / pm2 + omp / s2 * M) / mprec
-    mu = mmean + math.sqrt(1.0 / mprec) * normal(seed, series, it, SLOT_MU, 0)
-    r = (cur - mu) - phi * (prev - mu)
-    fr = (a1 - mu) - phi * (a0 - mu)
-    Q = wave_sum(r * r) + (0.0 if lit else fr * fr)
-    shape = pr["sigma_shape"] + ((Td + 1.0) * 0.5 if lit else Td * 0.5)
-    scale = pr["sigma_scale"] + 0.5 * Q
-    sig = math.sqrt(scale / gamma_unit(shape, seed, series, it, SLOT_SIGMA, KEY_SV)[0])
-    return phi, mu, sig, acc, st, attempts
-
-
-def prior(phi_update, literal, phi_a, phi_b, mu=(1.0, 2.0), sigma=(3.0, 0.5), prop=(100.0, 0.05)):
-    return dict(phi_update=phi_update, literal=literal, phi_a=phi_a, phi_b=phi_b, mu_mean=mu[0], mu_sd=mu[1], sigma_shape=sigma[0],
-                sigma_scale=sigma[1], prop_lambda=prop[0], prop_tau=prop[1])
-
-
-def as_tuple(pr):
-    return tuple(pr[k] for k in ("phi_update", "literal", "phi_a", "phi_b", "mu_mean", "mu_sd", "sigma_shape", "sigma_scale",
-                                 "prop_lambda", "prop_tau"))
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

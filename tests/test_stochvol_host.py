@@ -1,17 +1,12 @@
 """The stochastic-volatility driver (bayesian_dlms_amd/stochvol.py) without a GPU: what it passes to its three engine calls (injected
 fakes), the initial parameters, and the code object of the two kernels (dlm_sv.o: no scratch, no spills)."""
-import os
-import re
-import subprocess
-
 import numpy as np
 import pytest
 
 from bayesian_dlms_amd import _lib
 from bayesian_dlms_amd.gibbs import InverseGamma
 from bayesian_dlms_amd.stochvol import Beta, Gaussian, StochasticVolatility, SvParameters, initial_parameters
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from code_object import kernel_resources
 
 
 class _Fakes:
@@ -165,24 +160,8 @@ def test_simulate_has_the_models_moments():
     assert abs(np.mean((y * np.exp(-0.5 * alpha[:, 1:])) ** 2) - 1.0) < 0.03
 
 
-def test_sv_kernels_have_no_scratch_and_no_spills(tmp_path):
+def test_sv_kernels_have_no_scratch_and_no_spills():
     """dlm_sv.o's code object: k_sv_mixture and k_sv_params keep everything in registers (read as tests/test_studentt_host.py reads
     dlm_studentt.o)."""
-    from bayesian_dlms_amd import build as b
-    obj = os.path.join(ROOT, "bayesian_dlms_amd", "build", "dlm_sv.o")
-    if not os.path.exists(obj):
-        b.build()
-    llvm = "/opt/rocm/lib/llvm/bin"
-    fat, co = str(tmp_path / "fat.bin"), str(tmp_path / "sv.co")
-    subprocess.check_call([f"{llvm}/llvm-objcopy", "--dump-section", f".hip_fatbin={fat}", obj])
-    subprocess.check_call([f"{llvm}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}",
-                           "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"])
-    notes = subprocess.run([f"{llvm}/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
-    meta = {}
-    for blk in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:
-        get = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1))
-        meta[re.search(r"\.name:\s+(\S+)", blk).group(1)] = (get("private_segment_fixed_size"), get("vgpr_spill_count"))
     for kernel in ("k_sv_mixture", "k_sv_params"):
-        hit = [v for k, v in meta.items() if kernel in k]
-        assert len(hit) == 1, sorted(meta)
-        assert hit[0] == (0, 0), (kernel, hit)
+        assert kernel_resources("dlm_sv.o", kernel)[:2] == (0, 0), kernel

@@ -1,14 +1,11 @@
 """dlm_sv_ou_params_batch on the GPU (StochasticVolatility.samplePhiOu, sampleSigmaMetropOu, sampleMuOu in stepOu's order) and the
 StochasticVolatility.sample_ou driver.
 
-First a NumPy restatement of the kernel (bayesian_dlms_amd/csrc/dlm_sv_ou.hip), operation for operation and in the same summation
-order: the Philox stream, gibbs_rand, gamma_unit and the lane-sequential sums with their xor butterfly come from
-tests/test_studentt_gpu.py.  `sweep` is the same arithmetic vectorised over the chains on NumPy's generator, with switches for the
+The NumPy restatement of the kernel (bayesian_dlms_amd/csrc/dlm_sv_ou.hip), operation for operation and in the same summation
+order, is `ou_params_step` of tests/sampler_restatement.py.  `sweep` is the same arithmetic vectorised over the chains on NumPy's generator, with switches for the
 two corrections (Q23, Q24): the invariance test was rehearsed with it (profiles/r11_notes.md).  The tests compare the kernel with the
 restatement draw for draw, then check that the sampler leaves its target invariant, the bit-for-bit invariances, the bad rows, the
 argument errors and the driver."""
-import math
-
 import numpy as np
 import pytest
 
@@ -16,129 +13,15 @@ from bayesian_dlms_amd import _lib
 from bayesian_dlms_amd.engine import Engine, EngineError
 from bayesian_dlms_amd.gibbs import InverseGamma
 from bayesian_dlms_amd.stochvol import Beta, Gaussian, StochasticVolatility, SvParameters
-from test_studentt_gpu import gamma_unit, gibbs_rand, wave_sum
+from sampler_restatement import OU_FIELDS as FIELDS, ou_grid as grid, ou_params_inputs as params_inputs, ou_params_step, ou_paths
+from sampler_restatement import ou_prior as prior, ou_prior_tuple as as_tuple
 
-KEY_SVOU = 0x53564F55
-SLOT_PROP_A, SLOT_PROP_B, SLOT_ACC_PHI, SLOT_Z_SIGMA, SLOT_ACC_SIGMA, SLOT_Z_MU, SLOT_ACC_MU = (0x1FFFFF, 0x1FFFFE, 0x1FFFFD, 0x1FFFFC,
-                                                                                                  0x1FFFFB, 0x1FFFFA, 0x1FFFF9)
 RTOL = 1e-11
 BAND = 1e-9            # an accept decision is compared where |log u - Delta| exceeds it
-FIELDS = ("literal", "phi_a", "phi_b", "mu_mean", "mu_sd", "sigma_shape", "sigma_scale", "prop_lambda", "prop_tau", "delta_sigma", "delta_mu")
 in_band_total = []     # decisions inside the band, over the whole parametrisation of the draw-for-draw test
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
-# the restatement
-def prior(literal=0, phi=(5.0, 2.0), mu=(1.0, 2.0), sigma=(3.0, 0.5), prop=(10.0, 0.05), delta=(0.3, 0.3)):
-    return dict(literal=literal, phi_a=phi[0], phi_b=phi[1], mu_mean=mu[0], mu_sd=mu[1], sigma_shape=sigma[0], sigma_scale=sigma[1],
-                prop_lambda=prop[0], prop_tau=prop[1], delta_sigma=delta[0], delta_mu=delta[1])
-
-
-def as_tuple(pr):
-    return tuple(pr[k] for k in FIELDS)
-
-
-def _uniform_log(seed, series, it, slot):
-    u1, _ = gibbs_rand(seed, series, it, [slot], 0, 0, KEY_SVOU)
-    return math.log(u1[0])
-
-
-def _normal(seed, series, it, slot):
-    u1, u2 = gibbs_rand(seed, series, it, [slot], 0, 0, KEY_SVOU)
-    return math.sqrt(-2.0 * math.log(u1[0])) * math.cos(6.283185307179586476925286766559 * u2[0])
-
-
-def ou_sums(al, times, mu0, phi):
-    """(L, A, B, C, n) of one row at the rate phi: the terms of t = 2..T in t order (0 where dt = 0), summed as the wave sums them."""
-    T = al.size - 1
-    dt = times[1:] - times[:-1]                  # dt_t = times[t-1] - times[t-2], t = 2..T
-    pos = dt > 0.0
-    d = np.where(pos, dt, 1.0)
-    p, c = al[1:T] - mu0, al[2:T + 1] - mu0
-    with np.errstate(all="ignore"):
-        e = np.exp(-phi * d)
-        g = -np.expm1(-2.0 * phi * d)
-        ig = 1.0 / g
-        r, w = c - e * p, 1.0 - e
-        terms = (np.log(g), r * r * ig, r * w * ig, w * w * ig)
-        return tuple(wave_sum(np.where(pos, x, 0.0)) for x in terms) + (float(pos.sum()),)
-
-
-def ou_params_step(times, al, sv, pr, *, seed, series, it):
-    """One series of k_sv_ou_params.  al [T+1]; sv = (phi, mu, sigma); pr: the eleven fields of dlm_sv_ou_prior as a dict.
-    -> (phi, mu, sigma, accepted (phi, sigma, mu), status, margins (phi, sigma, mu), moves): margin = |log u - Delta| of a decision
-    that was made (inf where none was); moves = ((phi', Delta), (sigma', Delta), (mu', Delta)), what each move proposed and its log
-    acceptance ratio (tests/test_stochvol_ou_host.py holds them against the model's log density written out term by term)."""
-    nan3, inf3 = (math.nan,) * 3, [math.inf] * 3
-    lit = bool(pr["literal"])
-    phi0, mu0, sig0 = (float(x) for x in sv)
-    dt = times[1:] - times[:-1]
-    bad = not (0.0 < phi0 < 1.0) or not math.isfinite(mu0) or not (0.0 < sig0 < math.inf)
-    bad = bad or not bool(((dt >= 0.0) & (dt < math.inf)).all())
-    if bad:
-        return nan3 + ((0, 0, 0), _lib.ST_NONFINITE, inf3, None)
-    lam, tau = pr["prop_lambda"], pr["prop_tau"]
-    A0, B0 = lam * phi0 + tau, lam * (1.0 - phi0) + tau
-    ga = gamma_unit(A0, seed, series, it, SLOT_PROP_A, KEY_SVOU)[0]
-    gb = gamma_unit(B0, seed, series, it, SLOT_PROP_B, KEY_SVOU)[0]
-    phip = ga / (ga + gb)
-    L0, SA0, SB0, SC0, nd = ou_sums(al, times, mu0, phi0)
-    if not all(math.isfinite(x) for x in (L0, SA0, SB0, SC0)):
-        return nan3 + ((0, 0, 0), _lib.ST_NONFINITE, inf3, None)
-    margins, moves = list(inf3), [(phip, math.nan), None, None]
-    log, lg = math.log, math.lgamma
-    acc_phi = acc_sig = acc_mu = 0
-    phi, SA, SB, SC = phi0, SA0, SB0, SC0
-    if 0.0 < phip < 1.0:
-        L1, SA1, SB1, SC1, _ = ou_sums(al, times, mu0, phip)
-        A1, B1 = lam * phip + tau, lam * (1.0 - phip) + tau
-        pa, pb, s2 = pr["phi_a"], pr["phi_b"], sig0 * sig0
-        lt0 = (pa - 1.0) * log(phi0) + (pb - 1.0) * log(1.0 - phi0) + 0.5 * nd * log(2.0 * phi0) - 0.5 * L0 - phi0 * SA0 / s2
-        lt1 = (pa - 1.0) * log(phip) + (pb - 1.0) * log(1.0 - phip) + 0.5 * nd * log(2.0 * phip) - 0.5 * L1 - phip * SA1 / s2
-        lq_fwd = lg(A0 + B0) - lg(A0) - lg(B0) + (A0 - 1.0) * log(phip) + (B0 - 1.0) * log(1.0 - phip)
-        lq_back = lg(A1 + B1) - lg(A1) - lg(B1) + (A1 - 1.0) * log(phi0) + (B1 - 1.0) * log(1.0 - phi0)
-        lacc = lt1 - lt0 if lit else lt1 - lt0 + lq_back - lq_fwd
-        lu = _uniform_log(seed, series, it, SLOT_ACC_PHI)
-        moves[0] = (phip, lacc)
-        if not math.isnan(lacc):
-            margins[0] = abs(lu - lacc)
-        if lu < lacc:
-            acc_phi, phi, SA, SB, SC = 1, phip, SA1, SB1, SC1
-    d0 = al[0] - mu0
-    sig = sig0
-    sigp = sig0 * math.exp(pr["delta_sigma"] * _normal(seed, series, it, SLOT_Z_SIGMA))
-    moves[1] = (sigp, math.nan)
-    if 0.0 < sigp < math.inf:
-        sh, sc = pr["sigma_shape"], pr["sigma_scale"]
-        ls0, ls1 = log(sig0), log(sigp)
-        lt0 = -(sh + 1.0) * ls0 - sc / sig0 - nd * ls0 - phi * SA / (sig0 * sig0)
-        lt1 = -(sh + 1.0) * ls1 - sc / sigp - nd * ls1 - phi * SA / (sigp * sigp)
-        if not lit:
-            lt0 = lt0 - ls0 - d0 * d0 / (2.0 * sig0 * sig0)
-            lt1 = lt1 - ls1 - d0 * d0 / (2.0 * sigp * sigp)
-        lacc = lt1 - lt0 if lit else lt1 - lt0 + log(sigp / sig0)
-        lu = _uniform_log(seed, series, it, SLOT_ACC_SIGMA)
-        margins[1], moves[1] = abs(lu - lacc), (sigp, lacc)
-        if lu < lacc:
-            acc_sig, sig = 1, sigp
-    mu = mu0
-    mup = mu0 + pr["delta_mu"] * _normal(seed, series, it, SLOT_Z_MU)
-    dl, s2, ps2 = mup - mu0, sig * sig, pr["mu_sd"] * pr["mu_sd"]
-    Q1 = SA - 2.0 * dl * SB + dl * dl * SC
-    m0, m1 = mu0 - pr["mu_mean"], mup - pr["mu_mean"]
-    lt0 = -(m0 * m0) / (2.0 * ps2) - phi * SA / s2
-    lt1 = -(m1 * m1) / (2.0 * ps2) - phi * Q1 / s2
-    if not lit:
-        d1 = al[0] - mup
-        lt0 = lt0 - d0 * d0 / (2.0 * s2)
-        lt1 = lt1 - d1 * d1 / (2.0 * s2)
-    lu = _uniform_log(seed, series, it, SLOT_ACC_MU)
-    margins[2], moves[2] = abs(lu - (lt1 - lt0)), (mup, lt1 - lt0)
-    if lu < lt1 - lt0:
-        acc_mu, mu = 1, mup
-    return phi, mu, sig, (acc_phi, acc_sig, acc_mu), 0, margins, moves
-
-
 def sweep(times, alpha, sv, pr, rng, *, q23=True, q24=True):
     """The kernel's three moves for all chains at once on NumPy's generator (plain sums: the order is of no account here).
     q23 / q24 = False drop the proposal ratios / the initial state's term, as literal = 1 drops both.  -> (sv', accepted [N][3])."""
@@ -188,40 +71,6 @@ def sweep(times, alpha, sv, pr, rng, *, q23=True, q24=True):
     acc_mu = np.log(1.0 - rng.random(phi0.size)) < ltm(mup) - ltm(mu0)
     mu = np.where(acc_mu, mup, mu0)
     return np.stack([phi, mu, sig], axis=1), np.stack([acc_phi, acc_sig, acc_mu], axis=1).astype(np.int32)
-
-
-# ------------------------------------------------------------------------------------------------------------------------------
-def grid(T, seed):
-    """An irregular grid: gaps from [0.1, 3]; from T = 8 on one repeated time (a dt = 0 inside the row) and one long gap."""
-    gaps = np.random.default_rng(seed).uniform(0.1, 3.0, T - 1)
-    if T >= 8:
-        gaps[T // 2] = 0.0
-        gaps[T // 3] = 40.0
-    return np.concatenate([[0.5], 0.5 + np.cumsum(gaps)])
-
-
-def ou_paths(times, sv, rng):
-    """alpha [N][T+1] from the model at the parameters sv [N][3]: alpha_0 ~ N(mu, sigma^2), alpha_1 = alpha_0, then the OU transitions."""
-    N, T = sv.shape[0], times.size
-    phi, mu, sig = sv.T
-    alpha = np.empty((N, T + 1))
-    alpha[:, 0] = mu + sig * rng.standard_normal(N)
-    alpha[:, 1] = alpha[:, 0]
-    for t in range(2, T + 1):
-        dt = times[t - 1] - times[t - 2]
-        if dt == 0.0:
-            alpha[:, t] = alpha[:, t - 1]
-            continue
-        sd = sig * np.sqrt(-np.expm1(-2.0 * phi * dt) / (2.0 * phi))
-        alpha[:, t] = mu + np.exp(-phi * dt) * (alpha[:, t - 1] - mu) + sd * rng.standard_normal(N)
-    return alpha
-
-
-def params_inputs(N, T, seed):
-    rng = np.random.default_rng(seed)
-    times = grid(T, seed)
-    sv = np.stack([rng.uniform(0.1, 0.9, N), rng.uniform(-1.0, 2.0, N), rng.uniform(0.1, 0.5, N)], axis=1)
-    return times, ou_paths(times, sv, rng), sv
 
 
 DRAW_SHAPES = [(5, 2), (67, 65), (67, 66), (4, 129), (3, 1000)]

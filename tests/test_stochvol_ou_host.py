@@ -4,7 +4,6 @@ restated arithmetic of k_sv_ou_params (tests/test_stochvol_ou_gpu.py) against th
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,7 +11,8 @@ import pytest
 from bayesian_dlms_amd import _lib
 from bayesian_dlms_amd.gibbs import InverseGamma
 from bayesian_dlms_amd.stochvol import Beta, Gaussian, StochasticVolatility, SvParameters, initial_parameters
-from test_stochvol_ou_gpu import ou_params_step, params_inputs, prior
+from code_object import kernel_resources
+from sampler_restatement import ou_params_inputs as params_inputs, ou_params_step, ou_prior as prior
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -117,9 +117,19 @@ def _header_fields(name):
     return out
 
 
+def _struct_fields(cls):
+    return [(n, "int32_t" if t is _lib.ctypes.c_int32 else "double") for n, t in cls._fields_]
+
+
+@pytest.mark.parametrize("name,cls,count", [("dlm_sv_prior", _lib.SvPrior, 10), ("dlm_studentt_prior", _lib.StudentTPrior, 4)])
+def test_the_other_samplers_prior_structs_follow_the_header(name, cls, count):
+    want = _header_fields(name)
+    assert _struct_fields(cls) == want and len(want) == count
+
+
 def test_the_prior_struct_follows_the_header_and_carries_the_arguments():
     want = _header_fields("dlm_sv_ou_prior")
-    got = [(n, "int32_t" if t is _lib.ctypes.c_int32 else "double") for n, t in _lib.SvOuPrior._fields_]
+    got = _struct_fields(_lib.SvOuPrior)
     assert got == want and len(want) == 11
     fk, _, _, _ = _run(n_iter=1, prop_lambda=7.0, prop_tau=0.1, delta_sigma=0.2, delta_mu=0.3)
     pr = [c[1] for c in fk.calls if c[0] == "params"][0]["prior"]
@@ -231,21 +241,7 @@ def test_the_restated_ratios_are_the_models(literal):
     assert (seen > 0).all() and (seen < N).all()          # later moves were checked behind both outcomes of the earlier ones
 
 
-def test_the_kernel_has_no_scratch_and_no_spills(tmp_path):
+def test_the_kernel_has_no_scratch_and_no_spills():
     """dlm_sv_ou.o's code object, read as tests/test_stochvol_host.py reads dlm_sv.o: k_sv_ou_params keeps everything in registers."""
-    from bayesian_dlms_amd import build as b
-    obj = os.path.join(ROOT, "bayesian_dlms_amd", "build", "dlm_sv_ou.o")
-    if not os.path.exists(obj):
-        b.build()
-    llvm = "/opt/rocm/lib/llvm/bin"
-    fat, co = str(tmp_path / "fat.bin"), str(tmp_path / "svou.co")
-    subprocess.check_call([f"{llvm}/llvm-objcopy", "--dump-section", f".hip_fatbin={fat}", obj])
-    subprocess.check_call([f"{llvm}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}",
-                           "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"])
-    notes = subprocess.run([f"{llvm}/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
-    hit = []
-    for blk in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:
-        get = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1))
-        if "k_sv_ou_params" in re.search(r"\.name:\s+(\S+)", blk).group(1):
-            hit.append((get("private_segment_fixed_size"), get("vgpr_spill_count"), get("vgpr_count")))
-    assert len(hit) == 1 and hit[0][:2] == (0, 0) and hit[0][2] <= 128, hit          # (128 VGPRs: four waves per SIMD)
+    scratch, spills, vgprs = kernel_resources("dlm_sv_ou.o", "k_sv_ou_params")
+    assert (scratch, spills) == (0, 0) and vgprs <= 128, (scratch, spills, vgprs)          # (128 VGPRs: four waves per SIMD)

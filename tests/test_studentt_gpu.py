@@ -1,209 +1,20 @@
 """dlm_studentt_step_batch on the GPU (StudentT.step, StudentTGibbs.scala:182-212) and the StudentT.sample driver.
 
-First a NumPy restatement of one step (bayesian_dlms_amd/csrc/dlm_studentt.hip), operation for operation: Philox4x32-10 as
-dlm_internal.h defines it, the Marsaglia-Tsang Gamma of gamma_unit, the Poisson sampler (inversion / PTRS), the lane-sequential sums
-with their xor butterfly, and both modes.  The tests
+The NumPy restatement of one step (`step` of tests/sampler_restatement.py) follows bayesian_dlms_amd/csrc/dlm_studentt.hip operation
+for operation: the Philox stream, the Marsaglia-Tsang Gamma of gamma_unit, the Poisson sampler (inversion / PTRS), the lane-sequential
+sums with their xor butterfly, and both modes.  The tests
 compare the kernel with it draw for draw, then check the distributions, the nu chain's target, shard invariance and the driver."""
 import math
 
 import numpy as np
+import pytest
 
-MASK = np.uint64(0xFFFFFFFF)
-KEY_GIBBS, KEY_STUDENTT = 0x47494242, 0x53545544
-SLOT_PROP_GAMMA, SLOT_POISSON, SLOT_ACCEPT, SLOT_SCALE = 0x1FFFFF, 0x1FFFFE, 0x1FFFFD, 0x1FFFFC
-
-
-def philox(c0, c1, c2, c3, k0, k1):
-    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) for c in (c0, c1, c2, c3))
-    k0, k1 = np.uint64(k0), np.uint64(k1)
-    for _ in range(10):
-        p0 = np.uint64(0xD2511F53) * c0
-        p1 = np.uint64(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & MASK, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & MASK
-        k0 = (k0 + np.uint64(0x9E3779B9)) & MASK
-        k1 = (k1 + np.uint64(0xBB67AE85)) & MASK
-    return c0, c1, c2, c3
-
-
-def gibbs_rand(seed, series, it, comp, attempt, which, key):
-    comp = np.asarray(comp, dtype=np.uint64)
-    word = (comp * np.uint64(2048) + np.uint64(attempt) * np.uint64(2) + np.uint64(which)) & MASK
-    z = np.zeros_like(comp)
-    c = philox(z + np.uint64(series & 0xFFFFFFFF), z + np.uint64(series >> 32), z + np.uint64(it & 0xFFFFFFFF), word,
-               seed & 0xFFFFFFFF, (seed >> 32) ^ key)
-    f = [x.astype(np.float64) for x in c]
-    u1 = (f[0] * 4294967296.0 + f[1] + 1.0) * (1.0 / 18446744073709551616.0)
-    u2 = (f[2] * 4294967296.0 + f[3]) * (1.0 / 18446744073709551616.0)
-    return u1, u2
-
-
-def gamma_unit(a, seed, series, it, comp, key):
-    """Vectorised over (a, comp) for one series."""
-    a = np.array(a, dtype=np.float64, ndmin=1).copy()
-    comp = np.broadcast_to(np.asarray(comp, dtype=np.uint64), a.shape).copy()
-    boost = np.ones_like(a)
-    small = a < 1.0
-    if small.any():
-        u1, _ = gibbs_rand(seed, series, it, comp[small], 1023, 0, key)
-        boost[small] = u1 ** (1.0 / a[small])
-        a[small] += 1.0
-    dd = a - 1.0 / 3.0
-    cc = 1.0 / np.sqrt(9.0 * dd)
-    out = dd * boost
-    todo = np.ones(a.shape, bool)
-    for k in range(1023):
-        idx = np.nonzero(todo)[0]
-        if idx.size == 0:
-            break
-        u1, u2 = gibbs_rand(seed, series, it, comp[idx], k, 0, key)
-        x = np.sqrt(-2.0 * np.log(u1)) * np.cos(6.283185307179586476925286766559 * u2)
-        v = 1.0 + cc[idx] * x
-        pos = v > 0.0
-        v = np.where(pos, v, 1.0)
-        v = v * v * v
-        w1, _ = gibbs_rand(seed, series, it, comp[idx], k, 1, key)
-        ddi = dd[idx]
-        ok = pos & (np.log(w1) < 0.5 * x * x + ddi - ddi * v + ddi * np.log(v))
-        out[idx[ok]] = ddi[ok] * v[ok] * boost[idx[ok]]
-        todo[idx[ok]] = False
-    return out
-
-
-def ptrs_loggam(x):
-    if x == 1.0 or x == 2.0:
-        return 0.0
-    n = int(7.0 - x) if x < 7.0 else 0
-    x0 = x + n
-    x2 = (1.0 / x0) * (1.0 / x0)
-    c = [8.333333333333333e-02, -2.777777777777778e-03, 7.936507936507937e-04, -5.952380952380952e-04, 8.417508417508418e-04,
-         -1.917526917526918e-03, 6.410256410256410e-03, -2.955065359477124e-02, 1.796443723688307e-01, -1.39243221690590e+00]
-    gl0 = c[9]
-    for k in range(8, -1, -1):
-        gl0 *= x2
-        gl0 += c[k]
-    gl = gl0 / x0 + 0.5 * 1.8378770664093453e+00 + (x0 - 0.5) * math.log(x0) - x0
-    for _ in range(n):
-        gl -= math.log(x0 - 1.0)
-        x0 -= 1.0
-    return gl
-
-
-def poisson(lam, seed, series, it):
-    if not lam > 0.0:
-        return 0.0
-    if lam < 10.0:
-        _, u2 = gibbs_rand(seed, series, it, [SLOT_POISSON], 0, 0, KEY_STUDENTT)
-        u = u2[0]
-        p = math.exp(-lam); cdf = p; k = 0.0
-        while u > cdf and k < 200.0:
-            k += 1.0; p *= lam / k; cdf += p
-        return k
-    slam, loglam = math.sqrt(lam), math.log(lam)
-    b = 0.931 + 2.53 * slam
-    a = -0.059 + 0.02483 * b
-    invalpha = 1.1239 + 1.1328 / (b - 3.4)
-    vr = 0.9277 - 3.6224 / (b - 2.0)
-    for att in range(1023):
-        u1, u2 = gibbs_rand(seed, series, it, [SLOT_POISSON], att, 0, KEY_STUDENTT)
-        U, V = u2[0] - 0.5, u1[0]
-        us = 0.5 - abs(U)
-        if not us > 0.0:
-            continue
-        k = math.floor((2.0 * a / us + b) * U + lam + 0.43)
-        if us >= 0.07 and V <= vr:
-            return float(k)
-        if k < 0.0 or (us < 0.013 and V > us):
-            continue
-        if math.log(V) + math.log(invalpha) - math.log(a / (us * us) + b) <= -lam + k * loglam - ptrs_loggam(k + 1.0):
-            return float(k)
-    return math.floor(lam)
-
-
-def wave_sum(terms):
-    """terms [T] in t order (0 where a lane adds nothing): the lane-sequential sums, then the xor butterfly."""
-    T = terms.size
-    rows = -(-T // 64)
-    pad = np.zeros(rows * 64)
-    pad[:T] = terms
-    lanes = np.zeros(64)
-    for r in range(rows):
-        lanes = lanes + pad[r * 64:(r + 1) * 64]
-    idx = np.arange(64)
-    for m in (32, 16, 8, 4, 2, 1):
-        lanes = lanes + lanes[idx ^ m]
-    return lanes[0]
-
-
-def dot_rows(F, x):
-    """sum_i F[.., i] x[.., i] in i order (the kernel's loop)."""
-    f = np.zeros(x.shape[0])
-    for i in range(x.shape[1]):
-        f = f + F[:, i] * x[:, i]
-    return f
-
-
-def step(F, y, theta, stats, prior, s, nu, *, seed, series, it, literal):
-    """One series.  F [T][d] (time-varying) or [d]; y [T]; theta [T+1][d]; stats [d + 3].  Returns (v [T], s', nu', W diag [d],
-    accepted, loglik)."""
-    lam_prior, r, aw, bw = prior
-    T, d = y.size, theta.shape[1]
-    Ft = np.broadcast_to(np.asarray(F, dtype=np.float64).reshape(-1, d), (T, d))
-    L = d + 3
-    wsh = aw + 0.5 * stats[L - 1]
-    wd = np.array([(bw + 0.5 * stats[2 + i]) / gamma_unit(wsh, seed, series, it, 1 + i, KEY_GIBBS)[0] for i in range(d)])
-    dnu = float(nu)
-    q = dnu / (r + dnu)
-    g = gamma_unit(r, seed, series, it, SLOT_PROP_GAMMA, KEY_STUDENTT)[0]
-    nup = poisson(g * (q / (1.0 - q)), seed, series, it) + 1.0
-    prop_ok = 1.0 <= nup < 1.0e9
-    sc = math.sqrt(s)
-    den0 = dnu * sc * sc if literal else dnu * s
-    den1 = nup * sc * sc if literal else nup * s
-    f1 = dot_rows(Ft, theta[1:])
-    e1 = y - f1
-    e = y - dot_rows(Ft, theta[:-1]) if literal else e1
-    obs = ~np.isnan(y)
-    with np.errstate(invalid="ignore"):
-        A0 = wave_sum(np.where(obs, np.log1p(e1 * e1 / den0), 0.0))
-        A1 = wave_sum(np.where(obs, np.log1p(e1 * e1 / den1), 0.0))
-    nobs = float(obs.sum())
-    off = 0.0 if literal else 1.0
-    k1, k2 = dnu - off, nup - off
-    lg = math.lgamma
-    c0 = sc if literal else s
-    PI = 3.141592653589793
-    ll0 = nobs * (lg((dnu + 1.0) * 0.5) - 0.5 * math.log(PI * dnu * c0) - lg(dnu * 0.5)) - (dnu + 1.0) * 0.5 * A0
-    ll_out, acc = ll0, 0
-    if prop_ok:
-        ll1 = nobs * (lg((nup + 1.0) * 0.5) - 0.5 * math.log(PI * nup * c0) - lg(nup * 0.5)) - (nup + 1.0) * 0.5 * A1
-        lm0 = ll0 + (dnu * math.log(lam_prior) - lam_prior - lg(dnu + 1.0))
-        lm1 = ll1 + (nup * math.log(lam_prior) - lam_prior - lg(nup + 1.0))
-        q1, q2 = nup / (r + nup), dnu / (r + dnu)
-        pp1 = lg(r + k1) - lg(k1 + 1.0) - lg(r) + r * math.log(1.0 - q1) + k1 * math.log(q1)
-        pp2 = lg(r + k2) - lg(k2 + 1.0) - lg(r) + r * math.log(1.0 - q2) + k2 * math.log(q2)
-        lacc = lm1 + pp1 - lm0 - pp2
-        u1, _ = gibbs_rand(seed, series, it, [SLOT_ACCEPT], 0, 0, KEY_STUDENTT)
-        if math.log(u1[0]) < lacc:
-            acc, ll_out = 1, ll1
-    nu_v = float(nup) if (acc and not literal) else dnu
-    eobs = ~np.isnan(e)
-    shape = np.where(eobs | literal, (nu_v + 1.0) * 0.5, nu_v * 0.5)
-    beta = nu_v * s * 0.5 + np.where(eobs, np.nan_to_num(e) * np.nan_to_num(e) * 0.5, 0.0)
-    v = beta / gamma_unit(shape, seed, series, it, np.arange(T), KEY_STUDENTT)
-    R = wave_sum(1.0 / v)
-    snew = gamma_unit(T * nu_v * 0.5 + 1.0, seed, series, it, SLOT_SCALE, KEY_STUDENTT)[0] / (nu_v * 0.5 * R)
-    return v, snew, int(nup) if acc else int(nu), wd, acc, ll_out
-
-
-# ------------------------------------------------------------------------------------------------------------------------------
-# the GPU tests
-import pytest  # noqa: E402
-
-from bayesian_dlms_amd import _lib  # noqa: E402
-from bayesian_dlms_amd.dlm import Dlm, DlmParameters, materialise  # noqa: E402
-from bayesian_dlms_amd.engine import Engine, EngineError  # noqa: E402
-from bayesian_dlms_amd.gibbs import InverseGamma  # noqa: E402
-from bayesian_dlms_amd.studentt import NegativeBinomialProposal, Poisson, StudentT  # noqa: E402
+from bayesian_dlms_amd import _lib
+from bayesian_dlms_amd.dlm import Dlm, DlmParameters, materialise
+from bayesian_dlms_amd.engine import Engine, EngineError
+from bayesian_dlms_amd.gibbs import InverseGamma
+from bayesian_dlms_amd.studentt import NegativeBinomialProposal, Poisson, StudentT
+from sampler_restatement import step
 
 PRIOR = (3.0, 1.0, 3.0, 3.0)     # Poisson(3) prior of nu, proposal size 1, InverseGamma(3, 3) prior of W: the example's
 

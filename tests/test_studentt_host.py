@@ -1,9 +1,5 @@
 """The Student-t Gibbs driver (bayesian_dlms_amd/studentt.py) without a GPU: what it passes to its two engine calls (injected
 fakes), the initial nu, and the code object of the step kernel (dlm_studentt.o: no scratch, no spills)."""
-import os
-import re
-import subprocess
-
 import numpy as np
 import pytest
 
@@ -11,8 +7,7 @@ from bayesian_dlms_amd import _lib
 from bayesian_dlms_amd.dlm import Dlm, DlmParameters
 from bayesian_dlms_amd.gibbs import InverseGamma
 from bayesian_dlms_amd.studentt import NegativeBinomialProposal, Poisson, StudentT, initial_nu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from code_object import kernel_resources
 
 
 class _Fakes:
@@ -115,23 +110,7 @@ def test_initial_nu_is_never_zero_and_does_not_depend_on_the_sharding():
     np.testing.assert_array_equal(fk2.step_calls[0]["nu"], full[3:3 + N])
 
 
-def test_step_kernel_has_no_scratch_and_no_spills(tmp_path):
+def test_step_kernel_has_no_scratch_and_no_spills():
     """dlm_studentt.o's code object: k_studentt_step keeps everything in registers (read as test_per_wave_kernels_keep_their_registers
     reads dlm_wave48.o)."""
-    from bayesian_dlms_amd import build as b
-    obj = os.path.join(ROOT, "bayesian_dlms_amd", "build", "dlm_studentt.o")
-    if not os.path.exists(obj):
-        b.build()
-    llvm = "/opt/rocm/lib/llvm/bin"
-    fat, co = str(tmp_path / "fat.bin"), str(tmp_path / "st.co")
-    subprocess.check_call([f"{llvm}/llvm-objcopy", "--dump-section", f".hip_fatbin={fat}", obj])
-    subprocess.check_call([f"{llvm}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}",
-                           "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"])
-    notes = subprocess.run([f"{llvm}/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
-    meta = {}
-    for blk in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:
-        get = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1))
-        meta[re.search(r"\.name:\s+(\S+)", blk).group(1)] = (get("private_segment_fixed_size"), get("vgpr_spill_count"))
-    hit = [v for k, v in meta.items() if "k_studentt_step" in k]
-    assert len(hit) == 1, sorted(meta)
-    assert hit[0] == (0, 0), hit
+    assert kernel_resources("dlm_studentt.o", "k_studentt_step")[:2] == (0, 0)
