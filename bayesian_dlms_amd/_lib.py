@@ -84,6 +84,14 @@ class SvOuPrior(ctypes.Structure):
                 ("delta_sigma", ctypes.c_double), ("delta_mu", ctypes.c_double)]
 
 
+class FsvPrior(ctypes.Structure):
+    """dlm_fsv_prior: Gaussian(beta_mean, beta_sd) prior of the free loadings (the standard deviation, as Breeze takes it),
+    InverseGamma(sigma_shape, sigma_scale) of the observation variance sigma^2; literal = 1: the reference's arithmetic (Q27-Q30)."""
+    _fields_ = [("literal", ctypes.c_int32),
+                ("beta_mean", ctypes.c_double), ("beta_sd", ctypes.c_double),
+                ("sigma_shape", ctypes.c_double), ("sigma_scale", ctypes.c_double)]
+
+
 class Options(ctypes.Structure):
     _fields_ = [("flags", ctypes.c_uint32), ("mem", ctypes.c_int32),
                 ("seed", ctypes.c_uint64), ("series_offset", ctypes.c_uint64)]
@@ -122,6 +130,10 @@ SYMBOLS = [
                                            _V, _V, _V]),
     ("dlm_sv_ou_params_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, ctypes.POINTER(SvOuPrior), ctypes.c_uint64,
                                               _OP, _V, _V, _V]),
+    ("dlm_fsv_factors_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, _V, ctypes.c_int32,
+                                             ctypes.c_uint64, _OP, _V, _V]),
+    ("dlm_fsv_loadings_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, _V,
+                                              ctypes.POINTER(FsvPrior), ctypes.c_uint64, _OP, _V, _V, _V]),
     ("dlm_ou_ffbs_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, ctypes.c_int64, _V, ctypes.c_int64,
                                          _V, _OP, _V, _V, _V]),
     ("dlm_ar1_ffbs_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, ctypes.c_int64, _V, ctypes.c_int64,

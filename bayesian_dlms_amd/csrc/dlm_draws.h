@@ -1,4 +1,4 @@
-// The scalar draws of the Gibbs parameter steps (dlm_gibbs.hip, dlm_studentt.hip, dlm_sv.hip, dlm_sv_ou.hip), each defined here ONCE:
+// The scalar draws of the Gibbs parameter steps (dlm_gibbs.hip, dlm_studentt.hip, dlm_sv.hip, dlm_sv_ou.hip, dlm_fsv.hip), each defined here ONCE:
 // the Philox uniforms under a stream key, the Gamma, normal and log-uniform variates, the Beta proposal of the two stochastic-volatility
 // steps, the conjugate draw of a diagonal W, and the table of counter slots (dlm_engine.hip takes its limits on T from it).
 #pragma once
@@ -14,10 +14,13 @@ namespace dlm {
 //   DLM_KEY_STUDENTT  dlm_studentt_step_batch: comp = t for the variance v_t, DLM_ST_SLOT_* for its scalar draws
 //   DLM_KEY_SV        dlm_sv_mixture_batch: comp = t for the mixture indicator k_t; dlm_sv_params_batch: DLM_SV_SLOT_*
 //   DLM_KEY_SVOU      dlm_sv_ou_params_batch: DLM_SVOU_SLOT_*; the OU chain's mixture call draws under DLM_KEY_SV
+//   DLM_KEY_FSV       dlm_fsv_factors_batch: comp = t, attempt j for the normal of factor j at time t; dlm_fsv_loadings_batch: DLM_FSV_SLOT_*
+//                     (the factor chains' volatility calls draw under DLM_KEY_SV at the series (series_offset + n) k + j)
 constexpr unsigned DLM_KEY_GIBBS = 0x47494242u;      // "GIBB"
 constexpr unsigned DLM_KEY_STUDENTT = 0x53545544u;   // "STUD"
 constexpr unsigned DLM_KEY_SV = 0x5354564Fu;         // "STVO"
 constexpr unsigned DLM_KEY_SVOU = 0x53564F55u;       // "SVOU"
+constexpr unsigned DLM_KEY_FSV = 0x46535620u;        // "FSV "
 
 // ---- the slots ------------------------------------------------------------------------------------------------------------------
 // comp is a 21-bit field (the counter word is comp * 2048 + attempt * 2 + which).  A sampler whose per-time draws take comp = t < T
@@ -47,12 +50,20 @@ enum : unsigned {   // dlm_sv_ou_params_batch, DLM_KEY_SVOU (no per-time draws o
   DLM_SVOU_SLOT_Z_MU = DLM_SLOT_TOP - 5,        // mu's walk
   DLM_SVOU_SLOT_ACC_MU = DLM_SLOT_TOP - 6,      // mu's uniform
 };
+enum : unsigned {   // dlm_fsv_loadings_batch, DLM_KEY_FSV (dlm_fsv_factors_batch takes the slots t)
+  DLM_FSV_SLOT_SIGMA = DLM_SLOT_TOP,            // sigma^2: the Gamma of the InverseGamma
+  DLM_FSV_SLOT_ROW0 = DLM_SLOT_TOP - 1,         // row i of beta takes the slot DLM_FSV_SLOT_ROW0 - i, attempt j the normal of its entry j
+  DLM_FSV_SLOT_ROW_LAST = DLM_SLOT_TOP - 64,    // i <= 63 (p <= 64)
+};
 constexpr int DLM_ST_MAX_T = 0x1FFFFC;     // v_t takes slot t < T
 constexpr int DLM_SV_MAX_T = 0x1FFFF7;     // k_t takes slot t < T; 0x1FFFF8 and 0x1FFFF9 are kept free
 constexpr int DLM_SVOU_MAX_T = 0x1FFFF7;   // the chain's mixture call runs at the same T
+constexpr int DLM_FSV_MAX_T = 0x1FFFBF;    // the factors' normals take slot t < T
 static_assert(DLM_ST_SLOT_SCALE > (unsigned)DLM_ST_MAX_T - 1, "the Student-t step's scalar slots lie above every time slot");
 static_assert(DLM_SV_SLOT_ACCEPT > (unsigned)DLM_SV_MAX_T, "the SV step's scalar slots lie above every time slot");
 static_assert(DLM_SVOU_SLOT_ACC_MU > (unsigned)DLM_SVOU_MAX_T, "the OU step's scalar slots lie above every time slot");
+static_assert(DLM_FSV_SLOT_ROW_LAST > (unsigned)DLM_FSV_MAX_T - 1, "the loadings' slots lie above every time slot");
+static_assert(DLM_FSV_MAX_T <= DLM_SV_MAX_T, "the factor chains' mixture call runs at the same T");
 
 // ---- uniforms, normals, Gammas ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void gibbs_rand(unsigned long long seed, unsigned long long series, unsigned long long iteration,

@@ -1194,6 +1194,75 @@ int dlm_sv_ou_params_batch(dlm_engine* e, int32_t N, int32_t T, const double* ti
   return st.finish(opts->flags & DLM_OPT_ASYNC);
 }
 
+// what the two factor stochastic-volatility calls ask of their shape
+static int fsv_check_shape(dlm_engine* e, int32_t N, int32_t T, int32_t p, int32_t k) {
+  if (N < 1 || T < 2) return fail(e, DLM_ERR_ARG, "N >= 1 and T >= 2 (the factor chains' volatility calls need two observations)");
+  if (T > dlm::DLM_FSV_MAX_T) return fail(e, DLM_ERR_ARG, "T must stay below 2^21 - 64 (the Philox counter's slot field)");
+  if (k < 1 || k > dlm::DLM_FSV_MAX_K || p < k || p > dlm::DLM_FSV_MAX_P) return fail(e, DLM_ERR_ARG, "1 <= k <= 8 and k <= p <= 64");
+  if ((long long)N * ((T + 255) / 256) > 0x7FFFFFFFll) return fail(e, DLM_ERR_ARG, "N ceil(T / 256) must stay below 2^31 (one block per 256 times of a panel)");
+  return DLM_OK;
+}
+
+int dlm_fsv_factors_batch(dlm_engine* e, int32_t N, int32_t T, int32_t p, int32_t k, const double* y, const double* beta,
+                          const double* v, const double* alpha, int32_t literal, uint64_t iteration, const dlm_options* opts,
+                          double* f, int32_t* status) {
+  if (!e) return DLM_ERR_ARG;
+  int rc;
+  if ((rc = check_opts(e, opts))) return rc;
+  if ((rc = fsv_check_shape(e, N, T, p, k))) return rc;
+  if (literal != 0 && literal != 1) return fail(e, DLM_ERR_ARG, "literal: 0 or 1");
+  if (!y || !beta || !v || !f) return fail(e, DLM_ERR_ARG, "y, beta, v and f are required");
+  HIP_TRY(e, hipSetDevice(e->device));
+  dlm::FsvFactorsArgs a{};
+  const size_t n = N, t = T, pp = p, kk = k;
+  Stager st(e, opts->mem == DLM_MEM_HOST);
+  st.in(&a.y, y, n * t * pp);
+  st.in(&a.beta, beta, n * pp * kk);
+  st.in(&a.v, v, n * pp);
+  st.in(&a.alpha, alpha, alpha ? n * kk * (t + 1) : 0);
+  st.out(&a.f, f, n * kk * t);
+  st.zeroed_out(&a.status, (int*)status, status ? n : 0);
+  if ((rc = st.commit())) return rc;
+  a.N = N; a.T = T; a.p = p; a.k = k;
+  a.literal = literal;
+  a.rs = draw_stream(opts, iteration);
+  e->variant = "fsv-factors";
+  HIP_TRY(e, dlm::launch_fsv_factors(a, e->stream));
+  return st.finish(opts->flags & DLM_OPT_ASYNC);
+}
+
+int dlm_fsv_loadings_batch(dlm_engine* e, int32_t N, int32_t T, int32_t p, int32_t k, const double* y, const double* f,
+                           const double* beta_in, const double* v_in, const dlm_fsv_prior* prior, uint64_t iteration,
+                           const dlm_options* opts, double* beta_out, double* v_out, int32_t* status) {
+  if (!e) return DLM_ERR_ARG;
+  if (!prior) return fail(e, DLM_ERR_ARG, "null descriptor");
+  int rc;
+  if ((rc = check_opts(e, opts))) return rc;
+  if ((rc = fsv_check_shape(e, N, T, p, k))) return rc;
+  if (prior->literal != 0 && prior->literal != 1) return fail(e, DLM_ERR_ARG, "literal: 0 or 1");
+  if (!(is_positive(prior->beta_sd) && is_finite(prior->beta_mean))) return fail(e, DLM_ERR_ARG, "the Gaussian prior of beta needs a finite mean and a positive standard deviation");
+  if (!(is_positive(prior->sigma_shape) && is_positive(prior->sigma_scale))) return fail(e, DLM_ERR_ARG, "the InverseGamma prior of sigma^2 needs a positive shape and scale");
+  if (!y || !f || !beta_in || !beta_out || !v_out) return fail(e, DLM_ERR_ARG, "y, f, beta_in, beta_out and v_out are required");
+  HIP_TRY(e, hipSetDevice(e->device));
+  dlm::FsvLoadingsArgs a{};
+  const size_t n = N, t = T, pp = p, kk = k;
+  Stager st(e, opts->mem == DLM_MEM_HOST);
+  st.in(&a.y, y, n * t * pp);
+  st.in(&a.f, f, n * kk * t);
+  st.in(&a.beta_in, beta_in, n * pp * kk);
+  st.in(&a.v_in, v_in, v_in ? n * pp : 0);
+  st.out(&a.beta_out, beta_out, n * pp * kk);
+  st.out(&a.v_out, v_out, n * pp);
+  st.zeroed_out(&a.status, (int*)status, status ? n : 0);
+  if ((rc = st.commit())) return rc;
+  a.N = N; a.T = T; a.p = p; a.k = k;
+  a.prior = *prior;
+  a.rs = draw_stream(opts, iteration);
+  e->variant = "fsv-loadings";
+  HIP_TRY(e, dlm::launch_fsv_loadings(a, e->stream));
+  return st.finish(opts->flags & DLM_OPT_ASYNC);
+}
+
 static int ar1_common(dlm_engine* e, int32_t N, int32_t T, const double* times, bool ou, const double* y, const double* v,
                       int64_t v_stride, const double* sv, int64_t sv_stride, const double* z, const dlm_options* opts,
                       double* filt, double* theta, int32_t* status);

@@ -421,6 +421,35 @@ struct SvOuParamsArgs {
 };
 hipError_t launch_sv_ou_params(const SvOuParamsArgs& a, hipStream_t s);
 
+// ---- factor stochastic volatility: the factor draw and the draws of sigma^2 and the loading matrix around the factor chains'
+// AR(1) volatility calls (FactorSv.scala:168-186, :253-333, :516-541), dlm_fsv.hip -------------
+constexpr int DLM_FSV_MAX_K = 8, DLM_FSV_MAX_P = 64;
+struct FsvFactorsArgs {
+  int N, T, p, k;
+  const double* y;        // [N][T][p]
+  const double* beta;     // [N][p][k]
+  const double* v;        // [N][p]
+  const double* alpha;    // [N][k][T+1], or nullptr: unit factor variances (initialiseFactors)
+  int literal;
+  DrawStream rs;
+  double* f;              // [N][k][T]
+  int* status;            // [N], nullable (zeroed by the caller)
+};
+struct FsvLoadingsArgs {
+  int N, T, p, k;
+  const double* y;        // [N][T][p]
+  const double* f;        // [N][k][T]
+  const double* beta_in;  // [N][p][k]
+  const double* v_in;     // [N][p], nullable: what v_out keeps for a panel without an observed time
+  dlm_fsv_prior prior;
+  DrawStream rs;
+  double* beta_out;       // [N][p][k], may be beta_in
+  double* v_out;          // [N][p], may be v_in
+  int* status;            // [N], nullable (zeroed by the caller)
+};
+hipError_t launch_fsv_factors(const FsvFactorsArgs& a, hipStream_t s);
+hipError_t launch_fsv_loadings(const FsvLoadingsArgs& a, hipStream_t s);
+
 // ---- KalmanFilter.likelihood literally (transition density of the filtered means), dlm_loglik.hip ------
 size_t loglik_q7_ws_bytes(const KArgs& a);
 hipError_t launch_loglik_q7(const KArgs& a, const double* records, void* ws, hipStream_t s);   // a.loglik [N] <- records [N][T+1][d+dd]

@@ -419,6 +419,54 @@ class Engine:
         self._check(call(self.h, N, T, *grid, be.ptr(ab), be.ptr(sb), pr, int(iteration), op, be.ptr(sv_out), be.ptr(acc), be.ptr(status)))
         return {"sv": sv_out, "accepted": acc, "status": status}
 
+    def fsv_factors(self, y, beta, v, alpha, *, iteration, seed=0, series_offset=0, literal=False, flags=0, out=None):
+        """The factor draw of the factor stochastic-volatility sampler (dlm_fsv_factors_batch; FactorSv.sampleFactors,
+        FactorSv.scala:168-186) for N panels: y [N][T][p] (NaN = missing; a partially missing time is wholly missing), beta [N][p][k],
+        v [N][p] the diagonal of the observation variance, alpha [N][k][T+1] the factors' log-volatilities (alpha[..][t+1] belongs to
+        y[t]) or None: unit factor variances (initialiseFactors).  Returns {"f" [N][k][T], "status"}: f viewed as [N k][T] is the y of
+        sv_mixture, NaN where the time is missing.  literal=True: the reference's draw (Q27).  out: dict with an existing "f" buffer."""
+        be = self._backend(y)
+        if y.ndim != 3 or beta.ndim != 3:
+            raise EngineError("y must be [N][T][p] and beta [N][p][k]")
+        N, T, p, k = int(y.shape[0]), int(y.shape[1]), int(y.shape[2]), int(beta.shape[2])
+        yb, bb, vb, ab = be.put(y), be.put(beta), be.put(v), be.put(alpha)
+        if tuple(bb.shape) != (N, p, k) or tuple(vb.shape) != (N, p):
+            raise EngineError(f"beta must be [N][p][k] = {(N, p, k)} and v [N][p] = {(N, p)}, got {tuple(bb.shape)} and {tuple(vb.shape)}")
+        if ab is not None and tuple(ab.shape) != (N, k, T + 1):
+            raise EngineError(f"alpha must be [N][k][T+1] = {(N, k, T + 1)}, got {tuple(ab.shape)}")
+        f = _out_or_empty(be, out, "f", (N, k, T))
+        status = be.empty((N,), np.int32)
+        op = _lib.Options(flags, be.mem, seed, series_offset)
+        self._hold(flags, yb, bb, vb, ab)
+        self._check(self.lib.dlm_fsv_factors_batch(self.h, N, T, p, k, be.ptr(yb), be.ptr(bb), be.ptr(vb), be.ptr(ab), 1 if literal else 0,
+                                                   int(iteration), op, be.ptr(f), be.ptr(status)))
+        return {"f": f, "status": status}
+
+    def fsv_loadings(self, y, f, beta, prior, *, iteration, seed=0, series_offset=0, v=None, flags=0, out=None):
+        """sigma^2 and the loading matrix of the factor stochastic-volatility sampler given the factors (dlm_fsv_loadings_batch;
+        FactorSv.sampleSigmaUni, :516-541, then sampleBeta, :253-333) for N panels: y [N][T][p], f [N][k][T] as fsv_factors writes it,
+        beta [N][p][k] the current loadings.  prior: a _lib.FsvPrior, or its five fields in order (literal, beta_mean, beta_sd,
+        sigma_shape, sigma_scale).  v [N][p] (optional): what a panel without an observed time keeps.  Returns {"beta" [N][p][k],
+        "v" [N][p] (sigma^2 in every entry), "status"}.  out: dict of existing "beta" / "v" buffers (they may be the inputs)."""
+        be = self._backend(y)
+        if y.ndim != 3 or beta.ndim != 3:
+            raise EngineError("y must be [N][T][p] and beta [N][p][k]")
+        N, T, p, k = int(y.shape[0]), int(y.shape[1]), int(y.shape[2]), int(beta.shape[2])
+        yb, fb, bb, vb = be.put(y), be.put(f), be.put(beta), be.put(v)
+        if tuple(bb.shape) != (N, p, k) or tuple(fb.shape) != (N, k, T):
+            raise EngineError(f"beta must be [N][p][k] = {(N, p, k)} and f [N][k][T] = {(N, k, T)}, got {tuple(bb.shape)} and {tuple(fb.shape)}")
+        if vb is not None and tuple(vb.shape) != (N, p):
+            raise EngineError(f"v must be [N][p] = {(N, p)}, got {tuple(vb.shape)}")
+        pr = _as_prior(_lib.FsvPrior, prior)
+        beta_out = _out_or_empty(be, out, "beta", (N, p, k))
+        v_out = _out_or_empty(be, out, "v", (N, p))
+        status = be.empty((N,), np.int32)
+        op = _lib.Options(flags, be.mem, seed, series_offset)
+        self._hold(flags, yb, fb, bb, vb)
+        self._check(self.lib.dlm_fsv_loadings_batch(self.h, N, T, p, k, be.ptr(yb), be.ptr(fb), be.ptr(bb), be.ptr(vb), pr, int(iteration),
+                                                    op, be.ptr(beta_out), be.ptr(v_out), be.ptr(status)))
+        return {"beta": beta_out, "v": v_out, "status": status}
+
     def simulate(self, mat, params, N, *, seed=0, series_offset=0, device=False, want_x=True):
         """Dlm.simulateRegular over the model's time grid for N series (dlm_simulate_batch): (x [N][T+1][d], y [N][T][p])."""
         be = _Device(self.device) if device else _Host()

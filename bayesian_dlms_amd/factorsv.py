@@ -1,0 +1,200 @@
+"""Gibbs sampler of the factor stochastic-volatility model on the device (FactorSv.sampleAr, FactorSv.scala:546-562, :622-645).
+
+  y_t = beta f_t + eps_t,  eps_t ~ N(0, diag(v)),  f_{j,t} ~ N(0, exp(alpha_{j,t})),  alpha_j AR(1) with SvParameters (phi, mu, sigma_eta)_j
+  beta p x k: beta_ii = 1, beta_ij = 0 for j > i, beta_ij ~ Gaussian(mean, sd) elsewhere;  v = sigma^2 1_p, sigma^2 ~ InverseGamma
+
+A batch is N independent panels of p series, T times and k factors (1 <= k <= 8, k <= p <= 64); ys is [N][T][p], NaN = missing, and a
+partially missing time is wholly missing (encodePartiallyMissing, :150-157).  One iteration is five engine calls, in sampleStep's order:
+
+  dlm_sv_mixture_batch, dlm_ar1_ffbs_batch, dlm_sv_params_batch   on the N k factor series f viewed as [N k][T]: chain (n, j) is the
+                                                                  series (series_offset + n) k + j of those calls
+  dlm_fsv_factors_batch                                           f_t | (y_t, beta, v, alpha_{t+1})
+  dlm_fsv_loadings_batch                                          sigma^2 | (y, f, beta), then beta | (y, f, sigma^2) row by row
+
+The chain state -- f [N][k][T], alpha [N][k][T+1], sv [N][k][3], beta [N][p][k], v [N][p] -- never leaves the device between
+iterations; per iteration the parameters and the status cross to the host, plus f and alpha when asked for (keep_factors).
+
+The default is the corrected sampler (DESIGN.md 2, Q27-Q30, and Q16-Q19 of the volatility parameters); literal=True runs the
+reference's arithmetic in all five calls.  Q31: the reference's sampleStep draws the volatility state with the knot block sampler,
+which is not offered; the driver uses the reference's own alternative FactorSv.sampleVolatilityAr (:415-435), the mixture and FFBS
+draw of StochasticVolatility.sampleStateAr.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Iterator, Optional, Sequence
+
+import numpy as np
+
+from . import _lib
+from ._chain import host, or_status, place
+from .gibbs import InverseGamma
+from .stochvol import MASK64, Gaussian, StochasticVolatility, SvParameters
+
+MAX_K, MAX_P = 8, 64
+# the iteration index of initialiseFactors' normals: they share the stream of the iterations' factor draws, whose indices count from 0
+INIT_ITERATION = MASK64
+
+
+@dataclass
+class FsvParameters:
+    """FsvParameters(v, beta, factorParams) (FactorSv.scala:20-60): v a scalar (sigma^2) or the diagonal [p] of the observation
+    variance, beta [p][k], factor_params k SvParameters (or a [k][3] array of (phi, mu, sigma_eta))."""
+    v: object
+    beta: np.ndarray
+    factor_params: Sequence
+
+    def __post_init__(self):
+        self.beta = np.asarray(self.beta, dtype=np.float64)
+        if self.beta.ndim != 2:
+            raise ValueError(f"beta must be [p][k], got the shape {self.beta.shape}")
+        p, k = self.beta.shape
+        if not (1 <= k <= MAX_K and k <= p <= MAX_P):
+            raise ValueError(f"1 <= k <= {MAX_K} and k <= p <= {MAX_P}: got p = {p}, k = {k}")
+        v = np.asarray(self.v, dtype=np.float64)
+        if v.ndim == 2:
+            v = np.diagonal(v)
+        self.v = np.broadcast_to(v, (p,)).copy()
+        if not (self.v > 0.0).all():
+            raise ValueError("the observation variances must be positive")
+        sv = np.asarray([(q.phi, q.mu, q.sigma_eta) if isinstance(q, SvParameters) else q for q in self.factor_params], dtype=np.float64)
+        if sv.shape != (k, 3):
+            raise ValueError(f"factor_params must hold k = {k} (phi, mu, sigma_eta) triples, got the shape {sv.shape}")
+        if not ((np.abs(sv[:, 0]) < 1.0).all() and (sv[:, 2] > 0.0).all()):
+            raise ValueError("every factor needs a stationary phi and sigma_eta > 0")
+        self.factor_params = [SvParameters(*row) for row in sv]
+
+    @property
+    def p(self):
+        return self.beta.shape[0]
+
+    @property
+    def k(self):
+        return self.beta.shape[1]
+
+    def sv(self):
+        """[k][3] = (phi, mu, sigma_eta) per factor."""
+        return np.asarray([(q.phi, q.mu, q.sigma_eta) for q in self.factor_params], dtype=np.float64)
+
+
+class FactorSv:
+    @dataclass
+    class State:
+        """FactorSv.State (FactorSv.scala:62-66), batched.  params: {"beta" [N][p][k], "v" [N][p], "sv" [N][k][3]} on the host;
+        factors [N][k][T] and volatility [N][k][T+1] host copies when asked for (keep_factors) else None; status [N]: the five calls'
+        flags or'ed (the factor chains' flags folded onto their panel)."""
+        params: dict
+        factors: Optional[np.ndarray]
+        volatility: Optional[np.ndarray]
+        status: np.ndarray
+
+    @staticmethod
+    def make_beta(p: int, k: int) -> np.ndarray:
+        """makeBeta (:295-304): ones on the diagonal, zeros elsewhere."""
+        return FactorSv.build_beta(p, k, lambda: 0.0)
+
+    @staticmethod
+    def build_beta(p: int, k: int, prior) -> np.ndarray:
+        """buildBeta (:94-106): beta_ii = 1, beta_ij = 0 for j > i, one call of prior() for every entry below the diagonal (row by
+        row); prior may also be a number."""
+        if not (1 <= k <= MAX_K and k <= p <= MAX_P):
+            raise ValueError(f"1 <= k <= {MAX_K} and k <= p <= {MAX_P}: got p = {p}, k = {k}")
+        draw = prior if callable(prior) else (lambda: prior)
+        beta = np.zeros((p, k))
+        for i in range(p):
+            for j in range(k):
+                beta[i, j] = 1.0 if i == j else (float(draw()) if i > j else 0.0)
+        return beta
+
+    @staticmethod
+    def simulate(params: FsvParameters, T: int, N: int, seed: int = 0):
+        """FactorSv.simulate (:108-142) for N panels with NumPy: (y [N][T][p], f [N][k][T], alpha [N][k][T+1]), alpha[:, j, 0] the
+        stationary initial state of factor j.  For tests and benchmarks."""
+        rng = np.random.default_rng(seed)
+        p, k = params.p, params.k
+        sv = params.sv()
+        phi, mu, sig = sv[:, 0], sv[:, 1], sv[:, 2]
+        alpha = np.empty((N, k, T + 1))
+        alpha[:, :, 0] = mu + sig / np.sqrt(1.0 - phi * phi) * rng.standard_normal((N, k))
+        for t in range(T):
+            alpha[:, :, t + 1] = mu + phi * (alpha[:, :, t] - mu) + sig * rng.standard_normal((N, k))
+        f = rng.standard_normal((N, k, T)) * np.exp(0.5 * alpha[:, :, 1:])
+        y = np.einsum("ij,njt->nti", params.beta, f) + np.sqrt(params.v) * rng.standard_normal((N, T, p))
+        return y, f, alpha
+
+    @staticmethod
+    def _shape(ys, init_p):
+        if len(ys.shape) != 3:
+            raise ValueError(f"ys must be [N][T][p], got the shape {tuple(ys.shape)}")
+        N, T, p = (int(x) for x in ys.shape)
+        if p != init_p.p:
+            raise ValueError(f"ys has p = {p} series, the initial beta {init_p.p} rows")
+        if T < 2:
+            raise ValueError("the factor stochastic-volatility sampler needs T >= 2 (the reference's sums throw on a single observation)")
+        return N, T, p, init_p.k
+
+    @staticmethod
+    def initialise_state_ar(ys, init_p: FsvParameters, engine, *, seed: int = 0, series_offset: int = 0, literal: bool = False):
+        """initialiseStateAr (:595-610): initialiseFactors (:571-590; the factor draw with unit factor variances), then
+        StochasticVolatility.initial_state_ar on every factor series.  Returns the device-resident chain state {"y", "f" [N][k][T],
+        "alpha" [N][k][T+1], "sv" [N][k][3], "beta" [N][p][k], "v" [N][p], "ystar", "v_mix" (the mixture call's buffers), "status"}."""
+        N, T, p, k = FactorSv._shape(ys, init_p)
+        put, y = place(ys, engine, N, T * p)
+        y = y.reshape(N, T, p)
+        beta = put(np.broadcast_to(init_p.beta, (N, p, k)))
+        v = put(np.broadcast_to(init_p.v, (N, p)))
+        sv = put(np.broadcast_to(init_p.sv(), (N, k, 3)))
+        fac = engine.fsv_factors(y, beta, v, None, iteration=INIT_ITERATION, seed=seed, series_offset=series_offset, literal=literal)
+        f = fac["f"]
+        st = StochasticVolatility.initial_state_ar(f.reshape(N * k, T), sv.reshape(N * k, 3), engine, seed=seed,
+                                                   series_offset=series_offset * k)
+        status = or_status(fac["status"], FactorSv._fold(st["status"], N, k))
+        return {"y": y, "f": f, "alpha": st["alpha"].reshape(N, k, T + 1), "sv": sv, "beta": beta, "v": v, "ystar": st["ystar"],
+                "v_mix": st["v"], "status": status}
+
+    @staticmethod
+    def _fold(status, N, k):
+        """The [N k] flags of the factor chains or'ed onto their panels."""
+        return None if status is None else np.bitwise_or.reduce(host(status).astype(np.int32).reshape(N, k), axis=1)
+
+    @staticmethod
+    def sample_ar(prior_beta: Gaussian, prior_sigma_eta: InverseGamma, prior_mu: Gaussian, prior_phi: Gaussian, prior_sigma: InverseGamma,
+                  ys, init_p: FsvParameters, engine, *, n_iter: int, seed: int = 0, series_offset: int = 0, literal: bool = False,
+                  keep_factors: bool = True) -> Iterator["FactorSv.State"]:
+        """FactorSv.sampleAr (:622-645) for N independent panels: ys [N][T][p] (NaN = missing; numpy or a torch device tensor), every
+        panel started at init_p.  prior_beta: the Gaussian(mean, sd) of the free loadings; prior_sigma_eta, prior_mu, prior_phi: the
+        priors of sample_uni for every factor's (sigma_eta^2, mu, phi); prior_sigma: the InverseGamma of sigma^2.  Yields one State per
+        iteration."""
+        if not (isinstance(prior_beta, Gaussian) and isinstance(prior_mu, Gaussian) and isinstance(prior_phi, Gaussian)
+                and isinstance(prior_sigma_eta, InverseGamma) and isinstance(prior_sigma, InverseGamma)):
+            raise TypeError("the device evaluates Gaussian priors of beta, mu and phi and InverseGamma priors of sigma_eta^2 and sigma^2 only")
+        if not isinstance(init_p, FsvParameters):
+            raise TypeError("init_p must be an FsvParameters")
+        N, T, p, k = FactorSv._shape(ys, init_p)
+        lit = 1 if literal else 0
+        sv_prior = _lib.SvPrior(0, lit, prior_phi.mean, prior_phi.sd, prior_mu.mean, prior_mu.sd, prior_sigma_eta.shape,
+                                prior_sigma_eta.scale, 100.0, 0.05)
+        fsv_prior = _lib.FsvPrior(lit, prior_beta.mean, prior_beta.sd, prior_sigma.shape, prior_sigma.scale)
+        return FactorSv._run(ys, init_p, engine, sv_prior, fsv_prior, n_iter, seed, series_offset, literal, keep_factors, N, T, p, k)
+
+    @staticmethod
+    def _run(ys, init_p, engine, sv_prior, fsv_prior, n_iter, seed, series_offset, literal, keep_factors, N, T, p, k):
+        c = FactorSv.initialise_state_ar(ys, init_p, engine, seed=seed, series_offset=series_offset, literal=literal)
+        y, f, alpha, sv, beta, v = c["y"], c["f"], c["alpha"], c["sv"], c["beta"], c["v"]
+        bufs, status0 = {"ystar": c["ystar"], "v": c["v_mix"]}, c["status"]
+        for it in range(n_iter):
+            sv2 = sv.reshape(N * k, 3)
+            st = StochasticVolatility.sample_state_ar(f.reshape(N * k, T), alpha.reshape(N * k, T + 1), sv2, engine, iteration=it,
+                                                      seed=seed, series_offset=series_offset * k, out=bufs)
+            alpha, bufs = st["alpha"].reshape(N, k, T + 1), {"ystar": st["ystar"], "v": st["v"]}
+            res = engine.sv_params(alpha.reshape(N * k, T + 1), sv2, sv_prior, iteration=it, seed=seed, series_offset=series_offset * k,
+                                   out={"sv": sv2})
+            fac = engine.fsv_factors(y, beta, v, alpha, iteration=it, seed=seed, series_offset=series_offset, literal=literal,
+                                     out={"f": f})
+            load = engine.fsv_loadings(y, f, beta, fsv_prior, iteration=it, seed=seed, series_offset=series_offset, v=v,
+                                       out={"beta": beta, "v": v})
+            status = or_status(FactorSv._fold(or_status(st["status"], res.get("status")), N, k), or_status(fac["status"], load["status"]))
+            if it == 0:
+                status = or_status(status, status0)
+            params = {"beta": host(beta).copy(), "v": host(v).copy(), "sv": host(sv).copy()}
+            yield FactorSv.State(params, host(f).copy() if keep_factors else None, host(alpha).copy() if keep_factors else None, status)

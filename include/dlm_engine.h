@@ -387,6 +387,59 @@ int dlm_sv_ou_params_batch(dlm_engine* e, int32_t N, int32_t T, const double* ti
                            const dlm_sv_ou_prior* prior, uint64_t iteration, const dlm_options* opts, double* sv_out,
                            int32_t* accepted, int32_t* status);
 
+/* The factor half of the factor stochastic-volatility Gibbs sampler (FactorSv.sampleAr, FactorSv.scala:546-562) for N independent
+ * panels of p series, T times and k latent factors, 1 <= k <= 8, k <= p <= 64:
+ *   y_t = beta f_t + eps_t,  eps_t ~ N(0, diag(v)),  f_{j,t} ~ N(0, exp(alpha_{j,t})),  alpha_j AR(1) with (phi, mu, sigma_eta)_j;
+ *   beta p x k with beta_ii = 1, beta_ij = 0 for j > i, beta_ij ~ N(beta_mean, beta_sd^2) elsewhere;
+ *   v = sigma^2 1_p,  sigma^2 ~ InverseGamma(sigma_shape, sigma_scale).
+ * Layouts: y [N][T][p] (NaN = missing), f [N][k][T] (factor-major: viewed as [N k][T] it is the y of dlm_sv_mixture_batch; NaN where
+ * the time is missing), alpha [N][k][T+1] (alpha[..][t+1] belongs to y[t]), sv [N][k][3], beta [N][p][k] row-major, v [N][p].
+ * One iteration, in sampleStep's order:
+ *   dlm_sv_mixture_batch, dlm_ar1_ffbs_batch, dlm_sv_params_batch on the N k factor series f (a missing factor is a missing
+ *       observation); chain (n, j) is the series (series_offset + n) k + j of those calls.  Q31: the reference's sampleStep draws the
+ *       state with the knot block sampler, which is not offered; this is its own alternative sampleVolatilityAr (:415-435);
+ *   dlm_fsv_factors_batch    f_t | (y_t, beta, v, alpha_{t+1}) for every (n, t)                      (sampleFactors, :168-186)
+ *   dlm_fsv_loadings_batch   sigma^2 | (y, f, beta_old), then beta | (y, f, sigma^2) row by row      (sampleSigmaUni, :516-541;
+ *                                                                                                     sampleBeta / sampleBetaRow, :253-333)
+ * A time t is OBSERVED when all p components of y_t are finite (encodePartiallyMissing, :150-157, treats a partially missing y_t as
+ * wholly missing; both modes).  An unobserved time gets f_t = NaN and contributes to no sum.
+ *
+ * dlm_fsv_factors_batch.  For an observed time, with the Cholesky factor P_t = L L^T and z ~ N(0, I_k):
+ *   P_t = beta^T diag(1 / v) beta + diag(exp(-alpha_{.,t+1})),   m_t = P_t^-1 beta^T diag(1 / v) y_t,
+ *   f_t = m_t + L^-T z ~ N(m_t, P_t^-1);   literal = 1:  f_t = m_t + P_t^-1 z, of covariance P_t^-2 (Q27: rnorm, :222-232).
+ * alpha == NULL is initialiseFactors (:571-590): the second term of P_t is the identity.  z_j is the Box-Muller normal of slot t,
+ * attempt j of the stream below.  status [N] (nullable): DLM_ST_NOT_PD when a Cholesky pivot is not positive (that time is NaN);
+ * DLM_ST_NONFINITE for a non-finite beta or a v that is not positive and finite -- the whole panel's f is NaN -- and for a non-finite
+ * alpha_{j,t+1} or an exp(-alpha) that overflows -- that time is NaN.  Other panels are untouched.
+ *
+ * dlm_fsv_loadings_batch.  A time counts when y_t is observed and f_t is finite; over those times of a panel, n of them,
+ *   S = sum f_t f_t^T,   c_i = sum f_t y_ti,   ssy = sum |y_t - beta_in f_t|^2,
+ *   sigma^2 ~ InverseGamma(shape + n p / 2, scale + ssy / 2);  then for the rows i = 1 .. p - 1, q = min(i, k), S_q the leading block:
+ *   beta_{i,0:q} ~ N(P^-1 r, P^-1),  P = S_q / sigma^2 + I / beta_sd^2,  r = (c_i - [i < k] S_{0:q,i}) / sigma^2 + beta_mean / beta_sd^2
+ * (a row i < k regresses y_i - f_i on the earlier factors: its own loading is the fixed 1).  prior->literal = 1 is the reference's
+ * arithmetic: InverseGamma(shape + n / 2, scale + ssy / (2 p)); P = S_q / sigma^2 + I beta_sd^2 and
+ * r = c_i / sigma^2 (the prior variance where the precision belongs, no prior mean, f_i not removed); the draw P^-1 r + P^-1 z.
+ * beta_out [N][p][k] gets its fixed ones and zeros too and may be beta_in; v_out [N][p] holds sigma^2 in every entry and may be v_in.
+ * v_in is nullable.  status [N] (nullable): a panel without a counted time gets DLM_ST_NONFINITE and beta_out = beta_in, v_out = v_in
+ * (NaN without v_in); sums that are not finite give DLM_ST_NONFINITE and NaN; a non-positive pivot DLM_ST_NOT_PD and NaN in that row.
+ * The sums are taken in a fixed order without atomics: a panel's output depends on neither N nor its neighbours.
+ *
+ * Draws: a Philox stream of their own, counter (opts->seed, opts->series_offset + n, iteration, slot): slot t, attempt j for the
+ * factors' normals; at the top of the field one slot for the Gamma of sigma^2 and one per row of beta (attempt j: its entry j).
+ * Limits: N >= 1, 2 <= T < 2^21 - 64, N ceil(T / 256) < 2^31; k or p outside their limits, a non-positive beta_sd, shape or scale
+ * and literal outside {0, 1} are DLM_ERR_ARG.  opts: mem, seed, series_offset, DLM_OPT_ASYNC. */
+typedef struct {
+  int32_t literal;                 /* 1: the reference's arithmetic, Q27-Q30 */
+  double beta_mean, beta_sd;       /* Gaussian(mean, sd) as Breeze takes it */
+  double sigma_shape, sigma_scale; /* InverseGamma prior of sigma^2 */
+} dlm_fsv_prior;
+int dlm_fsv_factors_batch(dlm_engine* e, int32_t N, int32_t T, int32_t p, int32_t k, const double* y, const double* beta,
+                          const double* v, const double* alpha, int32_t literal, uint64_t iteration, const dlm_options* opts,
+                          double* f, int32_t* status);
+int dlm_fsv_loadings_batch(dlm_engine* e, int32_t N, int32_t T, int32_t p, int32_t k, const double* y, const double* f,
+                           const double* beta_in, const double* v_in, const dlm_fsv_prior* prior, uint64_t iteration,
+                           const dlm_options* opts, double* beta_out, double* v_out, int32_t* status);
+
 /* Per-series log-likelihood by the prediction-error decomposition,
  *   loglik[n] = sum_t log N(y_t^obs ; f_t^obs, Q_t^obs),
  * i.e. KalmanFilter.conditionalLikelihood (KalmanFilter.scala:138-153) summed over the series (steps with no observed

@@ -308,6 +308,24 @@ JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_svOuParams(JNIEnv
   throw_if(env, eng(h), dlm_sv_ou_params_batch(eng(h), n, t, ptr<const double>(times), ptr<const double>(alpha), ptr<const double>(svIn), &pr, static_cast<uint64_t>(iteration),
                                                &o, ptr<double>(svOut), ptr<int32_t>(accepted), ptr<int32_t>(status)));
 }
+// ---- the factor half of the factor stochastic-volatility sampler (FactorSv.scala:168-186, :253-333, :516-541) around the factor chains'
+// svMixture / ar1Ffbs / svParams calls; alpha = 0: initialiseFactors; vIn = 0: none.  The prior crosses as scalars in dlm_fsv_prior's field order.
+JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_fsvFactors(JNIEnv* env, jobject, jlong h, jint n, jint t, jint p, jint k, jlong y, jlong beta, jlong v, jlong alpha,
+                                                                          jint literal, jlong iteration, jlongArray opts, jlong f, jlong status) {
+  dlm_options o{};
+  if (!read_opts(env, opts, o)) return;
+  throw_if(env, eng(h), dlm_fsv_factors_batch(eng(h), n, t, p, k, ptr<const double>(y), ptr<const double>(beta), ptr<const double>(v), ptr<const double>(alpha), literal,
+                                              static_cast<uint64_t>(iteration), &o, ptr<double>(f), ptr<int32_t>(status)));
+}
+JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_fsvLoadings(JNIEnv* env, jobject, jlong h, jint n, jint t, jint p, jint k, jlong y, jlong f, jlong betaIn, jlong vIn,
+                                                                           jint literal, jdouble betaMean, jdouble betaSd, jdouble sigmaShape, jdouble sigmaScale, jlong iteration,
+                                                                           jlongArray opts, jlong betaOut, jlong vOut, jlong status) {
+  dlm_options o{};
+  if (!read_opts(env, opts, o)) return;
+  const dlm_fsv_prior pr{literal, betaMean, betaSd, sigmaShape, sigmaScale};
+  throw_if(env, eng(h), dlm_fsv_loadings_batch(eng(h), n, t, p, k, ptr<const double>(y), ptr<const double>(f), ptr<const double>(betaIn), ptr<const double>(vIn), &pr,
+                                               static_cast<uint64_t>(iteration), &o, ptr<double>(betaOut), ptr<double>(vOut), ptr<int32_t>(status)));
+}
 // ---- pooled-parameter Gibbs: reduce over series, then over GPUs (RCCL) ---------------------------------------------------------------
 JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_statsPool(JNIEnv* env, jobject, jlong h, jlong stats, jint n, jint l, jlong pooled, jlongArray opts) {
   dlm_options o{};
