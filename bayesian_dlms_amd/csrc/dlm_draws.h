@@ -16,11 +16,13 @@ namespace dlm {
 //   DLM_KEY_SVOU      dlm_sv_ou_params_batch: DLM_SVOU_SLOT_*; the OU chain's mixture call draws under DLM_KEY_SV
 //   DLM_KEY_FSV       dlm_fsv_factors_batch: comp = t, attempt j for the normal of factor j at time t; dlm_fsv_loadings_batch: DLM_FSV_SLOT_*
 //                     (the factor chains' volatility calls draw under DLM_KEY_SV at the series (series_offset + n) k + j)
+//   DLM_KEY_DLMFSV    dlm_dlmfsv_impute_batch: comp = t; attempt j < 8 the normal of factor j, attempt 8 + i the normal of component i
 constexpr unsigned DLM_KEY_GIBBS = 0x47494242u;      // "GIBB"
 constexpr unsigned DLM_KEY_STUDENTT = 0x53545544u;   // "STUD"
 constexpr unsigned DLM_KEY_SV = 0x5354564Fu;         // "STVO"
 constexpr unsigned DLM_KEY_SVOU = 0x53564F55u;       // "SVOU"
 constexpr unsigned DLM_KEY_FSV = 0x46535620u;        // "FSV "
+constexpr unsigned DLM_KEY_DLMFSV = 0x444C4653u;     // "DLFS"
 
 // ---- the slots ------------------------------------------------------------------------------------------------------------------
 // comp is a 21-bit field (the counter word is comp * 2048 + attempt * 2 + which).  A sampler whose per-time draws take comp = t < T

@@ -1263,6 +1263,86 @@ int dlm_fsv_loadings_batch(dlm_engine* e, int32_t N, int32_t T, int32_t p, int32
   return st.finish(opts->flags & DLM_OPT_ASYNC);
 }
 
+int dlm_dlmfsv_center_batch(dlm_engine* e, const dlm_model_desc* model, const double* y, const double* theta,
+                            const dlm_options* opts, double* r, int32_t* status) {
+  if (!e) return DLM_ERR_ARG;
+  if (!model) return fail(e, DLM_ERR_ARG, "null descriptor");
+  int rc;
+  if ((rc = check_opts(e, opts))) return rc;
+  const int d = model->d, p = model->p, T = model->T, N = model->N;
+  if (d < 1 || p < 1 || T < 1 || N < 1) return fail(e, DLM_ERR_ARG, "d, p, T, N must be >= 1");
+  if (d > 64 || p > dlm::DLM_FSV_MAX_P) return fail(e, DLM_ERR_UNSUPPORTED, "d and p are limited to 64 in this build");
+  if (!model->F || (model->f_stride != 0 && model->f_stride != (int64_t)d * p)) return fail(e, DLM_ERR_ARG, "F required; f_stride must be 0 or d p");
+  if ((long long)T * p > 0x7FFFF000ll) return fail(e, DLM_ERR_ARG, "T p must stay below 2^31 - 4096 (a panel's elements are indexed with an int)");
+  if ((long long)N * (((long long)T * p + 255) / 256) > 0x7FFFFFFFll) return fail(e, DLM_ERR_ARG, "N ceil(T p / 256) must stay below 2^31 (the grid of the centring kernel)");
+  if (!y || !theta || !r) return fail(e, DLM_ERR_ARG, "y, theta and r are required");
+  HIP_TRY(e, hipSetDevice(e->device));
+  dlm::DlmFsvCenterArgs a{};
+  const size_t n = N, t = T, pp = p, dd = d;
+  Stager st(e, opts->mem == DLM_MEM_HOST);
+  st.in(&a.F, model->F, (model->f_stride ? t : 1) * dd * pp);
+  st.in(&a.y, y, n * t * pp);
+  st.in(&a.theta, theta, n * (t + 1) * dd);
+  st.out(&a.r, r, n * t * pp);
+  st.zeroed_out(&a.status, (int*)status, status ? n : 0);
+  if ((rc = st.commit())) return rc;
+  a.N = N; a.T = T; a.p = p; a.d = d; a.f_stride = model->f_stride;
+  e->variant = "dlmfsv-center";
+  HIP_TRY(e, dlm::launch_dlmfsv_center(a, e->stream));
+  return st.finish(opts->flags & DLM_OPT_ASYNC);
+}
+
+int dlm_dlmfsv_impute_batch(dlm_engine* e, int32_t N, int32_t T, int32_t p, int32_t k, const double* r_in, const double* beta,
+                            const double* v, const double* alpha, uint64_t iteration, const dlm_options* opts, double* r_out,
+                            int32_t* status) {
+  if (!e) return DLM_ERR_ARG;
+  int rc;
+  if ((rc = check_opts(e, opts))) return rc;
+  if ((rc = fsv_check_shape(e, N, T, p, k))) return rc;
+  if (!r_in || !beta || !v || !alpha || !r_out) return fail(e, DLM_ERR_ARG, "r_in, beta, v, alpha and r_out are required");
+  HIP_TRY(e, hipSetDevice(e->device));
+  dlm::DlmFsvImputeArgs a{};
+  const size_t n = N, t = T, pp = p, kk = k;
+  Stager st(e, opts->mem == DLM_MEM_HOST);
+  st.in(&a.r_in, r_in, n * t * pp);
+  st.in(&a.beta, beta, n * pp * kk);
+  st.in(&a.v, v, n * pp);
+  st.in(&a.alpha, alpha, n * kk * (t + 1));
+  st.out(&a.r_out, r_out, n * t * pp);
+  st.zeroed_out(&a.status, (int*)status, status ? n : 0);
+  if ((rc = st.commit())) return rc;
+  a.N = N; a.T = T; a.p = p; a.k = k;
+  a.rs = draw_stream(opts, iteration);
+  e->variant = "dlmfsv-impute";
+  HIP_TRY(e, dlm::launch_dlmfsv_impute(a, e->stream));
+  return st.finish(opts->flags & DLM_OPT_ASYNC);
+}
+
+int dlm_dlmfsv_variance_batch(dlm_engine* e, int32_t N, int32_t T, int32_t p, int32_t k, const double* beta, const double* v,
+                              const double* alpha, const dlm_options* opts, double* V, int32_t* status) {
+  if (!e) return DLM_ERR_ARG;
+  int rc;
+  if ((rc = check_opts(e, opts))) return rc;
+  if (N < 1 || T < 1) return fail(e, DLM_ERR_ARG, "N >= 1 and T >= 1");
+  if (k < 1 || k > dlm::DLM_FSV_MAX_K || p < k || p > dlm::DLM_FSV_MAX_P) return fail(e, DLM_ERR_UNSUPPORTED, "1 <= k <= 8 and k <= p <= 64");
+  if ((long long)N * ((T + 63) / 64) > 0x7FFFFFFFll) return fail(e, DLM_ERR_ARG, "N ceil(T / 64) must stay below 2^31 (one block per 64 times of a panel)");
+  if (!beta || !v || !alpha || !V) return fail(e, DLM_ERR_ARG, "beta, v, alpha and V are required");
+  HIP_TRY(e, hipSetDevice(e->device));
+  dlm::DlmFsvVarianceArgs a{};
+  const size_t n = N, t = T, pp = p, kk = k;
+  Stager st(e, opts->mem == DLM_MEM_HOST);
+  st.in(&a.beta, beta, n * pp * kk);
+  st.in(&a.v, v, n * pp);
+  st.in(&a.alpha, alpha, n * kk * (t + 1));
+  st.out(&a.V, V, n * t * pp * pp);
+  st.zeroed_out(&a.status, (int*)status, status ? n : 0);
+  if ((rc = st.commit())) return rc;
+  a.N = N; a.T = T; a.p = p; a.k = k;
+  e->variant = "dlmfsv-variance";
+  HIP_TRY(e, dlm::launch_dlmfsv_variance(a, e->stream));
+  return st.finish(opts->flags & DLM_OPT_ASYNC);
+}
+
 static int ar1_common(dlm_engine* e, int32_t N, int32_t T, const double* times, bool ou, const double* y, const double* v,
                       int64_t v_stride, const double* sv, int64_t sv_stride, const double* z, const dlm_options* opts,
                       double* filt, double* theta, int32_t* status);

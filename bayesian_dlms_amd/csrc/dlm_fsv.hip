@@ -11,7 +11,7 @@
 // A time is OBSERVED when all p components of y_t are finite (encodePartiallyMissing, :150-157: a partially missing y_t is wholly
 // missing); k_fsv_loadings asks for a finite f_t too.  An unobserved time gets f_t = NaN and enters no sum.
 //
-// The small SPD systems (fsv_solve_draw).  P = L L^T by the row-oriented Cholesky factorisation, the lower triangle packed by rows:
+// The small SPD systems (fsv_solve_draw, dlm_fsv_solve.h).  P = L L^T by the row-oriented Cholesky factorisation, the lower triangle packed by rows:
 //   L_jj = sqrt(P_jj - sum_{m<j} L_jm^2),  L_ij = (P_ij - sum_{m<j} L_im L_jm) / L_jj,  the sums subtracted one by one in m order;
 //   u = L^-1 r by forward substitution, x = L^-T u by backward substitution (m ascending from i + 1).
 //   default:  x = L^-T (L^-1 r + z)      = P^-1 r + L^-T z   ~ N(P^-1 r, P^-1)
@@ -45,46 +45,10 @@
 // gamma_unit.  n = 0: DLM_ST_NONFINITE, beta_out = beta_in and v_out = v_in (NaN without a v_in).  Sums that are not finite:
 // DLM_ST_NONFINITE and NaN.  beta_old is in registers before the first barrier, so beta_out may be beta_in.
 #include "dlm_draws.h"
+#include "dlm_fsv_solve.h"
 #include "dlm_wave.h"
 
 namespace dlm {
-
-// x <- P^-1 x + (L^-T z, or P^-1 z with lit); P: the lower triangle packed by rows, overwritten by L.  false: a pivot was not positive
-template <int K>
-__device__ __forceinline__ bool fsv_solve_draw(double (&P)[K * (K + 1) / 2], double (&x)[K], const double (&z)[K], bool lit) {
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    double s = P[j * (j + 1) / 2 + j];
-#pragma unroll
-    for (int m = 0; m < j; ++m) s = s - P[j * (j + 1) / 2 + m] * P[j * (j + 1) / 2 + m];
-    ok = ok && s > 0.0;
-    const double d = sqrt(s);
-    P[j * (j + 1) / 2 + j] = d;
-#pragma unroll
-    for (int i = j + 1; i < K; ++i) {
-      double e = P[i * (i + 1) / 2 + j];
-#pragma unroll
-      for (int m = 0; m < j; ++m) e = e - P[i * (i + 1) / 2 + m] * P[j * (j + 1) / 2 + m];
-      P[i * (i + 1) / 2 + j] = e / d;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < K; ++i) {
-    double s = lit ? x[i] + z[i] : x[i];
-#pragma unroll
-    for (int m = 0; m < i; ++m) s = s - P[i * (i + 1) / 2 + m] * x[m];
-    x[i] = s / P[i * (i + 1) / 2 + i];
-  }
-#pragma unroll
-  for (int i = K - 1; i >= 0; --i) {
-    double s = lit ? x[i] : x[i] + z[i];
-#pragma unroll
-    for (int m = i + 1; m < K; ++m) s = s - P[m * (m + 1) / 2 + i] * x[m];
-    x[i] = s / P[i * (i + 1) / 2 + i];
-  }
-  return ok;
-}
 
 template <int K>
 __global__ __launch_bounds__(256) void k_fsv_factors(FsvFactorsArgs a, int blocks_per_panel) {

@@ -450,6 +450,39 @@ struct FsvLoadingsArgs {
 hipError_t launch_fsv_factors(const FsvFactorsArgs& a, hipStream_t s);
 hipError_t launch_fsv_loadings(const FsvLoadingsArgs& a, hipStream_t s);
 
+// ---- DLM with factor stochastic-volatility noise: what joins dlm_ffbs_batch to the factor sampler above (DlmFsv.scala:173-185;
+// DlmFsvSystem.calculateVariance, DlmFsvSystem.scala:126-131), dlm_dlmfsv.hip.  k and p as above, d <= 64 -------------
+struct DlmFsvCenterArgs {
+  int N, T, p, d;
+  const double* y;        // [N][T][p]
+  const double* theta;    // [N][T+1][d]
+  const double* F;        // [d*p] column-major, or [T][d*p] with f_stride = d*p
+  long long f_stride;
+  double* r;              // [N][T][p]
+  int* status;            // [N], nullable (zeroed by the caller)
+};
+struct DlmFsvVarianceArgs {
+  int N, T, p, k;
+  const double* beta;     // [N][p][k]
+  const double* v;        // [N][p]
+  const double* alpha;    // [N][k][T+1]
+  double* V;              // [N][T][p*p]
+  int* status;            // [N], nullable (zeroed by the caller)
+};
+struct DlmFsvImputeArgs {
+  int N, T, p, k;
+  const double* r_in;     // [N][T][p], NaN = missing
+  const double* beta;     // [N][p][k]
+  const double* v;        // [N][p]
+  const double* alpha;    // [N][k][T+1]
+  DrawStream rs;
+  double* r_out;          // [N][T][p], may be r_in
+  int* status;            // [N], nullable (zeroed by the caller)
+};
+hipError_t launch_dlmfsv_impute(const DlmFsvImputeArgs& a, hipStream_t s);
+hipError_t launch_dlmfsv_center(const DlmFsvCenterArgs& a, hipStream_t s);
+hipError_t launch_dlmfsv_variance(const DlmFsvVarianceArgs& a, hipStream_t s);
+
 // ---- KalmanFilter.likelihood literally (transition density of the filtered means), dlm_loglik.hip ------
 size_t loglik_q7_ws_bytes(const KArgs& a);
 hipError_t launch_loglik_q7(const KArgs& a, const double* records, void* ws, hipStream_t s);   // a.loglik [N] <- records [N][T+1][d+dd]

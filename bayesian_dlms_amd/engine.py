@@ -467,6 +467,64 @@ class Engine:
                                                     op, be.ptr(beta_out), be.ptr(v_out), be.ptr(status)))
         return {"beta": beta_out, "v": v_out, "status": status}
 
+    def dlmfsv_center(self, mat, y, theta, *, flags=0, out=None):
+        """The panel centred on the DLM's mean (dlm_dlmfsv_center_batch; factorObs, DlmFsv.scala:173-185) for N panels:
+        r[t] = y[t] - F_t^T theta[t+1], y [N][T][p] (a NaN stays NaN), theta [N][T+1][d] as ffbs writes it, mat the materialised model
+        (its F, time-invariant or per time).  Returns {"r" [N][T][p], "status"}.  out: dict with an existing "r" buffer."""
+        be = self._backend(y)
+        N = int(y.shape[0]); d, p, T = mat.d, mat.p, mat.T
+        yb, tb = be.put(y), be.put(theta)
+        if tuple(yb.shape) != (N, T, p) or tuple(tb.shape) != (N, T + 1, d):
+            raise EngineError(f"y must be [N][T][p] = {(N, T, p)} and theta [N][T+1][d] = {(N, T + 1, d)}, got {tuple(yb.shape)} and {tuple(tb.shape)}")
+        Fb = be.put(mat.F)
+        md = _lib.ModelDesc(d, p, T, N, be.ptr(Fb).value, mat.f_stride, None, 0, None, None)
+        r = _out_or_empty(be, out, "r", (N, T, p))
+        status = be.empty((N,), np.int32)
+        op = _lib.Options(flags, be.mem, 0, 0)
+        self._hold(flags, yb, tb, Fb)
+        self._check(self.lib.dlm_dlmfsv_center_batch(self.h, md, be.ptr(yb), be.ptr(tb), op, be.ptr(r), be.ptr(status)))
+        return {"r": r, "status": status}
+
+    def dlmfsv_impute(self, r, beta, v, alpha, *, iteration, seed=0, series_offset=0, flags=0, out=None):
+        """The missing components of the partially missing times of a centred panel, drawn given the observed ones
+        (dlm_dlmfsv_impute_batch): r [N][T][p] (NaN = missing), beta [N][p][k], v [N][p], alpha [N][k][T+1].  Times with
+        all or none of their components finite are copied.  Returns {"r" [N][T][p], "status"}.  out: dict with an existing "r" buffer
+        (it may be r itself)."""
+        be = self._backend(r)
+        if r.ndim != 3 or beta.ndim != 3:
+            raise EngineError("r must be [N][T][p] and beta [N][p][k]")
+        N, T, p, k = int(r.shape[0]), int(r.shape[1]), int(r.shape[2]), int(beta.shape[2])
+        rb, bb, vb, ab = be.put(r), be.put(beta), be.put(v), be.put(alpha)
+        if tuple(bb.shape) != (N, p, k) or tuple(vb.shape) != (N, p) or tuple(ab.shape) != (N, k, T + 1):
+            raise EngineError(f"beta must be [N][p][k] = {(N, p, k)}, v [N][p] = {(N, p)} and alpha [N][k][T+1] = {(N, k, T + 1)}, got "
+                              f"{tuple(bb.shape)}, {tuple(vb.shape)} and {tuple(ab.shape)}")
+        ro = _out_or_empty(be, out, "r", (N, T, p))
+        status = be.empty((N,), np.int32)
+        op = _lib.Options(flags, be.mem, seed, series_offset)
+        self._hold(flags, rb, bb, vb, ab)
+        self._check(self.lib.dlm_dlmfsv_impute_batch(self.h, N, T, p, k, be.ptr(rb), be.ptr(bb), be.ptr(vb), be.ptr(ab), int(iteration), op,
+                                                     be.ptr(ro), be.ptr(status)))
+        return {"r": ro, "status": status}
+
+    def dlmfsv_variance(self, beta, v, alpha, *, flags=0, out=None):
+        """The observation-variance stream of the DLM with factor stochastic-volatility noise (dlm_dlmfsv_variance_batch;
+        DlmFsvSystem.calculateVariance, DlmFsvSystem.scala:126-131) for N panels: V[n][t] = beta diag(exp(alpha[.., t+1])) beta^T + diag(v),
+        beta [N][p][k], v [N][p], alpha [N][k][T+1].  Returns {"V" [N][T][p*p] (symmetric bit for bit: the V of ffbs with
+        v_stride = T p p, v_tstride = p p), "status"}.  out: dict with an existing "V" buffer."""
+        be = self._backend(beta)
+        if beta.ndim != 3 or alpha.ndim != 3:
+            raise EngineError("beta must be [N][p][k] and alpha [N][k][T+1]")
+        N, p, k, T = int(beta.shape[0]), int(beta.shape[1]), int(beta.shape[2]), int(alpha.shape[2]) - 1
+        bb, vb, ab = be.put(beta), be.put(v), be.put(alpha)
+        if tuple(vb.shape) != (N, p) or tuple(ab.shape) != (N, k, T + 1):
+            raise EngineError(f"v must be [N][p] = {(N, p)} and alpha [N][k][T+1] = {(N, k, T + 1)}, got {tuple(vb.shape)} and {tuple(ab.shape)}")
+        V = _out_or_empty(be, out, "V", (N, T, p * p))
+        status = be.empty((N,), np.int32)
+        op = _lib.Options(flags, be.mem, 0, 0)
+        self._hold(flags, bb, vb, ab)
+        self._check(self.lib.dlm_dlmfsv_variance_batch(self.h, N, T, p, k, be.ptr(bb), be.ptr(vb), be.ptr(ab), op, be.ptr(V), be.ptr(status)))
+        return {"V": V, "status": status}
+
     def simulate(self, mat, params, N, *, seed=0, series_offset=0, device=False, want_x=True):
         """Dlm.simulateRegular over the model's time grid for N series (dlm_simulate_batch): (x [N][T+1][d], y [N][T][p])."""
         be = _Device(self.device) if device else _Host()

@@ -440,6 +440,55 @@ int dlm_fsv_loadings_batch(dlm_engine* e, int32_t N, int32_t T, int32_t p, int32
                            const double* beta_in, const double* v_in, const dlm_fsv_prior* prior, uint64_t iteration,
                            const dlm_options* opts, double* beta_out, double* v_out, int32_t* status);
 
+/* The DLM whose observation noise is a factor stochastic-volatility process (DlmFsv.scala:64-318) for N independent panels:
+ *   theta_0 ~ N(m0, C0),  theta_t = G theta_{t-1} + w_t,  w_t ~ N(0, W),  W diagonal;
+ *   y_t = F_t^T theta_t + beta f_t + eps_t,  eps_t ~ N(0, diag(v)),  f_{j,t} ~ N(0, exp(alpha_{j,t}))   (the factor part as above).
+ * The three calls here join dlm_ffbs_batch to the factor sampler's calls; one iteration, everything device-resident:
+ *   1 dlm_dlmfsv_center_batch     r_t = y_t - F_t^T theta_{t+1}                                      (factorObs, DlmFsv.scala:173-185)
+ *     dlm_dlmfsv_impute_batch     the missing components of a PARTIALLY missing r_t, drawn given its observed ones (Q34)
+ *   2 dlm_fsv_factors_batch on r  f | r, alpha, beta, v
+ *   3 dlm_sv_mixture_batch, dlm_ar1_ffbs_batch, dlm_sv_params_batch on f: alpha | f, then (phi, mu, sigma_eta) | alpha
+ *   4 dlm_fsv_loadings_batch on (r, f): sigma^2, beta
+ *   5 dlm_dlmfsv_variance_batch   V_t = beta diag(exp(alpha_{.,t+1})) beta^T + diag(v)               (DlmFsvSystem.calculateVariance, DlmFsvSystem.scala:126-131)
+ *   6 dlm_ffbs_batch with params->V = that stream, v_stride = T p p, v_tstride = p p, per-panel W: theta | y, V_{1:T}, W (f integrated out)
+ *   7 dlm_dinvgamma_step_batch on its statistics (W_out; V_out is not used): W | theta
+ * In this order step 6 followed by the next step 2 is one joint draw of (theta, f).  DlmFsv.sampleStep runs 3, 2, 4, 5, 6, 7, whose
+ * next step 3 conditions on the f drawn BEFORE theta was redrawn with f integrated out: not a valid sampler.
+ * y[t] belongs to theta[t+1] and alpha[..][t+1].  A wholly missing y_t is missing for every step.  A PARTIALLY missing y_t is partially
+ * observed for step 6; the factor calls take a time with any component missing as wholly missing, so the reference's steps 2-4 drop
+ * observations that its step 6 uses and do not draw from their full conditionals (Q34).  dlm_dlmfsv_impute_batch completes such a time
+ * first: with the factor draw that follows it is one joint draw of (the missing components, f_t) given the observed ones, and the
+ * completed panel is what steps 2-4 read.  Without the call the iteration is the reference's.
+ *
+ * dlm_dlmfsv_center_batch.  model: d <= 64, p <= 64, T, N and F (d x p column-major; f_stride 0, or d p: the table of T); G and the
+ * time grid are not read.  y, r [N][T][p]; theta [N][T+1][d] as dlm_ffbs_batch writes it.  r_ti = y_ti - sum_j F_ji theta_{t+1,j}, the
+ * sum taken with j ascending; a NaN y_ti stays NaN.  status [N] (nullable): DLM_ST_NONFINITE for a panel with a theta_{t+1,j} that is
+ * not finite.  r may be y.
+ *
+ * dlm_dlmfsv_variance_batch.  1 <= k <= 8, k <= p <= 64.  beta [N][p][k], v [N][p], alpha [N][k][T+1]; V [N][T][p p] gets
+ *   V_t(i, j) = sum_l (beta_il beta_jl) exp(alpha_{l,t+1})  (l ascending)  + [i == j] v_i
+ * for EVERY t, symmetric bit for bit.  status [N] (nullable): DLM_ST_NONFINITE for a panel with a beta or alpha that is not finite,
+ * an exp(alpha) that overflows or a v that is not positive and finite (V is then what the arithmetic gives).
+ *
+ * dlm_dlmfsv_impute_batch.  r_in, r_out [N][T][p] (r_out may be r_in), beta, v, alpha as above.  A time with all or none of its
+ * components finite is copied.  For any other, over its observed components i: P = sum_i beta_i beta_i^T / v_i + diag(exp(-alpha_{.,t+1})),
+ * f = P^-1 sum_i beta_i r_ti / v_i + L^-T z (P = L L^T), and every missing r_ti = sum_j beta_ij f_j + sqrt(v_i) z_i.  Draws: a Philox
+ * stream of its own, counter (opts->seed, opts->series_offset + n, iteration, slot t): attempt j for z_j, attempt 8 + i for z_i.
+ * status [N] (nullable): DLM_ST_NONFINITE for a non-finite beta or a v that is not positive and finite (the panel is copied), and for a
+ * non-finite alpha_{j,t+1} or an overflowing exp(-alpha) at a partially missing time; DLM_ST_NOT_PD for a pivot that is not positive
+ * (that time is copied).  Limits and their codes: those of dlm_fsv_factors_batch.  opts: mem, seed, series_offset, DLM_OPT_ASYNC.
+ *
+ * The centring and the variance call draw nothing; a panel's output depends on neither N nor its neighbours in any of the three.
+ * Their limits: N, T >= 1, T p < 2^31 - 4096, N ceil(T p / 256) < 2^31 and N ceil(T / 64) < 2^31 (DLM_ERR_ARG); d, p or k outside
+ * their limits are DLM_ERR_UNSUPPORTED.  opts: mem, DLM_OPT_ASYNC. */
+int dlm_dlmfsv_center_batch(dlm_engine* e, const dlm_model_desc* model, const double* y, const double* theta,
+                            const dlm_options* opts, double* r, int32_t* status);
+int dlm_dlmfsv_impute_batch(dlm_engine* e, int32_t N, int32_t T, int32_t p, int32_t k, const double* r_in, const double* beta,
+                            const double* v, const double* alpha, uint64_t iteration, const dlm_options* opts, double* r_out,
+                            int32_t* status);
+int dlm_dlmfsv_variance_batch(dlm_engine* e, int32_t N, int32_t T, int32_t p, int32_t k, const double* beta, const double* v,
+                              const double* alpha, const dlm_options* opts, double* V, int32_t* status);
+
 /* Per-series log-likelihood by the prediction-error decomposition,
  *   loglik[n] = sum_t log N(y_t^obs ; f_t^obs, Q_t^obs),
  * i.e. KalmanFilter.conditionalLikelihood (KalmanFilter.scala:138-153) summed over the series (steps with no observed

@@ -326,6 +326,32 @@ JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_fsvLoadings(JNIEn
   throw_if(env, eng(h), dlm_fsv_loadings_batch(eng(h), n, t, p, k, ptr<const double>(y), ptr<const double>(f), ptr<const double>(betaIn), ptr<const double>(vIn), &pr,
                                                static_cast<uint64_t>(iteration), &o, ptr<double>(betaOut), ptr<double>(vOut), ptr<int32_t>(status)));
 }
+// ---- the DLM with factor stochastic-volatility noise (DlmFsv.scala:173-185; DlmFsvSystem.scala:126-131): the centred panel for the factor calls above, the missing components of its partially missing times (rOut may be rIn) and the V_t stream for
+// ffbs.  The centring reads d, p, T, N and F of the model (model[4] = F, model[5] = f_stride, as make_model lays them out); status = 0: none.
+JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_dlmFsvCenter(JNIEnv* env, jobject, jlong h, jlongArray model, jlong y, jlong theta, jlongArray opts, jlong r, jlong status) {
+  if (!model || env->GetArrayLength(model) != 10) { throw_arg(env, "model must be long[10] = {d, p, T, N, F, fStride, G, nG, gIndex, dt}"); return; }
+  jlong m[10];
+  env->GetLongArrayRegion(model, 0, 10, m);
+  dlm_model_desc md{};
+  md.d = static_cast<int32_t>(m[0]); md.p = static_cast<int32_t>(m[1]); md.T = static_cast<int32_t>(m[2]); md.N = static_cast<int32_t>(m[3]);
+  md.F = ptr<const double>(m[4]); md.f_stride = m[5];
+  dlm_options o{};
+  if (!read_opts(env, opts, o)) return;
+  throw_if(env, eng(h), dlm_dlmfsv_center_batch(eng(h), &md,ptr<const double>(y), ptr<const double>(theta), &o, ptr<double>(r), ptr<int32_t>(status)));
+}
+JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_dlmFsvImpute(JNIEnv* env, jobject, jlong h, jint n, jint t, jint p, jint k, jlong rIn, jlong beta, jlong v, jlong alpha, jlong iteration,
+                                                                            jlongArray opts, jlong rOut, jlong status) {
+  dlm_options o{};
+  if (!read_opts(env, opts, o)) return;
+  throw_if(env, eng(h), dlm_dlmfsv_impute_batch(eng(h), n, t, p, k, ptr<const double>(rIn), ptr<const double>(beta), ptr<const double>(v), ptr<const double>(alpha), static_cast<uint64_t>(iteration), &o,
+                                                ptr<double>(rOut), ptr<int32_t>(status)));
+}
+JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_dlmFsvVariance(JNIEnv* env, jobject, jlong h, jint n, jint t, jint p, jint k, jlong beta, jlong v, jlong alpha, jlongArray opts,
+                                                                              jlong vOut, jlong status) {
+  dlm_options o{};
+  if (!read_opts(env, opts, o)) return;
+  throw_if(env, eng(h), dlm_dlmfsv_variance_batch(eng(h), n, t, p, k, ptr<const double>(beta), ptr<const double>(v), ptr<const double>(alpha), &o, ptr<double>(vOut), ptr<int32_t>(status)));
+}
 // ---- pooled-parameter Gibbs: reduce over series, then over GPUs (RCCL) ---------------------------------------------------------------
 JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_statsPool(JNIEnv* env, jobject, jlong h, jlong stats, jint n, jint l, jlong pooled, jlongArray opts) {
   dlm_options o{};

@@ -78,6 +78,10 @@ final class Native private[gpu] () {
   /** the factor half of the factor stochastic-volatility sampler (FactorSv.sampleFactors; sampleSigmaUni, then sampleBeta) around the factor chains' svMixture / ar1Ffbs / svParams calls: y [N][T][p], f [N][k][T], alpha [N][k][T+1] (0: initialiseFactors), beta [N][p][k], v [N][p] (vIn = 0: none); the prior as scalars in dlm_fsv_prior's order */
   @native def fsvFactors(h: Long, n: Int, t: Int, p: Int, k: Int, y: Long, beta: Long, v: Long, alpha: Long, literal: Int, iteration: Long, opts: Array[Long], f: Long, status: Long): Unit
   @native def fsvLoadings(h: Long, n: Int, t: Int, p: Int, k: Int, y: Long, f: Long, betaIn: Long, vIn: Long, literal: Int, betaMean: Double, betaSd: Double, sigmaShape: Double, sigmaScale: Double, iteration: Long, opts: Array[Long], betaOut: Long, vOut: Long, status: Long): Unit
+  /** the DLM with factor stochastic-volatility noise (DlmFsv.scala:173-185; DlmFsvSystem.calculateVariance): r = y - F^T theta for the factor calls above (the model's d, p, T, N, F are read); dlmFsvImpute draws the missing components of its partially missing times given the observed ones; V [N][T][p p] = beta diag(exp(alpha)) beta^T + diag(v), the V_t stream of ffbs */
+  @native def dlmFsvCenter(h: Long, model: Array[Long], y: Long, theta: Long, opts: Array[Long], r: Long, status: Long): Unit
+  @native def dlmFsvImpute(h: Long, n: Int, t: Int, p: Int, k: Int, rIn: Long, beta: Long, v: Long, alpha: Long, iteration: Long, opts: Array[Long], rOut: Long, status: Long): Unit
+  @native def dlmFsvVariance(h: Long, n: Int, t: Int, p: Int, k: Int, beta: Long, v: Long, alpha: Long, opts: Array[Long], vOut: Long, status: Long): Unit
   @native def statsPool(h: Long, stats: Long, n: Int, l: Int, pooled: Long, opts: Array[Long]): Unit
   @native def commUniqueId(): Array[Byte]
   @native def commInitRank(h: Long, nranks: Int, rank: Int, id: Array[Byte]): Unit
