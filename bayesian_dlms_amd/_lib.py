@@ -138,6 +138,7 @@ SYMBOLS = [
     ("dlm_dlmfsv_impute_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, _V, ctypes.c_uint64, _OP,
                                                _V, _V]),
     ("dlm_dlmfsv_variance_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, _OP, _V, _V]),
+    ("dlm_dlmfsvsys_innovations_batch", ctypes.c_int, [_V, _MP, _V, _OP, _V, _V]),
     ("dlm_ou_ffbs_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, ctypes.c_int64, _V, ctypes.c_int64,
                                          _V, _OP, _V, _V, _V]),
     ("dlm_ar1_ffbs_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, ctypes.c_int64, _V, ctypes.c_int64,

@@ -40,6 +40,19 @@
 // writes; the stores are plain or non-temporal by DLM_DLMFSV_NT_STORES (measured both ways).
 // A beta or alpha_{l,t+1} that is not finite, an exp(alpha) that overflows, a v that is not positive and finite: DLM_ST_NONFINITE for the
 // panel; V is what the arithmetic gives.
+//
+// The same model with the factor process as the SYSTEM noise (DlmFsvSystem.scala:215-344): theta_t = G theta_{t-1} + beta f_t + eps_t,
+// y_t = F_t^T theta_t + nu_t.  There the factor calls read the state's innovations (p := d) and k_dlmfsv_variance writes the W_t stream.
+//   k_dlmfsvsys_innovations   w_t = theta_{t+1} - G theta_t                            (factorState, DlmFsvSystem.scala:109-117)
+// theta [N][T+1][d], one G d x d column-major (G_ij at i + j d), w [N][T][d] (w[t] belongs to alpha[..][t+1], as y[t] does above), d <= 64.
+// k_dlmfsv_center's shape: one lane per output element (t, i), a block takes 2048 consecutive elements, 256 at a time, so theta_{t+1,i}
+// (element e + d of the panel's theta) and w_ti are fully coalesced -- they are the 16 bytes per element that must move: the d loads of
+// theta_t fall on the lines that theta_{t+1,i} asked for one time earlier, so HBM sees theta once -- and the block's copy of G
+// (32 KB at d = 64) is paid once per 2048.  w_ti = theta_{t+1,i} - s,  s = sum_j G_ij theta_{t,j} with j ascending from s = 0.  G sits in
+// LDS as it is: column-major already puts the d lanes of a time on consecutive doubles for every j, so no bank conflict whatever d is,
+// and the 64 / d times of a wave read the same words (a broadcast).  The d loads of theta_t are the same addresses in the d neighbouring
+// lanes: one request per distinct line, served by the vector L1.  A theta_{t,j} that is not finite, theta_0 and theta_T included (every
+// one is read): DLM_ST_NONFINITE for the panel (w is then what the arithmetic gives).  w must not alias theta.
 #include "dlm_draws.h"
 #include "dlm_fsv_solve.h"
 
@@ -90,6 +103,35 @@ __global__ __launch_bounds__(256) void k_dlmfsv_center(DlmFsvCenterArgs a, int b
       }
     }
     a.r[on + e] = a.y[on + e] - s;
+  }
+  if (bad && a.status) atomicOr(&a.status[n], DLM_ST_NONFINITE);
+}
+
+__global__ __launch_bounds__(256) void k_dlmfsvsys_innovations(DlmFsvSysInnovationsArgs a, int blocks_per_panel) {
+  extern __shared__ double sG[];   // G as it is: G_ij at i + j d
+  const int tid = threadIdx.x, d = a.d, Td = a.T * a.d;
+  const int n = (int)(blockIdx.x / (unsigned)blocks_per_panel);
+  const int e0 = (int)(blockIdx.x - (unsigned)n * (unsigned)blocks_per_panel) * DLM_DLMFSV_CENTER_ELEMS;
+  const int e1 = e0 + DLM_DLMFSV_CENTER_ELEMS < Td ? e0 + DLM_DLMFSV_CENTER_ELEMS : Td;
+  const double INF = __builtin_inf();
+  for (int q = tid; q < d * d; q += 256) sG[q] = a.G[q];
+  __syncthreads();
+  const double* thn = a.theta + (size_t)n * (a.T + 1) * d;
+  double* wn = a.w + (size_t)n * Td;
+  bool bad = false;
+  for (int e = e0 + tid; e < e1; e += 256) {
+    const int t = e / d, i = e - t * d;
+    const double* th = thn + (size_t)t * d;
+    double s = 0.0;
+#pragma unroll 4
+    for (int j = 0; j < d; ++j) {
+      const double x = th[j];
+      bad = bad || !(fabs(x) < INF);
+      s = s + sG[i + j * d] * x;
+    }
+    const double x1 = thn[(size_t)e + d];   // theta_{t+1,i}
+    bad = bad || !(fabs(x1) < INF);
+    wn[e] = x1 - s;
   }
   if (bad && a.status) atomicOr(&a.status[n], DLM_ST_NONFINITE);
 }
@@ -247,6 +289,11 @@ hipError_t launch_dlmfsv_center(const DlmFsvCenterArgs& a, hipStream_t s) {
   const int bpp = (int)(((long long)a.T * a.p + DLM_DLMFSV_CENTER_ELEMS - 1) / DLM_DLMFSV_CENTER_ELEMS);
   const size_t lds = a.f_stride ? 0 : sizeof(double) * (size_t)a.d * a.p;
   return launch(k_dlmfsv_center, dim3((unsigned)a.N * (unsigned)bpp), dim3(256), lds, s, a, bpp);
+}
+
+hipError_t launch_dlmfsvsys_innovations(const DlmFsvSysInnovationsArgs& a, hipStream_t s) {
+  const int bpp = (int)(((long long)a.T * a.d + DLM_DLMFSV_CENTER_ELEMS - 1) / DLM_DLMFSV_CENTER_ELEMS);
+  return launch(k_dlmfsvsys_innovations, dim3((unsigned)a.N * (unsigned)bpp), dim3(256), sizeof(double) * (size_t)a.d * a.d, s, a, bpp);
 }
 
 hipError_t launch_dlmfsv_variance(const DlmFsvVarianceArgs& a, hipStream_t s) {

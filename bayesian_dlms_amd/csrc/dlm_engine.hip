@@ -1343,6 +1343,36 @@ int dlm_dlmfsv_variance_batch(dlm_engine* e, int32_t N, int32_t T, int32_t p, in
   return st.finish(opts->flags & DLM_OPT_ASYNC);
 }
 
+int dlm_dlmfsvsys_innovations_batch(dlm_engine* e, const dlm_model_desc* model, const double* theta, const dlm_options* opts,
+                                    double* w, int32_t* status) {
+  if (!e) return DLM_ERR_ARG;
+  if (!model) return fail(e, DLM_ERR_ARG, "null descriptor");
+  int rc;
+  if ((rc = check_opts(e, opts))) return rc;
+  const int d = model->d, T = model->T, N = model->N;
+  if (d < 1 || T < 1 || N < 1) return fail(e, DLM_ERR_ARG, "d, T, N must be >= 1");
+  if (d > 64) return fail(e, DLM_ERR_UNSUPPORTED, "d is limited to 64 in this build");
+  if (model->g_index || model->dt) return fail(e, DLM_ERR_UNSUPPORTED, "the innovations take one G on the regular unit grid (no g_index, no dt): the AR(1) volatility of the factors has no dt");
+  if (!model->G || model->n_g != 1) return fail(e, DLM_ERR_ARG, "one G required (n_g = 1)");
+  if ((long long)T * d > 0x7FFFF000ll) return fail(e, DLM_ERR_ARG, "T d must stay below 2^31 - 4096 (a panel's elements are indexed with an int)");
+  if ((long long)N * (((long long)T * d + 255) / 256) > 0x7FFFFFFFll) return fail(e, DLM_ERR_ARG, "N ceil(T d / 256) must stay below 2^31 (the grid of the innovations kernel)");
+  if (!theta || !w) return fail(e, DLM_ERR_ARG, "theta and w are required");
+  if (w == theta) return fail(e, DLM_ERR_ARG, "w must not be theta");
+  HIP_TRY(e, hipSetDevice(e->device));
+  dlm::DlmFsvSysInnovationsArgs a{};
+  const size_t n = N, t = T, dd = d;
+  Stager st(e, opts->mem == DLM_MEM_HOST);
+  st.in(&a.G, model->G, dd * dd);
+  st.in(&a.theta, theta, n * (t + 1) * dd);
+  st.out(&a.w, w, n * t * dd);
+  st.zeroed_out(&a.status, (int*)status, status ? n : 0);
+  if ((rc = st.commit())) return rc;
+  a.N = N; a.T = T; a.d = d;
+  e->variant = "dlmfsvsys-innovations";
+  HIP_TRY(e, dlm::launch_dlmfsvsys_innovations(a, e->stream));
+  return st.finish(opts->flags & DLM_OPT_ASYNC);
+}
+
 static int ar1_common(dlm_engine* e, int32_t N, int32_t T, const double* times, bool ou, const double* y, const double* v,
                       int64_t v_stride, const double* sv, int64_t sv_stride, const double* z, const dlm_options* opts,
                       double* filt, double* theta, int32_t* status);

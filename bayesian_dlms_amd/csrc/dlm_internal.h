@@ -479,6 +479,14 @@ struct DlmFsvImputeArgs {
   double* r_out;          // [N][T][p], may be r_in
   int* status;            // [N], nullable (zeroed by the caller)
 };
+struct DlmFsvSysInnovationsArgs {   // the factor process as the system noise (factorState, DlmFsvSystem.scala:109-117)
+  int N, T, d;
+  const double* theta;    // [N][T+1][d]
+  const double* G;        // [d*d] column-major
+  double* w;              // [N][T][d], not theta
+  int* status;            // [N], nullable (zeroed by the caller)
+};
+hipError_t launch_dlmfsvsys_innovations(const DlmFsvSysInnovationsArgs& a, hipStream_t s);
 hipError_t launch_dlmfsv_impute(const DlmFsvImputeArgs& a, hipStream_t s);
 hipError_t launch_dlmfsv_center(const DlmFsvCenterArgs& a, hipStream_t s);
 hipError_t launch_dlmfsv_variance(const DlmFsvVarianceArgs& a, hipStream_t s);

@@ -525,6 +525,25 @@ class Engine:
         self._check(self.lib.dlm_dlmfsv_variance_batch(self.h, N, T, p, k, be.ptr(bb), be.ptr(vb), be.ptr(ab), op, be.ptr(V), be.ptr(status)))
         return {"V": V, "status": status}
 
+    def dlmfsvsys_innovations(self, mat, theta, *, flags=0, out=None):
+        """The state's innovations (dlm_dlmfsvsys_innovations_batch; factorState, DlmFsvSystem.scala:109-117) for N panels:
+        w[t] = theta[t+1] - G theta[t], theta [N][T+1][d] as ffbs writes it, mat the materialised model (its one G; a table of G or an
+        irregular grid is refused by the call).  Returns {"w" [N][T][d], "status"}.  out: dict with an existing "w" buffer (not theta)."""
+        be = self._backend(theta)
+        N = int(theta.shape[0]); d, T = mat.d, mat.T
+        tb = be.put(theta)
+        if tuple(tb.shape) != (N, T + 1, d):
+            raise EngineError(f"theta must be [N][T+1][d] = {(N, T + 1, d)}, got {tuple(tb.shape)}")
+        Gb, gi, dt = be.put(mat.G), be.put(mat.g_index, np.int32), be.put(mat.dt)
+        addr = lambda a: None if a is None else be.ptr(a).value
+        md = _lib.ModelDesc(d, mat.p, T, N, None, 0, addr(Gb), mat.n_g, addr(gi), addr(dt))
+        w = _out_or_empty(be, out, "w", (N, T, d))
+        status = be.empty((N,), np.int32)
+        op = _lib.Options(flags, be.mem, 0, 0)
+        self._hold(flags, tb, Gb, gi, dt)
+        self._check(self.lib.dlm_dlmfsvsys_innovations_batch(self.h, md, be.ptr(tb), op, be.ptr(w), be.ptr(status)))
+        return {"w": w, "status": status}
+
     def simulate(self, mat, params, N, *, seed=0, series_offset=0, device=False, want_x=True):
         """Dlm.simulateRegular over the model's time grid for N series (dlm_simulate_batch): (x [N][T+1][d], y [N][T][p])."""
         be = _Device(self.device) if device else _Host()

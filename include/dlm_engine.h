@@ -489,6 +489,32 @@ int dlm_dlmfsv_impute_batch(dlm_engine* e, int32_t N, int32_t T, int32_t p, int3
 int dlm_dlmfsv_variance_batch(dlm_engine* e, int32_t N, int32_t T, int32_t p, int32_t k, const double* beta, const double* v,
                               const double* alpha, const dlm_options* opts, double* V, int32_t* status);
 
+/* The DLM whose SYSTEM noise is a factor stochastic-volatility process (DlmFsvSystem.scala:215-344) for N independent panels:
+ *   theta_0 ~ N(m0, C0),  theta_t = G theta_{t-1} + beta f_t + eps_t,  eps_t ~ N(0, diag(v)),  f_{j,t} ~ N(0, exp(alpha_{j,t}));
+ *   y_t = F_t^T theta_t + nu_t,  nu_t ~ N(0, V),  V diagonal   (beta d x k, v [d]: the factor part as above with p := d).
+ * The call here and dlm_dlmfsv_variance_batch join dlm_ffbs_batch to the factor sampler's calls; one iteration, everything device-resident:
+ *   1 dlm_dlmfsvsys_innovations_batch  w_t = theta_{t+1} - G theta_t                                 (factorState, DlmFsvSystem.scala:109-117)
+ *   2 dlm_fsv_factors_batch on w (p := d)  f | w, alpha, beta, v
+ *   3 dlm_sv_mixture_batch, dlm_ar1_ffbs_batch, dlm_sv_params_batch on f: alpha | f, then (phi, mu, sigma_eta) | alpha
+ *   4 dlm_fsv_loadings_batch on (w, f): sigma^2, beta
+ *   5 dlm_dlmfsv_variance_batch with p := d: W_t = beta diag(exp(alpha_{.,t+1})) beta^T + diag(v)   (calculateVariance, DlmFsvSystem.scala:126-131)
+ *   6 dlm_ffbs_batch, the reference-form sampler, with params->W = that stream, w_stride = T d d, w_tstride = d d, per-panel diagonal V
+ *     (v_stride = p p), statistics on: theta | y, W_{1:T}, V (f integrated out)
+ *   7 dlm_dinvgamma_step_batch on its statistics (V_out; W_out is not used): V | theta, y  (sampleObservationMatrix, DlmFsvSystem.scala:246)
+ * In this order step 6 followed by the next steps 1 and 2 is one joint draw of (theta, f).  DlmFsvSystem.sampleStep runs 1, 3, 2, 4, 5, 6,
+ * 7, whose step 3 conditions on the f drawn BEFORE theta was redrawn with f integrated out: not a valid sampler.
+ * w[t] belongs to alpha[..][t+1], as y[t] does in the calls above.  The innovations are never missing: nothing is completed here, and a
+ * missing y is the state draw's business alone.
+ *
+ * dlm_dlmfsvsys_innovations_batch.  model: d <= 64, T, N and ONE G (d x d column-major, n_g = 1); F, p and the time grid are not read.
+ * A g_index table or a dt array (an irregular grid) is DLM_ERR_UNSUPPORTED: the AR(1) volatility has no dt.  theta [N][T+1][d] as
+ * dlm_ffbs_batch writes it; w [N][T][d] gets w_ti = theta_{t+1,i} - sum_j G_ij theta_{t,j}, the sum taken with j ascending from 0.
+ * status [N] (nullable): DLM_ST_NONFINITE for a panel with a theta that is not finite (w is then what the arithmetic gives).  w must
+ * not alias theta.  Draws nothing; a panel's output depends on neither N nor its neighbours.  Limits: N, T >= 1, T d < 2^31 - 4096,
+ * N ceil(T d / 256) < 2^31 (DLM_ERR_ARG); d > 64 is DLM_ERR_UNSUPPORTED.  opts: mem, DLM_OPT_ASYNC. */
+int dlm_dlmfsvsys_innovations_batch(dlm_engine* e, const dlm_model_desc* model, const double* theta, const dlm_options* opts,
+                                    double* w, int32_t* status);
+
 /* Per-series log-likelihood by the prediction-error decomposition,
  *   loglik[n] = sum_t log N(y_t^obs ; f_t^obs, Q_t^obs),
  * i.e. KalmanFilter.conditionalLikelihood (KalmanFilter.scala:138-153) summed over the series (steps with no observed

@@ -352,6 +352,19 @@ JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_dlmFsvVariance(JN
   if (!read_opts(env, opts, o)) return;
   throw_if(env, eng(h), dlm_dlmfsv_variance_batch(eng(h), n, t, p, k, ptr<const double>(beta), ptr<const double>(v), ptr<const double>(alpha), &o, ptr<double>(vOut), ptr<int32_t>(status)));
 }
+// ---- the DLM with factor stochastic-volatility SYSTEM noise (DlmFsvSystem.scala:109-117): w = theta_{t+1} - G theta_t for the factor calls above (p := d); dlmFsvVariance then writes the W_t stream for
+// ffbs.  Reads d, T, N and G of the model (model[6] = G, model[7] = nG, model[8] = gIndex, model[9] = dt, as make_model lays them out; a gIndex or dt is refused); status = 0: none.
+JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_dlmFsvSysInnovations(JNIEnv* env, jobject, jlong h, jlongArray model, jlong theta, jlongArray opts, jlong w, jlong status) {
+  if (!model || env->GetArrayLength(model) != 10) { throw_arg(env, "model must be long[10] = {d, p, T, N, F, fStride, G, nG, gIndex, dt}"); return; }
+  jlong m[10];
+  env->GetLongArrayRegion(model, 0, 10, m);
+  dlm_model_desc md{};
+  md.d = static_cast<int32_t>(m[0]); md.p = static_cast<int32_t>(m[1]); md.T = static_cast<int32_t>(m[2]); md.N = static_cast<int32_t>(m[3]);
+  md.G = ptr<const double>(m[6]); md.n_g = static_cast<int32_t>(m[7]); md.g_index = ptr<const int32_t>(m[8]); md.dt = ptr<const double>(m[9]);
+  dlm_options o{};
+  if (!read_opts(env, opts, o)) return;
+  throw_if(env, eng(h), dlm_dlmfsvsys_innovations_batch(eng(h), &md, ptr<const double>(theta), &o, ptr<double>(w), ptr<int32_t>(status)));
+}
 // ---- pooled-parameter Gibbs: reduce over series, then over GPUs (RCCL) ---------------------------------------------------------------
 JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_statsPool(JNIEnv* env, jobject, jlong h, jlong stats, jint n, jint l, jlong pooled, jlongArray opts) {
   dlm_options o{};

@@ -82,6 +82,8 @@ final class Native private[gpu] () {
   @native def dlmFsvCenter(h: Long, model: Array[Long], y: Long, theta: Long, opts: Array[Long], r: Long, status: Long): Unit
   @native def dlmFsvImpute(h: Long, n: Int, t: Int, p: Int, k: Int, rIn: Long, beta: Long, v: Long, alpha: Long, iteration: Long, opts: Array[Long], rOut: Long, status: Long): Unit
   @native def dlmFsvVariance(h: Long, n: Int, t: Int, p: Int, k: Int, beta: Long, v: Long, alpha: Long, opts: Array[Long], vOut: Long, status: Long): Unit
+  /** the DLM with factor stochastic-volatility system noise (DlmFsvSystem.factorState): w [N][T][d] = theta_{t+1} - G theta_t for the factor calls above with p := d (the model's d, T, N and its one G are read; a gIndex or dt is refused); dlmFsvVariance with p := d then writes the W_t stream of ffbs */
+  @native def dlmFsvSysInnovations(h: Long, model: Array[Long], theta: Long, opts: Array[Long], w: Long, status: Long): Unit
   @native def statsPool(h: Long, stats: Long, n: Int, l: Int, pooled: Long, opts: Array[Long]): Unit
   @native def commUniqueId(): Array[Byte]
   @native def commInitRank(h: Long, nranks: Int, rank: Int, id: Array[Byte]): Unit
