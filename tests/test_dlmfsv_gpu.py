@@ -10,6 +10,8 @@ where exp does.
       |V - V*| <= 8 (k + 4) 2^-53 (sum_l |beta_il beta_jl| e_l + v_i [i == j])
 The completion of the partially missing times (k_dlmfsv_impute) solves a k x k system and draws: it is held draw for draw at the project's
 draw-for-draw tolerance (tests/test_factorsv_gpu.py: rtol 1e-11, the systems' condition numbers asserted below 1e3).
+Beyond that condition number, at k = 4..7 and at the layout edges that no shape here has, tests/test_fsv_dense_reference_gpu.py holds the
+three kernels to a 50-digit dense reference within bounds derived from the arithmetic.
 Then the symmetry of V bit for bit, the status bits, the argument errors, the sharding, the driver against its calls composed by
 hand in both orders, the exact-invariance check of tests/test_dlmfsv_host.py on the device and a run on simulated data."""
 import functools
@@ -21,6 +23,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dlmfsv_restatement as dr  # noqa: E402
+import fsv_dense_reference as dense  # noqa: E402
 import fsv_restatement as fr  # noqa: E402
 
 from bayesian_dlms_amd import _lib  # noqa: E402
@@ -195,6 +198,23 @@ def test_impute_bad_panels_halves_and_argument_errors(eng):
     ro = np.zeros((N, T, p))
     _raises(-1, lambda: eng._check(eng.lib.dlm_dlmfsv_impute_batch(eng.h, N, T, p, k, r.ctypes.data, x["beta"].ctypes.data, None, x["alpha"].ctypes.data, 0, op,
                                                                      ro.ctypes.data, None)))
+
+
+def test_impute_a_pivot_that_rounds_to_zero_gets_not_pd_and_its_time_copied(eng):
+    """The input of tests/test_factorsv_gpu.py's not-positive-definite test (fsv_dense_reference.not_pd_inputs), with the component that
+    carries the loading 1e8 observed at that time and the other one missing."""
+    x = dense.not_pd_inputs()
+    kw = dict(iteration=ITER, seed=SEED, series_offset=OFFSET)
+    t, r = x["t"], x["part"]
+    clean = eng.dlmfsv_impute(r, x["beta"], x["v"], x["clean"], **kw)
+    assert not clean["status"].any() and np.isfinite(clean["r"]).all()
+    out = eng.dlmfsv_impute(_dev(r), _dev(x["beta"]), _dev(x["v"]), _dev(x["alpha"]), **kw)
+    got, st = out["r"].cpu().numpy(), out["status"].cpu().numpy()
+    assert st.tolist() == [_lib.ST_NOT_PD, 0]
+    assert np.array_equal(got[0, t], r[0, t], equal_nan=True) and np.isnan(got[0, t, 0])          # that time copied through
+    assert np.array_equal(np.delete(got[0], t, axis=0), np.delete(clean["r"][0], t, axis=0)) and np.array_equal(got[1], clean["r"][1])
+    want, wst, _ = dr.impute(r, x["beta"], x["v"], x["alpha"], seed=SEED, series_offset=OFFSET, it=ITER)
+    assert wst.tolist() == st.tolist() and np.array_equal(np.isnan(want), np.isnan(got))
 
 
 def test_bad_panels_get_their_status_and_leave_their_neighbours_alone(eng):

@@ -5,6 +5,8 @@ The kernels are held draw for draw to their NumPy restatement (tests/fsv_restate
 (tests/test_stochvol_gpu.py): the arithmetic is restated operation for operation (the build contracts no a * b + c), so what remains
 is the last bits of log, cos and exp, carried through systems whose condition number the inputs keep below 1e3 (asserted).  Then the
 exact-invariance check on the device, the bad rows, the argument errors, the sharding and the driver.
+Beyond condition numbers of 1e3 and at k = 4..7, which no shape here reaches, tests/test_fsv_dense_reference_gpu.py holds both kernels to a
+50-digit dense reference within bounds derived from the arithmetic.
 
 The largest relative difference seen on an MI355X is in profiles/r15_notes.md."""
 import functools
@@ -15,6 +17,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fsv_dense_reference as dense  # noqa: E402
 import fsv_restatement as fr  # noqa: E402
 
 from bayesian_dlms_amd import _lib  # noqa: E402
@@ -194,6 +197,52 @@ def test_bad_rows_get_their_status_and_leave_their_neighbours_alone(eng):
     assert np.array_equal(lout["beta"][4], beta[4]) and np.array_equal(lout["v"][4], v[4])
     for n in (0, 2, 3, 5):
         assert np.array_equal(lout["beta"][n], lclean["beta"][n]) and np.array_equal(lout["v"][n], lclean["v"][n])
+
+
+def test_a_pivot_that_rounds_to_zero_gets_not_pd_at_its_time_alone(eng):
+    """k = p = 2, beta_10 = 1e8, v = 1, alpha_{1,t+1} = 700 at one time of panel 0: the second pivot of P_t rounds to zero (in 50 digits the
+    matrix is positive definite: tests/test_fsv_dense_reference_host.py)."""
+    x = dense.not_pd_inputs()
+    kw = dict(iteration=ITER, seed=SEED, series_offset=OFFSET)
+    t = x["t"]
+    clean = eng.fsv_factors(x["y"], x["beta"], x["v"], x["clean"], **kw)
+    assert not clean["status"].any() and np.isfinite(clean["f"]).all()
+    out = eng.fsv_factors(_dev(x["y"]), _dev(x["beta"]), _dev(x["v"]), _dev(x["alpha"]), **kw)
+    f, st = out["f"].cpu().numpy(), out["status"].cpu().numpy()
+    assert st.tolist() == [_lib.ST_NOT_PD, 0]
+    assert np.isnan(f[0, :, t]).all()
+    assert np.array_equal(np.delete(f[0], t, axis=1), np.delete(clean["f"][0], t, axis=1)) and np.array_equal(f[1], clean["f"][1])
+    want, wst, _ = fr.factors(x["y"], x["beta"], x["v"], x["alpha"], seed=SEED, series_offset=OFFSET, it=ITER)
+    assert wst.tolist() == st.tolist() and np.array_equal(np.isnan(want), np.isnan(f))
+
+
+def test_loadings_with_a_first_pivot_that_underflows_get_not_pd(eng):
+    """The status is reachable in the loadings step: literal mode (P = S_q / sigma^2 + I s^2, Q29) with a prior standard deviation whose
+    square underflows and ONE counted time whose first factor's square underflows too give P_00 = 0 for every row.  (With a tiny but
+    representable s^2 and an ordinary f_t the rank-one S makes the second pivot rounding noise around zero; its sign then depends on the last
+    bits of sigma^2, whose Gamma draw the device and the restatement do not share to the bit, so that variant is not asserted.)"""
+    N, T, p, k = 2, 4, 4, 3
+    rng = np.random.default_rng(43)
+    f, y = rng.standard_normal((N, k, T)), rng.standard_normal((N, T, p))
+    beta = np.zeros((N, p, k))
+    beta[:, fr.free_mask(p, k)] = rng.uniform(-0.8, 0.8, (N, int(fr.free_mask(p, k).sum())))
+    beta[:, np.arange(k), np.arange(k)] = 1.0
+    prior = fr.fsv_prior(1, beta=(0.3, 1e-170))
+    pr = fr.fsv_prior_tuple(prior)
+    kw = dict(iteration=ITER, seed=SEED, series_offset=OFFSET)
+    clean = eng.fsv_loadings(y, f, beta, pr, **kw)
+    assert not clean["status"].any() and np.isfinite(clean["beta"]).all()
+    yb, fb = y.copy(), f.copy()
+    yb[0, 1:] = np.nan
+    fb[0, 0, 0] = 1e-170
+    out = eng.fsv_loadings(_dev(yb), _dev(fb), _dev(beta), pr, **kw)
+    b, v, st = out["beta"].cpu().numpy(), out["v"].cpu().numpy(), out["status"].cpu().numpy()
+    assert st.tolist() == [_lib.ST_NOT_PD, 0]
+    assert np.array_equal(np.isnan(b[0]), fr.free_mask(p, k)) and np.isfinite(v).all()
+    assert np.array_equal(b[1], clean["beta"][1]) and np.array_equal(v[1], clean["v"][1])
+    wb, wv, wst, _ = fr.loadings(yb, fb, beta, None, prior, seed=SEED, series_offset=OFFSET, it=ITER)
+    assert wst.tolist() == st.tolist() and np.array_equal(np.isnan(wb), np.isnan(b))
+    np.testing.assert_allclose(v, wv, rtol=RTOL)
 
 
 def test_argument_errors(eng):
