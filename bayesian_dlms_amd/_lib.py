@@ -39,6 +39,9 @@ OPT_TEST_FAIL_AFTER_TABLES = 1 << 30
 TABLES_NONE, TABLES_BUILT, TABLES_REUSED, TABLES_SKIPPED = 0, 1, 2, 3   # dlm_last_table_reuse
 ST_NONFINITE, ST_NOT_PD, ST_NOCONV = 1, 2, 4
 COMM_ID_BYTES = 128
+# dlm_pf_desc.family: the observation models of the particle filter (Dglm.scala:46-175, package.scala:13-28)
+OBS_GAUSSIAN, OBS_POISSON, OBS_NEGBIN, OBS_ZIP, OBS_STUDENTT, OBS_BETA = range(6)
+PF_MAX_D, PF_MIN_PARTICLES, PF_MAX_PARTICLES = 16, 64, 1024
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int32)
@@ -92,6 +95,12 @@ class FsvPrior(ctypes.Structure):
                 ("sigma_shape", ctypes.c_double), ("sigma_scale", ctypes.c_double)]
 
 
+class PfDesc(ctypes.Structure):
+    """dlm_pf_desc: the observation family (OBS_*), the number of particles (a multiple of 64, 64..1024), n0 (resample when ESS < n0;
+    negative: floor(P / 5) as ParticleFilter.likelihood) and literal = 1: the reference's arithmetic (Q37-Q39)."""
+    _fields_ = [("family", ctypes.c_int32), ("n_particles", ctypes.c_int32), ("n0", ctypes.c_int32), ("literal", ctypes.c_int32)]
+
+
 class Options(ctypes.Structure):
     _fields_ = [("flags", ctypes.c_uint32), ("mem", ctypes.c_int32),
                 ("seed", ctypes.c_uint64), ("series_offset", ctypes.c_uint64)]
@@ -139,6 +148,7 @@ SYMBOLS = [
                                                _V, _V]),
     ("dlm_dlmfsv_variance_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, _OP, _V, _V]),
     ("dlm_dlmfsvsys_innovations_batch", ctypes.c_int, [_V, _MP, _V, _OP, _V, _V]),
+    ("dlm_pf_batch", ctypes.c_int, [_V, _MP, _PP, ctypes.POINTER(PfDesc), _V, _V, ctypes.c_uint64, _OP, _V, _V, _V, _V, _V, _V]),
     ("dlm_ou_ffbs_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, ctypes.c_int64, _V, ctypes.c_int64,
                                          _V, _OP, _V, _V, _V]),
     ("dlm_ar1_ffbs_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, ctypes.c_int64, _V, ctypes.c_int64,

@@ -23,6 +23,12 @@ constexpr unsigned DLM_KEY_SV = 0x5354564Fu;         // "STVO"
 constexpr unsigned DLM_KEY_SVOU = 0x53564F55u;       // "SVOU"
 constexpr unsigned DLM_KEY_FSV = 0x46535620u;        // "FSV "
 constexpr unsigned DLM_KEY_DLMFSV = 0x444C4653u;     // "DLFS"
+//   DLM_KEY_PF        dlm_pf_batch: comp = t for the step into observation t, DLM_PF_SLOT_INIT for the initial cloud; attempt = the particle
+//                     (i < 1024: the attempt field's ten bits), which = 0.  The low byte of the key is the BLOCK of that (slot, particle):
+//                     block q < 8 gives the Box-Muller pair (cosine, sine) = the normals of the state components (2 q, 2 q + 1), block
+//                     DLM_PF_BLOCK_RESAMPLE the [0, 1) uniform u_i of the resampling search of step t (pf_rand, dlm_pf.hip)
+constexpr unsigned DLM_KEY_PF = 0x50462000u;         // "PF " and the block in the low byte
+constexpr unsigned DLM_PF_BLOCK_RESAMPLE = 8u;
 
 // ---- the slots ------------------------------------------------------------------------------------------------------------------
 // comp is a 21-bit field (the counter word is comp * 2048 + attempt * 2 + which).  A sampler whose per-time draws take comp = t < T
@@ -57,10 +63,18 @@ enum : unsigned {   // dlm_fsv_loadings_batch, DLM_KEY_FSV (dlm_fsv_factors_batc
   DLM_FSV_SLOT_ROW0 = DLM_SLOT_TOP - 1,         // row i of beta takes the slot DLM_FSV_SLOT_ROW0 - i, attempt j the normal of its entry j
   DLM_FSV_SLOT_ROW_LAST = DLM_SLOT_TOP - 64,    // i <= 63 (p <= 64)
 };
+enum : unsigned {   // dlm_pf_batch, DLM_KEY_PF (the steps take the slots t)
+  DLM_PF_SLOT_INIT = DLM_SLOT_TOP,              // the initial cloud x_0,i = m0 + chol(C0) z
+};
 constexpr int DLM_ST_MAX_T = 0x1FFFFC;     // v_t takes slot t < T
 constexpr int DLM_SV_MAX_T = 0x1FFFF7;     // k_t takes slot t < T; 0x1FFFF8 and 0x1FFFF9 are kept free
 constexpr int DLM_SVOU_MAX_T = 0x1FFFF7;   // the chain's mixture call runs at the same T
 constexpr int DLM_FSV_MAX_T = 0x1FFFBF;    // the factors' normals take slot t < T
+constexpr int DLM_PF_MAX_T = 0x1FFFFE;     // the step into observation t takes slot t < T
+constexpr int DLM_PF_MAX_D = 16, DLM_PF_MAX_P = 1024;
+static_assert(DLM_PF_SLOT_INIT > (unsigned)DLM_PF_MAX_T - 1, "the particle filter's initial cloud lies above every time slot");
+static_assert(DLM_PF_MAX_P <= 1024 && (DLM_PF_MAX_D + 1) / 2 <= (int)DLM_PF_BLOCK_RESAMPLE && DLM_PF_BLOCK_RESAMPLE < 256u,
+              "a particle fits the attempt field and a block the key's low byte");
 static_assert(DLM_ST_SLOT_SCALE > (unsigned)DLM_ST_MAX_T - 1, "the Student-t step's scalar slots lie above every time slot");
 static_assert(DLM_SV_SLOT_ACCEPT > (unsigned)DLM_SV_MAX_T, "the SV step's scalar slots lie above every time slot");
 static_assert(DLM_SVOU_SLOT_ACC_MU > (unsigned)DLM_SVOU_MAX_T, "the OU step's scalar slots lie above every time slot");

@@ -491,6 +491,29 @@ hipError_t launch_dlmfsv_impute(const DlmFsvImputeArgs& a, hipStream_t s);
 hipError_t launch_dlmfsv_center(const DlmFsvCenterArgs& a, hipStream_t s);
 hipError_t launch_dlmfsv_variance(const DlmFsvVarianceArgs& a, hipStream_t s);
 
+// ---- bootstrap particle filter of a DGLM, one wavefront per series (ParticleFilter.scala:38-85, Dglm.scala:46-175), dlm_pf.hip -------------
+struct PfArgs {
+  int d, T, N, P;         // P particles, a multiple of 64
+  int family, n0, literal;   // DLM_OBS_*; resample when ESS < n0 (resolved: >= 0); 1: Q37-Q39
+  const double* F; long long f_stride;   // F_t = F + t * f_stride (d doubles, p = 1)
+  const double* G; int n_g; const int* g_index; const double* dt;
+  const double* V; long long v_stride;   // v = V[n * v_stride]
+  const double* W; long long w_stride;
+  const double* m0; long long m0_stride;
+  const double* C0; long long c0_stride;
+  const double* obs_param;   // [N], nullable: nu of DLM_OBS_STUDENTT
+  const double* y;        // [N][T], NaN = missing
+  DrawStream rs;
+  double* ll;             // [N]
+  double* mean;           // [N][T][d], nullable
+  double* ess;            // [N][T], nullable
+  double* cloud;          // [N][d][P], nullable
+  double* weights;        // [N][P], nullable
+  int* status;            // [N], nullable (zeroed by the caller)
+};
+size_t pf_lds_bytes(int d, int P);   // the cloud [d][P], the weights and their running sums [2][P], chol(W) and chol(C0)
+hipError_t launch_pf(const PfArgs& a, hipStream_t s);
+
 // ---- KalmanFilter.likelihood literally (transition density of the filtered means), dlm_loglik.hip ------
 size_t loglik_q7_ws_bytes(const KArgs& a);
 hipError_t launch_loglik_q7(const KArgs& a, const double* records, void* ws, hipStream_t s);   // a.loglik [N] <- records [N][T+1][d+dd]

@@ -1,0 +1,317 @@
+// Bootstrap particle filter of a dynamic generalised linear model (ParticleFilter.step / likelihood, ParticleFilter.scala:38-85; the observation
+// models of Dglm.scala:46-175 and package.scala:13-28): dlm_pf_batch.  ONE WAVEFRONT PER SERIES.  Particle i = 64 s + lane sits in slot s of
+// its lane, S = P / 64 slots.  The cloud lives in LDS, component-major x[k][i] -- a lane's accesses are 64 consecutive doubles per slot, free of
+// bank conflicts -- next to the weights wg[i], one more row `cum` (the log-weights of a step, then the running sums of the resampling search,
+// then the row a component is gathered through), the ancestors and ONE d x d factor (chol(C0) for the initial cloud, chol(W) from then on).
+// A particle's state is in registers only while it is advanced: the template argument D makes those arrays registers.
+//
+// Every reduction runs in a FIXED order (tests/pf_restatement.py follows them operation for operation):
+//   max, sum of omega, sum of W^2, weighted means   per lane over its slots s = 0 .. S - 1 in order, then across the lanes: wave_max (a maximum
+//                                                   has no order) or the xor butterfly wave_sum (partners 32, 16, 8, 4, 2, 1);
+//   inclusive running sums of the weights           per slot the Hillis-Steele scan over the lanes (offsets 1, 2, 4, 8, 16, 32: v = v + v[lane - off]),
+//                                                   plus the carry = the running sum at the previous slot's lane 63 (carry + v);
+//   matrix-vector products                          index ascending from 0, the first product starts the sum.
+// No atomics, no dependence on N or on the neighbours.
+#include "dlm_wave.h"
+#include "dlm_draws.h"
+
+namespace dlm {
+namespace {
+
+constexpr double PF_PI = 3.14159265358979323846, PF_2PI = 6.283185307179586476925286766559;
+
+// ocml's lgamma, ONE copy of it: inlined at its nine call sites, its constants are hoisted out of the loops over t and take more registers
+// than the wave has
+__device__ __noinline__ double pf_lgamma(double v) { return lgamma(v); }
+
+// the two uniforms of block `block` of (slot, particle): u1 in (0, 1], u2 in [0, 1)
+__device__ __forceinline__ void pf_rand(const DrawStream& rs, unsigned long long series, unsigned slot, unsigned particle, unsigned block,
+                                        double& u1, double& u2) {
+  gibbs_rand(rs.seed, series, rs.iteration, slot, particle, 0u, u1, u2, DLM_KEY_PF | block);
+}
+
+// z ~ N(0, I_D) of (slot, particle): block q gives the components 2 q (cosine) and 2 q + 1 (sine)
+template <int D>
+__device__ __forceinline__ void pf_normals(const DrawStream& rs, unsigned long long series, unsigned slot, unsigned particle, double (&z)[D]) {
+#pragma unroll
+  for (int q = 0; q < (D + 1) / 2; ++q) {
+    double u1, u2;
+    pf_rand(rs, series, slot, particle, (unsigned)q, u1, u2);
+    const double r = sqrt(-2.0 * log(u1)), ang = PF_2PI * u2;
+    z[2 * q] = r * cos(ang);
+    if (2 * q + 1 < D) z[2 * q + 1] = r * sin(ang);
+  }
+}
+
+// Lower Cholesky factor of the column-major A (its lower triangle is read) into sl, row-major; lane 0 computes, every lane gets the verdict.
+// false: a pivot that is not positive (NaN included)
+template <int D>
+__device__ __forceinline__ bool pf_chol(const double* A, double* sl, int lane) {
+  int ok = 1;
+  if (lane == 0) {
+    for (int j = 0; j < D && ok; ++j) {
+      double s = A[j + j * D];
+      for (int k = 0; k < j; ++k) s -= sl[j * D + k] * sl[j * D + k];
+      if (!(s > 0.0)) { ok = 0; break; }
+      const double dj = sqrt(s);
+      sl[j * D + j] = dj;
+      for (int c = j + 1; c < D; ++c) sl[j * D + c] = 0.0;   // the products run over whole rows: a zero adds nothing
+      for (int i = j + 1; i < D; ++i) {
+        double t = A[i + j * D];
+        for (int k = 0; k < j; ++k) t -= sl[i * D + k] * sl[j * D + k];
+        sl[i * D + j] = t / dj;
+      }
+    }
+  }
+  wave_sync();
+  return __shfl(ok, 0, 64) != 0;
+}
+
+// what a step's log-density needs beyond (eta, the particle): made once per step, the same in every lane
+struct PfObs { double y, v, nu, c0, c1, c2; };
+
+__device__ __forceinline__ PfObs pf_obs(int family, int literal, double y, double v, double nu) {
+  PfObs o{y, v, nu, 0.0, 0.0, 0.0};
+  switch (family) {
+    case DLM_OBS_GAUSSIAN: o.c0 = 0.5 * log(PF_2PI * v); break;
+    case DLM_OBS_POISSON: o.y = trunc(y); o.c0 = pf_lgamma(o.y + 1.0); break;
+    case DLM_OBS_NEGBIN: o.c1 = exp(v); o.c0 = (pf_lgamma(o.c1 + y) - pf_lgamma(y + 1.0)) - pf_lgamma(o.c1); break;
+    case DLM_OBS_ZIP: { const double ev = exp(v); o.c1 = ev / (1.0 + ev); o.c2 = log(1.0 + ev); o.c0 = pf_lgamma(y + 1.0); break; }
+    case DLM_OBS_STUDENTT: {
+      const double sc = sqrt(v);
+      o.c1 = nu * sc * sc;
+      o.c0 = (pf_lgamma((nu + 1.0) * 0.5) - 0.5 * log(literal ? PF_PI * nu * sc : PF_PI * nu * sc * sc)) - pf_lgamma(nu * 0.5);   // Q39
+      break;
+    }
+    default: o.c1 = log(y); o.c2 = log(1.0 - y); break;   // DLM_OBS_BETA
+  }
+  return o;
+}
+
+// log p(y | eta, v) of the family, as the reference writes it
+__device__ __forceinline__ double pf_logdens(int family, const PfObs& o, double eta) {
+  switch (family) {
+    case DLM_OBS_GAUSSIAN: { const double e = o.y - eta; return -o.c0 - (0.5 * (e * e)) / o.v; }
+    case DLM_OBS_POISSON: return (o.y * eta - exp(eta)) - o.c0;
+    case DLM_OBS_NEGBIN: {
+      const double mu = exp(eta), size = o.c1;
+      return (o.c0 + size * log(size / (mu + size))) + o.y * log(mu / (mu + size));
+    }
+    case DLM_OBS_ZIP:
+      if (fabs(o.y) < 1e-5) return log(o.c1 + (1.0 - o.c1) * exp(-exp(eta)));
+      return ((o.y * eta - o.c2) - exp(eta)) - o.c0;
+    case DLM_OBS_STUDENTT: { const double e = o.y - eta; return o.c0 - ((o.nu + 1.0) * 0.5) * log1p((e * e) / o.c1); }
+    default: {   // DLM_OBS_BETA: logisticFunction(1.0) with its clamp, then Dglm.beta's (mean, variance) -> (alpha, beta)
+      const double mean = eta < -5.0 ? 0.0 : (eta > 5.0 ? 1.0 : 1.0 / (1.0 + exp(-eta)));
+      const double aa = (mean * (1.0 - mean)) / o.v;
+      const double al = mean * (aa - 1.0), be = (1.0 - mean) * (aa - 1.0);
+      if (!(al > 0.0 && be > 0.0)) return -__builtin_inf();   // Q41
+      return ((al - 1.0) * o.c1 + (be - 1.0) * o.c2) - ((pf_lgamma(al) + pf_lgamma(be)) - pf_lgamma(al + be));
+    }
+  }
+}
+
+// sum_i W_i x_k,i for every component, lane 0 stores them
+template <int D>
+__device__ __forceinline__ void pf_means(const double* x, const double* wg, int P, int lane, double* out) {
+  double acc[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) acc[k] = 0.0;
+  for (int i = lane; i < P; i += 64) {
+    const double w = wg[i];
+#pragma unroll
+    for (int k = 0; k < D; ++k) acc[k] = acc[k] + w * x[k * P + i];
+  }
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    const double m = wave_sum(acc[k]);
+    if (lane == 0) out[k] = m;
+  }
+}
+
+template <int D>
+__global__ __launch_bounds__(64, D <= 8 ? 2 : 1) void k_pf(PfArgs a) {
+  extern __shared__ double pf_lds[];
+  const int n = blockIdx.x, lane = threadIdx.x, P = a.P, T = a.T;
+  double* x = pf_lds;              // [D][P]
+  double* wg = x + (size_t)D * P;  // [P] the normalised weights W_t,i
+  double* cum = wg + P;            // [P]
+  double* sl = cum + P;            // [D][D] row-major
+  int* anc = (int*)(sl + D * D);   // [P]
+  const unsigned long long series = a.rs.series_offset + (unsigned long long)n;
+  const double rP = 1.0 / (double)P, nan = __builtin_nan("");
+  const double* y = a.y + (size_t)n * T;
+  double* mean = a.mean ? a.mean + (size_t)n * T * D : nullptr;
+  double* ess = a.ess ? a.ess + (size_t)n * T : nullptr;
+
+  int bad = 0, t_bad = 0;   // status bits of the series; the first step without results
+  double ll = 0.0;
+
+  // ---- the initial cloud x_0,i = m0 + chol(C0) z, then chol(W) for the steps
+  if (!pf_chol<D>(a.C0 + (size_t)n * a.c0_stride, sl, lane)) bad = DLM_ST_NOT_PD;
+  if (!bad) {
+    const double* m0 = a.m0 + (size_t)n * a.m0_stride;
+    for (int i = lane; i < P; i += 64) {
+      double z[D];
+      pf_normals<D>(a.rs, series, DLM_PF_SLOT_INIT, (unsigned)i, z);
+#pragma nounroll
+      for (int r = 0; r < D; ++r) {   // (a loop over r in the code: unrolled, the compiler holds every factor of every row in registers across the particles)
+        double acc = sl[r * D] * z[0];
+#pragma unroll
+        for (int c = 1; c < D; ++c) acc = acc + sl[r * D + c] * z[c];
+        x[r * P + i] = m0[r] + acc;
+      }
+      wg[i] = rP;
+    }
+    wave_sync();
+    if (!pf_chol<D>(a.W + (size_t)n * a.w_stride, sl, lane)) bad = DLM_ST_NOT_PD;
+  }
+
+  if (!bad) {
+    const double v = a.V[(size_t)n * a.v_stride], nu = a.obs_param ? a.obs_param[n] : 0.0;
+    double dt_held = 0.0;      // Q38, literal with one G: the intervals of the missing steps since the last observation
+    double ess_last = (double)P;
+    for (int t = 0; t < T; ++t) {
+      const double yt = y[t];
+      const bool missing = yt != yt;
+      const double dte = (a.dt ? a.dt[t] : 1.0) + dt_held;
+      dt_held = (missing && a.literal && a.n_g == 1) ? dte : 0.0;
+
+      // -- advance: x <- G x + sqrt(dt) L z (dt == 0: no advance, no noise)
+      if (dte != 0.0) {
+        const double* G = a.G + (size_t)(a.g_index ? a.g_index[t] : 0) * (D * D);
+        const double sdt = sqrt(dte);
+        for (int i = lane; i < P; i += 64) {
+          double z[D], xo[D];
+          pf_normals<D>(a.rs, series, (unsigned)t, (unsigned)i, z);
+#pragma unroll
+          for (int c = 0; c < D; ++c) xo[c] = x[c * P + i];
+#pragma nounroll
+          for (int r = 0; r < D; ++r) {
+            double gx = G[r] * xo[0];
+#pragma unroll
+            for (int c = 1; c < D; ++c) gx = gx + G[r + c * D] * xo[c];
+            double lz = sl[r * D] * z[0];
+#pragma unroll
+            for (int c = 1; c < D; ++c) lz = lz + sl[r * D + c] * z[c];
+            x[r * P + i] = gx + sdt * lz;
+          }
+        }
+      }
+
+      if (missing) {
+        if (mean) pf_means<D>(x, wg, P, lane, mean + (size_t)t * D);
+        if (ess && lane == 0) ess[t] = ess_last;
+        continue;
+      }
+
+      // -- log-weights, their maximum
+      const PfObs ob = pf_obs(a.family, a.literal, yt, v, nu);
+      const double* F = a.F + (size_t)t * a.f_stride;
+      double mx = -__builtin_inf();
+      for (int i = lane; i < P; i += 64) {
+        double eta = F[0] * x[i];
+#pragma unroll
+        for (int k = 1; k < D; ++k) eta = eta + F[k] * x[k * P + i];
+        const double l = pf_logdens(a.family, ob, eta);
+        cum[i] = l;
+        mx = fmax(mx, l);
+      }
+      const double m = wave_max(mx);
+      if (!(fabs(m) < __builtin_inf())) { bad = DLM_ST_NONFINITE; t_bad = t; break; }
+
+      // -- omega_i = W_{t-1,i} exp(l_i - m), their sum
+      double part = 0.0;
+      for (int i = lane; i < P; i += 64) {
+        const double om = (a.literal ? rP : wg[i]) * exp(cum[i] - m);   // Q37: the literal filter forgets the weights it did not resample
+        wg[i] = om;
+        part = part + om;
+      }
+      const double stot = wave_sum(part);
+      if (!(stot > 0.0 && stot < __builtin_inf())) { bad = DLM_ST_NONFINITE; t_bad = t; break; }
+      ll = ll + (m + log(stot));
+
+      // -- W_t,i = omega_i / s, sum W^2, the filtering mean
+      part = 0.0;
+      for (int i = lane; i < P; i += 64) {
+        const double w = wg[i] / stot;
+        wg[i] = w;
+        part = part + w * w;
+      }
+      const double sq = wave_sum(part);
+      if (mean) pf_means<D>(x, wg, P, lane, mean + (size_t)t * D);
+      ess_last = floor(1.0 / sq);
+      if (ess && lane == 0) ess[t] = ess_last;
+      if (!(ess_last < (double)a.n0)) continue;
+
+      // -- multinomial resampling: the running sums, the searches, the gather component by component
+      double carry = 0.0;
+      for (int i = lane; i < P; i += 64) {
+        double s = wg[i];
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+          const double up = __shfl_up(s, off, 64);
+          if (lane >= off) s = s + up;
+        }
+        s = carry + s;
+        cum[i] = s;
+        carry = __shfl(s, 63, 64);
+      }
+      const double total = carry;
+      wave_sync();
+      for (int i = lane; i < P; i += 64) {
+        double u1, u2;
+        pf_rand(a.rs, series, (unsigned)t, (unsigned)i, DLM_PF_BLOCK_RESAMPLE, u1, u2);
+        const double target = u2 * total;
+        int lo = 0, hi = P - 1;   // the first j with cum[j] > target; P - 1 when none is (u2 total rounding up to the total)
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (cum[mid] > target) hi = mid; else lo = mid + 1;
+        }
+        anc[i] = lo;
+      }
+      wave_sync();
+      for (int k = 0; k < D; ++k) {
+        for (int i = lane; i < P; i += 64) cum[i] = x[k * P + anc[i]];
+        wave_sync();
+        for (int i = lane; i < P; i += 64) x[k * P + i] = cum[i];
+        wave_sync();
+      }
+      for (int i = lane; i < P; i += 64) wg[i] = rP;
+      wave_sync();
+    }
+  }
+
+  // ---- results
+  if (bad) {
+    ll = -__builtin_inf();
+    if (mean) for (int j = t_bad * D + lane; j < T * D; j += 64) mean[j] = nan;
+    if (ess) for (int j = t_bad + lane; j < T; j += 64) ess[j] = nan;
+  }
+  if (lane == 0) {
+    a.ll[n] = ll;
+    if (a.status && bad) a.status[n] = bad;
+  }
+  const bool no_cloud = (bad & DLM_ST_NOT_PD) != 0;
+  if (a.cloud) {
+    double* c = a.cloud + (size_t)n * D * P;
+    for (int k = 0; k < D; ++k)
+      for (int i = lane; i < P; i += 64) c[(size_t)k * P + i] = no_cloud ? nan : x[k * P + i];
+  }
+  if (a.weights) {
+    double* w = a.weights + (size_t)n * P;
+    for (int i = lane; i < P; i += 64) w[i] = bad ? nan : wg[i];
+  }
+}
+
+}  // namespace
+
+size_t pf_lds_bytes(int d, int P) { return ((size_t)(d + 2) * P + (size_t)d * d) * sizeof(double) + (size_t)P * sizeof(int); }
+
+hipError_t launch_pf(const PfArgs& a, hipStream_t s) {
+  return pick<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>(a.d, [&](auto D) {
+    return launch(k_pf<decltype(D)::value>, dim3((unsigned)a.N), dim3(64), pf_lds_bytes(a.d, a.P), s, a);
+  });
+}
+
+}  // namespace dlm

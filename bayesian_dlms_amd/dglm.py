@@ -1,0 +1,305 @@
+"""Dynamic generalised linear models, the bootstrap particle filter and the particle-marginal Metropolis sampler built on it
+(the reference's Dglm.scala, ParticleFilter.scala and Metropolis.dglm, MetropolisHastings.scala:142-154).
+
+A `Dglm` is a `Dlm` with one of six observation models for its scalar observation; V(0, 0) = v is what each family makes of it
+(include/dlm_engine.h, dlm_pf_batch).  `ParticleFilter(n, n0).filter` runs the engine's filter for one series or a batch of them, with one
+parameter set or one per series; `Metropolis.dglm` is a generator of particle-marginal Metropolis states, one chain per series, one engine
+call per iteration, the proposal and the accept draws on the host.
+
+The initial cloud sits AT the first observation time (ParticleFilter.initialiseState, ParticleFilter.scala:63-70: time = the smallest
+observation time), so the first increment is 0 and the first step weights the initial cloud without advancing it -- the descriptor's dt == 0
+convention (the reference multiplies by g(0) and draws with covariance 0 there: DESIGN.md 2, Q40)."""
+from __future__ import annotations
+
+from dataclasses import dataclass, replace
+from typing import Callable, Optional
+
+import numpy as np
+
+from . import _lib
+from .api import pack_observations
+from .dlm import Dlm, DlmParameters, MaterialisedModel, materialise
+from .engine import EngineError, check_pf_shape
+
+
+def logistic_function(upper: float, number):
+    """Dglm.logisticFunction (Dglm.scala:33-41): 0 below -5, `upper` above 5."""
+    x = np.asarray(number, dtype=np.float64)
+    with np.errstate(over="ignore"):
+        mid = upper / (1.0 + np.exp(-x))
+    return np.where(x < -5.0, 0.0, np.where(x > 5.0, upper, mid))
+
+
+@dataclass(frozen=True)
+class Dglm:
+    """Dglm(observation, f, g, link, conditionalLikelihood) (Dglm.scala:14-23) with the observation model named instead of passed as
+    closures: `family` one of _lib.OBS_*, `nu` the degrees of freedom of the Student-t family."""
+
+    f: Callable[[float], np.ndarray]
+    g: Callable[[float], np.ndarray]
+    family: int = _lib.OBS_GAUSSIAN
+    nu: Optional[float] = None
+
+    @staticmethod
+    def gaussian(mod: Dlm) -> "Dglm":
+        """dlm2dglm (package.scala:13-28): y ~ N(eta, v)."""
+        return Dglm(mod.f, mod.g, _lib.OBS_GAUSSIAN)
+
+    @staticmethod
+    def poisson(mod: Dlm) -> "Dglm":
+        """Dglm.poisson (Dglm.scala:166-175): y ~ Poisson(exp(eta))."""
+        return Dglm(mod.f, mod.g, _lib.OBS_POISSON)
+
+    @staticmethod
+    def negative_binomial(mod: Dlm) -> "Dglm":
+        """Dglm.negativeBinomial (Dglm.scala:100-124): mean exp(eta), size exp(v)."""
+        return Dglm(mod.f, mod.g, _lib.OBS_NEGBIN)
+
+    @staticmethod
+    def zip(mod: Dlm) -> "Dglm":
+        """Dglm.zip (Dglm.scala:70-95): a zero with probability expit(v), else Poisson(exp(eta))."""
+        return Dglm(mod.f, mod.g, _lib.OBS_ZIP)
+
+    @staticmethod
+    def student_t(nu: float, mod: Dlm) -> "Dglm":
+        """Dglm.studentT (Dglm.scala:46-57): location eta, scale sqrt(v), nu degrees of freedom."""
+        if not nu > 0:
+            raise ValueError(f"the degrees of freedom must be positive, got {nu}")
+        return Dglm(mod.f, mod.g, _lib.OBS_STUDENTT, float(nu))
+
+    @staticmethod
+    def beta(mod: Dlm) -> "Dglm":
+        """Dglm.beta (Dglm.scala:132-161): mean logisticFunction(1)(eta), variance v < mean (1 - mean)."""
+        return Dglm(mod.f, mod.g, _lib.OBS_BETA)
+
+    @property
+    def dlm(self) -> Dlm:
+        return Dlm(self.f, self.g)
+
+    def link(self, eta):
+        """The mean function the reference calls `link`: eta for the Gaussian and Student-t families, exp(eta) for the counts, the logistic
+        function for Beta."""
+        eta = np.asarray(eta, dtype=np.float64)
+        if self.family in (_lib.OBS_GAUSSIAN, _lib.OBS_STUDENTT):
+            return eta
+        if self.family == _lib.OBS_BETA:
+            return logistic_function(1.0, eta)
+        return np.exp(eta)
+
+    def observation(self, eta: float, v: float, rng: np.random.Generator) -> float:
+        """One draw of y | eta, v (the `observation` closures of Dglm.scala)."""
+        fam = self.family
+        if fam == _lib.OBS_GAUSSIAN:
+            return float(rng.normal(eta, np.sqrt(v)))
+        if fam == _lib.OBS_POISSON:
+            return float(rng.poisson(np.exp(eta)))
+        if fam == _lib.OBS_NEGBIN:
+            size, mu = np.exp(v), np.exp(eta)
+            prob = mu / (size + mu)
+            return float(rng.poisson(rng.gamma(size, prob / (1.0 - prob))))
+        if fam == _lib.OBS_ZIP:
+            p = np.exp(v) / (1.0 + np.exp(v))
+            u, nonzero = rng.uniform(), rng.poisson(np.exp(eta))
+            return 0.0 if u < p else float(nonzero)
+        if fam == _lib.OBS_STUDENTT:
+            return float(eta + np.sqrt(v) * rng.standard_t(self.nu))
+        mean = float(logistic_function(1.0, eta))
+        a = mean * (1.0 - mean) / v
+        return float(rng.beta(mean * (a - 1.0), (1.0 - mean) * (a - 1.0)))
+
+    def simulate_regular(self, params: DlmParameters, n_steps: int, dt: float = 1.0, *, rng=None):
+        """Dglm.simulateRegular (Dglm.scala:224-232) on the host: x_0 ~ N(m0, C0) at time 0, then n_steps steps of length dt.  Returns
+        (times [n], y [n], x [n][d]).  (F is taken at the observation's time; the reference's `observation` evaluates f(1.0).)"""
+        rng = np.random.default_rng() if rng is None else rng
+        x = rng.multivariate_normal(params.m0, params.c0)
+        times = dt * np.arange(1, n_steps + 1, dtype=np.float64)
+        ys, xs = np.empty(n_steps), np.empty((n_steps, x.size))
+        g = np.atleast_2d(self.g(dt))
+        for k, t in enumerate(times):
+            x = g @ x + rng.multivariate_normal(np.zeros(x.size), params.w * dt)
+            eta = float(np.atleast_2d(self.f(float(t)))[:, 0] @ x)
+            ys[k] = self.observation(eta, float(params.v[0, 0]), rng)
+            xs[k] = x
+        return times, ys, xs
+
+
+def materialise_pf(mod, times) -> MaterialisedModel:
+    """The model's tables on the observation times with the initial state AT the first of them: dt_0 = 0 (no advance, its G is not read)."""
+    times = np.asarray(times, dtype=np.float64).reshape(-1)
+    mat = materialise(Dlm(mod.f, mod.g), times)
+    if times.size == 1:
+        return replace(mat, G=mat.G[:mat.d * mat.d], n_g=1, g_index=None, dt=np.zeros(1))
+    dts = np.concatenate([[0.0], np.diff(times)])
+    uniq = np.unique(dts[1:])
+    table, remap = [], []
+    for u in uniq:
+        gm = np.ascontiguousarray(np.atleast_2d(mod.g(float(u))).T).reshape(-1)
+        for k, have in enumerate(table):
+            if np.array_equal(have, gm):
+                remap.append(k)
+                break
+        else:
+            remap.append(len(table)); table.append(gm)
+    gi = np.concatenate([[0], np.asarray(remap, dtype=np.int32)[np.searchsorted(uniq, dts[1:])]]).astype(np.int32)
+    return replace(mat, G=np.concatenate(table), n_g=len(table), g_index=None if len(table) == 1 else gi, dt=dts)
+
+
+@dataclass
+class BatchedParameters:
+    """DlmParameters of N chains side by side: v [N][1][1], w [N][d][d], m0 [N][d], c0 [N][d][d]."""
+
+    v: np.ndarray
+    w: np.ndarray
+    m0: np.ndarray
+    c0: np.ndarray
+
+    @staticmethod
+    def of(p, n: Optional[int] = None) -> "BatchedParameters":
+        if isinstance(p, BatchedParameters):
+            return p
+        plist = [p] * (n or 1) if isinstance(p, DlmParameters) else list(p)
+        if n is not None and len(plist) != n:
+            raise ValueError(f"need {n} DlmParameters, got {len(plist)}")
+        return BatchedParameters(np.stack([q.v for q in plist]), np.stack([q.w for q in plist]), np.stack([q.m0 for q in plist]),
+                                 np.stack([q.c0 for q in plist]))
+
+    @property
+    def n(self) -> int:
+        return int(self.m0.shape[0])
+
+    def copy(self) -> "BatchedParameters":
+        return BatchedParameters(self.v.copy(), self.w.copy(), self.m0.copy(), self.c0.copy())
+
+    def where(self, take, other: "BatchedParameters") -> "BatchedParameters":
+        """Chain by chain: `other` where take, self elsewhere."""
+        t = np.asarray(take, dtype=bool)
+        return BatchedParameters(np.where(t[:, None, None], other.v, self.v), np.where(t[:, None, None], other.w, self.w),
+                                 np.where(t[:, None], other.m0, self.m0), np.where(t[:, None, None], other.c0, self.c0))
+
+    def packed(self):
+        """The tuple Engine.prepare takes: flat column-major arrays and their strides in doubles."""
+        N, d = self.m0.shape
+        cm = lambda a: np.ascontiguousarray(np.transpose(a, (0, 2, 1))).reshape(-1)
+        return (cm(self.v), int(self.v.shape[1] * self.v.shape[2]), cm(self.w), d * d, np.ascontiguousarray(self.m0).reshape(-1), d,
+                cm(self.c0), d * d, 0, 0)
+
+    def __getitem__(self, n: int) -> DlmParameters:
+        return DlmParameters(self.v[n], self.w[n], self.m0[n], self.c0[n])
+
+
+def _observations(ys):
+    """Vector[Data], a batch of them, or (times [T], y [T] or [N][T]) -> (times, y [N][T])."""
+    if isinstance(ys, tuple) and len(ys) == 2 and not hasattr(ys[0], "time"):
+        times, y = np.asarray(ys[0], dtype=np.float64), np.asarray(ys[1], dtype=np.float64)
+        y = y[None, :] if y.ndim == 1 else y
+        if y.ndim == 3 and y.shape[2] != 1:
+            raise EngineError(f"the particle filter takes a univariate observation (p = 1), got p = {y.shape[2]}")
+        return times, y.reshape(y.shape[0], -1)
+    times, y, _ = pack_observations(ys)
+    if y.shape[2] != 1:
+        raise EngineError(f"the particle filter takes a univariate observation (p = 1), got p = {y.shape[2]}")
+    return times, y[:, :, 0]
+
+
+class ParticleFilter:
+    """ParticleFilter(n, n0, multinomialResample) (ParticleFilter.scala:26-71) on the engine: n particles, resampling when ESS < n0
+    (negative: floor(n / 5), what ParticleFilter.likelihood passes)."""
+
+    def __init__(self, n: int, n0: int = -1):
+        check_pf_shape(1, 1, int(n))
+        self.n, self.n0 = int(n), int(n0)
+
+    def filter(self, mod: Dglm, ys, p, eng, *, seed: int = 0, iteration: int = 0, series_offset: int = 0, literal: bool = False):
+        """ys: Vector[Data], a batch of them on one time grid, or (times, y).  p: one DlmParameters, one per series, or a
+        BatchedParameters; with ONE series and several parameter sets every set filters that series (a bank of parameters, as the
+        particle-marginal sampler needs).  Returns {"ll" [N], "mean" [N][T][d], "ess" [N][T], "cloud" [N][d][n], "weights" [N][n],
+        "status" [N]} as NumPy arrays."""
+        times, y = _observations(ys)
+        f0 = np.atleast_2d(np.asarray(mod.f(float(times[0])), dtype=np.float64))
+        check_pf_shape(f0.shape[0], f0.shape[1], self.n)
+        mat = materialise_pf(mod, times)
+        if isinstance(p, DlmParameters):
+            N, params = y.shape[0], p
+        else:
+            bp = BatchedParameters.of(p)
+            N, params = bp.n, bp.packed()
+            if y.shape[0] == 1 and N > 1:
+                y = np.repeat(y, N, axis=0)
+            if y.shape[0] != N:
+                raise EngineError(f"{N} parameter sets for {y.shape[0]} series")
+        out = eng.particle_filter(mat, params, y, family=mod.family, n_particles=self.n, n0=self.n0, literal=literal, obs_param=mod.nu,
+                                  iteration=iteration, seed=seed, series_offset=series_offset)
+        return {k: None if v is None else np.asarray(v) for k, v in out.items()}
+
+    @staticmethod
+    def likelihood(mod: Dglm, ys, n: int, p, eng, **kw):
+        """ParticleFilter.likelihood(mod, ys, n)(p) (ParticleFilter.scala:78-85): the log-likelihood estimate(s) with n0 = floor(n / 5)."""
+        return ParticleFilter(n, -1).filter(mod, ys, p, eng, **kw)["ll"]
+
+
+INIT_ITERATION = 0xFFFFFFFF   # the Philox iteration of Metropolis.dglm's evaluation of the initial parameters
+
+
+@dataclass
+class MetropolisState:
+    """Metropolis.State(parameters, ll, accepted) (MetropolisHastings.scala) for N chains: ll is log-likelihood estimate + log prior."""
+
+    parameters: BatchedParameters
+    ll: np.ndarray
+    accepted: np.ndarray
+
+
+class Metropolis:
+    @staticmethod
+    def symmetric_proposal(delta: float):
+        """Metropolis.symmetricProposal (MetropolisHastings.scala:57-74): the diagonals of v, w and c0 move on the log scale, diag * exp(sqrt(delta) z),
+        and come back as DIAGONAL matrices; m0 moves additively, m0 + delta z.  Returns proposal(parameters, rng) -> parameters; the normals
+        are drawn in the order v, w, m0, c0, each [N][k] in one call."""
+        if not delta > 0:
+            raise ValueError(f"delta must be positive, got {delta}")
+        sd = float(np.sqrt(delta))
+
+        def diagonal(m, rng):
+            dg = np.diagonal(m, axis1=1, axis2=2)
+            new = dg * np.exp(sd * rng.standard_normal(dg.shape))
+            out = np.zeros_like(m)
+            idx = np.arange(m.shape[1])
+            out[:, idx, idx] = new
+            return out
+
+        def proposal(p: BatchedParameters, rng: np.random.Generator) -> BatchedParameters:
+            v = diagonal(p.v, rng)
+            w = diagonal(p.w, rng)
+            m0 = p.m0 + delta * rng.standard_normal(p.m0.shape)
+            c0 = diagonal(p.c0, rng)
+            return BatchedParameters(v, w, m0, c0)
+        return proposal
+
+    @staticmethod
+    def dglm(mod: Dglm, ys, proposal, prior, init_p, n: int, eng, n_iter: int, seed: int = 0, *, n_chains: Optional[int] = None,
+             literal: bool = False, evaluate_init: bool = False):
+        """Metropolis.dglm (MetropolisHastings.scala:142-154): particle-marginal Metropolis, one chain per series.  ys: one series (every
+        chain targets its posterior) or one per chain.  proposal(parameters, rng) -> parameters (symmetric: no Hastings term, as mStep);
+        prior(parameters) -> [N] log densities; init_p one DlmParameters (with n_chains), a sequence of them or a BatchedParameters.
+        Iteration k proposes, calls the particle filter ONCE for all chains (n particles, n0 = floor(n / 5), Philox iteration k and seed
+        `seed`), draws N uniforms and accepts where log u < (ll' + prior') - ll.  The host draws come from np.random.default_rng(seed), the
+        proposal's first.  Like the reference the chains start at ll = -1e99: the first proposal is accepted.  evaluate_init=True
+        starts them at the particle filter's estimate for init_p instead (Philox iteration INIT_ITERATION): chains that start in the
+        posterior then stay in it from the first iteration on.  Yields a MetropolisState per iteration."""
+        state = BatchedParameters.of(init_p, n_chains).copy()
+        N = state.n
+        rng = np.random.default_rng(seed)
+        ll = np.full(N, -1e99)
+        accepted = np.zeros(N, dtype=np.int64)
+        pf = ParticleFilter(n, -1)
+        if evaluate_init:
+            ll = pf.filter(mod, ys, state, eng, seed=seed, iteration=INIT_ITERATION, literal=literal)["ll"] + np.asarray(prior(state), dtype=np.float64)
+        for k in range(n_iter):
+            prop = proposal(state, rng)
+            prop_ll = pf.filter(mod, ys, prop, eng, seed=seed, iteration=k, literal=literal)["ll"] + np.asarray(prior(prop), dtype=np.float64)
+            with np.errstate(invalid="ignore"):
+                take = np.log(rng.uniform(size=N)) < prop_ll - ll
+            state = state.where(take, prop)
+            ll = np.where(take, prop_ll, ll)
+            accepted = accepted + take
+            yield MetropolisState(state.copy(), ll.copy(), accepted.copy())

@@ -68,6 +68,17 @@ def _as_prior(cls, prior):
     return cls(*((float if t is ctypes.c_double else int)(x) for (_, t), x in zip(cls._fields_, tuple(prior), strict=True)))
 
 
+def check_pf_shape(d: int, p: int, n_particles: int):
+    """What dlm_pf_batch asks of its shape, said before anything is staged (the engine answers the same with DLM_ERR_UNSUPPORTED)."""
+    if p != 1:
+        raise EngineError(f"the particle filter takes a univariate observation (p = 1: every Dglm family reads y(0) and V(0,0)), got p = {p}")
+    if not 1 <= d <= _lib.PF_MAX_D:
+        raise EngineError(f"the particle filter takes a state of dimension 1 <= d <= {_lib.PF_MAX_D}, got d = {d}")
+    if n_particles % 64 != 0 or not _lib.PF_MIN_PARTICLES <= n_particles <= _lib.PF_MAX_PARTICLES:
+        raise EngineError(f"the number of particles must be a multiple of 64 between {_lib.PF_MIN_PARTICLES} and {_lib.PF_MAX_PARTICLES} "
+                          f"(one wavefront per series, whole slots of particles), got {n_particles}")
+
+
 class _Host:
     mem = _lib.DLM_MEM_HOST
 
@@ -543,6 +554,46 @@ class Engine:
         self._hold(flags, tb, Gb, gi, dt)
         self._check(self.lib.dlm_dlmfsvsys_innovations_batch(self.h, md, be.ptr(tb), op, be.ptr(w), be.ptr(status)))
         return {"w": w, "status": status}
+
+    def particle_filter(self, mat, params, y, *, family, n_particles, n0=-1, literal=False, obs_param=None, iteration=0, seed=0,
+                        series_offset=0, flags=0, want_mean=True, want_ess=True, want_cloud=True, want_weights=True):
+        """Bootstrap particle filter of a dynamic generalised linear model (dlm_pf_batch; ParticleFilter.step, ParticleFilter.scala:38-61) for
+        N series of P = n_particles particles: y [N][T] (NaN = missing), params one DlmParameters, N of them or the packed tuple of
+        pack_params (per-series parameters: what a particle-marginal Metropolis step evaluates), family one of _lib.OBS_*, obs_param [N] or a
+        scalar: the degrees of freedom of OBS_STUDENTT.  n0: resample when ESS < n0 (negative: floor(P / 5), ParticleFilter.likelihood).
+        literal=True: the reference's arithmetic (Q37-Q39).  Returns {"ll" [N], "mean" [N][T][d], "ess" [N][T], "cloud" [N][d][P],
+        "weights" [N][P], "status" [N]}; the optional ones are None when not wanted.  A series with a status bit has ll = -inf."""
+        be = self._backend(y)
+        d, T = mat.d, mat.T
+        P = int(n_particles)
+        check_pf_shape(d, mat.p, P)
+        if family not in range(6):
+            raise EngineError(f"family must be one of _lib.OBS_* (0..5), got {family!r}")
+        N = int(y.shape[0])
+        if tuple(y.shape) not in ((N, T), (N, T, 1)):
+            raise EngineError(f"y must be [N][T] = {(N, T)}, got {tuple(y.shape)}")
+        yb = be.put(y).reshape(N, T)
+        if family == _lib.OBS_STUDENTT and obs_param is None:
+            raise EngineError("OBS_STUDENTT needs obs_param: the degrees of freedom (a scalar or one per series)")
+        ob = None
+        if obs_param is not None:
+            ob = be.put(np.full(N, float(obs_param)) if np.ndim(obs_param) == 0 else obs_param)
+            if tuple(ob.shape) != (N,):
+                raise EngineError(f"obs_param must be a scalar or [N] = {(N,)}, got {tuple(ob.shape)}")
+        md, pd, op, keep = self.prepare(mat, params, N, be, flags, seed, series_offset)
+        if pd.v_tstride or pd.w_tstride:
+            raise EngineError("the particle filter takes time-invariant V and W")
+        ll = be.empty((N,))
+        mean = be.empty((N, T, d)) if want_mean else None
+        ess = be.empty((N, T)) if want_ess else None
+        cloud = be.empty((N, d, P)) if want_cloud else None
+        weights = be.empty((N, P)) if want_weights else None
+        status = be.empty((N,), np.int32)
+        desc = _lib.PfDesc(int(family), P, int(n0), 1 if literal else 0)
+        self._hold(flags, yb, ob)
+        self._check(self.lib.dlm_pf_batch(self.h, md, pd, ctypes.byref(desc), be.ptr(ob), be.ptr(yb), int(iteration), op, be.ptr(ll),
+                                          be.ptr(mean), be.ptr(ess), be.ptr(cloud), be.ptr(weights), be.ptr(status)))
+        return {"ll": ll, "mean": mean, "ess": ess, "cloud": cloud, "weights": weights, "status": status}
 
     def simulate(self, mat, params, N, *, seed=0, series_offset=0, device=False, want_x=True):
         """Dlm.simulateRegular over the model's time grid for N series (dlm_simulate_batch): (x [N][T+1][d], y [N][T][p])."""

@@ -515,6 +515,48 @@ int dlm_dlmfsv_variance_batch(dlm_engine* e, int32_t N, int32_t T, int32_t p, in
 int dlm_dlmfsvsys_innovations_batch(dlm_engine* e, const dlm_model_desc* model, const double* theta, const dlm_options* opts,
                                     double* w, int32_t* status);
 
+/* Bootstrap particle filter of a dynamic GENERALISED linear model (ParticleFilter.step / likelihood, ParticleFilter.scala:38-85, over the
+ * observation models of Dglm.scala:46-175 and package.scala:13-28) for N independent series, P particles each, one wavefront per series:
+ *   x_0,i = m0 + chol(C0) z,   x_t,i = G_t x_{t-1,i} + sqrt(dt_t) chol(W) z,   eta_t,i = F_t^T x_t,i,   y_t ~ family(eta_t,i, V).
+ * p = 1 (every family reads y(0) and V(0,0)); d <= 16; P a multiple of 64, 64 <= P <= 1024; time-invariant V and W (v_tstride = w_tstride = 0);
+ * T <= 2^21 - 2 (the Philox counter's slot field); the cloud lives in LDS, (d + 2.5) P + d^2 doubles of it, which every shape inside these
+ * limits is granted on a device with 160 KB of LDS per workgroup; anything else is DLM_ERR_UNSUPPORTED.  V, W, m0, C0 per series or shared
+ * through the strides of `params`; `model` as everywhere: F_t, the table of G, g_index, dt (dt == 0: no advance and no noise), NaN = missing y.
+ * Families and what V(0,0) = v means (log-densities as the reference writes them):
+ *   DLM_OBS_GAUSSIAN  N(eta, v)                                   DLM_OBS_POISSON   Poisson(exp(eta)) at y truncated to an integer (toInt)
+ *   DLM_OBS_NEGBIN    mean exp(eta), size exp(v)                  DLM_OBS_ZIP       zero with probability expit(v), else Poisson(exp(eta)); |y| < 1e-5 is a zero
+ *   DLM_OBS_STUDENTT  location eta, scale sqrt(v), obs_param[n] degrees of freedom (obs_param required, > 0)
+ *   DLM_OBS_BETA      mean logisticFunction(1)(eta) (0 below -5, 1 above 5), variance v; parameters that are not positive give the particle
+ *                     the weight 0 (the reference's Beta constructor throws, Q41)
+ * Per step t, W_{-1,i} = 1 / P:  advance every particle; a missing y_t ends the step there (time does advance, Q38).  Otherwise
+ *   l_i = log p(y_t | eta_t,i, v),  m = max l_i,  w_i = exp(l_i - m),  omega_i = W_{t-1,i} w_i,  s = sum omega_i,
+ *   ll += m + log s,  W_t,i = omega_i / s,  ESS = floor(1 / sum W_t,i^2);  ESS < n0: multinomial resampling -- new particle i is a copy of the first j
+ *   whose inclusive cumulative weight exceeds u_i times the last one, u_i an independent [0, 1) uniform -- and W_t,i = 1 / P.
+ * pf->n0 < 0 stands for floor(P / 5) (ParticleFilter.likelihood); n0 = 0 never resamples, n0 > P always.
+ * pf->literal = 1 is the reference's arithmetic: the weights of a step that did not resample are forgotten (W_{t-1,i}
+ * = 1 / P at every step); with ONE G (n_g = 1) a missing step does not advance the time, so the next step advances the cloud over both
+ * intervals again; the Student-t normaliser 0.5 log(pi nu scale).
+ * Outputs: ll [N]; mean [N][T][d] (nullable) sum_i W_t,i x_t,i before any resampling; ess [N][T] (nullable; a missing step repeats the last
+ * value, P before the first); cloud [N][d][P] and weights [N][P] (nullable) after the last step; status [N] (nullable).
+ * A series whose m is not finite or whose s is not positive and finite gets DLM_ST_NONFINITE, one whose chol(W) or chol(C0) meets a pivot that
+ * is not positive DLM_ST_NOT_PD; either has ll = -inf (a Metropolis step rejects it), NaN in mean and ess from that step on and in weights,
+ * and does no further step.  The batch completes.
+ * Draws: Philox streams of their own (DLM_KEY_PF, dlm_draws.h), counter (opts->seed, opts->series_offset + n, iteration, slot t, particle i):
+ * block q gives the normals of the components 2 q and 2 q + 1, block 8 the resampling uniform.  Every sum runs in a fixed order without
+ * atomics: a series' results depend on neither N nor its neighbours nor on how the batch is split.
+ * opts: mem, seed, series_offset, DLM_OPT_ASYNC.  The call reads the model's tables and analyses nothing: it does not count as the "previous
+ * model-taking call" of DLM_OPT_MODEL_UNCHANGED. */
+enum { DLM_OBS_GAUSSIAN = 0, DLM_OBS_POISSON = 1, DLM_OBS_NEGBIN = 2, DLM_OBS_ZIP = 3, DLM_OBS_STUDENTT = 4, DLM_OBS_BETA = 5 };
+typedef struct {
+  int32_t family;       /* DLM_OBS_*                                                   */
+  int32_t n_particles;  /* P                                                           */
+  int32_t n0;           /* resample when ESS < n0; < 0: floor(P / 5)                   */
+  int32_t literal;      /* 1: the reference's arithmetic, Q37-Q39                      */
+} dlm_pf_desc;
+int dlm_pf_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_params_desc* params, const dlm_pf_desc* pf,
+                 const double* obs_param, const double* y, uint64_t iteration, const dlm_options* opts, double* ll,
+                 double* mean, double* ess, double* cloud, double* weights, int32_t* status);
+
 /* Per-series log-likelihood by the prediction-error decomposition,
  *   loglik[n] = sum_t log N(y_t^obs ; f_t^obs, Q_t^obs),
  * i.e. KalmanFilter.conditionalLikelihood (KalmanFilter.scala:138-153) summed over the series (steps with no observed

@@ -365,6 +365,17 @@ JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_dlmFsvSysInnovati
   if (!read_opts(env, opts, o)) return;
   throw_if(env, eng(h), dlm_dlmfsvsys_innovations_batch(eng(h), &md, ptr<const double>(theta), &o, ptr<double>(w), ptr<int32_t>(status)));
 }
+// ---- bootstrap particle filter of a dynamic generalised linear model (ParticleFilter.scala:38-85; Dglm.scala:46-175): the log-likelihood estimate of every series, and on request the filtering means, the
+// effective sample sizes, the final cloud and its weights (0: not wanted).  dlm_pf_desc crosses as scalars in its field order; obsParam = 0: none (required by the Student-t family).
+JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_particleFilter(JNIEnv* env, jobject, jlong h, jlongArray model, jlongArray params, jlongArray opts, jint family, jint nParticles, jint n0,
+                                                                              jint literal, jlong obsParam, jlong y, jlong iteration, jlong ll, jlong mean, jlong ess, jlong cloud, jlong weights,
+                                                                              jlong status) {
+  Desc d;
+  if (!read_desc(env, model, params, opts, d)) return;
+  const dlm_pf_desc pf{family, nParticles, n0, literal};
+  throw_if(env, eng(h), dlm_pf_batch(eng(h), &d.m, &d.q, &pf, ptr<const double>(obsParam), ptr<const double>(y), static_cast<uint64_t>(iteration), &d.o, ptr<double>(ll), ptr<double>(mean),
+                                     ptr<double>(ess), ptr<double>(cloud), ptr<double>(weights), ptr<int32_t>(status)));
+}
 // ---- pooled-parameter Gibbs: reduce over series, then over GPUs (RCCL) ---------------------------------------------------------------
 JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_statsPool(JNIEnv* env, jobject, jlong h, jlong stats, jint n, jint l, jlong pooled, jlongArray opts) {
   dlm_options o{};

@@ -84,6 +84,8 @@ final class Native private[gpu] () {
   @native def dlmFsvVariance(h: Long, n: Int, t: Int, p: Int, k: Int, beta: Long, v: Long, alpha: Long, opts: Array[Long], vOut: Long, status: Long): Unit
   /** the DLM with factor stochastic-volatility system noise (DlmFsvSystem.factorState): w [N][T][d] = theta_{t+1} - G theta_t for the factor calls above with p := d (the model's d, T, N and its one G are read; a gIndex or dt is refused); dlmFsvVariance with p := d then writes the W_t stream of ffbs */
   @native def dlmFsvSysInnovations(h: Long, model: Array[Long], theta: Long, opts: Array[Long], w: Long, status: Long): Unit
+  /** bootstrap particle filter of a DGLM (ParticleFilter.step / likelihood) for N series of nParticles particles (a multiple of 64, 64..1024; d <= 16, p = 1): family 0..5 = Gaussian, Poisson, negative binomial, zero-inflated Poisson, Student-t (obsParam [N]: the degrees of freedom), Beta; n0 < 0: floor(nParticles / 5); literal = 1: the reference's arithmetic (Q37-Q39).  ll [N]; mean [N][T][d], ess [N][T], cloud [N][d][nParticles], weights [N][nParticles] and status [N] are optional (0) */
+  @native def particleFilter(h: Long, model: Array[Long], params: Array[Long], opts: Array[Long], family: Int, nParticles: Int, n0: Int, literal: Int, obsParam: Long, y: Long, iteration: Long, ll: Long, mean: Long, ess: Long, cloud: Long, weights: Long, status: Long): Unit
   @native def statsPool(h: Long, stats: Long, n: Int, l: Int, pooled: Long, opts: Array[Long]): Unit
   @native def commUniqueId(): Array[Byte]
   @native def commInitRank(h: Long, nranks: Int, rank: Int, id: Array[Byte]): Unit
