@@ -101,6 +101,12 @@ class PfDesc(ctypes.Structure):
     _fields_ = [("family", ctypes.c_int32), ("n_particles", ctypes.c_int32), ("n0", ctypes.c_int32), ("literal", ctypes.c_int32)]
 
 
+class StorvikDesc(ctypes.Structure):
+    """dlm_storvik_desc: dlm_pf_desc's fields (literal = 1: Q39 and Q43) and learn_v = 1: V is learned too (OBS_GAUSSIAN only)."""
+    _fields_ = [("family", ctypes.c_int32), ("n_particles", ctypes.c_int32), ("n0", ctypes.c_int32), ("literal", ctypes.c_int32),
+                ("learn_v", ctypes.c_int32)]
+
+
 class Options(ctypes.Structure):
     _fields_ = [("flags", ctypes.c_uint32), ("mem", ctypes.c_int32),
                 ("seed", ctypes.c_uint64), ("series_offset", ctypes.c_uint64)]
@@ -149,6 +155,8 @@ SYMBOLS = [
     ("dlm_dlmfsv_variance_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, _OP, _V, _V]),
     ("dlm_dlmfsvsys_innovations_batch", ctypes.c_int, [_V, _MP, _V, _OP, _V, _V]),
     ("dlm_pf_batch", ctypes.c_int, [_V, _MP, _PP, ctypes.POINTER(PfDesc), _V, _V, ctypes.c_uint64, _OP, _V, _V, _V, _V, _V, _V]),
+    ("dlm_storvik_batch", ctypes.c_int, [_V, _MP, _PP, ctypes.POINTER(StorvikDesc), _V, ctypes.c_int64, _V, ctypes.c_int64, _V, _V, ctypes.c_uint64,
+                                         _OP, _V, _V, _V, _V, _V, _V, _V, _V]),
     ("dlm_ou_ffbs_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, ctypes.c_int64, _V, ctypes.c_int64,
                                          _V, _OP, _V, _V, _V]),
     ("dlm_ar1_ffbs_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, ctypes.c_int64, _V, ctypes.c_int64,

@@ -29,6 +29,14 @@ constexpr unsigned DLM_KEY_DLMFSV = 0x444C4653u;     // "DLFS"
 //                     DLM_PF_BLOCK_RESAMPLE the [0, 1) uniform u_i of the resampling search of step t (pf_rand, dlm_pf.hip)
 constexpr unsigned DLM_KEY_PF = 0x50462000u;         // "PF " and the block in the low byte
 constexpr unsigned DLM_PF_BLOCK_RESAMPLE = 8u;
+//   DLM_KEY_STORVIK   dlm_storvik_batch: comp and attempt field as DLM_KEY_PF (slot t or DLM_STORVIK_SLOT_INIT, the particle).  The low byte of the
+//                     key is the BLOCK: q < 8 the Box-Muller pair of the state components (2 q, 2 q + 1), DLM_STORVIK_BLOCK_RESAMPLE the resampling
+//                     uniform, DLM_STORVIK_BLOCK_GAMMA + k the Gamma of component k (k < d: the variance W_kk; k = d: V).  The second byte is the
+//                     ATTEMPT of that Gamma's rejection loop (the counter word has no room for it beside the particle): attempt j <
+//                     DLM_STORVIK_GAMMA_ATTEMPTS, `which` 0 its normal and 1 its accept uniform; DLM_STORVIK_GAMMA_ATTEMPTS itself the boost of a shape
+//                     below 1.  The second byte is 0 for every other block.
+constexpr unsigned DLM_KEY_STORVIK = 0x53740000u;    // "St", then the attempt byte and the block byte
+constexpr unsigned DLM_STORVIK_BLOCK_RESAMPLE = 8u, DLM_STORVIK_BLOCK_GAMMA = 9u, DLM_STORVIK_GAMMA_ATTEMPTS = 255u;
 
 // ---- the slots ------------------------------------------------------------------------------------------------------------------
 // comp is a 21-bit field (the counter word is comp * 2048 + attempt * 2 + which).  A sampler whose per-time draws take comp = t < T
@@ -75,6 +83,10 @@ constexpr int DLM_PF_MAX_D = 16, DLM_PF_MAX_P = 1024;
 static_assert(DLM_PF_SLOT_INIT > (unsigned)DLM_PF_MAX_T - 1, "the particle filter's initial cloud lies above every time slot");
 static_assert(DLM_PF_MAX_P <= 1024 && (DLM_PF_MAX_D + 1) / 2 <= (int)DLM_PF_BLOCK_RESAMPLE && DLM_PF_BLOCK_RESAMPLE < 256u,
               "a particle fits the attempt field and a block the key's low byte");
+constexpr unsigned DLM_STORVIK_SLOT_INIT = DLM_SLOT_TOP;   // dlm_storvik_batch, DLM_KEY_STORVIK: the initial cloud (the steps take the slots t < T <= DLM_PF_MAX_T)
+static_assert(DLM_STORVIK_BLOCK_GAMMA > DLM_STORVIK_BLOCK_RESAMPLE && (DLM_PF_MAX_D + 1) / 2 <= (int)DLM_STORVIK_BLOCK_RESAMPLE &&
+              DLM_STORVIK_BLOCK_GAMMA + (unsigned)DLM_PF_MAX_D < 256u && DLM_STORVIK_GAMMA_ATTEMPTS < 256u,
+              "the Storvik filter's blocks (the Gammas of d + 1 components included) and a Gamma's attempts fit a byte of the key each");
 static_assert(DLM_ST_SLOT_SCALE > (unsigned)DLM_ST_MAX_T - 1, "the Student-t step's scalar slots lie above every time slot");
 static_assert(DLM_SV_SLOT_ACCEPT > (unsigned)DLM_SV_MAX_T, "the SV step's scalar slots lie above every time slot");
 static_assert(DLM_SVOU_SLOT_ACC_MU > (unsigned)DLM_SVOU_MAX_T, "the OU step's scalar slots lie above every time slot");
@@ -106,28 +118,37 @@ __device__ __forceinline__ double draw_log_uniform(unsigned key, unsigned long l
   return log(u1);
 }
 
-// Gamma(a, 1): Marsaglia & Tsang, "A simple method for generating gamma variables" (2000); a < 1 by the u^(1/a) boost
-__device__ inline double gamma_unit(double a, unsigned long long seed, unsigned long long series, unsigned long long iteration, unsigned comp,
-                                    unsigned key = DLM_KEY_GIBBS) {
+// Gamma(a, 1): Marsaglia & Tsang, "A simple method for generating gamma variables" (2000); a < 1 by the u^(1/a) boost.  Written ONCE:
+// src(attempt, which, u1, u2) hands out the uniforms of attempt < n_attempts (which 0: the normal's pair, 1: the accept uniform) and of
+// attempt n_attempts, the boost.
+template <class Source>
+__device__ __forceinline__ double gamma_unit_from(double a, unsigned n_attempts, Source&& src) {
   double boost = 1.0;
   if (a < 1.0) {
     double u1, u2;
-    gibbs_rand(seed, series, iteration, comp, 1023u, 0u, u1, u2, key);
+    src(n_attempts, 0u, u1, u2);
     boost = pow(u1, 1.0 / a);
     a += 1.0;
   }
   const double dd = a - 1.0 / 3.0, cc = 1.0 / sqrt(9.0 * dd);
-  for (unsigned k = 0; k < 1023u; ++k) {
+  for (unsigned k = 0; k < n_attempts; ++k) {
     double u1, u2, w1, w2;
-    gibbs_rand(seed, series, iteration, comp, k, 0u, u1, u2, key);
+    src(k, 0u, u1, u2);
     const double x = sqrt(-2.0 * log(u1)) * cos(6.283185307179586476925286766559 * u2);
     double v = 1.0 + cc * x;
     if (v <= 0.0) continue;
     v = v * v * v;
-    gibbs_rand(seed, series, iteration, comp, k, 1u, w1, w2, key);
+    src(k, 1u, w1, w2);
     if (log(w1) < 0.5 * x * x + dd - dd * v + dd * log(v)) return dd * v * boost;
   }
   return dd * boost;   // unreachable in practice (acceptance > 95 % per attempt)
+}
+// the Gamma of a scalar slot: attempt k of the counter word, the boost at attempt 1023
+__device__ inline double gamma_unit(double a, unsigned long long seed, unsigned long long series, unsigned long long iteration, unsigned comp,
+                                    unsigned key = DLM_KEY_GIBBS) {
+  return gamma_unit_from(a, 1023u, [&](unsigned attempt, unsigned which, double& u1, double& u2) {
+    gibbs_rand(seed, series, iteration, comp, attempt, which, u1, u2, key);
+  });
 }
 
 // ---- the Beta proposal of phi (samplePhi, StochasticVolatility.scala:189-202; samplePhiOu of stepOu) ------------------------------

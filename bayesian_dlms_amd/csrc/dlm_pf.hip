@@ -12,17 +12,10 @@
 //                                                   plus the carry = the running sum at the previous slot's lane 63 (carry + v);
 //   matrix-vector products                          index ascending from 0, the first product starts the sum.
 // No atomics, no dependence on N or on the neighbours.
-#include "dlm_wave.h"
-#include "dlm_draws.h"
+#include "dlm_pf_common.h"
 
 namespace dlm {
 namespace {
-
-constexpr double PF_PI = 3.14159265358979323846, PF_2PI = 6.283185307179586476925286766559;
-
-// ocml's lgamma, ONE copy of it: inlined at its nine call sites, its constants are hoisted out of the loops over t and take more registers
-// than the wave has
-__device__ __noinline__ double pf_lgamma(double v) { return lgamma(v); }
 
 // the two uniforms of block `block` of (slot, particle): u1 in (0, 1], u2 in [0, 1)
 __device__ __forceinline__ void pf_rand(const DrawStream& rs, unsigned long long series, unsigned slot, unsigned particle, unsigned block,
@@ -40,92 +33,6 @@ __device__ __forceinline__ void pf_normals(const DrawStream& rs, unsigned long l
     const double r = sqrt(-2.0 * log(u1)), ang = PF_2PI * u2;
     z[2 * q] = r * cos(ang);
     if (2 * q + 1 < D) z[2 * q + 1] = r * sin(ang);
-  }
-}
-
-// Lower Cholesky factor of the column-major A (its lower triangle is read) into sl, row-major; lane 0 computes, every lane gets the verdict.
-// false: a pivot that is not positive (NaN included)
-template <int D>
-__device__ __forceinline__ bool pf_chol(const double* A, double* sl, int lane) {
-  int ok = 1;
-  if (lane == 0) {
-    for (int j = 0; j < D && ok; ++j) {
-      double s = A[j + j * D];
-      for (int k = 0; k < j; ++k) s -= sl[j * D + k] * sl[j * D + k];
-      if (!(s > 0.0)) { ok = 0; break; }
-      const double dj = sqrt(s);
-      sl[j * D + j] = dj;
-      for (int c = j + 1; c < D; ++c) sl[j * D + c] = 0.0;   // the products run over whole rows: a zero adds nothing
-      for (int i = j + 1; i < D; ++i) {
-        double t = A[i + j * D];
-        for (int k = 0; k < j; ++k) t -= sl[i * D + k] * sl[j * D + k];
-        sl[i * D + j] = t / dj;
-      }
-    }
-  }
-  wave_sync();
-  return __shfl(ok, 0, 64) != 0;
-}
-
-// what a step's log-density needs beyond (eta, the particle): made once per step, the same in every lane
-struct PfObs { double y, v, nu, c0, c1, c2; };
-
-__device__ __forceinline__ PfObs pf_obs(int family, int literal, double y, double v, double nu) {
-  PfObs o{y, v, nu, 0.0, 0.0, 0.0};
-  switch (family) {
-    case DLM_OBS_GAUSSIAN: o.c0 = 0.5 * log(PF_2PI * v); break;
-    case DLM_OBS_POISSON: o.y = trunc(y); o.c0 = pf_lgamma(o.y + 1.0); break;
-    case DLM_OBS_NEGBIN: o.c1 = exp(v); o.c0 = (pf_lgamma(o.c1 + y) - pf_lgamma(y + 1.0)) - pf_lgamma(o.c1); break;
-    case DLM_OBS_ZIP: { const double ev = exp(v); o.c1 = ev / (1.0 + ev); o.c2 = log(1.0 + ev); o.c0 = pf_lgamma(y + 1.0); break; }
-    case DLM_OBS_STUDENTT: {
-      const double sc = sqrt(v);
-      o.c1 = nu * sc * sc;
-      o.c0 = (pf_lgamma((nu + 1.0) * 0.5) - 0.5 * log(literal ? PF_PI * nu * sc : PF_PI * nu * sc * sc)) - pf_lgamma(nu * 0.5);   // Q39
-      break;
-    }
-    default: o.c1 = log(y); o.c2 = log(1.0 - y); break;   // DLM_OBS_BETA
-  }
-  return o;
-}
-
-// log p(y | eta, v) of the family, as the reference writes it
-__device__ __forceinline__ double pf_logdens(int family, const PfObs& o, double eta) {
-  switch (family) {
-    case DLM_OBS_GAUSSIAN: { const double e = o.y - eta; return -o.c0 - (0.5 * (e * e)) / o.v; }
-    case DLM_OBS_POISSON: return (o.y * eta - exp(eta)) - o.c0;
-    case DLM_OBS_NEGBIN: {
-      const double mu = exp(eta), size = o.c1;
-      return (o.c0 + size * log(size / (mu + size))) + o.y * log(mu / (mu + size));
-    }
-    case DLM_OBS_ZIP:
-      if (fabs(o.y) < 1e-5) return log(o.c1 + (1.0 - o.c1) * exp(-exp(eta)));
-      return ((o.y * eta - o.c2) - exp(eta)) - o.c0;
-    case DLM_OBS_STUDENTT: { const double e = o.y - eta; return o.c0 - ((o.nu + 1.0) * 0.5) * log1p((e * e) / o.c1); }
-    default: {   // DLM_OBS_BETA: logisticFunction(1.0) with its clamp, then Dglm.beta's (mean, variance) -> (alpha, beta)
-      const double mean = eta < -5.0 ? 0.0 : (eta > 5.0 ? 1.0 : 1.0 / (1.0 + exp(-eta)));
-      const double aa = (mean * (1.0 - mean)) / o.v;
-      const double al = mean * (aa - 1.0), be = (1.0 - mean) * (aa - 1.0);
-      if (!(al > 0.0 && be > 0.0)) return -__builtin_inf();   // Q41
-      return ((al - 1.0) * o.c1 + (be - 1.0) * o.c2) - ((pf_lgamma(al) + pf_lgamma(be)) - pf_lgamma(al + be));
-    }
-  }
-}
-
-// sum_i W_i x_k,i for every component, lane 0 stores them
-template <int D>
-__device__ __forceinline__ void pf_means(const double* x, const double* wg, int P, int lane, double* out) {
-  double acc[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k) acc[k] = 0.0;
-  for (int i = lane; i < P; i += 64) {
-    const double w = wg[i];
-#pragma unroll
-    for (int k = 0; k < D; ++k) acc[k] = acc[k] + w * x[k * P + i];
-  }
-#pragma unroll
-  for (int k = 0; k < D; ++k) {
-    const double m = wave_sum(acc[k]);
-    if (lane == 0) out[k] = m;
   }
 }
 
@@ -245,30 +152,12 @@ __global__ __launch_bounds__(64, D <= 8 ? 2 : 1) void k_pf(PfArgs a) {
       if (!(ess_last < (double)a.n0)) continue;
 
       // -- multinomial resampling: the running sums, the searches, the gather component by component
-      double carry = 0.0;
-      for (int i = lane; i < P; i += 64) {
-        double s = wg[i];
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-          const double up = __shfl_up(s, off, 64);
-          if (lane >= off) s = s + up;
-        }
-        s = carry + s;
-        cum[i] = s;
-        carry = __shfl(s, 63, 64);
-      }
-      const double total = carry;
+      const double total = pf_running_sums(wg, cum, P, lane);
       wave_sync();
       for (int i = lane; i < P; i += 64) {
         double u1, u2;
         pf_rand(a.rs, series, (unsigned)t, (unsigned)i, DLM_PF_BLOCK_RESAMPLE, u1, u2);
-        const double target = u2 * total;
-        int lo = 0, hi = P - 1;   // the first j with cum[j] > target; P - 1 when none is (u2 total rounding up to the total)
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (cum[mid] > target) hi = mid; else lo = mid + 1;
-        }
-        anc[i] = lo;
+        anc[i] = pf_ancestor(cum, P, u2 * total);
       }
       wave_sync();
       for (int k = 0; k < D; ++k) {

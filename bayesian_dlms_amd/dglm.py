@@ -1,5 +1,6 @@
-"""Dynamic generalised linear models, the bootstrap particle filter and the particle-marginal Metropolis sampler built on it
-(the reference's Dglm.scala, ParticleFilter.scala and Metropolis.dglm, MetropolisHastings.scala:142-154).
+"""Dynamic generalised linear models, the bootstrap particle filter, the particle-marginal Metropolis sampler built on it and the
+Storvik filter, which learns the variances online (the reference's Dglm.scala, ParticleFilter.scala, Metropolis.dglm,
+MetropolisHastings.scala:142-154, and Storvik.scala).
 
 A `Dglm` is a `Dlm` with one of six observation models for its scalar observation; V(0, 0) = v is what each family makes of it
 (include/dlm_engine.h, dlm_pf_batch).  `ParticleFilter(n, n0).filter` runs the engine's filter for one series or a batch of them, with one
@@ -235,6 +236,49 @@ class ParticleFilter:
     def likelihood(mod: Dglm, ys, n: int, p, eng, **kw):
         """ParticleFilter.likelihood(mod, ys, n)(p) (ParticleFilter.scala:78-85): the log-likelihood estimate(s) with n0 = floor(n / 5)."""
         return ParticleFilter(n, -1).filter(mod, ys, p, eng, **kw)["ll"]
+
+
+class StorvikFilter:
+    """StorvikFilter.filterTs(model, ys, p, priorV, priorW, n, n0) (Storvik.scala:179-189) on the engine (dlm_storvik_batch): a particle
+    filter whose particles carry the InverseGamma statistics of their own variances -- the diagonal of W, and V for the Gaussian family --
+    and draw them afresh at every step.  One pass gives the filtering distribution, the posterior of the variances at every time and an
+    unbiased estimate of the evidence p(y_1:T) (the reference's filter has no likelihood; its other departures are DESIGN.md 2, Q42-Q48)."""
+
+    def __init__(self, n: int, n0: int = -1):
+        check_pf_shape(1, 1, int(n))
+        self.n, self.n0 = int(n), int(n0)
+
+    def filter(self, mod: Dglm, ys, p: DlmParameters, prior_v, prior_w, eng, *, learn_v: Optional[bool] = None, seed: int = 0,
+               iteration: int = 0, series_offset: int = 0, literal: bool = False):
+        """ys as ParticleFilter.filter takes them; p: m0 and C0 of the initial cloud (and V when it is not learned; p.w is not read);
+        prior_v an InverseGamma (None when V is not learned), prior_w one InverseGamma for every component or d of them.  learn_v
+        defaults to "the family is Gaussian"; a family other than the Gaussian learns W alone.  Returns what ParticleFilter.filter
+        returns plus "scale_mean" [N][T][d+1] (the weighted means of the statistics' scales, V's last), "scales" [N][d+1][n], the shapes
+        "shape_w" [N][T][d] and "shape_v" [N][T] of the posteriors after step t (prior + 0.5 per advance / per observation: the time grid
+        and the missing pattern fix them, the kernel does not write them), and the Rao-Blackwellised posterior means "w_mean" [N][T][d] =
+        scale_mean / (shape - 1) and "v_mean" [N][T], NaN where the shape is <= 1 (and v_mean where V is not learned)."""
+        times, y = _observations(ys)
+        f0 = np.atleast_2d(np.asarray(mod.f(float(times[0])), dtype=np.float64))
+        d = f0.shape[0]
+        check_pf_shape(d, f0.shape[1], self.n)
+        mat = materialise_pf(mod, times)
+        learn_v = mod.family == _lib.OBS_GAUSSIAN if learn_v is None else bool(learn_v)
+        pws = [prior_w] * d if hasattr(prior_w, "shape") and hasattr(prior_w, "scale") else list(prior_w)
+        if len(pws) != d:
+            raise EngineError(f"prior_w: one InverseGamma or d = {d} of them, got {len(pws)}")
+        pw = np.array([[q.shape, q.scale] for q in pws], dtype=np.float64)
+        pv = np.array([prior_v.shape, prior_v.scale], dtype=np.float64) if learn_v else None
+        out = eng.storvik_filter(mat, p, y, pw, family=mod.family, n_particles=self.n, prior_v=pv, learn_v=learn_v, n0=self.n0,
+                                 literal=literal, obs_param=mod.nu, iteration=iteration, seed=seed, series_offset=series_offset)
+        out = {k: None if v is None else np.asarray(v) for k, v in out.items()}
+        N, T = y.shape
+        advances = np.cumsum(mat.dt != 0.0) if mat.dt is not None else np.arange(1, T + 1)
+        out["shape_w"] = np.broadcast_to((pw[None, :, 0] + 0.5 * advances[:, None].astype(np.float64))[None], (N, T, d)).copy()
+        out["shape_v"] = pv[0] + 0.5 * np.cumsum(~np.isnan(y), axis=1).astype(np.float64) if learn_v else np.full((N, T), np.nan)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out["w_mean"] = np.where(out["shape_w"] > 1.0, out["scale_mean"][:, :, :d] / (out["shape_w"] - 1.0), np.nan)
+            out["v_mean"] = np.where(out["shape_v"] > 1.0, out["scale_mean"][:, :, d] / (out["shape_v"] - 1.0), np.nan)
+        return out
 
 
 INIT_ITERATION = 0xFFFFFFFF   # the Philox iteration of Metropolis.dglm's evaluation of the initial parameters

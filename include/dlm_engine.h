@@ -557,6 +557,47 @@ int dlm_pf_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_params_de
                  const double* obs_param, const double* y, uint64_t iteration, const dlm_options* opts, double* ll,
                  double* mean, double* ess, double* cloud, double* weights, int32_t* status);
 
+/* Storvik filter of a dynamic generalised linear model (StorvikFilter.step / filterTs, Storvik.scala:105-189; Storvik 2002): the particle
+ * filter above with ONLINE PARAMETER LEARNING.  W is diagonal and unknown, W_kk ~ InverseGamma(prior_w[k][0], prior_w[k][1]) (shape, scale);
+ * with sv->learn_v = 1 (DLM_OBS_GAUSSIAN only: the statistic is conjugate for the Gaussian family alone, any other family is DLM_ERR_ARG) so
+ * is V ~ InverseGamma(prior_v[0], prior_v[1]); with learn_v = 0 V is params->V as in dlm_pf_batch and prior_v is not read.  params->W is
+ * never read, params->V only with learn_v = 0.  prior_v_stride / prior_w_stride: doubles between the priors of consecutive series, 0 = one
+ * prior for the batch.  Every particle carries the SCALES bw_k,i (k < d) and bv_i of its own posteriors; the shapes are the same for every
+ * particle, aw_k = prior shape + 0.5 (advances so far), av = prior shape + 0.5 (observations so far).  Shapes and limits as dlm_pf_batch,
+ * except the LDS: (2 d + 3.5) P + d^2 doubles, which d = 16 with P <= 512 and d <= 8 with P = 1024 are granted on a device with 160 KB per
+ * workgroup; more is DLM_ERR_UNSUPPORTED (d = 16, P = 1024).  Per step t, W_{-1,i} = 1 / P:
+ *   dt_t != 0:  w_k,i = bw_k,i / Gamma(aw_k, 1),  x'_k,i = (G_t x_i)_k + sqrt(dt_t w_k,i) z_k,i,  bw_k,i += 0.5 (x'_k,i - (G_t x_i)_k)^2 / dt_t;
+ *               dt_t == 0: no advance, no draw, no update (the reference divides by zero, Q46);
+ *   a missing y_t ends the step there: the means under the carried weights are written, the ESS repeats;
+ *   v_i = bv_i / Gamma(av, 1) (learn_v) or V,  l_i = log p(y_t | F_t^T x'_i, v_i),  then m, omega_i, s, ll, W_t,i and the ESS as in dlm_pf_batch;
+ *   learn_v:  bv_i += 0.5 (y_t - F_t^T x'_i)^2;
+ *   ESS < n0: multinomial resampling as in dlm_pf_batch of the particle's WHOLE tuple (x_i, bw_.,i, bv_i), W_t,i = 1 / P.
+ * The statistics are updated before the gather, on the particle that made the move (the reference pairs the states of two different
+ * particles there, Q42: not offered).  sv->literal = 1: the weights of a step that did not resample are forgotten (Q43) and the Student-t
+ * normaliser is Q39's.  ll estimates log p(y_1:T) with V and W integrated over their priors, without bias on the natural scale (the
+ * reference's filter accumulates no likelihood, Q48).
+ * Outputs: ll [N]; mean [N][T][d], ess [N][T], cloud [N][d][P], weights [N][P] (nullable) as dlm_pf_batch; scale_mean [N][T][d+1] (nullable)
+ * sum_i W_t,i bw_k,i for k < d and sum_i W_t,i bv_i for k = d, before any resampling: divided by (shape - 1) the Rao-Blackwellised posterior
+ * means of W_kk and V at time t; scales [N][d+1][P] (nullable) the rows bw_k and bv after the last step.  Without learn_v the entries k = d
+ * are NaN.  status [N] (nullable): DLM_ST_NOT_PD for a chol(C0) that fails or a prior shape or scale that is not positive (NaN included),
+ * DLM_ST_NONFINITE as in dlm_pf_batch; such a series has ll = -inf, NaN in mean, scale_mean and ess from the failing step on and in weights
+ * and scales, and its neighbours are untouched.
+ * Draws: the streams DLM_KEY_STORVIK (dlm_draws.h): a pure function of (opts->seed, opts->series_offset + n, iteration, t or the initial
+ * slot, particle, what), what = a normal pair, the resampling uniform or attempt j of the Gamma of component k <= d.
+ * opts: mem, seed, series_offset, DLM_OPT_ASYNC.  Like dlm_pf_batch the call does not count as the "previous model-taking call" of
+ * DLM_OPT_MODEL_UNCHANGED. */
+typedef struct {
+  int32_t family;       /* DLM_OBS_*                                                   */
+  int32_t n_particles;  /* P                                                           */
+  int32_t n0;           /* resample when ESS < n0; < 0: floor(P / 5)                   */
+  int32_t literal;      /* 1: the reference's arithmetic, Q39 and Q43                  */
+  int32_t learn_v;      /* 1: V is learned too (DLM_OBS_GAUSSIAN only)                 */
+} dlm_storvik_desc;
+int dlm_storvik_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_params_desc* params, const dlm_storvik_desc* sv,
+                      const double* prior_v, int64_t prior_v_stride, const double* prior_w, int64_t prior_w_stride,
+                      const double* obs_param, const double* y, uint64_t iteration, const dlm_options* opts, double* ll, double* mean,
+                      double* ess, double* scale_mean, double* cloud, double* weights, double* scales, int32_t* status);
+
 /* Per-series log-likelihood by the prediction-error decomposition,
  *   loglik[n] = sum_t log N(y_t^obs ; f_t^obs, Q_t^obs),
  * i.e. KalmanFilter.conditionalLikelihood (KalmanFilter.scala:138-153) summed over the series (steps with no observed

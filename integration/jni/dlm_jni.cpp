@@ -376,6 +376,19 @@ JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_particleFilter(JN
   throw_if(env, eng(h), dlm_pf_batch(eng(h), &d.m, &d.q, &pf, ptr<const double>(obsParam), ptr<const double>(y), static_cast<uint64_t>(iteration), &d.o, ptr<double>(ll), ptr<double>(mean),
                                      ptr<double>(ess), ptr<double>(cloud), ptr<double>(weights), ptr<int32_t>(status)));
 }
+// ---- Storvik filter of a dynamic generalised linear model (Storvik.scala:105-189): the particle filter above with the diagonal of W -- and with learnV = 1 (Gaussian family) V -- learned online from
+// InverseGamma priors: priorV [2] = (shape, scale), priorW [d][2], strides in doubles (0: one prior for the batch).  dlm_storvik_desc crosses as scalars in its field order; scaleMean [N][T][d+1] and
+// scales [N][d+1][nParticles] are optional (0) like the outputs of particleFilter.
+JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_storvikFilter(JNIEnv* env, jobject, jlong h, jlongArray model, jlongArray params, jlongArray opts, jint family, jint nParticles, jint n0,
+                                                                             jint literal, jint learnV, jlong priorV, jlong priorVStride, jlong priorW, jlong priorWStride, jlong obsParam, jlong y,
+                                                                             jlong iteration, jlong ll, jlong mean, jlong ess, jlong scaleMean, jlong cloud, jlong weights, jlong scales, jlong status) {
+  Desc d;
+  if (!read_desc(env, model, params, opts, d)) return;
+  const dlm_storvik_desc sv{family, nParticles, n0, literal, learnV};
+  throw_if(env, eng(h), dlm_storvik_batch(eng(h), &d.m, &d.q, &sv, ptr<const double>(priorV), static_cast<int64_t>(priorVStride), ptr<const double>(priorW), static_cast<int64_t>(priorWStride),
+                                          ptr<const double>(obsParam), ptr<const double>(y), static_cast<uint64_t>(iteration), &d.o, ptr<double>(ll), ptr<double>(mean), ptr<double>(ess),
+                                          ptr<double>(scaleMean), ptr<double>(cloud), ptr<double>(weights), ptr<double>(scales), ptr<int32_t>(status)));
+}
 // ---- pooled-parameter Gibbs: reduce over series, then over GPUs (RCCL) ---------------------------------------------------------------
 JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_statsPool(JNIEnv* env, jobject, jlong h, jlong stats, jint n, jint l, jlong pooled, jlongArray opts) {
   dlm_options o{};

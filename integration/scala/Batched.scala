@@ -86,6 +86,8 @@ final class Native private[gpu] () {
   @native def dlmFsvSysInnovations(h: Long, model: Array[Long], theta: Long, opts: Array[Long], w: Long, status: Long): Unit
   /** bootstrap particle filter of a DGLM (ParticleFilter.step / likelihood) for N series of nParticles particles (a multiple of 64, 64..1024; d <= 16, p = 1): family 0..5 = Gaussian, Poisson, negative binomial, zero-inflated Poisson, Student-t (obsParam [N]: the degrees of freedom), Beta; n0 < 0: floor(nParticles / 5); literal = 1: the reference's arithmetic (Q37-Q39).  ll [N]; mean [N][T][d], ess [N][T], cloud [N][d][nParticles], weights [N][nParticles] and status [N] are optional (0) */
   @native def particleFilter(h: Long, model: Array[Long], params: Array[Long], opts: Array[Long], family: Int, nParticles: Int, n0: Int, literal: Int, obsParam: Long, y: Long, iteration: Long, ll: Long, mean: Long, ess: Long, cloud: Long, weights: Long, status: Long): Unit
+  /** Storvik filter of a DGLM (StorvikFilter.filterTs): the particle filter above with the diagonal of W -- and with learnV = 1 (Gaussian family only) V -- learned online from InverseGamma priors, priorV [2] = (shape, scale) and priorW [d][2] (strides in doubles, 0: one prior for the batch); params' W is not read, its V only with learnV = 0; literal = 1: Q39 and Q43.  ll [N] estimates the evidence; scaleMean [N][T][d+1] (the weighted means of the statistics' scales: divided by shape - 1 the posterior means of the variances) and scales [N][d+1][nParticles] are optional (0) like mean, ess, cloud, weights and status */
+  @native def storvikFilter(h: Long, model: Array[Long], params: Array[Long], opts: Array[Long], family: Int, nParticles: Int, n0: Int, literal: Int, learnV: Int, priorV: Long, priorVStride: Long, priorW: Long, priorWStride: Long, obsParam: Long, y: Long, iteration: Long, ll: Long, mean: Long, ess: Long, scaleMean: Long, cloud: Long, weights: Long, scales: Long, status: Long): Unit
   @native def statsPool(h: Long, stats: Long, n: Int, l: Int, pooled: Long, opts: Array[Long]): Unit
   @native def commUniqueId(): Array[Byte]
   @native def commInitRank(h: Long, nranks: Int, rank: Int, id: Array[Byte]): Unit
