@@ -107,6 +107,13 @@ class StorvikDesc(ctypes.Structure):
                 ("learn_v", ctypes.c_int32)]
 
 
+class LwDesc(ctypes.Structure):
+    """dlm_lw_desc: dlm_storvik_desc's fields (literal = 1: Q39, Q50 and Q51; learn_v = 1: log V is learned too, for OBS_GAUSSIAN,
+    OBS_STUDENTT and OBS_BETA) and the shrinkage a, 0 < a <= 1."""
+    _fields_ = [("family", ctypes.c_int32), ("n_particles", ctypes.c_int32), ("n0", ctypes.c_int32), ("literal", ctypes.c_int32),
+                ("learn_v", ctypes.c_int32), ("a", ctypes.c_double)]
+
+
 class Options(ctypes.Structure):
     _fields_ = [("flags", ctypes.c_uint32), ("mem", ctypes.c_int32),
                 ("seed", ctypes.c_uint64), ("series_offset", ctypes.c_uint64)]
@@ -157,6 +164,8 @@ SYMBOLS = [
     ("dlm_pf_batch", ctypes.c_int, [_V, _MP, _PP, ctypes.POINTER(PfDesc), _V, _V, ctypes.c_uint64, _OP, _V, _V, _V, _V, _V, _V]),
     ("dlm_storvik_batch", ctypes.c_int, [_V, _MP, _PP, ctypes.POINTER(StorvikDesc), _V, ctypes.c_int64, _V, ctypes.c_int64, _V, _V, ctypes.c_uint64,
                                          _OP, _V, _V, _V, _V, _V, _V, _V, _V]),
+    ("dlm_lw_batch", ctypes.c_int, [_V, _MP, _PP, ctypes.POINTER(LwDesc), _V, ctypes.c_int64, _V, ctypes.c_int64, _V, _V, ctypes.c_uint64,
+                                    _OP, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
     ("dlm_ou_ffbs_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, ctypes.c_int64, _V, ctypes.c_int64,
                                          _V, _OP, _V, _V, _V]),
     ("dlm_ar1_ffbs_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, ctypes.c_int64, _V, ctypes.c_int64,

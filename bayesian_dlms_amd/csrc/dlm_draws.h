@@ -37,6 +37,12 @@ constexpr unsigned DLM_PF_BLOCK_RESAMPLE = 8u;
 //                     below 1.  The second byte is 0 for every other block.
 constexpr unsigned DLM_KEY_STORVIK = 0x53740000u;    // "St", then the attempt byte and the block byte
 constexpr unsigned DLM_STORVIK_BLOCK_RESAMPLE = 8u, DLM_STORVIK_BLOCK_GAMMA = 9u, DLM_STORVIK_GAMMA_ATTEMPTS = 255u;
+//   DLM_KEY_LW        dlm_lw_batch: comp and attempt field as DLM_KEY_PF (slot t or DLM_LW_SLOT_INIT, the particle).  The low byte of the key is the
+//                     BLOCK: q < 8 the Box-Muller pair of the state components (2 q, 2 q + 1), DLM_LW_BLOCK_RESAMPLE the uniform of the second
+//                     stage's resampling, DLM_LW_BLOCK_FIRST the uniform of the first (auxiliary) stage's, DLM_LW_BLOCK_PARAM + q the Box-Muller
+//                     pair of the log-variances (2 q, 2 q + 1) (k < d: log W_kk; k = d: log V).  The second byte is 0.
+constexpr unsigned DLM_KEY_LW = 0x4C570000u;         // "LW", a zero byte and the block byte
+constexpr unsigned DLM_LW_BLOCK_RESAMPLE = 8u, DLM_LW_BLOCK_FIRST = 9u, DLM_LW_BLOCK_PARAM = 10u;
 
 // ---- the slots ------------------------------------------------------------------------------------------------------------------
 // comp is a 21-bit field (the counter word is comp * 2048 + attempt * 2 + which).  A sampler whose per-time draws take comp = t < T
@@ -87,6 +93,11 @@ constexpr unsigned DLM_STORVIK_SLOT_INIT = DLM_SLOT_TOP;   // dlm_storvik_batch,
 static_assert(DLM_STORVIK_BLOCK_GAMMA > DLM_STORVIK_BLOCK_RESAMPLE && (DLM_PF_MAX_D + 1) / 2 <= (int)DLM_STORVIK_BLOCK_RESAMPLE &&
               DLM_STORVIK_BLOCK_GAMMA + (unsigned)DLM_PF_MAX_D < 256u && DLM_STORVIK_GAMMA_ATTEMPTS < 256u,
               "the Storvik filter's blocks (the Gammas of d + 1 components included) and a Gamma's attempts fit a byte of the key each");
+constexpr unsigned DLM_LW_SLOT_INIT = DLM_SLOT_TOP;   // dlm_lw_batch, DLM_KEY_LW: the initial cloud (the steps take the slots t < T <= DLM_PF_MAX_T)
+static_assert(DLM_LW_SLOT_INIT > (unsigned)DLM_PF_MAX_T - 1, "the Liu-West filter's initial cloud lies above every time slot");
+static_assert((DLM_PF_MAX_D + 1) / 2 <= (int)DLM_LW_BLOCK_RESAMPLE && DLM_LW_BLOCK_FIRST > DLM_LW_BLOCK_RESAMPLE && DLM_LW_BLOCK_PARAM > DLM_LW_BLOCK_FIRST &&
+              DLM_LW_BLOCK_PARAM + (unsigned)(DLM_PF_MAX_D + 2) / 2 <= 256u,
+              "the Liu-West filter's blocks (the pairs of d + 1 log-variances included) are distinct and fit the key's low byte");
 static_assert(DLM_ST_SLOT_SCALE > (unsigned)DLM_ST_MAX_T - 1, "the Student-t step's scalar slots lie above every time slot");
 static_assert(DLM_SV_SLOT_ACCEPT > (unsigned)DLM_SV_MAX_T, "the SV step's scalar slots lie above every time slot");
 static_assert(DLM_SVOU_SLOT_ACC_MU > (unsigned)DLM_SVOU_MAX_T, "the OU step's scalar slots lie above every time slot");

@@ -1495,6 +1495,75 @@ int dlm_storvik_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_para
   return st.finish(opts->flags & DLM_OPT_ASYNC);
 }
 
+int dlm_lw_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_params_desc* params, const dlm_lw_desc* lw,
+                 const double* prior_v, int64_t prior_v_stride, const double* prior_w, int64_t prior_w_stride,
+                 const double* obs_param, const double* y, uint64_t iteration, const dlm_options* opts, double* ll, double* mean,
+                 double* ess, double* psi_mean, double* psi_var, double* cloud, double* weights, double* psi, int32_t* status) {
+  if (!e) return DLM_ERR_ARG;
+  if (!model || !params || !lw) return fail(e, DLM_ERR_ARG, "null descriptor");
+  int rc;
+  if ((rc = check_opts(e, opts))) return rc;
+  const int d = model->d, T = model->T, N = model->N, P = lw->n_particles;
+  if (d < 1 || model->p < 1 || T < 1 || N < 1) return fail(e, DLM_ERR_ARG, "d, p, T, N must be >= 1");
+  if (!model->F || !model->G || model->n_g < 1) return fail(e, DLM_ERR_ARG, "model tables F/G missing");
+  if (model->n_g > 1 && !model->g_index) return fail(e, DLM_ERR_ARG, "n_g > 1 needs g_index");
+  if (model->f_stride != 0 && model->f_stride != (int64_t)d * model->p) return fail(e, DLM_ERR_ARG, "f_stride must be 0 or d*p");
+  if (!params->m0 || !params->C0) return fail(e, DLM_ERR_ARG, "parameter arrays m0/C0 missing");
+  if (lw->family < DLM_OBS_GAUSSIAN || lw->family > DLM_OBS_BETA) return fail(e, DLM_ERR_ARG, "family: one of DLM_OBS_*");
+  if (lw->literal != 0 && lw->literal != 1) return fail(e, DLM_ERR_ARG, "literal: 0 or 1");
+  if (lw->learn_v != 0 && lw->learn_v != 1) return fail(e, DLM_ERR_ARG, "learn_v: 0 or 1");
+  if (!(lw->a > 0.0 && lw->a <= 1.0)) return fail(e, DLM_ERR_ARG, "a: the shrinkage must satisfy 0 < a <= 1");
+  if (lw->learn_v && lw->family != DLM_OBS_GAUSSIAN && lw->family != DLM_OBS_STUDENTT && lw->family != DLM_OBS_BETA)
+    return fail(e, DLM_ERR_ARG, "learn_v = 1 needs DLM_OBS_GAUSSIAN, DLM_OBS_STUDENTT or DLM_OBS_BETA: the families whose v is a positive scale");
+  if (lw->learn_v ? !prior_v : !params->V) return fail(e, DLM_ERR_ARG, "learn_v = 1 needs prior_v, learn_v = 0 needs params->V");
+  if (!prior_w) return fail(e, DLM_ERR_ARG, "prior_w is required");
+  if ((prior_v_stride != 0 && prior_v_stride < 2) || (prior_w_stride != 0 && prior_w_stride < 2 * (int64_t)d)) return fail(e, DLM_ERR_ARG, "prior_v_stride must be 0 or >= 2, prior_w_stride 0 or >= 2 d");
+  if (lw->family == DLM_OBS_STUDENTT && !obs_param) return fail(e, DLM_ERR_ARG, "DLM_OBS_STUDENTT needs obs_param (the degrees of freedom of every series)");
+  if (!y || !ll) return fail(e, DLM_ERR_ARG, "y and ll are required");
+  if (model->p != 1) return fail(e, DLM_ERR_UNSUPPORTED, "the Liu-West filter takes a univariate observation (p = 1): every Dglm family reads y(0) and V(0,0)");
+  if (d > dlm::DLM_PF_MAX_D) return fail(e, DLM_ERR_UNSUPPORTED, "the Liu-West filter takes d <= 16");
+  if (P < 64 || P > dlm::DLM_PF_MAX_P || P % 64 != 0) return fail(e, DLM_ERR_UNSUPPORTED, "n_particles must be a multiple of 64 with 64 <= n_particles <= 1024 (one wavefront per series, whole slots of particles)");
+  if (T > dlm::DLM_PF_MAX_T) return fail(e, DLM_ERR_UNSUPPORTED, "T must stay below 2^21 - 1 (the Philox counter's slot field)");
+  if (!lw->learn_v && params->v_tstride) return fail(e, DLM_ERR_UNSUPPORTED, "the Liu-West filter takes a time-invariant V (v_tstride = 0)");
+  HIP_TRY(e, hipSetDevice(e->device));
+  const size_t lds = dlm::lw_lds_bytes(d, P), have = dlm::lds_limit();
+  if (have && lds > have) return fail(e, DLM_ERR_UNSUPPORTED, "d and n_particles need more LDS than a workgroup of this device gets: (2 d + 3.5) n_particles + d^2 + d + 1 doubles");
+  dlm::LwArgs a{};
+  const size_t n = N, t = T, dd = d, np = P;
+  Stager st(e, opts->mem == DLM_MEM_HOST);
+  st.in(&a.F, model->F, (model->f_stride ? t : 1) * dd);
+  st.in(&a.G, model->G, (size_t)model->n_g * dd * dd);
+  st.in(&a.g_index, (const int*)model->g_index, model->g_index ? t : 0);
+  st.in(&a.dt, model->dt, model->dt ? t : 0);
+  st.in(&a.V, lw->learn_v ? nullptr : params->V, params->v_stride ? (n - 1) * (size_t)params->v_stride + 1 : 1);   // (a null pointer stages nothing)
+  st.in(&a.m0, params->m0, params->m0_stride ? (n - 1) * (size_t)params->m0_stride + dd : dd);
+  st.in(&a.C0, params->C0, params->c0_stride ? (n - 1) * (size_t)params->c0_stride + dd * dd : dd * dd);
+  st.in(&a.prior_v, lw->learn_v ? prior_v : nullptr, prior_v_stride ? (n - 1) * (size_t)prior_v_stride + 2 : 2);
+  st.in(&a.prior_w, prior_w, prior_w_stride ? (n - 1) * (size_t)prior_w_stride + 2 * dd : 2 * dd);
+  st.in(&a.obs_param, obs_param, obs_param ? n : 0);
+  st.in(&a.y, y, n * t);
+  st.out(&a.ll, ll, n);
+  st.out(&a.mean, mean, mean ? n * t * dd : 0);
+  st.out(&a.ess, ess, ess ? n * t : 0);
+  st.out(&a.psi_mean, psi_mean, psi_mean ? n * t * (dd + 1) : 0);
+  st.out(&a.psi_var, psi_var, psi_var ? n * t * (dd + 1) : 0);
+  st.out(&a.cloud, cloud, cloud ? n * dd * np : 0);
+  st.out(&a.weights, weights, weights ? n * np : 0);
+  st.out(&a.psi, psi, psi ? n * (dd + 1) * np : 0);
+  st.zeroed_out(&a.status, (int*)status, status ? n : 0);
+  if ((rc = st.commit())) return rc;
+  a.d = d; a.T = T; a.N = N; a.P = P;
+  a.family = lw->family; a.literal = lw->literal; a.learn_v = lw->learn_v; a.a = lw->a;
+  a.n0 = lw->n0 < 0 ? P / 5 : lw->n0;
+  a.f_stride = model->f_stride; a.n_g = model->n_g;
+  a.v_stride = params->v_stride; a.m0_stride = params->m0_stride; a.c0_stride = params->c0_stride;
+  a.prior_v_stride = prior_v_stride; a.prior_w_stride = prior_w_stride;
+  a.rs = draw_stream(opts, iteration);
+  e->variant = "lw-wave";
+  HIP_TRY(e, dlm::launch_lw(a, e->stream));
+  return st.finish(opts->flags & DLM_OPT_ASYNC);
+}
+
 static int ar1_common(dlm_engine* e, int32_t N, int32_t T, const double* times, bool ou, const double* y, const double* v,
                       int64_t v_stride, const double* sv, int64_t sv_stride, const double* z, const dlm_options* opts,
                       double* filt, double* theta, int32_t* status);

@@ -1,6 +1,6 @@
-"""Dynamic generalised linear models, the bootstrap particle filter, the particle-marginal Metropolis sampler built on it and the
-Storvik filter, which learns the variances online (the reference's Dglm.scala, ParticleFilter.scala, Metropolis.dglm,
-MetropolisHastings.scala:142-154, and Storvik.scala).
+"""Dynamic generalised linear models, the bootstrap particle filter, the particle-marginal Metropolis sampler built on it, the
+Storvik filter, which learns the variances online, and the Liu-West and auxiliary particle filters (the reference's Dglm.scala,
+ParticleFilter.scala, Metropolis.dglm, MetropolisHastings.scala:142-154, Storvik.scala, LiuAndWest.scala and AuxFilter.scala).
 
 A `Dglm` is a `Dlm` with one of six observation models for its scalar observation; V(0, 0) = v is what each family makes of it
 (include/dlm_engine.h, dlm_pf_batch).  `ParticleFilter(n, n0).filter` runs the engine's filter for one series or a batch of them, with one
@@ -279,6 +279,74 @@ class StorvikFilter:
             out["w_mean"] = np.where(out["shape_w"] > 1.0, out["scale_mean"][:, :, :d] / (out["shape_w"] - 1.0), np.nan)
             out["v_mean"] = np.where(out["shape_v"] > 1.0, out["scale_mean"][:, :, d] / (out["shape_v"] - 1.0), np.nan)
         return out
+
+
+class LiuAndWestFilter:
+    """LiuAndWestFilter(n, prior, a, n0) (LiuAndWest.scala:26-82; Liu & West 2001) on the engine (dlm_lw_batch): an auxiliary particle
+    filter whose particles carry their own log-variances -- the diagonal of W, and V for the Gaussian, Student-t and Beta families --
+    shrunk towards their weighted mean by `a` and jittered with the kernel variance (1 - a^2) s^2 at every step.  It needs no conjugacy;
+    for a < 1 it is an approximation.  The priors are independent `stochvol.Gaussian`s on the LOG-variances (the reference draws the
+    variances from a Rand[DlmParameters] and takes logs); the reference's other departures are DESIGN.md 2, Q49-Q56."""
+
+    def __init__(self, n: int, a: float, n0: int = -1):
+        check_pf_shape(1, 1, int(n))
+        if not 0.0 < float(a) <= 1.0:
+            raise ValueError(f"the shrinkage a must satisfy 0 < a <= 1, got {a!r}")
+        self.n, self.a, self.n0 = int(n), float(a), int(n0)
+
+    def filter(self, mod: Dglm, ys, p: DlmParameters, prior_v, prior_w, eng, *, learn_v: Optional[bool] = None, seed: int = 0,
+               iteration: int = 0, series_offset: int = 0, literal: bool = False):
+        """ys as ParticleFilter.filter takes them; p: m0 and C0 of the initial cloud (and V when it is not learned; p.w is not read);
+        prior_v a Gaussian(mean, sd) on log V (None when V is not learned), prior_w one Gaussian on log W_kk for every component or d of
+        them; sd = 0 is a known variance.  learn_v defaults to "the family is Gaussian, Student-t or Beta".  Returns what
+        ParticleFilter.filter returns plus the raw "psi_mean" and "psi_var" [N][T][d+1] (mean and variance of the log-variances under the
+        weights of step t, V's last), "psi" [N][d+1][n], and the posterior means of the variances from the log-normal moments,
+        "w_mean" [N][T][d] = exp(psi_mean + psi_var / 2) and "v_mean" [N][T] (NaN where V is not learned)."""
+        times, y = _observations(ys)
+        f0 = np.atleast_2d(np.asarray(mod.f(float(times[0])), dtype=np.float64))
+        d = f0.shape[0]
+        check_pf_shape(d, f0.shape[1], self.n)
+        mat = materialise_pf(mod, times)
+        learn_v = mod.family in (_lib.OBS_GAUSSIAN, _lib.OBS_STUDENTT, _lib.OBS_BETA) if learn_v is None else bool(learn_v)
+        pws = [prior_w] * d if hasattr(prior_w, "mean") and hasattr(prior_w, "sd") else list(prior_w)
+        if len(pws) != d:
+            raise EngineError(f"prior_w: one Gaussian or d = {d} of them, got {len(pws)}")
+        pw = np.array([[q.mean, q.sd] for q in pws], dtype=np.float64)
+        pv = np.array([prior_v.mean, prior_v.sd], dtype=np.float64) if learn_v else None
+        out = eng.lw_filter(mat, p, y, pw, family=mod.family, n_particles=self.n, a=self.a, prior_v=pv, learn_v=learn_v, n0=self.n0,
+                            literal=literal, obs_param=mod.nu, iteration=iteration, seed=seed, series_offset=series_offset)
+        out = {k: None if v is None else np.asarray(v) for k, v in out.items()}
+        with np.errstate(invalid="ignore", over="ignore"):
+            moments = np.exp(out["psi_mean"] + out["psi_var"] / 2.0)
+        out["w_mean"], out["v_mean"] = moments[:, :, :d], moments[:, :, d]
+        return out
+
+
+class AuxFilter:
+    """AuxFilter(n) (AuxFilter.scala:12-66; Pitt & Shephard 1999) on the engine: the auxiliary particle filter for KNOWN parameters, which
+    is dlm_lw_batch with a = 1, prior standard deviations of 0 and means log diag(W); V is p.v.  Unlike the reference's, its second stage
+    divides by the first-stage density, resamples only when ESS < n0 and carries its weights otherwise, and its likelihood counts both
+    stages: exp(ll) is unbiased for p(y_1:T), so `likelihood` can stand in for ParticleFilter.likelihood."""
+
+    def __init__(self, n: int, n0: int = -1):
+        check_pf_shape(1, 1, int(n))
+        self.n, self.n0 = int(n), int(n0)
+
+    def filter(self, mod: Dglm, ys, p: DlmParameters, eng, *, seed: int = 0, iteration: int = 0, series_offset: int = 0,
+               literal: bool = False):
+        """ys as ParticleFilter.filter takes them; p: one DlmParameters with a DIAGONAL W (ValueError otherwise).  Returns what
+        LiuAndWestFilter.filter returns."""
+        w = np.atleast_2d(np.asarray(p.w, dtype=np.float64))
+        if np.any(w != np.diag(np.diag(w))):
+            raise ValueError("AuxFilter takes a diagonal W: the kernel's state noise is independent by component")
+        from .stochvol import Gaussian
+        prior_w = [Gaussian(float(np.log(v)), 0.0) for v in np.diag(w)]
+        return LiuAndWestFilter(self.n, 1.0, self.n0).filter(mod, ys, p, None, prior_w, eng, learn_v=False, seed=seed, iteration=iteration,
+                                                             series_offset=series_offset, literal=literal)
+
+    def likelihood(self, mod: Dglm, ys, p: DlmParameters, eng, **kw):
+        """AuxFilter.likelihood(mod, ys, n)(p) (AuxFilter.scala:69-75): the log-likelihood estimate of every series."""
+        return self.filter(mod, ys, p, eng, **kw)["ll"]
 
 
 INIT_ITERATION = 0xFFFFFFFF   # the Philox iteration of Metropolis.dglm's evaluation of the initial parameters

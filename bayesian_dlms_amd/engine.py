@@ -657,6 +657,73 @@ class Engine:
         return {"ll": ll, "mean": mean, "ess": ess, "scale_mean": scale_mean, "cloud": cloud, "weights": weights, "scales": scales,
                 "status": status}
 
+    def lw_filter(self, mat, params, y, prior_w, *, family, n_particles, a, prior_v=None, learn_v=None, n0=-1, literal=False,
+                  obs_param=None, iteration=0, seed=0, series_offset=0, flags=0, want_mean=True, want_ess=True, want_psi_mean=True,
+                  want_psi_var=True, want_cloud=True, want_weights=True, want_psi=True):
+        """Liu-West filter of a dynamic generalised linear model (dlm_lw_batch; LiuAndWestFilter.step, LiuAndWest.scala:47-81): an auxiliary
+        particle filter whose particles carry their own log-variances -- log W_kk, and with learn_v (default: the family is Gaussian,
+        Student-t or Beta) log V -- shrunk by `a` (0 < a <= 1) and jittered at every step.  prior_w: (mean, sd) of log W_kk per component,
+        [d][2] shared or [N][d][2] per series; prior_v: [2] or [N][2] (needed with learn_v); sd = 0: a known variance.  params as in
+        particle_filter: its W is not read, its V only without learn_v.  literal=True: Q39, Q50 and Q51.
+        Returns {"ll" [N], "mean" [N][T][d], "ess" [N][T], "psi_mean" [N][T][d+1], "psi_var" [N][T][d+1], "cloud" [N][d][P],
+        "weights" [N][P], "psi" [N][d+1][P], "status" [N]}; the optional ones are None when not wanted, the entries d of psi_mean, psi_var
+        and psi NaN without learn_v."""
+        be = self._backend(y)
+        d, T = mat.d, mat.T
+        P = int(n_particles)
+        check_pf_shape(d, mat.p, P)
+        if family not in range(6):
+            raise EngineError(f"family must be one of _lib.OBS_* (0..5), got {family!r}")
+        scale_family = family in (_lib.OBS_GAUSSIAN, _lib.OBS_STUDENTT, _lib.OBS_BETA)
+        learn_v = scale_family if learn_v is None else bool(learn_v)
+        if learn_v and not scale_family:
+            raise EngineError("learn_v needs OBS_GAUSSIAN, OBS_STUDENTT or OBS_BETA: the families whose v is a positive scale")
+        if learn_v and prior_v is None:
+            raise EngineError("learn_v needs prior_v = (mean, sd) of log V")
+        if not 0.0 < float(a) <= 1.0:
+            raise EngineError(f"the shrinkage a must satisfy 0 < a <= 1, got {a!r}")
+        N = int(y.shape[0])
+        if tuple(y.shape) not in ((N, T), (N, T, 1)):
+            raise EngineError(f"y must be [N][T] = {(N, T)}, got {tuple(y.shape)}")
+        yb = be.put(y).reshape(N, T)
+        if family == _lib.OBS_STUDENTT and obs_param is None:
+            raise EngineError("OBS_STUDENTT needs obs_param: the degrees of freedom (a scalar or one per series)")
+        ob = None
+        if obs_param is not None:
+            ob = be.put(np.full(N, float(obs_param)) if np.ndim(obs_param) == 0 else obs_param)
+            if tuple(ob.shape) != (N,):
+                raise EngineError(f"obs_param must be a scalar or [N] = {(N,)}, got {tuple(ob.shape)}")
+        pw = np.ascontiguousarray(prior_w, dtype=np.float64)
+        if pw.shape not in ((d, 2), (N, d, 2)):
+            raise EngineError(f"prior_w must be [d][2] = {(d, 2)} or [N][d][2], got {pw.shape}")
+        pw_stride = 2 * d if pw.ndim == 3 else 0
+        pv, pv_stride = None, 0
+        if learn_v:
+            pv = np.ascontiguousarray(prior_v, dtype=np.float64)
+            if pv.shape not in ((2,), (N, 2)):
+                raise EngineError(f"prior_v must be [2] or [N][2], got {pv.shape}")
+            pv_stride = 2 if pv.ndim == 2 else 0
+        pwb, pvb = be.put(pw), be.put(pv)
+        md, pd, op, keep = self.prepare(mat, params, N, be, flags, seed, series_offset)
+        if pd.v_tstride and not learn_v:
+            raise EngineError("the Liu-West filter takes a time-invariant V")
+        ll = be.empty((N,))
+        mean = be.empty((N, T, d)) if want_mean else None
+        ess = be.empty((N, T)) if want_ess else None
+        psi_mean = be.empty((N, T, d + 1)) if want_psi_mean else None
+        psi_var = be.empty((N, T, d + 1)) if want_psi_var else None
+        cloud = be.empty((N, d, P)) if want_cloud else None
+        weights = be.empty((N, P)) if want_weights else None
+        psi = be.empty((N, d + 1, P)) if want_psi else None
+        status = be.empty((N,), np.int32)
+        desc = _lib.LwDesc(int(family), P, int(n0), 1 if literal else 0, 1 if learn_v else 0, float(a))
+        self._hold(flags, yb, ob, pwb, pvb)
+        self._check(self.lib.dlm_lw_batch(self.h, md, pd, ctypes.byref(desc), be.ptr(pvb), pv_stride, be.ptr(pwb), pw_stride, be.ptr(ob),
+                                          be.ptr(yb), int(iteration), op, be.ptr(ll), be.ptr(mean), be.ptr(ess), be.ptr(psi_mean),
+                                          be.ptr(psi_var), be.ptr(cloud), be.ptr(weights), be.ptr(psi), be.ptr(status)))
+        return {"ll": ll, "mean": mean, "ess": ess, "psi_mean": psi_mean, "psi_var": psi_var, "cloud": cloud, "weights": weights,
+                "psi": psi, "status": status}
+
     def simulate(self, mat, params, N, *, seed=0, series_offset=0, device=False, want_x=True):
         """Dlm.simulateRegular over the model's time grid for N series (dlm_simulate_batch): (x [N][T+1][d], y [N][T][p])."""
         be = _Device(self.device) if device else _Host()

@@ -598,6 +598,55 @@ int dlm_storvik_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_para
                       const double* obs_param, const double* y, uint64_t iteration, const dlm_options* opts, double* ll, double* mean,
                       double* ess, double* scale_mean, double* cloud, double* weights, double* scales, int32_t* status);
 
+/* Liu-West filter of a dynamic generalised linear model (LiuAndWestFilter.step, LiuAndWest.scala:47-81; Liu & West 2001), and with a = 1 and
+ * prior standard deviations of 0 the auxiliary particle filter for known parameters (AuxFilter.step, AuxFilter.scala:18-56): an auxiliary
+ * particle filter whose particles carry their own LOG-VARIANCES psi_k,i -- k < d: log W_kk (W is diagonal, params->W is never read); k = d
+ * with lw->learn_v = 1: log V.  learn_v is allowed for DLM_OBS_GAUSSIAN, DLM_OBS_STUDENTT and DLM_OBS_BETA, where v is a positive scale; any
+ * other family with learn_v is DLM_ERR_ARG.  With learn_v = 0 V is params->V as in dlm_pf_batch and prior_v is not read.  The priors are
+ * independent Gaussians on the log-variances: prior_w [d][2] = (mean, sd) of log W_kk, prior_v [2] = (mean, sd) of log V; prior_v_stride /
+ * prior_w_stride: doubles between the priors of consecutive series, 0 = one prior for the batch.  sd = 0 makes the row a KNOWN variance
+ * exp(mean): it is neither shrunk nor jittered and takes no draws.  lw->a is the shrinkage, 0 < a <= 1 (anything else, NaN included, is
+ * DLM_ERR_ARG); h = sqrt(1 - a^2).  Shapes and limits as dlm_pf_batch, except the LDS: (2 d + 3.5) P + d^2 + d + 1 doubles, which d = 16 with
+ * P <= 512 and d <= 8 with P = 1024 are granted on a device with 160 KB per workgroup; more is DLM_ERR_UNSUPPORTED (d = 16, P = 1024).
+ *   x_0,i = m0 + chol(C0) z,   psi_k,i = mean_k + sd_k z',   W_{-1,i} = 1 / P.   Per step t, the learned rows being those with sd > 0:
+ *   a missing y_t:  x'_k,i = (G_t x_i)_k + sqrt(dt_t exp psi_k,i) z_k,i (dt_t == 0: nothing, Q40); psi and the weights are carried, the outputs
+ *               are written under the carried weights, the ESS repeats (the reference has no such branch, Q49).  Otherwise
+ *   moments:    pbar_k = sum_i W_{t-1,i} psi_k,i,  s2_k = sum_i W_{t-1,i} (psi_k,i - pbar_k)^2;
+ *   look-ahead: m_k,i = a psi_k,i + (1 - a) pbar_k,  mu_i = G_t x_i (dt_t == 0: x_i),  lambda_i = log p(y_t | F_t^T mu_i, exp m_d,i or V);
+ *   stage 1:    omega_i = W_{t-1,i} exp(lambda_i - max lambda),  A = sum omega,  ll += max lambda + log A;  ALWAYS resampled: new particle j is a copy
+ *               (x, m, lambda) of the first k whose inclusive cumulative omega exceeds u_j times the last one;
+ *   propagate:  psi'_r,j = m_r,k + h sqrt(s2_r) z'_r,j,  x'_r,j = mu_r,k + sqrt(dt_t exp psi'_r,j) z_r,j (the state noise uses the NEW variances),
+ *               l_j = log p(y_t | F_t^T x'_j, exp psi'_d,j or V) - lambda_k;
+ *   stage 2:    m2 = max l,  w_j = exp(l_j - m2),  B = sum w,  ll += m2 + log(B / P),  W_t,j = w_j / B,  ESS = floor(1 / sum W_t,j^2);
+ *               ESS < n0: multinomial resampling as in dlm_pf_batch of the WHOLE tuple (x_j, psi_.,j), W_t,j = 1 / P.
+ * lw->n0 < 0 stands for floor(P / 5).  lw->literal = 1: s2_k is the unweighted n - 1 variance about the unweighted mean, whatever the weights
+ * (varParameters, LiuAndWest.scala:51, Q50); l_j is not reduced by lambda_k (AuxFilter.scala:46, Q51); the Student-t normaliser is Q39's.
+ * ll estimates log p(y_1:T) -- for a = 1 without bias on the natural scale, the variances integrated over their priors (the reference's
+ * Liu-West filter accumulates no likelihood); for a < 1 the filter is an approximation.
+ * Outputs: ll [N]; mean [N][T][d], ess [N][T], cloud [N][d][P], weights [N][P] (nullable) as dlm_pf_batch; psi_mean, psi_var [N][T][d+1]
+ * (nullable): sum_j W_t,j psi'_k,j and sum_j W_t,j (psi'_k,j - psi_mean)^2, before the second stage's resampling; psi [N][d+1][P] (nullable)
+ * the rows of psi after the last step.  Without learn_v the entries k = d are NaN.  status [N] (nullable): DLM_ST_NOT_PD for a chol(C0) that
+ * fails, a prior sd that is negative or NaN or a prior mean that is not finite; DLM_ST_NONFINITE when a maximum is not finite or A or B is
+ * not positive and finite; such a series has ll = -inf, NaN in mean, psi_mean, psi_var and ess from the failing step on and in weights and
+ * psi, and its neighbours are untouched.
+ * Draws: the streams DLM_KEY_LW (dlm_draws.h): a pure function of (opts->seed, opts->series_offset + n, iteration, t or the initial slot,
+ * particle, block), block = a pair of state normals, the uniform of either stage, or a pair of the d + 1 log-variance normals.  Every sum
+ * runs in a fixed order without atomics.
+ * opts: mem, seed, series_offset, DLM_OPT_ASYNC.  Like dlm_pf_batch the call does not count as the "previous model-taking call" of
+ * DLM_OPT_MODEL_UNCHANGED. */
+typedef struct {
+  int32_t family;       /* DLM_OBS_*                                                   */
+  int32_t n_particles;  /* P                                                           */
+  int32_t n0;           /* the second stage resamples when ESS < n0; < 0: floor(P / 5) */
+  int32_t literal;      /* 1: the reference's arithmetic, Q39, Q50 and Q51             */
+  int32_t learn_v;      /* 1: log V is learned too (Gaussian, Student-t, Beta)         */
+  double a;             /* the shrinkage, 0 < a <= 1                                   */
+} dlm_lw_desc;
+int dlm_lw_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_params_desc* params, const dlm_lw_desc* lw,
+                 const double* prior_v, int64_t prior_v_stride, const double* prior_w, int64_t prior_w_stride,
+                 const double* obs_param, const double* y, uint64_t iteration, const dlm_options* opts, double* ll, double* mean,
+                 double* ess, double* psi_mean, double* psi_var, double* cloud, double* weights, double* psi, int32_t* status);
+
 /* Per-series log-likelihood by the prediction-error decomposition,
  *   loglik[n] = sum_t log N(y_t^obs ; f_t^obs, Q_t^obs),
  * i.e. KalmanFilter.conditionalLikelihood (KalmanFilter.scala:138-153) summed over the series (steps with no observed

@@ -389,6 +389,20 @@ JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_storvikFilter(JNI
                                           ptr<const double>(obsParam), ptr<const double>(y), static_cast<uint64_t>(iteration), &d.o, ptr<double>(ll), ptr<double>(mean), ptr<double>(ess),
                                           ptr<double>(scaleMean), ptr<double>(cloud), ptr<double>(weights), ptr<double>(scales), ptr<int32_t>(status)));
 }
+// ---- Liu-West filter of a dynamic generalised linear model (LiuAndWest.scala:47-81; with a = 1 and prior sds of 0 the auxiliary particle filter of AuxFilter.scala): every particle carries its own
+// log-variances, Gaussian priors on them: priorV [2] = (mean, sd) of log V, priorW [d][2] of log W_kk, strides in doubles (0: one prior for the batch).  dlm_lw_desc crosses as scalars in its field
+// order; psiMean, psiVar [N][T][d+1] and psi [N][d+1][nParticles] are optional (0) like the outputs of particleFilter.
+JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_lwFilter(JNIEnv* env, jobject, jlong h, jlongArray model, jlongArray params, jlongArray opts, jint family, jint nParticles, jint n0,
+                                                                        jint literal, jint learnV, jdouble a, jlong priorV, jlong priorVStride, jlong priorW, jlong priorWStride, jlong obsParam, jlong y,
+                                                                        jlong iteration, jlong ll, jlong mean, jlong ess, jlong psiMean, jlong psiVar, jlong cloud, jlong weights, jlong psi,
+                                                                        jlong status) {
+  Desc d;
+  if (!read_desc(env, model, params, opts, d)) return;
+  const dlm_lw_desc lw{family, nParticles, n0, literal, learnV, a};
+  throw_if(env, eng(h), dlm_lw_batch(eng(h), &d.m, &d.q, &lw, ptr<const double>(priorV), static_cast<int64_t>(priorVStride), ptr<const double>(priorW), static_cast<int64_t>(priorWStride),
+                                     ptr<const double>(obsParam), ptr<const double>(y), static_cast<uint64_t>(iteration), &d.o, ptr<double>(ll), ptr<double>(mean), ptr<double>(ess),
+                                     ptr<double>(psiMean), ptr<double>(psiVar), ptr<double>(cloud), ptr<double>(weights), ptr<double>(psi), ptr<int32_t>(status)));
+}
 // ---- pooled-parameter Gibbs: reduce over series, then over GPUs (RCCL) ---------------------------------------------------------------
 JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_statsPool(JNIEnv* env, jobject, jlong h, jlong stats, jint n, jint l, jlong pooled, jlongArray opts) {
   dlm_options o{};

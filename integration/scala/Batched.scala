@@ -88,6 +88,8 @@ final class Native private[gpu] () {
   @native def particleFilter(h: Long, model: Array[Long], params: Array[Long], opts: Array[Long], family: Int, nParticles: Int, n0: Int, literal: Int, obsParam: Long, y: Long, iteration: Long, ll: Long, mean: Long, ess: Long, cloud: Long, weights: Long, status: Long): Unit
   /** Storvik filter of a DGLM (StorvikFilter.filterTs): the particle filter above with the diagonal of W -- and with learnV = 1 (Gaussian family only) V -- learned online from InverseGamma priors, priorV [2] = (shape, scale) and priorW [d][2] (strides in doubles, 0: one prior for the batch); params' W is not read, its V only with learnV = 0; literal = 1: Q39 and Q43.  ll [N] estimates the evidence; scaleMean [N][T][d+1] (the weighted means of the statistics' scales: divided by shape - 1 the posterior means of the variances) and scales [N][d+1][nParticles] are optional (0) like mean, ess, cloud, weights and status */
   @native def storvikFilter(h: Long, model: Array[Long], params: Array[Long], opts: Array[Long], family: Int, nParticles: Int, n0: Int, literal: Int, learnV: Int, priorV: Long, priorVStride: Long, priorW: Long, priorWStride: Long, obsParam: Long, y: Long, iteration: Long, ll: Long, mean: Long, ess: Long, scaleMean: Long, cloud: Long, weights: Long, scales: Long, status: Long): Unit
+  /** Liu-West filter of a DGLM (LiuAndWestFilter.step; with a = 1 and prior sds of 0 the auxiliary particle filter of AuxFilter.step): every particle carries its own log-variances, the diagonal of W and with learnV = 1 (Gaussian, Student-t, Beta) V, under Gaussian priors priorV [2] = (mean, sd) of log V and priorW [d][2] of log W_kk (strides in doubles, 0: one prior for the batch; sd = 0: a known variance); a the shrinkage, 0 < a <= 1; literal = 1: Q39, Q50 and Q51.  ll [N]; psiMean, psiVar [N][T][d+1] (mean and variance of the log-variances at every time) and psi [N][d+1][nParticles] are optional (0) like mean, ess, cloud, weights and status */
+  @native def lwFilter(h: Long, model: Array[Long], params: Array[Long], opts: Array[Long], family: Int, nParticles: Int, n0: Int, literal: Int, learnV: Int, a: Double, priorV: Long, priorVStride: Long, priorW: Long, priorWStride: Long, obsParam: Long, y: Long, iteration: Long, ll: Long, mean: Long, ess: Long, psiMean: Long, psiVar: Long, cloud: Long, weights: Long, psi: Long, status: Long): Unit
   @native def statsPool(h: Long, stats: Long, n: Int, l: Int, pooled: Long, opts: Array[Long]): Unit
   @native def commUniqueId(): Array[Byte]
   @native def commInitRank(h: Long, nranks: Int, rank: Int, id: Array[Byte]): Unit
