@@ -18,7 +18,6 @@ import lw_restatement as lr
 import pf_cases as pc
 import pf_restatement as pr
 import storvik_cases as sc
-from bayesian_dlms_amd.dglm import Dglm
 
 SCALE_FAMILIES = (pr.GAUSSIAN, pr.STUDENTT, pr.BETA)
 PRIOR_SD = 0.5          # of every log-variance of the table
@@ -63,49 +62,18 @@ def inputs(name):
     """The arrays of a table entry: what the restatement takes, and through `engine_run` the engine.  The data are simulated from the model
     at the variances the priors are centred on."""
     c = by_name(name)
-    rng = np.random.default_rng(5000 + c["seed"] * 7919 + sum(map(ord, name)))
-    d, T, N, fam = c["d"], c["T"], c["N"], c["family"]
-    G0, Wfull, F = pc.dense_model(d, rng)
-    Wd = np.diag(Wfull).copy()
-    if c["irregular"]:
-        steps = np.array([0.0] + [(1.0, 0.5, 2.0)[k % 3] for k in range(1, T)])
-        steps[T // 2] = 0.0                     # one more dt = 0, inside the series
-        gi = np.array([0] + [k % 3 for k in range(1, T)], dtype=np.int32)
-        G = np.stack([G0, 0.95 * G0 @ G0.T @ G0, 0.8 * G0 @ G0])
-        dt = steps
-    else:
-        G, gi, dt = G0[None], None, np.array([c["dt0"]] + [1.0] * (T - 1))
-    level = pc.FAMILY_LEVEL[fam]
-    shift = np.zeros(d); shift[0] = level / F[0]
-    m0 = rng.standard_normal(d) * 0.3
-    C0 = 0.5 * Wfull + 0.2 * np.eye(d)
-    V = pc.FAMILY_V[fam] * c["v_scale"]
-    sd = np.full(d + 1, PRIOR_SD)
-    sd[list(range(d + 1)) if c["sd0"] == "all" else list(c["sd0"])] = 0.0
-    prior_w = np.stack([np.log(Wd), sd[:d]], axis=1)          # [d][2] = (mean, sd) of log W_kk
-    prior_v = np.array([np.log(V), sd[d]]) if c["learn_v"] else None
-    if c["per_series"]:
-        scale = np.exp(0.3 * rng.standard_normal(N))
-        C0n = C0[None] * scale[::-1, None, None]
-        m0n = m0[None] + 0.2 * rng.standard_normal((N, d))
-        prior_w = prior_w[None] + np.stack([np.log(scale), 0.05 * (np.arange(N) % 4)], axis=1)[:, None, :]
-        prior_v = prior_v[None] + np.stack([np.log(scale[::-1]), 0.1 * (np.arange(N) % 3)], axis=1)
-        Vn = np.full(N, V)
-    else:
-        C0n, m0n, Vn = C0, m0, V
-    mod = Dglm(lambda t: F[:, None], lambda s: G0, fam, 5.0 if fam == pr.STUDENTT else None)
-    y = np.empty((N, T))
-    Lw = np.sqrt(Wd)
-    for n in range(N):
-        x = (m0n[n] if c["per_series"] else m0) + shift + np.linalg.cholesky(C0n[n] if c["per_series"] else C0) @ rng.standard_normal(d)
-        for t in range(T):
-            if dt[t] != 0.0:
-                x = G[0 if gi is None else gi[t]] @ x + np.sqrt(dt[t]) * (Lw * rng.standard_normal(d))
-            y[n, t] = mod.observation(float(F @ x), float(V), rng)
-    for t in c["missing"]:
-        y[:, t] = np.nan
-    nu = 5.0 + np.arange(N) if fam == pr.STUDENTT else None
-    return dict(F=F, G=G, g_index=gi, dt=dt, V=Vn, W=np.diag(Wd), m0=m0n + shift, C0=C0n, y=y, nu=nu, prior_w=prior_w, prior_v=prior_v)
+
+    def priors(d, Wd, V, N, scale):
+        sd = np.full(d + 1, PRIOR_SD)
+        sd[list(range(d + 1)) if c["sd0"] == "all" else list(c["sd0"])] = 0.0
+        prior_w = np.stack([np.log(Wd), sd[:d]], axis=1)          # [d][2] = (mean, sd) of log W_kk
+        prior_v = np.array([np.log(V), sd[d]]) if c["learn_v"] else None
+        if scale is not None:
+            prior_w = prior_w[None] + np.stack([np.log(scale), 0.05 * (np.arange(N) % 4)], axis=1)[:, None, :]
+            prior_v = prior_v[None] + np.stack([np.log(scale[::-1]), 0.1 * (np.arange(N) % 3)], axis=1)
+        return prior_w, prior_v
+
+    return pc.learner_inputs(c, 5000, priors, c["dt0"])
 
 
 def run_args(name, **over):

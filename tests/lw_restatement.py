@@ -1,6 +1,6 @@
 """NumPy restatement of the Liu-West filter kernel (bayesian_dlms_amd/csrc/dlm_lw.hip, dlm_lw_batch), operation for operation and in the
 kernel's orders of summation, vectorised over the series of a batch.  The sums over the particles, the running sums of
-the two resampling searches, the Cholesky factor, the densities and Philox are tests/pf_restatement.py's, by import.
+the two resampling searches, the Cholesky factor, the densities, Philox and the addressing of the draws are tests/pf_restatement.py's, by import.
 
 The draws: Philox4x32-10 under the key DLM_KEY_LW | block (dlm_draws.h), counter (series, iteration, slot * 2048 + particle * 2): block
 q < 8 the Box-Muller pair of the state components 2 q and 2 q + 1, block 8 the uniform of the second stage's resampling, block 9 the uniform
@@ -12,33 +12,12 @@ margin_n0 and margin_int as tests/pf_restatement.py defines them, and the share 
 always does)."""
 import numpy as np
 
-from pf_restatement import (BETA, GAUSSIAN, ST_NONFINITE, ST_NOT_PD, STUDENTT, TWO_PI, _per_series, cholesky, log_density,  # noqa: F401
-                            matvec_lower, particle_sum, running_sums)
-from sampler_restatement import MASK, philox
+from pf_restatement import (BETA, GAUSSIAN, ST_NONFINITE, ST_NOT_PD, STUDENTT, _per_series, batch_rand, cholesky, log_density,  # noqa: F401
+                            matvec_lower, normal, particle_sum, running_sums)
 
 KEY_LW = 0x4C570000
 BLOCK_RESAMPLE, BLOCK_FIRST, BLOCK_PARAM = 8, 9, 10
 SLOT_INIT = 0x1FFFFF
-
-
-def lw_rand(seed, series, it, slot, P, block):
-    """series [n] -> (u1 in (0, 1], u2 in [0, 1)), each [n][P]."""
-    series = np.asarray(series, dtype=np.uint64)[:, None]
-    word = (np.uint64(slot) * np.uint64(2048) + np.arange(P, dtype=np.uint64) * np.uint64(2))[None, :] & MASK
-    z = np.zeros((series.shape[0], P), dtype=np.uint64)
-    c = philox(z + (series & MASK), z + (series >> np.uint64(32)), z + np.uint64(it & 0xFFFFFFFF), z + word,
-               seed & 0xFFFFFFFF, ((seed >> 32) & 0xFFFFFFFF) ^ (KEY_LW | block))
-    f = [x.astype(np.float64) for x in c]
-    u1 = (f[0] * 4294967296.0 + f[1] + 1.0) * (1.0 / 18446744073709551616.0)
-    u2 = (f[2] * 4294967296.0 + f[3]) * (1.0 / 18446744073709551616.0)
-    return u1, u2
-
-
-def normal(seed, series, it, slot, P, base, r):
-    """z_r [len(series)][P] of the group of blocks that starts at base: block base + r // 2, the cosine for an even r, the sine for an odd one."""
-    u1, u2 = lw_rand(seed, series, it, slot, P, base + (r >> 1))
-    rad, ang = np.sqrt(-2.0 * np.log(u1)), TWO_PI * u2
-    return rad * (np.sin(ang) if r & 1 else np.cos(ang))
 
 
 def moments(row, wg):
@@ -108,11 +87,11 @@ def run(*, F, G, g_index, dt, V, m0, C0, y, family, P, a, prior_w, prior_v=None,
     alive = ok0.copy()
     learned = pr[:, :, 1] > 0.0          # [N][rows]
     with np.errstate(all="ignore"):
-        z = np.stack([normal(seed, series, iteration, SLOT_INIT, P, 0, c) for c in range(d)], axis=1)
+        z = np.stack([normal(KEY_LW, seed, series, iteration, SLOT_INIT, P, 0, c) for c in range(d)], axis=1)
         x = m0[:, :, None] + matvec_lower(L0, z)
         psi = np.empty((N, rows, P))
         for r in range(rows):
-            zp = normal(seed, series, iteration, SLOT_INIT, P, BLOCK_PARAM, r) if learned[:, r].any() else 0.0
+            zp = normal(KEY_LW, seed, series, iteration, SLOT_INIT, P, BLOCK_PARAM, r) if learned[:, r].any() else 0.0
             psi[:, r] = np.where(learned[:, r, None], pr[:, r, 0, None] + pr[:, r, 1, None] * zp, pr[:, r, 0, None])
     wg = np.full((N, P), rP)
     hs = np.zeros((N, rows))
@@ -155,7 +134,7 @@ def run(*, F, G, g_index, dt, V, m0, C0, y, family, P, a, prior_w, prior_v=None,
                 if adv:
                     xn = x.copy()
                     for r in range(d):
-                        xn[:, r] = Gx(Gt, x, r) + np.sqrt(dte * np.exp(psi[:, r])) * normal(seed, series, iteration, t, P, 0, r)
+                        xn[:, r] = Gx(Gt, x, r) + np.sqrt(dte * np.exp(psi[:, r])) * normal(KEY_LW, seed, series, iteration, t, P, 0, r)
                     x = np.where(mis[:, None, None], xn, x)
                 outputs(t, mis)
                 ess[mis, t] = ess_last[mis]
@@ -192,7 +171,7 @@ def run(*, F, G, g_index, dt, V, m0, C0, y, family, P, a, prior_w, prior_v=None,
                 continue
             ll = np.where(obs, ll + (m1 + np.log(A)), ll)
             cum = running_sums(om)
-            _, u2 = lw_rand(seed, series, iteration, t, P, BLOCK_FIRST)
+            _, u2 = batch_rand(KEY_LW | BLOCK_FIRST, seed, series, iteration, t, P)
             target = u2 * cum[:, P - 1, None]
             anc = ancestors(cum, target, obs, mg)
             lam_anc = np.take_along_axis(lam, anc, axis=1)
@@ -204,11 +183,11 @@ def run(*, F, G, g_index, dt, V, m0, C0, y, family, P, a, prior_w, prior_v=None,
             eta = None
             for r in range(rows):
                 if learned[:, r].any():          # (a row nobody learns takes no draw: the kernel draws none, and Philox is what this file's time goes to)
-                    zp = normal(seed, series, iteration, t, P, BLOCK_PARAM, r)
+                    zp = normal(KEY_LW, seed, series, iteration, t, P, BLOCK_PARAM, r)
                     pn[:, r] = np.where(learned[:, r, None], psi[:, r] + hs[:, r, None] * zp, psi[:, r])
                 if r < d:
                     if adv:
-                        xn[:, r] = Gx(Gt, x, r) + np.sqrt(dte * np.exp(pn[:, r])) * normal(seed, series, iteration, t, P, 0, r)
+                        xn[:, r] = Gx(Gt, x, r) + np.sqrt(dte * np.exp(pn[:, r])) * normal(KEY_LW, seed, series, iteration, t, P, 0, r)
                     eta = Ft[0] * xn[:, r] if r == 0 else eta + Ft[r] * xn[:, r]
             x = np.where(obs[:, None, None], xn, x)
             psi = np.where(obs[:, None, None], pn, psi)
@@ -242,7 +221,7 @@ def run(*, F, G, g_index, dt, V, m0, C0, y, family, P, a, prior_w, prior_v=None,
             if not res.any():
                 continue
             cum = running_sums(wg)
-            _, u2 = lw_rand(seed, series, iteration, t, P, BLOCK_RESAMPLE)
+            _, u2 = batch_rand(KEY_LW | BLOCK_RESAMPLE, seed, series, iteration, t, P)
             target = u2 * cum[:, P - 1, None]
             anc = ancestors(cum, target, res, mg)
             x = np.where(res[:, None, None], np.take_along_axis(x, anc[:, None, :], axis=2), x)

@@ -59,6 +59,56 @@ def dense_model(d, rng):
     return G, W, F
 
 
+def time_grid(c, G0, dt0=0.0):
+    """(G [n_g][d][d], g_index, dt) of a table entry: irregular, three distinct G and a dt = 0 first and inside the series; else the one G
+    on the unit grid behind a first increment dt0 (0 puts the initial cloud AT the first observation)."""
+    T = c["T"]
+    if not c["irregular"]:
+        return G0[None], None, np.array([dt0] + [1.0] * (T - 1))
+    dt = np.array([0.0] + [(1.0, 0.5, 2.0)[k % 3] for k in range(1, T)])
+    dt[T // 2] = 0.0                     # one more dt = 0, inside the series
+    gi = np.array([0] + [k % 3 for k in range(1, T)], dtype=np.int32)
+    return np.stack([G0, 0.95 * G0 @ G0.T @ G0, 0.8 * G0 @ G0]), gi, dt
+
+
+def learner_inputs(c, seed_base, priors, dt0=0.0):
+    """The arrays of a table entry of a filter that learns the diagonal of W (tests/storvik_cases.py, tests/lw_cases.py): the dense model,
+    the grid, per-series m0 and C0, data simulated series by series at the model's own diagonal W and V, the missing values and nu.
+    priors(d, Wd, V, N, scale) -> (prior_w, prior_v) is the filter's own; scale [N] is the per-series factor, None for shared parameters."""
+    name = c["name"]
+    rng = np.random.default_rng(seed_base + c["seed"] * 7919 + sum(map(ord, name)))
+    d, T, N, fam = c["d"], c["T"], c["N"], c["family"]
+    G0, Wfull, F = dense_model(d, rng)
+    Wd = np.diag(Wfull).copy()
+    G, gi, dt = time_grid(c, G0, dt0)
+    shift = np.zeros(d); shift[0] = FAMILY_LEVEL[fam] / F[0]
+    m0 = rng.standard_normal(d) * 0.3
+    C0 = 0.5 * Wfull + 0.2 * np.eye(d)
+    V = FAMILY_V[fam] * c["v_scale"]
+    scale = None
+    if c["per_series"]:
+        scale = np.exp(0.3 * rng.standard_normal(N))
+        C0n = C0[None] * scale[::-1, None, None]
+        m0n = m0[None] + 0.2 * rng.standard_normal((N, d))
+        Vn = np.full(N, V)
+    else:
+        C0n, m0n, Vn = C0, m0, V
+    prior_w, prior_v = priors(d, Wd, V, N, scale)
+    mod = Dglm(lambda t: F[:, None], lambda s: G0, fam, 5.0 if fam == pr.STUDENTT else None)
+    y = np.empty((N, T))
+    Lw = np.sqrt(Wd)
+    for n in range(N):
+        x = (m0n[n] if c["per_series"] else m0) + shift + np.linalg.cholesky(C0n[n] if c["per_series"] else C0) @ rng.standard_normal(d)
+        for t in range(T):
+            if dt[t] != 0.0:
+                x = G[0 if gi is None else gi[t]] @ x + np.sqrt(dt[t]) * (Lw * rng.standard_normal(d))
+            y[n, t] = mod.observation(float(F @ x), float(V), rng)
+    for t in c["missing"]:
+        y[:, t] = np.nan
+    nu = 5.0 + np.arange(N) if fam == pr.STUDENTT else None
+    return dict(F=F, G=G, g_index=gi, dt=dt, V=Vn, W=np.diag(Wd), m0=m0n + shift, C0=C0n, y=y, nu=nu, prior_w=prior_w, prior_v=prior_v)
+
+
 @functools.lru_cache(maxsize=None)
 def inputs(name):
     """The arrays of a table entry: what the restatement takes, and through `engine_run` the engine."""
@@ -66,14 +116,7 @@ def inputs(name):
     rng = np.random.default_rng(1000 + c["seed"] * 7919 + sum(map(ord, name)))
     d, T, N, fam = c["d"], c["T"], c["N"], c["family"]
     G0, W, F = dense_model(d, rng)
-    if c["irregular"]:
-        steps = np.array([0.0] + [(1.0, 0.5, 2.0)[k % 3] for k in range(1, T)])
-        steps[T // 2] = 0.0                     # one more dt = 0, inside the series
-        gi = np.array([0] + [k % 3 for k in range(1, T)], dtype=np.int32)
-        G = np.stack([G0, 0.95 * G0 @ G0.T @ G0, 0.8 * G0 @ G0])
-        dt = steps
-    else:
-        G, gi, dt = G0[None], None, np.array([0.0] + [1.0] * (T - 1))   # the initial cloud sits at the first observation
+    G, gi, dt = time_grid(c, G0)
     level = FAMILY_LEVEL[fam]
     shift = np.zeros(d); shift[0] = level / F[0]
     m0 = rng.standard_normal(d) * 0.3

@@ -26,24 +26,39 @@ ST_NONFINITE, ST_NOT_PD = 1, 2
 TWO_PI = 6.283185307179586476925286766559
 
 
-def pf_rand(seed, series, it, slot, particles, block):
-    """series [N], particles [P] -> (u1 in (0, 1], u2 in [0, 1)), each [N][P]."""
-    series = np.asarray(series, dtype=np.uint64)[:, None]
-    word = (np.uint64(slot) * np.uint64(2048) + np.asarray(particles, dtype=np.uint64) * np.uint64(2))[None, :] & MASK
-    z = np.zeros((series.shape[0], word.shape[1]), dtype=np.uint64)
-    c = philox(z + (series & MASK), z + (series >> np.uint64(32)), z + np.uint64(it & 0xFFFFFFFF), z + word,
-               seed & 0xFFFFFFFF, ((seed >> 32) & 0xFFFFFFFF) ^ (KEY_PF | block))
+def rand(key, seed, series, it, slot, particles, which=0):
+    """The two uniforms of a particle kernel (gibbs_rand of dlm_draws.h) under `key` -- the filter's key | block, for the Storvik filter
+    | attempt << 8 too -- at the counter (series, iteration, slot * 2048 + particle * 2 + which).  series and particles broadcast against
+    one another ([N][1] and [P]: the whole batch; two flat arrays of one length: those pairs) -> (u1 in (0, 1], u2 in [0, 1)) of that shape."""
+    series, particles = np.broadcast_arrays(np.asarray(series, dtype=np.uint64), np.asarray(particles, dtype=np.uint64))
+    word = (np.uint64(slot) * np.uint64(2048) + particles * np.uint64(2) + np.uint64(which)) & MASK
+    z = np.zeros(series.shape, dtype=np.uint64)
+    c = philox(series & MASK, series >> np.uint64(32), z + np.uint64(it & 0xFFFFFFFF), word,
+               seed & 0xFFFFFFFF, ((seed >> 32) & 0xFFFFFFFF) ^ key)
     f = [x.astype(np.float64) for x in c]
     u1 = (f[0] * 4294967296.0 + f[1] + 1.0) * (1.0 / 18446744073709551616.0)
     u2 = (f[2] * 4294967296.0 + f[3]) * (1.0 / 18446744073709551616.0)
     return u1, u2
 
 
+def batch_rand(key, seed, series, it, slot, P):
+    """`rand` for every particle of every series: series [N] -> (u1, u2), each [N][P]."""
+    return rand(key, seed, np.asarray(series, dtype=np.uint64)[:, None], it, slot, np.arange(P, dtype=np.uint64))
+
+
+def normal(key, seed, series, it, slot, P, base, r):
+    """z_r [len(series)][P], one component of a Box-Muller pair (st_normal of dlm_storvik.hip, lw_normal of dlm_lw.hip): block
+    base + r // 2 under `key`, the cosine for an even r and the sine for an odd one."""
+    u1, u2 = batch_rand(key | (base + (r >> 1)), seed, series, it, slot, P)
+    rad, ang = np.sqrt(-2.0 * np.log(u1)), TWO_PI * u2
+    return rad * (np.sin(ang) if r & 1 else np.cos(ang))
+
+
 def normals(seed, series, it, slot, P, d):
-    """z [N][d][P]"""
+    """z [N][d][P]: the bootstrap filter's, a pair per Philox call"""
     z = np.empty((len(series), d, P))
     for q in range((d + 1) // 2):
-        u1, u2 = pf_rand(seed, series, it, slot, np.arange(P), q)
+        u1, u2 = batch_rand(KEY_PF | q, seed, series, it, slot, P)
         r, ang = np.sqrt(-2.0 * np.log(u1)), TWO_PI * u2
         z[:, 2 * q] = r * np.cos(ang)
         if 2 * q + 1 < d:
@@ -266,7 +281,7 @@ def run(*, F, G, g_index, dt, V, W, m0, C0, y, family, P, n0=-1, literal=False, 
                 continue
             cum = running_sums(wg)
             total = cum[:, P - 1]
-            _, u2 = pf_rand(seed, series, iteration, t, np.arange(P), BLOCK_RESAMPLE)
+            _, u2 = batch_rand(KEY_PF | BLOCK_RESAMPLE, seed, series, iteration, t, P)
             target = u2 * total[:, None]
             for n in np.nonzero(res)[0]:
                 top = np.maximum.accumulate(cum[n])          # the first j with cum[j] > target = the first j whose running maximum is

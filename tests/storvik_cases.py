@@ -17,7 +17,6 @@ from scipy.special import gammaln
 import pf_cases as pc
 import pf_restatement as pr
 import storvik_restatement as sr
-from bayesian_dlms_amd.dglm import Dglm
 
 
 def case(name, d, P, T, N, family=pr.GAUSSIAN, learn_v=True, n0=-1, literal=False, missing=(), irregular=False, per_series=False, seed=1,
@@ -54,48 +53,16 @@ def inputs(name):
     """The arrays of a table entry: what the restatement takes, and through `engine_run` the engine.  The data are simulated from the model
     at the variances the priors are centred on (prior mean = scale / (shape - 1) for the shape 4 of the table; the shape 0.6 keeps the scale)."""
     c = by_name(name)
-    rng = np.random.default_rng(3000 + c["seed"] * 7919 + sum(map(ord, name)))
-    d, T, N, fam = c["d"], c["T"], c["N"], c["family"]
-    G0, Wfull, F = pc.dense_model(d, rng)
-    Wd = np.diag(Wfull).copy()
-    if c["irregular"]:
-        steps = np.array([0.0] + [(1.0, 0.5, 2.0)[k % 3] for k in range(1, T)])
-        steps[T // 2] = 0.0                     # one more dt = 0, inside the series
-        gi = np.array([0] + [k % 3 for k in range(1, T)], dtype=np.int32)
-        G = np.stack([G0, 0.95 * G0 @ G0.T @ G0, 0.8 * G0 @ G0])
-        dt = steps
-    else:
-        G, gi, dt = G0[None], None, np.array([0.0] + [1.0] * (T - 1))   # the initial cloud sits at the first observation
-    level = pc.FAMILY_LEVEL[fam]
-    shift = np.zeros(d); shift[0] = level / F[0]
-    m0 = rng.standard_normal(d) * 0.3
-    C0 = 0.5 * Wfull + 0.2 * np.eye(d)
-    V = pc.FAMILY_V[fam] * c["v_scale"]
-    prior_w = np.stack([np.full(d, c["w_shape"]), 3.0 * Wd], axis=1)          # [d][2] = (shape, scale)
-    prior_v = np.array([4.0, 3.0 * V])
-    if c["per_series"]:
-        scale = np.exp(0.3 * rng.standard_normal(N))
-        C0n = C0[None] * scale[::-1, None, None]
-        m0n = m0[None] + 0.2 * rng.standard_normal((N, d))
-        prior_w = prior_w[None] * np.stack([np.ones(N), scale], axis=1)[:, None, :] + np.stack([0.25 * np.arange(N), np.zeros(N)], axis=1)[:, None, :]
-        prior_v = prior_v[None] * np.stack([np.ones(N), scale[::-1]], axis=1) + np.stack([0.5 * (np.arange(N) % 3), np.zeros(N)], axis=1)
-        Vn = np.full(N, V)
-    else:
-        C0n, m0n, Vn = C0, m0, V
-    mod = Dglm(lambda t: F[:, None], lambda s: G0, fam, 5.0 if fam == pr.STUDENTT else None)
-    y = np.empty((N, T))
-    Lw = np.sqrt(Wd)
-    for n in range(N):
-        x = (m0n[n] if c["per_series"] else m0) + shift + np.linalg.cholesky(C0n[n] if c["per_series"] else C0) @ rng.standard_normal(d)
-        for t in range(T):
-            if dt[t] != 0.0:
-                x = G[0 if gi is None else gi[t]] @ x + np.sqrt(dt[t]) * (Lw * rng.standard_normal(d))
-            y[n, t] = mod.observation(float(F @ x), float(V), rng)
-    for t in c["missing"]:
-        y[:, t] = np.nan
-    nu = 5.0 + np.arange(N) if fam == pr.STUDENTT else None
-    return dict(F=F, G=G, g_index=gi, dt=dt, V=Vn, W=np.diag(Wd), m0=m0n + shift, C0=C0n, y=y, nu=nu, prior_w=prior_w,
-                prior_v=prior_v if c["learn_v"] else None)
+
+    def priors(d, Wd, V, N, scale):
+        prior_w = np.stack([np.full(d, c["w_shape"]), 3.0 * Wd], axis=1)          # [d][2] = (shape, scale)
+        prior_v = np.array([4.0, 3.0 * V])
+        if scale is not None:
+            prior_w = prior_w[None] * np.stack([np.ones(N), scale], axis=1)[:, None, :] + np.stack([0.25 * np.arange(N), np.zeros(N)], axis=1)[:, None, :]
+            prior_v = prior_v[None] * np.stack([np.ones(N), scale[::-1]], axis=1) + np.stack([0.5 * (np.arange(N) % 3), np.zeros(N)], axis=1)
+        return prior_w, prior_v if c["learn_v"] else None
+
+    return pc.learner_inputs(c, 3000, priors)
 
 
 def run_args(name, **over):

@@ -1,6 +1,6 @@
 """NumPy restatement of the Storvik filter kernel (bayesian_dlms_amd/csrc/dlm_storvik.hip, dlm_storvik_batch), operation for operation and
 in the kernel's orders of summation, vectorised over the series of a batch.  The sums over the particles, the running
-sums of the resampling search, the Cholesky factor, the densities and Philox are tests/pf_restatement.py's, by import.
+sums of the resampling search, the Cholesky factor, the densities, Philox and the addressing of the draws are tests/pf_restatement.py's, by import.
 
 The draws: Philox4x32-10 under the key DLM_KEY_STORVIK | attempt << 8 | block (dlm_draws.h), counter (series, iteration,
 slot * 2048 + particle * 2 + which): block q < 8 the Box-Muller pair of the components 2 q and 2 q + 1, block 8 the resampling uniform,
@@ -13,9 +13,8 @@ absolute values of the terms on both sides -- and margin_v, the smallest |1 + c 
 observed steps that resampled."""
 import numpy as np
 
-from pf_restatement import (GAUSSIAN, ST_NONFINITE, ST_NOT_PD, TWO_PI, _per_series, cholesky, log_density, matvec_lower,  # noqa: F401
-                            particle_sum, running_sums)
-from sampler_restatement import MASK, philox
+from pf_restatement import (GAUSSIAN, ST_NONFINITE, ST_NOT_PD, TWO_PI, _per_series, batch_rand, cholesky, log_density,  # noqa: F401
+                            matvec_lower, normal, particle_sum, rand, running_sums)
 
 KEY_STORVIK = 0x53740000
 BLOCK_RESAMPLE, BLOCK_GAMMA, GAMMA_ATTEMPTS = 8, 9, 255
@@ -24,27 +23,11 @@ SLOT_INIT = 0x1FFFFF
 
 def st_rand(seed, series, it, slot, particles, block, attempt=0, which=0):
     """series, particles: flat arrays of one length -> (u1 in (0, 1], u2 in [0, 1)) of that length."""
-    series = np.asarray(series, dtype=np.uint64)
-    word = (np.uint64(slot) * np.uint64(2048) + np.asarray(particles, dtype=np.uint64) * np.uint64(2) + np.uint64(which)) & MASK
-    z = np.zeros(series.shape, dtype=np.uint64)
-    c = philox(series & MASK, series >> np.uint64(32), z + np.uint64(it & 0xFFFFFFFF), word,
-               seed & 0xFFFFFFFF, ((seed >> 32) & 0xFFFFFFFF) ^ (KEY_STORVIK | (attempt << 8) | block))
-    f = [x.astype(np.float64) for x in c]
-    u1 = (f[0] * 4294967296.0 + f[1] + 1.0) * (1.0 / 18446744073709551616.0)
-    u2 = (f[2] * 4294967296.0 + f[3]) * (1.0 / 18446744073709551616.0)
-    return u1, u2
+    return rand(KEY_STORVIK | (attempt << 8) | block, seed, series, it, slot, particles, which)
 
 
 def _grid(series, P):
     return np.repeat(np.asarray(series, dtype=np.uint64), P), np.tile(np.arange(P, dtype=np.uint64), len(series))
-
-
-def normal(seed, series, it, slot, P, r):
-    """z_r [len(series)][P]: block r // 2, the cosine for an even r and the sine for an odd one."""
-    ser, part = _grid(series, P)
-    u1, u2 = st_rand(seed, ser, it, slot, part, r >> 1)
-    rad, ang = np.sqrt(-2.0 * np.log(u1)), TWO_PI * u2
-    return (rad * (np.sin(ang) if r & 1 else np.cos(ang))).reshape(len(series), P)
 
 
 def gamma(shape, seed, series, it, slot, P, comp, margins):
@@ -117,7 +100,7 @@ def run(*, F, G, g_index, dt, V, m0, C0, y, family, P, prior_w, prior_v=None, le
         ok0 &= np.all(pv > 0.0, axis=1)
     status[~ok0] = ST_NOT_PD
     alive = ok0.copy()
-    z = np.stack([normal(seed, series, iteration, SLOT_INIT, P, c) for c in range(d)], axis=1)
+    z = np.stack([normal(KEY_STORVIK, seed, series, iteration, SLOT_INIT, P, 0, c) for c in range(d)], axis=1)
     x = m0[:, :, None] + matvec_lower(L0, z)
     bw = np.broadcast_to(pw[:, :, 1, None], (N, d, P)).copy()
     bv = np.broadcast_to(pv[:, 1, None], (N, P)).copy() if learn_v else np.zeros((N, P))
@@ -148,7 +131,7 @@ def run(*, F, G, g_index, dt, V, m0, C0, y, family, P, prior_w, prior_v=None, le
                     gx = Gt[r, 0] * xo[:, 0]
                     for c in range(1, d):
                         gx = gx + Gt[r, c] * xo[:, c]
-                    zr = normal(seed, series[who], iteration, t, P, r)
+                    zr = normal(KEY_STORVIK, seed, series[who], iteration, t, P, 0, r)
                     g = gamma(pw[who, r, 0] + 0.5 * float(n_adv), seed, series[who], iteration, t, P, r, mg)
                     b = bw[who, r]
                     w = b / g
@@ -210,9 +193,8 @@ def run(*, F, G, g_index, dt, V, m0, C0, y, family, P, prior_w, prior_v=None, le
                 continue
             cum = running_sums(wg)
             total = cum[:, P - 1]
-            ser, part = _grid(series, P)
-            _, u2 = st_rand(seed, ser, iteration, t, part, BLOCK_RESAMPLE)
-            target = u2.reshape(N, P) * total[:, None]
+            _, u2 = batch_rand(KEY_STORVIK | BLOCK_RESAMPLE, seed, series, iteration, t, P)
+            target = u2 * total[:, None]
             for n in np.nonzero(res)[0]:
                 top = np.maximum.accumulate(cum[n])
                 anc = np.minimum(np.searchsorted(top, target[n], side="right"), P - 1)
