@@ -764,6 +764,82 @@ __global__ void k_unpack_records(int d, long long count, int prec, const double*
   dense[i] = src[d + hi * (hi + 1) / 2 + lo];
 }
 
+// ---- the three particle filters of a DGLM (dlm_pf.hip, dlm_storvik.hip, dlm_lw.hip) ----
+// The checks they share, in the order every entry point makes them: the model and the descriptor's family and literal, then the filter's
+// `own` (its learn_v, its shrinkage, its priors), then the data and the shapes the kernels cover.  `name`: "the ... filter" of the messages;
+// reads_w: the bootstrap filter, which reads params->V and W; reads_v: params->V is read (a learning filter without learn_v)
+template <class Own>
+int pf_check(dlm_engine* e, const dlm_model_desc* model, const dlm_params_desc* params, int family, int literal, int P,
+             const double* obs_param, const double* y, const double* ll, const std::string& name, bool reads_v, bool reads_w, Own&& own) {
+  const int d = model->d, T = model->T, N = model->N;
+  if (d < 1 || model->p < 1 || T < 1 || N < 1) return fail(e, DLM_ERR_ARG, "d, p, T, N must be >= 1");
+  if (!model->F || !model->G || model->n_g < 1) return fail(e, DLM_ERR_ARG, "model tables F/G missing");
+  if (model->n_g > 1 && !model->g_index) return fail(e, DLM_ERR_ARG, "n_g > 1 needs g_index");
+  if (model->f_stride != 0 && model->f_stride != (int64_t)d * model->p) return fail(e, DLM_ERR_ARG, "f_stride must be 0 or d*p");
+  if ((reads_w && (!params->V || !params->W)) || !params->m0 || !params->C0) return fail(e, DLM_ERR_ARG, reads_w ? "parameter arrays missing" : "parameter arrays m0/C0 missing");
+  if (family < DLM_OBS_GAUSSIAN || family > DLM_OBS_BETA) return fail(e, DLM_ERR_ARG, "family: one of DLM_OBS_*");
+  if (literal != 0 && literal != 1) return fail(e, DLM_ERR_ARG, "literal: 0 or 1");
+  if (const int rc = own()) return rc;
+  if (family == DLM_OBS_STUDENTT && !obs_param) return fail(e, DLM_ERR_ARG, "DLM_OBS_STUDENTT needs obs_param (the degrees of freedom of every series)");
+  if (!y || !ll) return fail(e, DLM_ERR_ARG, "y and ll are required");
+  if (model->p != 1) return fail(e, DLM_ERR_UNSUPPORTED, name + " takes a univariate observation (p = 1): every Dglm family reads y(0) and V(0,0)");
+  if (d > dlm::DLM_PF_MAX_D) return fail(e, DLM_ERR_UNSUPPORTED, name + " takes d <= 16");
+  if (P < 64 || P > dlm::DLM_PF_MAX_P || P % 64 != 0) return fail(e, DLM_ERR_UNSUPPORTED, "n_particles must be a multiple of 64 with 64 <= n_particles <= 1024 (one wavefront per series, whole slots of particles)");
+  if (T > dlm::DLM_PF_MAX_T) return fail(e, DLM_ERR_UNSUPPORTED, "T must stay below 2^21 - 1 (the Philox counter's slot field)");
+  if (reads_w && (params->v_tstride || params->w_tstride)) return fail(e, DLM_ERR_UNSUPPORTED, name + " takes time-invariant V and W (v_tstride = w_tstride = 0)");
+  if (reads_v && params->v_tstride) return fail(e, DLM_ERR_UNSUPPORTED, name + " takes a time-invariant V (v_tstride = 0)");
+  return DLM_OK;
+}
+
+// what the two learning filters ask of learn_v's sources and of the priors' strides
+int pf_check_priors(dlm_engine* e, const dlm_params_desc* params, int d, int learn_v, const double* prior_v, int64_t prior_v_stride,
+                    const double* prior_w, int64_t prior_w_stride) {
+  if (learn_v ? !prior_v : !params->V) return fail(e, DLM_ERR_ARG, "learn_v = 1 needs prior_v, learn_v = 0 needs params->V");
+  if (!prior_w) return fail(e, DLM_ERR_ARG, "prior_w is required");
+  if ((prior_v_stride != 0 && prior_v_stride < 2) || (prior_w_stride != 0 && prior_w_stride < 2 * (int64_t)d)) return fail(e, DLM_ERR_ARG, "prior_v_stride must be 0 or >= 2, prior_w_stride 0 or >= 2 d");
+  return DLM_OK;
+}
+
+// What the three kernels read and write, staged into the fields every argument struct has under PfCommonArgs' names, with its scalars and
+// strides.  V: params->V, or null where the filter learns it (a null pointer stages nothing)
+template <class Args>
+void pf_stage(Stager& st, Args& a, const dlm_model_desc* model, const dlm_params_desc* params, int family, int literal, int n0, int P,
+              const double* V, const double* obs_param, const double* y, const dlm_options* opts, uint64_t iteration, double* ll,
+              double* mean, double* ess, double* cloud, double* weights, int32_t* status) {
+  const size_t n = model->N, t = model->T, dd = model->d, np = P;
+  st.in(&a.F, model->F, (model->f_stride ? t : 1) * dd);
+  st.in(&a.G, model->G, (size_t)model->n_g * dd * dd);
+  st.in(&a.g_index, (const int*)model->g_index, model->g_index ? t : 0);
+  st.in(&a.dt, model->dt, model->dt ? t : 0);
+  st.in(&a.V, V, params->v_stride ? (n - 1) * (size_t)params->v_stride + 1 : 1);
+  st.in(&a.m0, params->m0, params->m0_stride ? (n - 1) * (size_t)params->m0_stride + dd : dd);
+  st.in(&a.C0, params->C0, params->c0_stride ? (n - 1) * (size_t)params->c0_stride + dd * dd : dd * dd);
+  st.in(&a.obs_param, obs_param, obs_param ? n : 0);
+  st.in(&a.y, y, n * t);
+  st.out(&a.ll, ll, n);
+  st.out(&a.mean, mean, mean ? n * t * dd : 0);
+  st.out(&a.ess, ess, ess ? n * t : 0);
+  st.out(&a.cloud, cloud, cloud ? n * dd * np : 0);
+  st.out(&a.weights, weights, weights ? n * np : 0);
+  st.zeroed_out(&a.status, (int*)status, status ? n : 0);
+  a.d = model->d; a.T = model->T; a.N = model->N; a.P = P;
+  a.family = family; a.literal = literal;
+  a.n0 = n0 < 0 ? P / 5 : n0;   // ParticleFilter.likelihood: floor(n / 5)
+  a.f_stride = model->f_stride; a.n_g = model->n_g;
+  a.v_stride = params->v_stride; a.m0_stride = params->m0_stride; a.c0_stride = params->c0_stride;
+  a.rs = draw_stream(opts, iteration);
+}
+
+// the priors of a learning filter: prior_w [d][2] of every series, prior_v [2] with learn_v only
+template <class Args>
+void pf_stage_priors(Stager& st, Args& a, int learn_v, const double* prior_v, int64_t prior_v_stride, const double* prior_w,
+                     int64_t prior_w_stride) {
+  const size_t n = a.N, dd = a.d;
+  st.in(&a.prior_v, learn_v ? prior_v : nullptr, prior_v_stride ? (n - 1) * (size_t)prior_v_stride + 2 : 2);
+  st.in(&a.prior_w, prior_w, prior_w_stride ? (n - 1) * (size_t)prior_w_stride + 2 * dd : 2 * dd);
+  a.learn_v = learn_v; a.prior_v_stride = prior_v_stride; a.prior_w_stride = prior_w_stride;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1380,50 +1456,18 @@ int dlm_pf_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_params_de
   if (!model || !params || !pf) return fail(e, DLM_ERR_ARG, "null descriptor");
   int rc;
   if ((rc = check_opts(e, opts))) return rc;
-  const int d = model->d, T = model->T, N = model->N, P = pf->n_particles;
-  if (d < 1 || model->p < 1 || T < 1 || N < 1) return fail(e, DLM_ERR_ARG, "d, p, T, N must be >= 1");
-  if (!model->F || !model->G || model->n_g < 1) return fail(e, DLM_ERR_ARG, "model tables F/G missing");
-  if (model->n_g > 1 && !model->g_index) return fail(e, DLM_ERR_ARG, "n_g > 1 needs g_index");
-  if (model->f_stride != 0 && model->f_stride != (int64_t)d * model->p) return fail(e, DLM_ERR_ARG, "f_stride must be 0 or d*p");
-  if (!params->V || !params->W || !params->m0 || !params->C0) return fail(e, DLM_ERR_ARG, "parameter arrays missing");
-  if (pf->family < DLM_OBS_GAUSSIAN || pf->family > DLM_OBS_BETA) return fail(e, DLM_ERR_ARG, "family: one of DLM_OBS_*");
-  if (pf->literal != 0 && pf->literal != 1) return fail(e, DLM_ERR_ARG, "literal: 0 or 1");
-  if (pf->family == DLM_OBS_STUDENTT && !obs_param) return fail(e, DLM_ERR_ARG, "DLM_OBS_STUDENTT needs obs_param (the degrees of freedom of every series)");
-  if (!y || !ll) return fail(e, DLM_ERR_ARG, "y and ll are required");
-  if (model->p != 1) return fail(e, DLM_ERR_UNSUPPORTED, "the particle filter takes a univariate observation (p = 1): every Dglm family reads y(0) and V(0,0)");
-  if (d > dlm::DLM_PF_MAX_D) return fail(e, DLM_ERR_UNSUPPORTED, "the particle filter takes d <= 16");
-  if (P < 64 || P > dlm::DLM_PF_MAX_P || P % 64 != 0) return fail(e, DLM_ERR_UNSUPPORTED, "n_particles must be a multiple of 64 with 64 <= n_particles <= 1024 (one wavefront per series, whole slots of particles)");
-  if (T > dlm::DLM_PF_MAX_T) return fail(e, DLM_ERR_UNSUPPORTED, "T must stay below 2^21 - 1 (the Philox counter's slot field)");
-  if (params->v_tstride || params->w_tstride) return fail(e, DLM_ERR_UNSUPPORTED, "the particle filter takes time-invariant V and W (v_tstride = w_tstride = 0)");
+  const int d = model->d, P = pf->n_particles;
+  if ((rc = pf_check(e, model, params, pf->family, pf->literal, P, obs_param, y, ll, "the particle filter", true, true, [] { return DLM_OK; }))) return rc;
   HIP_TRY(e, hipSetDevice(e->device));
   const size_t lds = dlm::pf_lds_bytes(d, P), have = dlm::lds_limit();
   if (have && lds > have) return fail(e, DLM_ERR_UNSUPPORTED, "d and n_particles need more LDS than a workgroup of this device gets: (d + 2.5) n_particles + d^2 doubles");
   dlm::PfArgs a{};
-  const size_t n = N, t = T, dd = d, np = P;
+  const size_t n = model->N, dd = d;
   Stager st(e, opts->mem == DLM_MEM_HOST);
-  st.in(&a.F, model->F, (model->f_stride ? t : 1) * dd);
-  st.in(&a.G, model->G, (size_t)model->n_g * dd * dd);
-  st.in(&a.g_index, (const int*)model->g_index, model->g_index ? t : 0);
-  st.in(&a.dt, model->dt, model->dt ? t : 0);
-  st.in(&a.V, params->V, params->v_stride ? (n - 1) * (size_t)params->v_stride + 1 : 1);
+  pf_stage(st, a, model, params, pf->family, pf->literal, pf->n0, P, params->V, obs_param, y, opts, iteration, ll, mean, ess, cloud, weights, status);
   st.in(&a.W, params->W, params->w_stride ? (n - 1) * (size_t)params->w_stride + dd * dd : dd * dd);
-  st.in(&a.m0, params->m0, params->m0_stride ? (n - 1) * (size_t)params->m0_stride + dd : dd);
-  st.in(&a.C0, params->C0, params->c0_stride ? (n - 1) * (size_t)params->c0_stride + dd * dd : dd * dd);
-  st.in(&a.obs_param, obs_param, obs_param ? n : 0);
-  st.in(&a.y, y, n * t);
-  st.out(&a.ll, ll, n);
-  st.out(&a.mean, mean, mean ? n * t * dd : 0);
-  st.out(&a.ess, ess, ess ? n * t : 0);
-  st.out(&a.cloud, cloud, cloud ? n * dd * np : 0);
-  st.out(&a.weights, weights, weights ? n * np : 0);
-  st.zeroed_out(&a.status, (int*)status, status ? n : 0);
+  a.w_stride = params->w_stride;
   if ((rc = st.commit())) return rc;
-  a.d = d; a.T = T; a.N = N; a.P = P;
-  a.family = pf->family; a.literal = pf->literal;
-  a.n0 = pf->n0 < 0 ? P / 5 : pf->n0;   // ParticleFilter.likelihood: floor(n / 5)
-  a.f_stride = model->f_stride; a.n_g = model->n_g;
-  a.v_stride = params->v_stride; a.w_stride = params->w_stride; a.m0_stride = params->m0_stride; a.c0_stride = params->c0_stride;
-  a.rs = draw_stream(opts, iteration);
   e->variant = "pf-wave";
   HIP_TRY(e, dlm::launch_pf(a, e->stream));
   return st.finish(opts->flags & DLM_OPT_ASYNC);
@@ -1437,59 +1481,23 @@ int dlm_storvik_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_para
   if (!model || !params || !sv) return fail(e, DLM_ERR_ARG, "null descriptor");
   int rc;
   if ((rc = check_opts(e, opts))) return rc;
-  const int d = model->d, T = model->T, N = model->N, P = sv->n_particles;
-  if (d < 1 || model->p < 1 || T < 1 || N < 1) return fail(e, DLM_ERR_ARG, "d, p, T, N must be >= 1");
-  if (!model->F || !model->G || model->n_g < 1) return fail(e, DLM_ERR_ARG, "model tables F/G missing");
-  if (model->n_g > 1 && !model->g_index) return fail(e, DLM_ERR_ARG, "n_g > 1 needs g_index");
-  if (model->f_stride != 0 && model->f_stride != (int64_t)d * model->p) return fail(e, DLM_ERR_ARG, "f_stride must be 0 or d*p");
-  if (!params->m0 || !params->C0) return fail(e, DLM_ERR_ARG, "parameter arrays m0/C0 missing");
-  if (sv->family < DLM_OBS_GAUSSIAN || sv->family > DLM_OBS_BETA) return fail(e, DLM_ERR_ARG, "family: one of DLM_OBS_*");
-  if (sv->literal != 0 && sv->literal != 1) return fail(e, DLM_ERR_ARG, "literal: 0 or 1");
-  if (sv->learn_v != 0 && sv->learn_v != 1) return fail(e, DLM_ERR_ARG, "learn_v: 0 or 1");
-  if (sv->learn_v && sv->family != DLM_OBS_GAUSSIAN) return fail(e, DLM_ERR_ARG, "learn_v = 1 needs DLM_OBS_GAUSSIAN: the InverseGamma statistic of V is conjugate for the Gaussian family only (the others learn W alone)");
-  if (sv->learn_v ? !prior_v : !params->V) return fail(e, DLM_ERR_ARG, "learn_v = 1 needs prior_v, learn_v = 0 needs params->V");
-  if (!prior_w) return fail(e, DLM_ERR_ARG, "prior_w is required");
-  if ((prior_v_stride != 0 && prior_v_stride < 2) || (prior_w_stride != 0 && prior_w_stride < 2 * (int64_t)d)) return fail(e, DLM_ERR_ARG, "prior_v_stride must be 0 or >= 2, prior_w_stride 0 or >= 2 d");
-  if (sv->family == DLM_OBS_STUDENTT && !obs_param) return fail(e, DLM_ERR_ARG, "DLM_OBS_STUDENTT needs obs_param (the degrees of freedom of every series)");
-  if (!y || !ll) return fail(e, DLM_ERR_ARG, "y and ll are required");
-  if (model->p != 1) return fail(e, DLM_ERR_UNSUPPORTED, "the Storvik filter takes a univariate observation (p = 1): every Dglm family reads y(0) and V(0,0)");
-  if (d > dlm::DLM_PF_MAX_D) return fail(e, DLM_ERR_UNSUPPORTED, "the Storvik filter takes d <= 16");
-  if (P < 64 || P > dlm::DLM_PF_MAX_P || P % 64 != 0) return fail(e, DLM_ERR_UNSUPPORTED, "n_particles must be a multiple of 64 with 64 <= n_particles <= 1024 (one wavefront per series, whole slots of particles)");
-  if (T > dlm::DLM_PF_MAX_T) return fail(e, DLM_ERR_UNSUPPORTED, "T must stay below 2^21 - 1 (the Philox counter's slot field)");
-  if (!sv->learn_v && params->v_tstride) return fail(e, DLM_ERR_UNSUPPORTED, "the Storvik filter takes a time-invariant V (v_tstride = 0)");
+  const int d = model->d, P = sv->n_particles;
+  if ((rc = pf_check(e, model, params, sv->family, sv->literal, P, obs_param, y, ll, "the Storvik filter", !sv->learn_v, false, [&] {
+        if (sv->learn_v != 0 && sv->learn_v != 1) return fail(e, DLM_ERR_ARG, "learn_v: 0 or 1");
+        if (sv->learn_v && sv->family != DLM_OBS_GAUSSIAN) return fail(e, DLM_ERR_ARG, "learn_v = 1 needs DLM_OBS_GAUSSIAN: the InverseGamma statistic of V is conjugate for the Gaussian family only (the others learn W alone)");
+        return pf_check_priors(e, params, d, sv->learn_v, prior_v, prior_v_stride, prior_w, prior_w_stride);
+      }))) return rc;
   HIP_TRY(e, hipSetDevice(e->device));
   const size_t lds = dlm::storvik_lds_bytes(d, P), have = dlm::lds_limit();
   if (have && lds > have) return fail(e, DLM_ERR_UNSUPPORTED, "d and n_particles need more LDS than a workgroup of this device gets: (2 d + 3.5) n_particles + d^2 doubles");
   dlm::StorvikArgs a{};
-  const size_t n = N, t = T, dd = d, np = P;
+  const size_t n = model->N, t = model->T, dd = d, np = P;
   Stager st(e, opts->mem == DLM_MEM_HOST);
-  st.in(&a.F, model->F, (model->f_stride ? t : 1) * dd);
-  st.in(&a.G, model->G, (size_t)model->n_g * dd * dd);
-  st.in(&a.g_index, (const int*)model->g_index, model->g_index ? t : 0);
-  st.in(&a.dt, model->dt, model->dt ? t : 0);
-  st.in(&a.V, sv->learn_v ? nullptr : params->V, params->v_stride ? (n - 1) * (size_t)params->v_stride + 1 : 1);   // (a null pointer stages nothing)
-  st.in(&a.m0, params->m0, params->m0_stride ? (n - 1) * (size_t)params->m0_stride + dd : dd);
-  st.in(&a.C0, params->C0, params->c0_stride ? (n - 1) * (size_t)params->c0_stride + dd * dd : dd * dd);
-  st.in(&a.prior_v, sv->learn_v ? prior_v : nullptr, prior_v_stride ? (n - 1) * (size_t)prior_v_stride + 2 : 2);
-  st.in(&a.prior_w, prior_w, prior_w_stride ? (n - 1) * (size_t)prior_w_stride + 2 * dd : 2 * dd);
-  st.in(&a.obs_param, obs_param, obs_param ? n : 0);
-  st.in(&a.y, y, n * t);
-  st.out(&a.ll, ll, n);
-  st.out(&a.mean, mean, mean ? n * t * dd : 0);
-  st.out(&a.ess, ess, ess ? n * t : 0);
+  pf_stage(st, a, model, params, sv->family, sv->literal, sv->n0, P, sv->learn_v ? nullptr : params->V, obs_param, y, opts, iteration, ll, mean, ess, cloud, weights, status);
+  pf_stage_priors(st, a, sv->learn_v, prior_v, prior_v_stride, prior_w, prior_w_stride);
   st.out(&a.scale_mean, scale_mean, scale_mean ? n * t * (dd + 1) : 0);
-  st.out(&a.cloud, cloud, cloud ? n * dd * np : 0);
-  st.out(&a.weights, weights, weights ? n * np : 0);
   st.out(&a.scales, scales, scales ? n * (dd + 1) * np : 0);
-  st.zeroed_out(&a.status, (int*)status, status ? n : 0);
   if ((rc = st.commit())) return rc;
-  a.d = d; a.T = T; a.N = N; a.P = P;
-  a.family = sv->family; a.literal = sv->literal; a.learn_v = sv->learn_v;
-  a.n0 = sv->n0 < 0 ? P / 5 : sv->n0;
-  a.f_stride = model->f_stride; a.n_g = model->n_g;
-  a.v_stride = params->v_stride; a.m0_stride = params->m0_stride; a.c0_stride = params->c0_stride;
-  a.prior_v_stride = prior_v_stride; a.prior_w_stride = prior_w_stride;
-  a.rs = draw_stream(opts, iteration);
   e->variant = "storvik-wave";
   HIP_TRY(e, dlm::launch_storvik(a, e->stream));
   return st.finish(opts->flags & DLM_OPT_ASYNC);
@@ -1503,62 +1511,27 @@ int dlm_lw_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_params_de
   if (!model || !params || !lw) return fail(e, DLM_ERR_ARG, "null descriptor");
   int rc;
   if ((rc = check_opts(e, opts))) return rc;
-  const int d = model->d, T = model->T, N = model->N, P = lw->n_particles;
-  if (d < 1 || model->p < 1 || T < 1 || N < 1) return fail(e, DLM_ERR_ARG, "d, p, T, N must be >= 1");
-  if (!model->F || !model->G || model->n_g < 1) return fail(e, DLM_ERR_ARG, "model tables F/G missing");
-  if (model->n_g > 1 && !model->g_index) return fail(e, DLM_ERR_ARG, "n_g > 1 needs g_index");
-  if (model->f_stride != 0 && model->f_stride != (int64_t)d * model->p) return fail(e, DLM_ERR_ARG, "f_stride must be 0 or d*p");
-  if (!params->m0 || !params->C0) return fail(e, DLM_ERR_ARG, "parameter arrays m0/C0 missing");
-  if (lw->family < DLM_OBS_GAUSSIAN || lw->family > DLM_OBS_BETA) return fail(e, DLM_ERR_ARG, "family: one of DLM_OBS_*");
-  if (lw->literal != 0 && lw->literal != 1) return fail(e, DLM_ERR_ARG, "literal: 0 or 1");
-  if (lw->learn_v != 0 && lw->learn_v != 1) return fail(e, DLM_ERR_ARG, "learn_v: 0 or 1");
-  if (!(lw->a > 0.0 && lw->a <= 1.0)) return fail(e, DLM_ERR_ARG, "a: the shrinkage must satisfy 0 < a <= 1");
-  if (lw->learn_v && lw->family != DLM_OBS_GAUSSIAN && lw->family != DLM_OBS_STUDENTT && lw->family != DLM_OBS_BETA)
-    return fail(e, DLM_ERR_ARG, "learn_v = 1 needs DLM_OBS_GAUSSIAN, DLM_OBS_STUDENTT or DLM_OBS_BETA: the families whose v is a positive scale");
-  if (lw->learn_v ? !prior_v : !params->V) return fail(e, DLM_ERR_ARG, "learn_v = 1 needs prior_v, learn_v = 0 needs params->V");
-  if (!prior_w) return fail(e, DLM_ERR_ARG, "prior_w is required");
-  if ((prior_v_stride != 0 && prior_v_stride < 2) || (prior_w_stride != 0 && prior_w_stride < 2 * (int64_t)d)) return fail(e, DLM_ERR_ARG, "prior_v_stride must be 0 or >= 2, prior_w_stride 0 or >= 2 d");
-  if (lw->family == DLM_OBS_STUDENTT && !obs_param) return fail(e, DLM_ERR_ARG, "DLM_OBS_STUDENTT needs obs_param (the degrees of freedom of every series)");
-  if (!y || !ll) return fail(e, DLM_ERR_ARG, "y and ll are required");
-  if (model->p != 1) return fail(e, DLM_ERR_UNSUPPORTED, "the Liu-West filter takes a univariate observation (p = 1): every Dglm family reads y(0) and V(0,0)");
-  if (d > dlm::DLM_PF_MAX_D) return fail(e, DLM_ERR_UNSUPPORTED, "the Liu-West filter takes d <= 16");
-  if (P < 64 || P > dlm::DLM_PF_MAX_P || P % 64 != 0) return fail(e, DLM_ERR_UNSUPPORTED, "n_particles must be a multiple of 64 with 64 <= n_particles <= 1024 (one wavefront per series, whole slots of particles)");
-  if (T > dlm::DLM_PF_MAX_T) return fail(e, DLM_ERR_UNSUPPORTED, "T must stay below 2^21 - 1 (the Philox counter's slot field)");
-  if (!lw->learn_v && params->v_tstride) return fail(e, DLM_ERR_UNSUPPORTED, "the Liu-West filter takes a time-invariant V (v_tstride = 0)");
+  const int d = model->d, P = lw->n_particles;
+  if ((rc = pf_check(e, model, params, lw->family, lw->literal, P, obs_param, y, ll, "the Liu-West filter", !lw->learn_v, false, [&] {
+        if (lw->learn_v != 0 && lw->learn_v != 1) return fail(e, DLM_ERR_ARG, "learn_v: 0 or 1");
+        if (!(lw->a > 0.0 && lw->a <= 1.0)) return fail(e, DLM_ERR_ARG, "a: the shrinkage must satisfy 0 < a <= 1");
+        if (lw->learn_v && lw->family != DLM_OBS_GAUSSIAN && lw->family != DLM_OBS_STUDENTT && lw->family != DLM_OBS_BETA)
+          return fail(e, DLM_ERR_ARG, "learn_v = 1 needs DLM_OBS_GAUSSIAN, DLM_OBS_STUDENTT or DLM_OBS_BETA: the families whose v is a positive scale");
+        return pf_check_priors(e, params, d, lw->learn_v, prior_v, prior_v_stride, prior_w, prior_w_stride);
+      }))) return rc;
   HIP_TRY(e, hipSetDevice(e->device));
   const size_t lds = dlm::lw_lds_bytes(d, P), have = dlm::lds_limit();
   if (have && lds > have) return fail(e, DLM_ERR_UNSUPPORTED, "d and n_particles need more LDS than a workgroup of this device gets: (2 d + 3.5) n_particles + d^2 + d + 1 doubles");
   dlm::LwArgs a{};
-  const size_t n = N, t = T, dd = d, np = P;
+  const size_t n = model->N, t = model->T, dd = d, np = P;
   Stager st(e, opts->mem == DLM_MEM_HOST);
-  st.in(&a.F, model->F, (model->f_stride ? t : 1) * dd);
-  st.in(&a.G, model->G, (size_t)model->n_g * dd * dd);
-  st.in(&a.g_index, (const int*)model->g_index, model->g_index ? t : 0);
-  st.in(&a.dt, model->dt, model->dt ? t : 0);
-  st.in(&a.V, lw->learn_v ? nullptr : params->V, params->v_stride ? (n - 1) * (size_t)params->v_stride + 1 : 1);   // (a null pointer stages nothing)
-  st.in(&a.m0, params->m0, params->m0_stride ? (n - 1) * (size_t)params->m0_stride + dd : dd);
-  st.in(&a.C0, params->C0, params->c0_stride ? (n - 1) * (size_t)params->c0_stride + dd * dd : dd * dd);
-  st.in(&a.prior_v, lw->learn_v ? prior_v : nullptr, prior_v_stride ? (n - 1) * (size_t)prior_v_stride + 2 : 2);
-  st.in(&a.prior_w, prior_w, prior_w_stride ? (n - 1) * (size_t)prior_w_stride + 2 * dd : 2 * dd);
-  st.in(&a.obs_param, obs_param, obs_param ? n : 0);
-  st.in(&a.y, y, n * t);
-  st.out(&a.ll, ll, n);
-  st.out(&a.mean, mean, mean ? n * t * dd : 0);
-  st.out(&a.ess, ess, ess ? n * t : 0);
+  pf_stage(st, a, model, params, lw->family, lw->literal, lw->n0, P, lw->learn_v ? nullptr : params->V, obs_param, y, opts, iteration, ll, mean, ess, cloud, weights, status);
+  pf_stage_priors(st, a, lw->learn_v, prior_v, prior_v_stride, prior_w, prior_w_stride);
   st.out(&a.psi_mean, psi_mean, psi_mean ? n * t * (dd + 1) : 0);
   st.out(&a.psi_var, psi_var, psi_var ? n * t * (dd + 1) : 0);
-  st.out(&a.cloud, cloud, cloud ? n * dd * np : 0);
-  st.out(&a.weights, weights, weights ? n * np : 0);
   st.out(&a.psi, psi, psi ? n * (dd + 1) * np : 0);
-  st.zeroed_out(&a.status, (int*)status, status ? n : 0);
+  a.a = lw->a;
   if ((rc = st.commit())) return rc;
-  a.d = d; a.T = T; a.N = N; a.P = P;
-  a.family = lw->family; a.literal = lw->literal; a.learn_v = lw->learn_v; a.a = lw->a;
-  a.n0 = lw->n0 < 0 ? P / 5 : lw->n0;
-  a.f_stride = model->f_stride; a.n_g = model->n_g;
-  a.v_stride = params->v_stride; a.m0_stride = params->m0_stride; a.c0_stride = params->c0_stride;
-  a.prior_v_stride = prior_v_stride; a.prior_w_stride = prior_w_stride;
-  a.rs = draw_stream(opts, iteration);
   e->variant = "lw-wave";
   HIP_TRY(e, dlm::launch_lw(a, e->stream));
   return st.finish(opts->flags & DLM_OPT_ASYNC);

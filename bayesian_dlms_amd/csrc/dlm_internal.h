@@ -491,14 +491,16 @@ hipError_t launch_dlmfsv_impute(const DlmFsvImputeArgs& a, hipStream_t s);
 hipError_t launch_dlmfsv_center(const DlmFsvCenterArgs& a, hipStream_t s);
 hipError_t launch_dlmfsv_variance(const DlmFsvVarianceArgs& a, hipStream_t s);
 
-// ---- bootstrap particle filter of a DGLM, one wavefront per series (ParticleFilter.scala:38-85, Dglm.scala:46-175), dlm_pf.hip -------------
-struct PfArgs {
+// ---- the particle filters of a DGLM, one wavefront per series: what all three kernels read and write (dlm_pf_common.h) ---------------------
+// PfArgs and StorvikArgs derive from it.  LwArgs repeats the fields under the same names in the order k_lw was written with: its kernel
+// holds 106 SGPRs, and where the arguments lie decides how many of them it parks in VGPRs -- every derived order that was tried moves its
+// register count at some d (profiles/r23_notes.md).  The host code stages all three through one template.
+struct PfCommonArgs {
   int d, T, N, P;         // P particles, a multiple of 64
-  int family, n0, literal;   // DLM_OBS_*; resample when ESS < n0 (resolved: >= 0); 1: Q37-Q39
+  int family, n0, literal;   // DLM_OBS_*; resample when ESS < n0 (resolved: >= 0); 1: the reference's arithmetic (Q37-Q39, Q43)
   const double* F; long long f_stride;   // F_t = F + t * f_stride (d doubles, p = 1)
   const double* G; int n_g; const int* g_index; const double* dt;
-  const double* V; long long v_stride;   // v = V[n * v_stride]
-  const double* W; long long w_stride;
+  const double* V; long long v_stride;   // v = V[n * v_stride]; k_storvik reads it without learn_v only
   const double* m0; long long m0_stride;
   const double* C0; long long c0_stride;
   const double* obs_param;   // [N], nullable: nu of DLM_OBS_STUDENTT
@@ -510,38 +512,28 @@ struct PfArgs {
   double* cloud;          // [N][d][P], nullable
   double* weights;        // [N][P], nullable
   int* status;            // [N], nullable (zeroed by the caller)
+};
+
+// ---- bootstrap particle filter (ParticleFilter.scala:38-85, Dglm.scala:46-175), dlm_pf.hip ----------------------------------------------
+struct PfArgs : PfCommonArgs {
+  const double* W; long long w_stride;
 };
 size_t pf_lds_bytes(int d, int P);   // the cloud [d][P], the weights and their running sums [2][P], chol(W) and chol(C0)
 hipError_t launch_pf(const PfArgs& a, hipStream_t s);
 
-// ---- Storvik filter of a DGLM: a particle filter that learns the diagonal of W (and V, Gaussian family) online (Storvik.scala:105-159), dlm_storvik.hip ----
-struct StorvikArgs {
-  int d, T, N, P;         // P particles, a multiple of 64
-  int family, n0, literal, learn_v;   // DLM_OBS_*; resample when ESS < n0 (resolved: >= 0); 1: Q39, Q43; 1: V is learned (Gaussian family)
-  const double* F; long long f_stride;   // F_t = F + t * f_stride (d doubles, p = 1)
-  const double* G; int n_g; const int* g_index; const double* dt;
-  const double* V; long long v_stride;   // v = V[n * v_stride], read without learn_v only
-  const double* m0; long long m0_stride;
-  const double* C0; long long c0_stride;
+// ---- Storvik filter: a particle filter that learns the diagonal of W (and V, Gaussian family) online (Storvik.scala:105-159), dlm_storvik.hip ----
+struct StorvikArgs : PfCommonArgs {
+  int learn_v;            // 1: V is learned (Gaussian family)
   const double* prior_v; long long prior_v_stride;   // [2] = (shape, scale) at n * prior_v_stride, read with learn_v only
   const double* prior_w; long long prior_w_stride;   // [d][2] at n * prior_w_stride
-  const double* obs_param;   // [N], nullable: nu of DLM_OBS_STUDENTT
-  const double* y;        // [N][T], NaN = missing
-  DrawStream rs;
-  double* ll;             // [N]
-  double* mean;           // [N][T][d], nullable
-  double* ess;            // [N][T], nullable
   double* scale_mean;     // [N][T][d+1], nullable
-  double* cloud;          // [N][d][P], nullable
-  double* weights;        // [N][P], nullable
   double* scales;         // [N][d+1][P], nullable
-  int* status;            // [N], nullable (zeroed by the caller)
 };
 size_t storvik_lds_bytes(int d, int P);   // the cloud and the scales of W [2 d][P], the scale of V, the weights and their running sums [3][P], chol(C0), the ancestors
 hipError_t launch_storvik(const StorvikArgs& a, hipStream_t s);
 
-// ---- Liu-West filter of a DGLM: an auxiliary particle filter whose particles carry their own log-variances (LiuAndWest.scala:47-81, AuxFilter.scala), dlm_lw.hip ----
-struct LwArgs {
+// ---- Liu-West filter: an auxiliary particle filter whose particles carry their own log-variances (LiuAndWest.scala:47-81, AuxFilter.scala), dlm_lw.hip ----
+struct LwArgs {           // PfCommonArgs' fields and its own, in the order that holds k_lw's register counts (above)
   int d, T, N, P;         // P particles, a multiple of 64
   int family, n0, literal, learn_v;   // DLM_OBS_*; the second stage resamples when ESS < n0 (resolved: >= 0); 1: Q39, Q50, Q51; 1: log V is a row of psi
   double a;               // the shrinkage, 0 < a <= 1

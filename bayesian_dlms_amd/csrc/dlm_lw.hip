@@ -10,25 +10,18 @@
 // The first-stage log-density lambda_i travels with its particle through the auxiliary gather in wg: the running sums of the first-stage
 // weights are formed IN PLACE in wg (cum holds lambda meanwhile), and once the ancestors are known wg is free and takes lambda_anc.
 //
-// The orders of every sum are DESIGN.md 4.19's (dlm_pf_common.h) and 4.21's; tests/lw_restatement.py follows the kernel operation for operation.
+// The normals, the searches, the gathers, the second stage's normalisation and its resampling are dlm_pf_common.h's; the initial cloud and the
+// results of a series are written out here (below).  The orders of every sum are DESIGN.md 4.19's and 4.21's; tests/lw_restatement.py follows
+// the kernel operation for operation.
 #include "dlm_pf_common.h"
 
 namespace dlm {
 namespace {
 
-// the two uniforms of (slot, particle, block): u1 in (0, 1], u2 in [0, 1)
-__device__ __forceinline__ void lw_rand(const DrawStream& rs, unsigned long long series, unsigned slot, unsigned particle, unsigned block,
-                                        double& u1, double& u2) {
-  gibbs_rand(rs.seed, series, rs.iteration, slot, particle, 0u, u1, u2, DLM_KEY_LW | block);
-}
-
-// z_r ~ N(0, 1), component r of (slot, particle) in the group of blocks that starts at `base` (0: the state, DLM_LW_BLOCK_PARAM: the
-// log-variances): block base + r / 2 gives the Box-Muller pair, the cosine for an even r and the sine for an odd one
+// z_r ~ N(0, 1) of (slot, particle): pf_normal under the filter's key; the group of blocks `base` is 0 for the state and DLM_LW_BLOCK_PARAM
+// for the log-variances
 __device__ __forceinline__ double lw_normal(const DrawStream& rs, unsigned long long series, unsigned slot, unsigned particle, unsigned base, int r) {
-  double u1, u2;
-  lw_rand(rs, series, slot, particle, base + (unsigned)(r >> 1), u1, u2);
-  const double rad = sqrt(-2.0 * log(u1)), ang = PF_2PI * u2;
-  return rad * ((r & 1) ? sin(ang) : cos(ang));
+  return pf_normal(DLM_KEY_LW, rs, series, slot, particle, base, r);
 }
 
 // sum_i W_i row_i and, in a second pass, the centred second moment sum_i W_i (row_i - mean)^2: both sum like pf_means
@@ -42,16 +35,6 @@ __device__ __forceinline__ void lw_moments(const double* row, const double* wg, 
     acc = acc + wg[i] * (e * e);
   }
   var = wave_sum(acc);
-}
-
-// the gather of the tuple's `rows` rows (they start at x) by ancestor, row by row through `buf`
-__device__ __forceinline__ void lw_gather(double* x, int rows, double* buf, const int* anc, int P, int lane) {
-  for (int k = 0; k < rows; ++k) {
-    for (int i = lane; i < P; i += 64) buf[i] = x[k * P + anc[i]];
-    wave_sync();
-    for (int i = lane; i < P; i += 64) x[k * P + i] = buf[i];
-    wave_sync();
-  }
 }
 
 template <int D>
@@ -107,7 +90,7 @@ __global__ __launch_bounds__(64, D <= 8 ? 2 : 1) void k_lw(LwArgs a) {
   if (!pf_chol<D>(a.C0 + (size_t)n * a.c0_stride, sl, lane)) bad = DLM_ST_NOT_PD;
   if (!bad) {
     const double* m0 = a.m0 + (size_t)n * a.m0_stride;
-    for (int i = lane; i < P; i += 64) {
+    for (int i = lane; i < P; i += 64) {   // (not pf_init_cloud with psi as its rows: that takes a register off d = 4 and d = 10)
       double z[D];
 #pragma unroll
       for (int c = 0; c < D; ++c) z[c] = lw_normal(a.rs, series, DLM_LW_SLOT_INIT, (unsigned)i, 0u, c);
@@ -228,15 +211,11 @@ __global__ __launch_bounds__(64, D <= 8 ? 2 : 1) void k_lw(LwArgs a) {
       ll = ll + (m1 + log(A));
       const double total1 = pf_running_sums(wg, wg, P, lane);   // in place: a lane reads and writes its own particle
       wave_sync();
-      for (int i = lane; i < P; i += 64) {
-        double u1, u2;
-        lw_rand(a.rs, series, (unsigned)t, (unsigned)i, DLM_LW_BLOCK_FIRST, u1, u2);
-        anc[i] = pf_ancestor(wg, P, u2 * total1);
-      }
+      pf_search(DLM_KEY_LW | DLM_LW_BLOCK_FIRST, a.rs, series, (unsigned)t, wg, total1, anc, P, lane);
       wave_sync();
       for (int i = lane; i < P; i += 64) wg[i] = cum[anc[i]];   // lambda of the ancestor
       wave_sync();
-      lw_gather(x, D + rows_psi, cum, anc, P, lane);
+      pf_gather(x, D + rows_psi, cum, anc, P, lane);
 
       // -- propagate: psi' = m + h s z', x' = mu + sqrt(dt exp psi') z, l = log p(y | F^T x', exp psi'_d or V) - lambda into cum
       mx = -__builtin_inf();
@@ -286,34 +265,18 @@ __global__ __launch_bounds__(64, D <= 8 ? 2 : 1) void k_lw(LwArgs a) {
       const double B = wave_sum(part);
       if (!(B > 0.0 && B < __builtin_inf())) { bad = DLM_ST_NONFINITE; t_bad = t; break; }
       ll = ll + (m2 + log(B / (double)P));
-      part = 0.0;
-      for (int i = lane; i < P; i += 64) {
-        const double w = wg[i] / B;
-        wg[i] = w;
-        part = part + w * w;
-      }
-      const double sq = wave_sum(part);
+      const double sq = pf_normalise(wg, B, P, lane);
       outputs(t);
       ess_last = floor(1.0 / sq);
       if (ess && lane == 0) ess[t] = ess_last;
       if (!(ess_last < (double)a.n0)) continue;
 
       // -- multinomial resampling of the whole tuple (x, psi)
-      const double total2 = pf_running_sums(wg, cum, P, lane);
-      wave_sync();
-      for (int i = lane; i < P; i += 64) {
-        double u1, u2;
-        lw_rand(a.rs, series, (unsigned)t, (unsigned)i, DLM_LW_BLOCK_RESAMPLE, u1, u2);
-        anc[i] = pf_ancestor(cum, P, u2 * total2);
-      }
-      wave_sync();
-      lw_gather(x, D + rows_psi, cum, anc, P, lane);
-      for (int i = lane; i < P; i += 64) wg[i] = rP;
-      wave_sync();
+      pf_resample(DLM_KEY_LW | DLM_LW_BLOCK_RESAMPLE, a.rs, series, (unsigned)t, x, D + rows_psi, wg, rP, cum, anc, P, lane);
     }
   }
 
-  // ---- results
+  // ---- results (not pf_results: that adds a register at d = 9 and takes one off d = 10)
   if (bad) {
     ll = -__builtin_inf();
     if (mean) for (int j = t_bad * D + lane; j < T * D; j += 64) mean[j] = nan;

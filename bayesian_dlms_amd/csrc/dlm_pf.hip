@@ -11,7 +11,9 @@
 //   inclusive running sums of the weights           per slot the Hillis-Steele scan over the lanes (offsets 1, 2, 4, 8, 16, 32: v = v + v[lane - off]),
 //                                                   plus the carry = the running sum at the previous slot's lane 63 (carry + v);
 //   matrix-vector products                          index ascending from 0, the first product starts the sum.
-// No atomics, no dependence on N or on the neighbours.
+// No atomics, no dependence on N or on the neighbours.  The initial cloud, the weights from the log-weights, the resampling and the results
+// of a series are dlm_pf_common.h's, shared with k_storvik and k_lw; the paired normals pf_normals, which draw each Philox block once, are
+// this kernel's own.
 #include "dlm_pf_common.h"
 
 namespace dlm {
@@ -46,7 +48,7 @@ __global__ __launch_bounds__(64, D <= 8 ? 2 : 1) void k_pf(PfArgs a) {
   double* sl = cum + P;            // [D][D] row-major
   int* anc = (int*)(sl + D * D);   // [P]
   const unsigned long long series = a.rs.series_offset + (unsigned long long)n;
-  const double rP = 1.0 / (double)P, nan = __builtin_nan("");
+  const double rP = 1.0 / (double)P;
   const double* y = a.y + (size_t)n * T;
   double* mean = a.mean ? a.mean + (size_t)n * T * D : nullptr;
   double* ess = a.ess ? a.ess + (size_t)n * T : nullptr;
@@ -57,19 +59,8 @@ __global__ __launch_bounds__(64, D <= 8 ? 2 : 1) void k_pf(PfArgs a) {
   // ---- the initial cloud x_0,i = m0 + chol(C0) z, then chol(W) for the steps
   if (!pf_chol<D>(a.C0 + (size_t)n * a.c0_stride, sl, lane)) bad = DLM_ST_NOT_PD;
   if (!bad) {
-    const double* m0 = a.m0 + (size_t)n * a.m0_stride;
-    for (int i = lane; i < P; i += 64) {
-      double z[D];
-      pf_normals<D>(a.rs, series, DLM_PF_SLOT_INIT, (unsigned)i, z);
-#pragma nounroll
-      for (int r = 0; r < D; ++r) {   // (a loop over r in the code: unrolled, the compiler holds every factor of every row in registers across the particles)
-        double acc = sl[r * D] * z[0];
-#pragma unroll
-        for (int c = 1; c < D; ++c) acc = acc + sl[r * D + c] * z[c];
-        x[r * P + i] = m0[r] + acc;
-      }
-      wg[i] = rP;
-    }
+    pf_init_cloud<D>(a.m0 + (size_t)n * a.m0_stride, sl, x, wg, rP, P, lane,
+                     [&](int i, double (&z)[D]) { pf_normals<D>(a.rs, series, DLM_PF_SLOT_INIT, (unsigned)i, z); }, [](int, int) {});
     wave_sync();
     if (!pf_chol<D>(a.W + (size_t)n * a.w_stride, sl, lane)) bad = DLM_ST_NOT_PD;
   }
@@ -127,70 +118,21 @@ __global__ __launch_bounds__(64, D <= 8 ? 2 : 1) void k_pf(PfArgs a) {
       const double m = wave_max(mx);
       if (!(fabs(m) < __builtin_inf())) { bad = DLM_ST_NONFINITE; t_bad = t; break; }
 
-      // -- omega_i = W_{t-1,i} exp(l_i - m), their sum
-      double part = 0.0;
-      for (int i = lane; i < P; i += 64) {
-        const double om = (a.literal ? rP : wg[i]) * exp(cum[i] - m);   // Q37: the literal filter forgets the weights it did not resample
-        wg[i] = om;
-        part = part + om;
-      }
-      const double stot = wave_sum(part);
+      // -- omega_i = W_{t-1,i} exp(l_i - m), their sum; W_t,i = omega_i / s, sum W^2, the filtering mean
+      const double stot = pf_omega(cum, m, wg, a.literal, rP, P, lane);
       if (!(stot > 0.0 && stot < __builtin_inf())) { bad = DLM_ST_NONFINITE; t_bad = t; break; }
       ll = ll + (m + log(stot));
-
-      // -- W_t,i = omega_i / s, sum W^2, the filtering mean
-      part = 0.0;
-      for (int i = lane; i < P; i += 64) {
-        const double w = wg[i] / stot;
-        wg[i] = w;
-        part = part + w * w;
-      }
-      const double sq = wave_sum(part);
+      const double sq = pf_normalise(wg, stot, P, lane);
       if (mean) pf_means<D>(x, wg, P, lane, mean + (size_t)t * D);
       ess_last = floor(1.0 / sq);
       if (ess && lane == 0) ess[t] = ess_last;
       if (!(ess_last < (double)a.n0)) continue;
 
-      // -- multinomial resampling: the running sums, the searches, the gather component by component
-      const double total = pf_running_sums(wg, cum, P, lane);
-      wave_sync();
-      for (int i = lane; i < P; i += 64) {
-        double u1, u2;
-        pf_rand(a.rs, series, (unsigned)t, (unsigned)i, DLM_PF_BLOCK_RESAMPLE, u1, u2);
-        anc[i] = pf_ancestor(cum, P, u2 * total);
-      }
-      wave_sync();
-      for (int k = 0; k < D; ++k) {
-        for (int i = lane; i < P; i += 64) cum[i] = x[k * P + anc[i]];
-        wave_sync();
-        for (int i = lane; i < P; i += 64) x[k * P + i] = cum[i];
-        wave_sync();
-      }
-      for (int i = lane; i < P; i += 64) wg[i] = rP;
-      wave_sync();
+      pf_resample(DLM_KEY_PF | DLM_PF_BLOCK_RESAMPLE, a.rs, series, (unsigned)t, x, D, wg, rP, cum, anc, P, lane);   // component by component
     }
   }
 
-  // ---- results
-  if (bad) {
-    ll = -__builtin_inf();
-    if (mean) for (int j = t_bad * D + lane; j < T * D; j += 64) mean[j] = nan;
-    if (ess) for (int j = t_bad + lane; j < T; j += 64) ess[j] = nan;
-  }
-  if (lane == 0) {
-    a.ll[n] = ll;
-    if (a.status && bad) a.status[n] = bad;
-  }
-  const bool no_cloud = (bad & DLM_ST_NOT_PD) != 0;
-  if (a.cloud) {
-    double* c = a.cloud + (size_t)n * D * P;
-    for (int k = 0; k < D; ++k)
-      for (int i = lane; i < P; i += 64) c[(size_t)k * P + i] = no_cloud ? nan : x[k * P + i];
-  }
-  if (a.weights) {
-    double* w = a.weights + (size_t)n * P;
-    for (int i = lane; i < P; i += 64) w[i] = bad ? nan : wg[i];
-  }
+  pf_results<D>(a, n, lane, bad, t_bad, ll, x, wg, mean, ess, nullptr, nullptr, nullptr, 0);
 }
 
 }  // namespace

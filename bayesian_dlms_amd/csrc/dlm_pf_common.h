@@ -1,7 +1,10 @@
-// What the particle kernels share (dlm_pf.hip: k_pf, dlm_storvik.hip: k_storvik), each defined here ONCE: the Cholesky factor of the initial
-// cloud, the six observation densities of Dglm.scala:46-175, the weighted means over the particles, and the running sums and the search of
-// the multinomial resampling.  One wavefront per series, particle i = 64 s + lane, rows of P doubles in LDS; the orders of every sum are
-// those of DESIGN.md 4.19.
+// What the particle kernels share (dlm_pf.hip: k_pf, dlm_storvik.hip: k_storvik, dlm_lw.hip: k_lw), each defined here ONCE: the Cholesky
+// factor of the initial cloud, the six observation densities of Dglm.scala:46-175, the weighted means over the particles, the normal of one
+// component (pf_normal), the initial cloud (pf_init_cloud), the two loops that turn log-weights into weights (pf_omega, pf_normalise), the
+// multinomial resampling (pf_resample: pf_running_sums, pf_search over pf_ancestor, pf_gather) and the results of a series (pf_results).
+// One wavefront per series, particle i = 64 s + lane, rows of P doubles in LDS; the orders of every sum are those of DESIGN.md 4.19.
+// Every helper is inlined into its kernel; k_pf and k_storvik use all of them, k_lw all but pf_init_cloud and pf_results, either of which
+// moves its register count at some d (profiles/r23_notes.md).
 #pragma once
 #include "dlm_wave.h"
 #include "dlm_draws.h"
@@ -127,6 +130,136 @@ __device__ __forceinline__ int pf_ancestor(const double* cum, int P, double targ
     if (cum[mid] > target) hi = mid; else lo = mid + 1;
   }
   return lo;
+}
+
+// z_r ~ N(0, 1), component r of (slot, particle) in the group of blocks of the kernel's `key` that starts at `base`: block base + r / 2 gives
+// the Box-Muller pair, the cosine for an even r and the sine for an odd one
+__device__ __forceinline__ double pf_normal(unsigned key, const DrawStream& rs, unsigned long long series, unsigned slot, unsigned particle,
+                                            unsigned base, int r) {
+  double u1, u2;
+  gibbs_rand(rs.seed, series, rs.iteration, slot, particle, 0u, u1, u2, key | (base + (unsigned)(r >> 1)));
+  const double rad = sqrt(-2.0 * log(u1)), ang = PF_2PI * u2;
+  return rad * ((r & 1) ? sin(ang) : cos(ang));
+}
+
+// The initial cloud x_0,i = m0 + sl z_i (sl = chol(C0), row-major) with the weights rP = 1 / P.  normals(i, z) draws z_i; row(r, i) fills what
+// else the kernel keeps of particle i beside its component r < D, and once more with r = D
+template <int D, class Normals, class Row>
+__device__ __forceinline__ void pf_init_cloud(const double* m0, const double* sl, double* x, double* wg, double rP, int P, int lane,
+                                              Normals&& normals, Row&& row) {
+  for (int i = lane; i < P; i += 64) {
+    double z[D];
+    normals(i, z);
+#pragma nounroll
+    for (int r = 0; r < D; ++r) {   // (a loop over r in the code: unrolled, the compiler holds every factor of every row in registers across the particles)
+      double acc = sl[r * D] * z[0];
+#pragma unroll
+      for (int c = 1; c < D; ++c) acc = acc + sl[r * D + c] * z[c];
+      x[r * P + i] = m0[r] + acc;
+      row(r, i);
+    }
+    row(D, i);
+    wg[i] = rP;
+  }
+}
+
+// omega_i = W_{t-1,i} exp(l_i - m) into wg from the log-weights l_i in cum and their maximum m (the literal filter forgets the weights it
+// did not resample and takes rP = 1 / P: Q37, Q43); returns their sum.  (This and pf_normalise are two plain loops: one function with the
+// tests between them costs k_pf and k_storvik two registers)
+__device__ __forceinline__ double pf_omega(const double* cum, double m, double* wg, int literal, double rP, int P, int lane) {
+  double part = 0.0;
+  for (int i = lane; i < P; i += 64) {
+    const double om = (literal ? rP : wg[i]) * exp(cum[i] - m);
+    wg[i] = om;
+    part = part + om;
+  }
+  return wave_sum(part);
+}
+
+// W_t,i = omega_i / stot in place; returns sum W^2
+__device__ __forceinline__ double pf_normalise(double* wg, double stot, int P, int lane) {
+  double part = 0.0;
+  for (int i = lane; i < P; i += 64) {
+    const double w = wg[i] / stot;
+    wg[i] = w;
+    part = part + w * w;
+  }
+  return wave_sum(part);
+}
+
+// the ancestors of a multinomial resampling: anc_i = pf_ancestor at u_i total, u_i the second uniform of (slot, particle i) under key_block
+__device__ __forceinline__ void pf_search(unsigned key_block, const DrawStream& rs, unsigned long long series, unsigned slot, const double* cum,
+                                          double total, int* anc, int P, int lane) {
+  for (int i = lane; i < P; i += 64) {
+    double u1, u2;
+    gibbs_rand(rs.seed, series, rs.iteration, slot, (unsigned)i, 0u, u1, u2, key_block);
+    anc[i] = pf_ancestor(cum, P, u2 * total);
+  }
+}
+
+// the gather of a particle's tuple, the `rows` rows of P that start at x, by ancestor: row by row through `buf`
+__device__ __forceinline__ void pf_gather(double* x, int rows, double* buf, const int* anc, int P, int lane) {
+  for (int k = 0; k < rows; ++k) {
+    for (int i = lane; i < P; i += 64) buf[i] = x[k * P + anc[i]];
+    wave_sync();
+    for (int i = lane; i < P; i += 64) x[k * P + i] = buf[i];
+    wave_sync();
+  }
+}
+
+// multinomial resampling of the tuples under the weights wg: the running sums into cum, the searches, the gather, the weights back to rP = 1 / P
+__device__ __forceinline__ void pf_resample(unsigned key_block, const DrawStream& rs, unsigned long long series, unsigned slot, double* x,
+                                            int rows, double* wg, double rP, double* cum, int* anc, int P, int lane) {
+  const double total = pf_running_sums(wg, cum, P, lane);
+  wave_sync();
+  pf_search(key_block, rs, series, slot, cum, total, anc, P, lane);
+  wave_sync();
+  pf_gather(x, rows, cum, anc, P, lane);
+  for (int i = lane; i < P; i += 64) wg[i] = rP;
+  wave_sync();
+}
+
+// NaN into the steps t_bad .. T - 1 of a per-step output of `width` doubles a step (a null pointer: nothing)
+__device__ __forceinline__ void pf_no_results(double* out, int width, int t_bad, int T, int lane) {
+  if (out) for (int j = t_bad * width + lane; j < T * width; j += 64) out[j] = __builtin_nan("");
+}
+
+// The results of series n: ll (-inf with a status bit), the status, NaN from the first step without results on in the series' mean, ess
+// and the kernel's own per-step outputs step0 and step1 ([T][D + 1]; all four nullable); the cloud (NaN when it was never made), the weights, and into `own`
+// ([D + 1][P], nullable) the kernel's rows behind the cloud, the first `valid` of them (the others NaN)
+template <int D, class Args>
+__device__ __forceinline__ void pf_results(const Args& a, int n, int lane, int bad, int t_bad, double ll, const double* x,
+                                           const double* wg, double* mean, double* ess, double* step0, double* step1, double* own,
+                                           int valid) {
+  const int P = a.P, T = a.T;
+  const double nan = __builtin_nan("");
+  if (bad) {
+    ll = -__builtin_inf();
+    pf_no_results(mean, D, t_bad, T, lane);
+    pf_no_results(step0, D + 1, t_bad, T, lane);
+    pf_no_results(step1, D + 1, t_bad, T, lane);
+    pf_no_results(ess, 1, t_bad, T, lane);
+  }
+  if (lane == 0) {
+    a.ll[n] = ll;
+    if (a.status && bad) a.status[n] = bad;
+  }
+  const bool no_cloud = (bad & DLM_ST_NOT_PD) != 0;
+  if (a.cloud) {
+    double* c = a.cloud + (size_t)n * D * P;
+    for (int k = 0; k < D; ++k)
+      for (int i = lane; i < P; i += 64) c[(size_t)k * P + i] = no_cloud ? nan : x[k * P + i];
+  }
+  if (a.weights) {
+    double* w = a.weights + (size_t)n * P;
+    for (int i = lane; i < P; i += 64) w[i] = bad ? nan : wg[i];
+  }
+  if (own) {
+    double* o = own + (size_t)n * (D + 1) * P;
+    const double* rows = x + (size_t)D * P;
+    for (int k = 0; k <= D; ++k)
+      for (int i = lane; i < P; i += 64) o[(size_t)k * P + i] = (bad || k >= valid) ? nan : rows[k * P + i];
+  }
 }
 
 }  // namespace

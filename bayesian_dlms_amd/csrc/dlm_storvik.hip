@@ -10,7 +10,8 @@
 // The statistics are updated BEFORE the gather, on the particle that made the move: x_{t-1} and x_t of an update are always one particle's
 // own (the reference pairs the old cloud with the resampled one, Storvik.scala:139-141, Q42).
 //
-// The orders of every sum are DESIGN.md 4.19's (dlm_pf_common.h); scale_mean sums like the means.  tests/storvik_restatement.py follows the
+// The orders of every sum are DESIGN.md 4.19's; the initial cloud (the statistics at their priors are its extra rows), the normals, the weights
+// from the log-weights, the resampling and the results of a series are dlm_pf_common.h's.  scale_mean sums like the means.  tests/storvik_restatement.py follows the
 // kernel operation for operation.
 #include "dlm_pf_common.h"
 
@@ -21,14 +22,6 @@ namespace {
 __device__ __forceinline__ void st_rand(unsigned long long seed, unsigned long long series, unsigned long long iteration, unsigned slot,
                                         unsigned particle, unsigned block, unsigned attempt, unsigned which, double& u1, double& u2) {
   gibbs_rand(seed, series, iteration, slot, particle, which, u1, u2, DLM_KEY_STORVIK | (attempt << 8) | block);
-}
-
-// z_r ~ N(0, 1), component r of (slot, particle): block r / 2 gives the Box-Muller pair, the cosine for an even r and the sine for an odd one
-__device__ __forceinline__ double st_normal(const DrawStream& rs, unsigned long long series, unsigned slot, unsigned particle, int r) {
-  double u1, u2;
-  st_rand(rs.seed, series, rs.iteration, slot, particle, (unsigned)(r >> 1), 0u, 0u, u1, u2);
-  const double rad = sqrt(-2.0 * log(u1)), ang = PF_2PI * u2;
-  return rad * ((r & 1) ? sin(ang) : cos(ang));
 }
 
 // Gamma(shape, 1) of component comp (k < d: W_kk, d: V) of (slot, particle).  The kernel has ONE call site of it, the row loop of a step:
@@ -79,23 +72,13 @@ __global__ __launch_bounds__(64, D <= 8 ? 2 : 1) void k_storvik(StorvikArgs a) {
   if (a.learn_v && !(pv[0] > 0.0 && pv[1] > 0.0)) bad = DLM_ST_NOT_PD;
   if (!pf_chol<D>(a.C0 + (size_t)n * a.c0_stride, sl, lane)) bad = DLM_ST_NOT_PD;
   if (!bad) {
-    const double* m0 = a.m0 + (size_t)n * a.m0_stride;
     const double bv0 = a.learn_v ? pv[1] : 0.0;
-    for (int i = lane; i < P; i += 64) {
-      double z[D];
+    pf_init_cloud<D>(a.m0 + (size_t)n * a.m0_stride, sl, x, wg, rP, P, lane,
+                     [&](int i, double (&z)[D]) {
 #pragma unroll
-      for (int c = 0; c < D; ++c) z[c] = st_normal(a.rs, series, DLM_STORVIK_SLOT_INIT, (unsigned)i, c);
-#pragma nounroll
-      for (int r = 0; r < D; ++r) {
-        double acc = sl[r * D] * z[0];
-#pragma unroll
-        for (int c = 1; c < D; ++c) acc = acc + sl[r * D + c] * z[c];
-        x[r * P + i] = m0[r] + acc;
-        bw[r * P + i] = pw[2 * r + 1];
-      }
-      bv[i] = bv0;
-      wg[i] = rP;
-    }
+                       for (int c = 0; c < D; ++c) z[c] = pf_normal(DLM_KEY_STORVIK, a.rs, series, DLM_STORVIK_SLOT_INIT, (unsigned)i, 0u, c);
+                     },
+                     [&](int r, int i) { bw[r * P + i] = r < D ? pw[2 * r + 1] : bv0; });   // (row D of bw is bv)
     wave_sync();
   }
 
@@ -133,7 +116,7 @@ __global__ __launch_bounds__(64, D <= 8 ? 2 : 1) void k_storvik(StorvikArgs a) {
             double gx = G[r] * xo[0];
 #pragma unroll
             for (int c = 1; c < D; ++c) gx = gx + G[r + c * D] * xo[c];
-            const double z = st_normal(a.rs, series, (unsigned)t, (unsigned)i, r);
+            const double z = pf_normal(DLM_KEY_STORVIK, a.rs, series, (unsigned)t, (unsigned)i, 0u, r);
             const double b = bw[r * P + i];
             const double w = b / g;
             const double xn = gx + sqrt(dte * w) * z;
@@ -167,77 +150,22 @@ __global__ __launch_bounds__(64, D <= 8 ? 2 : 1) void k_storvik(StorvikArgs a) {
       const double m = wave_max(mx);
       if (!(fabs(m) < __builtin_inf())) { bad = DLM_ST_NONFINITE; t_bad = t; break; }
 
-      // -- omega_i = W_{t-1,i} exp(l_i - m), their sum
-      double part = 0.0;
-      for (int i = lane; i < P; i += 64) {
-        const double om = (a.literal ? rP : wg[i]) * exp(cum[i] - m);   // Q43 (Q37's form): the literal filter forgets the weights it did not resample
-        wg[i] = om;
-        part = part + om;
-      }
-      const double stot = wave_sum(part);
+      // -- omega_i = W_{t-1,i} exp(l_i - m), their sum; W_t,i = omega_i / s, sum W^2, the means
+      const double stot = pf_omega(cum, m, wg, a.literal, rP, P, lane);
       if (!(stot > 0.0 && stot < __builtin_inf())) { bad = DLM_ST_NONFINITE; t_bad = t; break; }
       ll = ll + (m + log(stot));
-
-      // -- W_t,i = omega_i / s, sum W^2, the means
-      part = 0.0;
-      for (int i = lane; i < P; i += 64) {
-        const double w = wg[i] / stot;
-        wg[i] = w;
-        part = part + w * w;
-      }
-      const double sq = wave_sum(part);
+      const double sq = pf_normalise(wg, stot, P, lane);
       outputs(t);
       ess_last = floor(1.0 / sq);
       if (ess && lane == 0) ess[t] = ess_last;
       if (!(ess_last < (double)a.n0)) continue;
 
-      // -- multinomial resampling: the running sums, the searches, the gather of the whole tuple (x, bw, bv) row by row
-      const double total = pf_running_sums(wg, cum, P, lane);
-      wave_sync();
-      for (int i = lane; i < P; i += 64) {
-        double u1, u2;
-        st_rand(a.rs.seed, series, a.rs.iteration, (unsigned)t, (unsigned)i, DLM_STORVIK_BLOCK_RESAMPLE, 0u, 0u, u1, u2);
-        anc[i] = pf_ancestor(cum, P, u2 * total);
-      }
-      wave_sync();
-      const int rows = 2 * D + (a.learn_v ? 1 : 0);
-      for (int k = 0; k < rows; ++k) {
-        for (int i = lane; i < P; i += 64) cum[i] = x[k * P + anc[i]];
-        wave_sync();
-        for (int i = lane; i < P; i += 64) x[k * P + i] = cum[i];
-        wave_sync();
-      }
-      for (int i = lane; i < P; i += 64) wg[i] = rP;
-      wave_sync();
+      // -- multinomial resampling of the whole tuple (x, bw, bv)
+      pf_resample(DLM_KEY_STORVIK | DLM_STORVIK_BLOCK_RESAMPLE, a.rs, series, (unsigned)t, x, 2 * D + (a.learn_v ? 1 : 0), wg, rP, cum, anc, P, lane);
     }
   }
 
-  // ---- results
-  if (bad) {
-    ll = -__builtin_inf();
-    if (mean) for (int j = t_bad * D + lane; j < T * D; j += 64) mean[j] = nan;
-    if (smean) for (int j = t_bad * (D + 1) + lane; j < T * (D + 1); j += 64) smean[j] = nan;
-    if (ess) for (int j = t_bad + lane; j < T; j += 64) ess[j] = nan;
-  }
-  if (lane == 0) {
-    a.ll[n] = ll;
-    if (a.status && bad) a.status[n] = bad;
-  }
-  const bool no_cloud = (bad & DLM_ST_NOT_PD) != 0;
-  if (a.cloud) {
-    double* c = a.cloud + (size_t)n * D * P;
-    for (int k = 0; k < D; ++k)
-      for (int i = lane; i < P; i += 64) c[(size_t)k * P + i] = no_cloud ? nan : x[k * P + i];
-  }
-  if (a.weights) {
-    double* w = a.weights + (size_t)n * P;
-    for (int i = lane; i < P; i += 64) w[i] = bad ? nan : wg[i];
-  }
-  if (a.scales) {   // [D + 1][P]: the rows of bw, then bv (NaN without learn_v)
-    double* sc = a.scales + (size_t)n * (D + 1) * P;
-    for (int k = 0; k <= D; ++k)
-      for (int i = lane; i < P; i += 64) sc[(size_t)k * P + i] = (bad || (k == D && !a.learn_v)) ? nan : bw[k * P + i];
-  }
+  pf_results<D>(a, n, lane, bad, t_bad, ll, x, wg, mean, ess, smean, nullptr, a.scales, D + (a.learn_v ? 1 : 0));
 }
 
 }  // namespace

@@ -202,6 +202,22 @@ def _observations(ys):
     return times, y[:, :, 0]
 
 
+def _filter_inputs(mod, ys, n):
+    """Model and observations of a filter of n particles -> (times, y [N][T], d, mat), after the check of the shape."""
+    times, y = _observations(ys)
+    f0 = np.atleast_2d(np.asarray(mod.f(float(times[0])), dtype=np.float64))
+    check_pf_shape(f0.shape[0], f0.shape[1], n)
+    return times, y, f0.shape[0], materialise_pf(mod, times)
+
+
+def _prior_rows(prior_w, d, first, second, noun):
+    """One prior or d of them -> [d][2], the attributes `first` and `second` of each; `noun` names the prior in the message."""
+    pws = [prior_w] * d if hasattr(prior_w, first) and hasattr(prior_w, second) else list(prior_w)
+    if len(pws) != d:
+        raise EngineError(f"prior_w: one {noun} or d = {d} of them, got {len(pws)}")
+    return np.array([[getattr(q, first), getattr(q, second)] for q in pws], dtype=np.float64)
+
+
 class ParticleFilter:
     """ParticleFilter(n, n0, multinomialResample) (ParticleFilter.scala:26-71) on the engine: n particles, resampling when ESS < n0
     (negative: floor(n / 5), what ParticleFilter.likelihood passes)."""
@@ -215,10 +231,7 @@ class ParticleFilter:
         BatchedParameters; with ONE series and several parameter sets every set filters that series (a bank of parameters, as the
         particle-marginal sampler needs).  Returns {"ll" [N], "mean" [N][T][d], "ess" [N][T], "cloud" [N][d][n], "weights" [N][n],
         "status" [N]} as NumPy arrays."""
-        times, y = _observations(ys)
-        f0 = np.atleast_2d(np.asarray(mod.f(float(times[0])), dtype=np.float64))
-        check_pf_shape(f0.shape[0], f0.shape[1], self.n)
-        mat = materialise_pf(mod, times)
+        times, y, d, mat = _filter_inputs(mod, ys, self.n)
         if isinstance(p, DlmParameters):
             N, params = y.shape[0], p
         else:
@@ -257,16 +270,9 @@ class StorvikFilter:
         "shape_w" [N][T][d] and "shape_v" [N][T] of the posteriors after step t (prior + 0.5 per advance / per observation: the time grid
         and the missing pattern fix them, the kernel does not write them), and the Rao-Blackwellised posterior means "w_mean" [N][T][d] =
         scale_mean / (shape - 1) and "v_mean" [N][T], NaN where the shape is <= 1 (and v_mean where V is not learned)."""
-        times, y = _observations(ys)
-        f0 = np.atleast_2d(np.asarray(mod.f(float(times[0])), dtype=np.float64))
-        d = f0.shape[0]
-        check_pf_shape(d, f0.shape[1], self.n)
-        mat = materialise_pf(mod, times)
+        times, y, d, mat = _filter_inputs(mod, ys, self.n)
         learn_v = mod.family == _lib.OBS_GAUSSIAN if learn_v is None else bool(learn_v)
-        pws = [prior_w] * d if hasattr(prior_w, "shape") and hasattr(prior_w, "scale") else list(prior_w)
-        if len(pws) != d:
-            raise EngineError(f"prior_w: one InverseGamma or d = {d} of them, got {len(pws)}")
-        pw = np.array([[q.shape, q.scale] for q in pws], dtype=np.float64)
+        pw = _prior_rows(prior_w, d, "shape", "scale", "InverseGamma")
         pv = np.array([prior_v.shape, prior_v.scale], dtype=np.float64) if learn_v else None
         out = eng.storvik_filter(mat, p, y, pw, family=mod.family, n_particles=self.n, prior_v=pv, learn_v=learn_v, n0=self.n0,
                                  literal=literal, obs_param=mod.nu, iteration=iteration, seed=seed, series_offset=series_offset)
@@ -302,16 +308,9 @@ class LiuAndWestFilter:
         ParticleFilter.filter returns plus the raw "psi_mean" and "psi_var" [N][T][d+1] (mean and variance of the log-variances under the
         weights of step t, V's last), "psi" [N][d+1][n], and the posterior means of the variances from the log-normal moments,
         "w_mean" [N][T][d] = exp(psi_mean + psi_var / 2) and "v_mean" [N][T] (NaN where V is not learned)."""
-        times, y = _observations(ys)
-        f0 = np.atleast_2d(np.asarray(mod.f(float(times[0])), dtype=np.float64))
-        d = f0.shape[0]
-        check_pf_shape(d, f0.shape[1], self.n)
-        mat = materialise_pf(mod, times)
+        times, y, d, mat = _filter_inputs(mod, ys, self.n)
         learn_v = mod.family in (_lib.OBS_GAUSSIAN, _lib.OBS_STUDENTT, _lib.OBS_BETA) if learn_v is None else bool(learn_v)
-        pws = [prior_w] * d if hasattr(prior_w, "mean") and hasattr(prior_w, "sd") else list(prior_w)
-        if len(pws) != d:
-            raise EngineError(f"prior_w: one Gaussian or d = {d} of them, got {len(pws)}")
-        pw = np.array([[q.mean, q.sd] for q in pws], dtype=np.float64)
+        pw = _prior_rows(prior_w, d, "mean", "sd", "Gaussian")
         pv = np.array([prior_v.mean, prior_v.sd], dtype=np.float64) if learn_v else None
         out = eng.lw_filter(mat, p, y, pw, family=mod.family, n_particles=self.n, a=self.a, prior_v=pv, learn_v=learn_v, n0=self.n0,
                             literal=literal, obs_param=mod.nu, iteration=iteration, seed=seed, series_offset=series_offset)

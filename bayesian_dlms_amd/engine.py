@@ -79,6 +79,54 @@ def check_pf_shape(d: int, p: int, n_particles: int):
                           f"(one wavefront per series, whole slots of particles), got {n_particles}")
 
 
+def _pf_shape(mat, n_particles, family):
+    """(d, T, P) of a call of one of the three particle filters, after the checks of its shape and of its family."""
+    P = int(n_particles)
+    check_pf_shape(mat.d, mat.p, P)
+    if family not in range(6):
+        raise EngineError(f"family must be one of _lib.OBS_* (0..5), got {family!r}")
+    return mat.d, mat.T, P
+
+
+def _pf_data(be, y, T, family, obs_param):
+    """(N, y [N][T], obs_param [N] or None) of a particle-filter call on the backend; a scalar obs_param is every series'."""
+    N = int(y.shape[0])
+    if tuple(y.shape) not in ((N, T), (N, T, 1)):
+        raise EngineError(f"y must be [N][T] = {(N, T)}, got {tuple(y.shape)}")
+    yb = be.put(y).reshape(N, T)
+    if family == _lib.OBS_STUDENTT and obs_param is None:
+        raise EngineError("OBS_STUDENTT needs obs_param: the degrees of freedom (a scalar or one per series)")
+    ob = None
+    if obs_param is not None:
+        ob = be.put(np.full(N, float(obs_param)) if np.ndim(obs_param) == 0 else obs_param)
+        if tuple(ob.shape) != (N,):
+            raise EngineError(f"obs_param must be a scalar or [N] = {(N,)}, got {tuple(ob.shape)}")
+    return N, yb, ob
+
+
+def _pf_priors(be, prior_w, prior_v, learn_v, N, d):
+    """The priors of a learning filter on the backend with their strides in doubles (0: shared by the series):
+    (prior_v or None, its stride, prior_w, its stride), the order the calls take them in."""
+    pw = np.ascontiguousarray(prior_w, dtype=np.float64)
+    if pw.shape not in ((d, 2), (N, d, 2)):
+        raise EngineError(f"prior_w must be [d][2] = {(d, 2)} or [N][d][2], got {pw.shape}")
+    pv = None
+    if learn_v:
+        pv = np.ascontiguousarray(prior_v, dtype=np.float64)
+        if pv.shape not in ((2,), (N, 2)):
+            raise EngineError(f"prior_v must be [2] or [N][2], got {pv.shape}")
+    return be.put(pv), 2 if learn_v and pv.ndim == 2 else 0, be.put(pw), 2 * d if pw.ndim == 3 else 0
+
+
+def _pf_outputs(be, N, **optional):
+    """The outputs of a particle-filter call in the order the call and the returned dict have them: "ll" [N], every optional
+    name=(wanted, shape) as a fresh buffer or None, "status" [N]."""
+    out = {"ll": be.empty((N,))}
+    out.update((name, be.empty(shape) if wanted else None) for name, (wanted, shape) in optional.items())
+    out["status"] = be.empty((N,), np.int32)
+    return out
+
+
 class _Host:
     mem = _lib.DLM_MEM_HOST
 
@@ -564,36 +612,18 @@ class Engine:
         literal=True: the reference's arithmetic (Q37-Q39).  Returns {"ll" [N], "mean" [N][T][d], "ess" [N][T], "cloud" [N][d][P],
         "weights" [N][P], "status" [N]}; the optional ones are None when not wanted.  A series with a status bit has ll = -inf."""
         be = self._backend(y)
-        d, T = mat.d, mat.T
-        P = int(n_particles)
-        check_pf_shape(d, mat.p, P)
-        if family not in range(6):
-            raise EngineError(f"family must be one of _lib.OBS_* (0..5), got {family!r}")
-        N = int(y.shape[0])
-        if tuple(y.shape) not in ((N, T), (N, T, 1)):
-            raise EngineError(f"y must be [N][T] = {(N, T)}, got {tuple(y.shape)}")
-        yb = be.put(y).reshape(N, T)
-        if family == _lib.OBS_STUDENTT and obs_param is None:
-            raise EngineError("OBS_STUDENTT needs obs_param: the degrees of freedom (a scalar or one per series)")
-        ob = None
-        if obs_param is not None:
-            ob = be.put(np.full(N, float(obs_param)) if np.ndim(obs_param) == 0 else obs_param)
-            if tuple(ob.shape) != (N,):
-                raise EngineError(f"obs_param must be a scalar or [N] = {(N,)}, got {tuple(ob.shape)}")
+        d, T, P = _pf_shape(mat, n_particles, family)
+        N, yb, ob = _pf_data(be, y, T, family, obs_param)
         md, pd, op, keep = self.prepare(mat, params, N, be, flags, seed, series_offset)
         if pd.v_tstride or pd.w_tstride:
             raise EngineError("the particle filter takes time-invariant V and W")
-        ll = be.empty((N,))
-        mean = be.empty((N, T, d)) if want_mean else None
-        ess = be.empty((N, T)) if want_ess else None
-        cloud = be.empty((N, d, P)) if want_cloud else None
-        weights = be.empty((N, P)) if want_weights else None
-        status = be.empty((N,), np.int32)
+        out = _pf_outputs(be, N, mean=(want_mean, (N, T, d)), ess=(want_ess, (N, T)), cloud=(want_cloud, (N, d, P)),
+                          weights=(want_weights, (N, P)))
         desc = _lib.PfDesc(int(family), P, int(n0), 1 if literal else 0)
         self._hold(flags, yb, ob)
-        self._check(self.lib.dlm_pf_batch(self.h, md, pd, ctypes.byref(desc), be.ptr(ob), be.ptr(yb), int(iteration), op, be.ptr(ll),
-                                          be.ptr(mean), be.ptr(ess), be.ptr(cloud), be.ptr(weights), be.ptr(status)))
-        return {"ll": ll, "mean": mean, "ess": ess, "cloud": cloud, "weights": weights, "status": status}
+        self._check(self.lib.dlm_pf_batch(self.h, md, pd, ctypes.byref(desc), be.ptr(ob), be.ptr(yb), int(iteration), op,
+                                          *(be.ptr(v) for v in out.values())))
+        return out
 
     def storvik_filter(self, mat, params, y, prior_w, *, family, n_particles, prior_v=None, learn_v=None, n0=-1, literal=False,
                        obs_param=None, iteration=0, seed=0, series_offset=0, flags=0, want_mean=True, want_ess=True, want_scale_mean=True,
@@ -606,56 +636,24 @@ class Engine:
         "scales" [N][d+1][P], "status" [N]}; the optional ones are None when not wanted, the entries d of scale_mean and scales NaN
         without learn_v."""
         be = self._backend(y)
-        d, T = mat.d, mat.T
-        P = int(n_particles)
-        check_pf_shape(d, mat.p, P)
-        if family not in range(6):
-            raise EngineError(f"family must be one of _lib.OBS_* (0..5), got {family!r}")
+        d, T, P = _pf_shape(mat, n_particles, family)
         learn_v = family == _lib.OBS_GAUSSIAN if learn_v is None else bool(learn_v)
         if learn_v and family != _lib.OBS_GAUSSIAN:
             raise EngineError("learn_v needs OBS_GAUSSIAN: the InverseGamma statistic of V is conjugate for the Gaussian family only")
         if learn_v and prior_v is None:
             raise EngineError("learn_v needs prior_v = (shape, scale)")
-        N = int(y.shape[0])
-        if tuple(y.shape) not in ((N, T), (N, T, 1)):
-            raise EngineError(f"y must be [N][T] = {(N, T)}, got {tuple(y.shape)}")
-        yb = be.put(y).reshape(N, T)
-        if family == _lib.OBS_STUDENTT and obs_param is None:
-            raise EngineError("OBS_STUDENTT needs obs_param: the degrees of freedom (a scalar or one per series)")
-        ob = None
-        if obs_param is not None:
-            ob = be.put(np.full(N, float(obs_param)) if np.ndim(obs_param) == 0 else obs_param)
-            if tuple(ob.shape) != (N,):
-                raise EngineError(f"obs_param must be a scalar or [N] = {(N,)}, got {tuple(ob.shape)}")
-        pw = np.ascontiguousarray(prior_w, dtype=np.float64)
-        if pw.shape not in ((d, 2), (N, d, 2)):
-            raise EngineError(f"prior_w must be [d][2] = {(d, 2)} or [N][d][2], got {pw.shape}")
-        pw_stride = 2 * d if pw.ndim == 3 else 0
-        pv, pv_stride = None, 0
-        if learn_v:
-            pv = np.ascontiguousarray(prior_v, dtype=np.float64)
-            if pv.shape not in ((2,), (N, 2)):
-                raise EngineError(f"prior_v must be [2] or [N][2], got {pv.shape}")
-            pv_stride = 2 if pv.ndim == 2 else 0
-        pwb, pvb = be.put(pw), be.put(pv)
+        N, yb, ob = _pf_data(be, y, T, family, obs_param)
+        pvb, pv_stride, pwb, pw_stride = _pf_priors(be, prior_w, prior_v, learn_v, N, d)
         md, pd, op, keep = self.prepare(mat, params, N, be, flags, seed, series_offset)
         if pd.v_tstride and not learn_v:
             raise EngineError("the Storvik filter takes a time-invariant V")
-        ll = be.empty((N,))
-        mean = be.empty((N, T, d)) if want_mean else None
-        ess = be.empty((N, T)) if want_ess else None
-        scale_mean = be.empty((N, T, d + 1)) if want_scale_mean else None
-        cloud = be.empty((N, d, P)) if want_cloud else None
-        weights = be.empty((N, P)) if want_weights else None
-        scales = be.empty((N, d + 1, P)) if want_scales else None
-        status = be.empty((N,), np.int32)
+        out = _pf_outputs(be, N, mean=(want_mean, (N, T, d)), ess=(want_ess, (N, T)), scale_mean=(want_scale_mean, (N, T, d + 1)),
+                          cloud=(want_cloud, (N, d, P)), weights=(want_weights, (N, P)), scales=(want_scales, (N, d + 1, P)))
         desc = _lib.StorvikDesc(int(family), P, int(n0), 1 if literal else 0, 1 if learn_v else 0)
         self._hold(flags, yb, ob, pwb, pvb)
         self._check(self.lib.dlm_storvik_batch(self.h, md, pd, ctypes.byref(desc), be.ptr(pvb), pv_stride, be.ptr(pwb), pw_stride, be.ptr(ob),
-                                               be.ptr(yb), int(iteration), op, be.ptr(ll), be.ptr(mean), be.ptr(ess), be.ptr(scale_mean),
-                                               be.ptr(cloud), be.ptr(weights), be.ptr(scales), be.ptr(status)))
-        return {"ll": ll, "mean": mean, "ess": ess, "scale_mean": scale_mean, "cloud": cloud, "weights": weights, "scales": scales,
-                "status": status}
+                                               be.ptr(yb), int(iteration), op, *(be.ptr(v) for v in out.values())))
+        return out
 
     def lw_filter(self, mat, params, y, prior_w, *, family, n_particles, a, prior_v=None, learn_v=None, n0=-1, literal=False,
                   obs_param=None, iteration=0, seed=0, series_offset=0, flags=0, want_mean=True, want_ess=True, want_psi_mean=True,
@@ -669,11 +667,7 @@ class Engine:
         "weights" [N][P], "psi" [N][d+1][P], "status" [N]}; the optional ones are None when not wanted, the entries d of psi_mean, psi_var
         and psi NaN without learn_v."""
         be = self._backend(y)
-        d, T = mat.d, mat.T
-        P = int(n_particles)
-        check_pf_shape(d, mat.p, P)
-        if family not in range(6):
-            raise EngineError(f"family must be one of _lib.OBS_* (0..5), got {family!r}")
+        d, T, P = _pf_shape(mat, n_particles, family)
         scale_family = family in (_lib.OBS_GAUSSIAN, _lib.OBS_STUDENTT, _lib.OBS_BETA)
         learn_v = scale_family if learn_v is None else bool(learn_v)
         if learn_v and not scale_family:
@@ -682,47 +676,19 @@ class Engine:
             raise EngineError("learn_v needs prior_v = (mean, sd) of log V")
         if not 0.0 < float(a) <= 1.0:
             raise EngineError(f"the shrinkage a must satisfy 0 < a <= 1, got {a!r}")
-        N = int(y.shape[0])
-        if tuple(y.shape) not in ((N, T), (N, T, 1)):
-            raise EngineError(f"y must be [N][T] = {(N, T)}, got {tuple(y.shape)}")
-        yb = be.put(y).reshape(N, T)
-        if family == _lib.OBS_STUDENTT and obs_param is None:
-            raise EngineError("OBS_STUDENTT needs obs_param: the degrees of freedom (a scalar or one per series)")
-        ob = None
-        if obs_param is not None:
-            ob = be.put(np.full(N, float(obs_param)) if np.ndim(obs_param) == 0 else obs_param)
-            if tuple(ob.shape) != (N,):
-                raise EngineError(f"obs_param must be a scalar or [N] = {(N,)}, got {tuple(ob.shape)}")
-        pw = np.ascontiguousarray(prior_w, dtype=np.float64)
-        if pw.shape not in ((d, 2), (N, d, 2)):
-            raise EngineError(f"prior_w must be [d][2] = {(d, 2)} or [N][d][2], got {pw.shape}")
-        pw_stride = 2 * d if pw.ndim == 3 else 0
-        pv, pv_stride = None, 0
-        if learn_v:
-            pv = np.ascontiguousarray(prior_v, dtype=np.float64)
-            if pv.shape not in ((2,), (N, 2)):
-                raise EngineError(f"prior_v must be [2] or [N][2], got {pv.shape}")
-            pv_stride = 2 if pv.ndim == 2 else 0
-        pwb, pvb = be.put(pw), be.put(pv)
+        N, yb, ob = _pf_data(be, y, T, family, obs_param)
+        pvb, pv_stride, pwb, pw_stride = _pf_priors(be, prior_w, prior_v, learn_v, N, d)
         md, pd, op, keep = self.prepare(mat, params, N, be, flags, seed, series_offset)
         if pd.v_tstride and not learn_v:
             raise EngineError("the Liu-West filter takes a time-invariant V")
-        ll = be.empty((N,))
-        mean = be.empty((N, T, d)) if want_mean else None
-        ess = be.empty((N, T)) if want_ess else None
-        psi_mean = be.empty((N, T, d + 1)) if want_psi_mean else None
-        psi_var = be.empty((N, T, d + 1)) if want_psi_var else None
-        cloud = be.empty((N, d, P)) if want_cloud else None
-        weights = be.empty((N, P)) if want_weights else None
-        psi = be.empty((N, d + 1, P)) if want_psi else None
-        status = be.empty((N,), np.int32)
+        out = _pf_outputs(be, N, mean=(want_mean, (N, T, d)), ess=(want_ess, (N, T)), psi_mean=(want_psi_mean, (N, T, d + 1)),
+                          psi_var=(want_psi_var, (N, T, d + 1)), cloud=(want_cloud, (N, d, P)), weights=(want_weights, (N, P)),
+                          psi=(want_psi, (N, d + 1, P)))
         desc = _lib.LwDesc(int(family), P, int(n0), 1 if literal else 0, 1 if learn_v else 0, float(a))
         self._hold(flags, yb, ob, pwb, pvb)
         self._check(self.lib.dlm_lw_batch(self.h, md, pd, ctypes.byref(desc), be.ptr(pvb), pv_stride, be.ptr(pwb), pw_stride, be.ptr(ob),
-                                          be.ptr(yb), int(iteration), op, be.ptr(ll), be.ptr(mean), be.ptr(ess), be.ptr(psi_mean),
-                                          be.ptr(psi_var), be.ptr(cloud), be.ptr(weights), be.ptr(psi), be.ptr(status)))
-        return {"ll": ll, "mean": mean, "ess": ess, "psi_mean": psi_mean, "psi_var": psi_var, "cloud": cloud, "weights": weights,
-                "psi": psi, "status": status}
+                                          be.ptr(yb), int(iteration), op, *(be.ptr(v) for v in out.values())))
+        return out
 
     def simulate(self, mat, params, N, *, seed=0, series_offset=0, device=False, want_x=True):
         """Dlm.simulateRegular over the model's time grid for N series (dlm_simulate_batch): (x [N][T+1][d], y [N][T][p])."""

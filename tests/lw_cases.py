@@ -91,13 +91,7 @@ def reference(name):
 
 def engine_run(eng, kw, device=False):
     """Engine.lw_filter on the arguments `lr.run` takes -> NumPy arrays."""
-    import torch
-    N = kw["y"].shape[0]
-    y = torch.as_tensor(kw["y"], device="cuda") if device else kw["y"]
-    out = eng.lw_filter(pc.materialised(kw), pc.packed_params(kw, N), y, kw["prior_w"], family=kw["family"], n_particles=kw["P"], a=kw["a"],
-                        prior_v=kw["prior_v"], learn_v=kw["learn_v"], n0=kw["n0"], literal=kw["literal"], obs_param=kw.get("nu"),
-                        iteration=kw["iteration"], seed=kw["seed"], series_offset=kw["series_offset"])
-    return {k: (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)) for k, v in out.items()}
+    return pc.engine_run(eng, kw, "lw_filter", device)
 
 
 # ---- check 1, known parameters: a = 1, every prior sd 0, Gaussian family -- the auxiliary particle filter, whose exp(ll) is unbiased for the

@@ -178,14 +178,16 @@ def packed_params(a, N):
             cm(C0), d * d if C0.ndim == 3 else 0, 0, 0)
 
 
-def engine_run(eng, kw, device=False):
-    """Engine.particle_filter on the arguments `pr.run` takes -> NumPy arrays."""
+def engine_run(eng, kw, method="particle_filter", device=False):
+    """The Engine's `method` (particle_filter, storvik_filter or lw_filter) on the arguments its restatement's `run` takes -> NumPy arrays:
+    the learning filters also get prior_w, prior_v and learn_v, lw_filter its shrinkage a."""
     import torch
     N = kw["y"].shape[0]
     y = torch.as_tensor(kw["y"], device="cuda") if device else kw["y"]
-    out = eng.particle_filter(materialised(kw), packed_params(kw, N), y, family=kw["family"], n_particles=kw["P"], n0=kw["n0"],
-                              literal=kw["literal"], obs_param=kw.get("nu"), iteration=kw["iteration"], seed=kw["seed"],
-                              series_offset=kw["series_offset"])
+    own = {"particle_filter": (), "storvik_filter": ("prior_v", "learn_v"), "lw_filter": ("prior_v", "learn_v", "a")}[method]
+    out = getattr(eng, method)(materialised(kw), packed_params(kw, N), y, *((kw["prior_w"],) if own else ()), family=kw["family"],
+                               n_particles=kw["P"], n0=kw["n0"], literal=kw["literal"], obs_param=kw.get("nu"), iteration=kw["iteration"],
+                               seed=kw["seed"], series_offset=kw["series_offset"], **{k: kw[k] for k in own})
     return {k: (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)) for k, v in out.items()}
 
 

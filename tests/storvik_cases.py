@@ -80,13 +80,7 @@ def reference(name):
 
 def engine_run(eng, kw, device=False):
     """Engine.storvik_filter on the arguments `sr.run` takes -> NumPy arrays."""
-    import torch
-    N = kw["y"].shape[0]
-    y = torch.as_tensor(kw["y"], device="cuda") if device else kw["y"]
-    out = eng.storvik_filter(pc.materialised(kw), pc.packed_params(kw, N), y, kw["prior_w"], family=kw["family"], n_particles=kw["P"],
-                             prior_v=kw["prior_v"], learn_v=kw["learn_v"], n0=kw["n0"], literal=kw["literal"], obs_param=kw.get("nu"),
-                             iteration=kw["iteration"], seed=kw["seed"], series_offset=kw["series_offset"])
-    return {k: (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)) for k, v in out.items()}
+    return pc.engine_run(eng, kw, "storvik_filter", device)
 
 
 # ---- the models of the evidence checks: Gaussian, T = 24, dt_0 = 0, y_7 missing, P = 128, n0 = -1, 4096 replicates that differ in the series

@@ -164,7 +164,8 @@ def test_learning_the_posterior_means_of_the_log_variances(runs, which):
 # VGPRs of k_pf and k_storvik at d = 1 .. 16 before dlm_lw.hip existed (profiles/r20_notes.md): the new kernel and its key change neither
 PF_VGPRS = [156, 157, 153, 159, 171, 176, 190, 193, 204, 212, 222, 230, 240, 247, 259, 270]
 STORVIK_VGPRS = [200, 209, 207, 211, 213, 217, 222, 227, 232, 237, 242, 247, 255, 262, 264, 266]
-# and of k_lw as it was written: whoever moves its parts into dlm_pf_common.h keeps these too (profiles/r22_notes.md)
+# and of k_lw as it was written.  Its normals, searches, gathers, normalisation and resampling are dlm_pf_common.h's now and keep
+# these; its initial cloud, its results tail and the order of LwArgs' fields stay its own because each moves a count (profiles/r23_notes.md)
 LW_VGPRS = [200, 205, 208, 205, 209, 212, 217, 220, 224, 229, 233, 237, 241, 245, 249, 253]
 
 
