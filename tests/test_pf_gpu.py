@@ -6,6 +6,7 @@ summation (the build contracts no a * b + c), so what remains is the last bits o
 and so must, in effect, the ancestors: a resampling that picked another particle anywhere leaves a final cloud that differs in the first
 digit.  tests/test_pf_host.py shows that no comparison of the kernel's is within 1e-11 of flipping on these inputs.  Then: the batch does not
 depend on how it is split, the estimate is unbiased and the means are the Kalman filter's on the device too, the bad series, and the driver.
+What kernel and restatement could share -- every family, an irregular grid, g_index, F_t, per-series parameters: tests/test_pf_exact_gpu.py.
 
 The largest relative difference seen on an MI355X is in profiles/r19_notes.md."""
 import os
