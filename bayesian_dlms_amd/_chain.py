@@ -1,5 +1,6 @@
-"""What the Gibbs drivers (studentt.py, stochvol.py) share about where a chain lives: its arrays stay on a torch device when an
-engine or a device tensor is given, and are host arrays otherwise (injected callables, for tests)."""
+"""What the Gibbs drivers (studentt.py, stochvol.py, factorsv.py and, through _dlmfsv.py, dlmfsv.py and dlmfsvsys.py) share about
+where a chain lives: its arrays stay on a torch device when an engine or a device tensor is given, and are host arrays otherwise
+(injected callables and stub engines, for tests)."""
 import numpy as np
 
 

@@ -25,21 +25,22 @@ and the next steps 1 and 2 are one joint draw of (theta, f).  literal_order=True
 Q36: initialise (:306-320) draws the first theta under W_t = 0.1 I whatever the initial parameters say; that is reproduced (it only
 moves the starting point).  ffbsSvd / sampleStateAr are not reproduced, for Q33's reason; theta is drawn with the reference-form
 dlm_ffbs_batch.  literal=True is the reference's arithmetic in the five factor calls (Q16-Q19, Q27-Q30).
+
+The checks, the initialisation and the sweep are _dlmfsv.py's, shared with dlmfsv.py (steps 2-4 are factorsv.factor_half); what is this
+sampler's own -- step 1, which variance is the stream, the first draw's W_t -- is KIND at the end of this file.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Iterator, Optional
+from typing import Iterator
 
 import numpy as np
 
-from . import _lib
-from ._chain import host, is_torch, or_status, place
-from .dlm import Dlm, DlmParameters, materialise
-from .dlmfsv import DlmFsv
+from . import _dlmfsv
+from .dlm import Dlm, DlmParameters
 from .factorsv import FactorSv, FsvParameters
 from .gibbs import InverseGamma
-from .stochvol import Gaussian, StochasticVolatility
+from .stochvol import Gaussian
 
 INIT_W = 0.1          # initialise (:311-312): the first state draw runs under W_t = 0.1 I
 
@@ -63,33 +64,18 @@ class DlmFsvSystemParameters:
 
 
 class DlmFsvSystem:
-    @dataclass
-    class State:
-        """DlmFsvSystem.State (:24-29), batched.  params: {"beta" [N][d][k], "v" [N][d], "sv" [N][k][3], "V" [N][p]} on the host; theta
-        [N][T+1][d], factors [N][k][T] and volatility [N][k][T+1] host copies when asked for (keep_states) else None; status [N]: the
-        flags of the iteration's calls or'ed (the factor chains' folded onto their panel)."""
-        params: dict
-        theta: Optional[np.ndarray]
-        factors: Optional[np.ndarray]
-        volatility: Optional[np.ndarray]
-        status: np.ndarray
+    State = _dlmfsv.State
 
     @staticmethod
     def _model(mod, T, times=None):
-        grid = np.arange(1, T + 1, dtype=np.float64) if times is None else np.asarray(host(times), dtype=np.float64).reshape(-1)
-        if grid.shape != (T,) or not np.array_equal(np.diff(grid), np.ones(T - 1)):
-            raise ValueError("DlmFsvSystem runs on a regular unit time grid (times[t+1] - times[t] = 1 for all t): the AR(1) log-volatility "
-                             "of the factors has no dt")
-        mat = materialise(mod, grid)
+        mat = _dlmfsv.unit_grid_model("DlmFsvSystem", mod, T, times)
         if mat.n_g != 1 or mat.g_index is not None or mat.dt is not None:
             raise ValueError("DlmFsvSystem takes a model with one G on the regular unit time grid")
         return mat
 
     @staticmethod
-    def _shape(ys, mat, init_p):
-        if len(ys.shape) != 3:
-            raise ValueError(f"ys must be [N][T][p], got the shape {tuple(ys.shape)}")
-        N, T, p = (int(x) for x in ys.shape)
+    def _shape(dims, mat, init_p):
+        N, T, p = dims
         d, k = mat.d, init_p.fsv.k
         if p != mat.p or init_p.dlm.v.shape != (p, p):
             raise ValueError(f"ys has p = {p} series, the model's F {mat.p} columns and V is {init_p.dlm.v.shape[0]} x {init_p.dlm.v.shape[1]}")
@@ -99,9 +85,7 @@ class DlmFsvSystem:
             raise ValueError(f"d = {d}: the innovations kernel takes d <= 64")
         if k > d:
             raise ValueError(f"k = {k} factors for d = {d} states: the factor model needs k <= d")
-        if T < 2:
-            raise ValueError("the factor stochastic-volatility sampler needs T >= 2 (the reference's sums throw on a single observation)")
-        return N, T, p, k, d
+        return k, d
 
     @staticmethod
     def simulate(mod: Dlm, params: DlmFsvSystemParameters, T: int, N: int, seed: int = 0):
@@ -131,37 +115,20 @@ class DlmFsvSystem:
         return (V.reshape(-1), p * p, W.reshape(-1), T * d * d, m0, 0, C0, 0, 0, d * d if T else 0)
 
     @staticmethod
+    def _data(engine, c, it, seed, series_offset):
+        """Step 1: the innovations of theta into c["y"] (it = None: initialise's)."""
+        inn = engine.dlmfsvsys_innovations(c["mat"], c["theta"], out={"w": c["y"]} if "y" in c else None)
+        c["y"] = inn["w"]
+        return {"innovations": inn["status"]}
+
+    @staticmethod
     def initialise_state(ys, mod, init_p: DlmFsvSystemParameters, engine, *, seed: int = 0, series_offset: int = 0, literal: bool = False,
                          times=None):
         """initialise (:306-320): one FFBS under W_t = 0.1 I (Q36), the innovations of that theta, then FactorSv.initialise_state_ar on
         them.  Returns the device-resident chain state: FactorSv's dict (its "y" is w, the innovations [N][T][d]) plus {"ys", "theta"
         [N][T+1][d], "V" [N][p*p], "m0", "C0", "W" [N][T][d*d] (not yet written), "mat"}.  Refuses a W_t stream that does not fit the
         device."""
-        if len(ys.shape) != 3:
-            raise ValueError(f"ys must be [N][T][p], got the shape {tuple(ys.shape)}")
-        mat = DlmFsvSystem._model(mod, int(ys.shape[1]), times)
-        N, T, p, k, d = DlmFsvSystem._shape(ys, mat, init_p)
-        nbytes = 8 * N * T * d * d
-        if engine is not None:
-            free, _ = engine.mem_info()
-            if nbytes > free:
-                raise MemoryError(f"the W_t stream of {N} panels x {T} times x {d} x {d} doubles takes {nbytes / 1e9:.2f} GB, the device has "
-                                  f"{free / 1e9:.2f} GB free: run fewer panels per call (series_offset keeps the draws)")
-        put, y = place(ys, engine, N, T * p)
-        y = y.reshape(N, T, p)
-        V = put(np.broadcast_to(np.ascontiguousarray(init_p.dlm.v.T).reshape(-1), (N, p * p)))
-        m0 = put(init_p.dlm.m0.reshape(-1))
-        C0 = put(np.ascontiguousarray(init_p.dlm.c0.T).reshape(-1))
-        w0 = put((INIT_W * np.eye(d)).reshape(-1))
-        out = engine.ffbs(mat, DlmFsvSystem._packed(V, p, w0, 0, d, m0, C0), y, seed=DlmFsv._seed_theta(seed, 0), series_offset=series_offset,
-                          want_theta=True, want_stats=False, want_filt=False)
-        theta = out["theta"]
-        inn = engine.dlmfsvsys_innovations(mat, theta)
-        c = FactorSv.initialise_state_ar(inn["w"], init_p.fsv, engine, seed=seed, series_offset=series_offset, literal=literal)
-        c["status"] = or_status(or_status(out["status"], inn["status"]), c["status"])
-        W = theta.new_empty((N, T, d * d)) if is_torch(theta) else np.empty((N, T, d * d))
-        c.update(ys=y, theta=theta, V=V, m0=m0, C0=C0, W=W, mat=mat)
-        return c
+        return _dlmfsv.initialise(KIND, ys, mod, init_p, engine, seed=seed, series_offset=series_offset, literal=literal, times=times)
 
     @staticmethod
     def sample(prior_beta: Gaussian, prior_sigma_eta: InverseGamma, prior_phi: Gaussian, prior_mu: Gaussian, prior_sigma: InverseGamma,
@@ -172,55 +139,12 @@ class DlmFsvSystem:
         panel started at init_p.  The priors are FactorSv.sample_ar's (in the reference's order here: sigma_eta, phi, mu) and prior_v, the
         InverseGamma of every V_ii.  literal: the reference's arithmetic in the five factor calls; literal_order: the reference's order
         of the steps (Q35).  times: None (1 .. T) or a regular unit grid.  Yields one State per iteration."""
-        if not (isinstance(prior_beta, Gaussian) and isinstance(prior_mu, Gaussian) and isinstance(prior_phi, Gaussian)
-                and isinstance(prior_sigma_eta, InverseGamma) and isinstance(prior_sigma, InverseGamma) and isinstance(prior_v, InverseGamma)):
-            raise TypeError("the device evaluates Gaussian priors of beta, phi and mu and InverseGamma priors of sigma_eta^2, sigma^2 and V_ii only")
-        if not isinstance(init_p, DlmFsvSystemParameters):
-            raise TypeError("init_p must be a DlmFsvSystemParameters")
-        if len(ys.shape) != 3:
-            raise ValueError(f"ys must be [N][T][p], got the shape {tuple(ys.shape)}")
-        mat = DlmFsvSystem._model(mod, int(ys.shape[1]), times)
-        DlmFsvSystem._shape(ys, mat, init_p)
-        lit = 1 if literal else 0
-        sv_prior = _lib.SvPrior(0, lit, prior_phi.mean, prior_phi.sd, prior_mu.mean, prior_mu.sd, prior_sigma_eta.shape,
-                                prior_sigma_eta.scale, 100.0, 0.05)
-        fsv_prior = _lib.FsvPrior(lit, prior_beta.mean, prior_beta.sd, prior_sigma.shape, prior_sigma.scale)
-        return DlmFsvSystem._run(ys, mod, init_p, engine, sv_prior, fsv_prior, prior_v, n_iter, seed, series_offset, literal, literal_order,
-                                 keep_states, times)
+        return _dlmfsv.sample(KIND, DlmFsvSystemParameters, (prior_beta, prior_sigma_eta, prior_mu, prior_phi, prior_sigma), prior_v, ys, mod,
+                              init_p, engine, n_iter=n_iter, seed=seed, series_offset=series_offset, literal=literal,
+                              literal_order=literal_order, keep_states=keep_states, times=times)
 
-    @staticmethod
-    def _run(ys, mod, init_p, engine, sv_prior, fsv_prior, prior_v, n_iter, seed, series_offset, literal, literal_order, keep_states, times):
-        c = DlmFsvSystem.initialise_state(ys, mod, init_p, engine, seed=seed, series_offset=series_offset, literal=literal, times=times)
-        mat, y, theta, V, m0, C0, W = c["mat"], c["ys"], c["theta"], c["V"], c["m0"], c["C0"], c["W"]
-        w, f, alpha, sv, beta, v = c["y"], c["f"], c["alpha"], c["sv"], c["beta"], c["v"]
-        bufs, status0 = {"ystar": c["ystar"], "v": c["v_mix"]}, c["status"]
-        N, T, p = (int(x) for x in y.shape)
-        k, d = int(beta.shape[2]), mat.d
-        so = series_offset
-        for it in range(n_iter):
-            inn = engine.dlmfsvsys_innovations(mat, theta, out={"w": w})
-            fac = None
-            if not literal_order:
-                fac = engine.fsv_factors(w, beta, v, alpha, iteration=it, seed=seed, series_offset=so, literal=literal, out={"f": f})
-            sv2 = sv.reshape(N * k, 3)
-            st = StochasticVolatility.sample_state_ar(f.reshape(N * k, T), alpha.reshape(N * k, T + 1), sv2, engine, iteration=it,
-                                                      seed=seed, series_offset=so * k, out=bufs)
-            alpha, bufs = st["alpha"].reshape(N, k, T + 1), {"ystar": st["ystar"], "v": st["v"]}
-            res = engine.sv_params(alpha.reshape(N * k, T + 1), sv2, sv_prior, iteration=it, seed=seed, series_offset=so * k, out={"sv": sv2})
-            if literal_order:
-                fac = engine.fsv_factors(w, beta, v, alpha, iteration=it, seed=seed, series_offset=so, literal=literal, out={"f": f})
-            load = engine.fsv_loadings(w, f, beta, fsv_prior, iteration=it, seed=seed, series_offset=so, v=v, out={"beta": beta, "v": v})
-            var = engine.dlmfsv_variance(beta, v, alpha, out={"V": W})
-            out = engine.ffbs(mat, DlmFsvSystem._packed(V, p, W, T, d, m0, C0), y, seed=DlmFsv._seed_theta(seed, it + 1), series_offset=so,
-                              want_theta=True, want_stats=True, want_filt=False)
-            theta = out["theta"]
-            V, _ = engine.dinvgamma_step(d, p, out["stats"], prior_v, prior_v, iteration=it, seed=seed, series_offset=so)
-            status = or_status(FactorSv._fold(or_status(st["status"], res.get("status")), N, k), or_status(fac["status"], load["status"]))
-            status = or_status(status, or_status(or_status(inn["status"], var["status"]), out["status"]))
-            if it == 0:
-                status = or_status(status, status0)
-            params = {"beta": host(beta).copy(), "v": host(v).copy(), "sv": host(sv).copy(),
-                      "V": np.diagonal(host(V).reshape(N, p, p), axis1=1, axis2=2).copy()}
-            keep = keep_states
-            yield DlmFsvSystem.State(params, host(theta).copy() if keep else None, host(f).copy() if keep else None,
-                                     host(alpha).copy() if keep else None, status)
+
+# the factor part is the system noise: W_t is the stream, V static; the first state draw runs under W_t = INIT_W I
+KIND = _dlmfsv.Kind(stream="W", param="V", first=INIT_W, model=DlmFsvSystem._model, shape=DlmFsvSystem._shape,
+                    data=DlmFsvSystem._data,
+                    packed=lambda c, T: DlmFsvSystem._packed(c["V"], c["mat"].p, c["W"], T, c["mat"].d, c["m0"], c["C0"]))

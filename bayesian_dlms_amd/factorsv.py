@@ -77,6 +77,16 @@ class FsvParameters:
         return np.asarray([(q.phi, q.mu, q.sigma_eta) for q in self.factor_params], dtype=np.float64)
 
 
+def panel_dims(ys):
+    """(N, T, p) of a batch of panels ys [N][T][p], as every sampler with a factor stochastic-volatility part takes it."""
+    if len(ys.shape) != 3:
+        raise ValueError(f"ys must be [N][T][p], got the shape {tuple(ys.shape)}")
+    N, T, p = (int(x) for x in ys.shape)
+    if T < 2:
+        raise ValueError("the factor stochastic-volatility sampler needs T >= 2 (the reference's sums throw on a single observation)")
+    return N, T, p
+
+
 class FactorSv:
     @dataclass
     class State:
@@ -124,13 +134,9 @@ class FactorSv:
 
     @staticmethod
     def _shape(ys, init_p):
-        if len(ys.shape) != 3:
-            raise ValueError(f"ys must be [N][T][p], got the shape {tuple(ys.shape)}")
-        N, T, p = (int(x) for x in ys.shape)
+        N, T, p = panel_dims(ys)
         if p != init_p.p:
             raise ValueError(f"ys has p = {p} series, the initial beta {init_p.p} rows")
-        if T < 2:
-            raise ValueError("the factor stochastic-volatility sampler needs T >= 2 (the reference's sums throw on a single observation)")
         return N, T, p, init_p.k
 
     @staticmethod
@@ -165,36 +171,75 @@ class FactorSv:
         panel started at init_p.  prior_beta: the Gaussian(mean, sd) of the free loadings; prior_sigma_eta, prior_mu, prior_phi: the
         priors of sample_uni for every factor's (sigma_eta^2, mu, phi); prior_sigma: the InverseGamma of sigma^2.  Yields one State per
         iteration."""
-        if not (isinstance(prior_beta, Gaussian) and isinstance(prior_mu, Gaussian) and isinstance(prior_phi, Gaussian)
-                and isinstance(prior_sigma_eta, InverseGamma) and isinstance(prior_sigma, InverseGamma)):
-            raise TypeError("the device evaluates Gaussian priors of beta, mu and phi and InverseGamma priors of sigma_eta^2 and sigma^2 only")
+        priors = pack_priors(prior_beta, prior_sigma_eta, prior_mu, prior_phi, prior_sigma, literal)
         if not isinstance(init_p, FsvParameters):
             raise TypeError("init_p must be an FsvParameters")
-        N, T, p, k = FactorSv._shape(ys, init_p)
-        lit = 1 if literal else 0
-        sv_prior = _lib.SvPrior(0, lit, prior_phi.mean, prior_phi.sd, prior_mu.mean, prior_mu.sd, prior_sigma_eta.shape,
-                                prior_sigma_eta.scale, 100.0, 0.05)
-        fsv_prior = _lib.FsvPrior(lit, prior_beta.mean, prior_beta.sd, prior_sigma.shape, prior_sigma.scale)
-        return FactorSv._run(ys, init_p, engine, sv_prior, fsv_prior, n_iter, seed, series_offset, literal, keep_factors, N, T, p, k)
+        FactorSv._shape(ys, init_p)
+        return FactorSv._run(ys, init_p, engine, priors, n_iter, seed, series_offset, literal, keep_factors)
 
     @staticmethod
-    def _run(ys, init_p, engine, sv_prior, fsv_prior, n_iter, seed, series_offset, literal, keep_factors, N, T, p, k):
+    def _run(ys, init_p, engine, priors, n_iter, seed, series_offset, literal, keep_factors):
         c = FactorSv.initialise_state_ar(ys, init_p, engine, seed=seed, series_offset=series_offset, literal=literal)
-        y, f, alpha, sv, beta, v = c["y"], c["f"], c["alpha"], c["sv"], c["beta"], c["v"]
-        bufs, status0 = {"ystar": c["ystar"], "v": c["v_mix"]}, c["status"]
+        N, k = int(c["f"].shape[0]), int(c["f"].shape[1])
         for it in range(n_iter):
-            sv2 = sv.reshape(N * k, 3)
-            st = StochasticVolatility.sample_state_ar(f.reshape(N * k, T), alpha.reshape(N * k, T + 1), sv2, engine, iteration=it,
-                                                      seed=seed, series_offset=series_offset * k, out=bufs)
-            alpha, bufs = st["alpha"].reshape(N, k, T + 1), {"ystar": st["ystar"], "v": st["v"]}
-            res = engine.sv_params(alpha.reshape(N * k, T + 1), sv2, sv_prior, iteration=it, seed=seed, series_offset=series_offset * k,
-                                   out={"sv": sv2})
-            fac = engine.fsv_factors(y, beta, v, alpha, iteration=it, seed=seed, series_offset=series_offset, literal=literal,
-                                     out={"f": f})
-            load = engine.fsv_loadings(y, f, beta, fsv_prior, iteration=it, seed=seed, series_offset=series_offset, v=v,
-                                       out={"beta": beta, "v": v})
-            status = or_status(FactorSv._fold(or_status(st["status"], res.get("status")), N, k), or_status(fac["status"], load["status"]))
-            if it == 0:
-                status = or_status(status, status0)
-            params = {"beta": host(beta).copy(), "v": host(v).copy(), "sv": host(sv).copy()}
-            yield FactorSv.State(params, host(f).copy() if keep_factors else None, host(alpha).copy() if keep_factors else None, status)
+            st = factor_half(engine, c, c["y"], priors, iteration=it, seed=seed, series_offset=series_offset, literal=literal,
+                             factors_last=True)
+            status = fold_status(st, N, k, c["status"] if it == 0 else None)
+            params = {"beta": host(c["beta"]).copy(), "v": host(c["v"]).copy(), "sv": host(c["sv"]).copy()}
+            yield FactorSv.State(params, *(host(c[key]).copy() if keep_factors else None for key in ("f", "alpha")), status)
+
+
+def pack_priors(prior_beta, prior_sigma_eta, prior_mu, prior_phi, prior_sigma, literal, also=None):
+    """The priors of the factor part, checked and packed for the device: (_lib.SvPrior of every factor's (phi, mu, sigma_eta^2) with the
+    conjugate phi update, _lib.FsvPrior of the loadings and sigma^2).  also: (name, prior) of one more InverseGamma the caller's sampler
+    takes, checked with them."""
+    inverse_gammas = (prior_sigma_eta, prior_sigma) + (() if also is None else (also[1],))
+    if not (all(isinstance(q, Gaussian) for q in (prior_beta, prior_mu, prior_phi)) and all(isinstance(q, InverseGamma) for q in inverse_gammas)):
+        raise TypeError("the device evaluates Gaussian priors of beta, mu and phi and InverseGamma priors of sigma_eta^2"
+                        + (" and sigma^2" if also is None else f", sigma^2 and {also[0]}") + " only")
+    lit = 1 if literal else 0
+    sv_prior = _lib.SvPrior(0, lit, prior_phi.mean, prior_phi.sd, prior_mu.mean, prior_mu.sd, prior_sigma_eta.shape, prior_sigma_eta.scale,
+                            100.0, 0.05)
+    return sv_prior, _lib.FsvPrior(lit, prior_beta.mean, prior_beta.sd, prior_sigma.shape, prior_sigma.scale)
+
+
+def factor_half(engine, c, x, priors, *, iteration, seed, series_offset, literal, factors_last):
+    """The factor model's part of one iteration on the chain state c (initialise_state_ar's dict) and the factor model's data x
+    [N][T][p], c updated in place with the buffers c holds reused:
+
+      f | x, alpha, beta, v                     before the volatility draw, or after the parameters of the volatility (factors_last:
+                                                sampleStep's order, where the next volatility draw conditions on this f)
+      alpha | f, then (phi, mu, sigma_eta) | alpha      on the N k factor series
+      sigma^2, beta | x, f
+
+    priors: pack_priors' pair.  Returns the calls' status flags by name, not yet or'ed: "factors" and "loadings" [N]; "volatility" (the
+    mixture and the FFBS call of sample_state_ar, or'ed there) and "sv_params" [N k], which fold_status folds onto their panels."""
+    sv_prior, fsv_prior = priors
+    N, k, T = (int(n) for n in c["f"].shape)
+    it, so = iteration, series_offset
+
+    def draw_factors():
+        return engine.fsv_factors(x, c["beta"], c["v"], c["alpha"], iteration=it, seed=seed, series_offset=so, literal=literal,
+                                  out={"f": c["f"]})
+
+    fac = None if factors_last else draw_factors()
+    sv2 = c["sv"].reshape(N * k, 3)
+    vol = StochasticVolatility.sample_state_ar(c["f"].reshape(N * k, T), c["alpha"].reshape(N * k, T + 1), sv2, engine, iteration=it,
+                                               seed=seed, series_offset=so * k, out={"ystar": c["ystar"], "v": c["v_mix"]})
+    c.update(alpha=vol["alpha"].reshape(N, k, T + 1), ystar=vol["ystar"], v_mix=vol["v"])
+    res = engine.sv_params(vol["alpha"], sv2, sv_prior, iteration=it, seed=seed, series_offset=so * k, out={"sv": sv2})
+    if factors_last:
+        fac = draw_factors()
+    load = engine.fsv_loadings(x, c["f"], c["beta"], fsv_prior, iteration=it, seed=seed, series_offset=so, v=c["v"],
+                               out={"beta": c["beta"], "v": c["v"]})
+    return {"factors": fac["status"], "volatility": vol["status"], "sv_params": res.get("status"), "loadings": load["status"]}
+
+
+def fold_status(st, N, k, status0=None):
+    """One iteration's status [N] from its calls' flags by name (factor_half's and whatever a driver adds): the factor chains' flags
+    folded onto their panel, the panels' or'ed, and status0, the initialisation's, on top."""
+    chains, status = or_status(st["volatility"], st["sv_params"]), status0
+    for name, flags in st.items():
+        if name not in ("volatility", "sv_params"):
+            status = or_status(status, flags)
+    return or_status(FactorSv._fold(chains, N, k), status)

@@ -26,11 +26,11 @@ import dlmfsv_restatement as dr  # noqa: E402
 import fsv_dense_reference as dense  # noqa: E402
 import fsv_restatement as fr  # noqa: E402
 
-from bayesian_dlms_amd import _lib  # noqa: E402
+from bayesian_dlms_amd import _chain, _dlmfsv, _lib  # noqa: E402
 from bayesian_dlms_amd.dlm import Dlm, DlmParameters, MaterialisedModel  # noqa: E402
-from bayesian_dlms_amd.dlmfsv import DlmFsv, DlmFsvParameters  # noqa: E402
+from bayesian_dlms_amd.dlmfsv import KIND, DlmFsv, DlmFsvParameters  # noqa: E402
 from bayesian_dlms_amd.engine import Engine, EngineError  # noqa: E402
-from bayesian_dlms_amd.factorsv import INIT_ITERATION, FactorSv, FsvParameters  # noqa: E402
+from bayesian_dlms_amd.factorsv import INIT_ITERATION, FactorSv, FsvParameters, pack_priors  # noqa: E402
 from bayesian_dlms_amd.gibbs import InverseGamma  # noqa: E402
 from bayesian_dlms_amd.stochvol import MASK64, Gaussian, SvParameters  # noqa: E402
 
@@ -409,44 +409,23 @@ def test_the_driver_refuses_a_v_stream_that_does_not_fit(eng, monkeypatch):
 
 
 # ---- exact invariance on the device ----------------------------------------------------------------------------------------------------------
-def _device_sweeps(eng, start, sweeps, seed=dr.SEED, impute_partial=True):
-    """`sweeps` iterations in the default order from `start` with the engine's calls, as the driver composes them."""
+def _driver_sweeps(eng, start, sweeps, seed=dr.SEED, impute_partial=True):
+    """`sweeps` iterations in the default order from `start`: the driver's own sweep on a chain state built from the start's arrays."""
     mat = dr.inv_mat()
-    N, T, p = start["y"].shape
-    k, d = start["beta"].shape[2], mat.d
-    y, theta, beta, v, alpha = (_dev(start[q]) for q in ("y", "theta", "beta", "v", "alpha"))
-    sv = _dev(start["sv"]).reshape(N * k, 3)
-    W = _dev(start["W"][:, :, None] * np.eye(d)).reshape(N, d * d)
-    m0, C0 = _dev(dr.INV_M0), _dev(dr.INV_C0.T.reshape(-1))
-    q = dr.INV_SV_PRIOR
-    svp = (0, 0, q["phi"][0], q["phi"][1], q["mu"][0], q["mu"][1], q["sigma"][0], q["sigma"][1], 100.0, 0.05)
-    fp = fr.fsv_prior_tuple(dr.INV_FSV_PRIOR)
+    N, d = start["y"].shape[0], mat.d
+    q, fp = dr.INV_SV_PRIOR, dr.INV_FSV_PRIOR
+    priors = pack_priors(Gaussian(fp["beta_mean"], fp["beta_sd"]), InverseGamma(*q["sigma"]), Gaussian(*q["mu"]), Gaussian(*q["phi"]),
+                         InverseGamma(fp["sigma_shape"], fp["sigma_scale"]), False)
+    c = _dlmfsv.chain(KIND, ys=_dev(start["y"]), mat=mat, m0=_dev(dr.INV_M0), C0=_dev(dr.INV_C0.T.reshape(-1)),
+                      W=_dev(start["W"][:, :, None] * np.eye(d)).reshape(N, d * d), **{key: _dev(start[key]) for key in ("theta", "beta", "v", "alpha", "sv")})
     empty = ~np.isfinite(start["y"]).all(axis=2).any(axis=1)          # no wholly observed time: the loadings call flags the panel and keeps its inputs
     for it in range(sweeps):
-        cen = eng.dlmfsv_center(mat, y, theta)
-        if impute_partial:
-            imp = eng.dlmfsv_impute(cen["r"], beta, v, alpha, iteration=it, seed=seed, out={"r": cen["r"]})
-            assert not imp["status"].cpu().numpy().any()
-        fac = eng.fsv_factors(cen["r"], beta, v, alpha, iteration=it, seed=seed)
-        f = fac["f"]
-        mix = eng.sv_mixture(f.reshape(N * k, T), alpha.reshape(N * k, T + 1), iteration=it, seed=seed)
-        ff = eng.ar1_ffbs(mix["ystar"], mix["v"], sv, seed=(seed * 1000003 + it + 1) & MASK64, want_filt=False)
-        alpha = ff["theta"].reshape(N, k, T + 1)
-        res = eng.sv_params(ff["theta"], sv, svp, iteration=it, seed=seed)
-        sv = res["sv"]
-        ld = eng.fsv_loadings(cen["r"], f, beta, fp, iteration=it, seed=seed, v=v)
-        beta, v = ld["beta"], ld["v"]
-        var = eng.dlmfsv_variance(beta, v, alpha)
-        out = eng.ffbs(mat, (var["V"].reshape(-1), T * p * p, W.reshape(-1), d * d, m0, 0, C0, 0, p * p, 0), y,
-                       seed=((seed * 1000003 + it + 1) ^ (1 << 63)) & MASK64, want_theta=True, want_stats=True, want_filt=False)
-        theta = out["theta"]
-        W = eng.dinvgamma_step(d, p, out["stats"], dr.INV_PRIOR_W, dr.INV_PRIOR_W, iteration=it, seed=seed)[1]
-        for name, st in (("center", cen), ("factors", fac), ("mixture", mix), ("ar1", ff), ("sv_params", res), ("variance", var), ("ffbs", out)):
-            assert not st["status"].cpu().numpy().any(), name
-        assert not ld["status"].cpu().numpy()[~empty].any()
-    host = lambda a: a.cpu().numpy()
-    return {"y": start["y"], "theta": host(theta), "alpha": host(alpha), "sv": host(sv).reshape(N, k, 3), "beta": host(beta), "v": host(v),
-            "W": np.diagonal(host(W).reshape(N, d, d), axis1=1, axis2=2).copy(), "f": host(f)}
+        st = _dlmfsv.sweep(KIND, eng, c, it, priors, dr.INV_PRIOR_W, seed=seed, literal_missing=not impute_partial)
+        assert set(st) == {"center", "factors", "volatility", "sv_params", "loadings", "variance", "ffbs"} | ({"impute"} if impute_partial else set())
+        for name, flags in st.items():          # ("volatility": the mixture and the AR(1) FFBS call, or'ed by sample_state_ar)
+            assert not _chain.host(flags)[~empty if name == "loadings" else slice(None)].any(), name
+    return {"y": start["y"], "W": np.diagonal(_chain.host(c["W"]).reshape(N, d, d), axis1=1, axis2=2).copy(),
+            **{key: _chain.host(c[key]) for key in ("theta", "alpha", "sv", "beta", "v", "f")}}
 
 
 @functools.lru_cache(maxsize=None)
@@ -460,7 +439,7 @@ def _start():
 @pytest.mark.parametrize("sweeps", [1, 3])
 def test_the_default_order_leaves_the_joint_law_invariant_on_the_device(eng, sweeps):
     start = _start()
-    fig = dr.figures(_device_sweeps(eng, start, sweeps), start)
+    fig = dr.figures(_driver_sweeps(eng, start, sweeps), start)
     print(f"{sweeps} sweep(s): {dr.describe(fig)}  moved: theta {fig['moved theta']:.3f} W {fig['moved W']:.3f}")
     assert dr.failed(fig) == [], dr.describe(fig)
     assert fig["moved theta"] > 0.05 and fig["moved W"] > 0.15          # new draws (tests/gibbs_invariance.py's floor for W)
@@ -470,7 +449,7 @@ def test_the_reference_treatment_of_partially_missing_times_is_what_the_completi
     """Q34, printed only: the device figures without the completion (residual variance 5.10 standard errors after three sweeps on an MI355X;
     6.08 in NumPy, which tests/test_dlmfsv_host.py asserts).  At this size the device figure sits at the bound, so nothing is asserted on it."""
     start = _start()
-    fig = dr.figures(_device_sweeps(eng, start, 3, impute_partial=False), start)
+    fig = dr.figures(_driver_sweeps(eng, start, 3, impute_partial=False), start)
     print(f"reference treatment, 3 sweeps: {dr.describe(fig)}   fails: {dr.failed(fig)}")
     assert np.isfinite([fig[c] for c in dr.CHECKS]).all()
 
@@ -480,7 +459,7 @@ def test_whole_missing_times_alone_leave_the_joint_law_invariant_on_the_device(e
     start = dr.exact_start()
     assert np.array_equal(np.isnan(start["y"]).any(axis=2), np.isnan(start["y"]).all(axis=2)) and np.isnan(start["y"]).any()
     for sweeps in (1, 3):
-        fig = dr.figures(_device_sweeps(eng, start, sweeps), start)
+        fig = dr.figures(_driver_sweeps(eng, start, sweeps), start)
         print(f"whole times only, {sweeps} sweep(s): {dr.describe(fig)}  moved: theta {fig['moved theta']:.3f} W {fig['moved W']:.3f}")
         assert dr.failed(fig) == [], dr.describe(fig)
         assert fig["moved theta"] > 0.05 and fig["moved W"] > 0.15

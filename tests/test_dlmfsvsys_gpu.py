@@ -16,13 +16,12 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dlmfsvsys_restatement as sr  # noqa: E402
-import fsv_restatement as fr  # noqa: E402
 
-from bayesian_dlms_amd import _lib  # noqa: E402
+from bayesian_dlms_amd import _chain, _dlmfsv, _lib  # noqa: E402
 from bayesian_dlms_amd.dlm import Dlm, DlmParameters, MaterialisedModel  # noqa: E402
-from bayesian_dlms_amd.dlmfsvsys import INIT_W, DlmFsvSystem, DlmFsvSystemParameters  # noqa: E402
+from bayesian_dlms_amd.dlmfsvsys import INIT_W, KIND, DlmFsvSystem, DlmFsvSystemParameters  # noqa: E402
 from bayesian_dlms_amd.engine import Engine, EngineError  # noqa: E402
-from bayesian_dlms_amd.factorsv import INIT_ITERATION, FactorSv, FsvParameters  # noqa: E402
+from bayesian_dlms_amd.factorsv import INIT_ITERATION, FactorSv, FsvParameters, pack_priors  # noqa: E402
 from bayesian_dlms_amd.gibbs import InverseGamma  # noqa: E402
 from bayesian_dlms_amd.stochvol import MASK64, Gaussian, SvParameters  # noqa: E402
 
@@ -260,40 +259,22 @@ def test_the_driver_refuses_a_w_stream_that_does_not_fit(eng, monkeypatch):
 
 
 # ---- exact invariance on the device ----------------------------------------------------------------------------------------------------------
-def _device_sweeps(eng, start, sweeps, seed=sr.SEED):
-    """`sweeps` iterations in the default order from `start` with the engine's calls, as the driver composes them."""
+def _driver_sweeps(eng, start, sweeps, seed=sr.SEED):
+    """`sweeps` iterations in the default order from `start`: the driver's own sweep on a chain state built from the start's arrays."""
     mat = sr.inv_mat()
     N, T, p = start["y"].shape
-    k, d = start["beta"].shape[2], mat.d
-    y, theta, beta, v, alpha = (_dev(start[q]) for q in ("y", "theta", "beta", "v", "alpha"))
-    sv = _dev(start["sv"]).reshape(N * k, 3)
-    V = _dev(start["V"][:, :, None] * np.eye(p)).reshape(N, p * p)
-    m0, C0 = _dev(sr.INV_M0), _dev(sr.INV_C0.T.reshape(-1))
-    q = sr.INV_SV_PRIOR
-    svp = (0, 0, q["phi"][0], q["phi"][1], q["mu"][0], q["mu"][1], q["sigma"][0], q["sigma"][1], 100.0, 0.05)
-    fp = fr.fsv_prior_tuple(sr.INV_FSV_PRIOR)
+    q, fp = sr.INV_SV_PRIOR, sr.INV_FSV_PRIOR
+    priors = pack_priors(Gaussian(fp["beta_mean"], fp["beta_sd"]), InverseGamma(*q["sigma"]), Gaussian(*q["mu"]), Gaussian(*q["phi"]),
+                         InverseGamma(fp["sigma_shape"], fp["sigma_scale"]), False)
+    c = _dlmfsv.chain(KIND, ys=_dev(start["y"]), mat=mat, m0=_dev(sr.INV_M0), C0=_dev(sr.INV_C0.T.reshape(-1)),
+                      V=_dev(start["V"][:, :, None] * np.eye(p)).reshape(N, p * p), **{key: _dev(start[key]) for key in ("theta", "beta", "v", "alpha", "sv")})
     for it in range(sweeps):
-        inn = eng.dlmfsvsys_innovations(mat, theta)
-        fac = eng.fsv_factors(inn["w"], beta, v, alpha, iteration=it, seed=seed)
-        f = fac["f"]
-        mix = eng.sv_mixture(f.reshape(N * k, T), alpha.reshape(N * k, T + 1), iteration=it, seed=seed)
-        ff = eng.ar1_ffbs(mix["ystar"], mix["v"], sv, seed=(seed * 1000003 + it + 1) & MASK64, want_filt=False)
-        alpha = ff["theta"].reshape(N, k, T + 1)
-        res = eng.sv_params(ff["theta"], sv, svp, iteration=it, seed=seed)
-        sv = res["sv"]
-        ld = eng.fsv_loadings(inn["w"], f, beta, fp, iteration=it, seed=seed, v=v)
-        beta, v = ld["beta"], ld["v"]
-        var = eng.dlmfsv_variance(beta, v, alpha)
-        out = eng.ffbs(mat, (V.reshape(-1), p * p, var["V"].reshape(-1), T * d * d, m0, 0, C0, 0, 0, d * d), y,
-                       seed=((seed * 1000003 + it + 1) ^ (1 << 63)) & MASK64, want_theta=True, want_stats=True, want_filt=False)
-        theta = out["theta"]
-        V = eng.dinvgamma_step(d, p, out["stats"], sr.INV_PRIOR_V, sr.INV_PRIOR_V, iteration=it, seed=seed)[0]
-        for name, st in (("innovations", inn), ("factors", fac), ("mixture", mix), ("ar1", ff), ("sv_params", res), ("loadings", ld), ("variance", var),
-                         ("ffbs", out)):
-            assert not st["status"].cpu().numpy().any(), name
-    host = lambda a: a.cpu().numpy()
-    return {"y": start["y"], "theta": host(theta), "alpha": host(alpha), "sv": host(sv).reshape(N, k, 3), "beta": host(beta), "v": host(v),
-            "V": np.diagonal(host(V).reshape(N, p, p), axis1=1, axis2=2).copy(), "f": host(f)}
+        st = _dlmfsv.sweep(KIND, eng, c, it, priors, sr.INV_PRIOR_V, seed=seed)
+        assert set(st) == {"innovations", "factors", "volatility", "sv_params", "loadings", "variance", "ffbs"}
+        for name, flags in st.items():          # ("volatility": the mixture and the AR(1) FFBS call, or'ed by sample_state_ar)
+            assert not _chain.host(flags).any(), name
+    return {"y": start["y"], "V": np.diagonal(_chain.host(c["V"]).reshape(N, p, p), axis1=1, axis2=2).copy(),
+            **{key: _chain.host(c[key]) for key in ("theta", "alpha", "sv", "beta", "v", "f")}}
 
 
 @functools.lru_cache(maxsize=None)
@@ -309,7 +290,7 @@ def test_the_default_order_leaves_the_joint_law_invariant_on_the_device(eng, swe
     """Measured on an MI355X (profiles/r17_notes.md): every figure within 2.1 standard errors after one sweep and within 2.8 after three but
     for the residual mean, 4.56 (one of its twelve columns; 2.25 a sweep later, at most 2.34 with other draw seeds); KS p at least 0.057."""
     start = _start()
-    fig = sr.figures(_device_sweeps(eng, start, sweeps), start)
+    fig = sr.figures(_driver_sweeps(eng, start, sweeps), start)
     print(f"{sweeps} sweep(s): {sr.describe(fig)}  moved: theta {fig['moved theta']:.3f} V {fig['moved V']:.3f}")
     assert sr.failed(fig) == [], sr.describe(fig)
     assert fig["moved theta"] > 0.05 and fig["moved V"] > 0.15          # new draws (tests/gibbs_invariance.py's floor)

@@ -1,8 +1,9 @@
 """Gibbs sampler of the DLM with factor stochastic-volatility SYSTEM noise at 512 panels of d = 20 states, k = 3 factors and 1000 times; the
 DLM is 20 local levels under |*| (p = 20, d = 20), simulated at V = 0.25 I, free loadings 0.5, sigma^2 = 0.05 and
 (phi, mu, sigma_eta) = (0.8, -1, 0.3) for every factor, --missing of the single components of y then set missing (default 0.02).  One
-iteration is the steps of bayesian_dlms_amd/dlmfsvsys.py in the default order; everything stays in HBM.  Prints one JSON line: ms per
-iteration and the wall time of each synchronous call (median over --iters iterations after --warmup), the fraction of the iteration that is
+iteration is the steps of bayesian_dlms_amd/dlmfsvsys.py in the default order -- the driver's own sweep, run on a timing wrapper of the engine
+(tools/timed_engine.py); everything stays in HBM.  Prints one JSON line: ms per iteration (the sum of the calls' wall times) and the wall
+time of each synchronous call (median over --iters iterations after --warmup), the fraction of the iteration that is
 the state draw, and for the innovations and the variance call their algorithmic bytes over their wall time as a rate:
   innovations  reads theta (8 N (T + 1) d) and G; writes w (8 N T d): 16 bytes per element
   variance     reads beta, v, alpha (8 N k (T + 1)); writes W (8 N T d^2)
@@ -15,55 +16,33 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+from bayesian_dlms_amd import _dlmfsv  # noqa: E402
 from bayesian_dlms_amd.dlm import Dlm, DlmParameters  # noqa: E402
-from bayesian_dlms_amd.dlmfsvsys import DlmFsvSystem, DlmFsvSystemParameters  # noqa: E402
+from bayesian_dlms_amd.dlmfsvsys import KIND, DlmFsvSystem, DlmFsvSystemParameters  # noqa: E402
 from bayesian_dlms_amd.engine import Engine  # noqa: E402
-from bayesian_dlms_amd.factorsv import FactorSv, FsvParameters  # noqa: E402
-from bayesian_dlms_amd.stochvol import MASK64, SvParameters  # noqa: E402
+from bayesian_dlms_amd.factorsv import FactorSv, FsvParameters, pack_priors  # noqa: E402
+from bayesian_dlms_amd.gibbs import InverseGamma  # noqa: E402
+from bayesian_dlms_amd.stochvol import Gaussian, SvParameters  # noqa: E402
+from timed_engine import time_fill, time_sweeps  # noqa: E402
 
 STEPS = ("innovations", "factors", "mixture", "ar1_ffbs", "sv_params", "loadings", "variance", "ffbs", "v")
+# the engine's methods behind them, in the order of the driver's sweep
+METHODS = ("dlmfsvsys_innovations", "fsv_factors", "sv_mixture", "ar1_ffbs", "sv_params", "fsv_loadings", "dlmfsv_variance", "ffbs", "dinvgamma_step")
 
 
 def run(eng, ys, mod, init, iters, warmup):
-    import torch
     c = DlmFsvSystem.initialise_state(ys, mod, init, eng, seed=1)
-    mat, y, theta, V, m0, C0, W = c["mat"], c["ys"], c["theta"], c["V"], c["m0"], c["C0"], c["W"]
-    w, f, alpha, beta, v = c["y"], c["f"], c["alpha"], c["beta"], c["v"]
-    N, T, p = (int(x) for x in y.shape)
-    k, d = init.fsv.k, mat.d
-    sv = c["sv"].reshape(N * k, 3)
-    bufs = {"ystar": c["ystar"], "v": c["v_mix"]}
-    sv_prior = (0, 0, 0.8, 0.1, 0.0, 1.0, 3.0, 0.3, 100.0, 0.05)
-    fsv_prior = (0, 0.0, 1.0, 3.0, 1.0)
-    prior_v = (3.0, 0.5)
-    rows, status = [], 0
-    for it in range(warmup + iters):
-        torch.cuda.synchronize()
-        t = [time.perf_counter()]
-        inn = eng.dlmfsvsys_innovations(mat, theta, out={"w": w}); t.append(time.perf_counter())
-        fac = eng.fsv_factors(w, beta, v, alpha, iteration=it, seed=1, out={"f": f}); t.append(time.perf_counter())
-        mix = eng.sv_mixture(f.reshape(N * k, T), alpha.reshape(N * k, T + 1), iteration=it, seed=1, out=bufs); t.append(time.perf_counter())
-        ff = eng.ar1_ffbs(mix["ystar"], mix["v"], sv, seed=1000004 + it, want_filt=False); t.append(time.perf_counter())
-        alpha = ff["theta"].reshape(N, k, T + 1)
-        res = eng.sv_params(ff["theta"], sv, sv_prior, iteration=it, seed=1, out={"sv": sv}); t.append(time.perf_counter())
-        ld = eng.fsv_loadings(w, f, beta, fsv_prior, iteration=it, seed=1, v=v, out={"beta": beta, "v": v}); t.append(time.perf_counter())
-        var = eng.dlmfsv_variance(beta, v, alpha, out={"V": W}); t.append(time.perf_counter())
-        out = eng.ffbs(mat, DlmFsvSystem._packed(V, p, W, T, d, m0, C0), y, seed=((1000003 + it + 1) ^ (1 << 63)) & MASK64, want_theta=True,
-                       want_stats=True, want_filt=False); t.append(time.perf_counter())
-        variant = eng.last_variant
-        theta = out["theta"]
-        V = eng.dinvgamma_step(d, p, out["stats"], prior_v, prior_v, iteration=it, seed=1)[0]; t.append(time.perf_counter())
-        for st in (inn, fac, mix, ff, res, ld, var, out):
-            status |= int(st["status"].max().item())
-        if it >= warmup:
-            rows.append([t[-1] - t[0]] + [b - a for a, b in zip(t[:-1], t[1:])])
-    med = np.median(np.array(rows) * 1e3, axis=0)
+    N, T, p = (int(x) for x in c["ys"].shape)
+    k, d = init.fsv.k, c["mat"].d
+    priors = pack_priors(Gaussian(0.0, 1.0), InverseGamma(3.0, 0.3), Gaussian(0.0, 1.0), Gaussian(0.8, 0.1), InverseGamma(3.0, 1.0), False)
+    sweep = lambda timed, it: _dlmfsv.sweep(KIND, timed, c, it, priors, InverseGamma(3.0, 0.5), seed=1)
+    med, variant, status = time_sweeps(eng, sweep, METHODS, iters, warmup)
+    beta, v, V, W = c["beta"], c["v"], c["V"], c["W"]
     res = {"ms_per_iter": round(float(med[0]), 3), "ffbs_variant": variant}
     res.update({name + "_ms": round(float(x), 3) for name, x in zip(STEPS, med[1:])})
     res["ffbs_fraction"] = round(res["ffbs_ms"] / res["ms_per_iter"], 4)
@@ -72,14 +51,7 @@ def run(eng, ys, mod, init, iters, warmup):
         res[name + "_bytes"] = nbytes[name]
         res[name + "_gbs"] = round(nbytes[name] / (res[name + "_ms"] * 1e-3) / 1e9, 1)
     # the same bytes written by dlm_buffer_fill into the W stream's buffer
-    fills = []
-    for _ in range(warmup + iters):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        eng._check(eng.lib.dlm_buffer_fill(eng.h, W.data_ptr(), 0, 0, 8 * N * T * d * d))
-        eng.sync()
-        fills.append(time.perf_counter() - t0)
-    fill_ms = float(np.median(fills[warmup:]) * 1e3)
+    fill_ms = time_fill(eng, W, 8 * N * T * d * d, iters, warmup)
     res["fill_w_bytes"], res["fill_w_ms"], res["fill_w_gbs"] = 8 * N * T * d * d, round(fill_ms, 3), round(8 * N * T * d * d / (fill_ms * 1e-3) / 1e9, 1)
     res["last_draw_mean"] = {"free_beta": round(float(beta.cpu().numpy()[:, np.tril(np.ones((d, k), bool), -1)].mean()), 3),
                              "sigma2": round(float(v.mean().item()), 3),

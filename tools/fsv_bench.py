@@ -1,8 +1,9 @@
 """Factor stochastic-volatility Gibbs at 512 panels of p = 20 series, k = 3 factors and 1000 times, simulated at free loadings 0.5,
 sigma^2 = 0.25 and (phi, mu, sigma_eta) = (0.8, 0, 0.3) for every factor.  One iteration = dlm_sv_mixture_batch, dlm_ar1_ffbs_batch,
-dlm_sv_params_batch on the N k factor series, then dlm_fsv_factors_batch and dlm_fsv_loadings_batch; everything stays in HBM.
-Prints one JSON line per arithmetic (default, literal): ms per iteration (median over --iters iterations after --warmup), the wall
-time of each of the five synchronous calls, and for the two new calls their algorithmic bytes over their wall time, as a rate and
+dlm_sv_params_batch on the N k factor series, then dlm_fsv_factors_batch and dlm_fsv_loadings_batch -- the driver's own
+factorsv.factor_half, run on a timing wrapper of the engine (tools/timed_engine.py); everything stays in HBM.
+Prints one JSON line per arithmetic (default, literal): ms per iteration (the sum of the calls' wall times; median over --iters iterations
+after --warmup), the wall time of each of the five synchronous calls, and for the two new calls their algorithmic bytes over their wall time, as a rate and
 as a share of the 8 TB/s nominal HBM peak DESIGN.md 4.5 prices against (a plain device copy reaches 4.6-5.3 TB/s there):
   factors   reads y (8 N T p), alpha (8 N k (T + 1)), beta and v; writes f (8 N k T)
   loadings  reads y (8 N T p), f (8 N k T), beta; writes beta and v
@@ -13,17 +14,19 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from bayesian_dlms_amd.engine import Engine  # noqa: E402
-from bayesian_dlms_amd.factorsv import FactorSv, FsvParameters  # noqa: E402
-from bayesian_dlms_amd.stochvol import SvParameters  # noqa: E402
+from bayesian_dlms_amd.factorsv import FactorSv, FsvParameters, factor_half, pack_priors  # noqa: E402
+from bayesian_dlms_amd.gibbs import InverseGamma  # noqa: E402
+from bayesian_dlms_amd.stochvol import Gaussian, SvParameters  # noqa: E402
+from timed_engine import time_sweeps  # noqa: E402
 
 HBM_NOMINAL = 8.0e12
+METHODS = ("sv_mixture", "ar1_ffbs", "sv_params", "fsv_factors", "fsv_loadings")          # sampleStep's order
 
 
 def call_bytes(N, T, p, k):
@@ -33,34 +36,13 @@ def call_bytes(N, T, p, k):
 
 
 def run(eng, y, init, iters, warmup, literal):
-    import torch
     N, T, p = (int(x) for x in y.shape)
     k = init.k
-    lit = 1 if literal else 0
     c = FactorSv.initialise_state_ar(y, init, eng, seed=1, literal=literal)
-    f, alpha, sv, beta, v = c["f"], c["alpha"], c["sv"].reshape(N * k, 3), c["beta"], c["v"]
-    bufs = {"ystar": c["ystar"], "v": c["v_mix"]}
-    sv_prior = (0, lit, 0.8, 0.1, 0.0, 1.0, 3.0, 0.3, 100.0, 0.05)
-    fsv_prior = (lit, 0.0, 1.0, 3.0, 1.0)
-    rows, status = [], 0
-    for it in range(warmup + iters):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        mix = eng.sv_mixture(f.reshape(N * k, T), alpha.reshape(N * k, T + 1), iteration=it, seed=1, out=bufs)
-        t1 = time.perf_counter()
-        ff = eng.ar1_ffbs(mix["ystar"], mix["v"], sv, seed=1000004 + it, want_filt=False)
-        t2 = time.perf_counter()
-        alpha = ff["theta"].reshape(N, k, T + 1)
-        res = eng.sv_params(ff["theta"], sv, sv_prior, iteration=it, seed=1, out={"sv": sv})
-        t3 = time.perf_counter()
-        fac = eng.fsv_factors(y, beta, v, alpha, iteration=it, seed=1, literal=literal, out={"f": f})
-        t4 = time.perf_counter()
-        ld = eng.fsv_loadings(y, f, beta, fsv_prior, iteration=it, seed=1, v=v, out={"beta": beta, "v": v})
-        t5 = time.perf_counter()
-        status |= int((mix["status"] | ff["status"] | res["status"]).max().item()) | int((fac["status"] | ld["status"]).max().item())
-        if it >= warmup:
-            rows.append((t5 - t0, t1 - t0, t2 - t1, t3 - t2, t4 - t3, t5 - t4))
-    r = np.median(np.array(rows) * 1e3, axis=0)
+    priors = pack_priors(Gaussian(0.0, 1.0), InverseGamma(3.0, 0.3), Gaussian(0.0, 1.0), Gaussian(0.8, 0.1), InverseGamma(3.0, 1.0), literal)
+    sweep = lambda timed, it: factor_half(timed, c, c["y"], priors, iteration=it, seed=1, series_offset=0, literal=literal, factors_last=True)
+    r, _, status = time_sweeps(eng, sweep, METHODS, iters, warmup)
+    beta, v = c["beta"], c["v"]
     nb = call_bytes(N, T, p, k)
     out = {"arithmetic": "literal" if literal else "default", "ms_per_iter": round(float(r[0]), 3), "mixture_ms": round(float(r[1]), 3),
            "ffbs_ms": round(float(r[2]), 3), "params_ms": round(float(r[3]), 3), "factors_ms": round(float(r[4]), 3),
