@@ -114,6 +114,22 @@ class LwDesc(ctypes.Structure):
                 ("learn_v", ctypes.c_int32), ("a", ctypes.c_double)]
 
 
+class RbDesc(ctypes.Structure):
+    """dlm_rb_desc: the number of particles, n0, literal = 1 (Q50, Q57 and Q58), learn_v = 1 (log V is learned too) and the shrinkage a,
+    0 < a <= 1.  The family is Gaussian."""
+    _fields_ = [("n_particles", ctypes.c_int32), ("n0", ctypes.c_int32), ("literal", ctypes.c_int32), ("learn_v", ctypes.c_int32),
+                ("a", ctypes.c_double)]
+
+
+RB_LDS_BYTES = 160 * 1024   # the LDS of a workgroup on gfx950
+
+
+def rb_lds_bytes(d: int, n_particles: int) -> int:
+    """rb_lds_bytes of dlm_rb.hip: the LDS dlm_rb_batch needs for (d, P)."""
+    tri = d * (d + 1) // 2
+    return ((tri + 2 * d + 3) * n_particles + 64 * tri + 3 * d + 1) * 8 + 4 * n_particles
+
+
 class Options(ctypes.Structure):
     _fields_ = [("flags", ctypes.c_uint32), ("mem", ctypes.c_int32),
                 ("seed", ctypes.c_uint64), ("series_offset", ctypes.c_uint64)]
@@ -166,6 +182,8 @@ SYMBOLS = [
                                          _OP, _V, _V, _V, _V, _V, _V, _V, _V]),
     ("dlm_lw_batch", ctypes.c_int, [_V, _MP, _PP, ctypes.POINTER(LwDesc), _V, ctypes.c_int64, _V, ctypes.c_int64, _V, _V, ctypes.c_uint64,
                                     _OP, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
+    ("dlm_rb_batch", ctypes.c_int, [_V, _MP, _PP, ctypes.POINTER(RbDesc), _V, ctypes.c_int64, _V, ctypes.c_int64, _V, ctypes.c_uint64,
+                                    _OP, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
     ("dlm_ou_ffbs_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, ctypes.c_int64, _V, ctypes.c_int64,
                                          _V, _OP, _V, _V, _V]),
     ("dlm_ar1_ffbs_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, ctypes.c_int64, _V, ctypes.c_int64,

@@ -43,6 +43,12 @@ constexpr unsigned DLM_STORVIK_BLOCK_RESAMPLE = 8u, DLM_STORVIK_BLOCK_GAMMA = 9u
 //                     pair of the log-variances (2 q, 2 q + 1) (k < d: log W_kk; k = d: log V).  The second byte is 0.
 constexpr unsigned DLM_KEY_LW = 0x4C570000u;         // "LW", a zero byte and the block byte
 constexpr unsigned DLM_LW_BLOCK_RESAMPLE = 8u, DLM_LW_BLOCK_FIRST = 9u, DLM_LW_BLOCK_PARAM = 10u;
+//   DLM_KEY_RB        dlm_rb_batch: comp and attempt field as DLM_KEY_PF (slot t or DLM_RB_SLOT_INIT, the particle).  The state is integrated out, so
+//                     there are no state normals.  The low byte of the key is the BLOCK: DLM_RB_BLOCK_RESAMPLE the uniform of the second stage's
+//                     resampling, DLM_RB_BLOCK_FIRST the uniform of the first (auxiliary) stage's, DLM_RB_BLOCK_PARAM + q the Box-Muller pair of
+//                     the log-variances (2 q, 2 q + 1) (k < d: log W_kk; k = d: log V).  The second byte is 0.
+constexpr unsigned DLM_KEY_RB = 0x52420000u;         // "RB", a zero byte and the block byte
+constexpr unsigned DLM_RB_BLOCK_RESAMPLE = 0u, DLM_RB_BLOCK_FIRST = 1u, DLM_RB_BLOCK_PARAM = 2u;
 
 // ---- the slots ------------------------------------------------------------------------------------------------------------------
 // comp is a 21-bit field (the counter word is comp * 2048 + attempt * 2 + which).  A sampler whose per-time draws take comp = t < T
@@ -98,6 +104,11 @@ static_assert(DLM_LW_SLOT_INIT > (unsigned)DLM_PF_MAX_T - 1, "the Liu-West filte
 static_assert((DLM_PF_MAX_D + 1) / 2 <= (int)DLM_LW_BLOCK_RESAMPLE && DLM_LW_BLOCK_FIRST > DLM_LW_BLOCK_RESAMPLE && DLM_LW_BLOCK_PARAM > DLM_LW_BLOCK_FIRST &&
               DLM_LW_BLOCK_PARAM + (unsigned)(DLM_PF_MAX_D + 2) / 2 <= 256u,
               "the Liu-West filter's blocks (the pairs of d + 1 log-variances included) are distinct and fit the key's low byte");
+constexpr unsigned DLM_RB_SLOT_INIT = DLM_SLOT_TOP;   // dlm_rb_batch, DLM_KEY_RB: the initial log-variances (the steps take the slots t < T <= DLM_PF_MAX_T)
+static_assert(DLM_RB_SLOT_INIT > (unsigned)DLM_PF_MAX_T - 1, "the Rao-Blackwellised filter's initial log-variances lie above every time slot");
+static_assert(DLM_RB_BLOCK_FIRST > DLM_RB_BLOCK_RESAMPLE && DLM_RB_BLOCK_PARAM > DLM_RB_BLOCK_FIRST &&
+              DLM_RB_BLOCK_PARAM + (unsigned)(DLM_PF_MAX_D + 2) / 2 <= 256u,
+              "the Rao-Blackwellised filter's blocks (the pairs of d + 1 log-variances included) are distinct and fit the key's low byte");
 static_assert(DLM_ST_SLOT_SCALE > (unsigned)DLM_ST_MAX_T - 1, "the Student-t step's scalar slots lie above every time slot");
 static_assert(DLM_SV_SLOT_ACCEPT > (unsigned)DLM_SV_MAX_T, "the SV step's scalar slots lie above every time slot");
 static_assert(DLM_SVOU_SLOT_ACC_MU > (unsigned)DLM_SVOU_MAX_T, "the OU step's scalar slots lie above every time slot");

@@ -1537,6 +1537,41 @@ int dlm_lw_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_params_de
   return st.finish(opts->flags & DLM_OPT_ASYNC);
 }
 
+int dlm_rb_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_params_desc* params, const dlm_rb_desc* rb,
+                 const double* prior_v, int64_t prior_v_stride, const double* prior_w, int64_t prior_w_stride,
+                 const double* y, uint64_t iteration, const dlm_options* opts, double* ll, double* mean, double* cov,
+                 double* ess, double* psi_mean, double* psi_var, double* means, double* covs, double* weights, double* psi,
+                 int32_t* status) {
+  if (!e) return DLM_ERR_ARG;
+  if (!model || !params || !rb) return fail(e, DLM_ERR_ARG, "null descriptor");
+  int rc;
+  if ((rc = check_opts(e, opts))) return rc;
+  const int d = model->d, P = rb->n_particles;
+  if ((rc = pf_check(e, model, params, DLM_OBS_GAUSSIAN, rb->literal, P, nullptr, y, ll, "the Rao-Blackwellised filter", !rb->learn_v, false, [&] {
+        if (rb->learn_v != 0 && rb->learn_v != 1) return fail(e, DLM_ERR_ARG, "learn_v: 0 or 1");
+        if (!(rb->a > 0.0 && rb->a <= 1.0)) return fail(e, DLM_ERR_ARG, "a: the shrinkage must satisfy 0 < a <= 1");
+        return pf_check_priors(e, params, d, rb->learn_v, prior_v, prior_v_stride, prior_w, prior_w_stride);
+      }))) return rc;
+  HIP_TRY(e, hipSetDevice(e->device));
+  const size_t lds = dlm::rb_lds_bytes(d, P), have = dlm::lds_limit();
+  if (have && lds > have) return fail(e, DLM_ERR_UNSUPPORTED, "d and n_particles need more LDS than a workgroup of this device gets: (d (d + 1) / 2 + 2 d + 3.5) n_particles + 32 d (d + 1) + 3 d + 1 doubles");
+  dlm::RbArgs a{};
+  const size_t n = model->N, t = model->T, dd = d, np = P;
+  Stager st(e, opts->mem == DLM_MEM_HOST);
+  pf_stage(st, a, model, params, DLM_OBS_GAUSSIAN, rb->literal, rb->n0, P, rb->learn_v ? nullptr : params->V, nullptr, y, opts, iteration, ll, mean, ess, means, weights, status);
+  pf_stage_priors(st, a, rb->learn_v, prior_v, prior_v_stride, prior_w, prior_w_stride);
+  st.out(&a.cov, cov, cov ? n * t * dd * dd : 0);
+  st.out(&a.psi_mean, psi_mean, psi_mean ? n * t * (dd + 1) : 0);
+  st.out(&a.psi_var, psi_var, psi_var ? n * t * (dd + 1) : 0);
+  st.out(&a.covs, covs, covs ? n * (dd * (dd + 1) / 2) * np : 0);
+  st.out(&a.psi, psi, psi ? n * (dd + 1) * np : 0);
+  a.a = rb->a;
+  if ((rc = st.commit())) return rc;
+  e->variant = "rb-wave";
+  HIP_TRY(e, dlm::launch_rb(a, e->stream));
+  return st.finish(opts->flags & DLM_OPT_ASYNC);
+}
+
 static int ar1_common(dlm_engine* e, int32_t N, int32_t T, const double* times, bool ou, const double* y, const double* v,
                       int64_t v_stride, const double* sv, int64_t sv_stride, const double* z, const dlm_options* opts,
                       double* filt, double* theta, int32_t* status);

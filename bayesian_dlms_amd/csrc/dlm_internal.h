@@ -560,6 +560,37 @@ struct LwArgs {           // PfCommonArgs' fields and its own, in the order that
 size_t lw_lds_bytes(int d, int P);   // the cloud [d][P], the log-variances [d + 1][P], the weights and their running sums [2][P], chol(C0), h s [d + 1], the ancestors
 hipError_t launch_lw(const LwArgs& a, hipStream_t s);
 
+// ---- Rao-Blackwellised filter of a Gaussian DLM: the Liu-West filter whose particles carry the Kalman moments (m, C) of the state given their own
+// log-variances in place of a drawn state (RaoBlackwellFilter.scala), dlm_rb.hip ----
+struct RbArgs {           // a struct of its own: the fields the host's shared staging fills keep PfCommonArgs' names
+  int d, T, N, P;         // P particles, a multiple of 64
+  int family, n0, literal, learn_v;   // always DLM_OBS_GAUSSIAN; the second stage resamples when ESS < n0 (resolved: >= 0); 1: Q50, Q57, Q58; 1: log V is a row of psi
+  double a;               // the shrinkage, 0 < a <= 1
+  const double* F; long long f_stride;   // F_t = F + t * f_stride (d doubles, p = 1)
+  const double* G; int n_g; const int* g_index; const double* dt;
+  const double* V; long long v_stride;   // v = V[n * v_stride], read without learn_v only
+  const double* m0; long long m0_stride;
+  const double* C0; long long c0_stride;   // column-major, the lower triangle is read
+  const double* prior_v; long long prior_v_stride;   // [2] = (mean, sd) of log V at n * prior_v_stride, read with learn_v only
+  const double* prior_w; long long prior_w_stride;   // [d][2] = (mean, sd) of log W_kk at n * prior_w_stride
+  const double* obs_param;   // always null (the shared staging's field)
+  const double* y;        // [N][T], NaN = missing
+  DrawStream rs;
+  double* ll;             // [N]
+  double* mean;           // [N][T][d], nullable
+  double* cov;            // [N][T][d][d], nullable: the mixture covariance
+  double* ess;            // [N][T], nullable
+  double* psi_mean;       // [N][T][d+1], nullable
+  double* psi_var;        // [N][T][d+1], nullable
+  double* cloud;          // [N][d][P], nullable: the particles' Kalman means after the last step
+  double* covs;           // [N][d(d+1)/2][P], nullable: their covariances, the lower triangle by rows
+  double* weights;        // [N][P], nullable
+  double* psi;            // [N][d+1][P], nullable
+  int* status;            // [N], nullable (zeroed by the caller)
+};
+size_t rb_lds_bytes(int d, int P);   // the means [d][P], the covariances [d(d+1)/2][P], the log-variances [d + 1][P], the weights and their running sums [2][P], one slot of predicted covariances [d(d+1)/2][64], G^T F [d], the step's mean [d], h s [d + 1], the ancestors
+hipError_t launch_rb(const RbArgs& a, hipStream_t s);
+
 // ---- KalmanFilter.likelihood literally (transition density of the filtered means), dlm_loglik.hip ------
 size_t loglik_q7_ws_bytes(const KArgs& a);
 hipError_t launch_loglik_q7(const KArgs& a, const double* records, void* ws, hipStream_t s);   // a.loglik [N] <- records [N][T+1][d+dd]

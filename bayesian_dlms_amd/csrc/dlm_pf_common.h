@@ -4,7 +4,8 @@
 // multinomial resampling (pf_resample: pf_running_sums, pf_search over pf_ancestor, pf_gather) and the results of a series (pf_results).
 // One wavefront per series, particle i = 64 s + lane, rows of P doubles in LDS; the orders of every sum are those of DESIGN.md 4.19.
 // Every helper is inlined into its kernel; k_pf and k_storvik use all of them, k_lw all but pf_init_cloud and pf_results, either of which
-// moves its register count at some d (profiles/r23_notes.md).
+// moves its register count at some d (profiles/r23_notes.md).  dlm_rb.hip's k_rb, which carries Kalman moments in place of a cloud, uses
+// pf_normal, pf_running_sums, pf_search, pf_gather, pf_resample, pf_normalise and pf_no_results.
 #pragma once
 #include "dlm_wave.h"
 #include "dlm_draws.h"

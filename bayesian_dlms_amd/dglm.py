@@ -1,6 +1,7 @@
 """Dynamic generalised linear models, the bootstrap particle filter, the particle-marginal Metropolis sampler built on it, the
-Storvik filter, which learns the variances online, and the Liu-West and auxiliary particle filters (the reference's Dglm.scala,
-ParticleFilter.scala, Metropolis.dglm, MetropolisHastings.scala:142-154, Storvik.scala, LiuAndWest.scala and AuxFilter.scala).
+Storvik filter, which learns the variances online, the Liu-West and auxiliary particle filters and the Rao-Blackwellised filter of a
+Gaussian DLM (the reference's Dglm.scala, ParticleFilter.scala, Metropolis.dglm, MetropolisHastings.scala:142-154, Storvik.scala,
+LiuAndWest.scala, AuxFilter.scala and RaoBlackwellFilter.scala).
 
 A `Dglm` is a `Dlm` with one of six observation models for its scalar observation; V(0, 0) = v is what each family makes of it
 (include/dlm_engine.h, dlm_pf_batch).  `ParticleFilter(n, n0).filter` runs the engine's filter for one series or a batch of them, with one
@@ -20,7 +21,7 @@ import numpy as np
 from . import _lib
 from .api import pack_observations
 from .dlm import Dlm, DlmParameters, MaterialisedModel, materialise
-from .engine import EngineError, check_pf_shape
+from .engine import EngineError, check_pf_shape, check_rb_lds
 
 
 def logistic_function(upper: float, number):
@@ -346,6 +347,43 @@ class AuxFilter:
     def likelihood(self, mod: Dglm, ys, p: DlmParameters, eng, **kw):
         """AuxFilter.likelihood(mod, ys, n)(p) (AuxFilter.scala:69-75): the log-likelihood estimate of every series."""
         return self.filter(mod, ys, p, eng, **kw)["ll"]
+
+
+class RaoBlackwellFilter:
+    """RaoBlackwellFilter(n, prior, a, n0) (RaoBlackwellFilter.scala) on the engine (dlm_rb_batch): the Liu-West filter for a GAUSSIAN DLM
+    whose particles carry, in place of a drawn state, the Kalman mean and covariance of the state given their own log-variances.  The state
+    is integrated out exactly; only the d + 1 variances are left to the particles, and with every variance known (sd = 0) the filter is the
+    Kalman filter.  The priors are independent `stochvol.Gaussian`s on the LOG-variances as in LiuAndWestFilter; the reference's departures
+    are DESIGN.md 2, Q57-Q62.  Every particle's covariance lives in LDS, so the particle count shrinks with d (engine.check_rb_lds)."""
+
+    def __init__(self, n: int, a: float, n0: int = -1):
+        check_pf_shape(1, 1, int(n))
+        if not 0.0 < float(a) <= 1.0:
+            raise ValueError(f"the shrinkage a must satisfy 0 < a <= 1, got {a!r}")
+        self.n, self.a, self.n0 = int(n), float(a), int(n0)
+
+    def filter(self, mod, ys, p: DlmParameters, prior_v, prior_w, eng, *, learn_v: bool = True, seed: int = 0, iteration: int = 0,
+               series_offset: int = 0, literal: bool = False):
+        """mod: a Dlm or a Gaussian Dglm (any other family: EngineError).  ys, p, prior_v, prior_w as LiuAndWestFilter.filter takes them;
+        learn_v defaults to True.  Returns the engine's outputs as NumPy arrays -- "ll" [N], "mean" [N][T][d], "cov" [N][T][d][d], "ess"
+        [N][T], "psi_mean", "psi_var" [N][T][d+1], "means" [N][d][n], "covs" [N][d(d+1)/2][n], "weights" [N][n], "psi" [N][d+1][n],
+        "status" [N] -- plus the posterior means of the variances from the log-normal moments, "w_mean" [N][T][d] =
+        exp(psi_mean + psi_var / 2) and "v_mean" [N][T] (NaN where V is not learned)."""
+        family = getattr(mod, "family", _lib.OBS_GAUSSIAN)
+        if family != _lib.OBS_GAUSSIAN:
+            raise EngineError(f"the Rao-Blackwellised filter takes a Gaussian DLM (the Kalman step integrates the state out), got family {family!r}")
+        times, y, d, mat = _filter_inputs(mod, ys, self.n)
+        check_rb_lds(d, self.n)
+        learn_v = bool(learn_v)
+        pw = _prior_rows(prior_w, d, "mean", "sd", "Gaussian")
+        pv = np.array([prior_v.mean, prior_v.sd], dtype=np.float64) if learn_v else None
+        out = eng.rb_filter(mat, p, y, pw, n_particles=self.n, a=self.a, prior_v=pv, learn_v=learn_v, n0=self.n0, literal=literal,
+                            iteration=iteration, seed=seed, series_offset=series_offset)
+        out = {k: None if v is None else np.asarray(v) for k, v in out.items()}
+        with np.errstate(invalid="ignore", over="ignore"):
+            moments = np.exp(out["psi_mean"] + out["psi_var"] / 2.0)
+        out["w_mean"], out["v_mean"] = moments[:, :, :d], moments[:, :, d]
+        return out
 
 
 INIT_ITERATION = 0xFFFFFFFF   # the Philox iteration of Metropolis.dglm's evaluation of the initial parameters

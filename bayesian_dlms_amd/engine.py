@@ -79,6 +79,15 @@ def check_pf_shape(d: int, p: int, n_particles: int):
                           f"(one wavefront per series, whole slots of particles), got {n_particles}")
 
 
+def check_rb_lds(d: int, n_particles: int):
+    """What dlm_rb_batch asks of (d, P) beyond check_pf_shape: every particle's covariance lives in LDS."""
+    need = _lib.rb_lds_bytes(d, n_particles)
+    if need > _lib.RB_LDS_BYTES:
+        raise EngineError(f"the Rao-Blackwellised filter keeps every particle's covariance in LDS: d = {d} with {n_particles} particles needs "
+                          f"{need} bytes of the {_lib.RB_LDS_BYTES} a workgroup gets (d <= 3: 1024 particles, d = 4: 896, d = 5: 640, "
+                          "d = 6: 512, d = 7: 384, d = 8: 320, d = 9: 256, d = 10: 192, d = 11 and 12: 128, d = 13 .. 16: 64)")
+
+
 def _pf_shape(mat, n_particles, family):
     """(d, T, P) of a call of one of the three particle filters, after the checks of its shape and of its family."""
     P = int(n_particles)
@@ -688,6 +697,38 @@ class Engine:
         self._hold(flags, yb, ob, pwb, pvb)
         self._check(self.lib.dlm_lw_batch(self.h, md, pd, ctypes.byref(desc), be.ptr(pvb), pv_stride, be.ptr(pwb), pw_stride, be.ptr(ob),
                                           be.ptr(yb), int(iteration), op, *(be.ptr(v) for v in out.values())))
+        return out
+
+    def rb_filter(self, mat, params, y, prior_w, *, n_particles, a, prior_v=None, learn_v=True, n0=-1, literal=False, iteration=0, seed=0,
+                  series_offset=0, flags=0, want_mean=True, want_cov=True, want_ess=True, want_psi_mean=True, want_psi_var=True,
+                  want_means=True, want_covs=True, want_weights=True, want_psi=True):
+        """Rao-Blackwellised particle filter of a Gaussian DLM (dlm_rb_batch; RaoBlackwellFilter.scala): the Liu-West filter of `lw_filter`
+        whose particles carry the Kalman mean and covariance of the state given their own log-variances in place of a drawn state.
+        prior_w, prior_v, a, n0 and params as in lw_filter (sd = 0: a known variance; with every variance known the filter is the Kalman
+        filter).  literal=True: Q50, Q57 and Q58.  Returns {"ll" [N], "mean" [N][T][d], "cov" [N][T][d][d] (the mixture covariance),
+        "ess" [N][T], "psi_mean", "psi_var" [N][T][d+1], "means" [N][d][P], "covs" [N][d(d+1)/2][P] (the lower triangles by rows),
+        "weights" [N][P], "psi" [N][d+1][P], "status" [N]}; the optional ones are None when not wanted, the entries d of psi_mean, psi_var
+        and psi NaN without learn_v."""
+        be = self._backend(y)
+        d, T, P = _pf_shape(mat, n_particles, _lib.OBS_GAUSSIAN)
+        check_rb_lds(d, P)
+        learn_v = bool(learn_v)
+        if learn_v and prior_v is None:
+            raise EngineError("learn_v needs prior_v = (mean, sd) of log V")
+        if not 0.0 < float(a) <= 1.0:
+            raise EngineError(f"the shrinkage a must satisfy 0 < a <= 1, got {a!r}")
+        N, yb, _ = _pf_data(be, y, T, _lib.OBS_GAUSSIAN, None)
+        pvb, pv_stride, pwb, pw_stride = _pf_priors(be, prior_w, prior_v, learn_v, N, d)
+        md, pd, op, keep = self.prepare(mat, params, N, be, flags, seed, series_offset)
+        if pd.v_tstride and not learn_v:
+            raise EngineError("the Rao-Blackwellised filter takes a time-invariant V")
+        out = _pf_outputs(be, N, mean=(want_mean, (N, T, d)), cov=(want_cov, (N, T, d, d)), ess=(want_ess, (N, T)),
+                          psi_mean=(want_psi_mean, (N, T, d + 1)), psi_var=(want_psi_var, (N, T, d + 1)), means=(want_means, (N, d, P)),
+                          covs=(want_covs, (N, d * (d + 1) // 2, P)), weights=(want_weights, (N, P)), psi=(want_psi, (N, d + 1, P)))
+        desc = _lib.RbDesc(P, int(n0), 1 if literal else 0, 1 if learn_v else 0, float(a))
+        self._hold(flags, yb, pwb, pvb)
+        self._check(self.lib.dlm_rb_batch(self.h, md, pd, ctypes.byref(desc), be.ptr(pvb), pv_stride, be.ptr(pwb), pw_stride, be.ptr(yb),
+                                          int(iteration), op, *(be.ptr(v) for v in out.values())))
         return out
 
     def simulate(self, mat, params, N, *, seed=0, series_offset=0, device=False, want_x=True):

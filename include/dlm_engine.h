@@ -647,6 +647,64 @@ int dlm_lw_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_params_de
                  const double* obs_param, const double* y, uint64_t iteration, const dlm_options* opts, double* ll, double* mean,
                  double* ess, double* psi_mean, double* psi_var, double* cloud, double* weights, double* psi, int32_t* status);
 
+/* Rao-Blackwellised particle filter of a Gaussian DLM (RaoBlackwellFilter.scala; Liu & West 2001 with the state integrated out): the Liu-West
+ * filter above whose particles carry, in place of a drawn state, the Kalman mean m_i [d] and covariance C_i [d][d] of the state GIVEN their own
+ * log-variances psi_k,i -- k < d: log W_kk (W is diagonal, params->W is never read); k = d with rb->learn_v = 1: log V.  The family is
+ * Gaussian, so there is no family and no obs_param.  With learn_v = 0 V is params->V (time-invariant) and prior_v is not read.  Priors,
+ * strides, known rows (sd = 0) and rb->a (0 < a <= 1, else DLM_ERR_ARG; h = sqrt(1 - a^2)) as dlm_lw_batch.  With every variance known the
+ * estimate IS the Kalman filter: ll the prediction-error log-likelihood, mean and cov the filtered moments, ESS = P, no Monte-Carlo error.
+ * Shapes and limits as dlm_pf_batch (p = 1, d <= 16, P a multiple of 64 in 64 .. 1024, T <= 2^21 - 2), except the LDS:
+ *   (d(d+1)/2 + 2 d + 3.5) P + 64 d(d+1)/2 + 3 d + 1 doubles
+ * (the covariances dominate; the 64 d(d+1)/2 are one slot of predicted covariances).  On a device with 160 KB per workgroup that grants
+ * P <= 1024 for d <= 3 (d = 3: 130,128 B), 896 for d = 4, 640 for d = 5, 512 for d = 6, 384 for d = 7, 320 for d = 8, 256 for d = 9,
+ * 192 for d = 10, 128 for d = 11 and 12 and P = 64 for d = 13 .. 16 (d = 16: 157,832 B); more is DLM_ERR_UNSUPPORTED.
+ *   m_0,i = m0,  C_0,i = C0 (its lower triangle is read),  psi_k,i = mean_k + sd_k z',  W_{-1,i} = 1 / P.  Per step t, learned rows: sd > 0;
+ *   predict(m, C, psi) stands for  g = G_t^T F_t (dt_t == 0: F_t),  f = g^T m,  Q = g^T C g + dt_t sum_k F_t,k^2 exp psi_k + (exp psi_d or V),
+ *   and N(y; f, Q) for -(1/2) log(2 pi Q) - (1/2) (y - f)^2 / Q:
+ *   a missing y_t:  m_i <- G_t m_i,  C_i <- G_t C_i G_t^T + dt_t diag(exp psi_k,i) (dt_t == 0: nothing); psi and the weights are carried, the
+ *               outputs are written under the carried weights, the ESS repeats (the reference has no such branch, Q60).  Otherwise
+ *   moments:    pbar_k, s2_k and the shrinkage mshr_k,i = a psi_k,i + (1 - a) pbar_k as dlm_lw_batch;
+ *   look-ahead: (f_i, Q_i) = predict(m_i, C_i, mshr_.,i),  lambda_i = N(y_t; f_i, Q_i): the predictive density of the Kalman step;
+ *   stage 1:    omega_i = W_{t-1,i} exp(lambda_i - max lambda),  A = sum omega,  ll += max lambda + log A;  ALWAYS resampled: new particle j is a copy
+ *               (m, C, mshr, lambda) of the first k whose inclusive cumulative omega exceeds u_j times the last one;
+ *   propagate:  psi'_r,j = mshr_r,k + h sqrt(s2_r) z'_r,j (learned rows),  (f, Q) = predict(m_k, C_k, psi'_.,j),  l_j = N(y_t; f, Q) - lambda_k
+ *               (variances that did not move -- a = 1, or every row known -- give l_j = 0 exactly: the same operations on the same numbers);
+ *               a = G_t m_k,  R = G_t C_k G_t^T + dt_t diag(exp psi'_k,j) (dt_t == 0: m_k, C_k),  K = R F_t / Q,  m'_j = a + K (y_t - f),
+ *               C'_j = (I - K F^T) R (I - K F^T)^T + K v K^T, the Joseph form (KalmanFilter.scala:89-90), its lower triangle kept;
+ *   stage 2:    m2 = max l,  w_j = exp(l_j - m2),  B = sum w,  ll += m2 + log(B / P),  W_t,j = w_j / B,  ESS = floor(1 / sum W_t,j^2);
+ *               ESS < n0: multinomial resampling as in dlm_pf_batch of the WHOLE tuple (m_j, C_j, psi_.,j), W_t,j = 1 / P.
+ * rb->n0 < 0 stands for floor(P / 5).  rb->literal = 1 is the reference's arithmetic where it is a one-line switch: the look-ahead density is
+ * N(y_t; f_i, exp mshr_d,i or V), at the predicted mean with the observation variance alone (RaoBlackwellFilter.scala:68-71, Q57); l_j is not
+ * reduced by lambda_k (:54, Q58); s2_k is the unweighted n - 1 variance (Q50).  The reference's other departures (Q59-Q62) are not offered.
+ * ll estimates log p(y_1:T) with the variances integrated over their priors -- for a = 1 without bias on the natural scale (the reference's
+ * filter accumulates no likelihood, Q62); for a < 1 the filter is an approximation.
+ * Outputs, all nullable but ll: ll [N]; mean [N][T][d] = sum_j W_t,j m_j; cov [N][T][d][d] = sum_j W_t,j (C_j + (m_j - mean)(m_j - mean)^T), the
+ * mixture covariance, full and symmetric bit for bit; ess [N][T]; psi_mean, psi_var [N][T][d+1] as dlm_lw_batch (all of step t before the
+ * second stage's resampling); after the last step means [N][d][P], covs [N][d(d+1)/2][P] (the lower triangle by rows: entry (r, c), c <= r,
+ * in row r (r + 1) / 2 + c), weights [N][P], psi [N][d+1][P].  Without learn_v the entries k = d are NaN.  status [N] (nullable):
+ * DLM_ST_NOT_PD for a prior sd that is negative or NaN, a prior mean that is not finite, or a Q that is not positive (NaN included) in the
+ * first observed step, where C0 is first used; DLM_ST_NONFINITE when a maximum is not finite, or A, B or any other Q is not positive and
+ * finite.  Such a series has ll = -inf, NaN in the per-step outputs from the failing step on and in means, covs, weights and psi, and its
+ * neighbours are untouched bit for bit.
+ * Draws: the streams DLM_KEY_RB (dlm_draws.h): a pure function of (opts->seed, opts->series_offset + n, iteration, t or the initial slot,
+ * particle, block), block = the uniform of either stage or a pair of the d + 1 log-variance normals; there are no state draws.  Every sum
+ * runs in a fixed order without atomics: a series' results depend on neither N nor its neighbours nor on how the
+ * batch is split.
+ * opts: mem, seed, series_offset, DLM_OPT_ASYNC.  Like dlm_pf_batch the call does not count as the "previous model-taking call" of
+ * DLM_OPT_MODEL_UNCHANGED. */
+typedef struct {
+  int32_t n_particles;  /* P                                                           */
+  int32_t n0;           /* the second stage resamples when ESS < n0; < 0: floor(P / 5) */
+  int32_t literal;      /* 1: the reference's arithmetic, Q50, Q57 and Q58             */
+  int32_t learn_v;      /* 1: log V is learned too                                     */
+  double a;             /* the shrinkage, 0 < a <= 1                                   */
+} dlm_rb_desc;
+int dlm_rb_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_params_desc* params, const dlm_rb_desc* rb,
+                 const double* prior_v, int64_t prior_v_stride, const double* prior_w, int64_t prior_w_stride,
+                 const double* y, uint64_t iteration, const dlm_options* opts, double* ll, double* mean, double* cov,
+                 double* ess, double* psi_mean, double* psi_var, double* means, double* covs, double* weights, double* psi,
+                 int32_t* status);
+
 /* Per-series log-likelihood by the prediction-error decomposition,
  *   loglik[n] = sum_t log N(y_t^obs ; f_t^obs, Q_t^obs),
  * i.e. KalmanFilter.conditionalLikelihood (KalmanFilter.scala:138-153) summed over the series (steps with no observed

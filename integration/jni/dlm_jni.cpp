@@ -403,6 +403,19 @@ JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_lwFilter(JNIEnv* 
                                      ptr<const double>(obsParam), ptr<const double>(y), static_cast<uint64_t>(iteration), &d.o, ptr<double>(ll), ptr<double>(mean), ptr<double>(ess),
                                      ptr<double>(psiMean), ptr<double>(psiVar), ptr<double>(cloud), ptr<double>(weights), ptr<double>(psi), ptr<int32_t>(status)));
 }
+// ---- Rao-Blackwellised filter of a Gaussian DLM (RaoBlackwellFilter.scala): the Liu-West filter whose particles carry the Kalman mean and covariance of the state given their own log-variances.
+// Priors and strides as lwFilter; dlm_rb_desc crosses as scalars in its field order; every output but ll is optional (0): mean [N][T][d], cov [N][T][d][d], ess [N][T], psiMean, psiVar [N][T][d+1],
+// means [N][d][nParticles], covs [N][d(d+1)/2][nParticles], weights [N][nParticles], psi [N][d+1][nParticles], status [N].
+JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_rbFilter(JNIEnv* env, jobject, jlong h, jlongArray model, jlongArray params, jlongArray opts, jint nParticles, jint n0, jint literal,
+                                                                        jint learnV, jdouble a, jlong priorV, jlong priorVStride, jlong priorW, jlong priorWStride, jlong y, jlong iteration, jlong ll,
+                                                                        jlong mean, jlong cov, jlong ess, jlong psiMean, jlong psiVar, jlong means, jlong covs, jlong weights, jlong psi, jlong status) {
+  Desc d;
+  if (!read_desc(env, model, params, opts, d)) return;
+  const dlm_rb_desc rb{nParticles, n0, literal, learnV, a};
+  throw_if(env, eng(h), dlm_rb_batch(eng(h), &d.m, &d.q, &rb, ptr<const double>(priorV), static_cast<int64_t>(priorVStride), ptr<const double>(priorW), static_cast<int64_t>(priorWStride),
+                                     ptr<const double>(y), static_cast<uint64_t>(iteration), &d.o, ptr<double>(ll), ptr<double>(mean), ptr<double>(cov), ptr<double>(ess), ptr<double>(psiMean),
+                                     ptr<double>(psiVar), ptr<double>(means), ptr<double>(covs), ptr<double>(weights), ptr<double>(psi), ptr<int32_t>(status)));
+}
 // ---- pooled-parameter Gibbs: reduce over series, then over GPUs (RCCL) ---------------------------------------------------------------
 JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_statsPool(JNIEnv* env, jobject, jlong h, jlong stats, jint n, jint l, jlong pooled, jlongArray opts) {
   dlm_options o{};

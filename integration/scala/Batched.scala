@@ -90,6 +90,8 @@ final class Native private[gpu] () {
   @native def storvikFilter(h: Long, model: Array[Long], params: Array[Long], opts: Array[Long], family: Int, nParticles: Int, n0: Int, literal: Int, learnV: Int, priorV: Long, priorVStride: Long, priorW: Long, priorWStride: Long, obsParam: Long, y: Long, iteration: Long, ll: Long, mean: Long, ess: Long, scaleMean: Long, cloud: Long, weights: Long, scales: Long, status: Long): Unit
   /** Liu-West filter of a DGLM (LiuAndWestFilter.step; with a = 1 and prior sds of 0 the auxiliary particle filter of AuxFilter.step): every particle carries its own log-variances, the diagonal of W and with learnV = 1 (Gaussian, Student-t, Beta) V, under Gaussian priors priorV [2] = (mean, sd) of log V and priorW [d][2] of log W_kk (strides in doubles, 0: one prior for the batch; sd = 0: a known variance); a the shrinkage, 0 < a <= 1; literal = 1: Q39, Q50 and Q51.  ll [N]; psiMean, psiVar [N][T][d+1] (mean and variance of the log-variances at every time) and psi [N][d+1][nParticles] are optional (0) like mean, ess, cloud, weights and status */
   @native def lwFilter(h: Long, model: Array[Long], params: Array[Long], opts: Array[Long], family: Int, nParticles: Int, n0: Int, literal: Int, learnV: Int, a: Double, priorV: Long, priorVStride: Long, priorW: Long, priorWStride: Long, obsParam: Long, y: Long, iteration: Long, ll: Long, mean: Long, ess: Long, psiMean: Long, psiVar: Long, cloud: Long, weights: Long, psi: Long, status: Long): Unit
+  /** Rao-Blackwellised filter of a Gaussian DLM (RaoBlackwellFilter): the Liu-West filter whose particles carry the Kalman mean and covariance of the state given their own log-variances instead of a drawn state; priors, strides, a and n0 as lwFilter; literal = 1: Q50, Q57 and Q58.  ll [N]; mean [N][T][d], cov [N][T][d][d] (the mixture covariance), ess [N][T], psiMean, psiVar [N][T][d+1], means [N][d][nParticles], covs [N][d(d+1)/2][nParticles] (lower triangles by rows), weights [N][nParticles], psi [N][d+1][nParticles] and status [N] are optional (0) */
+  @native def rbFilter(h: Long, model: Array[Long], params: Array[Long], opts: Array[Long], nParticles: Int, n0: Int, literal: Int, learnV: Int, a: Double, priorV: Long, priorVStride: Long, priorW: Long, priorWStride: Long, y: Long, iteration: Long, ll: Long, mean: Long, cov: Long, ess: Long, psiMean: Long, psiVar: Long, means: Long, covs: Long, weights: Long, psi: Long, status: Long): Unit
   @native def statsPool(h: Long, stats: Long, n: Int, l: Int, pooled: Long, opts: Array[Long]): Unit
   @native def commUniqueId(): Array[Byte]
   @native def commInitRank(h: Long, nranks: Int, rank: Int, id: Array[Byte]): Unit
