@@ -168,6 +168,8 @@ SYMBOLS = [
                                            _V, _V, _V]),
     ("dlm_sv_ou_params_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, ctypes.POINTER(SvOuPrior), ctypes.c_uint64,
                                               _OP, _V, _V, _V]),
+    ("dlm_sv_knots_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, ctypes.c_int32, _V, ctypes.c_int64, ctypes.c_uint64, _OP,
+                                          _V, _V, _V]),
     ("dlm_fsv_factors_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, _V, ctypes.c_int32,
                                              ctypes.c_uint64, _OP, _V, _V]),
     ("dlm_fsv_loadings_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, _V,

@@ -23,6 +23,9 @@ constexpr unsigned DLM_KEY_SV = 0x5354564Fu;         // "STVO"
 constexpr unsigned DLM_KEY_SVOU = 0x53564F55u;       // "SVOU"
 constexpr unsigned DLM_KEY_FSV = 0x46535620u;        // "FSV "
 constexpr unsigned DLM_KEY_DLMFSV = 0x444C4653u;     // "DLFS"
+//   DLM_KEY_SVKNOT    dlm_sv_knots_batch: comp = s for state s <= T: which 0 the normal of the state's proposal, which 1 the acceptance
+//                     uniform of the block whose first state is s
+constexpr unsigned DLM_KEY_SVKNOT = 0x53564B4Eu;     // "SVKN"
 //   DLM_KEY_PF        dlm_pf_batch: comp = t for the step into observation t, DLM_PF_SLOT_INIT for the initial cloud; attempt = the particle
 //                     (i < 1024: the attempt field's ten bits), which = 0.  The low byte of the key is the BLOCK of that (slot, particle):
 //                     block q < 8 gives the Box-Muller pair (cosine, sine) = the normals of the state components (2 q, 2 q + 1), block
@@ -89,6 +92,7 @@ enum : unsigned {   // dlm_pf_batch, DLM_KEY_PF (the steps take the slots t)
 constexpr int DLM_ST_MAX_T = 0x1FFFFC;     // v_t takes slot t < T
 constexpr int DLM_SV_MAX_T = 0x1FFFF7;     // k_t takes slot t < T; 0x1FFFF8 and 0x1FFFF9 are kept free
 constexpr int DLM_SVOU_MAX_T = 0x1FFFF7;   // the chain's mixture call runs at the same T
+constexpr int DLM_SVKNOT_MAX_T = 0x1FFFF6; // state s takes slot s <= T: T + 1 stays below 2^21 - 8, as the chain's parameter call asks of T
 constexpr int DLM_FSV_MAX_T = 0x1FFFBF;    // the factors' normals take slot t < T
 constexpr int DLM_PF_MAX_T = 0x1FFFFE;     // the step into observation t takes slot t < T
 constexpr int DLM_PF_MAX_D = 16, DLM_PF_MAX_P = 1024;

@@ -1270,6 +1270,50 @@ int dlm_sv_ou_params_batch(dlm_engine* e, int32_t N, int32_t T, const double* ti
   return st.finish(opts->flags & DLM_OPT_ASYNC);
 }
 
+int dlm_sv_knots_batch(dlm_engine* e, int32_t N, int32_t T, const double* y, const int32_t* knots, int32_t B, const double* sv,
+                       int64_t sv_stride, uint64_t iteration, const dlm_options* opts, double* alpha, int32_t* accepted, int32_t* status) {
+  if (!e) return DLM_ERR_ARG;
+  int rc;
+  if ((rc = check_opts(e, opts))) return rc;
+  if (N < 1 || T < 2) return fail(e, DLM_ERR_ARG, "N >= 1 and T >= 2 (the chain's parameter draws need two observations)");
+  if (T > dlm::DLM_SVKNOT_MAX_T) return fail(e, DLM_ERR_ARG, "T + 1 must stay below 2^21 - 8 (the Philox counter's slot field)");
+  if (!y || !knots || !sv || !alpha) return fail(e, DLM_ERR_ARG, "y, knots, sv and alpha are required");
+  if (B < 1 || B > T + 1) return fail(e, DLM_ERR_ARG, "1 <= B <= T + 1 blocks");
+  if (sv_stride != 0 && sv_stride != 3) return fail(e, DLM_ERR_ARG, "sv_stride must be 0 or 3");
+  HIP_TRY(e, hipSetDevice(e->device));
+  // the knots bound every index of the sweep: they are read on the host before anything is launched
+  std::vector<int32_t> kn((size_t)B + 1);
+  if (opts->mem == DLM_MEM_HOST) {
+    kn.assign(knots, knots + B + 1);
+  } else {
+    HIP_TRY(e, hipMemcpyAsync(kn.data(), knots, kn.size() * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+  }
+  if (kn[0] != 0 || kn[B] != T + 1) return fail(e, DLM_ERR_ARG, "knots[0] must be 0 and knots[B] must be T + 1");
+  for (int i = 0; i < B; ++i)
+    if (kn[i + 1] <= kn[i]) return fail(e, DLM_ERR_ARG, "knots must be strictly increasing");
+  dlm::SvKnotsArgs a{};
+  const size_t n = N, t = T;
+  Stager st(e, opts->mem == DLM_MEM_HOST);
+  st.in(&a.y, y, n * t);
+  st.in(&a.knots, (const int*)knots, (size_t)B + 1);
+  st.in(&a.sv, sv, sv_stride ? n * 3 : 3);
+  st.inout(&a.alpha, alpha, n * (t + 1));
+  st.inout(&a.accepted, (int*)accepted, accepted ? n : 0);
+  st.zeroed_out(&a.status, (int*)status, status ? n : 0);
+  if ((rc = st.commit())) return rc;
+  // scratch: the records [N][T+1][2], the proposal [N][T+1], and one more record per series, whose first N words are the row flags
+  if ((rc = ensure_side(e, n, t + 1))) return rc;
+  a.filt = e->side;
+  a.prop = e->side + 2 * n * (t + 1);
+  a.rowflag = (int*)(e->side + 3 * n * (t + 1));
+  a.N = N; a.T = T; a.B = B; a.sv_stride = sv_stride;
+  a.rs = draw_stream(opts, iteration);
+  e->variant = "sv-knots-lane";
+  HIP_TRY(e, dlm::launch_sv_knots(a, e->stream));
+  return st.finish(opts->flags & DLM_OPT_ASYNC);
+}
+
 // what the two factor stochastic-volatility calls ask of their shape
 static int fsv_check_shape(dlm_engine* e, int32_t N, int32_t T, int32_t p, int32_t k) {
   if (N < 1 || T < 2) return fail(e, DLM_ERR_ARG, "N >= 1 and T >= 2 (the factor chains' volatility calls need two observations)");

@@ -406,6 +406,22 @@ struct SvParamsArgs {
 hipError_t launch_sv_mixture(const SvMixArgs& a, hipStream_t s);
 hipError_t launch_sv_params(const SvParamsArgs& a, hipStream_t s);
 
+// ---- AR(1) stochastic volatility: the knot block sampler of the state (StochVolKnots.scala:74-176), one red-black sweep in place,
+// dlm_sv_knots.hip -------------
+struct SvKnotsArgs {
+  int N, T, B;
+  const double* y;        // [N][T]
+  const int* knots;       // [B+1], shared by the batch: 0 = k_0 < ... < k_B = T + 1 (checked on the host)
+  const double* sv; long long sv_stride;   // (phi, mu, sigma_eta): [N][3] with stride 3, or one triple with stride 0
+  DrawStream rs;
+  double* alpha;          // [N][T+1], in and out
+  double* filt;           // scratch [N][T+1][2]: the blocks' filtering records
+  double* prop;           // scratch [N][T+1]: ystar, then the proposal
+  int* rowflag;           // scratch [N]: the flags of the rows the sweep leaves alone
+  int* accepted; int* status;   // nullable
+};
+hipError_t launch_sv_knots(const SvKnotsArgs& a, hipStream_t s);   // the row check, the even blocks, the odd blocks
+
 // ---- stochastic volatility with Ornstein-Uhlenbeck log-volatility on an irregular grid: the three Metropolis moves after the OU
 // FFBS call (StochasticVolatility.scala:350-431, :459-478), dlm_sv_ou.hip -------------
 struct SvOuParamsArgs {

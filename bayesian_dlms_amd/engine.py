@@ -487,6 +487,44 @@ class Engine:
         self._check(call(self.h, N, T, *grid, be.ptr(ab), be.ptr(sb), pr, int(iteration), op, be.ptr(sv_out), be.ptr(acc), be.ptr(status)))
         return {"sv": sv_out, "accepted": acc, "status": status}
 
+    def sv_knots(self, y, alpha, sv, knots, *, iteration, accepted=None, seed=0, series_offset=0, out=None):
+        """One sweep of the knot block sampler over the log-volatility paths of N chains (dlm_sv_knots_batch;
+        StochasticVolatilityKnots.sampleState, StochVolKnots.scala:74-176): y [N][T] (NaN = missing), alpha [N][T+1] as ar1_ffbs writes
+        its theta, sv [N][3] or [3] = (phi, mu, sigma), knots [B+1] int32 shared by the batch (0 = knots[0] < ... < knots[B] = T + 1;
+        stochvol.sample_knots draws them).  Every block is proposed from the Gaussian approximation log y^2 + 1.27 ~ N(alpha, pi^2 / 2)
+        given its neighbours and accepted by a Metropolis step against the exact likelihood; even blocks first, then odd blocks.
+        accepted [N] int32 is incremented in place by the number of accepted blocks (None: a fresh zero array).  Returns {"alpha"
+        [N][T+1], "accepted", "status"}: alpha is a new buffer, the input is left as it is -- unless out["alpha"] is given: the sweep
+        runs in that buffer (it may be the input itself)."""
+        be = self._backend(y)
+        N, T = int(y.shape[0]), int(y.shape[1])
+        yb = be.put(y).reshape(N, T)
+        ab = be.put(alpha)
+        if tuple(ab.shape) != (N, T + 1):
+            raise EngineError(f"alpha must be [N][T+1] = {(N, T + 1)}, got {tuple(ab.shape)}")
+        svv = np.asarray(sv, dtype=np.float64) if not hasattr(sv, "data_ptr") else sv
+        if tuple(svv.shape) not in ((3,), (N, 3)):
+            raise EngineError(f"sv must be [3] or [N][3] = {(N, 3)}, got {tuple(svv.shape)}")
+        sv_stride = 3 if svv.ndim == 2 else 0
+        sb, kb = be.put(svv), be.put(knots, np.int32)
+        if kb.ndim != 1 or int(kb.shape[0]) < 2:
+            raise EngineError(f"knots must be [B+1] with B >= 1, got the shape {tuple(kb.shape)}")
+        new = _out_or_empty(be, out, "alpha", (N, T + 1))
+        if new is not ab:
+            if tuple(new.shape) != (N, T + 1):
+                raise EngineError(f"out['alpha'] must be [N][T+1] = {(N, T + 1)}, got {tuple(new.shape)}")
+            if isinstance(new, np.ndarray):
+                np.copyto(new, ab)
+            else:
+                new.copy_(ab)
+                be = self._backend(y)   # (the copy ran on torch's stream: the engine's waits for it)
+        acc = _counter(be, accepted, (N,))
+        status = be.empty((N,), np.int32)
+        op = _lib.Options(0, be.mem, seed, series_offset)
+        self._check(self.lib.dlm_sv_knots_batch(self.h, N, T, be.ptr(yb), be.ptr(kb), int(kb.shape[0]) - 1, be.ptr(sb), sv_stride,
+                                                int(iteration), op, be.ptr(new), be.ptr(acc), be.ptr(status)))
+        return {"alpha": new, "accepted": acc, "status": status}
+
     def fsv_factors(self, y, beta, v, alpha, *, iteration, seed=0, series_offset=0, literal=False, flags=0, out=None):
         """The factor draw of the factor stochastic-volatility sampler (dlm_fsv_factors_batch; FactorSv.sampleFactors,
         FactorSv.scala:168-186) for N panels: y [N][T][p] (NaN = missing; a partially missing time is wholly missing), beta [N][p][k],

@@ -18,6 +18,11 @@ The default is the corrected sampler; literal=True runs t
 are the families the device evaluates: `Gaussian` for mu and for the conjugate phi, `Beta` for the Metropolis-Hastings phi,
 `InverseGamma` for sigma_eta^2; the reference's arbitrary ContinuousDistr of sampleBeta is not offered.
 
+StochasticVolatilityKnots.sample_ar / sample_ar_beta are the same chains with the state drawn by the knot block sampler
+(StochVolKnots.scala): per iteration the knots are drawn on the host (sample_knots) and ONE dlm_sv_knots_batch sweep replaces the
+mixture and FFBS calls -- every block proposed from log y^2 + 1.27 ~ N(alpha, pi^2 / 2) given its neighbours and corrected by a
+Metropolis step, so the invariant law is the posterior of the model itself.
+
 sample_ou is the same chain with an Ornstein-Uhlenbeck log-volatility observed at arbitrary times (StochasticVolatility.sampleOu,
 :343-500):  alpha(t + dt) | alpha(t) ~ N(mu + e^(-phi dt) (alpha(t) - mu), sigma_eta^2 (1 - e^(-2 phi dt)) / (2 phi)),  phi the
 mean-reversion rate.  Its three calls are dlm_sv_mixture_batch, dlm_ou_ffbs_batch and dlm_sv_ou_params_batch (Metropolis moves of phi,
@@ -84,6 +89,27 @@ def initial_parameters(prior_phi, prior_mu: Gaussian, prior_sigma: InverseGamma,
     return out
 
 
+def sample_knots(min_size: int, max_size: int, T: int, rng: np.random.Generator) -> np.ndarray:
+    """The knots of one sweep of the block sampler over the T + 1 states alpha[0..T]: block sizes uniform on [min_size, max_size],
+    accumulated until they cover every state -> int32 [B+1], 0 = knots[0] < ... < knots[B] = T + 1, block i the states
+    knots[i] .. knots[i+1] - 1 (the last block may be shorter than min_size).  The corrected sampleKnots (StochVolKnots.scala:237-256;
+    DESIGN.md 2, Q64-Q65): the reference's knots end at n - 1 and come from scala.util.Random."""
+    if not 1 <= int(min_size) <= int(max_size):
+        raise ValueError(f"block sizes need 1 <= min_size <= max_size, got {min_size}, {max_size}")
+    if T < 1:
+        raise ValueError("T must be >= 1")
+    knots = [0]
+    while knots[-1] < T + 1:
+        knots.append(min(knots[-1] + int(rng.integers(int(min_size), int(max_size) + 1)), T + 1))
+    return np.asarray(knots, dtype=np.int32)
+
+
+def knots_rng(seed: int, iteration: int) -> np.random.Generator:
+    """The host generator of iteration `iteration`'s knots: keyed by (seed, iteration) alone, so every shard of a batch cuts its paths
+    at the same places."""
+    return np.random.default_rng([int(seed) & MASK64, int(iteration), 0x4B4E])
+
+
 class StochasticVolatility:
     @dataclass
     class State:
@@ -94,6 +120,7 @@ class StochasticVolatility:
         alpha: Optional[np.ndarray]
         accepted: np.ndarray
         status: np.ndarray
+        accepted_blocks: Optional[np.ndarray] = None   # StochasticVolatilityKnots: [N], the blocks of the state sweeps accepted so far
 
     @staticmethod
     def simulate(p: SvParameters, T: int, N: int, seed: int = 0):
@@ -165,9 +192,11 @@ class StochasticVolatility:
 
     @staticmethod
     def _sample(ys, prior, beta, prior_phi, prior_mu, prior_sigma, engine, *, n_iter, seed, params0, series_offset, keep_alpha,
-                ffbs, mixture, params, times=None):
+                ffbs, mixture, params, times=None, knots=None, sweep=None):
         # times [T]: the Ornstein-Uhlenbeck chain on that grid (sample_ou) -- the FFBS calls take the grid, the parameter call is
         # sv_ou_params with the grid in front and `accepted` is [N][3]; everything else is the AR(1) chain's plumbing
+        # knots = (min_size, max_size): the state step is ONE sv_knots sweep (StochasticVolatilityKnots) over knots drawn on the host
+        # from a generator keyed by (seed, iteration) -- the same for every shard -- and its acceptances are counted apart
         ou = times is not None
         N, T = int(ys.shape[0]), int(ys.shape[1])
         if T < 2:
@@ -194,10 +223,18 @@ class StochasticVolatility:
         st = StochasticVolatility.initial_state_ar(y, sv, engine, seed=seed, series_offset=series_offset, ffbs=ffbs, mixture=mixture,
                                                    **grid)
         alpha, bufs, status0 = st["alpha"], {"ystar": st["ystar"], "v": st["v"]}, st["status"]
+        blocks = put(np.zeros(N, dtype=np.int32), np.int32) if knots is not None else None
         for it in range(n_iter):
-            st = StochasticVolatility.sample_state_ar(y, alpha, sv, engine, iteration=it, seed=seed, series_offset=series_offset,
-                                                      ffbs=ffbs, mixture=mixture, out=bufs, **grid)
-            alpha, bufs = st["alpha"], {"ystar": st["ystar"], "v": st["v"]}
+            if knots is not None:
+                kn = sample_knots(knots[0], knots[1], T, knots_rng(seed, it))
+                run_sweep = sweep if sweep is not None else engine.sv_knots
+                st = run_sweep(y, alpha, sv, kn, iteration=it, accepted=blocks, seed=seed, series_offset=series_offset,
+                               out={"alpha": alpha})
+                alpha, blocks = st["alpha"], st["accepted"]
+            else:
+                st = StochasticVolatility.sample_state_ar(y, alpha, sv, engine, iteration=it, seed=seed, series_offset=series_offset,
+                                                          ffbs=ffbs, mixture=mixture, out=bufs, **grid)
+                alpha, bufs = st["alpha"], {"ystar": st["ystar"], "v": st["v"]}
             res = run_params(*lead, alpha, sv, prior, iteration=it, accepted=acc, seed=seed, series_offset=series_offset,
                              out={"sv": sv})
             sv, acc = res["sv"], res["accepted"]
@@ -205,7 +242,8 @@ class StochasticVolatility:
             if it == 0:
                 status = or_status(status, status0)
             yield StochasticVolatility.State(host(sv).copy(), host(alpha).copy() if keep_alpha else None,
-                                             host(acc).astype(np.int32), status)
+                                             host(acc).astype(np.int32), status,
+                                             None if blocks is None else host(blocks).astype(np.int32))
 
     @staticmethod
     def sample_uni(ys, prior_phi: Gaussian, prior_mu: Gaussian, prior_sigma: InverseGamma, engine, *, n_iter: int, seed: int = 0,
@@ -261,3 +299,56 @@ class StochasticVolatility:
                                             params0=params0, series_offset=series_offset, keep_alpha=keep_alpha, ffbs=ffbs,
                                             mixture=mixture, params=params, times=times)
 
+
+
+class StochasticVolatilityKnots:
+    """The stochastic-volatility sampler whose state step is the knot block sampler (StochasticVolatilityKnots.sampleParametersAr /
+    sampleArBeta, StochVolKnots.scala:291-379): per iteration the knots are drawn on the host (sample_knots from knots_rng(seed,
+    iteration)), ONE dlm_sv_knots_batch sweep moves alpha in place -- every block proposed from the Gaussian approximation
+    log y^2 + 1.27 ~ N(alpha, pi^2 / 2) given its neighbours and corrected by a Metropolis step, so the chain's invariant law is the
+    posterior of the model itself, not of the seven-component mixture -- and dlm_sv_params_batch draws (phi, mu, sigma) as in
+    StochasticVolatility.sample_uni / sample_beta.  The chain starts from initial_state_ar.  State.accepted keeps its meaning (the
+    Beta proposal's acceptances); State.accepted_blocks [N] counts the accepted blocks.  There is no literal mode of the state step
+    (DESIGN.md 2, Q63-Q66); literal=True is the parameter step's (Q16-Q19)."""
+
+    State = StochasticVolatility.State
+
+    @staticmethod
+    def _check_sizes(min_size, max_size):
+        if int(min_size) != min_size or int(max_size) != max_size or not 1 <= min_size <= max_size:
+            raise ValueError(f"block sizes need integers 1 <= min_size <= max_size, got {min_size}, {max_size}")
+        return int(min_size), int(max_size)
+
+    @staticmethod
+    def sample_ar(ys, prior_phi: Gaussian, prior_mu: Gaussian, prior_sigma: InverseGamma, engine, *, n_iter: int, min_size: int = 10,
+                  max_size: int = 100, seed: int = 0, params0=None, literal: bool = False, series_offset: int = 0,
+                  keep_alpha: bool = False, ffbs: Optional[Callable] = None, mixture: Optional[Callable] = None,
+                  params: Optional[Callable] = None, sweep: Optional[Callable] = None) -> Iterator["StochasticVolatility.State"]:
+        """sampleParametersAr (:354-369) for N independent series: ys [N][T] (NaN = missing; numpy or a torch device tensor), phi from
+        its Gaussian conjugate conditional on (-1, 1).  min_size / max_size: the block sizes of sample_knots (the reference passes 10,
+        100).  Everything else as StochasticVolatility.sample_uni; sweep= replaces engine.sv_knots, for tests."""
+        if not isinstance(prior_phi, Gaussian) or not isinstance(prior_mu, Gaussian) or not isinstance(prior_sigma, InverseGamma):
+            raise TypeError("the device evaluates a Gaussian prior of phi and of mu and an InverseGamma prior of sigma_eta^2 only")
+        knots = StochasticVolatilityKnots._check_sizes(min_size, max_size)
+        prior = _lib.SvPrior(0, 1 if literal else 0, prior_phi.mean, prior_phi.sd, prior_mu.mean, prior_mu.sd, prior_sigma.shape,
+                             prior_sigma.scale, 100.0, 0.05)
+        return StochasticVolatility._sample(ys, prior, False, prior_phi, prior_mu, prior_sigma, engine, n_iter=n_iter, seed=seed,
+                                            params0=params0, series_offset=series_offset, keep_alpha=keep_alpha, ffbs=ffbs,
+                                            mixture=mixture, params=params, knots=knots, sweep=sweep)
+
+    @staticmethod
+    def sample_ar_beta(ys, prior_phi: Beta, prior_mu: Gaussian, prior_sigma: InverseGamma, engine, *, n_iter: int, min_size: int = 10,
+                       max_size: int = 100, seed: int = 0, params0=None, literal: bool = False, series_offset: int = 0,
+                       keep_alpha: bool = False, prop_lambda: float = 100.0, prop_tau: float = 0.05, ffbs: Optional[Callable] = None,
+                       mixture: Optional[Callable] = None, params: Optional[Callable] = None,
+                       sweep: Optional[Callable] = None) -> Iterator["StochasticVolatility.State"]:
+        """sampleArBeta (:371-379): as sample_ar with phi in (0, 1) moved by Metropolis-Hastings, proposal
+        Beta(lambda phi + tau, lambda (1 - phi) + tau) (the reference passes 100, 0.05), prior Beta(a, b)."""
+        if not isinstance(prior_phi, Beta) or not isinstance(prior_mu, Gaussian) or not isinstance(prior_sigma, InverseGamma):
+            raise TypeError("the device evaluates a Beta prior of phi, a Gaussian prior of mu and an InverseGamma prior of sigma_eta^2 only")
+        knots = StochasticVolatilityKnots._check_sizes(min_size, max_size)
+        prior = _lib.SvPrior(1, 1 if literal else 0, prior_phi.a, prior_phi.b, prior_mu.mean, prior_mu.sd, prior_sigma.shape,
+                             prior_sigma.scale, float(prop_lambda), float(prop_tau))
+        return StochasticVolatility._sample(ys, prior, True, prior_phi, prior_mu, prior_sigma, engine, n_iter=n_iter, seed=seed,
+                                            params0=params0, series_offset=series_offset, keep_alpha=keep_alpha, ffbs=ffbs,
+                                            mixture=mixture, params=params, knots=knots, sweep=sweep)

@@ -387,6 +387,35 @@ int dlm_sv_ou_params_batch(dlm_engine* e, int32_t N, int32_t T, const double* ti
                            const dlm_sv_ou_prior* prior, uint64_t iteration, const dlm_options* opts, double* sv_out,
                            int32_t* accepted, int32_t* status);
 
+/* The knot block sampler of the AR(1) stochastic-volatility state (StochasticVolatilityKnots.sampleBlock / sampleState,
+ * StochVolKnots.scala:74-176): one sweep over N independent chains, in place.  Where dlm_sv_mixture_batch + dlm_ar1_ffbs_batch leave the
+ * posterior under the seven-component approximation of log eps^2 invariant, this sweep leaves the posterior of the model
+ *   y_t = eps_t exp(alpha_t / 2),  alpha_t = mu + phi (alpha_{t-1} - mu) + eta_t,  eta_t ~ N(0, sigma^2)
+ * itself invariant.  y [N][T] (NaN = missing); alpha [N][T+1], in and out, in the layout of dlm_ar1_ffbs_batch's theta (alpha[0] the
+ * state before the first observation, state s >= 1 observes y[s-1]); sv = (phi, mu, sigma) [N][3] with sv_stride = 3 or one shared
+ * triple with sv_stride = 0; knots [B+1] shared by the batch (as `times` is for the OU calls; they follow opts->mem and are read and
+ * checked on the host before anything runs): knots[0] = 0, knots[B] = T + 1, strictly increasing, block i the states
+ * alpha[knots[i] .. knots[i+1] - 1]; accepted [N] (in / out, nullable): incremented by the number of this call's accepted blocks;
+ * status [N] (nullable).
+ * One block, states lo..hi:
+ *   forward   stepUni on ystar_s = log y_{s-1}^2 + 1.27 with v = pi^2 / 2, from the point mass (alpha[lo-1], 0); lo = 0: from the
+ *             stationary record (mu, sigma^2 / (1 - phi^2)), alpha[0]'s own prior;
+ *   backward  backStepUni from the fixed alpha[hi+1]; hi = T: from a draw of the last filtering distribution;
+ *   accept    Metropolis.mAccept: Delta = sum_{s in block, s >= 1, y_{s-1} observed} [g(alpha'_s) - g(alpha_s)],
+ *             g(a) = -1/2 (a + y^2 e^{-a}) + (ystar - a)^2 / pi^2; accepted when log u < Delta; a block that observes nothing always.
+ * Sweep order: red-black -- the even blocks, then the odd blocks, each a launch with one GPU lane per (series, block); given the odd
+ * blocks the even ones are conditionally independent (each reads alpha[lo-1] and alpha[hi+1] only), so this is a valid Gibbs scan.
+ * An observed y whose log y^2 is not finite is treated as missing in the proposal and in Delta and the series gets DLM_ST_NONFINITE
+ * (Q20).  A series with |phi| >= 1 or sigma <= 0 gets DLM_ST_NOT_PD, one with a non-finite alpha or mu DLM_ST_NONFINITE: its row of
+ * alpha and its counter come back untouched.  There is no literal mode.
+ * Draws: a Philox stream of its own, counter (opts->seed, opts->series_offset + n, iteration, slot): slot s holds the normal of state
+ * s; the acceptance uniform of a block sits at the slot of its first state under which = 1.  Reproducible, independent of the sharding
+ * and of how blocks map to wavefronts.  Limits (DLM_ERR_ARG): N >= 1, T >= 2, T + 1 < 2^21 - 8, 1 <= B <= T + 1, knots as above,
+ * sv_stride 0 or 3, y / knots / sv / alpha required.  opts: mem, seed, series_offset, DLM_OPT_ASYNC. */
+int dlm_sv_knots_batch(dlm_engine* e, int32_t N, int32_t T, const double* y, const int32_t* knots, int32_t B,
+                       const double* sv, int64_t sv_stride, uint64_t iteration, const dlm_options* opts,
+                       double* alpha, int32_t* accepted, int32_t* status);
+
 /* The factor half of the factor stochastic-volatility Gibbs sampler (FactorSv.sampleAr, FactorSv.scala:546-562) for N independent
  * panels of p series, T times and k latent factors, 1 <= k <= 8, k <= p <= 64:
  *   y_t = beta f_t + eps_t,  eps_t ~ N(0, diag(v)),  f_{j,t} ~ N(0, exp(alpha_{j,t})),  alpha_j AR(1) with (phi, mu, sigma_eta)_j;

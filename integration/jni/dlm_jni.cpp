@@ -308,6 +308,15 @@ JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_svOuParams(JNIEnv
   throw_if(env, eng(h), dlm_sv_ou_params_batch(eng(h), n, t, ptr<const double>(times), ptr<const double>(alpha), ptr<const double>(svIn), &pr, static_cast<uint64_t>(iteration),
                                                &o, ptr<double>(svOut), ptr<int32_t>(accepted), ptr<int32_t>(status)));
 }
+// ---- the knot block sampler of the AR(1) stochastic-volatility state (StochVolKnots.scala:74-176): one red-black sweep over alpha in place; knots [B+1] int32 shared by
+// the batch (0 = knots[0] < ... < knots[B] = T + 1, placed as opts' mem says); svStride 3 or 0 (one shared triple); accepted = 0, status = 0: none
+JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_svKnots(JNIEnv* env, jobject, jlong h, jint n, jint t, jlong y, jlong knots, jint b, jlong sv, jlong svStride,
+                                                                       jlong iteration, jlongArray opts, jlong alpha, jlong accepted, jlong status) {
+  dlm_options o{};
+  if (!read_opts(env, opts, o)) return;
+  throw_if(env, eng(h), dlm_sv_knots_batch(eng(h), n, t, ptr<const double>(y), ptr<const int32_t>(knots), b, ptr<const double>(sv), static_cast<int64_t>(svStride),
+                                           static_cast<uint64_t>(iteration), &o, ptr<double>(alpha), ptr<int32_t>(accepted), ptr<int32_t>(status)));
+}
 // ---- the factor half of the factor stochastic-volatility sampler (FactorSv.scala:168-186, :253-333, :516-541) around the factor chains'
 // svMixture / ar1Ffbs / svParams calls; alpha = 0: initialiseFactors; vIn = 0: none.  The prior crosses as scalars in dlm_fsv_prior's field order.
 JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_fsvFactors(JNIEnv* env, jobject, jlong h, jint n, jint t, jint p, jint k, jlong y, jlong beta, jlong v, jlong alpha,

@@ -75,6 +75,8 @@ final class Native private[gpu] () {
   @native def svParams(h: Long, n: Int, t: Int, alpha: Long, svIn: Long, phiUpdate: Int, literal: Int, phiA: Double, phiB: Double, muMean: Double, muSd: Double, sigmaShape: Double, sigmaScale: Double, propLambda: Double, propTau: Double, iteration: Long, opts: Array[Long], svOut: Long, accepted: Long, status: Long): Unit
   /** the OU stochastic-volatility sampler's parameter step after ouFfbs (stepOu): Metropolis moves of phi, sigma, mu; the prior, the Beta proposal's (lambda, tau) and the walks' standard deviations as scalars in dlm_sv_ou_prior's order; accepted is [N][3] */
   @native def svOuParams(h: Long, n: Int, t: Int, times: Long, alpha: Long, svIn: Long, literal: Int, phiA: Double, phiB: Double, muMean: Double, muSd: Double, sigmaShape: Double, sigmaScale: Double, propLambda: Double, propTau: Double, deltaSigma: Double, deltaMu: Double, iteration: Long, opts: Array[Long], svOut: Long, accepted: Long, status: Long): Unit
+  /** the knot block sampler of the AR(1) stochastic-volatility state (StochasticVolatilityKnots.sampleState): one red-black sweep over alpha [N][T+1] in place; knots [B+1] Int shared by the batch (0 = knots(0) < ... < knots(B) = T + 1); svStride 3 or 0; accepted [N] (the accepted blocks are added) and status [N] are optional (0) */
+  @native def svKnots(h: Long, n: Int, t: Int, y: Long, knots: Long, b: Int, sv: Long, svStride: Long, iteration: Long, opts: Array[Long], alpha: Long, accepted: Long, status: Long): Unit
   /** the factor half of the factor stochastic-volatility sampler (FactorSv.sampleFactors; sampleSigmaUni, then sampleBeta) around the factor chains' svMixture / ar1Ffbs / svParams calls: y [N][T][p], f [N][k][T], alpha [N][k][T+1] (0: initialiseFactors), beta [N][p][k], v [N][p] (vIn = 0: none); the prior as scalars in dlm_fsv_prior's order */
   @native def fsvFactors(h: Long, n: Int, t: Int, p: Int, k: Int, y: Long, beta: Long, v: Long, alpha: Long, literal: Int, iteration: Long, opts: Array[Long], f: Long, status: Long): Unit
   @native def fsvLoadings(h: Long, n: Int, t: Int, p: Int, k: Int, y: Long, f: Long, betaIn: Long, vIn: Long, literal: Int, betaMean: Double, betaSd: Double, sigmaShape: Double, sigmaScale: Double, iteration: Long, opts: Array[Long], betaOut: Long, vOut: Long, status: Long): Unit
