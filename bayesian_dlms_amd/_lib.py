@@ -121,6 +121,14 @@ class RbDesc(ctypes.Structure):
                 ("a", ctypes.c_double)]
 
 
+class PgDesc(ctypes.Structure):
+    """dlm_pg_desc: the observation family (OBS_*), the number of particles (the reference particle included), ancestor_sampling = 1
+    (0: plain conditional SMC) and the bytes of engine workspace a launch may take (0: PG_WORKSPACE_CAP)."""
+    _fields_ = [("family", ctypes.c_int32), ("n_particles", ctypes.c_int32), ("ancestor_sampling", ctypes.c_int32),
+                ("workspace_cap", ctypes.c_int64)]
+
+
+PG_WORKSPACE_CAP = 8 << 30   # DLM_PG_WORKSPACE_CAP
 RB_LDS_BYTES = 160 * 1024   # the LDS of a workgroup on gfx950
 
 
@@ -186,6 +194,7 @@ SYMBOLS = [
                                     _OP, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
     ("dlm_rb_batch", ctypes.c_int, [_V, _MP, _PP, ctypes.POINTER(RbDesc), _V, ctypes.c_int64, _V, ctypes.c_int64, _V, ctypes.c_uint64,
                                     _OP, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
+    ("dlm_pg_batch", ctypes.c_int, [_V, _MP, _PP, ctypes.POINTER(PgDesc), _V, _V, _V, ctypes.c_uint64, _OP, _V, _V, _V, _V, _V, _V, _V, _V]),
     ("dlm_ou_ffbs_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, ctypes.c_int64, _V, ctypes.c_int64,
                                          _V, _OP, _V, _V, _V]),
     ("dlm_ar1_ffbs_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, ctypes.c_int64, _V, ctypes.c_int64,

@@ -52,6 +52,13 @@ constexpr unsigned DLM_LW_BLOCK_RESAMPLE = 8u, DLM_LW_BLOCK_FIRST = 9u, DLM_LW_B
 //                     the log-variances (2 q, 2 q + 1) (k < d: log W_kk; k = d: log V).  The second byte is 0.
 constexpr unsigned DLM_KEY_RB = 0x52420000u;         // "RB", a zero byte and the block byte
 constexpr unsigned DLM_RB_BLOCK_RESAMPLE = 0u, DLM_RB_BLOCK_FIRST = 1u, DLM_RB_BLOCK_PARAM = 2u;
+//   DLM_KEY_PG        dlm_pg_batch: comp and attempt field as DLM_KEY_PF (slot t for the step into observation t or DLM_PG_SLOT_INIT, the particle).
+//                     The low byte of the key is the BLOCK: q < 8 the Box-Muller pair of the state components (2 q, 2 q + 1) of a free particle,
+//                     DLM_PG_BLOCK_RESAMPLE the [0, 1) uniform of a free particle's ancestor search in step t, DLM_PG_BLOCK_REF the uniform of the
+//                     REFERENCE particle's ancestor (slot t, particle P - 1: ancestor sampling), DLM_PG_BLOCK_FINAL the uniform of the final index
+//                     k_T (slot DLM_PG_SLOT_INIT, particle 0).  The second byte is 0.
+constexpr unsigned DLM_KEY_PG = 0x50470000u;         // "PG", a zero byte and the block byte
+constexpr unsigned DLM_PG_BLOCK_RESAMPLE = 8u, DLM_PG_BLOCK_REF = 9u, DLM_PG_BLOCK_FINAL = 10u;
 
 // ---- the slots ------------------------------------------------------------------------------------------------------------------
 // comp is a 21-bit field (the counter word is comp * 2048 + attempt * 2 + which).  A sampler whose per-time draws take comp = t < T
@@ -113,6 +120,11 @@ static_assert(DLM_RB_SLOT_INIT > (unsigned)DLM_PF_MAX_T - 1, "the Rao-Blackwelli
 static_assert(DLM_RB_BLOCK_FIRST > DLM_RB_BLOCK_RESAMPLE && DLM_RB_BLOCK_PARAM > DLM_RB_BLOCK_FIRST &&
               DLM_RB_BLOCK_PARAM + (unsigned)(DLM_PF_MAX_D + 2) / 2 <= 256u,
               "the Rao-Blackwellised filter's blocks (the pairs of d + 1 log-variances included) are distinct and fit the key's low byte");
+constexpr unsigned DLM_PG_SLOT_INIT = DLM_SLOT_TOP;   // dlm_pg_batch, DLM_KEY_PG: the initial cloud and the final index (the steps take the slots t < T <= DLM_PF_MAX_T)
+static_assert(DLM_PG_SLOT_INIT > (unsigned)DLM_PF_MAX_T - 1, "the conditional filter's initial cloud and final index lie above every time slot");
+static_assert((DLM_PF_MAX_D + 1) / 2 <= (int)DLM_PG_BLOCK_RESAMPLE && DLM_PG_BLOCK_REF > DLM_PG_BLOCK_RESAMPLE && DLM_PG_BLOCK_FINAL > DLM_PG_BLOCK_REF &&
+              DLM_PG_BLOCK_FINAL < 256u,
+              "the conditional filter's blocks (state normals, free ancestors, the reference's ancestor, the final index) are distinct and fit the key's low byte");
 static_assert(DLM_ST_SLOT_SCALE > (unsigned)DLM_ST_MAX_T - 1, "the Student-t step's scalar slots lie above every time slot");
 static_assert(DLM_SV_SLOT_ACCEPT > (unsigned)DLM_SV_MAX_T, "the SV step's scalar slots lie above every time slot");
 static_assert(DLM_SVOU_SLOT_ACC_MU > (unsigned)DLM_SVOU_MAX_T, "the OU step's scalar slots lie above every time slot");

@@ -114,6 +114,8 @@ struct dlm_engine {
   //   zws       E R    the call's normals in the draw kernel's layout
   //   rtsws     E C    shared factors of the RTS smoother (4.13): control words, key and tables of the last call that made them -- kept
   //                    across calls, so nobody else lives here; reused where k_rts_key_check finds the call's key equal to theirs
+  //   pgws      E      dlm_pg_batch without its trace outputs: the clouds [launch][T+1][d][P] | behind them the ancestors [launch][T][P] of ONE launch
+  //                    (the launches of a call follow one another on the engine's stream)
   Workspace* workspaces = nullptr;   // (in front of the Ws members: they link themselves in)
   Ws<void> arena{workspaces};
   Ws<dlm::SparseT> sp_dev{workspaces};
@@ -123,6 +125,7 @@ struct dlm_engine {
   Ws<void> sampws{workspaces};
   Ws<double> zws{workspaces};
   Ws<void> rtsws{workspaces};
+  Ws<void> pgws{workspaces};
   dlm::SparseF* spf_dev = nullptr;     // tables of a structured F (tiled path), allocated once
   int sparse_k = 0;           // 0: some G is not structured (dense MFMA path, regular grids only)
   ncclComm_t comm = nullptr;
@@ -1613,6 +1616,59 @@ int dlm_rb_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_params_de
   if ((rc = st.commit())) return rc;
   e->variant = "rb-wave";
   HIP_TRY(e, dlm::launch_rb(a, e->stream));
+  return st.finish(opts->flags & DLM_OPT_ASYNC);
+}
+
+int dlm_pg_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_params_desc* params, const dlm_pg_desc* pg,
+                 const double* obs_param, const double* y, const double* ref, uint64_t iteration, const dlm_options* opts,
+                 double* ll, double* path, double* stats, int32_t* path_index, double* clouds, int32_t* ancestors,
+                 double* step_weights, int32_t* status) {
+  if (!e) return DLM_ERR_ARG;
+  if (!model || !params || !pg) return fail(e, DLM_ERR_ARG, "null descriptor");
+  int rc;
+  if ((rc = check_opts(e, opts))) return rc;
+  const int d = model->d, P = pg->n_particles;
+  if ((rc = pf_check(e, model, params, pg->family, 0, P, obs_param, y, ll, "particle Gibbs", true, true, [&] {
+        if (pg->ancestor_sampling != 0 && pg->ancestor_sampling != 1) return fail(e, DLM_ERR_ARG, "ancestor_sampling: 0 or 1");
+        if (pg->workspace_cap < 0) return fail(e, DLM_ERR_ARG, "workspace_cap: bytes, or 0 for DLM_PG_WORKSPACE_CAP");
+        if (!ref || !path || !stats) return fail(e, DLM_ERR_ARG, "ref, path and stats are required");
+        if ((clouds == nullptr) != (ancestors == nullptr)) return fail(e, DLM_ERR_ARG, "clouds and ancestors are given together or not at all");
+        return (int)DLM_OK;
+      }))) return rc;
+  HIP_TRY(e, hipSetDevice(e->device));
+  const size_t lds = dlm::pg_lds_bytes(d, P), have = dlm::lds_limit();
+  if (have && lds > have) return fail(e, DLM_ERR_UNSUPPORTED, "d and n_particles need more LDS than a workgroup of this device gets: (d + 2.5) n_particles + d^2 + d doubles");
+  dlm::PgArgs a{};
+  const size_t n = model->N, t = model->T, dd = d, np = P;
+  Stager st(e, opts->mem == DLM_MEM_HOST);
+  pf_stage(st, a, model, params, pg->family, 0, 0, P, params->V, obs_param, y, opts, iteration, ll, nullptr, nullptr, nullptr, nullptr, status);
+  st.in(&a.W, params->W, params->w_stride ? (n - 1) * (size_t)params->w_stride + dd * dd : dd * dd);
+  a.w_stride = params->w_stride;
+  a.ancestor_sampling = pg->ancestor_sampling;
+  st.in(&a.ref, ref, n * (t + 1) * dd);
+  st.out(&a.path, path, n * (t + 1) * dd);
+  st.out(&a.stats, stats, n * (dd + 3));
+  st.out(&a.path_index, (int*)path_index, path_index ? n * (t + 1) : 0);
+  st.out(&a.clouds, clouds, clouds ? n * (t + 1) * dd * np : 0);
+  st.out(&a.ancestors, (int*)ancestors, ancestors ? n * t * np : 0);
+  st.out(&a.step_weights, step_weights, step_weights ? n * t * np : 0);
+  if ((rc = st.commit())) return rc;
+  // the clouds and ancestors of every step: the caller's arrays, or the engine's workspace in launches of whole series under the cap
+  const size_t cloud_doubles = (t + 1) * dd * np, anc_ints = t * np;
+  const size_t per_series = cloud_doubles * sizeof(double) + anc_ints * sizeof(int);
+  size_t chunk = n;
+  if (!clouds) {
+    const size_t cap = pg->workspace_cap ? (size_t)pg->workspace_cap : (size_t)DLM_PG_WORKSPACE_CAP;
+    chunk = std::max<size_t>(1, std::min<size_t>(n, cap / per_series));
+    if ((rc = ensure(e, e->pgws, chunk * per_series))) return rc;
+    a.clouds = (double*)e->pgws.p;
+    a.ancestors = (int*)(a.clouds + chunk * cloud_doubles);
+  }
+  e->variant = "pg-wave";
+  for (size_t first = 0; first < n; first += chunk) {
+    a.n_first = (int)first;
+    HIP_TRY(e, dlm::launch_pg(a, (int)std::min(chunk, n - first), e->stream));
+  }
   return st.finish(opts->flags & DLM_OPT_ASYNC);
 }
 

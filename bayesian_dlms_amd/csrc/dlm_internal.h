@@ -607,6 +607,41 @@ struct RbArgs {           // a struct of its own: the fields the host's shared s
 size_t rb_lds_bytes(int d, int P);   // the means [d][P], the covariances [d(d+1)/2][P], the log-variances [d + 1][P], the weights and their running sums [2][P], one slot of predicted covariances [d(d+1)/2][64], G^T F [d], the step's mean [d], h s [d + 1], the ancestors
 hipError_t launch_rb(const RbArgs& a, hipStream_t s);
 
+// ---- Particle Gibbs: conditional SMC with ancestor sampling, one draw of the state path x_{0:T} | y, V, W of a DGLM (Andrieu, Doucet & Holenstein
+// 2010; Lindsten, Jordan & Schoen 2014; what ParticleGibbs.scala aims at), dlm_pg.hip ----
+// A struct of its own: the fields the host's shared staging fills keep PfCommonArgs' names (n0 and literal are staged and not read).  A LAUNCH serves
+// the series n_first .. n_first + (grid size) - 1 of the call: every per-series array of the call is indexed by the call's n, the two workspaces
+// `clouds` and `ancestors` by the launch's own block index.
+struct PgArgs {
+  int d, T, N, P;         // P particles, a multiple of 64; particle P - 1 is the reference
+  int family, n0, literal, ancestor_sampling;
+  int n_first;            // the launch's first series
+  const double* F; long long f_stride;   // F_t = F + t * f_stride (d doubles, p = 1)
+  const double* G; int n_g; const int* g_index; const double* dt;
+  const double* V; long long v_stride;
+  const double* W; long long w_stride;
+  const double* m0; long long m0_stride;
+  const double* C0; long long c0_stride;
+  const double* obs_param;   // [N], nullable: nu of DLM_OBS_STUDENTT
+  const double* y;        // [N][T], NaN = missing
+  const double* ref;      // [N][T+1][d] the reference path (may be `path`: a series reads all of its own before it writes)
+  DrawStream rs;
+  double* ll;             // [N]
+  double* mean;           // always null (the shared staging's fields)
+  double* ess;
+  double* cloud;
+  double* weights;
+  double* path;           // [N][T+1][d]
+  double* stats;          // [N][d + 3] = [ssy | n | ss (d) | T]
+  int* path_index;        // [N][T+1], nullable
+  double* step_weights;   // [N][T][P], nullable
+  double* clouds;         // [launch][T+1][d][P]: the call's output where it was asked for, else the engine's workspace
+  int* ancestors;         // [launch][T][P]
+  int* status;            // [N], nullable (zeroed by the caller)
+};
+size_t pg_lds_bytes(int d, int P);   // pf_lds_bytes plus d doubles: ref_{t+1}
+hipError_t launch_pg(const PgArgs& a, int n_series, hipStream_t s);   // the series a.n_first .. a.n_first + n_series - 1
+
 // ---- KalmanFilter.likelihood literally (transition density of the filtered means), dlm_loglik.hip ------
 size_t loglik_q7_ws_bytes(const KArgs& a);
 hipError_t launch_loglik_q7(const KArgs& a, const double* records, void* ws, hipStream_t s);   // a.loglik [N] <- records [N][T+1][d+dd]

@@ -1,6 +1,6 @@
 """Dynamic generalised linear models, the bootstrap particle filter, the particle-marginal Metropolis sampler built on it, the
-Storvik filter, which learns the variances online, the Liu-West and auxiliary particle filters and the Rao-Blackwellised filter of a
-Gaussian DLM (the reference's Dglm.scala, ParticleFilter.scala, Metropolis.dglm, MetropolisHastings.scala:142-154, Storvik.scala,
+Storvik filter, which learns the variances online, the Liu-West and auxiliary particle filters, the Rao-Blackwellised filter of a
+Gaussian DLM and particle Gibbs (`ParticleGibbs`: conditional SMC with ancestor sampling, then the conjugate variance draws) (the reference's Dglm.scala, ParticleFilter.scala, Metropolis.dglm, MetropolisHastings.scala:142-154, Storvik.scala,
 LiuAndWest.scala, AuxFilter.scala and RaoBlackwellFilter.scala).
 
 A `Dglm` is a `Dlm` with one of six observation models for its scalar observation; V(0, 0) = v is what each family makes of it
@@ -452,3 +452,128 @@ class Metropolis:
             ll = np.where(take, prop_ll, ll)
             accepted = accepted + take
             yield MetropolisState(state.copy(), ll.copy(), accepted.copy())
+
+
+@dataclass
+class ParticleGibbsState:
+    """One iteration of ParticleGibbs.sample: the state paths [N][T+1][d], the observation variances [N] and the diagonals of W [N][d]
+    behind them (device tensors), the conditional filter's log-likelihood figure of the sweep [N] and the worst status of the sweep."""
+
+    path: object
+    v: object
+    w: object
+    ll: object
+    status: int
+    m0: np.ndarray          # [N][d] and [N][d][d]: the initial parameters', which the sampler does not move
+    c0: np.ndarray
+
+    @property
+    def params(self) -> BatchedParameters:
+        """The chains' parameters as NumPy arrays (a copy off the device)."""
+        v = self.v.detach().cpu().numpy().reshape(-1, 1, 1)
+        w = self.w.detach().cpu().numpy()
+        N, d = w.shape
+        W = np.zeros((N, d, d)); idx = np.arange(d); W[:, idx, idx] = w
+        return BatchedParameters(v, W, self.m0.copy(), self.c0.copy())
+
+
+class ParticleGibbs:
+    """Particle Gibbs for a DGLM on the engine (dlm_pg_batch): what ParticleGibbs.scala and the commented-out ParticleGibbsAncestor.scala aim
+    at, built as the textbook algorithm (Andrieu, Doucet & Holenstein 2010; ancestor sampling: Lindsten, Jordan & Schoen 2014) -- the
+    reference's own step is not a valid kernel.  n particles, the conditioned path among them; one sweep leaves the
+    law of the state path given y and the parameters invariant for any n >= 2.
+
+    The time grid is the FFBS one (`materialise`, as gibbs_dinvgamma_device): the path has T + 1 records, record 0 the state one step
+    before the first observation, y_t belongs to record t + 1, and every one of the T transitions has dt_t != 0 -- which is what makes
+    dlm_dinvgamma_step_batch's InverseGamma(shape + T / 2, .) the exact conditional of W_ii.  (The particle FILTERS put the initial cloud AT
+    the first observation, `materialise_pf`; a path on that grid has one transition less than records.)"""
+
+    def __init__(self, n: int, ancestor_sampling: bool = True):
+        check_pf_shape(1, 1, int(n))
+        self.n, self.ancestor_sampling = int(n), bool(ancestor_sampling)
+
+    @staticmethod
+    def _inputs(mod, ys, n):
+        times, y = _observations(ys)
+        f0 = np.atleast_2d(np.asarray(mod.f(float(times[0])), dtype=np.float64))
+        check_pf_shape(f0.shape[0], f0.shape[1], n)
+        return times, y, materialise(Dlm(mod.f, mod.g), times)
+
+    @staticmethod
+    def _params(p, y):
+        """(N, y [N][T], what Engine.prepare takes) of one parameter set, one per series or a BatchedParameters"""
+        if isinstance(p, DlmParameters):
+            return y.shape[0], y, p
+        bp = BatchedParameters.of(p)
+        if y.shape[0] == 1 and bp.n > 1:
+            y = np.repeat(y, bp.n, axis=0)
+        if y.shape[0] != bp.n:
+            raise EngineError(f"{bp.n} parameter sets for {y.shape[0]} series")
+        return bp.n, y, bp.packed()
+
+    def initial_path(self, mod: Dglm, ys, p, eng, *, seed: int = 0, series_offset: int = 0):
+        """A path to start from, [N][T+1][d]: the FILTERING MEANS of one bootstrap-filter run with n particles (record t + 1 = the mean
+        after y_t; record 0 = m0).  It is not a draw of the smoothing law -- no start has to be: the sweeps forget it geometrically fast,
+        and with ancestor sampling within a few iterations."""
+        times, y, mat = self._inputs(mod, ys, self.n)
+        N, y, params = self._params(p, y)
+        out = eng.particle_filter(mat, params, y, family=mod.family, n_particles=self.n, obs_param=mod.nu, iteration=INIT_ITERATION, seed=seed,
+                                  series_offset=series_offset, want_ess=False, want_cloud=False, want_weights=False)
+        if np.any(np.asarray(out["status"]) != 0):
+            raise EngineError("the bootstrap filter of the initial path failed for some series (status != 0)")
+        m0 = np.asarray(p.m0 if isinstance(p, DlmParameters) else BatchedParameters.of(p).m0, dtype=np.float64)
+        first = np.broadcast_to(m0.reshape(-1, mat.d), (N, mat.d))[:, None, :]
+        return np.concatenate([first, np.asarray(out["mean"])], axis=1)
+
+    def sample_state(self, mod: Dglm, ys, p, ref, eng, *, seed: int = 0, iteration: int = 0, series_offset: int = 0, **want):
+        """One sweep: a new path [N][T+1][d] given the path `ref`, the data and the parameters.  Returns Engine.pg_sweep's dict as NumPy
+        arrays ("ll", "path", "stats", "status" and the traces asked for through want_path_index / want_trace / want_step_weights)."""
+        times, y, mat = self._inputs(mod, ys, self.n)
+        N, y, params = self._params(p, y)
+        out = eng.pg_sweep(mat, params, y, np.asarray(ref, dtype=np.float64), family=mod.family, n_particles=self.n,
+                           ancestor_sampling=self.ancestor_sampling, obs_param=mod.nu, iteration=iteration, seed=seed,
+                           series_offset=series_offset, **want)
+        return {k: None if v is None else np.asarray(v) for k, v in out.items()}
+
+    def sample(self, mod: Dglm, ys, prior_w, init_p, eng, n_iter: int, prior_v=None, seed: int = 0, *, init_path=None,
+               series_offset: int = 0):
+        """The Gibbs sampler, a generator of ParticleGibbsState: iteration k is ONE dlm_pg_batch (the path given the parameters; Philox
+        iteration k under `seed`) and ONE dlm_dinvgamma_step_batch on its statistics (the diagonal of W given the path, and for the
+        Gaussian family V given the path and y), everything device-resident.  prior_w, prior_v: InverseGamma (shape, scale) pairs or objects
+        with .shape / .scale; prior_v applies to the Gaussian family only (any other family keeps init_p's V, and giving one is an error).
+        init_p: one DlmParameters for every chain, one per series or a BatchedParameters (its W is read on the diagonal; m0 and C0 stay).
+        init_path [N][T+1][d]: the first reference path (default: `initial_path`)."""
+        import torch
+        if prior_v is not None and mod.family != _lib.OBS_GAUSSIAN:
+            raise EngineError("prior_v applies to the Gaussian family only: no other family's V has a conjugate draw")
+        times, y, mat = self._inputs(mod, ys, self.n)
+        bp = BatchedParameters.of(init_p, y.shape[0] if isinstance(init_p, DlmParameters) else None)
+        N, d, T = bp.n, mat.d, mat.T
+        if y.shape[0] == 1 and N > 1:
+            y = np.repeat(y, N, axis=0)
+        if y.shape[0] != N:
+            raise EngineError(f"{N} parameter sets for {y.shape[0]} series")
+        path0 = self.initial_path(mod, (times, y), bp, eng, seed=seed, series_offset=series_offset) if init_path is None else init_path
+        dev = torch.device("cuda", eng.device)
+        put = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)
+        yd, path = put(y), put(path0)
+        if tuple(path.shape) != (N, T + 1, d):
+            raise EngineError(f"init_path must be [N][T+1][d] = {(N, T + 1, d)}, got {tuple(path.shape)}")
+        idx = np.arange(d)
+        V, Wd = put(bp.v.reshape(N, 1)), put(bp.w[:, idx, idx])
+        m0, C0 = put(bp.m0.reshape(-1)), put(np.transpose(bp.c0, (0, 2, 1)).reshape(-1))
+        learn_v = prior_v is not None
+        for it in range(n_iter):
+            W = torch.diag_embed(Wd).reshape(N, d * d).contiguous()
+            packed = (V.reshape(-1), 1, W.reshape(-1), d * d, m0, d, C0, d * d)
+            out = eng.pg_sweep(mat, packed, yd, path, family=mod.family, n_particles=self.n, ancestor_sampling=self.ancestor_sampling,
+                               obs_param=mod.nu, iteration=it, seed=seed, series_offset=series_offset)
+            Vn, Wn = eng.dinvgamma_step(d, 1, out["stats"], prior_v if learn_v else (1.0, 1.0), prior_w, iteration=it, seed=seed,
+                                        series_offset=series_offset)
+            bad = out["status"] != 0
+            worst = int(out["status"].max().item())
+            path = torch.where(bad[:, None, None], path, out["path"]) if worst else out["path"]          # a failed series keeps its path and its parameters
+            if learn_v:
+                V = torch.where(bad[:, None], V, Vn.reshape(N, 1))
+            Wd = torch.where(bad[:, None], Wd, Wn.reshape(N, d, d)[:, idx, idx])
+            yield ParticleGibbsState(path, V.reshape(-1), Wd, out["ll"], worst, bp.m0, bp.c0)

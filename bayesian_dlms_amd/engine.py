@@ -769,6 +769,38 @@ class Engine:
                                           int(iteration), op, *(be.ptr(v) for v in out.values())))
         return out
 
+    def pg_sweep(self, mat, params, y, ref, *, family, n_particles, ancestor_sampling=True, obs_param=None, iteration=0, seed=0,
+                 series_offset=0, flags=0, in_place=False, want_path_index=False, want_trace=False, want_step_weights=False,
+                 workspace_cap=0):
+        """One particle-Gibbs draw of the state path of N series (dlm_pg_batch): conditional SMC with P = n_particles particles, the last
+        of which is the reference path ref [N][T+1][d] (dlm_ffbs_batch's convention: record 0 is the state before the first step, y[t]
+        belongs to record t + 1), with ancestor sampling unless ancestor_sampling=False.  y [N][T] (NaN = missing), params and family as
+        `particle_filter`.  in_place=True writes the new path over `ref` (which must then be a contiguous float64 array of the backend).
+        Returns {"ll" [N], "path" [N][T+1][d], "stats" [N][d + 3] = [ssy | n | ss | T] of the drawn path (what `dinvgamma_step` takes),
+        "path_index" [N][T+1] int32 (want_path_index), "clouds" [N][T+1][d][P] and "ancestors" [N][T][P] int32 (want_trace),
+        "step_weights" [N][T][P] (want_step_weights), "status" [N]}; what was not wanted is None.  workspace_cap: the bytes of engine
+        workspace one launch may take (0: _lib.PG_WORKSPACE_CAP); a larger batch runs as several launches, with the same results."""
+        be = self._backend(y)
+        d, T, P = _pf_shape(mat, n_particles, family)
+        N, yb, ob = _pf_data(be, y, T, family, obs_param)
+        if tuple(ref.shape) != (N, T + 1, d):
+            raise EngineError(f"ref must be [N][T+1][d] = {(N, T + 1, d)}, got {tuple(ref.shape)}")
+        rb = be.put(ref)
+        md, pd, op, keep = self.prepare(mat, params, N, be, flags, seed, series_offset)
+        if pd.v_tstride or pd.w_tstride:
+            raise EngineError("particle Gibbs takes time-invariant V and W")
+        out = {"ll": be.empty((N,)), "path": rb if in_place else be.empty((N, T + 1, d)), "stats": be.empty((N, d + 3)),
+               "path_index": be.empty((N, T + 1), np.int32) if want_path_index else None,
+               "clouds": be.empty((N, T + 1, d, P)) if want_trace else None,
+               "ancestors": be.empty((N, T, P), np.int32) if want_trace else None,
+               "step_weights": be.empty((N, T, P)) if want_step_weights else None,
+               "status": be.empty((N,), np.int32)}
+        desc = _lib.PgDesc(int(family), P, 1 if ancestor_sampling else 0, int(workspace_cap))
+        self._hold(flags, yb, ob, rb)
+        self._check(self.lib.dlm_pg_batch(self.h, md, pd, ctypes.byref(desc), be.ptr(ob), be.ptr(yb), be.ptr(rb), int(iteration), op,
+                                          *(be.ptr(v) for v in out.values())))
+        return out
+
     def simulate(self, mat, params, N, *, seed=0, series_offset=0, device=False, want_x=True):
         """Dlm.simulateRegular over the model's time grid for N series (dlm_simulate_batch): (x [N][T+1][d], y [N][T][p])."""
         be = _Device(self.device) if device else _Host()

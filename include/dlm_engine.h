@@ -734,6 +734,51 @@ int dlm_rb_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_params_de
                  double* ess, double* psi_mean, double* psi_var, double* means, double* covs, double* weights, double* psi,
                  int32_t* status);
 
+/* Particle Gibbs for a dynamic generalised linear model: ONE draw of the state path x_{0:T} | y, V, W of every series by conditional SMC
+ * with ancestor sampling (Andrieu, Doucet & Holenstein 2010; Lindsten, Jordan & Schoen 2014).  It is what ParticleGibbs.scala aims at; the
+ * reference's own step is not a valid kernel, so there is no literal mode.  The kernel leaves the law of
+ * x_{0:T} | y invariant for ANY P >= 2: started from a draw of it, `path` is a draw of it.  Shapes and limits as dlm_pf_batch (p = 1,
+ * d <= 16, P a multiple of 64 in 64 .. 1024, time-invariant V and W, T <= 2^21 - 2, the six families); LDS: dlm_pf_batch's plus d doubles.
+ * The path convention is dlm_ffbs_batch's: ref, path [N][T+1][d], record 0 is the state before the first step, y[t] belongs to record
+ * t + 1.  Particle P - 1 is the reference particle.  W_{-1,i} = 1 / P;
+ *   x_0,i = m0 + chol(C0) z (i < P - 1),  x_0,P-1 = ref_0;   then for t = 0 .. T - 1 -- EVERY step resamples, as ParticleGibbs.step does:
+ *   a_t,i (i < P - 1): the first j whose inclusive running sum of W_{t-1} exceeds u_i times the last one;
+ *   a_t,P-1: with pg->ancestor_sampling and dt_t != 0 drawn the same way from omega_j = W_{t-1,j} exp(q_j - max q),
+ *            q_j = -0.5 |L^-1 (ref_{t+1} - G_t x_t,j)|^2 / dt_t, L = chol(W);  otherwise P - 1 (dt_t = 0: no advance, ref_{t+1} is not read);
+ *   x_{t+1,i} = G_t x_{t,a_t,i} + sqrt(dt_t) L z (i < P - 1), x_{t+1,P-1} = ref_{t+1}   (dt_t = 0: x_{t+1,i} = x_{t,a_t,i} for every i);
+ *   a missing y_t: W_t,i = 1 / P.  Otherwise l_i = log p(y_t | F_t^T x_{t+1,i}, v), m = max l_i, w_i = exp(l_i - m), s = sum w_i,
+ *   ll += m + log(s / P), W_t,i = w_i / s;
+ *   at the end k_T ~ W_{T-1} by the same search, path_t = x_t,k_t, k_{t-1} = a_{t-1,k_t}.
+ * The trace-back needs the clouds x_t [T+1][d][P] and the ancestors a_t [T][P] of every step: they go to HBM as whole rows of P, into the
+ * `clouds` / `ancestors` outputs when they are given and otherwise into an engine workspace of (T + 1) d P doubles + T P int32 a series.
+ * A workspace above pg->workspace_cap bytes (0: DLM_PG_WORKSPACE_CAP = 8 GiB) is avoided by splitting the batch into launches of whole
+ * series; one series always runs.  A series' results depend on neither N nor its neighbours nor on the split.
+ * Outputs: ll [N] (the conditional filter's likelihood estimate; a diagnostic, NOT an unbiased estimate); path [N][T+1][d], which may be
+ * the array `ref` itself; stats [N][dlm_stats_len(d, 1, 0)] = [ssy | n | ss (d) | T] of the drawn path in dlm_ffbs_batch's layout --
+ * ss_i = sum over the steps with dt_t != 0 of (path_{t+1} - G_t path_t)_i^2 / dt_t, ssy and n over the observed y_t for DLM_OBS_GAUSSIAN
+ * and 0 otherwise -- so that dlm_dinvgamma_step_batch is the parameter step.  Nullable traces: path_index [N][T+1] (int32, the k_t);
+ * clouds [N][T+1][d][P] and ancestors [N][T][P] (int32), given together or not at all (DLM_ERR_ARG); step_weights [N][T][P] (the W_t).
+ * status [N] (nullable): DLM_ST_NOT_PD for a chol(C0) or chol(W) that meets a pivot that is not positive; DLM_ST_NONFINITE for a
+ * non-finite entry of `ref` that is read, a maximum that is not finite or a sum that is not positive and finite (the ancestor-sampling
+ * sum included).  Such a series has ll = -inf and NaN in path and stats (its traces are what the kernel had written by then); its
+ * neighbours are untouched and the batch completes.
+ * Draws: the streams DLM_KEY_PG (dlm_draws.h), a pure function of (opts->seed, opts->series_offset + n, iteration, slot t or the initial
+ * slot, particle, block): blocks q < 8 the state normals of a free particle, then one block each for a free particle's ancestor uniform,
+ * the reference's ancestor uniform and the final index.  Every sum runs in a fixed order without atomics.
+ * opts: mem, seed, series_offset, DLM_OPT_ASYNC.  Like dlm_pf_batch the call does not count as the "previous model-taking call" of
+ * DLM_OPT_MODEL_UNCHANGED. */
+#define DLM_PG_WORKSPACE_CAP (8ll << 30)
+typedef struct {
+  int32_t family;             /* DLM_OBS_*                                                   */
+  int32_t n_particles;        /* P, the reference particle included                          */
+  int32_t ancestor_sampling;  /* 1: the reference's ancestor is drawn; 0: plain conditional SMC */
+  int64_t workspace_cap;      /* bytes of engine workspace a launch may take; 0: DLM_PG_WORKSPACE_CAP */
+} dlm_pg_desc;
+int dlm_pg_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_params_desc* params, const dlm_pg_desc* pg,
+                 const double* obs_param, const double* y, const double* ref, uint64_t iteration, const dlm_options* opts,
+                 double* ll, double* path, double* stats, int32_t* path_index, double* clouds, int32_t* ancestors,
+                 double* step_weights, int32_t* status);
+
 /* Per-series log-likelihood by the prediction-error decomposition,
  *   loglik[n] = sum_t log N(y_t^obs ; f_t^obs, Q_t^obs),
  * i.e. KalmanFilter.conditionalLikelihood (KalmanFilter.scala:138-153) summed over the series (steps with no observed

@@ -425,6 +425,18 @@ JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_rbFilter(JNIEnv* 
                                      ptr<const double>(y), static_cast<uint64_t>(iteration), &d.o, ptr<double>(ll), ptr<double>(mean), ptr<double>(cov), ptr<double>(ess), ptr<double>(psiMean),
                                      ptr<double>(psiVar), ptr<double>(means), ptr<double>(covs), ptr<double>(weights), ptr<double>(psi), ptr<int32_t>(status)));
 }
+// ---- particle Gibbs for a dynamic generalised linear model (what ParticleGibbs.scala aims at): one conditional-SMC sweep with ancestor sampling per series, the new state path [N][T+1][d] given the path
+// `ref` (path may be ref), with the statistics [N][d+3] dinvgammaStep takes.  dlm_pg_desc crosses as scalars in its field order (workspaceCap = 0: the default cap); obsParam = 0: none; pathIndex
+// [N][T+1] int32, clouds [N][T+1][d][nParticles] with ancestors [N][T][nParticles] int32, stepWeights [N][T][nParticles] and status are optional (0).
+JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_pgSweep(JNIEnv* env, jobject, jlong h, jlongArray model, jlongArray params, jlongArray opts, jint family, jint nParticles,
+                                                                       jint ancestorSampling, jlong workspaceCap, jlong obsParam, jlong y, jlong ref, jlong iteration, jlong ll, jlong path, jlong stats,
+                                                                       jlong pathIndex, jlong clouds, jlong ancestors, jlong stepWeights, jlong status) {
+  Desc d;
+  if (!read_desc(env, model, params, opts, d)) return;
+  const dlm_pg_desc pg{family, nParticles, ancestorSampling, static_cast<int64_t>(workspaceCap)};
+  throw_if(env, eng(h), dlm_pg_batch(eng(h), &d.m, &d.q, &pg, ptr<const double>(obsParam), ptr<const double>(y), ptr<const double>(ref), static_cast<uint64_t>(iteration), &d.o, ptr<double>(ll),
+                                     ptr<double>(path), ptr<double>(stats), ptr<int32_t>(pathIndex), ptr<double>(clouds), ptr<int32_t>(ancestors), ptr<double>(stepWeights), ptr<int32_t>(status)));
+}
 // ---- pooled-parameter Gibbs: reduce over series, then over GPUs (RCCL) ---------------------------------------------------------------
 JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_statsPool(JNIEnv* env, jobject, jlong h, jlong stats, jint n, jint l, jlong pooled, jlongArray opts) {
   dlm_options o{};
