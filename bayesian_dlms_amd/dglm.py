@@ -21,7 +21,7 @@ import numpy as np
 from . import _lib
 from .api import pack_observations
 from .dlm import Dlm, DlmParameters, MaterialisedModel, materialise
-from .engine import EngineError, check_pf_shape, check_rb_lds
+from .engine import EngineError, check_pf_shape, check_rb_lds, check_shrinkage
 
 
 def logistic_function(upper: float, number):
@@ -203,12 +203,39 @@ def _observations(ys):
     return times, y[:, :, 0]
 
 
-def _filter_inputs(mod, ys, n):
-    """Model and observations of a filter of n particles -> (times, y [N][T], d, mat), after the check of the shape."""
+def _filter_inputs(mod, ys, n, grid=materialise_pf):
+    """Model and observations of a filter of n particles -> (times, y [N][T], d, mat), after the check of the shape.  grid: materialise_pf
+    (the initial cloud AT the first observation) or materialise (one step before it: particle Gibbs)."""
     times, y = _observations(ys)
     f0 = np.atleast_2d(np.asarray(mod.f(float(times[0])), dtype=np.float64))
     check_pf_shape(f0.shape[0], f0.shape[1], n)
-    return times, y, f0.shape[0], materialise_pf(mod, times)
+    return times, y, f0.shape[0], grid(Dlm(mod.f, mod.g), times)
+
+
+def _bank(p, y):
+    """(N, y [N][T], what Engine.prepare takes) of one DlmParameters, one per series or a BatchedParameters; ONE series is repeated for
+    N parameter sets, else the counts must agree."""
+    if isinstance(p, DlmParameters):
+        return y.shape[0], y, p
+    bp = BatchedParameters.of(p)
+    if y.shape[0] == 1 and bp.n > 1:
+        y = np.repeat(y, bp.n, axis=0)
+    if y.shape[0] != bp.n:
+        raise EngineError(f"{bp.n} parameter sets for {y.shape[0]} series")
+    return bp.n, y, bp.packed()
+
+
+def _numpy(out):
+    """An engine call's dict with every output as a NumPy array (None stays None)."""
+    return {k: None if v is None else np.asarray(v) for k, v in out.items()}
+
+
+def _lognormal_means(out, d):
+    """out with "w_mean" [N][T][d] and "v_mean" [N][T]: the means of the variances from the moments of their logs."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        moments = np.exp(out["psi_mean"] + out["psi_var"] / 2.0)
+    out["w_mean"], out["v_mean"] = moments[:, :, :d], moments[:, :, d]
+    return out
 
 
 def _prior_rows(prior_w, d, first, second, noun):
@@ -233,18 +260,9 @@ class ParticleFilter:
         particle-marginal sampler needs).  Returns {"ll" [N], "mean" [N][T][d], "ess" [N][T], "cloud" [N][d][n], "weights" [N][n],
         "status" [N]} as NumPy arrays."""
         times, y, d, mat = _filter_inputs(mod, ys, self.n)
-        if isinstance(p, DlmParameters):
-            N, params = y.shape[0], p
-        else:
-            bp = BatchedParameters.of(p)
-            N, params = bp.n, bp.packed()
-            if y.shape[0] == 1 and N > 1:
-                y = np.repeat(y, N, axis=0)
-            if y.shape[0] != N:
-                raise EngineError(f"{N} parameter sets for {y.shape[0]} series")
-        out = eng.particle_filter(mat, params, y, family=mod.family, n_particles=self.n, n0=self.n0, literal=literal, obs_param=mod.nu,
-                                  iteration=iteration, seed=seed, series_offset=series_offset)
-        return {k: None if v is None else np.asarray(v) for k, v in out.items()}
+        N, y, params = _bank(p, y)
+        return _numpy(eng.particle_filter(mat, params, y, family=mod.family, n_particles=self.n, n0=self.n0, literal=literal, obs_param=mod.nu,
+                                          iteration=iteration, seed=seed, series_offset=series_offset))
 
     @staticmethod
     def likelihood(mod: Dglm, ys, n: int, p, eng, **kw):
@@ -275,9 +293,8 @@ class StorvikFilter:
         learn_v = mod.family == _lib.OBS_GAUSSIAN if learn_v is None else bool(learn_v)
         pw = _prior_rows(prior_w, d, "shape", "scale", "InverseGamma")
         pv = np.array([prior_v.shape, prior_v.scale], dtype=np.float64) if learn_v else None
-        out = eng.storvik_filter(mat, p, y, pw, family=mod.family, n_particles=self.n, prior_v=pv, learn_v=learn_v, n0=self.n0,
-                                 literal=literal, obs_param=mod.nu, iteration=iteration, seed=seed, series_offset=series_offset)
-        out = {k: None if v is None else np.asarray(v) for k, v in out.items()}
+        out = _numpy(eng.storvik_filter(mat, p, y, pw, family=mod.family, n_particles=self.n, prior_v=pv, learn_v=learn_v, n0=self.n0,
+                                        literal=literal, obs_param=mod.nu, iteration=iteration, seed=seed, series_offset=series_offset))
         N, T = y.shape
         advances = np.cumsum(mat.dt != 0.0) if mat.dt is not None else np.arange(1, T + 1)
         out["shape_w"] = np.broadcast_to((pw[None, :, 0] + 0.5 * advances[:, None].astype(np.float64))[None], (N, T, d)).copy()
@@ -297,8 +314,7 @@ class LiuAndWestFilter:
 
     def __init__(self, n: int, a: float, n0: int = -1):
         check_pf_shape(1, 1, int(n))
-        if not 0.0 < float(a) <= 1.0:
-            raise ValueError(f"the shrinkage a must satisfy 0 < a <= 1, got {a!r}")
+        check_shrinkage(a, ValueError)
         self.n, self.a, self.n0 = int(n), float(a), int(n0)
 
     def filter(self, mod: Dglm, ys, p: DlmParameters, prior_v, prior_w, eng, *, learn_v: Optional[bool] = None, seed: int = 0,
@@ -315,11 +331,7 @@ class LiuAndWestFilter:
         pv = np.array([prior_v.mean, prior_v.sd], dtype=np.float64) if learn_v else None
         out = eng.lw_filter(mat, p, y, pw, family=mod.family, n_particles=self.n, a=self.a, prior_v=pv, learn_v=learn_v, n0=self.n0,
                             literal=literal, obs_param=mod.nu, iteration=iteration, seed=seed, series_offset=series_offset)
-        out = {k: None if v is None else np.asarray(v) for k, v in out.items()}
-        with np.errstate(invalid="ignore", over="ignore"):
-            moments = np.exp(out["psi_mean"] + out["psi_var"] / 2.0)
-        out["w_mean"], out["v_mean"] = moments[:, :, :d], moments[:, :, d]
-        return out
+        return _lognormal_means(_numpy(out), d)
 
 
 class AuxFilter:
@@ -358,8 +370,7 @@ class RaoBlackwellFilter:
 
     def __init__(self, n: int, a: float, n0: int = -1):
         check_pf_shape(1, 1, int(n))
-        if not 0.0 < float(a) <= 1.0:
-            raise ValueError(f"the shrinkage a must satisfy 0 < a <= 1, got {a!r}")
+        check_shrinkage(a, ValueError)
         self.n, self.a, self.n0 = int(n), float(a), int(n0)
 
     def filter(self, mod, ys, p: DlmParameters, prior_v, prior_w, eng, *, learn_v: bool = True, seed: int = 0, iteration: int = 0,
@@ -379,11 +390,7 @@ class RaoBlackwellFilter:
         pv = np.array([prior_v.mean, prior_v.sd], dtype=np.float64) if learn_v else None
         out = eng.rb_filter(mat, p, y, pw, n_particles=self.n, a=self.a, prior_v=pv, learn_v=learn_v, n0=self.n0, literal=literal,
                             iteration=iteration, seed=seed, series_offset=series_offset)
-        out = {k: None if v is None else np.asarray(v) for k, v in out.items()}
-        with np.errstate(invalid="ignore", over="ignore"):
-            moments = np.exp(out["psi_mean"] + out["psi_var"] / 2.0)
-        out["w_mean"], out["v_mean"] = moments[:, :, :d], moments[:, :, d]
-        return out
+        return _lognormal_means(_numpy(out), d)
 
 
 INIT_ITERATION = 0xFFFFFFFF   # the Philox iteration of Metropolis.dglm's evaluation of the initial parameters
@@ -492,31 +499,12 @@ class ParticleGibbs:
         check_pf_shape(1, 1, int(n))
         self.n, self.ancestor_sampling = int(n), bool(ancestor_sampling)
 
-    @staticmethod
-    def _inputs(mod, ys, n):
-        times, y = _observations(ys)
-        f0 = np.atleast_2d(np.asarray(mod.f(float(times[0])), dtype=np.float64))
-        check_pf_shape(f0.shape[0], f0.shape[1], n)
-        return times, y, materialise(Dlm(mod.f, mod.g), times)
-
-    @staticmethod
-    def _params(p, y):
-        """(N, y [N][T], what Engine.prepare takes) of one parameter set, one per series or a BatchedParameters"""
-        if isinstance(p, DlmParameters):
-            return y.shape[0], y, p
-        bp = BatchedParameters.of(p)
-        if y.shape[0] == 1 and bp.n > 1:
-            y = np.repeat(y, bp.n, axis=0)
-        if y.shape[0] != bp.n:
-            raise EngineError(f"{bp.n} parameter sets for {y.shape[0]} series")
-        return bp.n, y, bp.packed()
-
     def initial_path(self, mod: Dglm, ys, p, eng, *, seed: int = 0, series_offset: int = 0):
         """A path to start from, [N][T+1][d]: the FILTERING MEANS of one bootstrap-filter run with n particles (record t + 1 = the mean
         after y_t; record 0 = m0).  It is not a draw of the smoothing law -- no start has to be: the sweeps forget it geometrically fast,
         and with ancestor sampling within a few iterations."""
-        times, y, mat = self._inputs(mod, ys, self.n)
-        N, y, params = self._params(p, y)
+        times, y, d, mat = _filter_inputs(mod, ys, self.n, materialise)
+        N, y, params = _bank(p, y)
         out = eng.particle_filter(mat, params, y, family=mod.family, n_particles=self.n, obs_param=mod.nu, iteration=INIT_ITERATION, seed=seed,
                                   series_offset=series_offset, want_ess=False, want_cloud=False, want_weights=False)
         if np.any(np.asarray(out["status"]) != 0):
@@ -528,12 +516,11 @@ class ParticleGibbs:
     def sample_state(self, mod: Dglm, ys, p, ref, eng, *, seed: int = 0, iteration: int = 0, series_offset: int = 0, **want):
         """One sweep: a new path [N][T+1][d] given the path `ref`, the data and the parameters.  Returns Engine.pg_sweep's dict as NumPy
         arrays ("ll", "path", "stats", "status" and the traces asked for through want_path_index / want_trace / want_step_weights)."""
-        times, y, mat = self._inputs(mod, ys, self.n)
-        N, y, params = self._params(p, y)
-        out = eng.pg_sweep(mat, params, y, np.asarray(ref, dtype=np.float64), family=mod.family, n_particles=self.n,
-                           ancestor_sampling=self.ancestor_sampling, obs_param=mod.nu, iteration=iteration, seed=seed,
-                           series_offset=series_offset, **want)
-        return {k: None if v is None else np.asarray(v) for k, v in out.items()}
+        times, y, d, mat = _filter_inputs(mod, ys, self.n, materialise)
+        N, y, params = _bank(p, y)
+        return _numpy(eng.pg_sweep(mat, params, y, np.asarray(ref, dtype=np.float64), family=mod.family, n_particles=self.n,
+                                   ancestor_sampling=self.ancestor_sampling, obs_param=mod.nu, iteration=iteration, seed=seed,
+                                   series_offset=series_offset, **want))
 
     def sample(self, mod: Dglm, ys, prior_w, init_p, eng, n_iter: int, prior_v=None, seed: int = 0, *, init_path=None,
                series_offset: int = 0):
@@ -546,13 +533,10 @@ class ParticleGibbs:
         import torch
         if prior_v is not None and mod.family != _lib.OBS_GAUSSIAN:
             raise EngineError("prior_v applies to the Gaussian family only: no other family's V has a conjugate draw")
-        times, y, mat = self._inputs(mod, ys, self.n)
+        times, y, d, mat = _filter_inputs(mod, ys, self.n, materialise)
         bp = BatchedParameters.of(init_p, y.shape[0] if isinstance(init_p, DlmParameters) else None)
-        N, d, T = bp.n, mat.d, mat.T
-        if y.shape[0] == 1 and N > 1:
-            y = np.repeat(y, N, axis=0)
-        if y.shape[0] != N:
-            raise EngineError(f"{N} parameter sets for {y.shape[0]} series")
+        N, y, _ = _bank(bp, y)
+        T = mat.T
         path0 = self.initial_path(mod, (times, y), bp, eng, seed=seed, series_offset=series_offset) if init_path is None else init_path
         dev = torch.device("cuda", eng.device)
         put = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)

@@ -53,6 +53,45 @@ def _out_or_empty(be, out, name, shape, dtype=np.float64):
     return out[name] if out and name in out else be.empty(shape, dtype)
 
 
+# where each symbol takes a data pointer (void*), counted after the handle: the arguments Engine._call turns into addresses
+_POINTERS = {name: tuple(i for i, t in enumerate(args[1:]) if t is ctypes.c_void_p) for name, _, args in _lib.SYMBOLS}
+
+
+def _options(be, flags=0, seed=0, series_offset=0):
+    return _lib.Options(flags, be.mem, seed, series_offset)
+
+
+def _outputs(be, N, status=None, **spec):
+    """The outputs of a call in the order the call and the returned dict have them: every name=(wanted, shape[, dtype]) as a fresh
+    buffer or None, any other value (the caller's buffer, or None) as it is, and last "status" [N] (a fresh one unless given)."""
+    out = {name: (be.empty(*v[1:]) if v[0] else None) if isinstance(v, tuple) else v for name, v in spec.items()}
+    out["status"] = be.empty((N,), np.int32) if status is None else status
+    return out
+
+
+def _model_desc(be, mat, N, *, F=None, f_stride=0, G=None, n_g=0, g_index=None, dt=None):
+    """A ModelDesc of mat's shape that points at the given tables only (the others NULL) -> (descriptor, the arrays it points into:
+    what the call has to keep alive)."""
+    bufs = (be.put(F), be.put(G), be.put(g_index, np.int32), be.put(dt))
+    Fp, Gp, gip, dtp = (None if b is None else be.ptr(b).value for b in bufs)
+    return _lib.ModelDesc(mat.d, mat.p, mat.T, N, Fp, f_stride, Gp, n_g, gip, dtp), bufs
+
+
+def _strided(a, k, scalar=False):
+    """[k] shared by the series or [N][k], a NumPy array or a device tensor (with scalar=True also one number for all k) -> (the array,
+    its stride in doubles: 0 = shared)."""
+    a = a if hasattr(a, "data_ptr") else np.asarray(a, dtype=np.float64)
+    if scalar and np.ndim(a) == 0:
+        a = np.full(k, float(a))
+    return a, k if a.ndim == 2 else 0
+
+
+def check_shrinkage(a, error=None):
+    """The shrinkage of the Liu-West family, 0 < a <= 1 (NaN refused); raises `error` (default: EngineError)."""
+    if not 0.0 < float(a) <= 1.0:
+        raise (error or EngineError)(f"the shrinkage a must satisfy 0 < a <= 1, got {a!r}")
+
+
 def _counter(be, accepted, shape):
     """The caller's int32 acceptance counter (incremented in place), or a fresh one of zeros."""
     acc = be.put(np.zeros(shape, np.int32) if accepted is None else accepted, np.int32)
@@ -125,15 +164,6 @@ def _pf_priors(be, prior_w, prior_v, learn_v, N, d):
         if pv.shape not in ((2,), (N, 2)):
             raise EngineError(f"prior_v must be [2] or [N][2], got {pv.shape}")
     return be.put(pv), 2 if learn_v and pv.ndim == 2 else 0, be.put(pw), 2 * d if pw.ndim == 3 else 0
-
-
-def _pf_outputs(be, N, **optional):
-    """The outputs of a particle-filter call in the order the call and the returned dict have them: "ll" [N], every optional
-    name=(wanted, shape) as a fresh buffer or None, "status" [N]."""
-    out = {"ll": be.empty((N,))}
-    out.update((name, be.empty(shape) if wanted else None) for name, (wanted, shape) in optional.items())
-    out["status"] = be.empty((N,), np.int32)
-    return out
 
 
 class _Host:
@@ -242,6 +272,17 @@ class Engine:
         if flags & _lib.OPT_ASYNC:
             self._keep.append(objs)
 
+    def _call(self, name, be, flags, *args, keep=()):
+        """The C call `name`(handle, *args), its return code checked.  args in the C order: where the symbol takes a data pointer an
+        array of the backend crosses as its address and None as NULL; numbers cross as they are, and so do ctypes structures (the
+        declared argtypes pass them by reference).  This is also the one place that keeps what the kernels may still read alive
+        under DLM_OPT_ASYNC: every argument, and `keep` (the arrays behind a descriptor's pointers)."""
+        self._hold(flags, args, keep)
+        cargs, ptr = list(args), be.ptr
+        for i in _POINTERS[name]:
+            cargs[i] = ptr(cargs[i])
+        self._check(getattr(self.lib, name)(self.h, *cargs))
+
     # -- engine-owned device buffers (what a caller without torch uses; also exercised by the tests) ----------------
     def buffer_alloc(self, nbytes: int) -> int:
         p = ctypes.c_void_p()
@@ -314,16 +355,15 @@ class Engine:
             md = _lib.ModelDesc(mat.d, mat.p, mat.T, N, P("F"), mat.f_stride, P("G"), mat.n_g, P("gi"), P("dt"))
             pd = _lib.ParamsDesc(P("V"), vs, P("W"), ws, P("m0"), m0s, P("C0"), c0s, vts, wts)
             self._hold(flags, bufs)
-            return md, pd, _lib.Options(oflags, be.mem, seed, series_offset), bufs
+            return md, pd, _options(be, oflags, seed, series_offset), bufs
         self._staged = None
         bufs = {name: be.put(a, dt) for name, (a, dt) in items.items()}
         P = lambda a: (be.ptr(a).value if a is not None else None)
         md = _lib.ModelDesc(mat.d, mat.p, mat.T, N, P(bufs["F"]), mat.f_stride, P(bufs["G"]), mat.n_g,
                             P(bufs["gi"]), P(bufs["dt"]))
         pd = _lib.ParamsDesc(P(bufs["V"]), vs, P(bufs["W"]), ws, P(bufs["m0"]), m0s, P(bufs["C0"]), c0s, vts, wts)
-        op = _lib.Options(flags, be.mem, seed, series_offset)
         self._hold(flags, bufs)
-        return md, pd, op, bufs
+        return md, pd, _options(be, flags, seed, series_offset), bufs
 
     # -- entry points --------------------------------------------------------------
     def filter(self, mat, params, y, *, want_prior=False, want_fq=False, flags=0, out=None):
@@ -333,14 +373,10 @@ class Engine:
         rec = d + d * d
         yb = be.put(y).reshape(N, T, p)
         md, pd, op, keep = self.prepare(mat, params, N, be, flags)
-        self._hold(flags, yb)
         filt = out if out is not None else be.empty((N, T + 1, self.lib.dlm_packed_record_doubles(d) if flags & _lib.OPT_PACKED_SYM else rec))
-        prior = be.empty((N, T + 1, rec)) if want_prior else None
-        fq = be.empty((N, T + 1, p + p * p)) if want_fq else None
-        status = be.empty((N,), np.int32)
-        self._check(self.lib.dlm_filter_batch(self.h, md, pd, be.ptr(yb), op, be.ptr(filt), be.ptr(prior),
-                                              be.ptr(fq), be.ptr(status)))
-        return {"filt": filt, "prior": prior, "fq": fq, "status": status}
+        out = _outputs(be, N, filt=filt, prior=(want_prior, (N, T + 1, rec)), fq=(want_fq, (N, T + 1, p + p * p)))
+        self._call("dlm_filter_batch", be, flags, md, pd, yb, op, *out.values())
+        return out
 
     def loglik(self, mat, params, y, *, flags=0):
         """Per-series prediction-error log-likelihood (dlm_loglik_batch); nothing but [N] numbers leaves the GPU."""
@@ -348,10 +384,9 @@ class Engine:
         N = int(y.shape[0]); p, T = mat.p, mat.T
         yb = be.put(y).reshape(N, T, p)
         md, pd, op, keep = self.prepare(mat, params, N, be, flags)
-        ll = be.empty((N,))
-        status = be.empty((N,), np.int32)
-        self._check(self.lib.dlm_loglik_batch(self.h, md, pd, be.ptr(yb), op, be.ptr(ll), be.ptr(status)))
-        return {"loglik": ll, "status": status}
+        out = _outputs(be, N, loglik=(True, (N,)))
+        self._call("dlm_loglik_batch", be, flags, md, pd, yb, op, *out.values())
+        return out
 
     def ar1_ffbs(self, y, v, sv, *, z=None, seed=0, series_offset=0, want_filt=True, want_theta=True, times=None):
         """Scalar AR(1) FFBS, one lane per series (dlm_ar1_ffbs_batch; FilterAr.scala:15-82).  y [N][T] (NaN = missing),
@@ -360,25 +395,13 @@ class Engine:
         be = self._backend(y)
         N, T = int(y.shape[0]), int(y.shape[1])
         yb = be.put(y).reshape(N, T)
-        vv = np.asarray(v, dtype=np.float64) if not hasattr(v, "data_ptr") else v
-        if np.ndim(vv) == 0:
-            vv = np.full(T, float(vv))
-        v_stride = T if vv.ndim == 2 else 0
-        svv = np.asarray(sv, dtype=np.float64) if not hasattr(sv, "data_ptr") else sv
-        sv_stride = 3 if svv.ndim == 2 else 0
+        vv, v_stride = _strided(v, T, scalar=True)
+        svv, sv_stride = _strided(sv, 3)
         vb, sb, zb = be.put(vv), be.put(svv), be.put(z)
-        filt = be.empty((N, T + 1, 2)) if want_filt else None
-        theta = be.empty((N, T + 1)) if want_theta else None
-        status = be.empty((N,), np.int32)
-        op = _lib.Options(0, be.mem, seed, series_offset)
-        if times is None:
-            self._check(self.lib.dlm_ar1_ffbs_batch(self.h, N, T, be.ptr(yb), be.ptr(vb), v_stride, be.ptr(sb), sv_stride,
-                                                    be.ptr(zb), op, be.ptr(filt), be.ptr(theta), be.ptr(status)))
-        else:
-            tb = be.put(times)   # (a device tensor stays where it is)
-            self._check(self.lib.dlm_ou_ffbs_batch(self.h, N, T, be.ptr(tb), be.ptr(yb), be.ptr(vb), v_stride, be.ptr(sb),
-                                                   sv_stride, be.ptr(zb), op, be.ptr(filt), be.ptr(theta), be.ptr(status)))
-        return {"filt": filt, "theta": theta, "status": status}
+        out = _outputs(be, N, filt=(want_filt, (N, T + 1, 2)), theta=(want_theta, (N, T + 1)))
+        name, grid = ("dlm_ar1_ffbs_batch", ()) if times is None else ("dlm_ou_ffbs_batch", (be.put(times),))   # (a device tensor stays where it is)
+        self._call(name, be, 0, N, T, *grid, yb, vb, v_stride, sb, sv_stride, zb, _options(be, 0, seed, series_offset), *out.values())
+        return out
 
     def dinvgamma_step(self, d, p, stats, prior_v, prior_w, *, iteration, seed=0, series_offset=0):
         """GibbsSampling.dinvGammaStep on the device (dlm_dinvgamma_step_batch): stats [N][2p + d + 1] from an FFBS call
@@ -390,9 +413,8 @@ class Engine:
         av, bv = (prior_v.shape, prior_v.scale) if hasattr(prior_v, "scale") else prior_v
         aw, bw = (prior_w.shape, prior_w.scale) if hasattr(prior_w, "scale") else prior_w
         V = be.empty((N, p * p)); W = be.empty((N, d * d))
-        op = _lib.Options(0, be.mem, seed, series_offset)
-        self._check(self.lib.dlm_dinvgamma_step_batch(self.h, d, p, N, be.ptr(sb), float(av), float(bv), float(aw), float(bw),
-                                                      int(iteration), op, be.ptr(V), be.ptr(W)))
+        self._call("dlm_dinvgamma_step_batch", be, 0, int(d), int(p), N, sb, float(av), float(bv), float(aw), float(bw), int(iteration),
+                   _options(be, 0, seed, series_offset), V, W)
         return V, W
 
     def studentt_step(self, mat, y, theta, stats, prior, scale, nu, *, iteration, accepted=None, seed=0, series_offset=0,
@@ -410,22 +432,14 @@ class Engine:
         yb = be.put(y).reshape(N, T)
         tb, sb = be.put(theta), be.put(stats)
         scb, nub = be.put(scale), be.put(nu, np.int32)
-        Fb = be.put(mat.F)
-        v = _out_or_empty(be, out, "v", (N, T))
-        sc_out = _out_or_empty(be, out, "scale", (N,))
-        nu_out = _out_or_empty(be, out, "nu", (N,), np.int32)
-        W = _out_or_empty(be, out, "W", (N, d * d))
-        acc = _counter(be, accepted, (N,))
-        ll = be.empty((N,)) if want_loglik else None
-        status = be.empty((N,), np.int32)
-        md = _lib.ModelDesc(d, mat.p, T, N, be.ptr(Fb).value, mat.f_stride, None, mat.n_g, None, None)
-        pr = _as_prior(_lib.StudentTPrior, prior)
-        op = _lib.Options(flags | (_lib.OPT_STUDENTT_LITERAL if literal else 0), be.mem, seed, series_offset)
-        self._hold(flags, yb, tb, sb, scb, nub, Fb)
-        self._check(self.lib.dlm_studentt_step_batch(self.h, md, be.ptr(yb), be.ptr(tb), be.ptr(sb), pr, be.ptr(scb),
-                                                     be.ptr(nub), int(iteration), op, be.ptr(v), be.ptr(sc_out), be.ptr(nu_out),
-                                                     be.ptr(W), be.ptr(acc), be.ptr(ll), be.ptr(status)))
-        return {"v": v, "scale": sc_out, "nu": nu_out, "W": W, "accepted": acc, "loglik": ll, "status": status}
+        md, tables = _model_desc(be, mat, N, F=mat.F, f_stride=mat.f_stride, n_g=mat.n_g)
+        res = _outputs(be, N, v=_out_or_empty(be, out, "v", (N, T)), scale=_out_or_empty(be, out, "scale", (N,)),
+                       nu=_out_or_empty(be, out, "nu", (N,), np.int32), W=_out_or_empty(be, out, "W", (N, d * d)),
+                       accepted=_counter(be, accepted, (N,)), loglik=(want_loglik, (N,)))
+        op = _options(be, flags | (_lib.OPT_STUDENTT_LITERAL if literal else 0), seed, series_offset)
+        self._call("dlm_studentt_step_batch", be, flags, md, yb, tb, sb, _as_prior(_lib.StudentTPrior, prior), scb, nub, int(iteration), op,
+                   *res.values(), keep=tables)
+        return res
 
     def sv_mixture(self, y, alpha, *, iteration, seed=0, series_offset=0, want_k=False, flags=0, out=None):
         """The mixture indicators of the stochastic-volatility sampler (dlm_sv_mixture_batch; StochasticVolatility.sampleKt,
@@ -439,15 +453,10 @@ class Engine:
         ab = be.put(alpha)
         if ab is not None and tuple(ab.shape) != (N, T + 1):
             raise EngineError(f"alpha must be [N][T+1] = {(N, T + 1)}, got {tuple(ab.shape)}")
-        ystar = _out_or_empty(be, out, "ystar", (N, T))
-        v = _out_or_empty(be, out, "v", (N, T))
-        k = _out_or_empty(be, out, "k", (N, T), np.int8) if want_k and ab is not None else None
-        status = be.empty((N,), np.int32)
-        op = _lib.Options(flags, be.mem, seed, series_offset)
-        self._hold(flags, yb, ab)
-        self._check(self.lib.dlm_sv_mixture_batch(self.h, N, T, be.ptr(yb), be.ptr(ab), int(iteration), op, be.ptr(ystar), be.ptr(v),
-                                                  be.ptr(k), be.ptr(status)))
-        return {"ystar": ystar, "v": v, "k": k, "status": status}
+        res = _outputs(be, N, ystar=_out_or_empty(be, out, "ystar", (N, T)), v=_out_or_empty(be, out, "v", (N, T)),
+                       k=_out_or_empty(be, out, "k", (N, T), np.int8) if want_k and ab is not None else None)
+        self._call("dlm_sv_mixture_batch", be, flags, N, T, yb, ab, int(iteration), _options(be, flags, seed, series_offset), *res.values())
+        return res
 
     def sv_params(self, alpha, sv, prior, *, iteration, accepted=None, seed=0, series_offset=0, flags=0, out=None):
         """phi, mu, sigma of the stochastic-volatility sampler given the state draw (dlm_sv_params_batch; samplePhiConjugate or
@@ -478,14 +487,10 @@ class Engine:
         if tuple(sb.shape) != (N, 3):
             raise EngineError(f"sv must be [N][3] = {(N, 3)}, got {tuple(sb.shape)}")
         pr = _as_prior(_lib.SvOuPrior if ou else _lib.SvPrior, prior)
-        sv_out = _out_or_empty(be, out, "sv", (N, 3))
-        acc = _counter(be, accepted, (N, 3) if ou else (N,))
-        status = be.empty((N,), np.int32)
-        op = _lib.Options(flags, be.mem, seed, series_offset)
-        self._hold(flags, tb, ab, sb)
-        call, grid = (self.lib.dlm_sv_ou_params_batch, (be.ptr(tb),)) if ou else (self.lib.dlm_sv_params_batch, ())
-        self._check(call(self.h, N, T, *grid, be.ptr(ab), be.ptr(sb), pr, int(iteration), op, be.ptr(sv_out), be.ptr(acc), be.ptr(status)))
-        return {"sv": sv_out, "accepted": acc, "status": status}
+        res = _outputs(be, N, sv=_out_or_empty(be, out, "sv", (N, 3)), accepted=_counter(be, accepted, (N, 3) if ou else (N,)))
+        name, grid = ("dlm_sv_ou_params_batch", (tb,)) if ou else ("dlm_sv_params_batch", ())
+        self._call(name, be, flags, N, T, *grid, ab, sb, pr, int(iteration), _options(be, flags, seed, series_offset), *res.values())
+        return res
 
     def sv_knots(self, y, alpha, sv, knots, *, iteration, accepted=None, seed=0, series_offset=0, out=None):
         """One sweep of the knot block sampler over the log-volatility paths of N chains (dlm_sv_knots_batch;
@@ -502,10 +507,9 @@ class Engine:
         ab = be.put(alpha)
         if tuple(ab.shape) != (N, T + 1):
             raise EngineError(f"alpha must be [N][T+1] = {(N, T + 1)}, got {tuple(ab.shape)}")
-        svv = np.asarray(sv, dtype=np.float64) if not hasattr(sv, "data_ptr") else sv
+        svv, sv_stride = _strided(sv, 3)
         if tuple(svv.shape) not in ((3,), (N, 3)):
             raise EngineError(f"sv must be [3] or [N][3] = {(N, 3)}, got {tuple(svv.shape)}")
-        sv_stride = 3 if svv.ndim == 2 else 0
         sb, kb = be.put(svv), be.put(knots, np.int32)
         if kb.ndim != 1 or int(kb.shape[0]) < 2:
             raise EngineError(f"knots must be [B+1] with B >= 1, got the shape {tuple(kb.shape)}")
@@ -518,12 +522,10 @@ class Engine:
             else:
                 new.copy_(ab)
                 be = self._backend(y)   # (the copy ran on torch's stream: the engine's waits for it)
-        acc = _counter(be, accepted, (N,))
-        status = be.empty((N,), np.int32)
-        op = _lib.Options(0, be.mem, seed, series_offset)
-        self._check(self.lib.dlm_sv_knots_batch(self.h, N, T, be.ptr(yb), be.ptr(kb), int(kb.shape[0]) - 1, be.ptr(sb), sv_stride,
-                                                int(iteration), op, be.ptr(new), be.ptr(acc), be.ptr(status)))
-        return {"alpha": new, "accepted": acc, "status": status}
+        res = _outputs(be, N, alpha=new, accepted=_counter(be, accepted, (N,)))
+        self._call("dlm_sv_knots_batch", be, 0, N, T, yb, kb, int(kb.shape[0]) - 1, sb, sv_stride, int(iteration),
+                   _options(be, 0, seed, series_offset), *res.values())
+        return res
 
     def fsv_factors(self, y, beta, v, alpha, *, iteration, seed=0, series_offset=0, literal=False, flags=0, out=None):
         """The factor draw of the factor stochastic-volatility sampler (dlm_fsv_factors_batch; FactorSv.sampleFactors,
@@ -540,13 +542,10 @@ class Engine:
             raise EngineError(f"beta must be [N][p][k] = {(N, p, k)} and v [N][p] = {(N, p)}, got {tuple(bb.shape)} and {tuple(vb.shape)}")
         if ab is not None and tuple(ab.shape) != (N, k, T + 1):
             raise EngineError(f"alpha must be [N][k][T+1] = {(N, k, T + 1)}, got {tuple(ab.shape)}")
-        f = _out_or_empty(be, out, "f", (N, k, T))
-        status = be.empty((N,), np.int32)
-        op = _lib.Options(flags, be.mem, seed, series_offset)
-        self._hold(flags, yb, bb, vb, ab)
-        self._check(self.lib.dlm_fsv_factors_batch(self.h, N, T, p, k, be.ptr(yb), be.ptr(bb), be.ptr(vb), be.ptr(ab), 1 if literal else 0,
-                                                   int(iteration), op, be.ptr(f), be.ptr(status)))
-        return {"f": f, "status": status}
+        res = _outputs(be, N, f=_out_or_empty(be, out, "f", (N, k, T)))
+        self._call("dlm_fsv_factors_batch", be, flags, N, T, p, k, yb, bb, vb, ab, 1 if literal else 0, int(iteration),
+                   _options(be, flags, seed, series_offset), *res.values())
+        return res
 
     def fsv_loadings(self, y, f, beta, prior, *, iteration, seed=0, series_offset=0, v=None, flags=0, out=None):
         """sigma^2 and the loading matrix of the factor stochastic-volatility sampler given the factors (dlm_fsv_loadings_batch;
@@ -564,14 +563,10 @@ class Engine:
         if vb is not None and tuple(vb.shape) != (N, p):
             raise EngineError(f"v must be [N][p] = {(N, p)}, got {tuple(vb.shape)}")
         pr = _as_prior(_lib.FsvPrior, prior)
-        beta_out = _out_or_empty(be, out, "beta", (N, p, k))
-        v_out = _out_or_empty(be, out, "v", (N, p))
-        status = be.empty((N,), np.int32)
-        op = _lib.Options(flags, be.mem, seed, series_offset)
-        self._hold(flags, yb, fb, bb, vb)
-        self._check(self.lib.dlm_fsv_loadings_batch(self.h, N, T, p, k, be.ptr(yb), be.ptr(fb), be.ptr(bb), be.ptr(vb), pr, int(iteration),
-                                                    op, be.ptr(beta_out), be.ptr(v_out), be.ptr(status)))
-        return {"beta": beta_out, "v": v_out, "status": status}
+        res = _outputs(be, N, beta=_out_or_empty(be, out, "beta", (N, p, k)), v=_out_or_empty(be, out, "v", (N, p)))
+        self._call("dlm_fsv_loadings_batch", be, flags, N, T, p, k, yb, fb, bb, vb, pr, int(iteration),
+                   _options(be, flags, seed, series_offset), *res.values())
+        return res
 
     def dlmfsv_center(self, mat, y, theta, *, flags=0, out=None):
         """The panel centred on the DLM's mean (dlm_dlmfsv_center_batch; factorObs, DlmFsv.scala:173-185) for N panels:
@@ -582,14 +577,10 @@ class Engine:
         yb, tb = be.put(y), be.put(theta)
         if tuple(yb.shape) != (N, T, p) or tuple(tb.shape) != (N, T + 1, d):
             raise EngineError(f"y must be [N][T][p] = {(N, T, p)} and theta [N][T+1][d] = {(N, T + 1, d)}, got {tuple(yb.shape)} and {tuple(tb.shape)}")
-        Fb = be.put(mat.F)
-        md = _lib.ModelDesc(d, p, T, N, be.ptr(Fb).value, mat.f_stride, None, 0, None, None)
-        r = _out_or_empty(be, out, "r", (N, T, p))
-        status = be.empty((N,), np.int32)
-        op = _lib.Options(flags, be.mem, 0, 0)
-        self._hold(flags, yb, tb, Fb)
-        self._check(self.lib.dlm_dlmfsv_center_batch(self.h, md, be.ptr(yb), be.ptr(tb), op, be.ptr(r), be.ptr(status)))
-        return {"r": r, "status": status}
+        md, tables = _model_desc(be, mat, N, F=mat.F, f_stride=mat.f_stride)
+        res = _outputs(be, N, r=_out_or_empty(be, out, "r", (N, T, p)))
+        self._call("dlm_dlmfsv_center_batch", be, flags, md, yb, tb, _options(be, flags), *res.values(), keep=tables)
+        return res
 
     def dlmfsv_impute(self, r, beta, v, alpha, *, iteration, seed=0, series_offset=0, flags=0, out=None):
         """The missing components of the partially missing times of a centred panel, drawn given the observed ones
@@ -604,13 +595,10 @@ class Engine:
         if tuple(bb.shape) != (N, p, k) or tuple(vb.shape) != (N, p) or tuple(ab.shape) != (N, k, T + 1):
             raise EngineError(f"beta must be [N][p][k] = {(N, p, k)}, v [N][p] = {(N, p)} and alpha [N][k][T+1] = {(N, k, T + 1)}, got "
                               f"{tuple(bb.shape)}, {tuple(vb.shape)} and {tuple(ab.shape)}")
-        ro = _out_or_empty(be, out, "r", (N, T, p))
-        status = be.empty((N,), np.int32)
-        op = _lib.Options(flags, be.mem, seed, series_offset)
-        self._hold(flags, rb, bb, vb, ab)
-        self._check(self.lib.dlm_dlmfsv_impute_batch(self.h, N, T, p, k, be.ptr(rb), be.ptr(bb), be.ptr(vb), be.ptr(ab), int(iteration), op,
-                                                     be.ptr(ro), be.ptr(status)))
-        return {"r": ro, "status": status}
+        res = _outputs(be, N, r=_out_or_empty(be, out, "r", (N, T, p)))
+        self._call("dlm_dlmfsv_impute_batch", be, flags, N, T, p, k, rb, bb, vb, ab, int(iteration), _options(be, flags, seed, series_offset),
+                   *res.values())
+        return res
 
     def dlmfsv_variance(self, beta, v, alpha, *, flags=0, out=None):
         """The observation-variance stream of the DLM with factor stochastic-volatility noise (dlm_dlmfsv_variance_batch;
@@ -624,12 +612,9 @@ class Engine:
         bb, vb, ab = be.put(beta), be.put(v), be.put(alpha)
         if tuple(vb.shape) != (N, p) or tuple(ab.shape) != (N, k, T + 1):
             raise EngineError(f"v must be [N][p] = {(N, p)} and alpha [N][k][T+1] = {(N, k, T + 1)}, got {tuple(vb.shape)} and {tuple(ab.shape)}")
-        V = _out_or_empty(be, out, "V", (N, T, p * p))
-        status = be.empty((N,), np.int32)
-        op = _lib.Options(flags, be.mem, 0, 0)
-        self._hold(flags, bb, vb, ab)
-        self._check(self.lib.dlm_dlmfsv_variance_batch(self.h, N, T, p, k, be.ptr(bb), be.ptr(vb), be.ptr(ab), op, be.ptr(V), be.ptr(status)))
-        return {"V": V, "status": status}
+        res = _outputs(be, N, V=_out_or_empty(be, out, "V", (N, T, p * p)))
+        self._call("dlm_dlmfsv_variance_batch", be, flags, N, T, p, k, bb, vb, ab, _options(be, flags), *res.values())
+        return res
 
     def dlmfsvsys_innovations(self, mat, theta, *, flags=0, out=None):
         """The state's innovations (dlm_dlmfsvsys_innovations_batch; factorState, DlmFsvSystem.scala:109-117) for N panels:
@@ -640,15 +625,10 @@ class Engine:
         tb = be.put(theta)
         if tuple(tb.shape) != (N, T + 1, d):
             raise EngineError(f"theta must be [N][T+1][d] = {(N, T + 1, d)}, got {tuple(tb.shape)}")
-        Gb, gi, dt = be.put(mat.G), be.put(mat.g_index, np.int32), be.put(mat.dt)
-        addr = lambda a: None if a is None else be.ptr(a).value
-        md = _lib.ModelDesc(d, mat.p, T, N, None, 0, addr(Gb), mat.n_g, addr(gi), addr(dt))
-        w = _out_or_empty(be, out, "w", (N, T, d))
-        status = be.empty((N,), np.int32)
-        op = _lib.Options(flags, be.mem, 0, 0)
-        self._hold(flags, tb, Gb, gi, dt)
-        self._check(self.lib.dlm_dlmfsvsys_innovations_batch(self.h, md, be.ptr(tb), op, be.ptr(w), be.ptr(status)))
-        return {"w": w, "status": status}
+        md, tables = _model_desc(be, mat, N, G=mat.G, n_g=mat.n_g, g_index=mat.g_index, dt=mat.dt)
+        res = _outputs(be, N, w=_out_or_empty(be, out, "w", (N, T, d)))
+        self._call("dlm_dlmfsvsys_innovations_batch", be, flags, md, tb, _options(be, flags), *res.values(), keep=tables)
+        return res
 
     def particle_filter(self, mat, params, y, *, family, n_particles, n0=-1, literal=False, obs_param=None, iteration=0, seed=0,
                         series_offset=0, flags=0, want_mean=True, want_ess=True, want_cloud=True, want_weights=True):
@@ -664,12 +644,10 @@ class Engine:
         md, pd, op, keep = self.prepare(mat, params, N, be, flags, seed, series_offset)
         if pd.v_tstride or pd.w_tstride:
             raise EngineError("the particle filter takes time-invariant V and W")
-        out = _pf_outputs(be, N, mean=(want_mean, (N, T, d)), ess=(want_ess, (N, T)), cloud=(want_cloud, (N, d, P)),
-                          weights=(want_weights, (N, P)))
+        out = _outputs(be, N, ll=(True, (N,)), mean=(want_mean, (N, T, d)), ess=(want_ess, (N, T)), cloud=(want_cloud, (N, d, P)),
+                       weights=(want_weights, (N, P)))
         desc = _lib.PfDesc(int(family), P, int(n0), 1 if literal else 0)
-        self._hold(flags, yb, ob)
-        self._check(self.lib.dlm_pf_batch(self.h, md, pd, ctypes.byref(desc), be.ptr(ob), be.ptr(yb), int(iteration), op,
-                                          *(be.ptr(v) for v in out.values())))
+        self._call("dlm_pf_batch", be, flags, md, pd, desc, ob, yb, int(iteration), op, *out.values())
         return out
 
     def storvik_filter(self, mat, params, y, prior_w, *, family, n_particles, prior_v=None, learn_v=None, n0=-1, literal=False,
@@ -694,12 +672,10 @@ class Engine:
         md, pd, op, keep = self.prepare(mat, params, N, be, flags, seed, series_offset)
         if pd.v_tstride and not learn_v:
             raise EngineError("the Storvik filter takes a time-invariant V")
-        out = _pf_outputs(be, N, mean=(want_mean, (N, T, d)), ess=(want_ess, (N, T)), scale_mean=(want_scale_mean, (N, T, d + 1)),
-                          cloud=(want_cloud, (N, d, P)), weights=(want_weights, (N, P)), scales=(want_scales, (N, d + 1, P)))
+        out = _outputs(be, N, ll=(True, (N,)), mean=(want_mean, (N, T, d)), ess=(want_ess, (N, T)), scale_mean=(want_scale_mean, (N, T, d + 1)),
+                       cloud=(want_cloud, (N, d, P)), weights=(want_weights, (N, P)), scales=(want_scales, (N, d + 1, P)))
         desc = _lib.StorvikDesc(int(family), P, int(n0), 1 if literal else 0, 1 if learn_v else 0)
-        self._hold(flags, yb, ob, pwb, pvb)
-        self._check(self.lib.dlm_storvik_batch(self.h, md, pd, ctypes.byref(desc), be.ptr(pvb), pv_stride, be.ptr(pwb), pw_stride, be.ptr(ob),
-                                               be.ptr(yb), int(iteration), op, *(be.ptr(v) for v in out.values())))
+        self._call("dlm_storvik_batch", be, flags, md, pd, desc, pvb, pv_stride, pwb, pw_stride, ob, yb, int(iteration), op, *out.values())
         return out
 
     def lw_filter(self, mat, params, y, prior_w, *, family, n_particles, a, prior_v=None, learn_v=None, n0=-1, literal=False,
@@ -721,20 +697,17 @@ class Engine:
             raise EngineError("learn_v needs OBS_GAUSSIAN, OBS_STUDENTT or OBS_BETA: the families whose v is a positive scale")
         if learn_v and prior_v is None:
             raise EngineError("learn_v needs prior_v = (mean, sd) of log V")
-        if not 0.0 < float(a) <= 1.0:
-            raise EngineError(f"the shrinkage a must satisfy 0 < a <= 1, got {a!r}")
+        check_shrinkage(a)
         N, yb, ob = _pf_data(be, y, T, family, obs_param)
         pvb, pv_stride, pwb, pw_stride = _pf_priors(be, prior_w, prior_v, learn_v, N, d)
         md, pd, op, keep = self.prepare(mat, params, N, be, flags, seed, series_offset)
         if pd.v_tstride and not learn_v:
             raise EngineError("the Liu-West filter takes a time-invariant V")
-        out = _pf_outputs(be, N, mean=(want_mean, (N, T, d)), ess=(want_ess, (N, T)), psi_mean=(want_psi_mean, (N, T, d + 1)),
-                          psi_var=(want_psi_var, (N, T, d + 1)), cloud=(want_cloud, (N, d, P)), weights=(want_weights, (N, P)),
-                          psi=(want_psi, (N, d + 1, P)))
+        out = _outputs(be, N, ll=(True, (N,)), mean=(want_mean, (N, T, d)), ess=(want_ess, (N, T)), psi_mean=(want_psi_mean, (N, T, d + 1)),
+                       psi_var=(want_psi_var, (N, T, d + 1)), cloud=(want_cloud, (N, d, P)), weights=(want_weights, (N, P)),
+                       psi=(want_psi, (N, d + 1, P)))
         desc = _lib.LwDesc(int(family), P, int(n0), 1 if literal else 0, 1 if learn_v else 0, float(a))
-        self._hold(flags, yb, ob, pwb, pvb)
-        self._check(self.lib.dlm_lw_batch(self.h, md, pd, ctypes.byref(desc), be.ptr(pvb), pv_stride, be.ptr(pwb), pw_stride, be.ptr(ob),
-                                          be.ptr(yb), int(iteration), op, *(be.ptr(v) for v in out.values())))
+        self._call("dlm_lw_batch", be, flags, md, pd, desc, pvb, pv_stride, pwb, pw_stride, ob, yb, int(iteration), op, *out.values())
         return out
 
     def rb_filter(self, mat, params, y, prior_w, *, n_particles, a, prior_v=None, learn_v=True, n0=-1, literal=False, iteration=0, seed=0,
@@ -753,20 +726,17 @@ class Engine:
         learn_v = bool(learn_v)
         if learn_v and prior_v is None:
             raise EngineError("learn_v needs prior_v = (mean, sd) of log V")
-        if not 0.0 < float(a) <= 1.0:
-            raise EngineError(f"the shrinkage a must satisfy 0 < a <= 1, got {a!r}")
+        check_shrinkage(a)
         N, yb, _ = _pf_data(be, y, T, _lib.OBS_GAUSSIAN, None)
         pvb, pv_stride, pwb, pw_stride = _pf_priors(be, prior_w, prior_v, learn_v, N, d)
         md, pd, op, keep = self.prepare(mat, params, N, be, flags, seed, series_offset)
         if pd.v_tstride and not learn_v:
             raise EngineError("the Rao-Blackwellised filter takes a time-invariant V")
-        out = _pf_outputs(be, N, mean=(want_mean, (N, T, d)), cov=(want_cov, (N, T, d, d)), ess=(want_ess, (N, T)),
-                          psi_mean=(want_psi_mean, (N, T, d + 1)), psi_var=(want_psi_var, (N, T, d + 1)), means=(want_means, (N, d, P)),
-                          covs=(want_covs, (N, d * (d + 1) // 2, P)), weights=(want_weights, (N, P)), psi=(want_psi, (N, d + 1, P)))
+        out = _outputs(be, N, ll=(True, (N,)), mean=(want_mean, (N, T, d)), cov=(want_cov, (N, T, d, d)), ess=(want_ess, (N, T)),
+                       psi_mean=(want_psi_mean, (N, T, d + 1)), psi_var=(want_psi_var, (N, T, d + 1)), means=(want_means, (N, d, P)),
+                       covs=(want_covs, (N, d * (d + 1) // 2, P)), weights=(want_weights, (N, P)), psi=(want_psi, (N, d + 1, P)))
         desc = _lib.RbDesc(P, int(n0), 1 if literal else 0, 1 if learn_v else 0, float(a))
-        self._hold(flags, yb, pwb, pvb)
-        self._check(self.lib.dlm_rb_batch(self.h, md, pd, ctypes.byref(desc), be.ptr(pvb), pv_stride, be.ptr(pwb), pw_stride, be.ptr(yb),
-                                          int(iteration), op, *(be.ptr(v) for v in out.values())))
+        self._call("dlm_rb_batch", be, flags, md, pd, desc, pvb, pv_stride, pwb, pw_stride, yb, int(iteration), op, *out.values())
         return out
 
     def pg_sweep(self, mat, params, y, ref, *, family, n_particles, ancestor_sampling=True, obs_param=None, iteration=0, seed=0,
@@ -789,16 +759,11 @@ class Engine:
         md, pd, op, keep = self.prepare(mat, params, N, be, flags, seed, series_offset)
         if pd.v_tstride or pd.w_tstride:
             raise EngineError("particle Gibbs takes time-invariant V and W")
-        out = {"ll": be.empty((N,)), "path": rb if in_place else be.empty((N, T + 1, d)), "stats": be.empty((N, d + 3)),
-               "path_index": be.empty((N, T + 1), np.int32) if want_path_index else None,
-               "clouds": be.empty((N, T + 1, d, P)) if want_trace else None,
-               "ancestors": be.empty((N, T, P), np.int32) if want_trace else None,
-               "step_weights": be.empty((N, T, P)) if want_step_weights else None,
-               "status": be.empty((N,), np.int32)}
+        out = _outputs(be, N, ll=(True, (N,)), path=rb if in_place else be.empty((N, T + 1, d)), stats=(True, (N, d + 3)),
+                       path_index=(want_path_index, (N, T + 1), np.int32), clouds=(want_trace, (N, T + 1, d, P)),
+                       ancestors=(want_trace, (N, T, P), np.int32), step_weights=(want_step_weights, (N, T, P)))
         desc = _lib.PgDesc(int(family), P, 1 if ancestor_sampling else 0, int(workspace_cap))
-        self._hold(flags, yb, ob, rb)
-        self._check(self.lib.dlm_pg_batch(self.h, md, pd, ctypes.byref(desc), be.ptr(ob), be.ptr(yb), be.ptr(rb), int(iteration), op,
-                                          *(be.ptr(v) for v in out.values())))
+        self._call("dlm_pg_batch", be, flags, md, pd, desc, ob, yb, rb, int(iteration), op, *out.values())
         return out
 
     def simulate(self, mat, params, N, *, seed=0, series_offset=0, device=False, want_x=True):
@@ -806,21 +771,18 @@ class Engine:
         be = _Device(self.device) if device else _Host()
         d, p, T = mat.d, mat.p, mat.T
         md, pd, op, keep = self.prepare(mat, params, N, be, 0, seed, series_offset)
-        x = be.empty((N, T + 1, d)) if want_x else None
-        y = be.empty((N, T, p))
-        status = be.empty((N,), np.int32)
-        self._check(self.lib.dlm_simulate_batch(self.h, md, pd, op, be.ptr(x), be.ptr(y), be.ptr(status)))
-        return {"x": x, "y": y, "status": status}
+        out = _outputs(be, N, x=(want_x, (N, T + 1, d)), y=(True, (N, T, p)))
+        self._call("dlm_simulate_batch", be, 0, md, pd, op, *out.values())
+        return out
 
     def smooth(self, mat, params, filt, *, flags=0):
         be = self._backend(filt)
         N = int(filt.shape[0]); d, T = mat.d, mat.T
-        md, pd, op, keep = self.prepare(mat, params, N, be, flags)
         fb = be.put(filt)
-        smooth = be.empty((N, T + 1, d + d * d))
-        status = be.empty((N,), np.int32)
-        self._check(self.lib.dlm_smooth_batch(self.h, md, pd, be.ptr(fb), op, be.ptr(smooth), be.ptr(status)))
-        return {"smooth": smooth, "status": status}
+        md, pd, op, keep = self.prepare(mat, params, N, be, flags)
+        out = _outputs(be, N, smooth=(True, (N, T + 1, d + d * d)))
+        self._call("dlm_smooth_batch", be, flags, md, pd, fb, op, *out.values())
+        return out
 
     def filter_smooth(self, mat, params, y, *, flags=0, out=None, want_filt=True):
         """Fused filter + smoother.  want_filt=False keeps the filtered records inside the engine (packed on the
@@ -831,13 +793,10 @@ class Engine:
         recw = self.lib.dlm_packed_record_doubles(d) if flags & _lib.OPT_PACKED_SYM else d + d * d
         yb = be.put(y).reshape(N, T, p)
         md, pd, op, keep = self.prepare(mat, params, N, be, flags)
-        self._hold(flags, yb)
         filt = (out["filt"] if out else be.empty((N, T + 1, recw))) if want_filt else None
-        smooth = out["smooth"] if out else be.empty((N, T + 1, recw))
-        status = out["status"] if out else be.empty((N,), np.int32)
-        self._check(self.lib.dlm_filter_smooth_batch(self.h, md, pd, be.ptr(yb), op, be.ptr(filt),
-                                                     be.ptr(smooth), be.ptr(status)))
-        return {"filt": filt, "smooth": smooth, "status": status}
+        res = _outputs(be, N, out["status"] if out else None, filt=filt, smooth=out["smooth"] if out else be.empty((N, T + 1, recw)))
+        self._call("dlm_filter_smooth_batch", be, flags, md, pd, yb, op, *res.values())
+        return res
 
     def unpack_records(self, d, packed):
         """Packed records [..., dlm_packed_record_doubles(d)] -> dense [..., d + d*d] (dlm_unpack_records)."""
@@ -845,8 +804,7 @@ class Engine:
         pb = be.put(packed)
         count = int(np.prod(pb.shape[:-1]))
         dense = be.empty(tuple(pb.shape[:-1]) + (d + d * d,))
-        op = _lib.Options(0, be.mem, 0, 0)
-        self._check(self.lib.dlm_unpack_records(self.h, int(d), count, be.ptr(pb), op, be.ptr(dense)))
+        self._call("dlm_unpack_records", be, 0, int(d), count, pb, _options(be), dense)
         return dense
 
     def last_timing(self):
@@ -877,34 +835,26 @@ class Engine:
         N = int(y.shape[0]); d, p, T = mat.d, mat.p, mat.T
         rec = d + d * d
         yb = be.put(y).reshape(N, T, p)
-        zb = be.put(z)
+        zb, fb = be.put(z), be.put(filt)
         md, pd, op, keep = self.prepare(mat, params, N, be, flags, seed, series_offset)
-        self._hold(flags, yb, zb)
-        theta = be.empty((N, T + 1, d)) if want_theta else None
-        cond = be.empty((N, T + 1, rec)) if want_cond else None
         L = self.lib.dlm_stats_len(d, p, flags & ~_lib.OPT_FFBS_SIMSMOOTH)
-        stats = be.empty((N, L)) if want_stats else None
-        status = be.empty((N,), np.int32)
+        out = _outputs(be, N, theta=(want_theta, (N, T + 1, d)), cond=(want_cond, (N, T + 1, rec)), stats=(want_stats, (N, L)),
+                       filt=(want_filt, (N, T + 1, rec)) if filt is None else fb)
+        ws, rest = out["filt"], (out["theta"], out["cond"], out["stats"], out["status"])
         if filt is None:
-            ws = be.empty((N, T + 1, rec)) if want_filt else None
-            self._check(self.lib.dlm_ffbs_batch(self.h, md, pd, be.ptr(yb), be.ptr(zb), op, be.ptr(ws),
-                                                be.ptr(theta), be.ptr(cond), be.ptr(stats), be.ptr(status)))
+            self._call("dlm_ffbs_batch", be, flags, md, pd, yb, zb, op, ws, *rest)
         else:
-            ws = be.put(filt)
-            self._check(self.lib.dlm_backward_sample_batch(self.h, md, pd, be.ptr(yb), be.ptr(ws), be.ptr(zb),
-                                                           op, be.ptr(theta), be.ptr(cond), be.ptr(stats),
-                                                           be.ptr(status)))
-        return {"theta": theta, "cond": cond, "stats": stats, "filt": ws, "status": status}
+            self._call("dlm_backward_sample_batch", be, flags, md, pd, yb, ws, zb, op, *rest)
+        return out
 
     def svd_filter(self, mat, params, y, *, flags=0):
         be = self._backend(y)
         N = int(y.shape[0]); d, p, T = mat.d, mat.p, mat.T
         yb = be.put(y).reshape(N, T, p)
         md, pd, op, keep = self.prepare(mat, params, N, be, flags)
-        rec = be.empty((N, T + 1, 2 * d + d * d))
-        status = be.empty((N,), np.int32)
-        self._check(self.lib.dlm_svd_filter_batch(self.h, md, pd, be.ptr(yb), op, be.ptr(rec), be.ptr(status)))
-        return {"svd": rec, "status": status}
+        out = _outputs(be, N, svd=(True, (N, T + 1, 2 * d + d * d)))
+        self._call("dlm_svd_filter_batch", be, flags, md, pd, yb, op, *out.values())
+        return out
 
     def svd_ffbs(self, mat, params, y, *, z=None, seed=0, series_offset=0, flags=0, want_stats=True):
         be = self._backend(y)
@@ -912,22 +862,17 @@ class Engine:
         yb = be.put(y).reshape(N, T, p)
         zb = be.put(z)
         md, pd, op, keep = self.prepare(mat, params, N, be, flags, seed, series_offset)
-        ws = be.empty((N, T + 1, 2 * d + d * d))
-        theta = be.empty((N, T + 1, d))
-        L = self.lib.dlm_stats_len(d, p, flags)
-        stats = be.empty((N, L)) if want_stats else None
-        status = be.empty((N,), np.int32)
-        self._check(self.lib.dlm_svd_ffbs_batch(self.h, md, pd, be.ptr(yb), be.ptr(zb), op, be.ptr(ws),
-                                                be.ptr(theta), be.ptr(stats), be.ptr(status)))
-        return {"svd": ws, "theta": theta, "stats": stats, "status": status}
+        out = _outputs(be, N, svd=(True, (N, T + 1, 2 * d + d * d)), theta=(True, (N, T + 1, d)),
+                       stats=(want_stats, (N, self.lib.dlm_stats_len(d, p, flags))))
+        self._call("dlm_svd_ffbs_batch", be, flags, md, pd, yb, zb, op, *out.values())
+        return out
 
     def stats_pool(self, stats):
         be = self._backend(stats)
         N, L = int(stats.shape[0]), int(stats.shape[1])
         sb = be.put(stats)
         pooled = be.empty((L,))
-        op = _lib.Options(0, be.mem, 0, 0)
-        self._check(self.lib.dlm_stats_pool(self.h, be.ptr(sb), N, L, be.ptr(pooled), op))
+        self._call("dlm_stats_pool", be, 0, sb, N, L, pooled, _options(be))
         return pooled
 
     # -- RCCL ----------------------------------------------------------------------
