@@ -42,6 +42,8 @@ COMM_ID_BYTES = 128
 # dlm_pf_desc.family: the observation models of the particle filter (Dglm.scala:46-175, package.scala:13-28)
 OBS_GAUSSIAN, OBS_POISSON, OBS_NEGBIN, OBS_ZIP, OBS_STUDENTT, OBS_BETA = range(6)
 PF_MAX_D, PF_MIN_PARTICLES, PF_MAX_PARTICLES = 16, 64, 1024
+PF_MAX_T = 0x1FFFFE           # DLM_PF_MAX_T: the Philox counter's slot field
+PF_FORECAST_MAX_RANKS = 8     # dlm_pf_forecast_desc.n_ranks
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int32)
@@ -99,6 +101,13 @@ class PfDesc(ctypes.Structure):
     """dlm_pf_desc: the observation family (OBS_*), the number of particles (a multiple of 64, 64..1024), n0 (resample when ESS < n0;
     negative: floor(P / 5) as ParticleFilter.likelihood) and literal = 1: the reference's arithmetic (Q37-Q39)."""
     _fields_ = [("family", ctypes.c_int32), ("n_particles", ctypes.c_int32), ("n0", ctypes.c_int32), ("literal", ctypes.c_int32)]
+
+
+class PfForecastDesc(ctypes.Structure):
+    """dlm_pf_forecast_desc: the observation family (OBS_*), the number of particles, literal = 1 (Q38, Q39), the number of order statistics per
+    time (0..PF_FORECAST_MAX_RANKS) and the Philox slot of the first forecast step."""
+    _fields_ = [("family", ctypes.c_int32), ("n_particles", ctypes.c_int32), ("literal", ctypes.c_int32), ("n_ranks", ctypes.c_int32),
+                ("slot_offset", ctypes.c_int64)]
 
 
 class StorvikDesc(ctypes.Structure):
@@ -188,6 +197,9 @@ SYMBOLS = [
     ("dlm_dlmfsv_variance_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, _OP, _V, _V]),
     ("dlm_dlmfsvsys_innovations_batch", ctypes.c_int, [_V, _MP, _V, _OP, _V, _V]),
     ("dlm_pf_batch", ctypes.c_int, [_V, _MP, _PP, ctypes.POINTER(PfDesc), _V, _V, ctypes.c_uint64, _OP, _V, _V, _V, _V, _V, _V]),
+    # (ranks is a HOST array whatever opts->mem is: a typed pointer, not one of the data pointers Engine._call turns into addresses)
+    ("dlm_pf_forecast_particles", ctypes.c_int, [_V, _MP, _PP, ctypes.POINTER(PfForecastDesc), _V, _ip, _V, _V, _V, ctypes.c_uint64, _OP,
+                                             _V, _V, _V, _V, _V, _V, _V, _V]),
     ("dlm_storvik_batch", ctypes.c_int, [_V, _MP, _PP, ctypes.POINTER(StorvikDesc), _V, ctypes.c_int64, _V, ctypes.c_int64, _V, _V, ctypes.c_uint64,
                                          _OP, _V, _V, _V, _V, _V, _V, _V, _V]),
     ("dlm_lw_batch", ctypes.c_int, [_V, _MP, _PP, ctypes.POINTER(LwDesc), _V, ctypes.c_int64, _V, ctypes.c_int64, _V, _V, ctypes.c_uint64,

@@ -32,6 +32,19 @@ constexpr unsigned DLM_KEY_SVKNOT = 0x53564B4Eu;     // "SVKN"
 //                     DLM_PF_BLOCK_RESAMPLE the [0, 1) uniform u_i of the resampling search of step t (pf_rand, dlm_pf.hip)
 constexpr unsigned DLM_KEY_PF = 0x50462000u;         // "PF " and the block in the low byte
 constexpr unsigned DLM_PF_BLOCK_RESAMPLE = 8u;
+//                     dlm_pf_forecast_particles draws under DLM_KEY_PF too (slot slot_offset + h for step h, the blocks above for the state normals and the
+//                     resampling of an observed step), and its own blocks beside them: DLM_PF_BLOCK_RESAMPLE0 the uniform of the resampling of a
+//                     WEIGHTED entry cloud (slot slot_offset); DLM_PF_BLOCK_OBS the observation's first draw (u1, u2): the Box-Muller cosine of the
+//                     Gaussian and Student-t families, u1 the zero-inflation uniform, u2 the inversion uniform of a small Poisson rate;
+//                     DLM_PF_BLOCK_POISSON + j attempt j < DLM_PF_POISSON_ATTEMPTS of the transformed rejection of a large rate; DLM_PF_BLOCK_GAMMA_A
+//                     + j and DLM_PF_BLOCK_GAMMA_B + j attempt j < DLM_PF_GAMMA_ATTEMPTS of the first and the second Gamma of a draw (`which` 0 its
+//                     normal, 1 its accept uniform), j = DLM_PF_GAMMA_ATTEMPTS the boost of a shape below 1.  The attempts are BLOCKS because the
+//                     counter's attempt field holds the particle (dlm_obs_draws.h)
+constexpr unsigned DLM_PF_BLOCK_RESAMPLE0 = 9u, DLM_PF_BLOCK_OBS = 10u;
+constexpr unsigned DLM_PF_POISSON_ATTEMPTS = 32u, DLM_PF_GAMMA_ATTEMPTS = 32u;
+constexpr unsigned DLM_PF_BLOCK_POISSON = 11u;
+constexpr unsigned DLM_PF_BLOCK_GAMMA_A = DLM_PF_BLOCK_POISSON + DLM_PF_POISSON_ATTEMPTS;       // 43 .. 75
+constexpr unsigned DLM_PF_BLOCK_GAMMA_B = DLM_PF_BLOCK_GAMMA_A + DLM_PF_GAMMA_ATTEMPTS + 1u;     // 76 .. 108
 //   DLM_KEY_STORVIK   dlm_storvik_batch: comp and attempt field as DLM_KEY_PF (slot t or DLM_STORVIK_SLOT_INIT, the particle).  The low byte of the
 //                     key is the BLOCK: q < 8 the Box-Muller pair of the state components (2 q, 2 q + 1), DLM_STORVIK_BLOCK_RESAMPLE the resampling
 //                     uniform, DLM_STORVIK_BLOCK_GAMMA + k the Gamma of component k (k < d: the variance W_kk; k = d: V).  The second byte is the
@@ -106,6 +119,10 @@ constexpr int DLM_PF_MAX_D = 16, DLM_PF_MAX_P = 1024;
 static_assert(DLM_PF_SLOT_INIT > (unsigned)DLM_PF_MAX_T - 1, "the particle filter's initial cloud lies above every time slot");
 static_assert(DLM_PF_MAX_P <= 1024 && (DLM_PF_MAX_D + 1) / 2 <= (int)DLM_PF_BLOCK_RESAMPLE && DLM_PF_BLOCK_RESAMPLE < 256u,
               "a particle fits the attempt field and a block the key's low byte");
+static_assert(DLM_PF_BLOCK_RESAMPLE0 > DLM_PF_BLOCK_RESAMPLE && DLM_PF_BLOCK_OBS > DLM_PF_BLOCK_RESAMPLE0 && DLM_PF_BLOCK_POISSON > DLM_PF_BLOCK_OBS &&
+              DLM_PF_BLOCK_GAMMA_A >= DLM_PF_BLOCK_POISSON + DLM_PF_POISSON_ATTEMPTS && DLM_PF_BLOCK_GAMMA_B > DLM_PF_BLOCK_GAMMA_A + DLM_PF_GAMMA_ATTEMPTS &&
+              DLM_PF_BLOCK_GAMMA_B + DLM_PF_GAMMA_ATTEMPTS < 256u,
+              "the forecast's blocks (entry resampling, the observation's first draw, the Poisson attempts, two Gammas' attempts and boosts) are distinct from the filter's and from one another and fit the key's low byte");
 constexpr unsigned DLM_STORVIK_SLOT_INIT = DLM_SLOT_TOP;   // dlm_storvik_batch, DLM_KEY_STORVIK: the initial cloud (the steps take the slots t < T <= DLM_PF_MAX_T)
 static_assert(DLM_STORVIK_BLOCK_GAMMA > DLM_STORVIK_BLOCK_RESAMPLE && (DLM_PF_MAX_D + 1) / 2 <= (int)DLM_STORVIK_BLOCK_RESAMPLE &&
               DLM_STORVIK_BLOCK_GAMMA + (unsigned)DLM_PF_MAX_D < 256u && DLM_STORVIK_GAMMA_ATTEMPTS < 256u,

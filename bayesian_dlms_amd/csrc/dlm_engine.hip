@@ -1520,6 +1520,50 @@ int dlm_pf_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_params_de
   return st.finish(opts->flags & DLM_OPT_ASYNC);
 }
 
+int dlm_pf_forecast_particles(dlm_engine* e, const dlm_model_desc* model, const dlm_params_desc* params, const dlm_pf_forecast_desc* fc,
+                          const double* obs_param, const int32_t* ranks, const double* cloud0, const double* weights0, const double* y,
+                          uint64_t iteration, const dlm_options* opts, double* fmean, double* fquant, double* draws, double* ll,
+                          double* mean, double* cloud, double* weights, int32_t* status) {
+  if (!e) return DLM_ERR_ARG;
+  if (!model || !params || !fc) return fail(e, DLM_ERR_ARG, "null descriptor");
+  int rc;
+  if ((rc = check_opts(e, opts))) return rc;
+  const int d = model->d, P = fc->n_particles;
+  if ((rc = pf_check(e, model, params, fc->family, fc->literal, P, obs_param, y, ll, "the particle forecast", true, true, [&] {
+        if (fc->n_ranks < 0 || fc->n_ranks > 8) return fail(e, DLM_ERR_ARG, "n_ranks: 0 .. 8 order statistics per time");
+        if (fc->n_ranks && (!ranks || !fquant)) return fail(e, DLM_ERR_ARG, "n_ranks > 0 needs ranks and fquant");
+        for (int j = 0; j < fc->n_ranks; ++j)
+          if (ranks[j] < 0 || ranks[j] >= P) return fail(e, DLM_ERR_ARG, "a rank must satisfy 0 <= rank < n_particles");
+        if (!fmean) return fail(e, DLM_ERR_ARG, "fmean is required");
+        if (weights0 && !cloud0) return fail(e, DLM_ERR_ARG, "weights0 needs cloud0");
+        if (fc->slot_offset < 0) return fail(e, DLM_ERR_ARG, "slot_offset must be >= 0");
+        return (int)DLM_OK;
+      }))) return rc;
+  if (fc->slot_offset > (int64_t)dlm::DLM_PF_MAX_T - model->T)
+    return fail(e, DLM_ERR_UNSUPPORTED, "slot_offset + T must stay below 2^21 - 1 (the Philox counter's slot field)");
+  HIP_TRY(e, hipSetDevice(e->device));
+  const size_t lds = dlm::pf_lds_bytes(d, P), have = dlm::lds_limit();
+  if (have && lds > have) return fail(e, DLM_ERR_UNSUPPORTED, "d and n_particles need more LDS than a workgroup of this device gets: (d + 2.5) n_particles + d^2 doubles");
+  dlm::PfForecastArgs a{};
+  const size_t n = model->N, t = model->T, dd = d, np = P;
+  Stager st(e, opts->mem == DLM_MEM_HOST);
+  pf_stage(st, a, model, params, fc->family, fc->literal, P + 1, P, params->V, obs_param, y, opts, iteration, ll, mean, nullptr, cloud, weights, status);
+  st.in(&a.W, params->W, params->w_stride ? (n - 1) * (size_t)params->w_stride + dd * dd : dd * dd);
+  a.w_stride = params->w_stride;
+  st.in(&a.cloud0, cloud0, cloud0 ? n * dd * np : 0);
+  st.in(&a.weights0, weights0, weights0 ? n * np : 0);
+  st.out(&a.fmean, fmean, n * t);
+  st.out(&a.fquant, fc->n_ranks ? fquant : nullptr, n * t * (size_t)fc->n_ranks);
+  st.out(&a.draws, draws, draws ? n * t * np : 0);
+  a.slot_offset = (int)fc->slot_offset;
+  a.n_ranks = fc->n_ranks;
+  for (int j = 0; j < fc->n_ranks; ++j) a.ranks[j] = ranks[j];   // a host array whatever opts->mem: checked above, passed by value
+  if ((rc = st.commit())) return rc;
+  e->variant = "pf-forecast-wave";
+  HIP_TRY(e, dlm::launch_pf_forecast(a, e->stream));
+  return st.finish(opts->flags & DLM_OPT_ASYNC);
+}
+
 int dlm_storvik_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_params_desc* params, const dlm_storvik_desc* sv,
                       const double* prior_v, int64_t prior_v_stride, const double* prior_w, int64_t prior_w_stride,
                       const double* obs_param, const double* y, uint64_t iteration, const dlm_options* opts, double* ll, double* mean,

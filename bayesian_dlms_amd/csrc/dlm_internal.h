@@ -537,6 +537,20 @@ struct PfArgs : PfCommonArgs {
 size_t pf_lds_bytes(int d, int P);   // the cloud [d][P], the weights and their running sums [2][P], chol(W) and chol(C0)
 hipError_t launch_pf(const PfArgs& a, hipStream_t s);
 
+// ---- posterior-predictive forecast of a DGLM from a cloud (Dglm.forecastParticles, Dglm.scala:305-335), dlm_pf_forecast.hip -------------
+// k_pf's step plus one observation draw per particle and their order statistics.  T is the number H of forecast steps; ess is always null
+struct PfForecastArgs : PfCommonArgs {
+  const double* W; long long w_stride;
+  int slot_offset;        // step h draws from the Philox slot slot_offset + h
+  int n_ranks; int ranks[8];   // 0 <= ranks[j] < P
+  const double* cloud0;   // [N][d][P], nullable: the initial cloud is drawn from (m0, C0)
+  const double* weights0; // [N][P], nullable: equal weights
+  double* fmean;          // [N][T]
+  double* fquant;         // [N][T][n_ranks], nullable with n_ranks = 0
+  double* draws;          // [N][T][P], nullable
+};
+hipError_t launch_pf_forecast(const PfForecastArgs& a, hipStream_t s);   // the LDS is pf_lds_bytes: the draws are sorted in the row `cum`
+
 // ---- Storvik filter: a particle filter that learns the diagonal of W (and V, Gaussian family) online (Storvik.scala:105-159), dlm_storvik.hip ----
 struct StorvikArgs : PfCommonArgs {
   int learn_v;            // 1: V is learned (Gaussian family)

@@ -13,7 +13,9 @@ observation time), so the first increment is 0 and the first step weights the in
 convention (the reference multiplies by g(0) and draws with covariance 0 there: DESIGN.md 2, Q40)."""
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass, replace
+from functools import reduce
 from typing import Callable, Optional
 
 import numpy as np
@@ -21,7 +23,7 @@ import numpy as np
 from . import _lib
 from .api import pack_observations
 from .dlm import Dlm, DlmParameters, MaterialisedModel, materialise
-from .engine import EngineError, check_pf_shape, check_rb_lds, check_shrinkage
+from .engine import EngineError, check_pf_ranks, check_pf_shape, check_rb_lds, check_shrinkage
 
 
 def logistic_function(upper: float, number):
@@ -109,6 +111,98 @@ class Dglm:
         a = mean * (1.0 - mean) / v
         return float(rng.beta(mean * (a - 1.0), (1.0 - mean) * (a - 1.0)))
 
+    @staticmethod
+    def interval_ranks(n: int, prob: float):
+        """The indices Dglm.meanAndIntervals / medianAndIntervals read in a sorted sample of n (Dglm.scala:263-285): index = floor(n prob),
+        upper = sorted[index], lower = sorted[n - index], median = sorted[floor(n / 2)] -> (lower, median, upper).  A prob whose indices fall
+        outside [0, n) -- floor(n prob) = 0 reads sorted[n], floor(n prob) >= n reads sorted[index] past the end -- is refused with a ValueError;
+        the reference indexes out of bounds there (Q73).  The same rule gives the ranks `forecast_particles` passes to the kernel."""
+        n = int(n)
+        index = int(math.floor(n * prob)) if math.isfinite(prob) else -1
+        if n < 1 or not (0 <= index < n and 0 <= n - index < n):
+            raise ValueError(f"prob = {prob!r} with n = {n} samples reads sorted[{index}] and sorted[{n - index}]: outside [0, {n}) "
+                             "(the reference indexes out of bounds there)")
+        return n - index, n // 2, index
+
+    @staticmethod
+    def _sorted_samples(samples):
+        x = np.asarray(samples, dtype=np.float64)
+        x = x[:, None] if x.ndim == 1 else x
+        if x.ndim != 2 or x.shape[0] < 1:
+            raise ValueError(f"samples: n vectors of one length, got an array of shape {x.shape}")
+        return x, np.sort(x, axis=0)
+
+    @staticmethod
+    def mean_and_intervals(prob: float):
+        """Dglm.meanAndIntervals(prob)(samples) (Dglm.scala:263-272): samples [n][k], n draws of a vector -> (mean [k], lower [k], upper [k]),
+        the mean as the reference forms it (the samples added in order, times 1 / n), the interval by `interval_ranks`."""
+        def summarise(samples):
+            x, srt = Dglm._sorted_samples(samples)
+            lo, _, up = Dglm.interval_ranks(x.shape[0], prob)
+            return reduce(np.add, x) * (1.0 / x.shape[0]), srt[lo], srt[up]
+        return summarise
+
+    @staticmethod
+    def median_and_intervals(prob: float):
+        """Dglm.medianAndIntervals(prob)(samples) (Dglm.scala:274-285): (median [k] = sorted[floor(n / 2)], lower [k], upper [k])."""
+        def summarise(samples):
+            x, srt = Dglm._sorted_samples(samples)
+            lo, med, up = Dglm.interval_ranks(x.shape[0], prob)
+            return srt[med], srt[lo], srt[up]
+        return summarise
+
+    @staticmethod
+    def forecast_particles(mod: "Dglm", cloud, p, ys, eng, *, weights=None, prob: float = 0.75, summary: str = "mean", time0=None,
+                           n_particles: Optional[int] = None, slot_offset: int = 0, seed: int = 0, iteration: int = 0,
+                           series_offset: int = 0, literal: bool = False, return_draws: bool = False):
+        """Dglm.forecastParticles(mod, xt, p, ys) (Dglm.scala:297-331) on the engine (dlm_pf_forecast_particles), summarised as
+        Dglm.meanAndIntervals / medianAndIntervals summarise it, on the device: the cloud is pushed through the times of ys, every particle
+        draws one observation per time, and per time the mean (or the median) and the interval of `interval_ranks(n, prob)` of those draws
+        come back.  cloud [N][d][n] (or [d][n]: one series) with optional weights [N][n] (given: resampled once at entry); cloud=None draws it
+        from (m0, C0) -- a prior-predictive simulation, n_particles needed.  ys: the test period, Vector[Data] or (times, y [H] or [N][H]);
+        NaN = "forecast, do not update", an observed value updates the cloud and resamples it, as the reference does.  p as in
+        ParticleFilter.filter.  time0: the time of the cloud, the first step advances over times[0] - time0; None is the reference's scan, whose
+        first step has dt = 0 (the cloud sits AT the first forecast time, Q71).  slot_offset: the Philox slot of the first step (the number of
+        steps already filtered).  Returns {"time" [H], "mean" or "median" [N][H], "lower", "upper" [N][H], "state_mean" [N][H][d], "ll" [N],
+        "cloud" [N][d][n], "status" [N]} and "draws" [N][H][n] with return_draws."""
+        if summary not in ("mean", "median"):
+            raise ValueError(f'summary: "mean" or "median", got {summary!r}')
+        if cloud is None:
+            if weights is not None:
+                raise EngineError("weights need the cloud they weigh: pass cloud too")
+            if n_particles is None:
+                raise EngineError("cloud=None draws the cloud from (m0, C0): say how many particles with n_particles")
+            n = int(n_particles)
+        else:
+            cloud = cloud if hasattr(cloud, "data_ptr") else np.asarray(cloud, dtype=np.float64)
+            cloud = cloud[None] if cloud.ndim == 2 else cloud
+            if cloud.ndim != 3:
+                raise EngineError(f"cloud must be [N][d][n] or [d][n], got the shape {tuple(cloud.shape)}")
+            n = int(cloud.shape[2])
+            if weights is not None and np.ndim(weights) == 1:
+                weights = weights[None]
+        times, y = _observations(ys)
+        f0 = np.atleast_2d(np.asarray(mod.f(float(times[0])), dtype=np.float64))
+        check_pf_shape(f0.shape[0], f0.shape[1], n)
+        lo, med, up = Dglm.interval_ranks(n, prob)
+        ranks = check_pf_ranks((lo, up) if summary == "mean" else (lo, med, up), n)
+        mat = materialise_forecast(mod, times, time0)
+        N, y, params = _bank(p, y)
+        if cloud is not None and y.shape[0] == 1 and cloud.shape[0] > 1 and isinstance(p, DlmParameters):
+            N, y = int(cloud.shape[0]), np.repeat(y, cloud.shape[0], axis=0)
+        if cloud is not None and cloud.shape[0] != N:
+            raise EngineError(f"{cloud.shape[0]} clouds for {N} series")
+        out = _numpy(eng.pf_forecast(mat, params, y, family=mod.family, n_particles=n, ranks=ranks, cloud=cloud, weights=weights,
+                                     slot_offset=slot_offset, literal=literal, obs_param=mod.nu, iteration=iteration, seed=seed,
+                                     series_offset=series_offset, want_draws=return_draws))
+        q = out["fquant"]
+        res = {"time": times, "lower": q[:, :, 0], "upper": q[:, :, -1], "state_mean": out["mean"], "ll": out["ll"], "cloud": out["cloud"],
+               "status": out["status"]}
+        res[summary] = out["fmean"] if summary == "mean" else q[:, :, 1]
+        if return_draws:
+            res["draws"] = out["draws"]
+        return res
+
     def simulate_regular(self, params: DlmParameters, n_steps: int, dt: float = 1.0, *, rng=None):
         """Dglm.simulateRegular (Dglm.scala:224-232) on the host: x_0 ~ N(m0, C0) at time 0, then n_steps steps of length dt.  Returns
         (times [n], y [n], x [n][d]).  (F is taken at the observation's time; the reference's `observation` evaluates f(1.0).)"""
@@ -143,6 +237,32 @@ def materialise_pf(mod, times) -> MaterialisedModel:
         else:
             remap.append(len(table)); table.append(gm)
     gi = np.concatenate([[0], np.asarray(remap, dtype=np.int32)[np.searchsorted(uniq, dts[1:])]]).astype(np.int32)
+    return replace(mat, G=np.concatenate(table), n_g=len(table), g_index=None if len(table) == 1 else gi, dt=dts)
+
+
+def materialise_forecast(mod, times, time0=None) -> MaterialisedModel:
+    """The model's tables on the forecast times with the cloud at time0: dt_0 = times[0] - time0.  time0=None is the reference's scan
+    (Dglm.scala:302-311): the cloud sits AT the first forecast time and dt_0 = 0, which is materialise_pf (Q71)."""
+    times = np.asarray(times, dtype=np.float64).reshape(-1)
+    if time0 is None:
+        return materialise_pf(mod, times)
+    mat = materialise(Dlm(mod.f, mod.g), times)
+    dts = np.diff(np.concatenate([[float(time0)], times]))
+    if not np.all(dts >= 0.0):
+        raise ValueError("the forecast times must not decrease, and the first must not lie before time0")
+    nz = dts != 0.0
+    uniq = np.unique(dts[nz]) if nz.any() else np.array([1.0])
+    table, remap = [], []
+    for u in uniq:
+        gm = np.ascontiguousarray(np.atleast_2d(mod.g(float(u))).T).reshape(-1)
+        for k, have in enumerate(table):
+            if np.array_equal(have, gm):
+                remap.append(k)
+                break
+        else:
+            remap.append(len(table)); table.append(gm)
+    gi = np.zeros(times.size, dtype=np.int32)          # (a step with dt = 0 does not advance: its G is not read)
+    gi[nz] = np.asarray(remap, dtype=np.int32)[np.searchsorted(uniq, dts[nz])]
     return replace(mat, G=np.concatenate(table), n_g=len(table), g_index=None if len(table) == 1 else gi, dt=dts)
 
 
@@ -263,6 +383,19 @@ class ParticleFilter:
         N, y, params = _bank(p, y)
         return _numpy(eng.particle_filter(mat, params, y, family=mod.family, n_particles=self.n, n0=self.n0, literal=literal, obs_param=mod.nu,
                                           iteration=iteration, seed=seed, series_offset=series_offset))
+
+    def forecast(self, mod: Dglm, ys_train, ys_test, p, eng, *, seed: int = 0, iteration: int = 0, series_offset: int = 0,
+                 literal: bool = False, **kw):
+        """Filter the training period, then forecast the test period from the filter's cloud AND its weights (the end of the reference's
+        worked examples: TrafficModel.scala:185-191, Temperature.scala:288, NoModel.scala:203): Dglm.forecast_particles with
+        slot_offset = len(ys_train), so that the forecast continues the filter's Philox stream, and time0 = the last training time.
+        kw: prob, summary, return_draws.  Returns forecast_particles' dict and "filter": the filter's own."""
+        filt = self.filter(mod, ys_train, p, eng, seed=seed, iteration=iteration, series_offset=series_offset, literal=literal)
+        times = _observations(ys_train)[0]
+        out = Dglm.forecast_particles(mod, filt["cloud"], p, ys_test, eng, weights=filt["weights"], time0=float(times[-1]),
+                                      slot_offset=len(times), seed=seed, iteration=iteration, series_offset=series_offset, literal=literal, **kw)
+        out["filter"] = filt
+        return out
 
     @staticmethod
     def likelihood(mod: Dglm, ys, n: int, p, eng, **kw):

@@ -118,6 +118,17 @@ def check_pf_shape(d: int, p: int, n_particles: int):
                           f"(one wavefront per series, whole slots of particles), got {n_particles}")
 
 
+def check_pf_ranks(ranks, n_particles: int):
+    """The order statistics dlm_pf_forecast_particles writes per time: at most PF_FORECAST_MAX_RANKS ranks, each in [0, n_particles) -> the ranks as
+    a list of ints (the engine answers the same with DLM_ERR_ARG)."""
+    rk = [int(r) for r in ranks]
+    if len(rk) > _lib.PF_FORECAST_MAX_RANKS:
+        raise EngineError(f"a forecast takes at most {_lib.PF_FORECAST_MAX_RANKS} ranks (order statistics per time), got {len(rk)}")
+    if any(not 0 <= r < n_particles for r in rk):
+        raise EngineError(f"a rank must satisfy 0 <= rank < n_particles = {n_particles}, got {rk}")
+    return rk
+
+
 def check_rb_lds(d: int, n_particles: int):
     """What dlm_rb_batch asks of (d, P) beyond check_pf_shape: every particle's covariance lives in LDS."""
     need = _lib.rb_lds_bytes(d, n_particles)
@@ -648,6 +659,41 @@ class Engine:
                        weights=(want_weights, (N, P)))
         desc = _lib.PfDesc(int(family), P, int(n0), 1 if literal else 0)
         self._call("dlm_pf_batch", be, flags, md, pd, desc, ob, yb, int(iteration), op, *out.values())
+        return out
+
+    def pf_forecast(self, mat, params, y, *, family, n_particles, ranks=(), cloud=None, weights=None, slot_offset=0, literal=False,
+                    obs_param=None, iteration=0, seed=0, series_offset=0, flags=0, want_draws=False, want_mean=True, want_cloud=True,
+                    want_weights=False):
+        """Posterior-predictive forecast of a dynamic generalised linear model from a particle cloud (dlm_pf_forecast_particles;
+        Dglm.forecastParticles, Dglm.scala:297-331) for N series of P = n_particles particles: mat describes the H forecast steps (dt[0] the
+        gap from the time of the cloud), y [N][H] with NaN = "forecast, do not update"; an observed step updates and resamples the cloud.
+        cloud [N][d][P]: the cloud to start from (None: drawn from (m0, C0) as particle_filter draws it), weights [N][P] its weights (None:
+        equal; given: the cloud is resampled once at entry).  ranks: up to 8 order statistics of the P draws of a time, 0 <= rank < P.
+        slot_offset: step h draws from the Philox slot slot_offset + h (the number of steps filtered so far continues their stream).
+        params, family, obs_param, literal as in particle_filter.  Returns {"fmean" [N][H] the mean of the draws, "fquant" [N][H][len(ranks)]
+        their order statistics, "draws" [N][H][P], "ll" [N], "mean" [N][H][d] the filtering mean, "cloud" [N][d][P], "weights" [N][P],
+        "status" [N]}; the optional ones are None when not wanted.  A series with a status bit has ll = -inf and NaN from the failing step on."""
+        d, T, P = _pf_shape(mat, n_particles, family)
+        rk = check_pf_ranks(ranks, P)
+        if weights is not None and cloud is None:
+            raise EngineError("weights need the cloud they weigh: pass cloud too")
+        if not 0 <= int(slot_offset) <= _lib.PF_MAX_T - T:
+            raise EngineError(f"slot_offset + the number of steps must stay within {_lib.PF_MAX_T} (the Philox counter's slot field), got {slot_offset} + {T}")
+        be = self._backend(y)
+        N, yb, ob = _pf_data(be, y, T, family, obs_param)
+        cb, wb = be.put(cloud), be.put(weights)
+        if cb is not None and tuple(cb.shape) != (N, d, P):
+            raise EngineError(f"cloud must be [N][d][P] = {(N, d, P)}, got {tuple(cb.shape)}")
+        if wb is not None and tuple(wb.shape) != (N, P):
+            raise EngineError(f"weights must be [N][P] = {(N, P)}, got {tuple(wb.shape)}")
+        md, pd, op, keep = self.prepare(mat, params, N, be, flags, seed, series_offset)
+        if pd.v_tstride or pd.w_tstride:
+            raise EngineError("the particle forecast takes time-invariant V and W")
+        out = _outputs(be, N, fmean=(True, (N, T)), fquant=(bool(rk), (N, T, len(rk))), draws=(want_draws, (N, T, P)), ll=(True, (N,)),
+                       mean=(want_mean, (N, T, d)), cloud=(want_cloud, (N, d, P)), weights=(want_weights, (N, P)))
+        desc = _lib.PfForecastDesc(int(family), P, 1 if literal else 0, len(rk), int(slot_offset))
+        rkc = (ctypes.c_int32 * len(rk))(*rk) if rk else None          # a host array whatever the backend: the call reads it before it returns
+        self._call("dlm_pf_forecast_particles", be, flags, md, pd, desc, ob, rkc, cb, wb, yb, int(iteration), op, *out.values())
         return out
 
     def storvik_filter(self, mat, params, y, prior_w, *, family, n_particles, prior_v=None, learn_v=None, n0=-1, literal=False,

@@ -586,6 +586,40 @@ int dlm_pf_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_params_de
                  const double* obs_param, const double* y, uint64_t iteration, const dlm_options* opts, double* ll,
                  double* mean, double* ess, double* cloud, double* weights, int32_t* status);
 
+/* Posterior-predictive forecast of a DGLM from a particle cloud (Dglm.forecastParticles, Dglm.scala:305-335): dlm_pf_batch's step, and at every
+ * step one draw of the observation per particle, summarised where the draws are.  Shapes, limits, families and LDS as dlm_pf_batch; `model`
+ * describes the H = model->T forecast steps (dt[0] the gap from the time of the cloud), y [N][H] with NaN = "forecast, do not update".
+ * At entry: cloud0 == NULL draws the initial cloud from (m0, C0) exactly as dlm_pf_batch does (a prior-predictive simulation, or with
+ * slot_offset = 0 the filter itself); cloud0 [N][d][P] starts from it, with equal weights when weights0 == NULL, else after ONE multinomial
+ * resampling under weights0 [N][P] (non-negative, need not sum to 1), so that every later cloud has equal weights.
+ * Per step h (Philox slot fc->slot_offset + h):
+ *   1. advance the cloud as dlm_pf_batch does (same key, slot, blocks 0..7);  2. eta_i = F_h^T x_i;
+ *   3. ytilde_i ~ family(eta_i, v), drawn EXACTLY (dlm_obs_draws.h; DESIGN.md 4.25: Poisson by inversion below a rate of 10 and Hoermann's PTRS from
+ *      there on, NegBin as a Gamma mixture of it, ZIP, Student-t as a Gamma scale mixture, Beta from two Gammas), before any weighting;
+ *   4. fmean[h] = (1 / P) sum_i ytilde_i in the fixed order of DESIGN.md 4.19;  5. draws[h][i] = ytilde_i when `draws` is given;
+ *   6. the draws are sorted (a bitonic network in LDS) and fquant[h][j] = sorted[ranks[j]];
+ *   7. y_h observed: weigh, ll += m + log s, mean[h] = the filtering mean, and ALWAYS resample with block 8 of the slot, as dlm_pf_batch does
+ *      with n0 > P (Dglm.scala:322-328).  y_h NaN: mean[h] is the mean of the carried cloud and the step ends.
+ * fc->literal as in dlm_pf_batch (Q38, Q39).  ranks is a HOST array of fc->n_ranks entries whatever opts->mem is.
+ * A draw that is not finite, or a rate that is not finite or above 1e15 (Beta parameters that are not positive included, Q41), stops the series
+ * with DLM_ST_NONFINITE; so do entry weights without a positive finite sum; the other statuses as dlm_pf_batch.  A stopped series has ll = -inf and
+ * NaN in fmean, fquant, draws and mean from that step on.  The batch completes.
+ * DLM_ERR_ARG: n_ranks outside 0..8, a rank outside [0, P), fquant missing with n_ranks > 0, fmean missing, weights0 without cloud0, slot_offset
+ * < 0 and what dlm_pf_batch refuses so; DLM_ERR_UNSUPPORTED: slot_offset + H beyond 2^21 - 2 and the shapes dlm_pf_batch refuses.
+ * Draws: DLM_KEY_PF, counter (opts->seed, opts->series_offset + n, iteration, slot, particle); the blocks are listed in dlm_draws.h.  Results
+ * depend on neither N nor the neighbours nor how the batch is split.  opts: mem, seed, series_offset, DLM_OPT_ASYNC. */
+typedef struct {
+  int32_t family;       /* DLM_OBS_*                                                   */
+  int32_t n_particles;  /* P                                                           */
+  int32_t literal;      /* 1: the reference's arithmetic, Q38, Q39                     */
+  int32_t n_ranks;      /* 0..8 order statistics per time                              */
+  int64_t slot_offset;  /* step h draws from the Philox slot slot_offset + h           */
+} dlm_pf_forecast_desc;
+int dlm_pf_forecast_particles(dlm_engine* e, const dlm_model_desc* model, const dlm_params_desc* params, const dlm_pf_forecast_desc* fc,
+                          const double* obs_param, const int32_t* ranks, const double* cloud0, const double* weights0, const double* y,
+                          uint64_t iteration, const dlm_options* opts, double* fmean, double* fquant, double* draws, double* ll,
+                          double* mean, double* cloud, double* weights, int32_t* status);
+
 /* Storvik filter of a dynamic generalised linear model (StorvikFilter.step / filterTs, Storvik.scala:105-189; Storvik 2002): the particle
  * filter above with ONLINE PARAMETER LEARNING.  W is diagonal and unknown, W_kk ~ InverseGamma(prior_w[k][0], prior_w[k][1]) (shape, scale);
  * with sv->learn_v = 1 (DLM_OBS_GAUSSIAN only: the statistic is conjugate for the Gaussian family alone, any other family is DLM_ERR_ARG) so

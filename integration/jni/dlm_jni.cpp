@@ -385,6 +385,29 @@ JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_particleFilter(JN
   throw_if(env, eng(h), dlm_pf_batch(eng(h), &d.m, &d.q, &pf, ptr<const double>(obsParam), ptr<const double>(y), static_cast<uint64_t>(iteration), &d.o, ptr<double>(ll), ptr<double>(mean),
                                      ptr<double>(ess), ptr<double>(cloud), ptr<double>(weights), ptr<int32_t>(status)));
 }
+// ---- posterior-predictive forecast of a dynamic generalised linear model from a particle cloud (Dglm.forecastParticles, Dglm.scala:297-331): the model describes the H forecast steps, y [N][H] with NaN =
+// "forecast, do not update".  dlm_pf_forecast_desc crosses as scalars (family, nParticles, literal, slotOffset) and ranks, a long[] of at most 8 order statistics in [0, nParticles) (null or empty: none), which
+// the engine reads on the host.  cloud0 [N][d][nParticles] (0: drawn from (m0, C0)), weights0 [N][nParticles] (0: equal).  fmean [N][H] and ll [N] are required; fquant [N][H][ranks.length] with ranks; draws
+// [N][H][nParticles], mean [N][H][d], cloud, weights and status are optional (0).
+JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_particleForecast(JNIEnv* env, jobject, jlong h, jlongArray model, jlongArray params, jlongArray opts, jint family, jint nParticles, jint literal,
+                                                                                jlong slotOffset, jlongArray ranks, jlong obsParam, jlong cloud0, jlong weights0, jlong y, jlong iteration, jlong fmean,
+                                                                                jlong fquant, jlong draws, jlong ll, jlong mean, jlong cloud, jlong weights, jlong status) {
+  Desc d;
+  if (!read_desc(env, model, params, opts, d)) return;
+  const jsize nRanks = ranks ? env->GetArrayLength(ranks) : 0;
+  if (nRanks > 8) { throw_arg(env, "particleForecast: at most 8 ranks"); return; }
+  jlong rk[8] = {0};
+  int32_t rk32[8] = {0};
+  if (nRanks) env->GetLongArrayRegion(ranks, 0, nRanks, rk);
+  for (jsize j = 0; j < nRanks; ++j) {
+    if (rk[j] < 0 || rk[j] >= nParticles) { throw_arg(env, "particleForecast: a rank must satisfy 0 <= rank < nParticles"); return; }
+    rk32[j] = static_cast<int32_t>(rk[j]);
+  }
+  const dlm_pf_forecast_desc fc{family, nParticles, literal, static_cast<int32_t>(nRanks), static_cast<int64_t>(slotOffset)};
+  throw_if(env, eng(h), dlm_pf_forecast_particles(eng(h), &d.m, &d.q, &fc, ptr<const double>(obsParam), rk32, ptr<const double>(cloud0), ptr<const double>(weights0), ptr<const double>(y),
+                                                  static_cast<uint64_t>(iteration), &d.o, ptr<double>(fmean), ptr<double>(fquant), ptr<double>(draws), ptr<double>(ll), ptr<double>(mean), ptr<double>(cloud),
+                                                  ptr<double>(weights), ptr<int32_t>(status)));
+}
 // ---- Storvik filter of a dynamic generalised linear model (Storvik.scala:105-189): the particle filter above with the diagonal of W -- and with learnV = 1 (Gaussian family) V -- learned online from
 // InverseGamma priors: priorV [2] = (shape, scale), priorW [d][2], strides in doubles (0: one prior for the batch).  dlm_storvik_desc crosses as scalars in its field order; scaleMean [N][T][d+1] and
 // scales [N][d+1][nParticles] are optional (0) like the outputs of particleFilter.
