@@ -110,6 +110,22 @@ class PfForecastDesc(ctypes.Structure):
                 ("slot_offset", ctypes.c_int64)]
 
 
+FC_VAR, FC_LOGVAR, FC_IG_SCALE = range(3)   # DLM_FC_*: what the rows of pw and pv of dlm_pf_forecast_learned hold
+
+
+class PfForecastLearnedDesc(ctypes.Structure):
+    """dlm_pf_forecast_learned_desc: the observation family (OBS_*), the number of particles, var_kind (FC_*: the particles' rows are
+    variances, log-variances or InverseGamma scales), the number of order statistics per time (0..PF_FORECAST_MAX_RANKS) and the Philox slot
+    of the first forecast step."""
+    _fields_ = [("family", ctypes.c_int32), ("n_particles", ctypes.c_int32), ("var_kind", ctypes.c_int32), ("n_ranks", ctypes.c_int32),
+                ("slot_offset", ctypes.c_int64)]
+
+
+def pf_forecast_learned_lds_bytes(d: int, n_particles: int) -> int:
+    """pf_forecast_learned_lds_bytes of dlm_pf_forecast_learned.hip: the LDS dlm_pf_forecast_learned needs for (d, P)."""
+    return (2 * d + 3) * n_particles * 8 + 4 * n_particles
+
+
 class StorvikDesc(ctypes.Structure):
     """dlm_storvik_desc: dlm_pf_desc's fields (literal = 1: Q39 and Q43) and learn_v = 1: V is learned too (OBS_GAUSSIAN only)."""
     _fields_ = [("family", ctypes.c_int32), ("n_particles", ctypes.c_int32), ("n0", ctypes.c_int32), ("literal", ctypes.c_int32),
@@ -206,6 +222,10 @@ SYMBOLS = [
                                     _OP, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
     ("dlm_rb_batch", ctypes.c_int, [_V, _MP, _PP, ctypes.POINTER(RbDesc), _V, ctypes.c_int64, _V, ctypes.c_int64, _V, ctypes.c_uint64,
                                     _OP, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
+    # (ranks: a host array, as above)
+    ("dlm_pf_forecast_learned", ctypes.c_int, [_V, _MP, _PP, ctypes.POINTER(PfForecastLearnedDesc), _V, _ip, _V, _V, _V, _V, _V, ctypes.c_int64,
+                                               ctypes.c_uint64, _OP, _V, _V, _V, _V, _V, _V, _V, _V]),
+    ("dlm_rb_state_draw", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _V, _V, ctypes.c_int64, ctypes.c_uint64, _OP, _V, _V]),
     ("dlm_pg_batch", ctypes.c_int, [_V, _MP, _PP, ctypes.POINTER(PgDesc), _V, _V, _V, ctypes.c_uint64, _OP, _V, _V, _V, _V, _V, _V, _V, _V]),
     ("dlm_ou_ffbs_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, ctypes.c_int64, _V, ctypes.c_int64,
                                          _V, _OP, _V, _V, _V]),

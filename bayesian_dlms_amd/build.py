@@ -6,14 +6,14 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdlm_engine.so")
-SOURCES = ["dlm_engine.hip", "dlm_generic.hip", "dlm_mfma16.hip", "dlm_sparse16.hip", "dlm_sampler16.hip", "dlm_tiled.hip", "dlm_wave48.hip", "dlm_svd.hip", "dlm_ar1.hip", "dlm_lane.hip", "dlm_gibbs.hip", "dlm_loglik.hip", "dlm_studentt.hip", "dlm_sv.hip", "dlm_sv_ou.hip", "dlm_sv_knots.hip", "dlm_fsv.hip", "dlm_dlmfsv.hip", "dlm_pf.hip", "dlm_storvik.hip", "dlm_lw.hip", "dlm_rb.hip", "dlm_pg.hip", "dlm_pf_forecast.hip"]
+SOURCES = ["dlm_engine.hip", "dlm_generic.hip", "dlm_mfma16.hip", "dlm_sparse16.hip", "dlm_sampler16.hip", "dlm_tiled.hip", "dlm_wave48.hip", "dlm_svd.hip", "dlm_ar1.hip", "dlm_lane.hip", "dlm_gibbs.hip", "dlm_loglik.hip", "dlm_studentt.hip", "dlm_sv.hip", "dlm_sv_ou.hip", "dlm_sv_knots.hip", "dlm_fsv.hip", "dlm_dlmfsv.hip", "dlm_pf.hip", "dlm_storvik.hip", "dlm_lw.hip", "dlm_rb.hip", "dlm_pg.hip", "dlm_pf_forecast.hip", "dlm_pf_forecast_learned.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 FLAGS = BASE_FLAGS + ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 # dlm_wave48.hip keeps whole matrices in registers (up to the 512-register budget of a wave): its accumulators may live
 # in AGPRs, and the VGPR-form rewrite pass of this compiler crashes on it
 FILE_FLAGS = {"dlm_wave48.hip": BASE_FLAGS}
-# an object is stale when its source or any of these is newer (dlm_wave.h: the device primitives of the kernel files; dlm_draws.h: the draws of the Gibbs parameter steps; dlm_pf_common.h: what the particle kernels share; dlm_obs_draws.h: the forecast kernel's observation draws)
+# an object is stale when its source or any of these is newer (dlm_wave.h: the device primitives of the kernel files; dlm_draws.h: the draws of the Gibbs parameter steps; dlm_pf_common.h: what the particle kernels share; dlm_obs_draws.h: the forecast kernels' observation draws and sort)
 HEADERS = [os.path.join(CSRC, "dlm_internal.h"), os.path.join(CSRC, "dlm_wave.h"), os.path.join(CSRC, "dlm_draws.h"), os.path.join(CSRC, "dlm_pf_common.h"), os.path.join(CSRC, "dlm_obs_draws.h"), os.path.join(CSRC, "dlm_fsv_solve.h"), os.path.join(HERE, "..", "include", "dlm_engine.h")]
 
 

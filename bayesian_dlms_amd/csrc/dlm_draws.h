@@ -65,6 +65,16 @@ constexpr unsigned DLM_LW_BLOCK_RESAMPLE = 8u, DLM_LW_BLOCK_FIRST = 9u, DLM_LW_B
 //                     the log-variances (2 q, 2 q + 1) (k < d: log W_kk; k = d: log V).  The second byte is 0.
 constexpr unsigned DLM_KEY_RB = 0x52420000u;         // "RB", a zero byte and the block byte
 constexpr unsigned DLM_RB_BLOCK_RESAMPLE = 0u, DLM_RB_BLOCK_FIRST = 1u, DLM_RB_BLOCK_PARAM = 2u;
+//                     dlm_rb_state_draw draws under DLM_KEY_RB too, at the slot its caller names: DLM_RB_BLOCK_STATE + q, q < 8, the Box-Muller pair
+//                     of the components (2 q, 2 q + 1) of z in x_i = m_i + chol(C_i) z (blocks no step of dlm_rb_batch uses)
+constexpr unsigned DLM_RB_BLOCK_STATE = 16u;
+//   DLM_KEY_FCL       dlm_pf_forecast_learned, DLM_FC_IG_SCALE only (its state normals, entry resampling and observation draws are DLM_KEY_PF's, above):
+//                     comp = slot_offset, the attempt field the particle.  The low byte of the key is the BLOCK: DLM_FCL_BLOCK_GAMMA + k the Gamma of the
+//                     variance of component k (k < d: W_kk; k = d: V), drawn ONCE per particle after the entry resampling.  The second byte is the ATTEMPT
+//                     of that Gamma's rejection loop, as under DLM_KEY_STORVIK: attempt j < DLM_FCL_GAMMA_ATTEMPTS, `which` 0 its normal and 1 its accept
+//                     uniform; DLM_FCL_GAMMA_ATTEMPTS itself the boost of a shape below 1.
+constexpr unsigned DLM_KEY_FCL = 0x464C0000u;        // "FL", then the attempt byte and the block byte
+constexpr unsigned DLM_FCL_BLOCK_GAMMA = 0u, DLM_FCL_GAMMA_ATTEMPTS = 255u;
 //   DLM_KEY_PG        dlm_pg_batch: comp and attempt field as DLM_KEY_PF (slot t for the step into observation t or DLM_PG_SLOT_INIT, the particle).
 //                     The low byte of the key is the BLOCK: q < 8 the Box-Muller pair of the state components (2 q, 2 q + 1) of a free particle,
 //                     DLM_PG_BLOCK_RESAMPLE the [0, 1) uniform of a free particle's ancestor search in step t, DLM_PG_BLOCK_REF the uniform of the
@@ -137,6 +147,12 @@ static_assert(DLM_RB_SLOT_INIT > (unsigned)DLM_PF_MAX_T - 1, "the Rao-Blackwelli
 static_assert(DLM_RB_BLOCK_FIRST > DLM_RB_BLOCK_RESAMPLE && DLM_RB_BLOCK_PARAM > DLM_RB_BLOCK_FIRST &&
               DLM_RB_BLOCK_PARAM + (unsigned)(DLM_PF_MAX_D + 2) / 2 <= 256u,
               "the Rao-Blackwellised filter's blocks (the pairs of d + 1 log-variances included) are distinct and fit the key's low byte");
+static_assert(DLM_RB_BLOCK_STATE >= DLM_RB_BLOCK_PARAM + (unsigned)(DLM_PF_MAX_D + 2) / 2 && DLM_RB_BLOCK_STATE + (unsigned)(DLM_PF_MAX_D + 1) / 2 <= 256u,
+              "the state draw's blocks lie above the Rao-Blackwellised filter's own and fit the key's low byte");
+static_assert(DLM_FCL_BLOCK_GAMMA + (unsigned)DLM_PF_MAX_D < 256u && DLM_FCL_GAMMA_ATTEMPTS < 256u && (DLM_KEY_FCL & 0xFFFFu) == 0u &&
+              DLM_KEY_FCL != DLM_KEY_STORVIK && DLM_KEY_FCL != DLM_KEY_LW && DLM_KEY_FCL != DLM_KEY_RB && DLM_KEY_FCL != DLM_KEY_PG &&
+              (DLM_KEY_FCL >> 16) != (DLM_KEY_PF >> 16),
+              "the learned forecast's Gammas (d + 1 components) and their attempts fit a byte of the key each, under a key of their own");
 constexpr unsigned DLM_PG_SLOT_INIT = DLM_SLOT_TOP;   // dlm_pg_batch, DLM_KEY_PG: the initial cloud and the final index (the steps take the slots t < T <= DLM_PF_MAX_T)
 static_assert(DLM_PG_SLOT_INIT > (unsigned)DLM_PF_MAX_T - 1, "the conditional filter's initial cloud and final index lie above every time slot");
 static_assert((DLM_PF_MAX_D + 1) / 2 <= (int)DLM_PG_BLOCK_RESAMPLE && DLM_PG_BLOCK_REF > DLM_PG_BLOCK_RESAMPLE && DLM_PG_BLOCK_FINAL > DLM_PG_BLOCK_REF &&

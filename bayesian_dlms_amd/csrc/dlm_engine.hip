@@ -1663,6 +1663,107 @@ int dlm_rb_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_params_de
   return st.finish(opts->flags & DLM_OPT_ASYNC);
 }
 
+int dlm_pf_forecast_learned(dlm_engine* e, const dlm_model_desc* model, const dlm_params_desc* params, const dlm_pf_forecast_learned_desc* fc,
+                            const double* obs_param, const int32_t* ranks, const double* cloud0, const double* weights0, const double* pw,
+                            const double* pv, const double* shapes, int64_t shapes_stride, uint64_t iteration, const dlm_options* opts,
+                            double* fmean, double* fquant, double* draws, double* mean, double* cloud, double* var_w, double* var_v,
+                            int32_t* status) {
+  if (!e) return DLM_ERR_ARG;
+  if (!model || !params || !fc) return fail(e, DLM_ERR_ARG, "null descriptor");
+  int rc;
+  if ((rc = check_opts(e, opts))) return rc;
+  const int d = model->d, T = model->T, N = model->N, P = fc->n_particles, family = fc->family;
+  if (d < 1 || model->p < 1 || T < 1 || N < 1) return fail(e, DLM_ERR_ARG, "d, p, T, N must be >= 1");
+  if (!model->F || !model->G || model->n_g < 1) return fail(e, DLM_ERR_ARG, "model tables F/G missing");
+  if (model->n_g > 1 && !model->g_index) return fail(e, DLM_ERR_ARG, "n_g > 1 needs g_index");
+  if (model->f_stride != 0 && model->f_stride != (int64_t)d * model->p) return fail(e, DLM_ERR_ARG, "f_stride must be 0 or d*p");
+  if (family < DLM_OBS_GAUSSIAN || family > DLM_OBS_BETA) return fail(e, DLM_ERR_ARG, "family: one of DLM_OBS_*");
+  if (fc->var_kind != DLM_FC_VAR && fc->var_kind != DLM_FC_LOGVAR && fc->var_kind != DLM_FC_IG_SCALE) return fail(e, DLM_ERR_ARG, "var_kind: one of DLM_FC_*");
+  if (!cloud0 || !pw) return fail(e, DLM_ERR_ARG, "cloud0 and pw are required: the particles carry their own variances");
+  if (!fmean) return fail(e, DLM_ERR_ARG, "fmean is required");
+  if (fc->var_kind == DLM_FC_IG_SCALE && !shapes) return fail(e, DLM_ERR_ARG, "DLM_FC_IG_SCALE needs shapes (the InverseGamma shapes of the d + 1 components)");
+  if (shapes_stride != 0 && shapes_stride < (int64_t)d + 1) return fail(e, DLM_ERR_ARG, "shapes_stride must be 0 or >= d + 1");
+  if (pv && fc->var_kind != DLM_FC_VAR && (family == DLM_OBS_NEGBIN || family == DLM_OBS_ZIP))
+    return fail(e, DLM_ERR_ARG, "pv of DLM_OBS_NEGBIN and DLM_OBS_ZIP is no variance (a log size, a logit): DLM_FC_VAR only");
+  if (!pv && !params->V) return fail(e, DLM_ERR_ARG, "pv == NULL needs params->V");
+  if (!pv && params->v_tstride) return fail(e, DLM_ERR_ARG, "the learned forecast takes a time-invariant V (v_tstride = 0)");
+  if (fc->n_ranks < 0 || fc->n_ranks > 8) return fail(e, DLM_ERR_ARG, "n_ranks: 0 .. 8 order statistics per time");
+  if (fc->n_ranks && (!ranks || !fquant)) return fail(e, DLM_ERR_ARG, "n_ranks > 0 needs ranks and fquant");
+  for (int j = 0; j < fc->n_ranks; ++j)
+    if (ranks[j] < 0 || ranks[j] >= P) return fail(e, DLM_ERR_ARG, "a rank must satisfy 0 <= rank < n_particles");
+  if (fc->slot_offset < 0) return fail(e, DLM_ERR_ARG, "slot_offset must be >= 0");
+  if (family == DLM_OBS_STUDENTT && !obs_param) return fail(e, DLM_ERR_ARG, "DLM_OBS_STUDENTT needs obs_param (the degrees of freedom of every series)");
+  if (model->p != 1) return fail(e, DLM_ERR_UNSUPPORTED, "the learned forecast takes a univariate observation (p = 1): every Dglm family reads y(0) and V(0,0)");
+  if (d > dlm::DLM_PF_MAX_D) return fail(e, DLM_ERR_UNSUPPORTED, "the learned forecast takes d <= 16");
+  if (P < 64 || P > dlm::DLM_PF_MAX_P || P % 64 != 0) return fail(e, DLM_ERR_UNSUPPORTED, "n_particles must be a multiple of 64 with 64 <= n_particles <= 1024 (one wavefront per series, whole slots of particles)");
+  if (T > dlm::DLM_PF_MAX_T || fc->slot_offset > (int64_t)dlm::DLM_PF_MAX_T - T)
+    return fail(e, DLM_ERR_UNSUPPORTED, "slot_offset + T must stay below 2^21 - 1 (the Philox counter's slot field)");
+  HIP_TRY(e, hipSetDevice(e->device));
+  const size_t lds = dlm::pf_forecast_learned_lds_bytes(d, P), have = dlm::lds_limit();
+  if (have && lds > have) return fail(e, DLM_ERR_UNSUPPORTED, "d and n_particles need more LDS than a workgroup of this device gets: (2 d + 3.5) n_particles doubles");
+  dlm::PfForecastLearnedArgs a{};
+  const size_t n = N, t = T, dd = d, np = P;
+  Stager st(e, opts->mem == DLM_MEM_HOST);
+  st.in(&a.F, model->F, (model->f_stride ? t : 1) * dd);
+  st.in(&a.G, model->G, (size_t)model->n_g * dd * dd);
+  st.in(&a.g_index, (const int*)model->g_index, model->g_index ? t : 0);
+  st.in(&a.dt, model->dt, model->dt ? t : 0);
+  st.in(&a.V, pv ? nullptr : params->V, params->v_stride ? (n - 1) * (size_t)params->v_stride + 1 : 1);
+  st.in(&a.obs_param, obs_param, obs_param ? n : 0);
+  st.in(&a.cloud0, cloud0, n * dd * np);
+  st.in(&a.weights0, weights0, weights0 ? n * np : 0);
+  st.in(&a.pw, pw, n * dd * np);
+  st.in(&a.pv, pv, pv ? n * np : 0);
+  const bool ig = fc->var_kind == DLM_FC_IG_SCALE;
+  st.in(&a.shapes, ig ? shapes : nullptr, shapes_stride ? (n - 1) * (size_t)shapes_stride + dd + 1 : dd + 1);
+  st.out(&a.fmean, fmean, n * t);
+  st.out(&a.fquant, fc->n_ranks ? fquant : nullptr, n * t * (size_t)fc->n_ranks);
+  st.out(&a.draws, draws, draws ? n * t * np : 0);
+  st.out(&a.mean, mean, mean ? n * t * dd : 0);
+  st.out(&a.cloud, cloud, cloud ? n * dd * np : 0);
+  st.out(&a.var_w, var_w, var_w ? n * dd * np : 0);
+  st.out(&a.var_v, var_v, var_v ? n * np : 0);
+  st.zeroed_out(&a.status, (int*)status, status ? n : 0);
+  a.d = d; a.T = T; a.N = N; a.P = P;
+  a.family = family; a.var_kind = fc->var_kind;
+  a.f_stride = model->f_stride; a.n_g = model->n_g; a.v_stride = params->v_stride; a.shapes_stride = shapes_stride;
+  a.rs = draw_stream(opts, iteration);
+  a.slot_offset = (int)fc->slot_offset;
+  a.n_ranks = fc->n_ranks;
+  for (int j = 0; j < fc->n_ranks; ++j) a.ranks[j] = ranks[j];   // a host array whatever opts->mem: checked above, passed by value
+  if ((rc = st.commit())) return rc;
+  e->variant = "pf-forecast-learned-wave";
+  HIP_TRY(e, dlm::launch_pf_forecast_learned(a, e->stream));
+  return st.finish(opts->flags & DLM_OPT_ASYNC);
+}
+
+int dlm_rb_state_draw(dlm_engine* e, int32_t d, int32_t N, int32_t P, const double* means, const double* covs, int64_t slot,
+                      uint64_t iteration, const dlm_options* opts, double* cloud, int32_t* status) {
+  if (!e) return DLM_ERR_ARG;
+  int rc;
+  if ((rc = check_opts(e, opts))) return rc;
+  if (d < 1 || N < 1) return fail(e, DLM_ERR_ARG, "d, N must be >= 1");
+  if (!means || !covs || !cloud) return fail(e, DLM_ERR_ARG, "means, covs and cloud are required");
+  if (slot < 0 || slot > (int64_t)dlm::DLM_SLOT_TOP) return fail(e, DLM_ERR_ARG, "slot must satisfy 0 <= slot <= 2^21 - 1 (the Philox counter's slot field)");
+  if (d > dlm::DLM_PF_MAX_D) return fail(e, DLM_ERR_UNSUPPORTED, "the state draw takes d <= 16");
+  if (P < 64 || P > dlm::DLM_PF_MAX_P || P % 64 != 0) return fail(e, DLM_ERR_UNSUPPORTED, "n_particles must be a multiple of 64 with 64 <= n_particles <= 1024 (one wavefront per series, whole slots of particles)");
+  HIP_TRY(e, hipSetDevice(e->device));
+  dlm::RbStateDrawArgs a{};
+  const size_t n = N, dd = d, np = P;
+  Stager st(e, opts->mem == DLM_MEM_HOST);
+  st.in(&a.means, means, n * dd * np);
+  st.in(&a.covs, covs, n * (dd * (dd + 1) / 2) * np);
+  st.out(&a.cloud, cloud, n * dd * np);
+  st.zeroed_out(&a.status, (int*)status, status ? n : 0);
+  a.d = d; a.N = N; a.P = P;
+  a.rs = draw_stream(opts, iteration);
+  a.slot = (unsigned)slot;
+  if ((rc = st.commit())) return rc;
+  e->variant = "rb-state-draw";
+  HIP_TRY(e, dlm::launch_rb_state_draw(a, e->stream));
+  return st.finish(opts->flags & DLM_OPT_ASYNC);
+}
+
 int dlm_pg_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_params_desc* params, const dlm_pg_desc* pg,
                  const double* obs_param, const double* y, const double* ref, uint64_t iteration, const dlm_options* opts,
                  double* ll, double* path, double* stats, int32_t* path_index, double* clouds, int32_t* ancestors,

@@ -621,6 +621,48 @@ struct RbArgs {           // a struct of its own: the fields the host's shared s
 size_t rb_lds_bytes(int d, int P);   // the means [d][P], the covariances [d(d+1)/2][P], the log-variances [d + 1][P], the weights and their running sums [2][P], one slot of predicted covariances [d(d+1)/2][64], G^T F [d], the step's mean [d], h s [d + 1], the ancestors
 hipError_t launch_rb(const RbArgs& a, hipStream_t s);
 
+// ---- posterior-predictive forecast from the cloud of a LEARNING filter, whose particles carry their own variances (dlm_storvik_batch's scales,
+// dlm_lw_batch's and dlm_rb_batch's psi), dlm_pf_forecast_learned.hip.  k_pf_forecast's layout and step with a diagonal state noise s_k,i and an
+// observation scale v_i per particle; nothing is observed, weighted or resampled after the entry.  T is the number H of forecast steps
+struct PfForecastLearnedArgs {
+  int d, T, N, P;         // P particles, a multiple of 64
+  int family, var_kind;   // DLM_OBS_*; DLM_FC_VAR, DLM_FC_LOGVAR or DLM_FC_IG_SCALE: what the rows of pw and pv hold
+  const double* F; long long f_stride;   // F_t = F + t * f_stride (d doubles, p = 1)
+  const double* G; int n_g; const int* g_index; const double* dt;
+  const double* V; long long v_stride;   // v = V[n * v_stride] for every particle, read without pv only
+  const double* obs_param;   // [N], nullable: nu of DLM_OBS_STUDENTT
+  DrawStream rs;
+  int slot_offset;        // step h draws from the Philox slot slot_offset + h
+  int n_ranks; int ranks[8];   // 0 <= ranks[j] < P
+  const double* cloud0;   // [N][d][P]
+  const double* weights0; // [N][P], nullable: equal weights
+  const double* pw;       // [N][d][P] the rows of the state variances
+  const double* pv;       // [N][P], nullable: the row of the observation scale
+  const double* shapes; long long shapes_stride;   // [d + 1] at n * shapes_stride, DLM_FC_IG_SCALE only (entry d is read with pv only)
+  double* fmean;          // [N][T]
+  double* fquant;         // [N][T][n_ranks], nullable with n_ranks = 0
+  double* draws;          // [N][T][P], nullable
+  double* mean;           // [N][T][d], nullable
+  double* cloud;          // [N][d][P], nullable
+  double* var_w;          // [N][d][P], nullable: the variances the steps used
+  double* var_v;          // [N][P], nullable
+  int* status;            // [N], nullable (zeroed by the caller)
+};
+size_t pf_forecast_learned_lds_bytes(int d, int P);   // the cloud and the standard deviations of the state noise [2 d][P], the observation scale, the weights and the row of the draws [3][P], the ancestors
+hipError_t launch_pf_forecast_learned(const PfForecastLearnedArgs& a, hipStream_t s);
+
+// ---- a state per particle from the Kalman moments dlm_rb_batch leaves: x_i = m_i + chol(C_i) z_i, dlm_pf_forecast_learned.hip ----
+struct RbStateDrawArgs {
+  int d, N, P;
+  const double* means;    // [N][d][P]
+  const double* covs;     // [N][d(d+1)/2][P], the lower triangles by rows
+  DrawStream rs;
+  unsigned slot;
+  double* cloud;          // [N][d][P]
+  int* status;            // [N], nullable (zeroed by the caller)
+};
+hipError_t launch_rb_state_draw(const RbStateDrawArgs& a, hipStream_t s);   // no dynamic LDS: a particle's factor lives in its thread's registers
+
 // ---- Particle Gibbs: conditional SMC with ancestor sampling, one draw of the state path x_{0:T} | y, V, W of a DGLM (Andrieu, Doucet & Holenstein
 // 2010; Lindsten, Jordan & Schoen 2014; what ParticleGibbs.scala aims at), dlm_pg.hip ----
 // A struct of its own: the fields the host's shared staging fills keep PfCommonArgs' names (n0 and literal are staged and not read).  A LAUNCH serves

@@ -1,5 +1,6 @@
 // Draws of the six observation models of a DGLM (the `observation` closures of Dglm.scala:46-175): pf_obs_draw is the sampling counterpart of
-// dlm_pf_common.h's pf_logdens, with its parameterisation.  Used by dlm_pf_forecast.hip's k_pf_forecast alone: the five filtering kernels
+// dlm_pf_common.h's pf_logdens, with its parameterisation.  Used by the two forecast kernels alone (dlm_pf_forecast.hip's k_pf_forecast,
+// dlm_pf_forecast_learned.hip's k_pf_forecast_learned), with the sort of a step's draws at its end: the five filtering kernels
 // do not include this file, and dlm_pf_common.h is as it was.  tests/pff_restatement.py restates every function here operation for operation.
 //
 // Randomness: Philox under DLM_KEY_PF in the particle filter's counter layout (seed, series, iteration, slot, particle).  The particle
@@ -20,7 +21,9 @@
 // A rate that is not finite, negative or above PF_RATE_MAX = 1e15, a NegBin size that is not positive and finite and Beta parameters that are not
 // positive (Q41) give NaN: the kernel stops the series with DLM_ST_NONFINITE, as it does for any draw that is not finite.
 // pf_gamma_draw and pf_poisson_draw are ONE __noinline__ copy each, as pf_lgamma is: inlined at their call sites in the six
-// families they would be held in registers across the loop over the particles.
+// families they would be held in registers across the loop over the particles.  That is k_pf_forecast's trade, whose weighting loop is live beside
+// them.  k_pf_forecast_learned has no weighting and takes the bodies inlined (pf_obs_draw<true>): no call frames, so no scratch,
+// and fewer registers than with the calls.
 #pragma once
 #include "dlm_pf_common.h"
 
@@ -37,14 +40,15 @@ __device__ __forceinline__ void pf_site_rand(const PfDrawSite& s, unsigned block
   gibbs_rand(s.seed, s.series, s.iteration, s.slot, s.particle, which, u1, u2, DLM_KEY_PF | block);
 }
 
-// Gamma(a, 1) from the blocks base .. base + DLM_PF_GAMMA_ATTEMPTS
-__device__ __noinline__ double pf_gamma_draw(double a, unsigned base, PfDrawSite s) {
+// Gamma(a, 1) from the blocks base .. base + DLM_PF_GAMMA_ATTEMPTS: the body, and the ONE __noinline__ copy of it
+__device__ __forceinline__ double pf_gamma_draw_body(double a, unsigned base, const PfDrawSite& s) {
   return gamma_unit_from(a, DLM_PF_GAMMA_ATTEMPTS,
                          [&](unsigned attempt, unsigned which, double& u1, double& u2) { pf_site_rand(s, base + attempt, which, u1, u2); });
 }
+__device__ __noinline__ double pf_gamma_draw(double a, unsigned base, PfDrawSite s) { return pf_gamma_draw_body(a, base, s); }
 
-// Poisson(lam), exactly; NaN for a rate outside [0, PF_RATE_MAX]
-__device__ __noinline__ double pf_poisson_draw(double lam, PfDrawSite s) {
+// Poisson(lam), exactly; NaN for a rate outside [0, PF_RATE_MAX]: the body, and below it the ONE __noinline__ copy of it
+__device__ __forceinline__ double pf_poisson_draw_body(double lam, const PfDrawSite& s) {
   if (!(lam >= 0.0 && lam <= PF_RATE_MAX)) return __builtin_nan("");
   if (lam < PF_POISSON_PTRS_FROM) {
     double u1, u;
@@ -75,10 +79,19 @@ __device__ __noinline__ double pf_poisson_draw(double lam, PfDrawSite s) {
   }
   return floor(lam);
 }
+__device__ __noinline__ double pf_poisson_draw(double lam, PfDrawSite s) { return pf_poisson_draw_body(lam, s); }
 
-// one draw of y | eta, v (nu: the degrees of freedom of DLM_OBS_STUDENTT), pf_logdens's parameterisation
+// one draw of y | eta, v (nu: the degrees of freedom of DLM_OBS_STUDENTT), pf_logdens's parameterisation.  INLINE: the Gamma and Poisson draws
+// are inlined into the caller instead of called (k_pf_forecast_learned: a call's frame is scratch); the arithmetic is the same
+template <bool INLINE = false>
 __device__ __forceinline__ double pf_obs_draw(int family, double eta, double v, double nu, const PfDrawSite& s) {
   const double nan = __builtin_nan("");
+  auto pf_gamma_draw = [](double a, unsigned base, const PfDrawSite& at) {
+    if constexpr (INLINE) return pf_gamma_draw_body(a, base, at); else return dlm::pf_gamma_draw(a, base, at);
+  };
+  auto pf_poisson_draw = [](double lam, const PfDrawSite& at) {
+    if constexpr (INLINE) return pf_poisson_draw_body(lam, at); else return dlm::pf_poisson_draw(lam, at);
+  };
   switch (family) {
     case DLM_OBS_GAUSSIAN: {
       double u1, u2;
@@ -114,6 +127,37 @@ __device__ __forceinline__ double pf_obs_draw(int family, double eta, double v, 
       if (!(al > 0.0 && be > 0.0 && al < __builtin_inf() && be < __builtin_inf())) return nan;   // Q41
       const double ga = pf_gamma_draw(al, DLM_PF_BLOCK_GAMMA_A, s), gb = pf_gamma_draw(be, DLM_PF_BLOCK_GAMMA_B, s);
       return ga / (ga + gb);
+    }
+  }
+}
+
+// ---- the sort of a step's draws, in place in an LDS row (k_pf_forecast and k_pf_forecast_learned; described at the head of dlm_pf_forecast.hip) ----
+// compare-exchange of the sort: the smaller value to the smaller index; a partner among the virtual +inf is skipped
+__device__ __forceinline__ void fc_cmpx(double* v, int i, int l, int P) {
+  if (l < P) {
+    const double a = v[i], b = v[l];
+    if (a > b) { v[i] = b; v[l] = a; }
+  }
+}
+
+// v[0 .. P) ascending, P a multiple of 64 (any: P2 is the next power of two)
+__device__ __forceinline__ void fc_sort(double* v, int P, int lane) {
+  int P2 = 64;
+  while (P2 < P) P2 <<= 1;   // at most four doublings: P <= 1024
+  const int half = P2 >> 1;
+  for (int k = 2; k <= P2; k <<= 1) {
+    const int hk = k >> 1;
+    for (int t = lane; t < half; t += 64) {   // the mirror substep
+      const int blk = t / hk, off = t - blk * hk;
+      fc_cmpx(v, blk * k + off, blk * k + (k - 1 - off), P);
+    }
+    wave_sync();
+    for (int j = hk >> 1; j >= 1; j >>= 1) {
+      for (int t = lane; t < half; t += 64) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+        fc_cmpx(v, i, i | j, P);
+      }
+      wave_sync();
     }
   }
 }

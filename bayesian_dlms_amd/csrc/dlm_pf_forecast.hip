@@ -32,36 +32,6 @@ __device__ __forceinline__ void fc_normals(const DrawStream& rs, unsigned long l
   }
 }
 
-// compare-exchange of the sort: the smaller value to the smaller index; a partner among the virtual +inf is skipped
-__device__ __forceinline__ void fc_cmpx(double* v, int i, int l, int P) {
-  if (l < P) {
-    const double a = v[i], b = v[l];
-    if (a > b) { v[i] = b; v[l] = a; }
-  }
-}
-
-// v[0 .. P) ascending, P a multiple of 64 (any: P2 is the next power of two)
-__device__ __forceinline__ void fc_sort(double* v, int P, int lane) {
-  int P2 = 64;
-  while (P2 < P) P2 <<= 1;   // at most four doublings: P <= 1024
-  const int half = P2 >> 1;
-  for (int k = 2; k <= P2; k <<= 1) {
-    const int hk = k >> 1;
-    for (int t = lane; t < half; t += 64) {   // the mirror substep
-      const int blk = t / hk, off = t - blk * hk;
-      fc_cmpx(v, blk * k + off, blk * k + (k - 1 - off), P);
-    }
-    wave_sync();
-    for (int j = hk >> 1; j >= 1; j >>= 1) {
-      for (int t = lane; t < half; t += 64) {
-        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-        fc_cmpx(v, i, i | j, P);
-      }
-      wave_sync();
-    }
-  }
-}
-
 template <int D>
 __global__ __launch_bounds__(64, D <= 8 ? 2 : 1) void k_pf_forecast(PfForecastArgs a) {
   extern __shared__ double pf_lds[];

@@ -23,7 +23,7 @@ import numpy as np
 from . import _lib
 from .api import pack_observations
 from .dlm import Dlm, DlmParameters, MaterialisedModel, materialise
-from .engine import EngineError, check_pf_ranks, check_pf_shape, check_rb_lds, check_shrinkage
+from .engine import EngineError, check_pf_forecast_learned_lds, check_pf_ranks, check_pf_shape, check_rb_lds, check_shrinkage
 
 
 def logistic_function(upper: float, number):
@@ -203,6 +203,50 @@ class Dglm:
             res["draws"] = out["draws"]
         return res
 
+    @staticmethod
+    def forecast_learned(mod: "Dglm", cloud, var_w, var_v, times, p, eng, *, var_kind: int, shapes=None, weights=None, prob: float = 0.75,
+                         summary: str = "mean", time0=None, slot_offset: int = 0, seed: int = 0, iteration: int = 0,
+                         series_offset: int = 0, return_draws: bool = False):
+        """`forecast_particles` from the cloud of a LEARNING filter, whose particles carry their own variances (dlm_pf_forecast_learned):
+        cloud [N][d][n] (or [d][n]: one series), var_w [N][d][n] the rows of the state variances and var_v [N][n] the row of the observation
+        scale (None: every particle takes p.v), read by var_kind -- _lib.FC_VAR variances, _lib.FC_LOGVAR log-variances (the filters'
+        "psi"), _lib.FC_IG_SCALE the Storvik filter's "scales" with `shapes` [d+1] or [N][d+1] (V's last): every particle then draws its
+        variances ONCE and keeps them over the horizon.  weights [N][n]: the tuples are resampled once at entry.  times [H]: the forecast
+        times; a pure forecast -- there are no test-period observations in this call: to fold them in, run the filter over them first.  p:
+        only its V is read, and only without var_v.  prob, summary, time0, slot_offset as in forecast_particles.  Returns forecast_particles'
+        dict without "ll", plus "var_w" [N][d][n] and "var_v" [N][n]: the variances the steps used."""
+        if summary not in ("mean", "median"):
+            raise ValueError(f'summary: "mean" or "median", got {summary!r}')
+        if cloud is None or var_w is None:
+            raise EngineError("the forecast from a learning filter needs its cloud and the particles' variance rows var_w")
+        as_array = lambda a: a if a is None or hasattr(a, "data_ptr") else np.asarray(a, dtype=np.float64)
+        cloud, var_w, var_v, weights = as_array(cloud), as_array(var_w), as_array(var_v), as_array(weights)
+        if cloud.ndim == 2:
+            cloud, var_w = cloud[None], var_w[None]
+            var_v = var_v[None] if var_v is not None and var_v.ndim == 1 else var_v
+            weights = weights[None] if weights is not None and weights.ndim == 1 else weights
+        if cloud.ndim != 3:
+            raise EngineError(f"cloud must be [N][d][n] or [d][n], got the shape {tuple(cloud.shape)}")
+        n = int(cloud.shape[2])
+        times = np.asarray(times, dtype=np.float64).reshape(-1)
+        f0 = np.atleast_2d(np.asarray(mod.f(float(times[0])), dtype=np.float64))
+        check_pf_shape(f0.shape[0], f0.shape[1], n)
+        check_pf_forecast_learned_lds(f0.shape[0], n)
+        lo, med, up = Dglm.interval_ranks(n, prob)
+        ranks = check_pf_ranks((lo, up) if summary == "mean" else (lo, med, up), n)
+        mat = materialise_forecast(mod, times, time0)
+        params = p if isinstance(p, DlmParameters) else BatchedParameters.of(p, int(cloud.shape[0])).packed()
+        out = _numpy(eng.pf_forecast_learned(mat, params, cloud, var_w, var_v, family=mod.family, var_kind=var_kind, shapes=shapes,
+                                             weights=weights, ranks=ranks, slot_offset=slot_offset, obs_param=mod.nu, iteration=iteration,
+                                             seed=seed, series_offset=series_offset, want_draws=return_draws))
+        q = out["fquant"]
+        res = {"time": times, "lower": q[:, :, 0], "upper": q[:, :, -1], "state_mean": out["mean"], "cloud": out["cloud"],
+               "var_w": out["var_w"], "var_v": out["var_v"], "status": out["status"]}
+        res[summary] = out["fmean"] if summary == "mean" else q[:, :, 1]
+        if return_draws:
+            res["draws"] = out["draws"]
+        return res
+
     def simulate_regular(self, params: DlmParameters, n_steps: int, dt: float = 1.0, *, rng=None):
         """Dglm.simulateRegular (Dglm.scala:224-232) on the host: x_0 ~ N(m0, C0) at time 0, then n_steps steps of length dt.  Returns
         (times [n], y [n], x [n][d]).  (F is taken at the observation's time; the reference's `observation` evaluates f(1.0).)"""
@@ -366,6 +410,18 @@ def _prior_rows(prior_w, d, first, second, noun):
     return np.array([[getattr(q, first), getattr(q, second)] for q in pws], dtype=np.float64)
 
 
+def _forecast_from_filter(mod, filt, var_w, var_v, ys_train, times_test, p, eng, *, cloud=None, **kw):
+    """What the `forecast` of the three learning filters share: Dglm.forecast_learned from the filter's cloud (or `cloud`) and weights with
+    time0 = the last training time and slot_offset = len(ys_train), so that the forecast continues the filter's Philox slots; "filter": the
+    filter's own dict."""
+    times = _observations(ys_train)[0]
+    gmod = mod if isinstance(mod, Dglm) else Dglm.gaussian(mod)
+    out = Dglm.forecast_learned(gmod, filt["cloud"] if cloud is None else cloud, var_w, var_v, times_test, p, eng, weights=filt["weights"],
+                                time0=float(times[-1]), slot_offset=len(times), **kw)
+    out["filter"] = filt
+    return out
+
+
 class ParticleFilter:
     """ParticleFilter(n, n0, multinomialResample) (ParticleFilter.scala:26-71) on the engine: n particles, resampling when ESS < n0
     (negative: floor(n / 5), what ParticleFilter.likelihood passes)."""
@@ -437,6 +493,21 @@ class StorvikFilter:
             out["v_mean"] = np.where(out["shape_v"] > 1.0, out["scale_mean"][:, :, d] / (out["shape_v"] - 1.0), np.nan)
         return out
 
+    def forecast(self, mod: Dglm, ys_train, times_test, p: DlmParameters, prior_v, prior_w, eng, *, learn_v: Optional[bool] = None,
+                 seed: int = 0, iteration: int = 0, series_offset: int = 0, literal: bool = False, **kw):
+        """Filter the training period, then forecast the times times_test [H] from the filter's cloud, its weights and every particle's OWN
+        InverseGamma posterior -- "scales" with the final shapes shape_w[:, -1] and shape_v[:, -1] --, so that the band carries the
+        uncertainty of the variances (Dglm.forecast_learned with _lib.FC_IG_SCALE, time0 = the last training time and slot_offset =
+        len(ys_train)).  To fold in test-period observations, filter them too.  kw: prob, summary, return_draws.  Returns
+        forecast_learned's dict and "filter": the filter's own."""
+        filt = self.filter(mod, ys_train, p, prior_v, prior_w, eng, learn_v=learn_v, seed=seed, iteration=iteration,
+                           series_offset=series_offset, literal=literal)
+        d = filt["cloud"].shape[1]
+        learned = mod.family == _lib.OBS_GAUSSIAN if learn_v is None else bool(learn_v)          # (else V is p.v, and its shape is not read)
+        shapes = np.concatenate([filt["shape_w"][:, -1], (filt["shape_v"][:, -1] if learned else np.ones(len(filt["ll"])))[:, None]], axis=1)
+        return _forecast_from_filter(mod, filt, filt["scales"][:, :d], filt["scales"][:, d] if learned else None, ys_train, times_test, p, eng,
+                                     var_kind=_lib.FC_IG_SCALE, shapes=shapes, seed=seed, iteration=iteration, series_offset=series_offset, **kw)
+
 
 class LiuAndWestFilter:
     """LiuAndWestFilter(n, prior, a, n0) (LiuAndWest.scala:26-82; Liu & West 2001) on the engine (dlm_lw_batch): an auxiliary particle
@@ -466,6 +537,19 @@ class LiuAndWestFilter:
                             literal=literal, obs_param=mod.nu, iteration=iteration, seed=seed, series_offset=series_offset)
         return _lognormal_means(_numpy(out), d)
 
+    def forecast(self, mod: Dglm, ys_train, times_test, p: DlmParameters, prior_v, prior_w, eng, *, learn_v: Optional[bool] = None,
+                 seed: int = 0, iteration: int = 0, series_offset: int = 0, literal: bool = False, **kw):
+        """Filter the training period, then forecast the times times_test [H] from the filter's cloud, its weights and every particle's OWN
+        log-variances "psi" (Dglm.forecast_learned with _lib.FC_LOGVAR, time0 = the last training time and slot_offset = len(ys_train)):
+        the band carries the uncertainty of the variances.  To fold in test-period observations, filter them too.  kw: prob, summary,
+        return_draws.  Returns forecast_learned's dict and "filter": the filter's own."""
+        filt = self.filter(mod, ys_train, p, prior_v, prior_w, eng, learn_v=learn_v, seed=seed, iteration=iteration,
+                           series_offset=series_offset, literal=literal)
+        d = filt["cloud"].shape[1]
+        learned = mod.family in (_lib.OBS_GAUSSIAN, _lib.OBS_STUDENTT, _lib.OBS_BETA) if learn_v is None else bool(learn_v)   # (else V is p.v)
+        return _forecast_from_filter(mod, filt, filt["psi"][:, :d], filt["psi"][:, d] if learned else None, ys_train, times_test, p, eng,
+                                     var_kind=_lib.FC_LOGVAR, seed=seed, iteration=iteration, series_offset=series_offset, **kw)
+
 
 class AuxFilter:
     """AuxFilter(n) (AuxFilter.scala:12-66; Pitt & Shephard 1999) on the engine: the auxiliary particle filter for KNOWN parameters, which
@@ -481,13 +565,23 @@ class AuxFilter:
                literal: bool = False):
         """ys as ParticleFilter.filter takes them; p: one DlmParameters with a DIAGONAL W (ValueError otherwise).  Returns what
         LiuAndWestFilter.filter returns."""
+        return LiuAndWestFilter(self.n, 1.0, self.n0).filter(mod, ys, p, None, self._known(p), eng, learn_v=False, seed=seed, iteration=iteration,
+                                                             series_offset=series_offset, literal=literal)
+
+    def _known(self, p: DlmParameters):
+        """p.w as the Liu-West filter's known log-variances: Gaussian(log W_kk, 0) per component."""
         w = np.atleast_2d(np.asarray(p.w, dtype=np.float64))
         if np.any(w != np.diag(np.diag(w))):
             raise ValueError("AuxFilter takes a diagonal W: the kernel's state noise is independent by component")
         from .stochvol import Gaussian
-        prior_w = [Gaussian(float(np.log(v)), 0.0) for v in np.diag(w)]
-        return LiuAndWestFilter(self.n, 1.0, self.n0).filter(mod, ys, p, None, prior_w, eng, learn_v=False, seed=seed, iteration=iteration,
-                                                             series_offset=series_offset, literal=literal)
+        return [Gaussian(float(np.log(v)), 0.0) for v in np.diag(w)]
+
+    def forecast(self, mod: Dglm, ys_train, times_test, p: DlmParameters, eng, *, seed: int = 0, iteration: int = 0, series_offset: int = 0,
+                 literal: bool = False, **kw):
+        """Filter the training period, then forecast times_test [H] from the filter's cloud and weights: LiuAndWestFilter.forecast with the
+        known variances of p.  kw: prob, summary, return_draws."""
+        return LiuAndWestFilter(self.n, 1.0, self.n0).forecast(mod, ys_train, times_test, p, None, self._known(p), eng, learn_v=False, seed=seed,
+                                                               iteration=iteration, series_offset=series_offset, literal=literal, **kw)
 
     def likelihood(self, mod: Dglm, ys, p: DlmParameters, eng, **kw):
         """AuxFilter.likelihood(mod, ys, n)(p) (AuxFilter.scala:69-75): the log-likelihood estimate of every series."""
@@ -524,6 +618,23 @@ class RaoBlackwellFilter:
         out = eng.rb_filter(mat, p, y, pw, n_particles=self.n, a=self.a, prior_v=pv, learn_v=learn_v, n0=self.n0, literal=literal,
                             iteration=iteration, seed=seed, series_offset=series_offset)
         return _lognormal_means(_numpy(out), d)
+
+    def forecast(self, mod, ys_train, times_test, p: DlmParameters, prior_v, prior_w, eng, *, learn_v: bool = True, seed: int = 0,
+                 iteration: int = 0, series_offset: int = 0, literal: bool = False, **kw):
+        """Filter the training period, draw a state per particle from its Kalman moments (Engine.rb_state_draw: x_i = m_i + chol(C_i) z_i,
+        at the Philox slot len(ys_train)), then forecast times_test [H] from that cloud, the filter's weights and every particle's OWN
+        log-variances "psi" (Dglm.forecast_learned with _lib.FC_LOGVAR, time0 = the last training time, slot_offset = len(ys_train)).  To
+        fold in test-period observations, filter them too.  kw: prob, summary, return_draws.  Returns forecast_learned's dict, "filter":
+        the filter's own, and "cloud0" [N][d][n]: the drawn states."""
+        filt = self.filter(mod, ys_train, p, prior_v, prior_w, eng, learn_v=learn_v, seed=seed, iteration=iteration,
+                           series_offset=series_offset, literal=literal)
+        d, T = filt["means"].shape[1], len(_observations(ys_train)[0])
+        drawn = _numpy(eng.rb_state_draw(filt["means"], filt["covs"], slot=T, iteration=iteration, seed=seed, series_offset=series_offset))
+        out = _forecast_from_filter(mod, filt, filt["psi"][:, :d], filt["psi"][:, d] if learn_v else None, ys_train, times_test, p, eng,
+                                    cloud=drawn["cloud"], var_kind=_lib.FC_LOGVAR, seed=seed, iteration=iteration,
+                                    series_offset=series_offset, **kw)
+        out["cloud0"] = drawn["cloud"]
+        return out
 
 
 INIT_ITERATION = 0xFFFFFFFF   # the Philox iteration of Metropolis.dglm's evaluation of the initial parameters

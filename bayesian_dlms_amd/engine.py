@@ -138,6 +138,15 @@ def check_rb_lds(d: int, n_particles: int):
                           "d = 6: 512, d = 7: 384, d = 8: 320, d = 9: 256, d = 10: 192, d = 11 and 12: 128, d = 13 .. 16: 64)")
 
 
+def check_pf_forecast_learned_lds(d: int, n_particles: int):
+    """What dlm_pf_forecast_learned asks of (d, P) beyond check_pf_shape: every particle's state variances live in LDS beside the cloud."""
+    need = _lib.pf_forecast_learned_lds_bytes(d, n_particles)
+    if need > _lib.RB_LDS_BYTES:
+        raise EngineError(f"the forecast from a learning filter's cloud keeps every particle's variances in LDS: d = {d} with {n_particles} "
+                          f"particles needs {need} bytes of the {_lib.RB_LDS_BYTES} a workgroup gets ((2 d + 3.5) n_particles doubles: "
+                          "d = 16 with at most 512 particles, d <= 8 with 1024)")
+
+
 def _pf_shape(mat, n_particles, family):
     """(d, T, P) of a call of one of the three particle filters, after the checks of its shape and of its family."""
     P = int(n_particles)
@@ -783,6 +792,83 @@ class Engine:
                        covs=(want_covs, (N, d * (d + 1) // 2, P)), weights=(want_weights, (N, P)), psi=(want_psi, (N, d + 1, P)))
         desc = _lib.RbDesc(P, int(n0), 1 if literal else 0, 1 if learn_v else 0, float(a))
         self._call("dlm_rb_batch", be, flags, md, pd, desc, pvb, pv_stride, pwb, pw_stride, yb, int(iteration), op, *out.values())
+        return out
+
+    def pf_forecast_learned(self, mat, params, cloud, var_w, var_v=None, *, family, var_kind, shapes=None, weights=None, ranks=(),
+                            slot_offset=0, obs_param=None, iteration=0, seed=0, series_offset=0, flags=0, want_draws=False, want_mean=True,
+                            want_cloud=True, want_var=True):
+        """Posterior-predictive forecast from the cloud of a learning filter (dlm_pf_forecast_learned): `pf_forecast` with a diagonal state
+        noise and an observation scale PER PARTICLE.  cloud [N][d][P]; var_w [N][d][P] and var_v [N][P] (None: every particle takes
+        params' V) the particles' rows, read by var_kind: _lib.FC_VAR variances, _lib.FC_LOGVAR log-variances (`psi` of lw_filter and
+        rb_filter), _lib.FC_IG_SCALE the InverseGamma scales of storvik_filter with shapes [d+1] or [N][d+1] (V's last), from which every
+        particle draws its variances ONCE.  weights [N][P]: the cloud's weights (None: equal; given: the tuples are resampled once at
+        entry).  mat describes the H forecast steps as for pf_forecast; a pure forecast -- nothing is observed: to fold in test-period
+        observations, run the filter over them first.  params: V alone is read (without var_v).  ranks, slot_offset, obs_param as in
+        pf_forecast.  Returns {"fmean" [N][H], "fquant" [N][H][len(ranks)], "draws" [N][H][P], "mean" [N][H][d] the mean of the cloud,
+        "cloud" [N][d][P], "var_w" [N][d][P] and "var_v" [N][P] the variances the steps used, "status" [N]}; the optional ones are None
+        when not wanted.  A series with a status bit has NaN from the failing step on."""
+        if cloud is None or var_w is None:
+            raise EngineError("the forecast from a learning filter needs its cloud and the particles' variance rows var_w")
+        if len(cloud.shape) != 3:
+            raise EngineError(f"cloud must be [N][d][P], got the shape {tuple(cloud.shape)}")
+        N, P = int(cloud.shape[0]), int(cloud.shape[2])
+        d, T, P = _pf_shape(mat, P, family)
+        check_pf_forecast_learned_lds(d, P)
+        rk = check_pf_ranks(ranks, P)
+        if var_kind not in (_lib.FC_VAR, _lib.FC_LOGVAR, _lib.FC_IG_SCALE):
+            raise EngineError(f"var_kind must be one of _lib.FC_* (0..2), got {var_kind!r}")
+        if var_kind == _lib.FC_IG_SCALE and shapes is None:
+            raise EngineError("FC_IG_SCALE needs shapes: the InverseGamma shapes of the d + 1 components")
+        if var_v is not None and var_kind != _lib.FC_VAR and family in (_lib.OBS_NEGBIN, _lib.OBS_ZIP):
+            raise EngineError("var_v of OBS_NEGBIN and OBS_ZIP is no variance (a log size, a logit): FC_VAR only")
+        if family == _lib.OBS_STUDENTT and obs_param is None:
+            raise EngineError("OBS_STUDENTT needs obs_param: the degrees of freedom (a scalar or one per series)")
+        if not 0 <= int(slot_offset) <= _lib.PF_MAX_T - T:
+            raise EngineError(f"slot_offset + the number of steps must stay within {_lib.PF_MAX_T} (the Philox counter's slot field), got {slot_offset} + {T}")
+        be = self._backend(cloud)
+        cb, wb, pwb, pvb = be.put(cloud), be.put(weights), be.put(var_w), be.put(var_v)
+        for name, b, shape in (("cloud", cb, (N, d, P)), ("var_w", pwb, (N, d, P)), ("var_v", pvb, (N, P)), ("weights", wb, (N, P))):
+            if b is not None and tuple(b.shape) != shape:
+                raise EngineError(f"{name} must have the shape {shape}, got {tuple(b.shape)}")
+        ob = None
+        if obs_param is not None:
+            ob = be.put(np.full(N, float(obs_param)) if np.ndim(obs_param) == 0 else obs_param)
+            if tuple(ob.shape) != (N,):
+                raise EngineError(f"obs_param must be a scalar or [N] = {(N,)}, got {tuple(ob.shape)}")
+        sb, s_stride = None, 0
+        if var_kind == _lib.FC_IG_SCALE:
+            sh, s_stride = _strided(shapes, d + 1)
+            sb = be.put(sh)
+            if tuple(sb.shape) not in ((d + 1,), (N, d + 1)):
+                raise EngineError(f"shapes must be [d+1] = {(d + 1,)} or [N][d+1], got {tuple(sb.shape)}")
+        md, pd, op, keep = self.prepare(mat, params, N, be, flags, seed, series_offset)
+        if pd.v_tstride and var_v is None:
+            raise EngineError("the forecast from a learning filter takes a time-invariant V")
+        out = _outputs(be, N, fmean=(True, (N, T)), fquant=(bool(rk), (N, T, len(rk))), draws=(want_draws, (N, T, P)),
+                       mean=(want_mean, (N, T, d)), cloud=(want_cloud, (N, d, P)), var_w=(want_var, (N, d, P)), var_v=(want_var, (N, P)))
+        desc = _lib.PfForecastLearnedDesc(int(family), P, int(var_kind), len(rk), int(slot_offset))
+        rkc = (ctypes.c_int32 * len(rk))(*rk) if rk else None          # a host array whatever the backend: the call reads it before it returns
+        self._call("dlm_pf_forecast_learned", be, flags, md, pd, desc, ob, rkc, cb, wb, pwb, pvb, sb, s_stride, int(iteration), op,
+                   *out.values())
+        return out
+
+    def rb_state_draw(self, means, covs, *, slot, iteration=0, seed=0, series_offset=0, flags=0):
+        """A state per particle from the Kalman moments rb_filter leaves (dlm_rb_state_draw): x_i = m_i + chol(C_i) z_i from means
+        [N][d][P] and covs [N][d(d+1)/2][P] (the lower triangles by rows); the normals come from the Philox slot `slot` of the
+        Rao-Blackwellised filter's stream, in blocks of their own (the number of steps filtered is the natural slot).  Returns {"cloud"
+        [N][d][P], "status" [N]}; a series with a covariance that is not positive definite has DLM_ST_NOT_PD and NaN in its cloud."""
+        if len(means.shape) != 3:
+            raise EngineError(f"means must be [N][d][P], got the shape {tuple(means.shape)}")
+        N, d, P = (int(s) for s in means.shape)
+        check_pf_shape(d, 1, P)
+        if tuple(covs.shape) != (N, d * (d + 1) // 2, P):
+            raise EngineError(f"covs must be [N][d(d+1)/2][P] = {(N, d * (d + 1) // 2, P)}, got {tuple(covs.shape)}")
+        if not 0 <= int(slot) <= _lib.PF_MAX_T + 1:
+            raise EngineError(f"slot must satisfy 0 <= slot <= {_lib.PF_MAX_T + 1} (the Philox counter's slot field), got {slot}")
+        be = self._backend(means)
+        out = _outputs(be, N, cloud=(True, (N, d, P)))
+        self._call("dlm_rb_state_draw", be, flags, d, N, P, be.put(means), be.put(covs), int(slot), int(iteration),
+                   _options(be, flags, seed, series_offset), *out.values())
         return out
 
     def pg_sweep(self, mat, params, y, ref, *, family, n_particles, ancestor_sampling=True, obs_param=None, iteration=0, seed=0,

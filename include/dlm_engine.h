@@ -768,6 +768,71 @@ int dlm_rb_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_params_de
                  double* ess, double* psi_mean, double* psi_var, double* means, double* covs, double* weights, double* psi,
                  int32_t* status);
 
+/* Posterior-predictive forecast of a DGLM from the cloud of a LEARNING filter -- dlm_storvik_batch, dlm_lw_batch, and dlm_rb_batch after
+ * dlm_rb_state_draw below --, whose particles carry their own variances: dlm_pf_forecast_particles' step with a diagonal state noise
+ * w_k,i and an observation scale v_i PER PARTICLE, so that the band keeps the parameter uncertainty the filter was run to obtain.  A pure
+ * forecast: nothing is observed, weighted or resampled after the entry, and there is no likelihood; to fold in test-period observations, run
+ * the filter over them first and forecast from the cloud it leaves.  `model` describes the H = model->T forecast steps (dt[0] the gap from
+ * the time of the cloud) as for dlm_pf_forecast_particles; shapes and families as dlm_pf_batch (p = 1, d <= 16, P a multiple of 64 in
+ * 64 .. 1024).  LDS: (2 d + 3.5) P doubles (the cloud, the standard deviations of the state noise, the observation scale, the weights, the
+ * row of the draws, the ancestors), which d = 16 with P <= 512 and d <= 8 with P = 1024 are granted on a device with 160 KB per workgroup;
+ * more is DLM_ERR_UNSUPPORTED (d = 16, P = 1024), before any launch.  params: V alone is read, and only when pv == NULL (every particle
+ * takes v = V[n * v_stride], as the family takes it); W, m0 and C0 are never read.
+ * At entry: cloud0 [N][d][P]; the rows pw [N][d][P] of the state variances and pv [N][P] of the observation scale (nullable); weights0
+ * [N][P] (nullable: equal weights), non-negative with a positive finite sum, else DLM_ST_NONFINITE: ONE multinomial resampling of the
+ * whole tuple (x_i, pw_i, pv_i) with the draws dlm_pf_forecast_particles uses there.  Then the rows become variances by fc->var_kind:
+ *   DLM_FC_VAR       they are variances;
+ *   DLM_FC_LOGVAR    the variance is exp(row): the rows of `psi` of dlm_lw_batch and dlm_rb_batch;
+ *   DLM_FC_IG_SCALE  the rows are the InverseGamma scales of dlm_storvik_batch (`scales`), shapes [d + 1] (V's last, read with pv only) at
+ *                    n * shapes_stride (0: shared) their shapes: w_k,i = pw_k,i / Gamma(shape_k, 1), and v_i likewise, drawn ONCE per
+ *                    particle after the resampling and held for the whole horizon (the parameters are static).
+ * A variance that is not finite or is negative, a zero one under DLM_FC_IG_SCALE or in pv, or a shape that is not positive and finite
+ * gives DLM_ST_NOT_PD for that series alone (a zero DLM_FC_VAR / DLM_FC_LOGVAR row of pw is a known, noiseless component).  v of
+ * DLM_OBS_NEGBIN and DLM_OBS_ZIP is no variance (a log size, a logit) and of DLM_OBS_POISSON is not read: there it has to be finite only,
+ * and pv is taken under DLM_FC_VAR alone.
+ * Per step h (Philox slot fc->slot_offset + h):
+ *   1. dt_h != 0: x'_k,i = (G_h x_i)_k + sqrt(dt_h) (sqrt(w_k,i) z_k,i), z the state normals of dlm_pf_batch (DLM_KEY_PF, blocks 0..7): a cloud
+ *      whose particles all carry diag(W) and V reproduces dlm_pf_forecast_particles with that W and every y NaN bit for bit;
+ *   2. eta_i = F_h^T x'_i;  3. ytilde_i ~ family(eta_i, v_i), the exact samplers of dlm_pf_forecast_particles;
+ *   4. fmean[h], draws[h][i], the sort, fquant[h][j] = sorted[ranks[j]] and mean[h] (the equal-weight mean of the cloud) as there.
+ * ranks is a HOST array of fc->n_ranks entries whatever opts->mem is.  After the last step: cloud [N][d][P]; var_w [N][d][P] and var_v
+ * [N][P], the variances the steps used (written at entry: the Gamma draws can be seen); status [N].  Every output but fmean is nullable.
+ * A draw or rate that is not finite stops the series with DLM_ST_NONFINITE and NaN in fmean, fquant, draws and mean from that step on; a
+ * series stopped at entry has NaN in var_w and var_v too, and with DLM_ST_NOT_PD in cloud.  The batch completes, the neighbours untouched.
+ * DLM_ERR_ARG: cloud0, pw or fmean missing; shapes missing with DLM_FC_IG_SCALE; a var_kind that is none of the three; pv given for
+ * DLM_OBS_NEGBIN or DLM_OBS_ZIP under DLM_FC_LOGVAR or DLM_FC_IG_SCALE; params->V missing without pv; n_ranks outside 0..8, a rank outside
+ * [0, P), fquant missing with n_ranks > 0; slot_offset < 0; a time-varying V (v_tstride != 0) without pv; shapes_stride neither 0 nor >= d + 1;
+ * DLM_OBS_STUDENTT without obs_param.  DLM_ERR_UNSUPPORTED: the shapes above, slot_offset + H beyond 2^21 - 2.
+ * Draws: DLM_KEY_PF as dlm_pf_forecast_particles (counter (opts->seed, opts->series_offset + n, iteration, slot, particle)), the Gammas
+ * under DLM_KEY_FCL at the slot slot_offset (dlm_draws.h).  Results depend on neither N nor the neighbours nor how the batch is split.
+ * opts: mem, seed, series_offset, DLM_OPT_ASYNC.  Like dlm_pf_batch the call does not count as the "previous model-taking call" of
+ * DLM_OPT_MODEL_UNCHANGED. */
+enum { DLM_FC_VAR = 0, DLM_FC_LOGVAR = 1, DLM_FC_IG_SCALE = 2 };
+typedef struct {
+  int32_t family;       /* DLM_OBS_*                                                   */
+  int32_t n_particles;  /* P                                                           */
+  int32_t var_kind;     /* DLM_FC_*: what the rows of pw and pv hold                   */
+  int32_t n_ranks;      /* 0..8 order statistics per time                              */
+  int64_t slot_offset;  /* step h draws from the Philox slot slot_offset + h           */
+} dlm_pf_forecast_learned_desc;
+int dlm_pf_forecast_learned(dlm_engine* e, const dlm_model_desc* model, const dlm_params_desc* params, const dlm_pf_forecast_learned_desc* fc,
+                            const double* obs_param, const int32_t* ranks, const double* cloud0, const double* weights0, const double* pw,
+                            const double* pv, const double* shapes, int64_t shapes_stride, uint64_t iteration, const dlm_options* opts,
+                            double* fmean, double* fquant, double* draws, double* mean, double* cloud, double* var_w, double* var_v,
+                            int32_t* status);
+
+/* A state per particle from the Kalman moments dlm_rb_batch leaves: cloud [N][d][P], x_i = m_i + chol(C_i) z_i from means [N][d][P] and
+ * covs [N][d(d+1)/2][P] (the lower triangles by rows), so that dlm_pf_forecast_learned can forecast from the Rao-Blackwellised filter
+ * (with its weights and psi; the draw comes BEFORE that call's entry resampling -- either order is valid, this one keeps one entry form).
+ * One wavefront per series, a particle's factor in its thread's registers, the Cholesky in the order of operations of the particle
+ * filters' own; no LDS.  d <= 16, P a multiple of 64 in 64 .. 1024 (DLM_ERR_UNSUPPORTED otherwise); N, d >= 1, 0 <= slot <= 2^21 - 1,
+ * means, covs and cloud required (DLM_ERR_ARG).  A pivot that is not positive (NaN included) in any particle gives the WHOLE series
+ * DLM_ST_NOT_PD and NaN in its cloud; nothing else is touched.  Draws: DLM_KEY_RB, counter (opts->seed, opts->series_offset + n, iteration,
+ * slot, particle), blocks DLM_RB_BLOCK_STATE + q (dlm_draws.h), which no step of dlm_rb_batch uses: slot = the number of steps filtered
+ * is the natural choice.  opts: mem, seed, series_offset, DLM_OPT_ASYNC. */
+int dlm_rb_state_draw(dlm_engine* e, int32_t d, int32_t N, int32_t P, const double* means, const double* covs, int64_t slot,
+                      uint64_t iteration, const dlm_options* opts, double* cloud, int32_t* status);
+
 /* Particle Gibbs for a dynamic generalised linear model: ONE draw of the state path x_{0:T} | y, V, W of every series by conditional SMC
  * with ancestor sampling (Andrieu, Doucet & Holenstein 2010; Lindsten, Jordan & Schoen 2014).  It is what ParticleGibbs.scala aims at; the
  * reference's own step is not a valid kernel, so there is no literal mode.  The kernel leaves the law of

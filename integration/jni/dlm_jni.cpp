@@ -448,6 +448,38 @@ JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_rbFilter(JNIEnv* 
                                      ptr<const double>(y), static_cast<uint64_t>(iteration), &d.o, ptr<double>(ll), ptr<double>(mean), ptr<double>(cov), ptr<double>(ess), ptr<double>(psiMean),
                                      ptr<double>(psiVar), ptr<double>(means), ptr<double>(covs), ptr<double>(weights), ptr<double>(psi), ptr<int32_t>(status)));
 }
+// ---- posterior-predictive forecast from the cloud of a learning filter (storvikFilter's cloud / weights / scales, lwFilter's and -- after rbStateDraw -- rbFilter's cloud / weights / psi): particleForecast
+// with a diagonal state noise pw [N][d][nParticles] and an observation scale pv [N][nParticles] (0: params' V) per particle, read by varKind (0 variances, 1 log-variances, 2 InverseGamma scales with
+// shapes [d+1] at a stride of shapesStride doubles, 0: shared).  A pure forecast: model describes the H steps, there is no y.  dlm_pf_forecast_learned_desc crosses as scalars; ranks as in particleForecast;
+// every output but fmean is optional (0).
+JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_particleForecastLearned(JNIEnv* env, jobject, jlong h, jlongArray model, jlongArray params, jlongArray opts, jint family, jint nParticles,
+                                                                                       jint varKind, jlong slotOffset, jlongArray ranks, jlong obsParam, jlong cloud0, jlong weights0, jlong pw, jlong pv,
+                                                                                       jlong shapes, jlong shapesStride, jlong iteration, jlong fmean, jlong fquant, jlong draws, jlong mean, jlong cloud,
+                                                                                       jlong varW, jlong varV, jlong status) {
+  Desc d;
+  if (!read_desc(env, model, params, opts, d)) return;
+  const jsize nRanks = ranks ? env->GetArrayLength(ranks) : 0;
+  if (nRanks > 8) { throw_arg(env, "particleForecastLearned: at most 8 ranks"); return; }
+  jlong rk[8] = {0};
+  int32_t rk32[8] = {0};
+  if (nRanks) env->GetLongArrayRegion(ranks, 0, nRanks, rk);
+  for (jsize j = 0; j < nRanks; ++j) {
+    if (rk[j] < 0 || rk[j] >= nParticles) { throw_arg(env, "particleForecastLearned: a rank must satisfy 0 <= rank < nParticles"); return; }
+    rk32[j] = static_cast<int32_t>(rk[j]);
+  }
+  const dlm_pf_forecast_learned_desc fc{family, nParticles, varKind, static_cast<int32_t>(nRanks), static_cast<int64_t>(slotOffset)};
+  throw_if(env, eng(h), dlm_pf_forecast_learned(eng(h), &d.m, &d.q, &fc, ptr<const double>(obsParam), rk32, ptr<const double>(cloud0), ptr<const double>(weights0), ptr<const double>(pw),
+                                                ptr<const double>(pv), ptr<const double>(shapes), static_cast<int64_t>(shapesStride), static_cast<uint64_t>(iteration), &d.o, ptr<double>(fmean),
+                                                ptr<double>(fquant), ptr<double>(draws), ptr<double>(mean), ptr<double>(cloud), ptr<double>(varW), ptr<double>(varV), ptr<int32_t>(status)));
+}
+// ---- a state per particle from the Kalman moments rbFilter leaves: cloud [N][d][nParticles], x_i = m_i + chol(C_i) z_i, the normals from the Philox slot `slot` of the filter's stream
+JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_rbStateDraw(JNIEnv* env, jobject, jlong h, jint d, jint n, jint nParticles, jlong means, jlong covs, jlong slot, jlong iteration,
+                                                                           jlongArray opts, jlong cloud, jlong status) {
+  dlm_options o{};
+  if (!read_opts(env, opts, o)) return;
+  throw_if(env, eng(h), dlm_rb_state_draw(eng(h), d, n, nParticles, ptr<const double>(means), ptr<const double>(covs), static_cast<int64_t>(slot), static_cast<uint64_t>(iteration), &o,
+                                          ptr<double>(cloud), ptr<int32_t>(status)));
+}
 // ---- particle Gibbs for a dynamic generalised linear model (what ParticleGibbs.scala aims at): one conditional-SMC sweep with ancestor sampling per series, the new state path [N][T+1][d] given the path
 // `ref` (path may be ref), with the statistics [N][d+3] dinvgammaStep takes.  dlm_pg_desc crosses as scalars in its field order (workspaceCap = 0: the default cap); obsParam = 0: none; pathIndex
 // [N][T+1] int32, clouds [N][T+1][d][nParticles] with ancestors [N][T][nParticles] int32, stepWeights [N][T][nParticles] and status are optional (0).

@@ -96,6 +96,10 @@ final class Native private[gpu] () {
   @native def lwFilter(h: Long, model: Array[Long], params: Array[Long], opts: Array[Long], family: Int, nParticles: Int, n0: Int, literal: Int, learnV: Int, a: Double, priorV: Long, priorVStride: Long, priorW: Long, priorWStride: Long, obsParam: Long, y: Long, iteration: Long, ll: Long, mean: Long, ess: Long, psiMean: Long, psiVar: Long, cloud: Long, weights: Long, psi: Long, status: Long): Unit
   /** Rao-Blackwellised filter of a Gaussian DLM (RaoBlackwellFilter): the Liu-West filter whose particles carry the Kalman mean and covariance of the state given their own log-variances instead of a drawn state; priors, strides, a and n0 as lwFilter; literal = 1: Q50, Q57 and Q58.  ll [N]; mean [N][T][d], cov [N][T][d][d] (the mixture covariance), ess [N][T], psiMean, psiVar [N][T][d+1], means [N][d][nParticles], covs [N][d(d+1)/2][nParticles] (lower triangles by rows), weights [N][nParticles], psi [N][d+1][nParticles] and status [N] are optional (0) */
   @native def rbFilter(h: Long, model: Array[Long], params: Array[Long], opts: Array[Long], nParticles: Int, n0: Int, literal: Int, learnV: Int, a: Double, priorV: Long, priorVStride: Long, priorW: Long, priorWStride: Long, y: Long, iteration: Long, ll: Long, mean: Long, cov: Long, ess: Long, psiMean: Long, psiVar: Long, means: Long, covs: Long, weights: Long, psi: Long, status: Long): Unit
+  /** Posterior-predictive forecast from the cloud of a learning filter (storvikFilter's cloud / weights / scales; lwFilter's and, after rbStateDraw, rbFilter's cloud / weights / psi): particleForecast with a diagonal state noise pw [N][d][nParticles] and an observation scale pv [N][nParticles] (0: params' V) per particle, read by varKind (0 variances, 1 log-variances, 2 InverseGamma scales with shapes [d+1] at shapesStride doubles, 0: shared -- every particle draws its variances once).  A pure forecast: model describes the H steps; to fold in test-period observations, filter them first.  Every output but fmean is optional (0). */
+  @native def particleForecastLearned(h: Long, model: Array[Long], params: Array[Long], opts: Array[Long], family: Int, nParticles: Int, varKind: Int, slotOffset: Long, ranks: Array[Long], obsParam: Long, cloud0: Long, weights0: Long, pw: Long, pv: Long, shapes: Long, shapesStride: Long, iteration: Long, fmean: Long, fquant: Long, draws: Long, mean: Long, cloud: Long, varW: Long, varV: Long, status: Long): Unit
+  /** A state per particle from the Kalman moments rbFilter leaves: cloud [N][d][nParticles], x_i = m_i + chol(C_i) z_i, the normals from the Philox slot `slot` of the filter's stream (the number of steps filtered). */
+  @native def rbStateDraw(h: Long, d: Int, n: Int, nParticles: Int, means: Long, covs: Long, slot: Long, iteration: Long, opts: Array[Long], cloud: Long, status: Long): Unit
   /** Particle Gibbs for a DGLM (what ParticleGibbs aims at; its own step is not a valid kernel): one conditional-SMC sweep with ancestor sampling per series -- the new state path [N][T+1][d] given the path `ref` (path may be ref) and the statistics [N][d+3] dinvgammaStep takes; workspaceCap = 0: the default cap on the engine workspace of a launch; obsParam = 0: none; pathIndex, clouds with ancestors, stepWeights and status are optional (0). */
   @native def pgSweep(h: Long, model: Array[Long], params: Array[Long], opts: Array[Long], family: Int, nParticles: Int, ancestorSampling: Int, workspaceCap: Long, obsParam: Long, y: Long, ref: Long, iteration: Long, ll: Long, path: Long, stats: Long, pathIndex: Long, clouds: Long, ancestors: Long, stepWeights: Long, status: Long): Unit
   @native def statsPool(h: Long, stats: Long, n: Int, l: Int, pooled: Long, opts: Array[Long]): Unit
