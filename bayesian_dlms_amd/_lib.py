@@ -44,6 +44,9 @@ OBS_GAUSSIAN, OBS_POISSON, OBS_NEGBIN, OBS_ZIP, OBS_STUDENTT, OBS_BETA = range(6
 PF_MAX_D, PF_MIN_PARTICLES, PF_MAX_PARTICLES = 16, 64, 1024
 PF_MAX_T = 0x1FFFFE           # DLM_PF_MAX_T: the Philox counter's slot field
 PF_FORECAST_MAX_RANKS = 8     # dlm_pf_forecast_desc.n_ranks
+# dlm_resample_desc.scheme: the ancestor step of the particle filter's resampling (dlm_pf_resampled)
+RESAMPLE_MULTINOMIAL, RESAMPLE_STRATIFIED, RESAMPLE_SYSTEMATIC, RESAMPLE_METROPOLIS = range(4)
+PF_MAX_MH_STEPS = 64          # DLM_PF_MAX_MH_STEPS: dlm_resample_desc.mh_steps under RESAMPLE_METROPOLIS
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int32)
@@ -101,6 +104,12 @@ class PfDesc(ctypes.Structure):
     """dlm_pf_desc: the observation family (OBS_*), the number of particles (a multiple of 64, 64..1024), n0 (resample when ESS < n0;
     negative: floor(P / 5) as ParticleFilter.likelihood) and literal = 1: the reference's arithmetic (Q37-Q39)."""
     _fields_ = [("family", ctypes.c_int32), ("n_particles", ctypes.c_int32), ("n0", ctypes.c_int32), ("literal", ctypes.c_int32)]
+
+
+class ResampleDesc(ctypes.Structure):
+    """dlm_resample_desc: the scheme (RESAMPLE_*) and the steps of a Metropolis chain, 1..PF_MAX_MH_STEPS under RESAMPLE_METROPOLIS and 0
+    under every other scheme."""
+    _fields_ = [("scheme", ctypes.c_int32), ("mh_steps", ctypes.c_int32)]
 
 
 class PfForecastDesc(ctypes.Structure):
@@ -213,6 +222,8 @@ SYMBOLS = [
     ("dlm_dlmfsv_variance_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, _OP, _V, _V]),
     ("dlm_dlmfsvsys_innovations_batch", ctypes.c_int, [_V, _MP, _V, _OP, _V, _V]),
     ("dlm_pf_batch", ctypes.c_int, [_V, _MP, _PP, ctypes.POINTER(PfDesc), _V, _V, ctypes.c_uint64, _OP, _V, _V, _V, _V, _V, _V]),
+    ("dlm_pf_resampled", ctypes.c_int, [_V, _MP, _PP, ctypes.POINTER(PfDesc), ctypes.POINTER(ResampleDesc), _V, _V, ctypes.c_uint64, _OP,
+                                        _V, _V, _V, _V, _V, _V]),
     # (ranks is a HOST array whatever opts->mem is: a typed pointer, not one of the data pointers Engine._call turns into addresses)
     ("dlm_pf_forecast_particles", ctypes.c_int, [_V, _MP, _PP, ctypes.POINTER(PfForecastDesc), _V, _ip, _V, _V, _V, ctypes.c_uint64, _OP,
                                              _V, _V, _V, _V, _V, _V, _V, _V]),

@@ -45,6 +45,12 @@ constexpr unsigned DLM_PF_POISSON_ATTEMPTS = 32u, DLM_PF_GAMMA_ATTEMPTS = 32u;
 constexpr unsigned DLM_PF_BLOCK_POISSON = 11u;
 constexpr unsigned DLM_PF_BLOCK_GAMMA_A = DLM_PF_BLOCK_POISSON + DLM_PF_POISSON_ATTEMPTS;       // 43 .. 75
 constexpr unsigned DLM_PF_BLOCK_GAMMA_B = DLM_PF_BLOCK_GAMMA_A + DLM_PF_GAMMA_ATTEMPTS + 1u;     // 76 .. 108
+//                     dlm_pf_resampled with DLM_RESAMPLE_METROPOLIS draws under DLM_KEY_PF too: block DLM_PF_BLOCK_MH0 + s of (slot t, particle i)
+//                     gives step s < mh_steps <= DLM_PF_MAX_MH_STEPS of particle i's chain in the resampling of step t, u1 its acceptance uniform
+//                     and u2 its proposal.  The stratified scheme reads the u2 of DLM_PF_BLOCK_RESAMPLE of every particle as the multinomial one
+//                     does, the systematic scheme particle 0's alone
+constexpr unsigned DLM_PF_BLOCK_MH0 = 128u;
+constexpr int DLM_PF_MAX_MH_STEPS = 64;                                                         // 128 .. 191
 //   DLM_KEY_STORVIK   dlm_storvik_batch: comp and attempt field as DLM_KEY_PF (slot t or DLM_STORVIK_SLOT_INIT, the particle).  The low byte of the
 //                     key is the BLOCK: q < 8 the Box-Muller pair of the state components (2 q, 2 q + 1), DLM_STORVIK_BLOCK_RESAMPLE the resampling
 //                     uniform, DLM_STORVIK_BLOCK_GAMMA + k the Gamma of component k (k < d: the variance W_kk; k = d: V).  The second byte is the
@@ -133,6 +139,8 @@ static_assert(DLM_PF_BLOCK_RESAMPLE0 > DLM_PF_BLOCK_RESAMPLE && DLM_PF_BLOCK_OBS
               DLM_PF_BLOCK_GAMMA_A >= DLM_PF_BLOCK_POISSON + DLM_PF_POISSON_ATTEMPTS && DLM_PF_BLOCK_GAMMA_B > DLM_PF_BLOCK_GAMMA_A + DLM_PF_GAMMA_ATTEMPTS &&
               DLM_PF_BLOCK_GAMMA_B + DLM_PF_GAMMA_ATTEMPTS < 256u,
               "the forecast's blocks (entry resampling, the observation's first draw, the Poisson attempts, two Gammas' attempts and boosts) are distinct from the filter's and from one another and fit the key's low byte");
+static_assert(DLM_PF_BLOCK_MH0 > DLM_PF_BLOCK_GAMMA_B + DLM_PF_GAMMA_ATTEMPTS && DLM_PF_BLOCK_MH0 + (unsigned)DLM_PF_MAX_MH_STEPS <= 256u,
+              "the Metropolis resampling's blocks lie above every block of the filter and of the forecast and fit the key's low byte");
 constexpr unsigned DLM_STORVIK_SLOT_INIT = DLM_SLOT_TOP;   // dlm_storvik_batch, DLM_KEY_STORVIK: the initial cloud (the steps take the slots t < T <= DLM_PF_MAX_T)
 static_assert(DLM_STORVIK_BLOCK_GAMMA > DLM_STORVIK_BLOCK_RESAMPLE && (DLM_PF_MAX_D + 1) / 2 <= (int)DLM_STORVIK_BLOCK_RESAMPLE &&
               DLM_STORVIK_BLOCK_GAMMA + (unsigned)DLM_PF_MAX_D < 256u && DLM_STORVIK_GAMMA_ATTEMPTS < 256u,

@@ -1499,21 +1499,34 @@ int dlm_dlmfsvsys_innovations_batch(dlm_engine* e, const dlm_model_desc* model, 
 int dlm_pf_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_params_desc* params, const dlm_pf_desc* pf,
                  const double* obs_param, const double* y, uint64_t iteration, const dlm_options* opts, double* ll,
                  double* mean, double* ess, double* cloud, double* weights, int32_t* status) {
+  const dlm_resample_desc rs{DLM_RESAMPLE_MULTINOMIAL, 0};
+  return dlm_pf_resampled(e, model, params, pf, &rs, obs_param, y, iteration, opts, ll, mean, ess, cloud, weights, status);
+}
+
+int dlm_pf_resampled(dlm_engine* e, const dlm_model_desc* model, const dlm_params_desc* params, const dlm_pf_desc* pf,
+                           const dlm_resample_desc* resample, const double* obs_param, const double* y, uint64_t iteration,
+                           const dlm_options* opts, double* ll, double* mean, double* ess, double* cloud, double* weights, int32_t* status) {
   if (!e) return DLM_ERR_ARG;
-  if (!model || !params || !pf) return fail(e, DLM_ERR_ARG, "null descriptor");
+  if (!model || !params || !pf || !resample) return fail(e, DLM_ERR_ARG, "null descriptor");
   int rc;
   if ((rc = check_opts(e, opts))) return rc;
   const int d = model->d, P = pf->n_particles;
-  if ((rc = pf_check(e, model, params, pf->family, pf->literal, P, obs_param, y, ll, "the particle filter", true, true, [] { return DLM_OK; }))) return rc;
+  if ((rc = pf_check(e, model, params, pf->family, pf->literal, P, obs_param, y, ll, "the particle filter", true, true, [&] {
+        if (resample->scheme < DLM_RESAMPLE_MULTINOMIAL || resample->scheme > DLM_RESAMPLE_METROPOLIS) return fail(e, DLM_ERR_ARG, "scheme: one of DLM_RESAMPLE_*");
+        if (resample->scheme == DLM_RESAMPLE_METROPOLIS ? (resample->mh_steps < 1 || resample->mh_steps > dlm::DLM_PF_MAX_MH_STEPS) : resample->mh_steps != 0)
+          return fail(e, DLM_ERR_ARG, "mh_steps: 1 .. 64 under DLM_RESAMPLE_METROPOLIS, 0 under every other scheme");
+        return (int)DLM_OK;
+      }))) return rc;
   HIP_TRY(e, hipSetDevice(e->device));
   const size_t lds = dlm::pf_lds_bytes(d, P), have = dlm::lds_limit();
   if (have && lds > have) return fail(e, DLM_ERR_UNSUPPORTED, "d and n_particles need more LDS than a workgroup of this device gets: (d + 2.5) n_particles + d^2 doubles");
-  dlm::PfArgs a{};
+  dlm::PfSchemeArgs a{};
   const size_t n = model->N, dd = d;
   Stager st(e, opts->mem == DLM_MEM_HOST);
   pf_stage(st, a, model, params, pf->family, pf->literal, pf->n0, P, params->V, obs_param, y, opts, iteration, ll, mean, ess, cloud, weights, status);
   st.in(&a.W, params->W, params->w_stride ? (n - 1) * (size_t)params->w_stride + dd * dd : dd * dd);
   a.w_stride = params->w_stride;
+  a.resample = resample->scheme; a.mh_steps = resample->mh_steps;
   if ((rc = st.commit())) return rc;
   e->variant = "pf-wave";
   HIP_TRY(e, dlm::launch_pf(a, e->stream));

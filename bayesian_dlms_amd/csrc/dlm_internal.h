@@ -534,8 +534,12 @@ struct PfCommonArgs {
 struct PfArgs : PfCommonArgs {
   const double* W; long long w_stride;
 };
+// dlm_pf_resampled: k_pf's arguments and the scheme.  DLM_RESAMPLE_MULTINOMIAL launches k_pf on the PfArgs part, any other scheme k_pf_scheme
+struct PfSchemeArgs : PfArgs {
+  int resample, mh_steps;   // DLM_RESAMPLE_*; the steps of a Metropolis chain, 1 .. DLM_PF_MAX_MH_STEPS (0 under the other schemes)
+};
 size_t pf_lds_bytes(int d, int P);   // the cloud [d][P], the weights and their running sums [2][P], chol(W) and chol(C0)
-hipError_t launch_pf(const PfArgs& a, hipStream_t s);
+hipError_t launch_pf(const PfSchemeArgs& a, hipStream_t s);
 
 // ---- posterior-predictive forecast of a DGLM from a cloud (Dglm.forecastParticles, Dglm.scala:305-335), dlm_pf_forecast.hip -------------
 // k_pf's step plus one observation draw per particle and their order statistics.  T is the number H of forecast steps; ess is always null

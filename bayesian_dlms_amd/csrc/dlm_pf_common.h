@@ -1,7 +1,8 @@
 // What the particle kernels share (dlm_pf.hip: k_pf, dlm_storvik.hip: k_storvik, dlm_lw.hip: k_lw), each defined here ONCE: the Cholesky
 // factor of the initial cloud, the six observation densities of Dglm.scala:46-175, the weighted means over the particles, the normal of one
 // component (pf_normal), the initial cloud (pf_init_cloud), the two loops that turn log-weights into weights (pf_omega, pf_normalise), the
-// multinomial resampling (pf_resample: pf_running_sums, pf_search over pf_ancestor, pf_gather) and the results of a series (pf_results).
+// multinomial resampling (pf_resample: pf_running_sums, pf_search over pf_ancestor, pf_gather), the same with the ancestor step of another
+// scheme (pf_resample_by: pf_search_strata, pf_metropolis; k_pf's alone) and the results of a series (pf_results).
 // One wavefront per series, particle i = 64 s + lane, rows of P doubles in LDS; the orders of every sum are those of DESIGN.md 4.19.
 // Every helper is inlined into its kernel; k_pf and k_storvik use all of them, k_lw all but pf_init_cloud and pf_results, either of which
 // moves its register count at some d (profiles/r23_notes.md).  dlm_rb.hip's k_rb, which carries Kalman moments in place of a cloud, uses
@@ -198,6 +199,39 @@ __device__ __forceinline__ void pf_search(unsigned key_block, const DrawStream& 
   }
 }
 
+// the ancestors of a stratified (DLM_RESAMPLE_STRATIFIED) or systematic resampling: anc_i = pf_ancestor at ((i + u) / P) total, u the second
+// uniform of (slot, particle i) under key_block, or with `systematic` of (slot, particle 0) for every i -- every lane draws that one block,
+// which costs the wave one draw, and no other.  The targets ascend with i, so the ancestors do not decrease
+__device__ __forceinline__ void pf_search_strata(unsigned key_block, const DrawStream& rs, unsigned long long series, unsigned slot,
+                                                 const double* cum, double total, int* anc, int P, int lane, bool systematic) {
+  double u1, u0 = 0.0;
+  if (systematic) gibbs_rand(rs.seed, series, rs.iteration, slot, 0u, 0u, u1, u0, key_block);
+  for (int i = lane; i < P; i += 64) {
+    double u = u0;
+    if (!systematic) gibbs_rand(rs.seed, series, rs.iteration, slot, (unsigned)i, 0u, u1, u, key_block);
+    anc[i] = pf_ancestor(cum, P, (((double)i + u) / (double)P) * total);
+  }
+}
+
+// the ancestors of a Metropolis resampling (Murray, Lee & Jacob 2016) of b steps: particle i's chain starts at k = i; step s proposes
+// j = min(floor(u2 P), P - 1) and moves there when u1 W_k <= W_j, (u1, u2) the uniforms of (slot, particle i) under key_block0 + s; anc_i is
+// the last k.  No running sums and no division: a k of weight 0 always moves.  The reads wg[j] are scattered over the lanes' banks
+__device__ __forceinline__ void pf_metropolis(unsigned key_block0, const DrawStream& rs, unsigned long long series, unsigned slot,
+                                              const double* wg, int* anc, int P, int b, int lane) {
+  for (int i = lane; i < P; i += 64) {
+    int k = i;
+    double wk = wg[i];
+    for (int s = 0; s < b; ++s) {
+      double u1, u2;
+      gibbs_rand(rs.seed, series, rs.iteration, slot, (unsigned)i, 0u, u1, u2, key_block0 + (unsigned)s);
+      const int j = min((int)(u2 * (double)P), P - 1);   // (u2 >= 0: the conversion is the floor; u2 P can round up to P)
+      const double wj = wg[j];
+      if (u1 * wk <= wj) { k = j; wk = wj; }
+    }
+    anc[i] = k;
+  }
+}
+
 // the gather of a particle's tuple, the `rows` rows of P that start at x, by ancestor: row by row through `buf`
 __device__ __forceinline__ void pf_gather(double* x, int rows, double* buf, const int* anc, int P, int lane) {
   for (int k = 0; k < rows; ++k) {
@@ -214,6 +248,26 @@ __device__ __forceinline__ void pf_resample(unsigned key_block, const DrawStream
   const double total = pf_running_sums(wg, cum, P, lane);
   wave_sync();
   pf_search(key_block, rs, series, slot, cum, total, anc, P, lane);
+  wave_sync();
+  pf_gather(x, rows, cum, anc, P, lane);
+  for (int i = lane; i < P; i += 64) wg[i] = rP;
+  wave_sync();
+}
+
+// pf_resample with the ancestor step of a scheme OTHER than the multinomial one (`scheme`: DLM_RESAMPLE_STRATIFIED, _SYSTEMATIC or _METROPOLIS,
+// the same in every lane), dlm_pf_resampled's: the stratified and systematic searches read block key | block, the Metropolis chains the
+// blocks key | block_mh0 + s, s < mh_steps, and form no running sums.  The gather and the weights are pf_resample's
+__device__ __forceinline__ void pf_resample_by(int scheme, int mh_steps, unsigned key, unsigned block, unsigned block_mh0, const DrawStream& rs,
+                                               unsigned long long series, unsigned slot, double* x, int rows, double* wg, double rP,
+                                               double* cum, int* anc, int P, int lane) {
+  if (scheme == DLM_RESAMPLE_METROPOLIS) {
+    wave_sync();   // the chains read the other lanes' weights
+    pf_metropolis(key | block_mh0, rs, series, slot, wg, anc, P, mh_steps, lane);
+  } else {
+    const double total = pf_running_sums(wg, cum, P, lane);
+    wave_sync();
+    pf_search_strata(key | block, rs, series, slot, cum, total, anc, P, lane, scheme == DLM_RESAMPLE_SYSTEMATIC);
+  }
   wave_sync();
   pf_gather(x, rows, cum, anc, P, lane);
   for (int i = lane; i < P; i += 64) wg[i] = rP;

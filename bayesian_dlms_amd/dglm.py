@@ -23,7 +23,8 @@ import numpy as np
 from . import _lib
 from .api import pack_observations
 from .dlm import Dlm, DlmParameters, MaterialisedModel, materialise
-from .engine import EngineError, check_pf_forecast_learned_lds, check_pf_ranks, check_pf_shape, check_rb_lds, check_shrinkage
+from .engine import (EngineError, check_pf_forecast_learned_lds, check_pf_ranks, check_pf_resample, check_pf_shape, check_rb_lds,
+                     check_shrinkage)
 
 
 def logistic_function(upper: float, number):
@@ -422,13 +423,47 @@ def _forecast_from_filter(mod, filt, var_w, var_v, ys_train, times_test, p, eng,
     return out
 
 
-class ParticleFilter:
-    """ParticleFilter(n, n0, multinomialResample) (ParticleFilter.scala:26-71) on the engine: n particles, resampling when ESS < n0
-    (negative: floor(n / 5), what ParticleFilter.likelihood passes)."""
+@dataclass(frozen=True)
+class Resampling:
+    """The `resample` argument of the reference's ParticleFilter(n, n0, resample) (ParticleFilter.scala:26-30, 140-216), named instead of
+    passed as a function: Resampling.multinomial, .stratified, .systematic and .metropolis(b) (dlm_resample_desc, include/dlm_engine.h).
+    The first three keep the likelihood estimate unbiased; stratified and systematic resampling lower its variance, and systematic draws
+    one uniform per step.  metropolis(b) is the reference's metropolisResampling(b): b Metropolis steps per particle on the weights, BIASED
+    for every finite b -- fit for filtering, not for a likelihood a sampler accepts on."""
 
-    def __init__(self, n: int, n0: int = -1):
+    scheme: int = _lib.RESAMPLE_MULTINOMIAL
+    mh_steps: int = 0
+
+    def __post_init__(self):
+        check_pf_resample(self.scheme, self.mh_steps)
+
+    @staticmethod
+    def metropolis(b: int) -> "Resampling":
+        """ParticleFilter.metropolisResampling(b) (ParticleFilter.scala:159-181), 1 <= b <= _lib.PF_MAX_MH_STEPS."""
+        return Resampling(_lib.RESAMPLE_METROPOLIS, b)
+
+    @property
+    def unbiased(self) -> bool:
+        return self.scheme != _lib.RESAMPLE_METROPOLIS
+
+    @staticmethod
+    def of(resample) -> "Resampling":
+        """A Resampling as it is; one of _lib.RESAMPLE_* as the scheme without steps."""
+        return resample if isinstance(resample, Resampling) else Resampling(resample, 0)
+
+
+Resampling.multinomial = Resampling(_lib.RESAMPLE_MULTINOMIAL)
+Resampling.stratified = Resampling(_lib.RESAMPLE_STRATIFIED)
+Resampling.systematic = Resampling(_lib.RESAMPLE_SYSTEMATIC)
+
+
+class ParticleFilter:
+    """ParticleFilter(n, n0, resample) (ParticleFilter.scala:26-71) on the engine: n particles, resampling when ESS < n0 (negative:
+    floor(n / 5), what ParticleFilter.likelihood passes) by the scheme `resample`, a `Resampling` (default: multinomial)."""
+
+    def __init__(self, n: int, n0: int = -1, resample: Resampling = Resampling.multinomial):
         check_pf_shape(1, 1, int(n))
-        self.n, self.n0 = int(n), int(n0)
+        self.n, self.n0, self.resample = int(n), int(n0), Resampling.of(resample)
 
     def filter(self, mod: Dglm, ys, p, eng, *, seed: int = 0, iteration: int = 0, series_offset: int = 0, literal: bool = False):
         """ys: Vector[Data], a batch of them on one time grid, or (times, y).  p: one DlmParameters, one per series, or a
@@ -438,13 +473,16 @@ class ParticleFilter:
         times, y, d, mat = _filter_inputs(mod, ys, self.n)
         N, y, params = _bank(p, y)
         return _numpy(eng.particle_filter(mat, params, y, family=mod.family, n_particles=self.n, n0=self.n0, literal=literal, obs_param=mod.nu,
-                                          iteration=iteration, seed=seed, series_offset=series_offset))
+                                          iteration=iteration, seed=seed, series_offset=series_offset, resample=self.resample.scheme,
+                                          mh_steps=self.resample.mh_steps))
 
     def forecast(self, mod: Dglm, ys_train, ys_test, p, eng, *, seed: int = 0, iteration: int = 0, series_offset: int = 0,
                  literal: bool = False, **kw):
         """Filter the training period, then forecast the test period from the filter's cloud AND its weights (the end of the reference's
         worked examples: TrafficModel.scala:185-191, Temperature.scala:288, NoModel.scala:203): Dglm.forecast_particles with
         slot_offset = len(ys_train), so that the forecast continues the filter's Philox stream, and time0 = the last training time.
+        The training period is filtered with the filter's own resampling scheme; the forecast kernel's resampling (of the weighted entry
+        cloud, and after an observed test value) stays multinomial whatever the scheme.
         kw: prob, summary, return_draws.  Returns forecast_particles' dict and "filter": the filter's own."""
         filt = self.filter(mod, ys_train, p, eng, seed=seed, iteration=iteration, series_offset=series_offset, literal=literal)
         times = _observations(ys_train)[0]
@@ -454,9 +492,10 @@ class ParticleFilter:
         return out
 
     @staticmethod
-    def likelihood(mod: Dglm, ys, n: int, p, eng, **kw):
-        """ParticleFilter.likelihood(mod, ys, n)(p) (ParticleFilter.scala:78-85): the log-likelihood estimate(s) with n0 = floor(n / 5)."""
-        return ParticleFilter(n, -1).filter(mod, ys, p, eng, **kw)["ll"]
+    def likelihood(mod: Dglm, ys, n: int, p, eng, *, resample: Resampling = Resampling.multinomial, **kw):
+        """ParticleFilter.likelihood(mod, ys, n)(p) (ParticleFilter.scala:78-85): the log-likelihood estimate(s) with n0 = floor(n / 5),
+        resampling by `resample` (unbiased under every scheme but Resampling.metropolis)."""
+        return ParticleFilter(n, -1, resample).filter(mod, ys, p, eng, **kw)["ll"]
 
 
 class StorvikFilter:
@@ -677,7 +716,7 @@ class Metropolis:
 
     @staticmethod
     def dglm(mod: Dglm, ys, proposal, prior, init_p, n: int, eng, n_iter: int, seed: int = 0, *, n_chains: Optional[int] = None,
-             literal: bool = False, evaluate_init: bool = False):
+             literal: bool = False, evaluate_init: bool = False, resample: Resampling = Resampling.multinomial):
         """Metropolis.dglm (MetropolisHastings.scala:142-154): particle-marginal Metropolis, one chain per series.  ys: one series (every
         chain targets its posterior) or one per chain.  proposal(parameters, rng) -> parameters (symmetric: no Hastings term, as mStep);
         prior(parameters) -> [N] log densities; init_p one DlmParameters (with n_chains), a sequence of them or a BatchedParameters.
@@ -685,24 +724,35 @@ class Metropolis:
         `seed`), draws N uniforms and accepts where log u < (ll' + prior') - ll.  The host draws come from np.random.default_rng(seed), the
         proposal's first.  Like the reference the chains start at ll = -1e99: the first proposal is accepted.  evaluate_init=True
         starts them at the particle filter's estimate for init_p instead (Philox iteration INIT_ITERATION): chains that start in the
-        posterior then stay in it from the first iteration on.  Yields a MetropolisState per iteration."""
-        state = BatchedParameters.of(init_p, n_chains).copy()
-        N = state.n
-        rng = np.random.default_rng(seed)
-        ll = np.full(N, -1e99)
-        accepted = np.zeros(N, dtype=np.int64)
-        pf = ParticleFilter(n, -1)
-        if evaluate_init:
-            ll = pf.filter(mod, ys, state, eng, seed=seed, iteration=INIT_ITERATION, literal=literal)["ll"] + np.asarray(prior(state), dtype=np.float64)
-        for k in range(n_iter):
-            prop = proposal(state, rng)
-            prop_ll = pf.filter(mod, ys, prop, eng, seed=seed, iteration=k, literal=literal)["ll"] + np.asarray(prior(prop), dtype=np.float64)
-            with np.errstate(invalid="ignore"):
-                take = np.log(rng.uniform(size=N)) < prop_ll - ll
-            state = state.where(take, prop)
-            ll = np.where(take, prop_ll, ll)
-            accepted = accepted + take
-            yield MetropolisState(state.copy(), ll.copy(), accepted.copy())
+        posterior then stay in it from the first iteration on.  resample: the filter's resampling scheme, one of the three UNBIASED ones
+        (stratified and systematic lower the variance of the estimate, which is what governs the mixing); Resampling.metropolis(b) is
+        refused with an EngineError: its estimate is biased, and the chain would target another posterior.  Yields a MetropolisState per
+        iteration."""
+        resample = Resampling.of(resample)
+        if not resample.unbiased:
+            raise EngineError(f"Metropolis.dglm needs an unbiased likelihood estimate: Metropolis resampling with {resample.mh_steps} steps is "
+                              "biased for every finite number of steps, and particle-marginal Metropolis on a biased estimate targets the "
+                              "wrong posterior; use Resampling.multinomial, .stratified or .systematic")
+
+        def chain():          # (the refusal above is raised by the call, not by the first next())
+            state = BatchedParameters.of(init_p, n_chains).copy()
+            N = state.n
+            rng = np.random.default_rng(seed)
+            ll = np.full(N, -1e99)
+            accepted = np.zeros(N, dtype=np.int64)
+            pf = ParticleFilter(n, -1, resample)
+            if evaluate_init:
+                ll = pf.filter(mod, ys, state, eng, seed=seed, iteration=INIT_ITERATION, literal=literal)["ll"] + np.asarray(prior(state), dtype=np.float64)
+            for k in range(n_iter):
+                prop = proposal(state, rng)
+                prop_ll = pf.filter(mod, ys, prop, eng, seed=seed, iteration=k, literal=literal)["ll"] + np.asarray(prior(prop), dtype=np.float64)
+                with np.errstate(invalid="ignore"):
+                    take = np.log(rng.uniform(size=N)) < prop_ll - ll
+                state = state.where(take, prop)
+                ll = np.where(take, prop_ll, ll)
+                accepted = accepted + take
+                yield MetropolisState(state.copy(), ll.copy(), accepted.copy())
+        return chain()
 
 
 @dataclass

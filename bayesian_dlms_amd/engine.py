@@ -118,6 +118,21 @@ def check_pf_shape(d: int, p: int, n_particles: int):
                           f"(one wavefront per series, whole slots of particles), got {n_particles}")
 
 
+def check_pf_resample(resample, mh_steps):
+    """What dlm_pf_resampled asks of its resampling descriptor -> (scheme, mh_steps) as ints (the engine answers the same with
+    DLM_ERR_ARG)."""
+    if isinstance(resample, bool) or not isinstance(resample, (int, np.integer)) or not _lib.RESAMPLE_MULTINOMIAL <= resample <= _lib.RESAMPLE_METROPOLIS:
+        raise EngineError(f"resample must be one of _lib.RESAMPLE_* (0..3), got {resample!r}")
+    if isinstance(mh_steps, bool) or not isinstance(mh_steps, (int, np.integer)):
+        raise EngineError(f"mh_steps must be an integer, got {mh_steps!r}")
+    if resample == _lib.RESAMPLE_METROPOLIS:
+        if not 1 <= mh_steps <= _lib.PF_MAX_MH_STEPS:
+            raise EngineError(f"Metropolis resampling takes 1 <= mh_steps <= {_lib.PF_MAX_MH_STEPS}, got {mh_steps}")
+    elif mh_steps != 0:
+        raise EngineError(f"mh_steps belongs to RESAMPLE_METROPOLIS alone: it must be 0 under every other scheme, got {mh_steps}")
+    return int(resample), int(mh_steps)
+
+
 def check_pf_ranks(ranks, n_particles: int):
     """The order statistics dlm_pf_forecast_particles writes per time: at most PF_FORECAST_MAX_RANKS ranks, each in [0, n_particles) -> the ranks as
     a list of ints (the engine answers the same with DLM_ERR_ARG)."""
@@ -651,13 +666,17 @@ class Engine:
         return res
 
     def particle_filter(self, mat, params, y, *, family, n_particles, n0=-1, literal=False, obs_param=None, iteration=0, seed=0,
-                        series_offset=0, flags=0, want_mean=True, want_ess=True, want_cloud=True, want_weights=True):
-        """Bootstrap particle filter of a dynamic generalised linear model (dlm_pf_batch; ParticleFilter.step, ParticleFilter.scala:38-61) for
+                        series_offset=0, flags=0, want_mean=True, want_ess=True, want_cloud=True, want_weights=True,
+                        resample=_lib.RESAMPLE_MULTINOMIAL, mh_steps=0):
+        """Bootstrap particle filter of a dynamic generalised linear model (dlm_pf_batch, and dlm_pf_resampled under any scheme but the multinomial one; ParticleFilter.step, ParticleFilter.scala:38-61) for
         N series of P = n_particles particles: y [N][T] (NaN = missing), params one DlmParameters, N of them or the packed tuple of
         pack_params (per-series parameters: what a particle-marginal Metropolis step evaluates), family one of _lib.OBS_*, obs_param [N] or a
         scalar: the degrees of freedom of OBS_STUDENTT.  n0: resample when ESS < n0 (negative: floor(P / 5), ParticleFilter.likelihood).
-        literal=True: the reference's arithmetic (Q37-Q39).  Returns {"ll" [N], "mean" [N][T][d], "ess" [N][T], "cloud" [N][d][P],
+        literal=True: the reference's arithmetic (Q37-Q39).  resample: one of _lib.RESAMPLE_* (multinomial: dlm_pf_batch bit for bit;
+        stratified and systematic: unbiased too, with a smaller variance of ll; Metropolis with mh_steps = 1..PF_MAX_MH_STEPS chain steps:
+        BIASED, include/dlm_engine.h says how).  Returns {"ll" [N], "mean" [N][T][d], "ess" [N][T], "cloud" [N][d][P],
         "weights" [N][P], "status" [N]}; the optional ones are None when not wanted.  A series with a status bit has ll = -inf."""
+        scheme, b = check_pf_resample(resample, mh_steps)
         be = self._backend(y)
         d, T, P = _pf_shape(mat, n_particles, family)
         N, yb, ob = _pf_data(be, y, T, family, obs_param)
@@ -667,7 +686,10 @@ class Engine:
         out = _outputs(be, N, ll=(True, (N,)), mean=(want_mean, (N, T, d)), ess=(want_ess, (N, T)), cloud=(want_cloud, (N, d, P)),
                        weights=(want_weights, (N, P)))
         desc = _lib.PfDesc(int(family), P, int(n0), 1 if literal else 0)
-        self._call("dlm_pf_batch", be, flags, md, pd, desc, ob, yb, int(iteration), op, *out.values())
+        if scheme == _lib.RESAMPLE_MULTINOMIAL:          # (dlm_pf_batch IS dlm_pf_resampled with this scheme: one host path, the same bits)
+            self._call("dlm_pf_batch", be, flags, md, pd, desc, ob, yb, int(iteration), op, *out.values())
+        else:
+            self._call("dlm_pf_resampled", be, flags, md, pd, desc, _lib.ResampleDesc(scheme, b), ob, yb, int(iteration), op, *out.values())
         return out
 
     def pf_forecast(self, mat, params, y, *, family, n_particles, ranks=(), cloud=None, weights=None, slot_offset=0, literal=False,

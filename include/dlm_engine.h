@@ -586,6 +586,34 @@ int dlm_pf_batch(dlm_engine* e, const dlm_model_desc* model, const dlm_params_de
                  const double* obs_param, const double* y, uint64_t iteration, const dlm_options* opts, double* ll,
                  double* mean, double* ess, double* cloud, double* weights, int32_t* status);
 
+/* dlm_pf_batch with the resampling scheme chosen (the `resample` argument of ParticleFilter(n, n0, resample), ParticleFilter.scala:26-30): every
+ * argument, shape, limit, output, status and draw as in dlm_pf_batch, and one more descriptor.  Only the ANCESTOR step of a resampling differs;
+ * the ESS test, the gather, W_t,i = 1 / P afterwards, ll, mean and ess are dlm_pf_batch's.  With cum_j the inclusive cumulative weights, their last
+ * one `total`, anc(target) the first j with cum_j > target (P - 1 when none is) and u_i the [0, 1) uniform of block 8 of (slot t, particle i):
+ *   DLM_RESAMPLE_MULTINOMIAL  anc_i = anc(u_i total): dlm_pf_batch, bit for bit (dlm_pf_batch IS this call with {DLM_RESAMPLE_MULTINOMIAL, 0})
+ *   DLM_RESAMPLE_STRATIFIED   anc_i = anc(((i + u_i) / P) total): one uniform per stratum [i / P, (i + 1) / P)
+ *   DLM_RESAMPLE_SYSTEMATIC   anc_i = anc(((i + u_0) / P) total): ONE uniform, particle 0's; the other P - 1 blocks of the step are not drawn
+ *   DLM_RESAMPLE_METROPOLIS   mh_steps = b, 1 <= b <= 64; no cumulative weights.  Particle i starts at k = i; for s = 0 .. b - 1, with (u1, u2) the
+ *                             uniforms of block 128 + s of (slot t, particle i): j = min(floor(u2 P), P - 1), and k moves to j when u1 W_k <= W_j
+ *                             (a k of weight 0 always moves; there is no division).  anc_i is the last k.
+ * The three unbiased schemes keep E[exp(ll)] = the likelihood exactly, for every P and n0 (the offspring counts have the means P W_j); stratified
+ * and systematic resampling never have a larger variance of the offspring counts than multinomial, and every count N_j of a systematic step is
+ * floor(P W_j) or that plus 1.  The reference's systematicResample is not followed (every index it returns is -1).
+ * Metropolis resampling is BIASED for a finite b: a chain forgets its start at the rate 1 - 1 / (P max_j W_j) per step, so that after b steps the
+ * ancestors still favour the particles' own indices and E[exp(ll)] is not the likelihood (DESIGN.md 4.27 has the measurements); it is the
+ * reference's worked example (metropolisResampling(10), written here without its 0 / 0: Q76) and needs no collective operation, but a
+ * particle-marginal Metropolis sampler must not be run on it.
+ * DLM_ERR_ARG: resample == NULL, a scheme that is none of the four, mh_steps outside 1 .. 64 under DLM_RESAMPLE_METROPOLIS, mh_steps != 0 under
+ * any other scheme; everything dlm_pf_batch answers.  dlm_last_variant: "pf-wave". */
+enum { DLM_RESAMPLE_MULTINOMIAL = 0, DLM_RESAMPLE_STRATIFIED = 1, DLM_RESAMPLE_SYSTEMATIC = 2, DLM_RESAMPLE_METROPOLIS = 3 };
+typedef struct {
+  int32_t scheme;       /* DLM_RESAMPLE_*                                              */
+  int32_t mh_steps;     /* b of DLM_RESAMPLE_METROPOLIS, 1 .. 64; 0 under the others   */
+} dlm_resample_desc;
+int dlm_pf_resampled(dlm_engine* e, const dlm_model_desc* model, const dlm_params_desc* params, const dlm_pf_desc* pf,
+                           const dlm_resample_desc* resample, const double* obs_param, const double* y, uint64_t iteration,
+                           const dlm_options* opts, double* ll, double* mean, double* ess, double* cloud, double* weights, int32_t* status);
+
 /* Posterior-predictive forecast of a DGLM from a particle cloud (Dglm.forecastParticles, Dglm.scala:305-335): dlm_pf_batch's step, and at every
  * step one draw of the observation per particle, summarised where the draws are.  Shapes, limits, families and LDS as dlm_pf_batch; `model`
  * describes the H = model->T forecast steps (dt[0] the gap from the time of the cloud), y [N][H] with NaN = "forecast, do not update".

@@ -385,6 +385,18 @@ JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_particleFilter(JN
   throw_if(env, eng(h), dlm_pf_batch(eng(h), &d.m, &d.q, &pf, ptr<const double>(obsParam), ptr<const double>(y), static_cast<uint64_t>(iteration), &d.o, ptr<double>(ll), ptr<double>(mean),
                                      ptr<double>(ess), ptr<double>(cloud), ptr<double>(weights), ptr<int32_t>(status)));
 }
+// ---- particleFilter with the resampling scheme chosen (the `resample` argument of ParticleFilter(n, n0, resample)): dlm_resample_desc crosses as scalars in its field order behind dlm_pf_desc's; scheme 0..3 =
+// multinomial (particleFilter bit for bit), stratified, systematic, Metropolis with mhSteps = 1..64 chain steps (biased: not for a particle-marginal sampler); mhSteps = 0 under every other scheme.
+JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_particleFilterResampled(JNIEnv* env, jobject, jlong h, jlongArray model, jlongArray params, jlongArray opts, jint family, jint nParticles,
+                                                                                       jint n0, jint literal, jint scheme, jint mhSteps, jlong obsParam, jlong y, jlong iteration, jlong ll, jlong mean,
+                                                                                       jlong ess, jlong cloud, jlong weights, jlong status) {
+  Desc d;
+  if (!read_desc(env, model, params, opts, d)) return;
+  const dlm_pf_desc pf{family, nParticles, n0, literal};
+  const dlm_resample_desc rs{scheme, mhSteps};
+  throw_if(env, eng(h), dlm_pf_resampled(eng(h), &d.m, &d.q, &pf, &rs, ptr<const double>(obsParam), ptr<const double>(y), static_cast<uint64_t>(iteration), &d.o, ptr<double>(ll),
+                                               ptr<double>(mean), ptr<double>(ess), ptr<double>(cloud), ptr<double>(weights), ptr<int32_t>(status)));
+}
 // ---- posterior-predictive forecast of a dynamic generalised linear model from a particle cloud (Dglm.forecastParticles, Dglm.scala:297-331): the model describes the H forecast steps, y [N][H] with NaN =
 // "forecast, do not update".  dlm_pf_forecast_desc crosses as scalars (family, nParticles, literal, slotOffset) and ranks, a long[] of at most 8 order statistics in [0, nParticles) (null or empty: none), which
 // the engine reads on the host.  cloud0 [N][d][nParticles] (0: drawn from (m0, C0)), weights0 [N][nParticles] (0: equal).  fmean [N][H] and ll [N] are required; fquant [N][H][ranks.length] with ranks; draws

@@ -88,6 +88,8 @@ final class Native private[gpu] () {
   @native def dlmFsvSysInnovations(h: Long, model: Array[Long], theta: Long, opts: Array[Long], w: Long, status: Long): Unit
   /** bootstrap particle filter of a DGLM (ParticleFilter.step / likelihood) for N series of nParticles particles (a multiple of 64, 64..1024; d <= 16, p = 1): family 0..5 = Gaussian, Poisson, negative binomial, zero-inflated Poisson, Student-t (obsParam [N]: the degrees of freedom), Beta; n0 < 0: floor(nParticles / 5); literal = 1: the reference's arithmetic (Q37-Q39).  ll [N]; mean [N][T][d], ess [N][T], cloud [N][d][nParticles], weights [N][nParticles] and status [N] are optional (0) */
   @native def particleFilter(h: Long, model: Array[Long], params: Array[Long], opts: Array[Long], family: Int, nParticles: Int, n0: Int, literal: Int, obsParam: Long, y: Long, iteration: Long, ll: Long, mean: Long, ess: Long, cloud: Long, weights: Long, status: Long): Unit
+  /** particleFilter with the resampling scheme of ParticleFilter(n, n0, resample) chosen: scheme 0 = multinomial (particleFilter bit for bit), 1 = stratified, 2 = systematic (both unbiased, with a smaller variance of ll; systematic draws one uniform per step), 3 = Metropolis with mhSteps = 1..64 steps per particle (metropolisResampling(b); biased for every finite b: not for a particle-marginal sampler); mhSteps = 0 under schemes 0..2 */
+  @native def particleFilterResampled(h: Long, model: Array[Long], params: Array[Long], opts: Array[Long], family: Int, nParticles: Int, n0: Int, literal: Int, scheme: Int, mhSteps: Int, obsParam: Long, y: Long, iteration: Long, ll: Long, mean: Long, ess: Long, cloud: Long, weights: Long, status: Long): Unit
   /** posterior-predictive forecast of a DGLM from a particle cloud (Dglm.forecastParticles): the model describes the H forecast steps, y [N][H] with NaN = "forecast, do not update" (an observed value updates and resamples the cloud); step h draws from the Philox slot slotOffset + h.  ranks: at most 8 order statistics in [0, nParticles) of the nParticles draws of a time (null: none).  cloud0 [N][d][nParticles] (0: drawn from (m0, C0)), weights0 [N][nParticles] (0: equal; given: resampled once at entry).  fmean [N][H] and ll [N] are required, fquant [N][H][ranks.length] with ranks; draws [N][H][nParticles], mean [N][H][d], cloud, weights and status are optional (0) */
   @native def particleForecast(h: Long, model: Array[Long], params: Array[Long], opts: Array[Long], family: Int, nParticles: Int, literal: Int, slotOffset: Long, ranks: Array[Long], obsParam: Long, cloud0: Long, weights0: Long, y: Long, iteration: Long, fmean: Long, fquant: Long, draws: Long, ll: Long, mean: Long, cloud: Long, weights: Long, status: Long): Unit
   /** Storvik filter of a DGLM (StorvikFilter.filterTs): the particle filter above with the diagonal of W -- and with learnV = 1 (Gaussian family only) V -- learned online from InverseGamma priors, priorV [2] = (shape, scale) and priorW [d][2] (strides in doubles, 0: one prior for the batch); params' W is not read, its V only with learnV = 0; literal = 1: Q39 and Q43.  ll [N] estimates the evidence; scaleMean [N][T][d+1] (the weighted means of the statistics' scales: divided by shape - 1 the posterior means of the variances) and scales [N][d+1][nParticles] are optional (0) like mean, ess, cloud, weights and status */
