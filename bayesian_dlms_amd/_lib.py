@@ -172,6 +172,18 @@ def rb_lds_bytes(d: int, n_particles: int) -> int:
     return ((tri + 2 * d + 3) * n_particles + 64 * tri + 3 * d + 1) * 8 + 4 * n_particles
 
 
+class MixtureDesc(ctypes.Structure):
+    """dlm_mixture_desc: rows, components per row, times, dimension, the number of quantiles, and the row, component and time strides
+    (in doubles) of f and of Q."""
+    _fields_ = [("N", ctypes.c_int32), ("C", ctypes.c_int32), ("H", ctypes.c_int32), ("p", ctypes.c_int32), ("nq", ctypes.c_int32),
+                ("f_nstride", ctypes.c_int64), ("f_cstride", ctypes.c_int64), ("f_tstride", ctypes.c_int64),
+                ("q_nstride", ctypes.c_int64), ("q_cstride", ctypes.c_int64), ("q_tstride", ctypes.c_int64)]
+
+
+SVPATH_MAX_H, SVPATH_MAX_R = 0x1FFFFF, 1024   # DLM_SVPATH_MAX_H, DLM_SVPATH_MAX_R (dlm_draws.h)
+MIX_MAX_P, MIX_MAX_NQ, MIX_LDS_C, MIX_MAX_C = 64, 8, 4096, 1 << 30   # DLM_MIX_MAX_P, DLM_MIX_MAX_NQ, DLM_MIX_LDS_C, DLM_MIX_MAX_C (dlm_internal.h)
+
+
 class Options(ctypes.Structure):
     _fields_ = [("flags", ctypes.c_uint32), ("mem", ctypes.c_int32),
                 ("seed", ctypes.c_uint64), ("series_offset", ctypes.c_uint64)]
@@ -237,6 +249,9 @@ SYMBOLS = [
     ("dlm_pf_forecast_learned", ctypes.c_int, [_V, _MP, _PP, ctypes.POINTER(PfForecastLearnedDesc), _V, _ip, _V, _V, _V, _V, _V, ctypes.c_int64,
                                                ctypes.c_uint64, _OP, _V, _V, _V, _V, _V, _V, _V, _V]),
     ("dlm_rb_state_draw", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _V, _V, ctypes.c_int64, ctypes.c_uint64, _OP, _V, _V]),
+    ("dlm_sv_paths", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _V, _V, ctypes.c_uint64, _OP, _V, _V]),
+    # (probs is a HOST array whatever opts->mem is: a typed pointer, as ranks above)
+    ("dlm_gaussian_mixture_summary", ctypes.c_int, [_V, ctypes.POINTER(MixtureDesc), _V, _V, ctypes.POINTER(ctypes.c_double), _OP, _V, _V, _V, _V]),
     ("dlm_pg_batch", ctypes.c_int, [_V, _MP, _PP, ctypes.POINTER(PgDesc), _V, _V, _V, ctypes.c_uint64, _OP, _V, _V, _V, _V, _V, _V, _V, _V]),
     ("dlm_ou_ffbs_batch", ctypes.c_int, [_V, ctypes.c_int32, ctypes.c_int32, _V, _V, _V, ctypes.c_int64, _V, ctypes.c_int64,
                                          _V, _OP, _V, _V, _V]),

@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdlm_engine.so")
-SOURCES = ["dlm_engine.hip", "dlm_generic.hip", "dlm_mfma16.hip", "dlm_sparse16.hip", "dlm_sampler16.hip", "dlm_tiled.hip", "dlm_wave48.hip", "dlm_svd.hip", "dlm_ar1.hip", "dlm_lane.hip", "dlm_gibbs.hip", "dlm_loglik.hip", "dlm_studentt.hip", "dlm_sv.hip", "dlm_sv_ou.hip", "dlm_sv_knots.hip", "dlm_fsv.hip", "dlm_dlmfsv.hip", "dlm_pf.hip", "dlm_storvik.hip", "dlm_lw.hip", "dlm_rb.hip", "dlm_pg.hip", "dlm_pf_forecast.hip", "dlm_pf_forecast_learned.hip"]
+SOURCES = ["dlm_engine.hip", "dlm_generic.hip", "dlm_mfma16.hip", "dlm_sparse16.hip", "dlm_sampler16.hip", "dlm_tiled.hip", "dlm_wave48.hip", "dlm_svd.hip", "dlm_ar1.hip", "dlm_lane.hip", "dlm_gibbs.hip", "dlm_loglik.hip", "dlm_studentt.hip", "dlm_sv.hip", "dlm_sv_ou.hip", "dlm_sv_knots.hip", "dlm_fsv.hip", "dlm_dlmfsv.hip", "dlm_fsv_forecast.hip", "dlm_pf.hip", "dlm_storvik.hip", "dlm_lw.hip", "dlm_rb.hip", "dlm_pg.hip", "dlm_pf_forecast.hip", "dlm_pf_forecast_learned.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 FLAGS = BASE_FLAGS + ["-mllvm", "-amdgpu-mfma-vgpr-form"]

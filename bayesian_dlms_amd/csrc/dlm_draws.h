@@ -88,6 +88,12 @@ constexpr unsigned DLM_FCL_BLOCK_GAMMA = 0u, DLM_FCL_GAMMA_ATTEMPTS = 255u;
 //                     k_T (slot DLM_PG_SLOT_INIT, particle 0).  The second byte is 0.
 constexpr unsigned DLM_KEY_PG = 0x50470000u;         // "PG", a zero byte and the block byte
 constexpr unsigned DLM_PG_BLOCK_RESAMPLE = 8u, DLM_PG_BLOCK_REF = 9u, DLM_PG_BLOCK_FINAL = 10u;
+//   DLM_KEY_SVPATH    dlm_sv_paths: comp = the step h of the path (1 .. H; DLM_SVPATH_SLOT_START = 0 the draw of a stationary start), the attempt
+//                     field the path r < 1024, which = 0.  The low byte of the key is the FACTOR j < 8.  The second byte is 0.
+constexpr unsigned DLM_KEY_SVPATH = 0x53500000u;     // "SP", a zero byte and the factor byte
+constexpr unsigned DLM_SVPATH_SLOT_START = 0u;
+constexpr int DLM_SVPATH_MAX_H = 0x1FFFFF;           // step h takes slot h <= H
+constexpr int DLM_SVPATH_MAX_R = 1024;
 
 // ---- the slots ------------------------------------------------------------------------------------------------------------------
 // comp is a 21-bit field (the counter word is comp * 2048 + attempt * 2 + which).  A sampler whose per-time draws take comp = t < T
@@ -166,6 +172,10 @@ static_assert(DLM_PG_SLOT_INIT > (unsigned)DLM_PF_MAX_T - 1, "the conditional fi
 static_assert((DLM_PF_MAX_D + 1) / 2 <= (int)DLM_PG_BLOCK_RESAMPLE && DLM_PG_BLOCK_REF > DLM_PG_BLOCK_RESAMPLE && DLM_PG_BLOCK_FINAL > DLM_PG_BLOCK_REF &&
               DLM_PG_BLOCK_FINAL < 256u,
               "the conditional filter's blocks (state normals, free ancestors, the reference's ancestor, the final index) are distinct and fit the key's low byte");
+static_assert((DLM_KEY_SVPATH & 0xFFFFu) == 0u && (DLM_KEY_SVPATH >> 16) != (DLM_KEY_PF >> 16) && DLM_KEY_SVPATH != DLM_KEY_STORVIK &&
+              DLM_KEY_SVPATH != DLM_KEY_LW && DLM_KEY_SVPATH != DLM_KEY_RB && DLM_KEY_SVPATH != DLM_KEY_FCL && DLM_KEY_SVPATH != DLM_KEY_PG &&
+              DLM_SVPATH_MAX_R <= 1024 && (unsigned)DLM_SVPATH_MAX_H <= DLM_SLOT_TOP,
+              "the volatility paths draw under a key of their own; a path fits the attempt field, a factor the key's low byte, a step the slot field");
 static_assert(DLM_ST_SLOT_SCALE > (unsigned)DLM_ST_MAX_T - 1, "the Student-t step's scalar slots lie above every time slot");
 static_assert(DLM_SV_SLOT_ACCEPT > (unsigned)DLM_SV_MAX_T, "the SV step's scalar slots lie above every time slot");
 static_assert(DLM_SVOU_SLOT_ACC_MU > (unsigned)DLM_SVOU_MAX_T, "the OU step's scalar slots lie above every time slot");

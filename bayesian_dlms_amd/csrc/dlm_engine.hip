@@ -116,6 +116,8 @@ struct dlm_engine {
   //                    across calls, so nobody else lives here; reused where k_rts_key_check finds the call's key equal to theirs
   //   pgws      E      dlm_pg_batch without its trace outputs: the clouds [launch][T+1][d][P] | behind them the ancestors [launch][T][P] of ONE launch
   //                    (the launches of a call follow one another on the engine's stream)
+  //   mixws     E      dlm_gaussian_mixture_summary with more components than a cell holds in LDS: the packed pairs [launch's cells][C][2] of ONE
+  //                    launch of the quantile kernel
   Workspace* workspaces = nullptr;   // (in front of the Ws members: they link themselves in)
   Ws<void> arena{workspaces};
   Ws<dlm::SparseT> sp_dev{workspaces};
@@ -126,6 +128,7 @@ struct dlm_engine {
   Ws<double> zws{workspaces};
   Ws<void> rtsws{workspaces};
   Ws<void> pgws{workspaces};
+  Ws<double> mixws{workspaces};
   dlm::SparseF* spf_dev = nullptr;     // tables of a structured F (tiled path), allocated once
   int sparse_k = 0;           // 0: some G is not structured (dense MFMA path, regular grids only)
   ncclComm_t comm = nullptr;
@@ -1774,6 +1777,96 @@ int dlm_rb_state_draw(dlm_engine* e, int32_t d, int32_t N, int32_t P, const doub
   if ((rc = st.commit())) return rc;
   e->variant = "rb-state-draw";
   HIP_TRY(e, dlm::launch_rb_state_draw(a, e->stream));
+  return st.finish(opts->flags & DLM_OPT_ASYNC);
+}
+
+int dlm_sv_paths(dlm_engine* e, int32_t N, int32_t k, int32_t H, int32_t R, const double* sv, const double* alpha0, uint64_t iteration,
+                 const dlm_options* opts, double* alpha, int32_t* status) {
+  if (!e) return DLM_ERR_ARG;
+  int rc;
+  if ((rc = check_opts(e, opts))) return rc;
+  if (N < 1 || H < 1) return fail(e, DLM_ERR_ARG, "N >= 1 and H >= 1");
+  if (H > dlm::DLM_SVPATH_MAX_H) return fail(e, DLM_ERR_ARG, "H must stay at or below 2^21 - 1 (the Philox counter's slot field)");
+  if (k < 1 || k > dlm::DLM_FSV_MAX_K) return fail(e, DLM_ERR_UNSUPPORTED, "1 <= k <= 8");
+  if (R < 64 || R > dlm::DLM_SVPATH_MAX_R || R % 64 != 0) return fail(e, DLM_ERR_UNSUPPORTED, "n_paths must be a multiple of 64 with 64 <= n_paths <= 1024 (one lane per path, the path in the counter's attempt field)");
+  if ((long long)N * (R / 64) > 0x7FFFFFFFll) return fail(e, DLM_ERR_ARG, "N n_paths / 64 must stay below 2^31 (one block per 64 paths of a row)");
+  if (!sv || !alpha) return fail(e, DLM_ERR_ARG, "sv and alpha are required");
+  HIP_TRY(e, hipSetDevice(e->device));
+  dlm::SvPathsArgs a{};
+  const size_t n = N, kk = k, h = H, r = R;
+  Stager st(e, opts->mem == DLM_MEM_HOST);
+  st.in(&a.sv, sv, n * kk * 3);
+  st.in(&a.alpha0, alpha0, alpha0 ? n * kk : 0);
+  st.out(&a.alpha, alpha, n * r * kk * (h + 1));
+  st.zeroed_out(&a.status, (int*)status, status ? n : 0);
+  if ((rc = st.commit())) return rc;
+  a.N = N; a.k = k; a.H = H; a.R = R;
+  a.rs = draw_stream(opts, iteration);
+  e->variant = "sv-paths";
+  HIP_TRY(e, dlm::launch_sv_paths(a, e->stream));
+  return st.finish(opts->flags & DLM_OPT_ASYNC);
+}
+
+int dlm_gaussian_mixture_summary(dlm_engine* e, const dlm_mixture_desc* mx, const double* f, const double* Q, const double* probs,
+                                 const dlm_options* opts, double* mean, double* cov, double* quant, int32_t* status) {
+  if (!e) return DLM_ERR_ARG;
+  if (!mx) return fail(e, DLM_ERR_ARG, "null descriptor");
+  int rc;
+  if ((rc = check_opts(e, opts))) return rc;
+  const int N = mx->N, C = mx->C, H = mx->H, p = mx->p, nq = mx->nq;
+  if (N < 1 || C < 1 || H < 1 || p < 1) return fail(e, DLM_ERR_ARG, "N, C, H, p must be >= 1");
+  if (p > dlm::DLM_MIX_MAX_P) return fail(e, DLM_ERR_UNSUPPORTED, "p is limited to 64");
+  if (C > dlm::DLM_MIX_MAX_C) return fail(e, DLM_ERR_ARG, "C must stay at or below 2^30 (the kernels index a row's components with an int)");
+  if (nq < 0 || nq > dlm::DLM_MIX_MAX_NQ) return fail(e, DLM_ERR_ARG, "0 <= nq <= 8 quantiles per cell");
+  if (nq > 0 && (!probs || !quant)) return fail(e, DLM_ERR_ARG, "probs and quant are required with nq > 0");
+  for (int j = 0; j < nq; ++j)
+    if (!(probs[j] > 0.0 && probs[j] < 1.0)) return fail(e, DLM_ERR_ARG, "every prob must lie inside (0, 1)");
+  if (!Q || !mean || !cov) return fail(e, DLM_ERR_ARG, "Q, mean and cov are required");
+  const int64_t strides[6] = {mx->f_nstride, mx->f_cstride, mx->f_tstride, mx->q_nstride, mx->q_cstride, mx->q_tstride};
+  for (int j = f ? 0 : 3; j < 6; ++j)
+    if (strides[j] < 0) return fail(e, DLM_ERR_ARG, "the strides must not be negative");
+  if ((long long)N * H * p > 0x7FFFFFFFll) return fail(e, DLM_ERR_ARG, "N H p must stay below 2^31 (one block per cell)");
+  HIP_TRY(e, hipSetDevice(e->device));
+  dlm::MixtureArgs a{};
+  const size_t n = N, c = C, h = H, pp = p;
+  // what the strides reach: the last component of the last row at the last time, and its p (p p) doubles
+  const size_t f_extent = (n - 1) * (size_t)mx->f_nstride + (c - 1) * (size_t)mx->f_cstride + (h - 1) * (size_t)mx->f_tstride + pp;
+  const size_t q_extent = (n - 1) * (size_t)mx->q_nstride + (c - 1) * (size_t)mx->q_cstride + (h - 1) * (size_t)mx->q_tstride + pp * pp;
+  // host memory, f and Q inside one buffer (the fq records): one staged range serves both
+  const bool one_range = opts->mem == DLM_MEM_HOST && f && Q >= f && (size_t)(Q - f) < f_extent;
+  Stager st(e, opts->mem == DLM_MEM_HOST);
+  if (one_range) {
+    st.in(&a.f, f, std::max(f_extent, (size_t)(Q - f) + q_extent));
+  } else {
+    st.in(&a.f, f, f ? f_extent : 0);
+    st.in(&a.Q, Q, q_extent);
+  }
+  st.out(&a.mean, mean, n * h * pp);
+  st.out(&a.cov, cov, n * h * pp * pp);
+  st.out(&a.quant, quant, nq ? n * h * pp * (size_t)nq : 0);
+  st.zeroed_out(&a.status, (int*)status, status ? n : 0);
+  if ((rc = st.commit())) return rc;
+  if (one_range) a.Q = a.f + (Q - f);
+  a.N = N; a.C = C; a.H = H; a.p = p; a.nq = nq;
+  a.f_nstride = mx->f_nstride; a.f_cstride = mx->f_cstride; a.f_tstride = mx->f_tstride;
+  a.q_nstride = mx->q_nstride; a.q_cstride = mx->q_cstride; a.q_tstride = mx->q_tstride;
+  for (int j = 0; j < nq; ++j) a.probs[j] = probs[j];   // a host array whatever opts->mem: checked above, passed by value
+  e->variant = "mixture-summary";
+  HIP_TRY(e, dlm::launch_mixture_moments(a, e->stream));
+  if (nq > 0) {
+    // beyond DLM_MIX_LDS_C components a cell's pairs live in the engine's workspace: launches of whole cells under the cap
+    const size_t cells = n * h * pp, per_cell = c * 2 * sizeof(double);
+    size_t chunk = cells;
+    if (C > dlm::DLM_MIX_LDS_C) {
+      chunk = std::max<size_t>(1, std::min<size_t>(cells, (size_t)DLM_MIXTURE_WORKSPACE_CAP / per_cell));
+      if ((rc = ensure(e, e->mixws, chunk * per_cell))) return rc;
+      a.pack = e->mixws;
+    }
+    for (size_t first = 0; first < cells; first += chunk) {
+      a.cell_first = (int)first;
+      HIP_TRY(e, dlm::launch_mixture_quantiles(a, (int)std::min(chunk, cells - first), e->stream));
+    }
+  }
   return st.finish(opts->flags & DLM_OPT_ASYNC);
 }
 

@@ -507,6 +507,35 @@ hipError_t launch_dlmfsv_impute(const DlmFsvImputeArgs& a, hipStream_t s);
 hipError_t launch_dlmfsv_center(const DlmFsvCenterArgs& a, hipStream_t s);
 hipError_t launch_dlmfsv_variance(const DlmFsvVarianceArgs& a, hipStream_t s);
 
+// ---- posterior-predictive forecasts of the factor stochastic-volatility models: future log-volatility paths and the summary of the
+// Gaussian mixture they give per time (mean, total covariance, exact marginal quantiles), dlm_fsv_forecast.hip -------------
+struct SvPathsArgs {
+  int N, k, H, R;
+  const double* sv;       // [N][k][3] = (phi, mu, sigma_eta)
+  const double* alpha0;   // [N][k], or nullptr: a stationary start
+  DrawStream rs;
+  double* alpha;          // [N][R][k][H+1]
+  int* status;            // [N], nullable (zeroed by the caller)
+};
+constexpr int DLM_MIX_MAX_P = 64, DLM_MIX_MAX_NQ = 8, DLM_MIX_MAX_C = 1 << 30;   // (C + 256 fits an int: the kernels' component loops)
+constexpr int DLM_MIX_LDS_C = 4096;   // the components of a cell that k_mixture_quantiles holds in LDS; beyond it they are packed into `pack`
+struct MixtureArgs {
+  int N, C, H, p, nq;
+  const double* f;        // component c of row n at time h: f + n f_nstride + c f_cstride + h f_tstride (p doubles), or nullptr: 0
+  const double* Q;        // ... Q + n q_nstride + c q_cstride + h q_tstride (p p doubles, symmetric)
+  long long f_nstride, f_cstride, f_tstride, q_nstride, q_cstride, q_tstride;
+  double probs[DLM_MIX_MAX_NQ];
+  int cell_first;         // k_mixture_quantiles: the launch serves the cells cell_first .. cell_first + (grid size) - 1 of the N H p
+  double* pack;           // C > DLM_MIX_LDS_C: [launch's cells][C][2] = (f_ci, sqrt(2 Q_cii)), else nullptr
+  double* mean;           // [N][H][p]
+  double* cov;            // [N][H][p p]
+  double* quant;          // [N][H][p][nq], nullable with nq = 0
+  int* status;            // [N], nullable (zeroed by the caller)
+};
+hipError_t launch_sv_paths(const SvPathsArgs& a, hipStream_t s);
+hipError_t launch_mixture_moments(const MixtureArgs& a, hipStream_t s);
+hipError_t launch_mixture_quantiles(const MixtureArgs& a, int cells, hipStream_t s);
+
 // ---- the particle filters of a DGLM, one wavefront per series: what all three kernels read and write (dlm_pf_common.h) ---------------------
 // PfArgs and StorvikArgs derive from it.  LwArgs repeats the fields under the same names in the order k_lw was written with: its kernel
 // holds 106 SGPRs, and where the arguments lie decides how many of them it parks in VGPRs -- every derived order that was tried moves its

@@ -143,6 +143,21 @@ class DlmFsvSystem:
                               init_p, engine, n_iter=n_iter, seed=seed, series_offset=series_offset, literal=literal,
                               literal_order=literal_order, keep_states=keep_states, times=times)
 
+    @staticmethod
+    def forecast(mod: Dlm, ys, draws, horizon: int, engine, *, m0, c0, n_paths: int = 64, prob: float = 0.75, probs=None, seed: int = 0,
+                 series_offset: int = 0, times=None, budget=None):
+        """DlmFsvSystem.forecast (DlmFsvSystem.scala:441-486) as a PURE forecast of y_{T+1 .. T+horizon} from kept draws (Q77-Q82 for what
+        the reference's own does).  Per draw: (m_T, C_T) from the Kalman filter over ys under the draw's own W_t stream (its theta is
+        integrated out), n_paths log-volatility paths from the draw's alpha_T, W_h = beta diag(exp(alpha_{.,T+h})) beta^T + diag(v),
+        and the Kalman forecast under it with the draw's diagonal V.  draws: a list of the States of sample kept with their states, or a dict
+        of stacked arrays {"beta", "v", "sv", "V" [M][N][.], "alpha" [M][N][k][T+1]}.  m0, c0: the prior of theta_0 the sampler
+        ran with (init_p.dlm.m0, init_p.dlm.c0).  Returns {"mean" [N][H][p], "cov" [N][H][p][p] (the total predictive covariance),
+        "lower", "upper" [N][H][p] the exact mixture quantiles at 1 - prob and prob (Dlm.summariseForecast's interval), "quantiles"
+        [N][H][p][len(probs)] or None, "status" [N]}.  times: the training grid (a non-unit grid raises the sampler's error).
+        budget: bytes of device memory the call may use (default: 60 % of what is free)."""
+        return _dlmfsv.forecast(KIND, mod, ys, draws, horizon, engine, m0=m0, c0=c0, n_paths=n_paths, prob=prob, probs=probs, seed=seed,
+                                series_offset=series_offset, times=times, budget=budget)
+
 
 # the factor part is the system noise: W_t is the stream, V static; the first state draw runs under W_t = INIT_W I
 KIND = _dlmfsv.Kind(stream="W", param="V", first=INIT_W, model=DlmFsvSystem._model, shape=DlmFsvSystem._shape,

@@ -162,6 +162,32 @@ def check_pf_forecast_learned_lds(d: int, n_particles: int):
                           "d = 16 with at most 512 particles, d <= 8 with 1024)")
 
 
+def check_sv_paths_shape(k: int, horizon: int, n_paths: int):
+    """What dlm_sv_paths takes: 1 <= k <= 8 chains, a horizon inside the Philox slot field, whole wavefronts of paths up to 1024."""
+    if not 1 <= k <= 8:
+        raise EngineError(f"k = {k}: the volatility paths take 1 <= k <= 8 factors")
+    if not 1 <= horizon <= _lib.SVPATH_MAX_H:
+        raise EngineError(f"horizon must satisfy 1 <= horizon <= {_lib.SVPATH_MAX_H}, got {horizon}")
+    if n_paths < 64 or n_paths > _lib.SVPATH_MAX_R or n_paths % 64:
+        raise EngineError(f"n_paths must be a multiple of 64 with 64 <= n_paths <= {_lib.SVPATH_MAX_R}, got {n_paths}")
+
+
+def check_mixture_shape(N: int, C: int, H: int, p: int, probs):
+    """What dlm_gaussian_mixture_summary takes; returns probs as a list of floats."""
+    if min(N, C, H, p) < 1:
+        raise EngineError(f"N, C, H, p must be >= 1, got {(N, C, H, p)}")
+    if C > _lib.MIX_MAX_C:
+        raise EngineError(f"C = {C}: the mixture summary takes at most 2^30 components per row")
+    if p > _lib.MIX_MAX_P:
+        raise EngineError(f"p = {p}: the mixture summary takes p <= {_lib.MIX_MAX_P}")
+    pr = [float(q) for q in np.asarray(probs, dtype=np.float64).reshape(-1)]
+    if len(pr) > _lib.MIX_MAX_NQ:
+        raise EngineError(f"at most {_lib.MIX_MAX_NQ} quantiles per call, got {len(pr)}")
+    if not all(0.0 < q < 1.0 for q in pr):
+        raise EngineError(f"every prob must lie inside (0, 1), got {pr}")
+    return pr
+
+
 def _pf_shape(mat, n_particles, family):
     """(d, T, P) of a call of one of the three particle filters, after the checks of its shape and of its family."""
     P = int(n_particles)
@@ -663,6 +689,66 @@ class Engine:
         md, tables = _model_desc(be, mat, N, G=mat.G, n_g=mat.n_g, g_index=mat.g_index, dt=mat.dt)
         res = _outputs(be, N, w=_out_or_empty(be, out, "w", (N, T, d)))
         self._call("dlm_dlmfsvsys_innovations_batch", be, flags, md, tb, _options(be, flags), *res.values(), keep=tables)
+        return res
+
+    def sv_paths(self, sv, horizon, n_paths, *, alpha0=None, iteration=0, seed=0, series_offset=0, flags=0, out=None):
+        """Future log-volatility paths of the factor stochastic-volatility models (dlm_sv_paths; StochasticVolatility.stepState): sv
+        [N][k][3] = (phi, mu, sigma_eta), alpha0 [N][k] the start of every path of a row or None: a draw from the stationary law.  Returns
+        {"alpha" [N][R][k][H+1] (entry 0 the start; viewed as [N R][k][H+1] the alpha of dlmfsv_variance with T = H), "status"}; path r of
+        row n is a pure function of (seed, series_offset + n, iteration, r), so a call with more paths or other rows repeats it.  A row
+        with |phi| >= 1 or sigma <= 0 has DLM_ST_NOT_PD, one with a non-finite input DLM_ST_NONFINITE, and NaN paths.  out: dict with an
+        existing "alpha" buffer."""
+        if len(sv.shape) != 3 or int(sv.shape[2]) != 3:
+            raise EngineError(f"sv must be [N][k][3], got the shape {tuple(sv.shape)}")
+        N, k, H, R = int(sv.shape[0]), int(sv.shape[1]), int(horizon), int(n_paths)
+        check_sv_paths_shape(k, H, R)
+        be = self._backend(sv)
+        sb, ab = be.put(sv), be.put(alpha0)
+        if ab is not None and tuple(ab.shape) != (N, k):
+            raise EngineError(f"alpha0 must be [N][k] = {(N, k)}, got {tuple(ab.shape)}")
+        res = _outputs(be, N, alpha=_out_or_empty(be, out, "alpha", (N, R, k, H + 1)))
+        self._call("dlm_sv_paths", be, flags, N, k, H, R, sb, ab, int(iteration), _options(be, flags, seed, series_offset), *res.values())
+        return res
+
+    def gaussian_mixture_summary(self, N, C, H, p, *, fq=None, Q=None, f=None, q_strides=None, f_strides=None, probs=(), flags=0, out=None):
+        """Mean, total covariance and exact marginal quantiles of the equal-weight mixture of C Gaussians N(f_c, Q_c) per row and time
+        (dlm_gaussian_mixture_summary), read in place:
+          fq   the records [N C][H+1][p + p p] of filter(..., want_fq=True) on N C rows (record 0 is skipped), or
+          Q    [N C][H][p p] (a variance stream of dlmfsv_variance as it is) with f [N C][H][p] or None (zero means);
+               q_strides / f_strides = (row, component, time) in doubles say where a differently laid out Q / f has its records.
+        probs: up to 8 probabilities inside (0, 1).  Returns {"mean" [N][H][p], "cov" [N][H][p p] (symmetric bit for bit), "quant"
+        [N][H][p][nq] or None, "status" [N]}.  A quantile is the root of the mixture's CDF bracketed to adjacent doubles (bisection
+        safeguarding Newton; no sampling).  A row with a Q_ii that is not positive and finite has DLM_ST_NOT_PD, with a non-finite f
+        DLM_ST_NONFINITE, and NaN in that cell.  out: dict of existing "mean" / "cov" / "quant" buffers."""
+        N, C, H, p = int(N), int(C), int(H), int(p)
+        pr = check_mixture_shape(N, C, H, p, probs)
+        rec, pp = p + p * p, p * p
+        if (fq is None) == (Q is None):
+            raise EngineError("give either fq (the filter's records) or Q (with an optional f)")
+        be = self._backend(fq if fq is not None else Q)
+        size = lambda a: int(a.numel() if hasattr(a, "numel") else a.size)
+        if fq is not None:
+            flat = be.put(fq).reshape(-1)
+            if size(flat) != N * C * (H + 1) * rec:
+                raise EngineError(f"fq must hold [N C][H+1][p + p p] = {(N * C, H + 1, rec)} doubles, got {size(flat)}")
+            fb, qb = flat[rec:], flat[rec + p:]
+            fs = qs = (C * (H + 1) * rec, (H + 1) * rec, rec)
+        else:
+            qb = be.put(Q).reshape(-1)
+            fb = None if f is None else be.put(f).reshape(-1)
+            qs = tuple(int(s) for s in q_strides) if q_strides is not None else (C * H * pp, H * pp, pp)
+            fs = tuple(int(s) for s in f_strides) if f_strides is not None else (C * H * p, H * p, p)
+            if len(qs) != 3 or len(fs) != 3 or min(qs + fs) < 0:
+                raise EngineError("q_strides and f_strides are (row, component, time) strides in doubles, none negative")
+            extent = lambda s, last: (N - 1) * s[0] + (C - 1) * s[1] + (H - 1) * s[2] + last
+            if size(qb) < extent(qs, pp) or (fb is not None and size(fb) < extent(fs, p)):
+                raise EngineError("Q / f is smaller than what N, C, H, p and the strides reach")
+        nq = len(pr)
+        res = _outputs(be, N, mean=_out_or_empty(be, out, "mean", (N, H, p)), cov=_out_or_empty(be, out, "cov", (N, H, pp)),
+                       quant=_out_or_empty(be, out, "quant", (N, H, p, nq)) if nq else None)
+        desc = _lib.MixtureDesc(N, C, H, p, nq, *fs, *qs)
+        prc = (ctypes.c_double * nq)(*pr) if nq else None          # a host array whatever the backend: the call reads it before it returns
+        self._call("dlm_gaussian_mixture_summary", be, flags, desc, fb, qb, prc, _options(be, flags), *res.values())
         return res
 
     def particle_filter(self, mat, params, y, *, family, n_particles, n0=-1, literal=False, obs_param=None, iteration=0, seed=0,

@@ -188,6 +188,20 @@ class FactorSv:
             params = {"beta": host(c["beta"]).copy(), "v": host(c["v"]).copy(), "sv": host(c["sv"]).copy()}
             yield FactorSv.State(params, *(host(c[key]).copy() if keep_factors else None for key in ("f", "alpha")), status)
 
+    @staticmethod
+    def forecast(draws, horizon: int, engine, *, n_paths: int = 64, prob: float = 0.75, probs=None, seed: int = 0, series_offset: int = 0,
+                 budget=None):
+        """The posterior predictive of y_{T+1 .. T+horizon} from kept draws: given a draw and a future log-volatility
+        path, y_{T+h} ~ N(0, beta diag(exp(alpha_{.,T+h})) beta^T + diag(v)); the paths start at the draw's alpha_T and follow
+        StochasticVolatility.stepState, n_paths per draw.  draws: a list of the States of sample_ar kept with their factors, or a dict
+        of stacked arrays {"beta" [M][N][p][k], "v" [M][N][p], "sv" [M][N][k][3], "alpha" [M][N][k][T+1]}.  Returns {"mean" [N][H][p]
+        (zeros), "cov" [N][H][p][p] the predictive covariance matrices, "lower", "upper" [N][H][p] the exact mixture quantiles at
+        1 - prob and prob (Dlm.summariseForecast's interval), "quantiles" [N][H][p][len(probs)] or None, "status" [N]}.  A pure
+        forecast: no test data is taken.  budget: bytes of device memory the call may use (default: 60 % of what is free)."""
+        from . import _dlmfsv
+        return _dlmfsv.forecast(None, None, None, draws, horizon, engine, n_paths=n_paths, prob=prob, probs=probs, seed=seed,
+                                series_offset=series_offset, budget=budget)
+
 
 def pack_priors(prior_beta, prior_sigma_eta, prior_mu, prior_phi, prior_sigma, literal, also=None):
     """The priors of the factor part, checked and packed for the device: (_lib.SvPrior of every factor's (phi, mu, sigma_eta^2) with the

@@ -861,6 +861,52 @@ int dlm_pf_forecast_learned(dlm_engine* e, const dlm_model_desc* model, const dl
 int dlm_rb_state_draw(dlm_engine* e, int32_t d, int32_t N, int32_t P, const double* means, const double* covs, int64_t slot,
                       uint64_t iteration, const dlm_options* opts, double* cloud, int32_t* status);
 
+/* Posterior-predictive forecasts of the factor stochastic-volatility models (FactorSv, DlmFsv, DlmFsvSystem).  A posterior
+ * draw's forecast is, given a future log-volatility path, Gaussian: the two calls here make the paths and summarise the mixture over draws
+ * and paths; dlm_dlmfsv_variance_batch (with T = H) and dlm_filter_batch (on all-NaN data, want fq) stand between them.
+ *
+ * dlm_sv_paths: alpha [N][R][k][H+1], R paths of the k AR(1) log-volatilities of every row -- viewed as [N R][k][H+1] the alpha of
+ * dlm_dlmfsv_variance_batch with T = H.  Entry 0 of a path is its start: alpha0 [N][k], or with alpha0 == NULL a draw from the stationary
+ * law N(mu, sigma^2 / (1 - phi^2)); entry h = 1 .. H is alpha_h = mu + phi (alpha_{h-1} - mu) + sigma z (StochasticVolatility.stepState;
+ * sv [N][k][3] = (phi, mu, sigma_eta), sigma_eta a standard deviation).  One lane per (row, path), the k chains in registers.  Draws:
+ * DLM_KEY_SVPATH + j (dlm_draws.h), counter (opts->seed, opts->series_offset + n, iteration, slot h (0: the stationary start), path r):
+ * a pure function of those, so the first 64 paths of an R = 128 call are the R = 64 call bit for bit and a row's paths depend on neither
+ * N nor the sharding.  1 <= k <= 8, R a multiple of 64 in 64 .. 1024 (DLM_ERR_UNSUPPORTED otherwise); N >= 1, 1 <= H <= 2^21 - 1, sv and
+ * alpha required (DLM_ERR_ARG).  A row with a non-finite sv or alpha0: DLM_ST_NONFINITE; else with |phi| >= 1 or sigma <= 0:
+ * DLM_ST_NOT_PD; its paths are NaN, other rows untouched.  opts: mem, seed, series_offset, DLM_OPT_ASYNC. */
+int dlm_sv_paths(dlm_engine* e, int32_t N, int32_t k, int32_t H, int32_t R, const double* sv, const double* alpha0, uint64_t iteration,
+                 const dlm_options* opts, double* alpha, int32_t* status);
+
+/* dlm_gaussian_mixture_summary: for N rows, H times and the equal-weight mixture of C Gaussians N(f_c, Q_c) of dimension p at each,
+ *   mean [N][H][p]      sum_c f_c / C
+ *   cov  [N][H][p p]    sum_c (Q_c + f_c f_c^T) / C - mean mean^T, the total predictive covariance, symmetric bit for bit
+ *   quant [N][H][p][nq] the exact quantiles at probs [nq] of the marginal mixture sum_c N(f_c,i, Q_c,ii) / C
+ * Component c of row n at time h is read at f + n f_nstride + c f_cstride + h f_tstride (p doubles; f == NULL: 0) and Q + n q_nstride +
+ * c q_cstride + h q_tstride (p p doubles, symmetric), strides in doubles, so nothing is repacked: with rec = p + p p,
+ *   the fq records [N C][H+1][rec] of dlm_filter_batch:   f = fq + rec, Q = fq + rec + p (record 0 skipped), nstride = C (H + 1) rec,
+ *                                                         cstride = (H + 1) rec, tstride = rec for both
+ *   a variance stream [N C][H][p p]:                      f = NULL, Q = the stream, q_nstride = C H p p, q_cstride = H p p, q_tstride = p p
+ * Sums run over c ascending in a fixed order, without atomics: a row's result depends on neither N nor its neighbours (dlm_fsv_forecast.hip
+ * has the order).  QUANTILES: the mixture's CDF F is solved by bisection safeguarding Newton.  The bracket starts at
+ * [min f - (|z| + 1) max s, max f + (|z| + 1) max s], z = normcdfinv(prob), s = sqrt(2 Q_ii); every evaluation moves the end on its side, so
+ * the computed F(lo) < prob <= F(hi) throughout.  STOPPING RULE: an exact hit F(x) == prob returns x; otherwise the search ends when hi is the
+ * double next to lo and returns hi, so |F(q) - prob| <= density(q) spacing(q) + the rounding of the computed F (below C 2^-52).  No Monte
+ * Carlo.  A cell's (f_c,i, s_c) pairs are held in LDS up to C = 4096; beyond that they are packed once into an engine workspace of at most
+ * DLM_MIXTURE_WORKSPACE_CAP bytes per launch.  1 <= C <= 2^30 (tested to 2^20; the kernels index the components with an int), p <= 64
+ * (DLM_ERR_UNSUPPORTED), 0 <= nq <= 8 with every prob
+ * inside (0, 1), N H p < 2^31, strides >= 0, Q, mean, cov required, probs and quant with nq > 0 (DLM_ERR_ARG).  probs is a HOST array
+ * whatever opts->mem.  With DLM_MEM_HOST an f and a Q that lie inside one buffer (the fq layout) are staged as ONE range.  A Q_c,ii that is not positive and finite gives the row DLM_ST_NOT_PD, a non-finite f_c,i DLM_ST_NONFINITE; mean_i,
+ * the quantiles of cell i and row and column i of cov are NaN.  opts: mem, DLM_OPT_ASYNC. */
+#define DLM_MIXTURE_WORKSPACE_CAP (1ll << 30)
+typedef struct {
+  int32_t N, C, H, p;   /* rows, components per row, times, dimension                  */
+  int32_t nq;           /* 0..8 quantiles per cell                                     */
+  int64_t f_nstride, f_cstride, f_tstride;   /* in doubles; not read with f == NULL    */
+  int64_t q_nstride, q_cstride, q_tstride;
+} dlm_mixture_desc;
+int dlm_gaussian_mixture_summary(dlm_engine* e, const dlm_mixture_desc* mx, const double* f, const double* Q, const double* probs,
+                                 const dlm_options* opts, double* mean, double* cov, double* quant, int32_t* status);
+
 /* Particle Gibbs for a dynamic generalised linear model: ONE draw of the state path x_{0:T} | y, V, W of every series by conditional SMC
  * with ancestor sampling (Andrieu, Doucet & Holenstein 2010; Lindsten, Jordan & Schoen 2014).  It is what ParticleGibbs.scala aims at; the
  * reference's own step is not a valid kernel, so there is no literal mode.  The kernel leaves the law of

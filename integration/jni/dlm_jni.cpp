@@ -492,6 +492,28 @@ JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_rbStateDraw(JNIEn
   throw_if(env, eng(h), dlm_rb_state_draw(eng(h), d, n, nParticles, ptr<const double>(means), ptr<const double>(covs), static_cast<int64_t>(slot), static_cast<uint64_t>(iteration), &o,
                                           ptr<double>(cloud), ptr<int32_t>(status)));
 }
+// ---- posterior-predictive forecasts of the factor stochastic-volatility models: nPaths future log-volatility paths per row, alpha [N][nPaths][k][H+1] from sv [N][k][3] and the starts alpha0 [N][k]
+// (0: the stationary law); status is optional (0)
+JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_svPaths(JNIEnv* env, jobject, jlong h, jint n, jint k, jint horizon, jint nPaths, jlong sv, jlong alpha0, jlong iteration, jlongArray opts,
+                                                                       jlong alpha, jlong status) {
+  dlm_options o{};
+  if (!read_opts(env, opts, o)) return;
+  throw_if(env, eng(h), dlm_sv_paths(eng(h), n, k, horizon, nPaths, ptr<const double>(sv), ptr<const double>(alpha0), static_cast<uint64_t>(iteration), &o, ptr<double>(alpha), ptr<int32_t>(status)));
+}
+// ---- ... and the summary of the Gaussian mixture over draws and paths: mean [N][H][p], cov [N][H][p p], quant [N][H][p][nProbs] of the c components per row read through the (row, component,
+// time) strides fStrides / qStrides (three longs each, in doubles); f = 0: zero means; probs is a HOST address of nProbs doubles (a direct buffer's) whatever opts' mem; dlm_mixture_desc crosses as scalars and the two arrays
+JNIEXPORT void JNICALL Java_com_github_jonnylaw_dlm_gpu_Native_gaussianMixtureSummary(JNIEnv* env, jobject, jlong h, jint n, jint c, jint horizon, jint p, jlongArray fStrides, jlongArray qStrides, jlong f,
+                                                                                      jlong q, jlong probs, jint nProbs, jlongArray opts, jlong mean, jlong cov, jlong quant, jlong status) {
+  dlm_options o{};
+  if (!read_opts(env, opts, o)) return;
+  if (nProbs < 0 || nProbs > 8 || (nProbs && !probs)) { throw_arg(env, "gaussianMixtureSummary: 0 <= nProbs <= 8, and probs is a host address with nProbs > 0"); return; }
+  if (!fStrides || !qStrides || env->GetArrayLength(fStrides) != 3 || env->GetArrayLength(qStrides) != 3) { throw_arg(env, "gaussianMixtureSummary: fStrides and qStrides hold three strides each"); return; }
+  jlong fs[3], qs[3];
+  env->GetLongArrayRegion(fStrides, 0, 3, fs);
+  env->GetLongArrayRegion(qStrides, 0, 3, qs);
+  const dlm_mixture_desc mx{n, c, horizon, p, nProbs, fs[0], fs[1], fs[2], qs[0], qs[1], qs[2]};
+  throw_if(env, eng(h), dlm_gaussian_mixture_summary(eng(h), &mx, ptr<const double>(f), ptr<const double>(q), ptr<const double>(probs), &o, ptr<double>(mean), ptr<double>(cov), ptr<double>(quant), ptr<int32_t>(status)));
+}
 // ---- particle Gibbs for a dynamic generalised linear model (what ParticleGibbs.scala aims at): one conditional-SMC sweep with ancestor sampling per series, the new state path [N][T+1][d] given the path
 // `ref` (path may be ref), with the statistics [N][d+3] dinvgammaStep takes.  dlm_pg_desc crosses as scalars in its field order (workspaceCap = 0: the default cap); obsParam = 0: none; pathIndex
 // [N][T+1] int32, clouds [N][T+1][d][nParticles] with ancestors [N][T][nParticles] int32, stepWeights [N][T][nParticles] and status are optional (0).

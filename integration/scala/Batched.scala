@@ -102,6 +102,10 @@ final class Native private[gpu] () {
   @native def particleForecastLearned(h: Long, model: Array[Long], params: Array[Long], opts: Array[Long], family: Int, nParticles: Int, varKind: Int, slotOffset: Long, ranks: Array[Long], obsParam: Long, cloud0: Long, weights0: Long, pw: Long, pv: Long, shapes: Long, shapesStride: Long, iteration: Long, fmean: Long, fquant: Long, draws: Long, mean: Long, cloud: Long, varW: Long, varV: Long, status: Long): Unit
   /** A state per particle from the Kalman moments rbFilter leaves: cloud [N][d][nParticles], x_i = m_i + chol(C_i) z_i, the normals from the Philox slot `slot` of the filter's stream (the number of steps filtered). */
   @native def rbStateDraw(h: Long, d: Int, n: Int, nParticles: Int, means: Long, covs: Long, slot: Long, iteration: Long, opts: Array[Long], cloud: Long, status: Long): Unit
+  /** Future log-volatility paths of the factor stochastic-volatility models: alpha [N][nPaths][k][H+1] from sv [N][k][3] = (phi, mu, sigma_eta) and the starts alpha0 [N][k] (0: the stationary law); path r of row n is a pure function of (seed, seriesOffset + n, iteration, r).  status is optional (0). */
+  @native def svPaths(h: Long, n: Int, k: Int, horizon: Int, nPaths: Int, sv: Long, alpha0: Long, iteration: Long, opts: Array[Long], alpha: Long, status: Long): Unit
+  /** Mean [N][H][p], total covariance [N][H][p p] and exact marginal quantiles [N][H][p][nProbs] of the equal-weight mixture of c Gaussians per row and time, read in place through the (row, component, time) strides in doubles (the fq records of filterBatch or a variance stream; f = 0: zero means); probs is the HOST address of nProbs <= 8 doubles, whatever mem says.  What DlmFsv.forecast / DlmFsvSystem.forecast summarise, over every kept draw and path. */
+  @native def gaussianMixtureSummary(h: Long, n: Int, c: Int, horizon: Int, p: Int, fStrides: Array[Long], qStrides: Array[Long], f: Long, q: Long, probs: Long, nProbs: Int, opts: Array[Long], mean: Long, cov: Long, quant: Long, status: Long): Unit
   /** Particle Gibbs for a DGLM (what ParticleGibbs aims at; its own step is not a valid kernel): one conditional-SMC sweep with ancestor sampling per series -- the new state path [N][T+1][d] given the path `ref` (path may be ref) and the statistics [N][d+3] dinvgammaStep takes; workspaceCap = 0: the default cap on the engine workspace of a launch; obsParam = 0: none; pathIndex, clouds with ancestors, stepWeights and status are optional (0). */
   @native def pgSweep(h: Long, model: Array[Long], params: Array[Long], opts: Array[Long], family: Int, nParticles: Int, ancestorSampling: Int, workspaceCap: Long, obsParam: Long, y: Long, ref: Long, iteration: Long, ll: Long, path: Long, stats: Long, pathIndex: Long, clouds: Long, ancestors: Long, stepWeights: Long, status: Long): Unit
   @native def statsPool(h: Long, stats: Long, n: Int, l: Int, pooled: Long, opts: Array[Long]): Unit
